@@ -5,7 +5,7 @@
     python bench.py --gpus N --steps K --warmup W
 
 N > 1: either launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` (the driver's way: the
-ranks find RANK / LOCAL_RANK / WORLD_SIZE in the environment), or started plainly -- bench.py then re-executes ITSELF under
+ranks find RANK / LOCAL_RANK / WORLD_SIZE in the environment), or started plainly -- bench.py then runs ITSELF in a child process under
 torch.distributed.run (127.0.0.1, a free port), one process per GPU, backend "nccl" (= RCCL over xGMI).
 
 A "step" = one forward of B samples per GPU (B x NV views -> B skeletons) on synthetic inputs already resident in HBM,
@@ -27,6 +27,9 @@ Besides the driver contract the line carries
   batch_sweep   samples/s at the reference's own batch sizes (5 = train, 10 = val; human36m_vol_softmax.yaml:17-18) and B = 1;
   cpu_baseline  the CPU oracle (torch-CPU restatement of the reference path, same ATen ops, same weights) timed on this
                 box's host cores on a bounded sample BEFORE the GPU timing (rank 0, N = 1 only).
+
+``--dump-outputs DIR`` also writes the arrays the last timed step returned (rank 0) as DIR/<name>.npy (dump_outputs); inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -44,8 +47,6 @@ PKG = os.path.join(ROOT, "learnable-triangulation-pytorch_amd")
 for p in (ROOT, PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")          # before the first HIP call: see lt_hip.py (streams that share a hardware queue serialise)
 
 import numpy as np
 import torch
@@ -164,14 +165,14 @@ def parity_block(kp_gpu, refs, dtype, cuboid_side=2500.0):
 
 
 def self_launch(args):
-    """--gpus N > 1 without a torchrun environment: re-execute under torch.distributed.run, one process per GPU."""
+    """--gpus N > 1 without a torchrun environment: run under torch.distributed.run, one process per GPU, in a child process; exits with its code."""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["LT_BENCH_SELF_LAUNCHED"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def sub_leg(argv, timeout_s):
@@ -396,6 +397,8 @@ def compact_line(res):
     if cb:
         out["cpu_baseline"] = {"value": _r(cb["value"]), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"], "cpu_model": cb["cpu_model"], "sample": cb["sample"],
                                "kind_note": "oracle/ = the reference's ATen ops, pinned at 0.0 on all 88 stages (tests/golden)"}
+    if res.get("dumped_outputs"):
+        out["dumped_outputs"] = res["dumped_outputs"]["dir"]
     out["full_record"] = "stderr '# leg ...' lines; gpurun_out/bench_full.json"
     return out
 
@@ -467,6 +470,51 @@ class ClockSampler:
             return {"sclk_mhz": round(sum(sclk) / len(sclk)), "power_w": round(sum(power) / len(power)) if power else None, "samples": len(sclk)}
         except Exception:
             return None
+
+
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: all .npy files together
+DUMP_SAMPLE_ELEMS = 2 << 20      # outputs up to this many elements are written whole, larger ones as this many elements at fixed, seeded positions
+
+
+def forward_outputs(out):
+    """The forward's 7-tuple (the reference's return order) as named arrays: what a caller of the timed path receives.  Tensors stay where they are;
+    the cuboids are host objects (one position per sample, the same sides for all)."""
+    kp, feats, probs, conf, cuboids, coords, base_points = out
+    named = {"keypoints_3d": kp, "features": feats, "volumes": probs, "vol_confidences": conf, "coord_volumes": coords, "base_points": base_points,
+             "cuboid_positions": np.stack([np.asarray(c.position, dtype=np.float64) for c in cuboids]),
+             "cuboid_sides": np.stack([np.asarray(c.sides, dtype=np.float64) for c in cuboids])}
+    return {k: v for k, v in named.items() if v is not None}
+
+
+def dump_outputs(named, path):
+    """Write every array as ``path/<name>.npy``: float64 stays float64, everything else becomes float32.  An array of more than DUMP_SAMPLE_ELEMS
+    elements is written as the DUMP_SAMPLE_ELEMS elements of its flattened form at sorted positions drawn without replacement by a generator seeded
+    with the array's name -- the same positions in every run of the same shape.  Returns {name: {"shape", "written", "sampled"}}."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    arrays, info = {}, {}
+    for name, t in named.items():
+        full_shape = tuple(t.shape)
+        n = int(np.prod(full_shape))
+        idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, DUMP_SAMPLE_ELEMS, replace=False)) if n > DUMP_SAMPLE_ELEMS else None
+        if isinstance(t, torch.Tensor):
+            t = t.detach()
+            if idx is not None:
+                t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            a = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        else:
+            a = np.asarray(t)
+            if idx is not None:
+                a = a.reshape(-1)[idx]
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        arrays[name] = a
+        info[name] = {"shape": list(full_shape), "written": list(a.shape), "sampled": n > DUMP_SAMPLE_ELEMS}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BUDGET_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return info
 
 
 def time_steps(step, n, barrier):
@@ -822,17 +870,22 @@ def main():
     ap.add_argument("--cpu-parity-samples", type=int, default=2, help="samples of the timed batch the CPU oracle evaluates as parity references")
     ap.add_argument("--fp32-parity-batch", type=int, default=0, help="with --no-extras: also run this many samples through the exact-fp32 kernel set and report their "
                     "parity (the config-4 child leg of the default run: the driver line then shows config 4 inside the tolerance)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the arrays the last timed step returned (rank 0's "
+                    "shard) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: small outputs whole, large ones as a fixed seeded sample of "
+                    "their elements (see dump_outputs).  Forward runs only")
     ap.add_argument("--stub-cpu", action="store_true", help="TEST ONLY: gloo backend, no GPU, step() is a sleep (exercises launcher + timing plumbing)")
     ap.add_argument("--preflight", action="store_true", help="N-GPU sanity run before a scaling session (VERDICT r5 'next' 7): communicator census (ranks, distinct "
                     "devices, RCCL version), ONE timed 64 MB all-reduce, ONE data-parallel training step with the replicas checked identical, then exit with its own JSON line")
     args = ap.parse_args()
+    if args.dump_outputs and (args.train or args.train_trajectory or args.preflight or args.stub_cpu):
+        ap.error("--dump-outputs writes what the timed forward returns: not with --train, --train-trajectory, --preflight or --stub-cpu")
     if not args.batch:
         # 64 samples (256 images) per GPU per step from round 4 on: two full rounds of 288-row tiles on the 256 CUs and half the per-sample share of the
         # ~220 launches' fixed cost (+3 % over 32 samples; 48 samples = 1.5 rounds is slower than either); rounds 1-3 timed 32, which stays in batch_sweep
         args.batch = 4 if args.train_trajectory else 8 if args.train else 16 if args.volume >= 128 else 64
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args)       # does not return
+        self_launch(args)       # does not return (exits with the launcher's code)
 
     import lt_dist
     world, rank, local = lt_dist.init("gloo" if args.stub_cpu else "nccl")   # "nccl" on PyTorch-ROCm is RCCL (xGMI inside the node)
@@ -933,6 +986,7 @@ def main():
     value, total_samples, dt = lt_dist.job_throughput(B * args.steps, dt_local, dev)   # all ranks' samples / slowest rank
     per_rank = lt_dist.gather_floats(B * args.steps / dt_local, dev)
     assert torch.isfinite(out[0]).all()
+    dumped = dump_outputs(forward_outputs(out), args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     comm = lt_dist.comm_info(dev)          # all ranks: an all-reduce of ones through the communicator (nranks), backend, RCCL version, devices
 
     result = None
@@ -946,6 +1000,8 @@ def main():
                        "hip_graph": not args.no_graph, "self_launched": os.environ.get("LT_BENCH_SELF_LAUNCHED") == "1"},
             "per_rank_samples_per_s": per_rank, "rccl": comm,
         }
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         if refs is not None:
             result["parity"] = parity_block(out[0], refs, args.dtype, model.cuboid_side)
         if not args.no_profile:

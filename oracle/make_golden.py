@@ -676,11 +676,50 @@ def gen_alg2(mvn):
                         hm_sub=sub(hm.reshape(6, 17, 32, 32), 2), sd_digest=np.array(synth.state_dict_checksum(sd)))
 
 
+def gen_experiments():
+    """The reference's human36m experiment files (train and eval), each as its parsed YAML mapping, keyed by '<train|eval>/<file name>': the
+    config surface tests/test_host_logic.py builds the models from (it writes them back out as YAML and reads them with mvn.utils.cfg)."""
+    import glob
+    import yaml
+    root = os.path.join(ref_loader.REFERENCE_ROOT, "experiments", "human36m")
+    out = {}
+    for f in sorted(glob.glob(os.path.join(root, "*", "*.yaml"))):
+        with open(f) as fin:
+            out[os.path.relpath(f, root)] = yaml.safe_load(fin)
+    with open(os.path.join(GOLD, "experiments_human36m.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def gen_pose_net_loading(mvn):
+    """The REFERENCE's get_pose_net (pose_resnet.py:321-377) on the fake checkpoints of tests/test_pose_net_loading.py (the same helper builds them)
+    under the same RNG state: per case, the digest of every tensor of the state dict it returns."""
+    import tempfile
+    sys.path.insert(0, os.path.dirname(GOLD))
+    from test_pose_net_loading import CASES, _cfg, _fake_checkpoint, case_id
+    nl, J = 18, 17
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        for wrap, prefix, joints_ckpt in CASES:
+            path = os.path.join(d, "ckpt.pth")
+            _fake_checkpoint(path, nl, joints_ckpt, wrap, prefix)
+            torch.manual_seed(1234)
+            sd = mvn.models.pose_resnet.get_pose_net(_cfg(nl, ckpt=path, init=True, joints=J), device="cpu").state_dict()
+            out[case_id(wrap, prefix, joints_ckpt)] = {k: synth.tensor_digest(v) for k, v in sd.items()}
+    with open(os.path.join(GOLD, "pose_net_loading.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
     torch.manual_seed(0)
     os.makedirs(GOLD, exist_ok=True)
     mvn = ref_loader.load()
-    which = sys.argv[1:] or ["ops", "nets", "vol", "vol2", "vol3", "vol4", "alg", "alg2", "caffe", "pipe2d", "data", "grad", "train", "train_conf", "train_alg", "train_frozen", "train_sum", "train_max", "train_r50", "train_alg_noconf", "train_cmu"]
+    which = sys.argv[1:] or ["ops", "nets", "vol", "vol2", "vol3", "vol4", "alg", "alg2", "caffe", "pipe2d", "data", "grad", "train", "train_conf", "train_alg", "train_frozen", "train_sum", "train_max", "train_r50", "train_alg_noconf", "train_cmu", "experiments", "pose_net_loading"]
+    if "experiments" in which:
+        print("[experiments]"); gen_experiments()
+    if "pose_net_loading" in which:
+        print("[pose_net_loading]"); gen_pose_net_loading(mvn)
     if "ops" in which:
         print("[ops]"); gen_ops(mvn)
     if "nets" in which:

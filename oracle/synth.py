@@ -74,6 +74,13 @@ def state_dict_checksum(sd):
     return [s, q]
 
 
+def tensor_digest(t):
+    """sha256 of a tensor's dtype, shape and bytes: equal digests <=> torch.equal with the same dtype."""
+    import hashlib
+    t = t.detach().cpu().contiguous()
+    return hashlib.sha256(("%s %s " % (t.dtype, tuple(t.shape))).encode() + t.numpy().tobytes()).hexdigest()
+
+
 def ring_cameras(n_views, image_size, radius=4000.0, height=1000.0, inside=False):
     """NV pinhole cameras on a ring looking at the origin, z up.
 

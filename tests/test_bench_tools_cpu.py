@@ -117,3 +117,43 @@ def test_clock_sampler_counts_only_reads_inside_the_timed_window(tmp_path):
     full["roofline"].update(sclk_mhz=2090, power_w=1368)
     c = bench.compact_line(full)
     assert c["roofline"]["sclk_mhz"] == 2090 and c["roofline"]["power_w"] == 1368 and len(json.dumps(c)) <= 4096
+
+
+def test_dump_outputs_writes_the_forward_tuple_within_budget(tmp_path):
+    """--dump-outputs: every array of the forward's 7-tuple as <name>.npy (float32 / float64), the large ones as a fixed seeded sample of their
+    elements -- the same positions in every run -- and all of it within the 64 MB budget."""
+    import numpy as np
+    import torch
+    import bench
+    from mvn.utils.volumetric import Cuboid3D
+    g = torch.Generator().manual_seed(5)
+    B, NV = 2, 4
+    kp = torch.randn(B, 17, 3, generator=g)
+    feats = torch.randn(B, NV, 32, 96, 96, generator=g).to(torch.bfloat16)       # 2.4 M elements > DUMP_SAMPLE_ELEMS: sampled
+    probs = torch.rand(B, 17, 48, 48, 48, generator=g)                              # 3.8 M elements: sampled
+    coords = torch.randn(B, 32, 32, 32, 3, generator=g)                             # 196 K elements: whole
+    base = torch.randn(B, 3, generator=g, dtype=torch.float64)
+    cub = [Cuboid3D(np.array([1.0, 2.0, 3.0]) * i, np.array([2500.0] * 3)) for i in range(B)]
+    out = (kp, feats, probs, None, cub, coords, base)
+    info = bench.dump_outputs(bench.forward_outputs(out), str(tmp_path / "a"))
+    names = {"keypoints_3d", "features", "volumes", "coord_volumes", "base_points", "cuboid_positions", "cuboid_sides"}
+    assert set(info) == names and sorted(os.listdir(str(tmp_path / "a"))) == sorted(n + ".npy" for n in names)
+    total = 0
+    for n in names:
+        a = np.load(str(tmp_path / "a" / (n + ".npy")))
+        total += a.nbytes
+        assert a.dtype == (np.float64 if n in ("base_points", "cuboid_positions", "cuboid_sides") else np.float32), n
+        assert list(a.shape) == info[n]["written"]
+    assert total <= bench.DUMP_BUDGET_BYTES
+    assert info["features"]["sampled"] and info["volumes"]["sampled"] and not info["coord_volumes"]["sampled"]
+    assert np.array_equal(np.load(str(tmp_path / "a" / "keypoints_3d.npy")), kp.numpy())
+    assert np.array_equal(np.load(str(tmp_path / "a" / "coord_volumes.npy")), coords.numpy())
+    assert np.array_equal(np.load(str(tmp_path / "a" / "cuboid_positions.npy")), np.stack([c.position for c in cub]))
+    # the sample is a subset of the array's elements at the same positions in a second run
+    vs = np.load(str(tmp_path / "a" / "volumes.npy"))
+    assert vs.shape == (bench.DUMP_SAMPLE_ELEMS,) and np.isin(vs, probs.numpy().ravel()).all()
+    bench.dump_outputs(bench.forward_outputs(out), str(tmp_path / "b"))
+    for n in names:
+        assert np.array_equal(np.load(str(tmp_path / "a" / (n + ".npy"))), np.load(str(tmp_path / "b" / (n + ".npy")))), n
+    fs = np.load(str(tmp_path / "a" / "features.npy"))
+    assert np.isin(fs, feats.float().numpy().ravel()).all()

@@ -236,21 +236,26 @@ def test_c_abi_exports_every_declared_symbol():
     assert l.lt_pwchain_fwd(ctypes.byref(pd), 1, 1, None) == -1 and b"plane" in l.lt_last_error()
 
 
-REF_EXPERIMENTS = "/root/reference/experiments/human36m"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_EXPERIMENTS), reason="the reference checkout is only present in the build container")
-def test_reference_experiment_yamls_build_the_models():
+def test_reference_experiment_yamls_build_the_models(golden_dir, tmp_path):
     """north_star: "keeps ... the experiments/*.yaml config surface".  Every vol / alg experiment file of the reference (train and eval), read with
     mvn.utils.cfg.load_config exactly as train.py:397 does, constructs the model class train.py:400-404 picks -- with the keys the constructors read
     (volume_aggregation_method, volume_softmax, volume_multiplier, volume_size, cuboid_side, kind, use_gt_pelvis, use_confidences, heatmap_*,
     backbone.*) -- and the state dict has the reference layout (oracle/spec.py, pinned against the reference's own modules by make_golden).  Only
-    ``init_weights`` is switched off (the checkpoints are not part of the repository); the ransac file is SURVEY's out-of-scope CPU baseline."""
+    ``init_weights`` is switched off (the checkpoints are not part of the repository); the ransac file is SURVEY's out-of-scope CPU baseline.
+    The files' contents are the fixture tests/golden/experiments_human36m.json (oracle/make_golden.py "experiments"), written back out as YAML here."""
     import glob
+    import json
+    import yaml
     from mvn.utils import cfg
     from mvn.models.triangulation import AlgebraicTriangulationNet, VolumetricTriangulationNet
     from oracle import spec
-    files = sorted(glob.glob(os.path.join(REF_EXPERIMENTS, "*", "*.yaml")))
+    with open(os.path.join(golden_dir, "experiments_human36m.json")) as fin:
+        experiments = json.load(fin)
+    for rel, content in experiments.items():
+        os.makedirs(os.path.dirname(str(tmp_path / rel)), exist_ok=True)
+        with open(str(tmp_path / rel), "w") as fout:
+            yaml.safe_dump(content, fout)
+    files = sorted(glob.glob(os.path.join(str(tmp_path), "*", "*.yaml")))
     assert len(files) >= 5
     seen = set()
     for f in files:

@@ -1,5 +1,5 @@
 import os, sys, time, json
-ROOT="/root/repo"
+ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0]=[ROOT, ROOT+"/learnable-triangulation-pytorch_amd"]
 import torch, bench
 from mvn.models.triangulation import VolumetricTriangulationNet
