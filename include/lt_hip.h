@@ -437,6 +437,22 @@ int lt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
 int lt_triangulate_dlt(const float* proj, const float* points, const float* conf, float* out, int32_t B, int32_t NV,
                        int32_t J, void* stream);
 
+/* RANSACTriangulationNet (reference mvn/models/triangulation.py:17-128), 2D part: the backbone's N,h,w,(ld) fp32 heatmaps ->
+ * heatmaps_nchw N,J,h,w (the raw heatmaps the model returns, bit-identical to lt_nhwc_to_nchw_f32) and, in the same pass, the argmax
+ * of torch.max(hm.view(N, J, -1), -1): indices N,J int64 (or NULL; a NaN wins with the first NaN's index, a tie goes to the smallest
+ * index) and keypoints N,J,2 int64 (or NULL) = (trunc(idx % w * f32(image_w / w)), trunc(idx / w * f32(image_h / h))), the
+ * reference's float products stored into an int64 tensor (:45-52).  J <= 32. */
+int lt_heatmap_argmax_nchw_f32(const float* heatmaps, int32_t ld, float* heatmaps_nchw, int64_t* indices, int64_t* keypoints,
+                               int32_t N, int32_t J, int32_t h, int32_t w, int32_t image_h, int32_t image_w, void* stream);
+/* RANSACTriangulationNet.triangulate_ransac (reference :75-128) for every (sample, joint), fp64 inside.  proj B,NV,3,4 fp32;
+ * points B,NV,J,2 int64; pairs B,J,n_iters,2 int32 = the 2-view hypotheses to try, in order (the reference's random draws), or
+ * NULL = every pair (a, b), a < b, in lexicographic order (exhaustive: always at least as large an inlier set as any draw; n_iters
+ * is then ignored).  A hypothesis' inlier set = the pair + every view with reprojection error 1/2 |p - pi(X)| < eps, kept when
+ * strictly larger than the best so far; the final DLT on the inliers is refined with direct_opt by minimising scipy's
+ * least_squares(loss='huber') objective.  out_kp3d B,J,3 fp32; out_inliers B,J,NV uint8 (1 = inlier) or NULL.  2 <= NV <= 32. */
+int lt_triangulate_ransac(const float* proj, const int64_t* points, const int32_t* pairs, int32_t n_iters, double eps, int32_t direct_opt,
+                          float* out_kp3d, uint8_t* out_inliers, int32_t B, int32_t NV, int32_t J, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Chain of up to LT_PWCHAIN_MAX pointwise (1x1x1) convolutions evaluated per voxel without the
  * intermediate activations leaving the registers:  y = L_n(...L_1(x)),

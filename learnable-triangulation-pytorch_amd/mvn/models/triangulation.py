@@ -2,12 +2,15 @@
 
     VolumetricTriangulationNet(config, device).forward(images, proj_matricies, batch)
     AlgebraicTriangulationNet(config, device).forward(images, proj_matricies, batch)
+    RANSACTriangulationNet(config, device).forward(images, proj_matricies, batch)
 
 Same constructor side effects on ``config``, same ``state_dict()`` keys, same return tuples.  The whole
 forward is ONE recorded plan of liblt_hip launches per input shape, captured into a hipGraph:
 
     images --lt_nchw_to_nhwc--> [graph: PoseResNet convs -> process_features 1x1 -> lt_coord_volumes ->
     lt_unproject_fwd -> V2V convs -> lt_softargmax3d_fwd] --> outputs
+
+The RANSAC net's plan ends in lt_heatmap_argmax_nchw_f32; lt_triangulate_ransac follows it on the same stream (inference only).
 
 Host work per call is numpy fp64 camera algebra for B*NV 3x4 matrices (vectorised; the reference
 deep-copies B*NV Camera objects) and one small H2D copy of the geometry block.
@@ -766,3 +769,81 @@ class AlgebraicTriangulationNet(_PlannedNet):
         kp2d = kp2d * scale
         kp3d = multiview.triangulate_batch_of_points(proj_matricies.to(device), kp2d, confidences_batch=conf)
         return kp3d, kp2d, heatmaps, conf
+
+
+class RANSACTriangulationNet(_PlannedNet):
+    """Reference :17-128.  The backbone and lt_heatmap_argmax_nchw_f32 (raw NCHW heatmaps + argmax keypoints in one pass) are one
+    recorded plan; lt_triangulate_ransac then triangulates every (sample, joint) on the same stream (the reference loops over them in
+    Python with numpy SVDs and a scipy Huber fit each).  The 2-view hypotheses are every pair in lexicographic order instead of
+    n_iters random draws: deterministic, and the inlier set found is at least as large as any the draws can find.  Inference only:
+    the reference's RANSAC output carries no gradient."""
+
+    def __init__(self, config, device="cuda:0"):
+        super().__init__()
+        m = config.model
+        m.backbone.alg_confidences = False        # reference :21-22
+        m.backbone.vol_confidences = False
+        self.backbone = pose_resnet.get_pose_net(m.backbone, device=device)
+        self.direct_optimization = m.direct_optimization
+        self.reprojection_error_epsilon = 15
+
+    def _build_plan(self, B, NV, Hh, W, device):
+        b = E.PlanBuilder(device, self.compute_dtype, self.tile_override)
+        lib = H.lib()
+        x_in = b.alloc((B * NV, 1, Hh, W, E.min_cin_of(self.compute_dtype)))
+        x_in.pooled = False
+        hm, feats, _, _ = self.backbone.record(b, x_in, want_heatmaps=True)
+        b.release(feats)
+        N = B * NV
+        J, h, w = hm.shape[4], hm.shape[2], hm.shape[3]
+        assert hm.t.dtype == torch.float32, hm.t.dtype     # the heatmap head stores fp32 in every compute dtype
+        ld = hm.t.shape[-1]
+        hm_nchw = torch.empty(N, J, h, w, dtype=torch.float32, device=device)
+        kp2d = torch.empty(N, J, 2, dtype=torch.int64, device=device)
+        b.custom(lambda st: H.check(lib.lt_heatmap_argmax_nchw_f32(hm.t.data_ptr(), ld, hm_nchw.data_ptr(), None, kp2d.data_ptr(), N, J, h, w,
+                                                                   Hh, W, st), "lt_heatmap_argmax_nchw_f32"),
+                 "heatmap_argmax", nbytes=2 * N * J * h * w * 4)
+        plan = b.finish()
+        plan.keep += [hm_nchw, kp2d]
+        return {"plan": plan, "x_in": x_in, "hm": hm_nchw, "kp2d": kp2d, "hw": (h, w), "J": J}
+
+    def forward(self, images, proj_matricies, batch):
+        """Returns (keypoints_3d (B,J,3) fp32, keypoints_2d (B,NV,J,2) int64 image pixels, raw heatmaps (B,NV,J,h,w), confidences
+        (B,NV,J) zeros) -- reference :27-73."""
+        H.require_gpu(images, "images")
+        if _bn_in_train_mode(self):
+            raise NotImplementedError("RANSACTriangulationNet runs in eval() only: its triangulation carries no gradient (the reference "
+                                      "ships only an evaluation config for it)")
+        _sync_buffers_before_eval(self)
+        device = images.device
+        B, NV = images.shape[:2]
+        Hh, W = images.shape[3:]
+        key = (B, NV, Hh, W, self.compute_dtype, device, self.tile_override)
+        with torch.cuda.device(device):
+            P = self._plan_for(key, lambda: self._build_plan(B, NV, Hh, W, device))
+            h, w = P["hw"]; J = P["J"]
+            st = torch.cuda.current_stream(device).cuda_stream
+            x = images.reshape(B * NV, 3, Hh, W).float().contiguous()
+            H.check(H.lib().lt_nchw_to_nhwc(H.dtype_code(self.compute_dtype), x.data_ptr(), P["x_in"].t.data_ptr(), B * NV, 3, Hh * W,
+                                            P["x_in"].t.shape[-1], st), "lt_nchw_to_nhwc")
+            P["plan"].run_eager(st)
+            heatmaps = P["hm"].reshape(B, NV, J, h, w).clone()
+            kp2d = P["kp2d"].reshape(B, NV, J, 2).clone()
+            kp3d = multiview.triangulate_ransac_batch(proj_matricies.to(device), kp2d, None, self.reprojection_error_epsilon,
+                                                      self.direct_optimization)
+            conf = torch.zeros(B, NV, J, dtype=torch.float32, device=device)
+        return kp3d, kp2d, heatmaps, conf
+
+    def triangulate_ransac(self, proj_matricies, points, n_iters=10, reprojection_error_epsilon=15, direct_optimization=True, device=None):
+        """Reference :75-128 for one point: numpy proj_matricies (NV, 3, 4) and points (NV, 2) -> (point (3,) fp64 of the fp32 result,
+        sorted inlier view indices).  Runs lt_triangulate_ransac on a 1 x 1 batch; ``n_iters`` is accepted for compatibility -- every
+        pair is tried."""
+        assert len(proj_matricies) == len(points)
+        assert len(points) >= 2
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        if dev.type != "cuda":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        P = torch.as_tensor(np.asarray(proj_matricies, dtype=np.float32)).to(dev)[None]
+        pts = torch.as_tensor(np.asarray(points).astype(np.int64)).to(dev)[None, :, None, :]
+        kp, inl = multiview.triangulate_ransac_batch(P, pts, None, reprojection_error_epsilon, direct_optimization, return_inliers=True)
+        return kp[0, 0].double().cpu().numpy(), np.nonzero(inl[0, 0].cpu().numpy())[0]

@@ -1,7 +1,7 @@
 """Camera model and multi-view helpers with the reference's names (mvn/utils/multiview.py).
 
 Host geometry stays numpy fp64 exactly like the reference; the batched DLT runs in liblt_hip
-(lt_triangulate_dlt)."""
+(lt_triangulate_dlt), the batched RANSAC triangulation too (lt_triangulate_ransac)."""
 import numpy as np
 import torch
 
@@ -140,3 +140,53 @@ def triangulate_point_from_multiple_views_linear_torch(proj_matricies, points, c
     """Single-point form of the above (reference :141-168)."""
     conf = None if confidences is None else confidences[None, :, None]
     return triangulate_batch_of_points(proj_matricies[None], points[None, :, None, :], conf)[0, 0]
+
+
+def triangulate_point_from_multiple_views_linear(proj_matricies, points):
+    """Host DLT of one point (reference :113-138), numpy fp64: rows x P[2] - P[0] and y P[2] - P[1] per view, the right singular
+    vector of the smallest singular value, dehomogenised.  proj_matricies (N, 3, 4), points (N, 2) -> (3,)."""
+    assert len(proj_matricies) == len(points)
+    P = np.asarray(proj_matricies)
+    p = np.asarray(points)
+    A = np.zeros((2 * len(P), 4))
+    for v in range(len(P)):
+        A[2 * v] = p[v][0] * P[v][2, :] - P[v][0, :]
+        A[2 * v + 1] = p[v][1] * P[v][2, :] - P[v][1, :]
+    vh = np.linalg.svd(A, full_matrices=False)[2]
+    return homogeneous_to_euclidean(vh[3, :])
+
+
+def calc_reprojection_error_matrix(keypoints_3d, keypoints_2d_list, proj_matricies):
+    """Half the pixel distance between each view's 2D point and the projection of each 3D point (reference :186-193): keypoints_3d
+    (M, 3), keypoints_2d_list (N, 2) (one point per view, compared with every 3D point), proj_matricies (N, 3, 4) -> (M, N)."""
+    cols = [0.5 * np.sqrt(np.sum((p2 - project_3d_points_to_image_plane_without_distortion(P, keypoints_3d)) ** 2, axis=1))
+            for p2, P in zip(keypoints_2d_list, proj_matricies)]
+    return np.vstack(cols).T
+
+
+def triangulate_ransac_batch(proj_matricies_batch, points_batch, pairs=None, reprojection_error_epsilon=15.0, direct_optimization=True,
+                             return_inliers=False):
+    """RANSAC triangulation of every (sample, joint) in one lt_triangulate_ransac launch (reference triangulation.py:75-128 per point).
+    proj (B, NV, 3, 4), points (B, NV, J, 2) integer pixel coordinates -> keypoints_3d (B, J, 3) fp32 [, inliers (B, J, NV) bool].
+    ``pairs`` (B, J, n_iters, 2): the 2-view hypotheses to try in order (e.g. the reference's random draws); None = every pair in
+    lexicographic order, which finds at least as large an inlier set as any n_iters draws (the one deliberate deviation from the
+    reference: deterministic, no random numbers on the device)."""
+    H.require_gpu(points_batch, "points_batch")
+    dev = points_batch.device
+    P = proj_matricies_batch.to(dev, torch.float32).contiguous()
+    pts = points_batch.to(torch.int64).contiguous()
+    B, NV, J = pts.shape[:3]
+    if tuple(P.shape) != (B, NV, 3, 4) or tuple(pts.shape) != (B, NV, J, 2):
+        raise ValueError("proj_matricies_batch (B, NV, 3, 4) and points_batch (B, NV, J, 2) expected, got %s and %s" % (tuple(P.shape), tuple(pts.shape)))
+    n_iters = 0
+    if pairs is not None:
+        pairs = torch.as_tensor(pairs).to(dev, torch.int32).contiguous()
+        n_iters = pairs.shape[2]
+        if tuple(pairs.shape) != (B, J, n_iters, 2):
+            raise ValueError("pairs must be (B, J, n_iters, 2), got %s" % (tuple(pairs.shape),))
+    out = torch.empty(B, J, 3, dtype=torch.float32, device=dev)
+    inl = torch.empty(B, J, NV, dtype=torch.uint8, device=dev) if return_inliers else None
+    H.check(H.lib().lt_triangulate_ransac(P.data_ptr(), pts.data_ptr(), H.ptr(pairs), n_iters, float(reprojection_error_epsilon),
+                                          int(bool(direct_optimization)), out.data_ptr(), H.ptr(inl), B, NV, J,
+                                          torch.cuda.current_stream(dev).cuda_stream), "lt_triangulate_ransac")
+    return (out, inl.bool()) if return_inliers else out
