@@ -188,6 +188,42 @@ int lt_conv_cout_pad(int32_t cout);
  * when the whole batch fits, a multiple of 8 where possible otherwise, 0 when a single sample is too large. */
 int32_t lt_conv_chunk_samples(int32_t N, int64_t per_sample);
 
+/* ---- kernel selection (host only: no GPU needed) ----------------------------------------------------------------------------------------------------
+ * The rules by which a plan host (lt_engine.PlanBuilder, lt_plan_create_vol) picks a fused launch, a split-K tap-group count or the fragment layout of a
+ * convolution's weights.  Activations are given as their channels-last shape (N, D, H, W, C) (D = 1 for 2D maps), weights as their state-dict shape
+ * (lt_wshape).  The rules hold for weights fixed when the plan is built.  Each reads its A/B switches at every call; a switch is on when it is set to
+ * anything but "" or "0".  Boolean rules return 1 / 0. */
+typedef struct lt_wshape {
+    int32_t nd;                /* 4 (Conv2d / ConvTranspose2d) or 5 (3D) */
+    int64_t s[5];
+} lt_wshape;
+/* lt_conv_skip_fwd: the second 3x3x3 32 -> 32 convolution of a Res3DBlock with its 1x1x1 16 -> 32 skip convolution computed in the launch, on shapes
+ * the column-walk halo kernel takes in every sample chunk (LT_NO_CONV_SKIP, LT_HALO_NO_COL, LT_HALO_NO_PERSIST, LT_CONV_NO_HALO: off) */
+int lt_sel_conv_skip(int32_t dtype, const int32_t x[5], const lt_wshape* w, const int32_t skip_x[5], const lt_wshape* skip_w);
+/* lt_conv_cat2_fwd: a Bottleneck's 1x1 expand of t2 and its 1x1 stride-s downsample of x as one launch, from 200 tiles of 288 x 256 on
+ * (LT_NO_CONV_CAT2, LT_CONV_NO_V7, LT_CONV_NO_V3: off; LT_CAT2_ANY_SIZE: any size) */
+int lt_sel_conv_cat2(int32_t dtype, const int32_t t2[5], const lt_wshape* w_expand, const int32_t x[5], const lt_wshape* w_down, int32_t stride_down);
+/* split-K tap groups S (1 = not split) of a 3x3x3 / stride 1 / pad 1 convolution with >= 128 input channels on at most 8^3 voxels; d: its descriptor
+ * (the flags carry LT_EPI_STORE_F32 / LT_EPI_SIGMOID, which rule it out, as does transposed) (LT_CONV_NO_SPLITK: off) */
+int lt_sel_splitk_slices(const lt_conv_desc* d, const lt_wshape* w, int32_t transposed);
+/* lt_bottleneck_fwd: an identity Bottleneck (C, P) = (256, 64) or (512, 128), stride 1, H % 8 == 0, W % 16 == 0 (LT_NO_BNECK: off) */
+int lt_sel_bottleneck(int32_t dtype, const int32_t x[5], const lt_wshape w[3], const int32_t strides[3]);
+/* lt_bottleneck_ds_fwd: ResNet layer1's first Bottleneck 64 -> 64 -> 256 with its stride-1 downsample (LT_NO_BNECK, LT_NO_BNECK_DS: off) */
+int lt_sel_bottleneck_ds(int32_t dtype, const int32_t x[5], const lt_wshape w[3], const int32_t strides[3], const lt_wshape* w_down, int32_t stride_down);
+/* lt_expand_reduce_fwd: the 1x1 256 -> 1024 expand of a Bottleneck and the 1x1 1024 -> 256 reduce of the next one, from 36 x 96 pixels on
+ * (LT_NO_XR: off; LT_XR_ANY_SIZE: any size) */
+int lt_sel_expand_reduce(int32_t dtype, const int32_t t2[5], const int32_t res[5], const lt_wshape* w_expand, const lt_wshape* w_reduce);
+/* lt_stem_pool_fwd: the 7x7 / stride 2 / pad 3 stem convolution to 64 channels of an 8-channel (padded) map with a 3x3 / stride 2 / pad 1 max pool
+ * (pool = kernel, stride, pad) */
+int lt_sel_stem_pool(int32_t dtype, const int32_t x[5], const lt_wshape* w, int32_t stride, int32_t pad, const int32_t pool[3]);
+/* lt_pwchain_fwd: a chain of nlayers pointwise convolutions from 32 channels, inner widths 32, the last <= 32, over a multiple of 64 voxels */
+int lt_sel_pwchain(int32_t dtype, const int32_t x[5], int32_t nlayers, const lt_wshape* w);
+/* weight_frag_layout for every phase of the convolution d (0 = none): 2 for conv2d_halo_kernel (a 3x3 256 -> 256 on 24-wide maps or a 4x4 / stride-2
+ * transposed 256 -> 256, from 60 tiles of 8 x 24 pixels on, d->tile == LT_TILE_AUTO, no residual; LT_CONV_NO_H2D, LT_CONV_V1, LT_DECONV_NO_H2D (the
+ * transposed ones): off; LT_H2D_ANY_SIZE: any size) and for conv3d_halo_wreg_kernel (3x3x3 64 -> 64, 32 -> 64, 128 -> 128, 16 -> 32), 3 for conv_igemm7
+ * and 1 for conv_igemm6 (cout_pad % 256 == 0, k_pad % 64 == 0: 1 for pointwise layers with k_pad <= 256 and under LT_CONV_NO_V7).  bf16 only. */
+int lt_sel_frag_layout(const lt_conv_desc* d, const lt_wshape* w, int32_t transposed, int32_t has_residual);
+
 /* max pooling, channels-last, window k / stride s / zero-size padding p per dim (padding never wins):
  * F.max_pool2d(x,3,2,1) (pose_resnet.py:297) and F.max_pool3d(x,2,2) (v2v.py:51) */
 int lt_maxpool_fwd(int32_t dtype, const void* x, void* y, int32_t N, int32_t D, int32_t H, int32_t W, int32_t C,

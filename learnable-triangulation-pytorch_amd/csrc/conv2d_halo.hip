@@ -248,25 +248,15 @@ int launch_halo2d(const Halo2dArgs& a0, hipStream_t s, long long first = 0, long
 
 namespace lt {
 
-// 1 = launched, 0 = not applicable (fall back), < 0 = error.  Takes: bf16, 256 -> 256 dense channels, maps whose width is a multiple of 24 and whose
-// height is a multiple of 8, iteration space == input grid, every tap within one pixel of the output pixel, no residual, plain bf16 store, weights of every
-// phase in the fragment order of the transposed product (weight_frag_layout 2); one phase of nine taps (3x3 / stride 1 / pad 1) or four phases of four
-// taps with output stride 2 (4x4 / stride 2 / pad 1 transposed).
+// 1 = launched, 0 = not applicable (fall back), < 0 = error.  Takes: bf16, the geometry of halo2d_fits (conv_common.h), no residual or second source,
+// weights of every phase in the fragment order of the transposed product (weight_frag_layout 2).  The taps live in device memory: their range is
+// checked by the kernel (it traps); halo2d_fits checks the geometry that implies it.
 int conv2d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, hipStream_t s) {
-    if (dtype != LT_BF16 || (nphase != 1 && nphase != 4) || c.D != 1 || c.Do != 1 || c.OD != 1) return 0;
-    if (c.sh != 1 || c.sw != 1 || c.H != c.Ho || c.W != c.Wo || c.W % 24 || c.H % 8) return 0;
-    if (c.Cin != 256 || cout_pad != 256 || c.Cout != 256 || c.ldc % 8 || c.res || c.skip_x || c.x2) return 0;
-    if (c.flags & (LT_EPI_STORE_F32 | LT_EPI_SIGMOID)) return 0;
-    const int nt = nphase == 1 ? 9 : 4;
-    // the taps live in device memory: their range is checked by the kernel (it traps); here the geometry that implies it -- a "same" 3x3 (pad 1) or the
-    // 2 x 2-tap parities of a 4x4 / stride-2 / pad-1 transposed convolution (recorded with pad 0 and signed tap offsets)
-    if (c.pd != 0) return 0;
-    if (nphase == 1 && (c.osh != 1 || c.osw != 1 || c.OH != c.Ho || c.OW != c.Wo || c.ph != 1 || c.pw != 1)) return 0;
-    if (nphase == 4 && (c.osh != 2 || c.osw != 2 || c.OH != 2 * c.Ho || c.OW != 2 * c.Wo || c.ph != 0 || c.pw != 0)) return 0;
+    if (dtype != LT_BF16 || c.res || c.skip_x || c.x2 || !halo2d_fits(c, cout_pad, nphase)) return 0;
     Halo2dArgs a;
     for (int p = 0; p < nphase; ++p) {
         const PhaseArg& ph = c.phase[p];
-        if (!ph.wfrag_t || ph.ntaps != nt || ph.ood) return 0;
+        if (!ph.wfrag_t) return 0;
         a.ph[p].wfrag = (const bf16_t*)ph.wfrag_t; a.ph[p].taps = ph.taps; a.ph[p].ooh = ph.ooh; a.ph[p].oow = ph.oow;
     }
     a.x = (const bf16_t*)c.x; a.y = (bf16_t*)c.y;
@@ -288,7 +278,7 @@ int conv2d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, hipS
         // workgroups are half as long, so the tail costs half a round instead of a whole one (128 images = 384 tiles: 256 + 2 x 128)
         const long long rem = tiles8 % n_cu;
         // (the split point must be a whole row of tiles, so that 8-row tile t and the 4-row tiles 2 t, 2 t + 1 cover the same pixels)
-        const bool split = !th && tiles8 > n_cu && rem > 0 && 2 * rem <= n_cu && (tiles8 - rem) % (c.W / 24) == 0 && !getenv("LT_H2D_NO_TAIL4");
+        const bool split = !th && tiles8 > n_cu && rem > 0 && 2 * rem <= n_cu && (tiles8 - rem) % (c.W / 24) == 0 && !env_on("LT_H2D_NO_TAIL4");
         if (split) {
             rc = launch_halo2d<8, 9, 1>(a, s, 0, tiles8 - rem);
             if (rc == LT_OK) rc = launch_halo2d<4, 9, 1>(a, s, 2 * (tiles8 - rem), 2 * rem);

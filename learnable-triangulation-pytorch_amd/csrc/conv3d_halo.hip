@@ -1957,12 +1957,10 @@ int conv3d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, bool
         return rc == LT_OK ? 1 : rc;                                                            \
     }
     // persistent variant: needs a few tiles per workgroup to amortise the weight load, and total % 8 == 0 for the XCD dealing
-    static const bool no_persist = getenv("LT_HALO_NO_PERSIST") != nullptr;   // A/B
+    static const bool no_persist = env_on("LT_HALO_NO_PERSIST");   // A/B
     if (bf && ks == 3 && cout_pad == 32 && c.Cout == 32 && c.ldc % 4 == 0 && c.Cin == 32 && nblk >= 1024 && nblk % 8 == 0 && !no_persist) {
-        // column walk (sliding plane window + overlapped epilogue) when every workgroup gets whole columns of >= 2 tiles
-        const char* nocol = getenv("LT_HALO_NO_COL");    // A/B, read per call
-        const long long cols = (long long)c.N * a.tiles_h * a.tiles_w;
-        if (!nocol && a.tiles_d >= 2 && cols % 8 == 0 && cols >= 256 && c.ldc % 8 == 0) {
+        // column walk (sliding plane window + overlapped epilogue) when every workgroup gets whole columns of >= 2 tiles (LT_HALO_NO_COL: A/B, read per call)
+        if (!env_on("LT_HALO_NO_COL") && halo_col_fits(c.N, c.D, c.H, c.W) && c.ldc % 8 == 0) {
             int rc = launch_halo_col<bf16_t>(a, s);
             return rc == LT_OK ? 1 : rc;
         }
@@ -1974,26 +1972,26 @@ int conv3d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, bool
     if (c.skip_x) return LT_ERR_UNSUPPORTED;             // the computed residual exists in the column-walk kernel only
     if (f32_out) return 0;
     // halo-only LDS, weights as fragments from global memory (lt_conv_pack_weights_t32): 64 -> 64, 32 -> 64, 128 -> 128
-    if (bf && ks == 3 && c.Cout == cout_pad && c.ldc % 8 == 0 && a.wfrag && !getenv("LT_HALO_NO_WREG")) {
+    if (bf && ks == 3 && c.Cout == cout_pad && c.ldc % 8 == 0 && a.wfrag && !env_on("LT_HALO_NO_WREG")) {
         int rc = 1;
         if (c.Cin == 64 && cout_pad == 64) rc = launch_halo_wreg<bf16_t, 64, 64>(a, s);
-        else if (c.Cin == 16 && cout_pad == 32 && !getenv("LT_HALO_NO_WREG16")) rc = launch_halo_wreg<bf16_t, 16, 32>(a, s);
+        else if (c.Cin == 16 && cout_pad == 32 && !env_on("LT_HALO_NO_WREG16")) rc = launch_halo_wreg<bf16_t, 16, 32>(a, s);
         else if (c.Cin == 32 && cout_pad == 64) rc = launch_halo_wreg<bf16_t, 32, 64>(a, s);
         else if (c.Cin == 128 && cout_pad == 128) rc = launch_halo_wreg<bf16_t, 128, 128>(a, s);
         if (rc != 1) return rc == LT_OK ? 1 : rc;
     }
-    static const bool row_chunks = getenv("LT_HALO_ROW") != nullptr;   // A/B: 3-tap weight chunks -> 51 KB of LDS -> 3 workgroups per CU
+    static const bool row_chunks = env_on("LT_HALO_ROW");   // A/B: 3-tap weight chunks -> 51 KB of LDS -> 3 workgroups per CU
     if (f8) {
         // e4m3 operands (train_precision 'fp8v2v'): the one-tile loader-wave kernel at half the bytes per voxel / per weight slab; bf16 stores.  The byte
         // geometries are the bf16 ones of half the channel count: (64, 64) = bf16 (32 -> 64), (32, 32) = bf16 (16 -> 32)
-        if (c.Cout % 8 || c.ldc % 8 || getenv("LT_HALO_NO_FP8")) return 0;
+        if (c.Cout % 8 || c.ldc % 8 || env_on("LT_HALO_NO_FP8")) return 0;
         HALO_CASE_L(fp8_t, 3, 64, 64, 9, 2, 1, true)
         HALO_CASE_L(fp8_t, 3, 32, 32, 9, 2, 1, true)
         HALO_CASE_L(fp8_t, 3, 32, 64, 9, 2, 1, true)
         return 0;
     }
     if (bf) {
-        static const bool no_ldr = getenv("LT_HALO_NO_LDR") != nullptr;   // A/B: no loader waves in the one-tile kernel
+        static const bool no_ldr = env_on("LT_HALO_NO_LDR");   // A/B: no loader waves in the one-tile kernel
         if (!no_ldr) {
             HALO_CASE_L(bf16_t, 3, 64, 64, 3, 3, 1, true)
             HALO_CASE_L(bf16_t, 3, 32, 32, 9, 2, 1, true)
@@ -2005,8 +2003,8 @@ int conv3d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, bool
         HALO_CASE(bf16_t, 3, 16, 32, 9, 2, 1)
         HALO_CASE(bf16_t, 3, 64, 64, 3, 2, 1)
         HALO_CASE(bf16_t, 3, 32, 64, 9, 2, 1)
-        static const bool no_ring = getenv("LT_HALO_NO_RING") != nullptr;   // A/B: 1-tap fragment lookahead for 7^3
-        static const bool no_h7 = getenv("LT_HALO_NO_H7") != nullptr;       // A/B: no loader-wave 7^3 kernel
+        static const bool no_ring = env_on("LT_HALO_NO_RING");   // A/B: 1-tap fragment lookahead for 7^3
+        static const bool no_h7 = env_on("LT_HALO_NO_H7");       // A/B: no loader-wave 7^3 kernel
         if (no_ring) { HALO_CASE(bf16_t, 7, 32, 16, 7, 4, 1) }
         if (ks == 7 && c.Cin == 32 && cout_pad == 16 && !no_h7) {
             int rc = launch_halo7(a, s);
@@ -2015,7 +2013,7 @@ int conv3d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, bool
         HALO_CASE(bf16_t, 7, 32, 16, 7, 4, 2)
         // round 6: 7^3 16 -> 32 = the INPUT GRADIENT of the front layer in the 16-bit training step (the flipped / transposed filter): it ran on the generic
         // 256 x 32 implicit-GEMM tile with four taps per 128-byte K step (1.78 ms at 8 samples, 4.2 % of the step's kernel time); LT_HALO_NO_D7=1: that tile again (A/B)
-        if (!getenv("LT_HALO_NO_D7")) { HALO_CASE(bf16_t, 7, 16, 32, 7, 4, 2) }
+        if (!env_on("LT_HALO_NO_D7")) { HALO_CASE(bf16_t, 7, 16, 32, 7, 4, 2) }
     } else {
         // round 6: 3^3 32 -> 32 (nine layers at 64^3, 23 % of the exact-fp32 forward) in two channel phases of 16: 38 KB of halo + 18 KB of weight ring instead of
         // 77 + 36 KB -> TWO workgroups per CU = two waves per SIMD, so that one tile's halo load, chunk barriers, fp64 flushes and epilogue run under the other
@@ -2033,7 +2031,7 @@ int conv3d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, bool
         // round 6: the 7^3 layers of the exact-fp32 kernel set.  32 -> 16 (V2V's front layer, 18 % of the fp32 forward on the generic 256 x 16 tile at 51 % of
         // the fp32 MFMA peak): two channel phases of 16 over a 123 KB halo image (NPH = 2, see the kernel).  16 -> 32 (its input gradient in the fp32
         // training step): one phase, one-tap lookahead, two weight buffers (151 KB).  LT_HALO_NO_F7=1: the generic tiles again (A/B).
-        if (ks == 7 && !getenv("LT_HALO_NO_F7")) {
+        if (ks == 7 && !env_on("LT_HALO_NO_F7")) {
             if (c.Cin == 32 && cout_pad == 16) {
                 int rc = launch_halo<float, 7, 16, 16, 4, 8, 8, 7, 4, 2, false, 2>(a, s);
                 return rc == LT_OK ? 1 : rc;

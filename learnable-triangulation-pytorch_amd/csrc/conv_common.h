@@ -43,6 +43,52 @@ struct ConvArgs {
     int Cin2, H2, W2, s2;
 };
 
+// The descriptor's geometry, flags and phases as kernel arguments (tensor pointers, M, log2Cin and the second sources are the caller's).
+inline ConvArgs conv_args_of(const lt_conv_desc& d) {
+    ConvArgs a = {};
+    a.N = d.N; a.D = d.D; a.H = d.H; a.W = d.W; a.Cin = d.Cin;
+    a.Do = d.Do; a.Ho = d.Ho; a.Wo = d.Wo;
+    a.sd = d.stride[0]; a.sh = d.stride[1]; a.sw = d.stride[2];
+    a.pd = d.pad[0]; a.ph = d.pad[1]; a.pw = d.pad[2];
+    a.OD = d.OD; a.OH = d.OH; a.OW = d.OW;
+    a.osd = d.out_stride[0]; a.osh = d.out_stride[1]; a.osw = d.out_stride[2];
+    a.Cout = d.Cout; a.ldc = d.ldc; a.k_pad = d.k_pad; a.flags = d.flags; a.tiles_n = 1; a.stages = d.stages;
+    for (int p = 0; p < d.nphase && p < LT_CONV_MAX_PHASES; ++p) {
+        const lt_conv_phase& ph = d.phase[p];
+        a.phase[p].w = ph.weight;
+        a.phase[p].wfrag = ph.weight_frag_layout == 1 ? ph.weight_frag : nullptr;
+        a.phase[p].wfrag_t = ph.weight_frag_layout == 2 ? ph.weight_frag : nullptr;
+        a.phase[p].wfrag32 = ph.weight_frag_layout == 3 ? ph.weight_frag : nullptr;
+        a.phase[p].taps = (const int4*)ph.taps; a.phase[p].ntaps = ph.ntaps;
+        a.phase[p].ood = ph.out_off[0]; a.phase[p].ooh = ph.out_off[1]; a.phase[p].oow = ph.out_off[2];
+    }
+    return a;
+}
+
+// The geometry conv3d_halo_col_kernel (the column walk, and with it lt_conv_skip_fwd) covers: tiles of 4 x 8 x 8 voxels, at least 1024 of them in
+// multiples of 8 (XCD dealing), and whole columns of >= 2 tiles for every workgroup (>= 256 columns, a multiple of 8).  conv3d_halo_try checks it at
+// launch time, lt_sel_conv_skip at plan time for every sample chunk.
+inline bool halo_col_fits(long long N, int D, int H, int W) {
+    if (D % 4 || H % 8 || W % 8) return false;
+    const long long nblk = N * (D / 4) * (H / 8) * (W / 8), cols = N * (H / 8) * (W / 8);
+    return nblk >= 1024 && nblk % 8 == 0 && D / 4 >= 2 && cols % 8 == 0 && cols >= 256;
+}
+
+// The layers conv2d_halo_kernel covers, whatever the weights and extra sources: 256 -> 256 dense channels, maps whose width is a multiple of 24 and
+// whose height is a multiple of 8, iteration space == input grid, plain store; one phase of nine taps (a "same" 3x3 / stride 1 / pad 1) or four
+// phases of four taps with output stride 2 (the 2 x 2-tap parities of a 4x4 / stride-2 / pad-1 transposed convolution, recorded with pad 0 and
+// signed tap offsets).  conv2d_halo_try checks it at launch time, lt_sel_frag_layout at plan time (a 2D layer packed for it has no other kernel).
+inline bool halo2d_fits(const ConvArgs& c, int cout_pad, int nphase) {
+    if ((nphase != 1 && nphase != 4) || c.D != 1 || c.Do != 1 || c.OD != 1) return false;
+    if (c.sh != 1 || c.sw != 1 || c.H != c.Ho || c.W != c.Wo || c.W % 24 || c.H % 8) return false;
+    if (c.Cin != 256 || cout_pad != 256 || c.Cout != 256 || c.ldc % 8 || (c.flags & (LT_EPI_STORE_F32 | LT_EPI_SIGMOID)) || c.pd != 0) return false;
+    if (nphase == 1 && (c.osh != 1 || c.osw != 1 || c.OH != c.Ho || c.OW != c.Wo || c.ph != 1 || c.pw != 1)) return false;
+    if (nphase == 4 && (c.osh != 2 || c.osw != 2 || c.OH != 2 * c.Ho || c.OW != 2 * c.Wo || c.ph != 0 || c.pw != 0)) return false;
+    for (int p = 0; p < nphase; ++p)
+        if (c.phase[p].ntaps != (nphase == 1 ? 9 : 4) || c.phase[p].ood) return false;
+    return true;
+}
+
 union V16 {
     uint4 u;
     f32x4 f;

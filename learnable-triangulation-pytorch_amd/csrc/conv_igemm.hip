@@ -259,11 +259,11 @@ int dispatch(const ConvArgs& a, int cout_pad, int nphase, int max_taps, int tile
         LT_CHECK_LAUNCH("lt_conv_fwd(direct)");
         return LT_OK;
     }
-    static const bool force_v1 = getenv("LT_CONV_V1") != nullptr;   // A/B switches for profiling sessions
-    static const bool no_halo = getenv("LT_CONV_NO_HALO") != nullptr;
-    static const bool no_respf = getenv("LT_CONV_NO_RESPF") != nullptr;
+    static const bool force_v1 = env_on("LT_CONV_V1");   // A/B switches for profiling sessions
+    static const bool no_halo = env_on("LT_CONV_NO_HALO");
+    static const bool no_respf = env_on("LT_CONV_NO_RESPF");
     if (no_respf) const_cast<ConvArgs&>(a).flags |= LT_EPI_NO_RES_PREFETCH;
-    static const bool no_xcd = getenv("LT_CONV_NO_XCD") != nullptr;
+    static const bool no_xcd = env_on("LT_CONV_NO_XCD");
     if (no_xcd) const_cast<ConvArgs&>(a).flags |= LT_EPI_NO_XCD_REMAP;
     if ((tile == LT_TILE_AUTO && !force_v1 && !no_halo) || tile == LT_TILE_HALO) {
         const int rc = conv3d_halo_try(sizeof(T) == 4 ? LT_F32 : LT_BF16, a, cout_pad, nphase, tile == LT_TILE_HALO, s);
@@ -284,8 +284,8 @@ int dispatch(const ConvArgs& a, int cout_pad, int nphase, int max_taps, int tile
         if (rc < 0) return rc;
         if (rc == 1) return LT_OK;
         // a 2D layer whose weights were packed in layout 2 has NO layout-1 / -3 fragments: the generic tiles would still compute it (from the plain
-        // [cout][k] weights) at a fraction of the rate, silently.  The plan builder's gate mirrors conv2d_halo_try's predicate; a mismatch is a bug: say so
-        // (ADVICE r5).  (3D layers carry layout-2 fragments for conv3d_halo_wreg_kernel, whose siblings above take them when it declines -- a 3^3 layer on a
+        // [cout][k] weights) at a fraction of the rate, silently.  The plan-time gate (lt_sel_frag_layout) shares halo2d_fits with conv2d_halo_try; a
+        // mismatch is a bug: say so.  (3D layers carry layout-2 fragments for conv3d_halo_wreg_kernel, whose siblings above take them when it declines -- a 3^3 layer on a
         // volume of ONE voxel plane, V2V's deepest level in small test volumes, has D == 1 too: the 2D signature is 256 -> 256 with 9 or 4 taps.)
         if (a.D == 1 && a.Do == 1 && a.OD == 1 && a.Cin == 256 && cout_pad == 256 && (a.phase[0].ntaps == 9 || a.phase[0].ntaps == 4)) {
             set_error("lt_conv_fwd: 2D layer with weight_frag_layout 2 (conv2d_halo_kernel) but the halo kernel does not cover it: Cin %d, Cout %d, ldc %d, "
@@ -294,7 +294,7 @@ int dispatch(const ConvArgs& a, int cout_pad, int nphase, int max_taps, int tile
             return LT_ERR_UNSUPPORTED;
         }
     }
-    static const bool no_v3 = getenv("LT_CONV_NO_V3") != nullptr;   // A/B switch
+    static const bool no_v3 = env_on("LT_CONV_NO_V3");   // A/B switch
     if ((tile == LT_TILE_AUTO && !force_v1 && !no_v3) || tile == LT_TILE3_288) {
         const int rc = conv3_try(sizeof(T) == 4 ? LT_F32 : LT_BF16, a, cout_pad, nphase, max_taps, tile == LT_TILE3_288, s);
         if (rc < 0) return rc;
@@ -393,15 +393,8 @@ static int conv_fwd_impl(const lt_conv_desc* d, const void* x, const float* bias
     const long long out_pix = (long long)d->N * d->OD * d->OH * d->OW;
     LT_REQUIRE(M > 0 && M < (1ll << 31) && in_elems < (1ll << 31) && out_pix < (1ll << 31), LT_ERR_UNSUPPORTED,
                "lt_conv_fwd: tensor too large for 32-bit indexing (M=%lld, in=%lld)", M, in_elems);
-    ConvArgs a;
-    a.x = x; a.y = y; a.res = residual; a.bias = bias; a.scale = scale; a.shift = shift;
-    a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.log2Cin = l2;
-    a.Do = d->Do; a.Ho = d->Ho; a.Wo = d->Wo;
-    a.sd = d->stride[0]; a.sh = d->stride[1]; a.sw = d->stride[2];
-    a.pd = d->pad[0]; a.ph = d->pad[1]; a.pw = d->pad[2];
-    a.OD = d->OD; a.OH = d->OH; a.OW = d->OW;
-    a.osd = d->out_stride[0]; a.osh = d->out_stride[1]; a.osw = d->out_stride[2];
-    a.Cout = d->Cout; a.ldc = d->ldc; a.k_pad = d->k_pad; a.flags = d->flags; a.M = (int)M; a.tiles_n = 1; a.stages = d->stages;
+    ConvArgs a = conv_args_of(*d);
+    a.x = x; a.y = y; a.res = residual; a.bias = bias; a.scale = scale; a.shift = shift; a.log2Cin = l2; a.M = (int)M;
     a.skip_x = skip ? skip->x : nullptr; a.skip_w = skip ? skip->weight_frag : nullptr;
     a.x2 = cat2 ? cat2->x : nullptr; a.Cin2 = cat2 ? cat2->cin : 0; a.H2 = cat2 ? cat2->H : 0; a.W2 = cat2 ? cat2->W : 0; a.s2 = cat2 ? cat2->stride : 0;
     int max_taps = 0;
@@ -409,10 +402,6 @@ static int conv_fwd_impl(const lt_conv_desc* d, const void* x, const float* bias
         const lt_conv_phase& ph = d->phase[p];
         LT_REQUIRE(ph.weight && ph.taps && ph.ntaps >= 1, LT_ERR_INVALID, "lt_conv_fwd: phase %d incomplete", p);
         LT_REQUIRE((long long)ph.ntaps * d->Cin <= d->k_pad, LT_ERR_INVALID, "lt_conv_fwd: phase %d: ntaps*Cin > k_pad", p);
-        a.phase[p].w = ph.weight; a.phase[p].wfrag = ph.weight_frag_layout == 1 ? ph.weight_frag : nullptr;
-        a.phase[p].wfrag_t = ph.weight_frag_layout == 2 ? ph.weight_frag : nullptr;
-        a.phase[p].wfrag32 = ph.weight_frag_layout == 3 ? ph.weight_frag : nullptr; a.phase[p].taps = (const int4*)ph.taps; a.phase[p].ntaps = ph.ntaps;
-        a.phase[p].ood = ph.out_off[0]; a.phase[p].ooh = ph.out_off[1]; a.phase[p].oow = ph.out_off[2];
         if (ph.ntaps > max_taps) max_taps = ph.ntaps;
     }
     LT_REQUIRE(max_taps <= 2048, LT_ERR_UNSUPPORTED, "lt_conv_fwd: too many taps (%d)", max_taps);

@@ -667,7 +667,7 @@ int dispatch2(const ConvArgs& a, int cout_pad, int nphase, int max_taps, int til
         else tile = blocks(128, 128) >= minblk ? LT_TILE2_128x128 : (blocks(128, 64) >= minblk ? LT_TILE2_128x64 : LT_TILE2_64x64);
     }
     // uniform-tap path: every 128-byte K step lies inside one tap
-    static const bool no_ut = getenv("LT_CONV_NO_UT") != nullptr;   // A/B switch
+    static const bool no_ut = env_on("LT_CONV_NO_UT");   // A/B switch
     const int mode = pw ? 1 : (((a.Cin * (int)sizeof(T)) % ROW_BYTES == 0 && !no_ut) ? 2 : 0);
     // ring depth: 3 stages cost a resident workgroup per CU on the big tiles, so they only pay when the grid leaves at most
     // one workgroup per CU anyway (tiny layers: pure latency chains)

@@ -173,7 +173,7 @@ namespace lt {
 // phase grid == input grid (then the tap can only be the identity: any other would read outside the input), Cin in
 // {16, 32, 64, 128}, Cout in {32, 64} dense in cout_pad, 16-byte aligned rows, M % 64 == 0, plain bf16 store.
 int conv_pw_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, hipStream_t s) {
-    static const bool off = getenv("LT_CONV_NO_PW") != nullptr;   // A/B
+    static const bool off = env_on("LT_CONV_NO_PW");   // A/B
     if (off || dtype != LT_BF16) return 0;
     if (c.sd != 1 || c.sh != 1 || c.sw != 1 || c.pd || c.ph || c.pw || c.D != c.Do || c.H != c.Ho || c.W != c.Wo) return 0;
     if (c.flags & (LT_EPI_STORE_F32 | LT_EPI_SIGMOID)) return 0;

@@ -6,12 +6,19 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/lt_hip.h"
 
 namespace lt {
 
 void set_error(const char* fmt, ...);
+
+// An on/off A/B switch (LT_NO_*, LT_CONV_NO_*, LT_HALO_NO_*, ...): on when set to anything but "" or "0".  Switches that carry a value read getenv.
+inline bool env_on(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] && !(e[0] == '0' && !e[1]);
+}
 
 #define LT_REQUIRE(cond, code, ...)        \
     do {                                   \

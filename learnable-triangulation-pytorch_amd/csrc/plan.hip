@@ -3,8 +3,8 @@
 // A non-Python host hands over the reference's state_dict (names + host fp32 arrays) and the model configuration once, and then calls the forward with
 // device images and host camera parameters: layer -> kernel selection, every batch threshold, the eval-BatchNorm fold, weight packing (GEMM layout,
 // MFMA fragment orders, parity phases of the transposed convolutions, split-K tap groups), buffer reuse and the captured hipGraph all live behind this
-// file -- the same rules lt_engine.py / mvn/models/*.py apply when the Python modules record their plan (tests/test_gpu_plan_abi.py holds the two
-// against each other and against the reference's golden outputs).
+// file -- the same recording lt_engine.py / mvn/models/*.py do when the Python modules record their plan, by the same kernel-selection rules (lt_sel_*,
+// select.hip: both hosts call them); tests/test_gpu_plan_abi.py holds the two against each other and against the reference's golden outputs.
 //
 // What it replaces in the reference (file:line): VolumetricTriangulationNet.__init__ / forward (mvn/models/triangulation.py:204-355), PoseResNet
 // (mvn/models/pose_resnet.py:57-318: Bottleneck / BasicBlock / Bottleneck_CAFFE, _make_layer, _make_deconv_layer, GlobalAveragePoolingHead), V2VModel
@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <array>
 #include <deque>
 #include <functional>
 #include <map>
@@ -45,8 +46,6 @@ namespace {
 constexpr float BN_EPS = 1e-5f;
 constexpr int GEO_RING = 4;
 
-bool envset(const char* k) { const char* e = getenv(k); return e && e[0] && !(e[0] == '0' && !e[1]); }
-
 unsigned short bf16_rne(float f) {          // torch's float -> bfloat16 (round to nearest even, NaN kept quiet)
     unsigned u;
     memcpy(&u, &f, 4);
@@ -76,6 +75,15 @@ struct Act {
     long long numel() const { return (long long)n * d * h * w * c; }
     bool null() const { return p == nullptr; }
 };
+
+// the selection rules' (select.hip) view of shapes
+lt_wshape wshape(const WT& w) {
+    lt_wshape r = {};
+    r.nd = w.nd;
+    for (int i = 0; i < 5; ++i) r.s[i] = w.s[i];
+    return r;
+}
+std::array<int32_t, 5> dims(const Act& a) { return {a.n, a.d, a.h, a.w, a.c}; }
 
 struct PhaseSpec { std::vector<float> w; std::vector<int32_t> taps; int ntaps = 0; int off[3] = {0, 0, 0}; };
 struct ConvSpec {
@@ -315,37 +323,6 @@ struct lt_plan {
         const Act* skip_x = nullptr; const WT* skip_w = nullptr; const float* skip_bias = nullptr; const BN* skip_bn = nullptr;
     };
 
-    // PlanBuilder.can_conv_skip
-    bool can_conv_skip(const int xs[5], const WT& w, const Act& sx, const WT& sw) {
-        if (dtype != LT_BF16 || envset("LT_NO_CONV_SKIP") || envset("LT_HALO_NO_COL") || envset("LT_HALO_NO_PERSIST") || envset("LT_CONV_NO_HALO")) return false;
-        if (!(w.nd == 5 && w.s[0] == 32 && w.s[1] == 32 && w.s[2] == 3 && w.s[3] == 3 && w.s[4] == 3)) return false;
-        if (!(sw.nd == 5 && sw.s[0] == 32 && sw.s[1] == 16 && sw.s[2] == 1 && sw.s[3] == 1 && sw.s[4] == 1)) return false;
-        const int N = xs[0], D = xs[1], Hh = xs[2], W = xs[3], Cin = xs[4];
-        if (Cin != 32 || sx.n != N || sx.d != D || sx.h != Hh || sx.w != W || sx.c != 16 || D % 4 || Hh % 8 || W % 8 || D / 4 < 2) return false;
-        const int nc = lt_conv_chunk_samples(N, (long long)D * Hh * W * 32);
-        if (nc < 1) return false;
-        const int last = N - (N - 1) / nc * nc;
-        for (int n : {nc, last}) {
-            const long long nblk = (long long)n * (D / 4) * (Hh / 8) * (W / 8), cols = (long long)n * (Hh / 8) * (W / 8);
-            if (!(nblk >= 1024 && nblk % 8 == 0 && cols % 8 == 0 && cols >= 256)) return false;
-        }
-        return true;
-    }
-
-    // PlanBuilder.splitk_slices: V2V's 3^3 128 -> 128 layers at the 8^3 / 4^3 / 2^3 levels as S tap-group phases + lt_splitk_reduce
-    int splitk_slices(const ConvSpec& sp, const WT& w, const ConvOpt& o) {
-        if (dtype != LT_BF16 || o.transposed || o.out_f32 || o.sigmoid || envset("LT_CONV_NO_SPLITK")) return 1;
-        if (w.nd != 5 || w.s[2] != 3 || w.s[3] != 3 || w.s[4] != 3 || sp.st[0] != 1 || sp.st[1] != 1 || sp.st[2] != 1 || sp.pd[0] != 1 || sp.pd[1] != 1 || sp.pd[2] != 1) return 1;
-        if (sp.Cin < 128 || sp.Cin % 64 || sp.Cout % 4 || sp.Cout != sp.cout_pad || sp.D * sp.H * sp.W > 512) return 1;
-        const long long rows = (long long)sp.N * sp.Do * sp.Ho * sp.Wo;
-        const int bm = rows >= 8192 ? 128 : 64;
-        const long long tiles = ((rows + bm - 1) / bm) * (sp.cout_pad / bm);
-        long long S = 256 / tiles;
-        if (S > 8) S = 8;
-        if (S < 1) S = 1;
-        return (int)S;
-    }
-
     void fill_desc(lt_conv_desc& d, const ConvSpec& sp) {
         memset(&d, 0, sizeof(d));
         d.dtype = dtype;
@@ -354,6 +331,10 @@ struct lt_plan {
         d.OD = sp.OD; d.OH = sp.OH; d.OW = sp.OW;
         d.Cout = sp.Cout; d.ldc = sp.Cout; d.cout_pad = sp.cout_pad; d.k_pad = sp.k_pad;
         d.nphase = (int)sp.ph.size(); d.flags = sp.flags; d.tile = 0; d.stages = 0;
+        for (size_t i = 0; i < sp.ph.size(); ++i) {
+            d.phase[i].ntaps = sp.ph[i].ntaps;
+            for (int k = 0; k < 3; ++k) d.phase[i].out_off[k] = sp.ph[i].off[k];
+        }
     }
 
     int pack_frag(const void* wdev, size_t elems, int which, int cout_pad, int k_pad, int cin, int ntaps, const void** out) {
@@ -374,9 +355,11 @@ struct lt_plan {
         const int in[5] = {x.n, x.d, x.h, x.w, x.c};
         ConvSpec sp;
         PL_TRY(make_conv_spec(w, o.bias, o.bn, in, o.stride, o.pad, es, o.transposed, flags, 0, sp));
+        const lt_wshape ws = wshape(w);
         lt_conv_skip* sk = nullptr;
         if (o.skip_x) {
-            LT_REQUIRE(!o.residual && !o.relu_pre && !o.out_f32 && can_conv_skip(in, w, *o.skip_x, *o.skip_w), LT_ERR_INVALID, "plan: conv_skip on an unsupported shape");
+            const lt_wshape sws = wshape(*o.skip_w);
+            LT_REQUIRE(!o.residual && !o.relu_pre && !o.out_f32 && lt_sel_conv_skip(dtype, in, &ws, dims(*o.skip_x).data(), &sws), LT_ERR_INVALID, "plan: conv_skip on an unsupported shape");
             const int sin[5] = {o.skip_x->n, o.skip_x->d, o.skip_x->h, o.skip_x->w, o.skip_x->c};
             ConvSpec ss;
             PL_TRY(make_conv_spec(*o.skip_w, o.skip_bias, o.skip_bn, sin, 1, 0, es, false, 0, 0, ss));
@@ -392,49 +375,26 @@ struct lt_plan {
             sk->x = o.skip_x->p; sk->cin = 16; sk->weight_frag = wfr;
             ++n_conv_skip;
         }
-        const int S = splitk_slices(sp, w, o);
+        lt_conv_desc d0;
+        fill_desc(d0, sp);
+        const int S = lt_sel_splitk_slices(&d0, &ws, o.transposed);
         if (S > 1) return conv_splitk(x, w, sp, S, o.residual, y);
         PL_TRY(alloc(sp.N, sp.OD, sp.OH, sp.OW, sp.Cout, o.out_f32 ? 4 : es, y));
         if (o.residual) LT_REQUIRE(o.residual->n == y.n && o.residual->d == y.d && o.residual->h == y.h && o.residual->w == y.w && o.residual->c == y.c && o.residual->es == es,
                                    LT_ERR_INVALID, "plan: residual shape");
-        conv_descs.emplace_back();
+        conv_descs.push_back(d0);
         lt_conv_desc& d = conv_descs.back();
-        fill_desc(d, sp);
-        const bool bf = dtype == LT_BF16;
-        const bool k1 = [&] { for (int i = 2; i < w.nd; ++i) if (w.s[i] != 1) return false; return true; }();
+        // the weights ALSO in the MFMA fragment order of the kernel that will run the layer (bf16 plans)
+        const int layout = lt_sel_frag_layout(&d, &ws, o.transposed, o.residual != nullptr);
+        if (layout == 2 && w.nd == 4) ++n_halo2d;
         for (size_t i = 0; i < sp.ph.size(); ++i) {
             const PhaseSpec& ph = sp.ph[i];
             const void* wdev; PL_TRY(upload_w(ph.w, &wdev));
             const int32_t* tdev; PL_TRY(upload_i32(ph.taps, &tdev));
-            d.phase[i].weight = wdev; d.phase[i].taps = tdev; d.phase[i].ntaps = ph.ntaps;
-            for (int k = 0; k < 3; ++k) d.phase[i].out_off[k] = ph.off[k];
-            const size_t elems = (size_t)sp.cout_pad * sp.k_pad;
-            // ---- the weights ALSO in the MFMA fragment order of the kernel that will run the layer (lt_engine.PlanBuilder.conv's rules, bf16 plans)
-            const bool w2d_3x3 = !o.transposed && w.nd == 4 && w.s[0] == 256 && w.s[1] == 256 && w.s[2] == 3 && w.s[3] == 3;
-            const bool w2d_4x4t = o.transposed && w.nd == 4 && w.s[0] == 256 && w.s[1] == 256 && w.s[2] == 4 && w.s[3] == 4;
-            bool all4 = true;
-            for (auto& q : sp.ph) all4 = all4 && q.ntaps == 4;
-            if (bf && x.c == 256 && sp.D == 1 && sp.W % 24 == 0 && sp.H % 8 == 0 && !o.residual && !o.out_f32 && !o.sigmoid && !envset("LT_CONV_NO_H2D") &&
-                sp.Cout == 256 && sp.cout_pad == 256 && d.ldc % 8 == 0 && !envset("LT_CONV_V1") &&
-                ((long long)sp.N * (sp.H / 8) * (sp.W / 24) >= 60 || envset("LT_H2D_ANY_SIZE")) &&
-                ((w2d_3x3 && sp.st[1] == 1 && sp.st[2] == 1 && sp.pd[1] == 1 && sp.pd[2] == 1 && sp.W == 24 && sp.OH == sp.H && sp.OW == sp.W) ||
-                 (w2d_4x4t && sp.ph.size() == 4 && !envset("LT_DECONV_NO_H2D") && sp.ostr[1] == 2 && sp.ostr[2] == 2 && sp.OH == 2 * sp.H && sp.OW == 2 * sp.W && all4))) {
-                // ResNet layer3's 3x3 256 -> 256 on 24-wide maps and the head's 4x4 / stride-2 transposed 256 -> 256, from 60 tiles of 8 x 24 pixels on: conv2d_halo_kernel
-                const void* wfr; PL_TRY(pack_frag(wdev, elems, 2, sp.cout_pad, sp.k_pad, 256, ph.ntaps, &wfr));
-                d.phase[i].weight_frag = wfr; d.phase[i].weight_frag_layout = 2;
-                if (i == 0) ++n_halo2d;
-            } else if (bf && sp.cout_pad % 256 == 0 && sp.k_pad % 64 == 0) {
-                // the 288-row layers: fragment order of the 32x32x16 MFMA (conv_igemm7); short-K pointwise layers: the 144-row variant of conv_igemm6 (16x16x32 order)
-                const bool short_pw = k1 && sp.k_pad <= 256 && !o.transposed;
-                const int layout = (!envset("LT_CONV_NO_V7") && !short_pw) ? 3 : 1;
-                const void* wfr; PL_TRY(pack_frag(wdev, elems, layout, sp.cout_pad, sp.k_pad, 0, 0, &wfr));
+            d.phase[i].weight = wdev; d.phase[i].taps = tdev;
+            if (layout) {
+                const void* wfr; PL_TRY(pack_frag(wdev, (size_t)sp.cout_pad * sp.k_pad, layout, sp.cout_pad, sp.k_pad, sp.Cin, ph.ntaps, &wfr));
                 d.phase[i].weight_frag = wfr; d.phase[i].weight_frag_layout = layout;
-            } else if (bf && !o.transposed && w.nd == 5 && x.c == w.s[1] && w.s[2] == 3 && w.s[3] == 3 && w.s[4] == 3 && sp.st[0] == 1 && sp.st[1] == 1 && sp.st[2] == 1 &&
-                       sp.pd[0] == 1 && sp.pd[1] == 1 && sp.pd[2] == 1 &&
-                       ((w.s[0] == 64 && w.s[1] == 64) || (w.s[0] == 64 && w.s[1] == 32) || (w.s[0] == 128 && w.s[1] == 128) || (w.s[0] == 32 && w.s[1] == 16))) {
-                // V2V's 3x3x3 64 -> 64, 32 -> 64, 128 -> 128, 16 -> 32: fragments of the transposed product for conv3d_halo_wreg_kernel
-                const void* wfr; PL_TRY(pack_frag(wdev, elems, 2, sp.cout_pad, sp.k_pad, (int)w.s[1], 27, &wfr));
-                d.phase[i].weight_frag = wfr; d.phase[i].weight_frag_layout = 2;
             }
         }
         const float *bi, *sc, *sh;
@@ -496,18 +456,7 @@ struct lt_plan {
         return LT_OK;
     }
 
-    // PlanBuilder.can_conv_cat2 / conv_cat2: expand + (strided) downsample branch of a Bottleneck's first block as ONE pointwise convolution over [t2 | x]
-    bool can_conv_cat2(const int t2s[5], const WT& we, const Act& x, const WT& wd, int sds) {
-        if (dtype != LT_BF16 || envset("LT_NO_CONV_CAT2") || envset("LT_CONV_NO_V7") || envset("LT_CONV_NO_V3")) return false;
-        const int N = t2s[0], D = t2s[1], Ho = t2s[2], Wo = t2s[3], P = t2s[4];
-        if (D != 1 || we.nd != 4 || wd.nd != 4 || we.s[2] != 1 || we.s[3] != 1 || wd.s[2] != 1 || wd.s[3] != 1) return false;
-        const int Cc = (int)we.s[0], Cin2 = (int)wd.s[1];
-        if (we.s[1] != P || wd.s[0] != Cc || (sds != 1 && sds != 2) || x.n != N || x.d != 1 || x.h != Ho * sds || x.w != Wo * sds || x.c != Cin2) return false;
-        if (P % 32 || Cin2 % 32 || (P + Cin2) % 64 || Cc % 256 || (P & (P - 1))) return false;
-        const long long tiles = (((long long)N * Ho * Wo + 287) / 288) * (Cc / 256);
-        if (tiles < 200 && !envset("LT_CAT2_ANY_SIZE")) return false;
-        return (long long)N * Ho * Wo * Cc < (1ll << 31) && (long long)N * x.h * x.w * Cin2 < (1ll << 31);
-    }
+    // PlanBuilder.conv_cat2: expand + (strided) downsample branch of a Bottleneck's first block as ONE pointwise convolution over [t2 | x]
     int conv_cat2(const Act& t2, const WT& we, const BN& bne, const Act& x, const WT& wd, const BN& bnd, int sds, Act& y) {
         const int N = t2.n, Ho = t2.h, Wo = t2.w, P = t2.c, Cc = (int)we.s[0], Cin2 = (int)wd.s[1];
         const int t2s[5] = {t2.n, t2.d, t2.h, t2.w, t2.c}, xs[5] = {x.n, x.d, x.h, x.w, x.c};
@@ -547,21 +496,8 @@ struct lt_plan {
         return LT_OK;
     }
 
-    // PlanBuilder.can_chain_pointwise / pwchain: V2V's pointwise tail in one pass, planar fp32 logits
+    // PlanBuilder.pwchain: V2V's pointwise tail in one pass, planar fp32 logits
     struct PwLayer { WT w; const float* bias; const BN* bn; bool relu; };
-    bool can_chain_pointwise(const Act& x, const std::vector<PwLayer>& L) {
-        if (dtype != LT_BF16 || L.empty() || (int)L.size() > LT_PWCHAIN_MAX || x.c != 32) return false;
-        if (((long long)x.n * x.d * x.h * x.w) % 64) return false;
-        int cin = 32;
-        for (size_t i = 0; i < L.size(); ++i) {
-            const WT& w = L[i].w;
-            for (int k = 2; k < w.nd; ++k) if (w.s[k] != 1) return false;
-            if (w.s[1] != cin || w.s[0] > 32) return false;
-            if (i + 1 < L.size() && w.s[0] != 32) return false;
-            cin = (int)w.s[0];
-        }
-        return true;
-    }
     int pwchain(const Act& x, const std::vector<PwLayer>& L, Act& y) {
         pw_descs.emplace_back();
         lt_pwchain_desc& d = pw_descs.back();
@@ -619,14 +555,6 @@ struct lt_plan {
         flops += 2.0 * in[0] * in[2] * in[3] * sp.Cout * sp.ph[0].ntaps * sp.Cin;
         return LT_OK;
     }
-    bool can_bottleneck(const Act& x, const WT w[3], const int strides[3]) {
-        if (dtype != LT_BF16 || envset("LT_NO_BNECK")) return false;
-        if (x.d != 1 || strides[0] != 1 || strides[1] != 1 || strides[2] != 1) return false;
-        const int Cc = x.c, P = (int)w[0].s[0];
-        if (!((Cc == 256 && P == 64) || (Cc == 512 && P == 128))) return false;
-        if (!(w[0].s[0] == P && w[0].s[1] == Cc && w[0].s[2] == 1 && w[1].s[0] == P && w[1].s[1] == P && w[1].s[2] == 3 && w[1].s[3] == 3 && w[2].s[0] == Cc && w[2].s[1] == P && w[2].s[2] == 1)) return false;
-        return x.h % 8 == 0 && x.w % 16 == 0 && (long long)x.n * x.h * x.w * Cc < (1ll << 31);
-    }
     int bottleneck(const Act& x, const WT w[3], const BN bn[3], Act& y) {
         PL_TRY(alloc(x.n, 1, x.h, x.w, x.c, es, y));
         bneck_descs.emplace_back();
@@ -643,15 +571,6 @@ struct lt_plan {
         ops.push_back([=](hipStream_t s) { return lt_bottleneck_fwd(dp, xp, yp, s); });
         ++n_bneck;
         return LT_OK;
-    }
-    bool can_bottleneck_ds(const Act& x, const WT w[3], const int strides[3], const WT& wd, int sds) {
-        if (dtype != LT_BF16 || envset("LT_NO_BNECK") || envset("LT_NO_BNECK_DS")) return false;
-        if (x.d != 1 || strides[0] != 1 || strides[1] != 1 || strides[2] != 1 || sds != 1) return false;
-        const int P = (int)w[0].s[0], Cc = (int)w[2].s[0];
-        if (!(x.c == 64 && P == 64 && Cc == 256)) return false;
-        if (!(w[0].s[1] == 64 && w[0].s[2] == 1 && w[1].s[0] == P && w[1].s[1] == P && w[1].s[2] == 3 && w[1].s[3] == 3 && w[2].s[1] == P && w[2].s[2] == 1 &&
-              wd.s[0] == Cc && wd.s[1] == 64 && wd.s[2] == 1 && wd.s[3] == 1)) return false;
-        return x.h % 8 == 0 && x.w % 16 == 0 && (long long)x.n * x.h * x.w * Cc < (1ll << 31);
     }
     int bottleneck_ds(const Act& x, const WT w[3], const BN bn[3], const WT& wd, const BN& bnd, Act& y) {
         const int Cc = (int)w[2].s[0];
@@ -673,13 +592,6 @@ struct lt_plan {
         ops.push_back([=](hipStream_t s) { return lt_bottleneck_ds_fwd(dp, xp, yp, s); });
         ++n_bneck_ds;
         return LT_OK;
-    }
-    bool can_expand_reduce(const Act& t2, const Act& res, const WT& we, const WT& wr) {
-        if (dtype != LT_BF16 || envset("LT_NO_XR")) return false;
-        if (t2.d != 1 || res.d != 1 || t2.n != res.n || t2.h != res.h || t2.w != res.w) return false;
-        if (!(res.c == 1024 && t2.c == 256)) return false;
-        if ((long long)t2.n * t2.h * t2.w < 36 * 96 && !envset("LT_XR_ANY_SIZE")) return false;
-        return we.s[0] == 1024 && we.s[1] == 256 && we.s[2] == 1 && we.s[3] == 1 && wr.s[0] == 256 && wr.s[1] == 1024 && wr.s[2] == 1 && wr.s[3] == 1;
     }
     int expand_reduce(const Act& t2, const Act& res, const WT& we, const BN& bne, const WT& wr, const BN& bnr, Act& y, Act& t1) {
         const int N = t2.n, Hh = t2.h, W = t2.w, P = t2.c, Cc = res.c;
@@ -747,8 +659,10 @@ struct lt_plan {
     // block's reduce where the plan supports the shape (t1n is then the next block's first activation, null otherwise).
     int record_block(const Block& b, const Act& x, const Act* t1_in, const Block* nxt, Act& y, Act& t1n) {
         t1n = Act();
-        if (b.bottleneck && !b.has_ds && !t1_in && !nxt && can_bottleneck(x, b.w, b.strides)) return bottleneck(x, b.w, b.bn, y);
-        if (b.bottleneck && b.has_ds && !t1_in && !nxt && can_bottleneck_ds(x, b.w, b.strides, b.wd, b.sds)) return bottleneck_ds(x, b.w, b.bn, b.wd, b.bnd, y);
+        const lt_wshape w3[3] = {wshape(b.w[0]), wshape(b.w[1]), wshape(b.w[2])}, wd = wshape(b.wd);
+        if (b.bottleneck && !b.has_ds && !t1_in && !nxt && lt_sel_bottleneck(dtype, dims(x).data(), w3, b.strides)) return bottleneck(x, b.w, b.bn, y);
+        if (b.bottleneck && b.has_ds && !t1_in && !nxt && lt_sel_bottleneck_ds(dtype, dims(x).data(), w3, b.strides, &wd, b.sds))
+            return bottleneck_ds(x, b.w, b.bn, b.wd, b.bnd, y);
         if (t1_in || nxt) {
             Act t1, t2;
             ConvOpt o;
@@ -756,7 +670,8 @@ struct lt_plan {
             else { o = ConvOpt(); o.bn = &b.bn[0]; o.relu = true; PL_TRY(conv(x, b.w[0], o, t1)); }
             o = ConvOpt(); o.bn = &b.bn[1]; o.relu = true; o.pad = 1; PL_TRY(conv(t1, b.w[1], o, t2));
             release(t1);
-            if (nxt && can_expand_reduce(t2, x, b.w[2], nxt->w[0])) {
+            const lt_wshape wr = nxt ? wshape(nxt->w[0]) : lt_wshape{};
+            if (nxt && lt_sel_expand_reduce(dtype, dims(t2).data(), dims(x).data(), &w3[2], &wr)) {
                 PL_TRY(expand_reduce(t2, x, b.w[2], b.bn[2], nxt->w[0], nxt->bn[0], y, t1n));
                 release(t2);
                 return LT_OK;
@@ -768,7 +683,7 @@ struct lt_plan {
         if (b.bottleneck && b.has_ds) {
             const int Ho = (x.h - 1) / b.sds + 1, Wo = (x.w - 1) / b.sds + 1;
             const int t2s[5] = {x.n, 1, Ho, Wo, (int)b.w[2].s[1]};
-            if (can_conv_cat2(t2s, b.w[2], x, b.wd, b.sds)) {
+            if (lt_sel_conv_cat2(dtype, t2s, &w3[2], dims(x).data(), &wd, b.sds)) {
                 Act t1, t2; ConvOpt o;
                 o.bn = &b.bn[0]; o.relu = true; o.stride = b.strides[0]; PL_TRY(conv(x, b.w[0], o, t1));
                 o = ConvOpt(); o.bn = &b.bn[1]; o.relu = true; o.stride = b.strides[1]; o.pad = 1; PL_TRY(conv(t1, b.w[1], o, t2));
@@ -837,7 +752,9 @@ struct lt_plan {
         WT w1; BN bn1;
         PL_TRY(get("backbone.conv1.weight", w1, 4)); PL_TRY(get_bn("backbone.bn1", 64, bn1));
         Act y;
-        if (dtype == LT_BF16 && w1.s[0] == 64 && w1.s[1] == 3 && w1.s[2] == 7 && w1.s[3] == 7) PL_TRY(stem_pool(N, Hh, W, w1, bn1, y));
+        const int32_t stem_in[5] = {N, 1, Hh, W, 8}, pool[3] = {3, 2, 1};
+        const lt_wshape ws1 = wshape(w1);
+        if (w1.s[1] == 3 && lt_sel_stem_pool(dtype, stem_in, &ws1, 2, 3, pool)) PL_TRY(stem_pool(N, Hh, W, w1, bn1, y));          // reads the 3-channel images
         else {
             // fp32 plans: the images go through lt_nchw_to_nhwc (pre op) into a 4-channel map, then conv1 + max pool
             const int cpad = 16 / es;
@@ -909,7 +826,8 @@ struct lt_plan {
         if (has_skip) PL_TRY(load_c3(pre + ".skip_con.0", pre + ".skip_con.1", false, sk));
         const int mid[5] = {x.n, x.d, x.h, x.w, (int)c0.w.s[0]};
         Act y, z;
-        if (has_skip && can_conv_skip(mid, c3.w, x, sk.w)) {
+        const lt_wshape w3 = wshape(c3.w), wsk = has_skip ? wshape(sk.w) : lt_wshape{};
+        if (has_skip && lt_sel_conv_skip(dtype, mid, &w3, dims(x).data(), &wsk)) {
             ConvOpt o; o.bias = c0.b; o.bn = &c0.bn; o.pad = 1; o.relu = true; PL_TRY(conv(x, c0.w, o, y));
             o = ConvOpt(); o.bias = c3.b; o.bn = &c3.bn; o.pad = 1; o.relu = true; o.skip_x = &x; o.skip_w = &sk.w; o.skip_bias = sk.b; o.skip_bn = &sk.bn;
             PL_TRY(conv(y, c3.w, o, z)); release(y);
@@ -957,7 +875,8 @@ struct lt_plan {
         PL_TRY(load_c3(V + "back_layers.2.block.0", V + "back_layers.2.block.1", false, t2));
         PL_TRY(load_c3(V + "output_layer", "", false, ol));
         std::vector<PwLayer> chain = {{t1.w, t1.b, &t1.bn, true}, {t2.w, t2.b, &t2.bn, true}, {ol.w, ol.b, nullptr, false}};
-        if (can_chain_pointwise(x, chain)) {          // the pointwise tail (back_layers[1:] + output_layer) as ONE pass, (N, J, V, V, V) planar fp32 logits
+        const lt_wshape wchain[3] = {wshape(t1.w), wshape(t2.w), wshape(ol.w)};
+        if (lt_sel_pwchain(dtype, dims(x).data(), 3, wchain)) {          // the pointwise tail (back_layers[1:] + output_layer) as ONE pass, (N, J, V, V, V) planar fp32 logits
             PL_TRY(pwchain(x, chain, logits_out)); release(x);
             return LT_OK;
         }

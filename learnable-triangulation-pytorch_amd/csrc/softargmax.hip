@@ -308,7 +308,7 @@ __global__ __launch_bounds__(256) void sa3_probs_kernel(const SA3Args a) {
 
 // planar logits whose volumes are float4-addressable take the vectorised kernels
 bool sa3_planar_vec(const SA3Args& a) {
-    static const bool off = getenv("LT_SA3_NO_VEC") != nullptr;
+    static const bool off = env_on("LT_SA3_NO_VEC");
     return !off && a.nvox % 4 == 0 && ((uintptr_t)a.logits & 15) == 0 && ((uintptr_t)a.coords & 15) == 0 &&
            (!a.probs || ((uintptr_t)a.probs & 15) == 0);
 }

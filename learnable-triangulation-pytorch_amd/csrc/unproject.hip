@@ -466,13 +466,13 @@ namespace {
 int unproject_dispatch(UnprojArgs& a, int dtype, bool grid, hipStream_t st) {
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
     a.bricked = (a.v0 % 4 == 0 && a.v1 % 4 == 0 && a.v2 % 16 == 0) ? 1 : 0;
-    a.blocked = (a.bricked && a.v0 % 32 == 0 && a.v1 % 32 == 0 && a.v2 % 32 == 0 && !getenv("LT_UNPROJ_RASTER")) ? 1 : 0;          // LT_UNPROJ_RASTER=1: the old order (A/B)
+    a.blocked = (a.bricked && a.v0 % 32 == 0 && a.v1 % 32 == 0 && a.v2 % 32 == 0 && !env_on("LT_UNPROJ_RASTER")) ? 1 : 0;          // LT_UNPROJ_RASTER=1: the old order (A/B)
     a.chunks = (int)cdiv(nvox, 256);
     a.xcd_pin = (a.B % 8 == 0) ? 1 : 0;
     LT_REQUIRE((long long)a.B * a.chunks < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_fwd: grid too large");
     const unsigned nblk = (unsigned)((long long)a.B * a.chunks);
     // quad kernel: bf16, 32 channels, 4 or 8 views, view softmax, bricked volume (BASELINE configurations 2 and 4)
-    const char* no_q4 = getenv("LT_UNPROJ_NO_Q4");       // A/B, read per call
+    const bool no_q4 = env_on("LT_UNPROJ_NO_Q4");       // A/B, read per call
     const bool quad = dtype == LT_BF16 && a.C == 32 && (a.NV == 4 || a.NV == 8) && a.bricked && a.agg == LT_AGG_SOFTMAX && !no_q4 &&
                       (long long)a.NV * a.h * a.w * a.C < (1ll << 30);
     if (quad) {

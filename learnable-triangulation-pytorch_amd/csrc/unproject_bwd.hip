@@ -549,7 +549,7 @@ int blocks_k1(long long nvox, int C) {
     return (int)(blocks < 2048 ? blocks : 2048);
 }
 
-bool gather_takes(int C) { return C >= 4 && C <= 64 && (C & (C - 1)) == 0 && getenv("LT_UNPROJ_BWD_ATOMICS") == nullptr; }
+bool gather_takes(int C) { return C >= 4 && C <= 64 && (C & (C - 1)) == 0 && !env_on("LT_UNPROJ_BWD_ATOMICS"); }
 
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 

@@ -958,13 +958,13 @@ extern "C" int lt_conv_wgrad_bf16(const void* dy16, const void* x16, const int32
 extern "C" int lt_conv_wgrad_bf16_nhwc_ok(int32_t N, int32_t D, int32_t H, int32_t W, int32_t Cin, int32_t ldx, int32_t Do, int32_t Ho, int32_t Wo, const int32_t stride[3],
                                           const int32_t pad[3], int32_t Cout, int32_t ldy, int32_t cout_pad, int32_t k_pad, int32_t ntaps) {
     if (!stride || !pad || N < 1 || ntaps < 1 || Cin < 1) return 0;
-    if (getenv("LT_WGRAD16_PACKED")) return 0;
+    if (env_on("LT_WGRAD16_PACKED")) return 0;
     const int G = (int)cdiv(N, 8);
     const long long M = (long long)G * Do * Ho * Wo;
     const bool unit = stride[0] == 1 && stride[1] == 1 && stride[2] == 1 && D == Do && H == Ho && W == Wo;
     // the V2V 3^3 layers: the LDS-brick kernel, staged from the channels-last tensors when a workgroup's 32 input channels are whole 8-channel chunks
     if (brick16_ok(D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, cout_pad, k_pad, ntaps))
-        return Cin % 32 == 0 && ldx == Cin && ldy % 8 == 0 && !getenv("LT_WGRAD16_BRICK_PACKED") && (long long)N * D * H * W * Cin < (1ll << 31) &&
+        return Cin % 32 == 0 && ldx == Cin && ldy % 8 == 0 && !env_on("LT_WGRAD16_BRICK_PACKED") && (long long)N * D * H * W * Cin < (1ll << 31) &&
                (long long)N * D * H * W * ldy < (1ll << 31);
     if (unit && ntaps == 343 && Cin == 32 && Cout == 16) return 0;
     if (ilog2_exact(Cin) < 0 || k_pad % 4 || k_pad < ntaps * Cin || cout_pad < Cout || ldy < Cout || ldx < Cin) return 0;

@@ -9,7 +9,6 @@ Everything numerical happens in liblt_hip.so.  This module only
   * issues the C-ABI calls on an explicit stream and owns the hipGraph.
 """
 import ctypes as C
-import os
 from collections import OrderedDict
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
@@ -292,25 +291,41 @@ class PlanBuilder:
 
     def can_conv_skip(self, x_shape, weight, skip_shape, skip_weight):
         """True when lt_conv_skip_fwd covers this convolution + computed residual: the second 3x3x3 convolution (32 -> 32) of a Res3DBlock whose skip
-        connection is a 1x1x1 convolution of a 16-channel tensor (v2v.py:20-42, :76), bf16 plan over build-time weights, on a shape the column-walk halo
-        kernel takes -- the conditions of conv3d_halo_try, mirrored (the C side has no fallback and fails loudly).  LT_NO_CONV_SKIP=1: off (A/B)."""
-        if (self.dtype != torch.bfloat16 or self.out_dtype != torch.bfloat16 or self.live_weights or self.tile_override or
-                any(os.environ.get(k) for k in ("LT_NO_CONV_SKIP", "LT_HALO_NO_COL", "LT_HALO_NO_PERSIST", "LT_CONV_NO_HALO"))):
+        connection is a 1x1x1 convolution of a 16-channel tensor (v2v.py:20-42, :76), over build-time weights (lt_sel_conv_skip)."""
+        if self.out_dtype != torch.bfloat16 or self.live_weights or self.tile_override:
             return False
-        if tuple(weight.shape) != (32, 32, 3, 3, 3) or tuple(skip_weight.shape) != (32, 16, 1, 1, 1):
-            return False
-        N, D, Hh, W, Cin = x_shape
-        if Cin != 32 or tuple(skip_shape) != (N, D, Hh, W, 16) or D % 4 or Hh % 8 or W % 8 or D // 4 < 2:
-            return False
-        # batches beyond 2^31 elements run as sample chunks inside the C entry point (round 6): EVERY chunk has to satisfy the kernel's conditions
-        nc = conv_chunk_samples(N, D * Hh * W * 32)
-        if nc < 1:
-            return False
-        for n in {nc, N - (N - 1) // nc * nc}:          # the full chunks and the last one
-            nblk, cols = n * (D // 4) * (Hh // 8) * (W // 8), n * (Hh // 8) * (W // 8)
-            if not (nblk >= 1024 and nblk % 8 == 0 and cols % 8 == 0 and cols >= 256):
-                return False
-        return True
+        return bool(H.lib().lt_sel_conv_skip(self.code, H.dims(x_shape), H.wshape(weight), H.dims(skip_shape), H.wshape(skip_weight)))
+
+    def _desc(self, spec):
+        """The lt_conv_fwd descriptor of ``spec`` without its tensor pointers."""
+        d = H.ConvDesc()
+        d.dtype = self.code
+        d.N, d.D, d.H, d.W, d.Cin = spec.N, spec.D, spec.H, spec.W, spec.Cin
+        d.Do, d.Ho, d.Wo = spec.Do, spec.Ho, spec.Wo
+        d.stride = H.i3(spec.stride); d.pad = H.i3(spec.pad)
+        d.OD, d.OH, d.OW = spec.OD, spec.OH, spec.OW
+        d.out_stride = H.i3(spec.out_stride)
+        d.Cout, d.ldc, d.cout_pad, d.k_pad = spec.Cout, spec.Cout, spec.cout_pad, spec.k_pad
+        d.nphase, d.flags, d.tile, d.stages = len(spec.phases), spec.flags, self.tile_override, self.stages
+        for i, ph in enumerate(spec.phases):
+            d.phase[i].ntaps = ph.taps.shape[0]; d.phase[i].out_off = H.i3(ph.out_off)
+        return d
+
+    def frag_layout(self, spec, weight, transposed, residual):
+        """weight_frag_layout the convolution's weights are packed in (lt_sel_frag_layout; 0 = none).  With live weights none, unless the training tape
+        gathers the live Parameters into the fragment layout itself (live_frag)."""
+        if self.live_weights and not self.live_frag:
+            return 0
+        return H.lib().lt_sel_frag_layout(self._desc(spec), H.wshape(weight), int(transposed), int(residual))
+
+    @staticmethod
+    def _frag_packer(layout, spec, ntaps):
+        """pack(src_ptr, dst_ptr): one phase's [cout_pad][k_pad] weights of ``spec`` into fragment layout ``layout`` on the current stream."""
+        if layout == 2:
+            return lambda sp, dp, a=(spec.cout_pad, spec.k_pad, spec.Cin, ntaps): H.check(
+                H.lib().lt_conv_pack_weights_t32(sp, *a, dp, H.cur_stream()), "lt_conv_pack_weights_t32")
+        name = "lt_conv_pack_weights32" if layout == 3 else "lt_conv_pack_weights"
+        return lambda sp, dp, a=(spec.cout_pad, spec.k_pad): H.check(getattr(H.lib(), name)(sp, *a, dp, H.cur_stream()), name)
 
     def conv(self, x, weight, bias=None, bn=None, stride=1, pad=0, transposed=False, relu=False, relu_pre=False,
              residual=None, out_f32=False, out=None, sigmoid=False, output_padding=0, residual_f32=False, skip=None):
@@ -347,79 +362,22 @@ class PlanBuilder:
             self.keep.append(residual.t)
         if residual is not None:
             assert residual.shape == y.shape and residual.t.dtype == (torch.float32 if residual_f32 else self.out_dtype), (residual.shape, y.shape)
-        d = H.ConvDesc()
-        d.dtype = self.code
-        d.N, d.D, d.H, d.W, d.Cin = spec.N, spec.D, spec.H, spec.W, spec.Cin
-        d.Do, d.Ho, d.Wo = spec.Do, spec.Ho, spec.Wo
-        d.stride = H.i3(spec.stride); d.pad = H.i3(spec.pad)
-        d.OD, d.OH, d.OW = spec.OD, spec.OH, spec.OW
-        d.out_stride = H.i3(spec.out_stride)
-        d.Cout, d.ldc, d.cout_pad, d.k_pad = spec.Cout, spec.Cout, spec.cout_pad, spec.k_pad
-        d.nphase, d.flags, d.tile, d.stages = len(spec.phases), spec.flags, self.tile_override, self.stages
+        d = self._desc(spec)
+        # wide bf16 layers also get their weights in the MFMA fragment order of the kernel that will run them: packed once, here
+        layout = self.frag_layout(spec, weight, transposed, residual is not None)
         wdevs, wfrags = [], []
         for i, ph in enumerate(spec.phases):
             wdev = self.const(ph.weight, self.dtype)
             wdevs.append(wdev)
             tdev = self.const(ph.taps)
             d.phase[i].weight = wdev.data_ptr(); d.phase[i].taps = tdev.data_ptr()
-            d.phase[i].ntaps = ph.taps.shape[0]; d.phase[i].out_off = H.i3(ph.out_off)
-            # wide bf16 layers also get their weights in MFMA fragment order (B operand read straight from global memory by
-            # the 288 x 256 kernel); packed once, here
-            if self.live_weights and not self.live_frag:
-                pass
-            elif (self.dtype == torch.bfloat16 and not self.dry_run and x.shape[-1] == 256 and spec.D == 1 and spec.W % 24 == 0 and spec.H % 8 == 0
-                  and residual is None and not out_f32 and not sigmoid and not self.tile_override and os.environ.get("LT_CONV_NO_H2D") != "1"
-                  and spec.Cout == spec.cout_pad == 256 and d.ldc % 8 == 0 and not any(os.environ.get(k) for k in ("LT_CONV_V1",))
-                  and (spec.N * (spec.H // 8) * (spec.W // 24) >= 60 or os.environ.get("LT_H2D_ANY_SIZE") == "1")
-                  # conv2d_halo_try's predicate, mirrored (the dispatcher fails loudly on a layout-2 2D layer the kernel declines): a "same" 3x3 / stride 1 /
-                  # pad 1, or the four 2 x 2-tap parities of a 4x4 / stride 2 / pad 1 / output_padding 0 transposed convolution that doubles the map
-                  and ((not transposed and tuple(weight.shape) == (256, 256, 3, 3) and spec.stride == (1, 1, 1) and spec.pad == (0, 1, 1) and spec.W == 24
-                        and (spec.OH, spec.OW) == (spec.Ho, spec.Wo) == (spec.H, spec.W) and spec.out_stride == (1, 1, 1)) or
-                       (transposed and tuple(weight.shape) == (256, 256, 4, 4) and len(spec.phases) == 4 and os.environ.get("LT_DECONV_NO_H2D") != "1"
-                        and output_padding == 0 and spec.out_stride == (1, 2, 2) and (spec.OH, spec.OW) == (2 * spec.H, 2 * spec.W)
-                        and all(int(p.taps.shape[0]) == 4 for p in spec.phases)))):
-                # ResNet layer3's 3x3 256 -> 256 on 24-wide maps and the 4x4 / stride-2 transposed convolutions 256 -> 256 of the head (four parities of
-                # 2 x 2 taps), from 60 tiles of 8 x 24 pixels on (= 5 samples of 4 views; measured with the threshold off: 799.9 -> 811.3 samples/s at 5 samples,
-                # 1145 -> 1172 at 10, 1406 -> 1428 at 32 -- a tile is a ~40 us serial chain, so a handful of them loses to the small implicit-GEMM tiles):
-                # fragments of the transposed product for conv2d_halo_kernel (input halo resident in LDS; LT_CONV_NO_H2D=1 keeps conv_igemm7,
-                # LT_DECONV_NO_H2D=1 only for the transposed ones)
+            if layout and not self.dry_run:
                 wfr = torch.empty_like(wdev)
-                pack = lambda sp, dp, a=(spec.cout_pad, spec.k_pad, 256, int(ph.taps.shape[0])): H.check(
-                    H.lib().lt_conv_pack_weights_t32(sp, a[0], a[1], a[2], a[3], dp, H.cur_stream()), "lt_conv_pack_weights_t32")
-                pack(wdev.data_ptr(), wfr.data_ptr())
-                self.keep.append(wfr)
-                wfrags.append((i, wfr, pack))
-                d.phase[i].weight_frag, d.phase[i].weight_frag_layout = wfr.data_ptr(), 2
-            elif self.dtype == torch.bfloat16 and not self.dry_run and spec.cout_pad % 256 == 0 and spec.k_pad % 64 == 0:
-                wfr = torch.empty_like(wdev)
-                # the 288-row layers get their weights in the fragment order of the 32x32x16 MFMA (conv_igemm7: +1 % end to end over
-                # conv_igemm6, 3x3 256->256 90.8 -> 87.4 us, 1x1 1024->256 50.9 -> 48.2 us inside the forward; LT_CONV_NO_V7=1 when the
-                # plan is built keeps conv_igemm6); the short-K pointwise layers stay on the 144-row variant of conv_igemm6 and its
-                # 16x16x32 order (measured: conv_igemm7 103.6 vs 85.6 us on 256->1024)
-                short_pw = all(k == 1 for k in weight.shape[2:]) and spec.k_pad <= 256 and not transposed
-                if os.environ.get("LT_CONV_NO_V7") != "1" and not short_pw:
-                    pack = lambda sp, dp, a=(spec.cout_pad, spec.k_pad): H.check(H.lib().lt_conv_pack_weights32(sp, a[0], a[1], dp, H.cur_stream()),
-                                                                                 "lt_conv_pack_weights32")
-                    layout = 3
-                else:
-                    pack = lambda sp, dp, a=(spec.cout_pad, spec.k_pad): H.check(H.lib().lt_conv_pack_weights(sp, a[0], a[1], dp, H.cur_stream()),
-                                                                                 "lt_conv_pack_weights")
-                    layout = 1
+                pack = self._frag_packer(layout, spec, int(ph.taps.shape[0]))
                 pack(wdev.data_ptr(), wfr.data_ptr())
                 self.keep.append(wfr)
                 wfrags.append((i, wfr, pack))
                 d.phase[i].weight_frag, d.phase[i].weight_frag_layout = wfr.data_ptr(), layout
-            elif (self.dtype == torch.bfloat16 and not self.dry_run and not transposed and x.shape[-1] == weight.shape[1]
-                  and tuple(weight.shape) in ((64, 64, 3, 3, 3), (64, 32, 3, 3, 3), (128, 128, 3, 3, 3), (32, 16, 3, 3, 3))
-                  and spec.stride == (1, 1, 1) and spec.pad == (1, 1, 1)):
-                # 3x3x3 64 -> 64, 32 -> 64, 128 -> 128, 16 -> 32 (V2V): fragments of the transposed product for conv3d_halo_wreg_kernel
-                wfr = torch.empty_like(wdev)
-                pack = lambda sp, dp, a=(spec.cout_pad, spec.k_pad, int(weight.shape[1])): H.check(
-                    H.lib().lt_conv_pack_weights_t32(sp, a[0], a[1], a[2], 27, dp, H.cur_stream()), "lt_conv_pack_weights_t32")
-                pack(wdev.data_ptr(), wfr.data_ptr())
-                self.keep.append(wfr)
-                wfrags.append((i, wfr, pack))
-                d.phase[i].weight_frag, d.phase[i].weight_frag_layout = wfr.data_ptr(), 2
         bi, sc, sh = self.const(spec.bias), self.const(spec.scale), self.const(spec.shift)
         self.keep.append(d)
         macs = spec.N * spec.Do * spec.Ho * spec.Wo * spec.Cout * sum(int(p.taps.shape[0]) for p in spec.phases) * (
@@ -450,25 +408,10 @@ class PlanBuilder:
 
     # ---- last 1x1 convolution of a Bottleneck + its downsample branch as ONE pointwise convolution over two sources ---------------------------------
     def can_conv_cat2(self, t2_shape, w_expand, x_shape, w_down, stride_down):
-        """True when lt_conv_cat2_fwd covers  relu(bn3(conv1x1(t2)) + bn_d(conv1x1_d(x), stride s)): bf16 plan over build-time weights, 2D maps, both
-        channel counts multiples of 32 with a sum that is a multiple of 64, the block width a multiple of 256, s in (1, 2) and x's map exactly s times
-        t2's (LT_NO_CONV_CAT2=1: off; needs conv_igemm7, so LT_CONV_NO_V7=1 turns it off too)."""
-        if (self.dtype != torch.bfloat16 or self.out_dtype != torch.bfloat16 or self.live_weights or self.tile_override or
-                os.environ.get("LT_NO_CONV_CAT2") == "1" or os.environ.get("LT_CONV_NO_V7") == "1" or os.environ.get("LT_CONV_NO_V3") == "1"):
+        """True when lt_conv_cat2_fwd covers  relu(bn3(conv1x1(t2)) + bn_d(conv1x1_d(x), stride s)) over build-time weights (lt_sel_conv_cat2)."""
+        if self.out_dtype != torch.bfloat16 or self.live_weights or self.tile_override:
             return False
-        N, D, Ho, Wo, P = t2_shape
-        if D != 1 or w_expand.dim() != 4 or w_down.dim() != 4 or tuple(w_expand.shape[2:]) != (1, 1) or tuple(w_down.shape[2:]) != (1, 1):
-            return False
-        Cc, Cin2 = w_expand.shape[0], w_down.shape[1]
-        if w_expand.shape[1] != P or w_down.shape[0] != Cc or stride_down not in (1, 2) or tuple(x_shape) != (N, 1, Ho * stride_down, Wo * stride_down, Cin2):
-            return False
-        if P % 32 or Cin2 % 32 or (P + Cin2) % 64 or Cc % 256 or P & (P - 1):
-            return False
-        # one kernel with 288 x 256 tiles, one workgroup per CU: below ~200 tiles (lt_conv_fwd's own rule for that tile) the separate launches on
-        # smaller tiles fill the chip better (LT_CAT2_ANY_SIZE=1: always -- tests)
-        if -(-(N * Ho * Wo) // 288) * (Cc // 256) < 200 and os.environ.get("LT_CAT2_ANY_SIZE") != "1":
-            return False
-        return N * Ho * Wo * Cc < 2 ** 31 and N * x_shape[2] * x_shape[3] * Cin2 < 2 ** 31
+        return bool(H.lib().lt_sel_conv_cat2(self.code, H.dims(t2_shape), H.wshape(w_expand), H.dims(x_shape), H.wshape(w_down), stride_down))
 
     def conv_cat2(self, t2, w_expand, bn_expand, x, w_down, bn_down, stride_down):
         """relu(bn3(conv1x1(t2)) + bn_d(conv1x1_d(x), stride s)) as ONE launch (lt_conv_cat2_fwd): a pointwise convolution over the channel concatenation
@@ -521,21 +464,13 @@ class PlanBuilder:
 
     # ---- split-K for the tiny levels of V2V ---------------------------------------------------------------------------------------
     def splitk_slices(self, spec, weight, transposed, out_f32, sigmoid, out):
-        """Number of tap groups S the reduction of this convolution is cut into (1 = not split).  Taken for bf16 plans' 3 x 3 x 3 / stride 1
-        convolutions with >= 128 input channels on volumes of at most 8^3 voxels -- V2V's 128 -> 128 layers at the 8^3 / 4^3 / 2^3 levels
-        (v2v.py:78-90), 18 launches of ~30 us each whatever the batch: K = 3456 is a 54-step latency chain for the one or few workgroups
-        the few output rows give.  S is chosen so that tiles x S fills the chip (<= 8: lt_conv_fwd's phase limit)."""
-        if (self.dtype != torch.bfloat16 or self.live_weights or transposed or out_f32 or sigmoid or out is not None or os.environ.get("LT_CONV_NO_SPLITK") == "1"
-                or self.tile_override):
+        """Number of tap groups S the reduction of this convolution is cut into (1 = not split; lt_sel_splitk_slices): V2V's 3 x 3 x 3 128 -> 128
+        layers at the 8^3 / 4^3 / 2^3 levels (v2v.py:78-90) in bf16 plans over build-time weights."""
+        if self.live_weights or out is not None or self.tile_override:
             return 1
-        if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or spec.stride != (1, 1, 1) or spec.pad != (1, 1, 1):
-            return 1
-        if spec.Cin < 128 or spec.Cin % 64 or spec.Cout % 4 or spec.Cout != spec.cout_pad or spec.D * spec.H * spec.W > 512:
-            return 1
-        rows = spec.N * spec.Do * spec.Ho * spec.Wo
-        bm = 128 if rows >= 8192 else 64
-        tiles = -(-rows // bm) * (spec.cout_pad // bm)
-        return max(1, min(8, 256 // tiles))
+        d = self._desc(spec)
+        d.flags |= (H.EPI_STORE_F32 if out_f32 else 0) | (H.EPI_SIGMOID if sigmoid else 0)
+        return H.lib().lt_sel_splitk_slices(d, H.wshape(weight), int(transposed))
 
     def _conv_splitk(self, x, weight, spec, S, residual):
         """The convolution as S tap-group phases of ONE lt_conv_fwd launch (fp32 partial sums, depth-stacked) + lt_splitk_reduce (the
@@ -558,22 +493,13 @@ class PlanBuilder:
             assert residual.shape == y.shape and residual.t.dtype == self.dtype, (residual.shape, y.shape)
             self.keep.append(residual.t)
         rows = spec.N * spec.Do * spec.Ho * spec.Wo
-        d = H.ConvDesc()
-        d.dtype = self.code
-        d.N, d.D, d.H, d.W, d.Cin = spec.N, spec.D, spec.H, spec.W, Cin
-        d.Do, d.Ho, d.Wo = spec.Do, spec.Ho, spec.Wo
-        d.stride = H.i3(spec.stride); d.pad = H.i3(spec.pad)
-        d.OD, d.OH, d.OW = S * spec.Do, spec.Ho, spec.Wo
-        d.out_stride = H.i3((1, 1, 1))
-        d.Cout, d.ldc, d.cout_pad, d.k_pad = spec.Cout, spec.Cout, spec.cout_pad, kp
-        d.nphase, d.flags, d.stages = S, H.EPI_STORE_F32, self.stages
+        d = self._desc(pspec)
         d.tile = H.TILE2_128x128 if rows >= 8192 else H.TILE2_64x64        # the generic implicit GEMM: its grid.y runs the phases side by side
         wdevs = []
         for i, ph in enumerate(pspec.phases):
             wdev, tdev = self.const(ph.weight, self.dtype), self.const(ph.taps)
             wdevs.append(wdev)
             d.phase[i].weight = wdev.data_ptr(); d.phase[i].taps = tdev.data_ptr()
-            d.phase[i].ntaps = ph.taps.shape[0]; d.phase[i].out_off = H.i3(ph.out_off)
         ibi, isc, ish = (self.const(t) for t in ident)
         bi, sc, sh = self.const(spec.bias), self.const(spec.scale), self.const(spec.shift)
         self.keep.append(d)
@@ -596,20 +522,9 @@ class PlanBuilder:
         return y
 
     def can_chain_pointwise(self, x, layers):
-        """True when lt_pwchain_fwd covers this chain: bf16 plan, 32 input channels, 1x1x1 kernels, inner widths 32, last
-        width <= 32 stored as fp32, voxel count a multiple of 64.  layers: [(weight, bias, bn, relu), ...]."""
-        if self.dtype != torch.bfloat16 or not (1 <= len(layers) <= H.PWCHAIN_MAX) or x.shape[-1] != 32:
-            return False
-        if int(np.prod(x.shape[:-1])) % 64:
-            return False
-        cin = 32
-        for i, (w, _, _, _) in enumerate(layers):
-            if tuple(w.shape[2:]) != (1,) * (w.dim() - 2) or w.shape[1] != cin or w.shape[0] > 32:
-                return False
-            if i + 1 < len(layers) and w.shape[0] != 32:
-                return False
-            cin = w.shape[0]
-        return True
+        """True when lt_pwchain_fwd covers this chain (lt_sel_pwchain).  layers: [(weight, bias, bn, relu), ...]."""
+        ws = (H.WShape * len(layers))(*[H.wshape(w) for w, _, _, _ in layers])
+        return bool(H.lib().lt_sel_pwchain(self.code, H.dims(x.shape), len(layers), ws))
 
     def pwchain(self, x, layers, planar=False):
         """Chain of pointwise convolutions in one pass over the volume (lt_pwchain_fwd); the last layer's output is fp32.
@@ -654,19 +569,10 @@ class PlanBuilder:
 
     # ---- whole identity Bottleneck block in one launch (ResNet layer1 / layer2) -----------------------------------------------------
     def can_bottleneck(self, x, convs, strides):
-        """True when lt_bottleneck_fwd covers the block: bf16 plan over build-time weights, 2D map, three stride-1 convolutions
-        1x1 C->P, 3x3 P->P, 1x1 P->C with (C, P) = (256, 64) or (512, 128), no downsample (the caller checks), H % 8 == 0 and W % 16 == 0."""
-        if self.dtype != torch.bfloat16 or self.live_weights or self.tile_override or os.environ.get("LT_NO_BNECK") == "1":
+        """True when lt_bottleneck_fwd covers the identity block (no downsample: the caller checks) over build-time weights (lt_sel_bottleneck)."""
+        if self.live_weights or self.tile_override or len(convs) != 3:
             return False
-        N, D, Hh, W, Cc = x.shape
-        if D != 1 or len(convs) != 3 or any(s != 1 for s in strides):
-            return False
-        P = convs[0].shape[0]
-        if (Cc, P) not in ((256, 64), (512, 128)):
-            return False
-        if (tuple(convs[0].shape) != (P, Cc, 1, 1) or tuple(convs[1].shape) != (P, P, 3, 3) or tuple(convs[2].shape) != (Cc, P, 1, 1)):
-            return False
-        return Hh % 8 == 0 and W % 16 == 0 and N * Hh * W * Cc < 2 ** 31
+        return bool(H.lib().lt_sel_bottleneck(self.code, H.dims(x.shape), (H.WShape * 3)(*map(H.wshape, convs)), H.i3(strides)))
 
     def bottleneck(self, x, convs, bns):
         """relu(bn3(conv1x1(relu(bn2(conv3x3(relu(bn1(conv1x1(x)))))))) + x) in ONE launch (lt_bottleneck_fwd: the two bottleneck-width tensors
@@ -709,21 +615,11 @@ class PlanBuilder:
 
     # ---- the first Bottleneck of ResNet layer1 (downsample branch, stride 1) in one launch --------------------------------------------------
     def can_bottleneck_ds(self, x, convs, strides, w_down, stride_down):
-        """True when lt_bottleneck_ds_fwd covers the block: bf16 plan over build-time weights, 2D map, stride-1 convolutions 1x1 64->64, 3x3 64->64,
-        1x1 64->256 and a stride-1 1x1 64->256 downsample, H % 8 == 0 and W % 16 == 0 (LT_NO_BNECK_DS=1 or LT_NO_BNECK=1: off -- the A/B switches)."""
-        if (self.dtype != torch.bfloat16 or self.live_weights or self.tile_override or os.environ.get("LT_NO_BNECK") == "1" or
-                os.environ.get("LT_NO_BNECK_DS") == "1"):
+        """True when lt_bottleneck_ds_fwd covers the block with its downsample branch over build-time weights (lt_sel_bottleneck_ds)."""
+        if self.live_weights or self.tile_override or len(convs) != 3:
             return False
-        N, D, Hh, W, Cin = x.shape
-        if D != 1 or len(convs) != 3 or any(s != 1 for s in strides) or stride_down != 1:
-            return False
-        P, Cc = convs[0].shape[0], convs[2].shape[0]
-        if (Cin, P, Cc) != (64, 64, 256):
-            return False
-        if (tuple(convs[0].shape) != (P, Cin, 1, 1) or tuple(convs[1].shape) != (P, P, 3, 3) or tuple(convs[2].shape) != (Cc, P, 1, 1) or
-                tuple(w_down.shape) != (Cc, Cin, 1, 1)):
-            return False
-        return Hh % 8 == 0 and W % 16 == 0 and N * Hh * W * Cc < 2 ** 31
+        return bool(H.lib().lt_sel_bottleneck_ds(self.code, H.dims(x.shape), (H.WShape * 3)(*map(H.wshape, convs)), H.i3(strides), H.wshape(w_down),
+                                                  stride_down))
 
     def bottleneck_ds(self, x, convs, bns, w_down, bn_down):
         """relu(bn3(conv1x1(relu(bn2(conv3x3(relu(bn1(conv1x1(x)))))))) + bn_d(conv1x1_d(x))) in ONE launch (lt_bottleneck_ds_fwd): the two bottleneck-width
@@ -767,22 +663,10 @@ class PlanBuilder:
 
     # ---- the seam between two identity Bottleneck blocks in one launch (ResNet layer3): expand of block i + reduce of block i + 1 -----------
     def can_expand_reduce(self, t2, res, w_expand, w_reduce):
-        """True when lt_expand_reduce_fwd covers the seam: bf16 plan over build-time weights, 2D maps, 1x1 P -> C expand with a C-channel residual and
-        1x1 C -> P reduce with (C, P) = (1024, 256) (LT_NO_XR=1: off -- the A/B switch)."""
-        if self.dtype != torch.bfloat16 or self.live_weights or self.tile_override or os.environ.get("LT_NO_XR") == "1":
+        """True when lt_expand_reduce_fwd covers the seam between two identity Bottlenecks over build-time weights (lt_sel_expand_reduce)."""
+        if self.live_weights or self.tile_override:
             return False
-        if t2.shape[1] != 1 or res.shape[1] != 1 or tuple(t2.shape[:4]) != tuple(res.shape[:4]):
-            return False
-        P, Cc = t2.shape[-1], res.shape[-1]
-        if (Cc, P) != (1024, 256):
-            return False
-        # one tile per workgroup and one workgroup per CU.  With 96-row tiles only, 1 / 2 samples (24 / 48 tiles) lost 8 % / 2.5 % end to end to the two
-        # launches (144-row tiles x 4 column tiles, two workgroups per CU) and the builder fused from 64 tiles on; the launcher now picks 64- and 32-row tiles
-        # for small row counts (measured, forward samples/s, 96 / 64 / 32-row tiles / two launches: 1 sample 277 / 286 / 297 / 301, 2 samples 446 / 461 / 470 /
-        # 454, 5 samples 857 / 876 / 836 / 827, 10 samples 1186 / 1135 / 1122 / 1104), so the seam is fused from 2 samples = 36 tiles of 96 rows on
-        if t2.shape[0] * t2.shape[2] * t2.shape[3] < 36 * 96 and os.environ.get("LT_XR_ANY_SIZE") != "1":
-            return False
-        return tuple(w_expand.shape) == (Cc, P, 1, 1) and tuple(w_reduce.shape) == (P, Cc, 1, 1)
+        return bool(H.lib().lt_sel_expand_reduce(self.code, H.dims(t2.shape), H.dims(res.shape), H.wshape(w_expand), H.wshape(w_reduce)))
 
     def expand_reduce(self, t2, res, w_expand, bn_expand, w_reduce, bn_reduce):
         """y = relu(bn3(conv1x1(t2)) + res) and t1' = relu(bn1'(conv1x1'(y))) in ONE launch (lt_expand_reduce_fwd: the reduce consumes y from LDS).
@@ -821,11 +705,8 @@ class PlanBuilder:
         return y, t1
 
     def can_stem_pool(self, x, weight, stride, pad, pool):
-        """True when lt_stem_pool_fwd covers conv -> BN -> ReLU -> max pool: bf16 plan, 2D map with 8 (padded) channels,
-        7x7 / stride 2 / pad 3 convolution to 64 channels, 3x3 / stride 2 / pad 1 pool."""
-        return (self.dtype == torch.bfloat16 and x.shape[1] == 1 and x.shape[-1] == 8 and weight.dim() == 4
-                and tuple(weight.shape[2:]) == (7, 7) and weight.shape[0] == 64 and weight.shape[1] <= 8
-                and stride == 2 and pad == 3 and tuple(pool) == (3, 2, 1))
+        """True when lt_stem_pool_fwd covers conv -> BN -> ReLU -> max pool (lt_sel_stem_pool)."""
+        return bool(H.lib().lt_sel_stem_pool(self.code, H.dims(x.shape), H.wshape(weight), stride, pad, H.i3(pool)))
 
     def stem_pool(self, x, weight, bn, image_cell=None):
         """conv 7x7/2 (no bias) + eval BN + ReLU + max pool 3x3/2 in one pass (lt_stem_pool_fwd).  x: Act [N,1,H,W,8];

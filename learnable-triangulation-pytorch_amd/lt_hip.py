@@ -49,6 +49,20 @@ class ConvCat2(C.Structure):
     _fields_ = [("x", vp), ("cin", i32), ("H", i32), ("W", i32), ("stride", i32)]
 
 
+class WShape(C.Structure):
+    _fields_ = [("nd", i32), ("s", i64 * 5)]
+
+
+def wshape(t):
+    """lt_wshape of a weight tensor (any device, the meta device included: only its shape is read)."""
+    return WShape(t.dim(), (i64 * 5)(*t.shape))
+
+
+def dims(shape):
+    """(N, D, H, W, C) of a channels-last activation as the int32[5] the lt_sel_* rules take."""
+    return (i32 * 5)(*shape)
+
+
 PWCHAIN_MAX = 3
 
 
@@ -108,6 +122,15 @@ SIGNATURES = {
     "lt_conv_cat2_fwd": (C.c_int, [C.POINTER(ConvDesc), vp, C.POINTER(ConvCat2), vp, vp, vp, vp, vp, vp]),
     "lt_conv_cout_pad": (C.c_int, [i32]),
     "lt_conv_chunk_samples": (i32, [i32, i64]),
+    "lt_sel_conv_skip": (C.c_int, [i32, i32 * 5, C.POINTER(WShape), i32 * 5, C.POINTER(WShape)]),
+    "lt_sel_conv_cat2": (C.c_int, [i32, i32 * 5, C.POINTER(WShape), i32 * 5, C.POINTER(WShape), i32]),
+    "lt_sel_splitk_slices": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(WShape), i32]),
+    "lt_sel_bottleneck": (C.c_int, [i32, i32 * 5, WShape * 3, i32 * 3]),
+    "lt_sel_bottleneck_ds": (C.c_int, [i32, i32 * 5, WShape * 3, i32 * 3, C.POINTER(WShape), i32]),
+    "lt_sel_expand_reduce": (C.c_int, [i32, i32 * 5, i32 * 5, C.POINTER(WShape), C.POINTER(WShape)]),
+    "lt_sel_stem_pool": (C.c_int, [i32, i32 * 5, C.POINTER(WShape), i32, i32, i32 * 3]),
+    "lt_sel_pwchain": (C.c_int, [i32, i32 * 5, i32, C.POINTER(WShape)]),
+    "lt_sel_frag_layout": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(WShape), i32, i32]),
     "lt_conv_pack_weights": (C.c_int, [vp, i32, i32, vp, vp]),
     "lt_conv_pack_weights_t32": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
     "lt_conv_pack_weights32": (C.c_int, [vp, i32, i32, vp, vp]),
