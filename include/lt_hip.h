@@ -472,6 +472,17 @@ int lt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
  * of the (2NV x 4) system by Jacobi eigen-iteration on A^T A in fp64. */
 int lt_triangulate_dlt(const float* proj, const float* points, const float* conf, float* out, int32_t B, int32_t NV,
                        int32_t J, void* stream);
+/* AlgebraicTriangulationNet after the 2D soft-argmax (reference triangulation.py:166-193), every (sample, joint) in one launch:
+ *   confidences = raw / (sum of raw over the views) + 1e-5   (raw: conf_raw[(b * NV + v) * ld_conf + j], the alg_confidences head's sigmoid
+ *                                                             outputs; conf_raw NULL = uniform 1, i.e. 1 / NV + 1e-5)
+ *   keypoints_2d = keypoints_hm * (scale_x, scale_y)          (heatmap -> image pixels; pass f32(W / w), f32(H / h))
+ *   keypoints_3d = the DLT of lt_triangulate_dlt on (keypoints_2d, confidences)
+ * keypoints_hm B*NV,J,2 (lt_softargmax2d_fwd's coords); proj B,NV,3,4 at image resolution; outputs keypoints_2d B,NV,J,2 and confidences
+ * B,NV,J (either may be NULL), keypoints_3d B,J,3.  Bit-identical to the torch sequence conf / conf.sum(1) + 1e-5, kp * scale,
+ * lt_triangulate_dlt: one IEEE rounding per step, no contraction, the view sum in the order of torch's GPU reduction (four
+ * interleaved partial sums, view v into partial v % 4; plain view order up to four views).  NV >= 2. */
+int lt_alg_tail_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                    float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV, int32_t J, void* stream);
 
 /* RANSACTriangulationNet (reference mvn/models/triangulation.py:17-128), 2D part: the backbone's N,h,w,(ld) fp32 heatmaps ->
  * heatmaps_nchw N,J,h,w (the raw heatmaps the model returns, bit-identical to lt_nhwc_to_nchw_f32) and, in the same pass, the argmax
@@ -633,7 +644,8 @@ int lt_event_destroy(void* ev);
 
 /* ---------------------------------------------------------------------------------------------
  * PLAN-LEVEL entry points ("whole-network plan entry points that own pre-packed weights and a hipGraph"; round 6).
- * Everything the Python host does between the reference's module API and the kernel-level calls above lives behind these four symbols, so that a
+ * Everything the Python host does between the reference's module API and the kernel-level calls above lives behind these six symbols, for all three
+ * of the reference's models (volumetric: _vol; algebraic and RANSAC: _alg; lt_plan_info / lt_plan_destroy: any plan), so that a
  * host in any language can run the timed forward: layer -> kernel selection with every batch threshold (fused stem, whole-bottleneck launches, the
  * layer3 seam kernel, conv_cat2, the 2D / 3D halo kernels by weight layout, split-K of the tiny V2V levels, the pointwise tail), the eval-BatchNorm fold
  * as ATen evaluates it, weight packing (GEMM layout, MFMA fragment orders, parity phases of the stride-2 transposed convolutions), buffer reuse, the
@@ -658,6 +670,19 @@ int lt_event_destroy(void* ev);
  *   reference's 7-tuple are host values the caller already has.  Asynchronous; the first call captures the hipGraph (use_graph), later calls replay it.
  *   stream == NULL with use_graph: the legacy default stream cannot be captured, so the forward runs on a stream the plan owns, ordered behind the default
  *   stream's earlier work and in front of its later work by events.  Not thread-safe per plan (one forward of a plan at a time).
+ * lt_plan_create_alg  = AlgebraicTriangulationNet (reference triangulation.py:131-200, cfg.model = LT_MODEL_ALG) or RANSACTriangulationNet (:17-128,
+ *                       LT_MODEL_RANSAC, eval only) + load_state_dict + the plan recording.  weights as for lt_plan_create_vol; ALG reads the backbone with
+ *   backbone.final_layer.* and, with use_confidences, backbone.alg_confidences.*; RANSAC the backbone with backbone.final_layer.*.  Config errors (model,
+ *   dtype, shape, RANSAC's num_joints <= 32 and 2 <= NV <= 32) are LT_ERR_INVALID before any device call.  The captured part is the backbone with
+ *   final_layer (and the confidence head) and the heatmaps' NCHW pass (RANSAC: lt_heatmap_argmax_nchw_f32); the tail runs eagerly on every call
+ *   (ALG: lt_softargmax2d_fwd + lt_alg_tail_fwd; RANSAC: lt_triangulate_ransac over every view pair), so the graph holds no caller pointer.
+ * lt_plan_forward_alg = the eval forward of that model.  images: DEVICE (B, NV, 3, H, W) fp32; proj: DEVICE fp32 (B, NV, 3, 4), the reference's
+ *   proj_matricies_batch at image resolution.  Outputs, DEVICE, written on `stream`; all but keypoints_3d may be NULL:
+ *     ALG     keypoints_3d (B, J, 3) fp32; keypoints_2d (B, NV, J, 2) fp32 image pixels; heatmaps (B, NV, J, h, w) after integrate_tensor_2d
+ *             (softmax or ReLU-normalised); confidences (B, NV, J) normalised over the views + 1e-5 (uniform 1 / NV + 1e-5 without the head).
+ *     RANSAC  keypoints_3d (B, J, 3) fp32; keypoints_2d (B, NV, J, 2) INT64 argmax pixels; heatmaps (B, NV, J, h, w) raw; confidences zeros.
+ *   Streams, graph capture and threading as lt_plan_forward_vol.  lt_plan_forward_vol on an algebraic / RANSAC plan and lt_plan_forward_alg on a
+ *   volumetric plan are LT_ERR_INVALID.  lt_plan_info describes any plan: the census fields count the backbone's fused kernels (the V2V ones are 0).
  * -------------------------------------------------------------------------------------------*/
 typedef struct lt_plan lt_plan;
 typedef struct lt_named_tensor {
@@ -693,6 +718,24 @@ typedef struct lt_plan_info_t {
 int lt_plan_create_vol(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out);
 int lt_plan_forward_vol(lt_plan* plan, const float* images, const double* K_host, const double* R_host, const double* t_host, const double* base_points_host,
                         const double* rot_host, float* keypoints_3d, float* volumes, float* features, float* coord_volumes, float* vol_confidences, void* stream);
+enum { LT_MODEL_ALG = 1, LT_MODEL_RANSAC = 2 };
+typedef struct lt_alg_plan_config {
+    int32_t model;                        /* LT_MODEL_ALG (AlgebraicTriangulationNet) | LT_MODEL_RANSAC (RANSACTriangulationNet, eval only) */
+    int32_t dtype;                        /* LT_F32 | LT_BF16 */
+    int32_t num_layers;                   /* config.model.backbone.num_layers: 18 | 34 | 50 | 101 | 152 */
+    int32_t style_caffe;                  /* config.model.backbone.style == "caffe" */
+    int32_t num_joints;                   /* 17 */
+    int32_t B, NV, H, W;                  /* samples, views per sample, image size */
+    int32_t use_confidences;              /* ALG: config.model.use_confidences (the alg_confidences head) */
+    int32_t heatmap_softmax;              /* ALG: config.model.heatmap_softmax */
+    double heatmap_multiplier;            /* ALG: config.model.heatmap_multiplier */
+    int32_t direct_optimization;          /* RANSAC: config.model.direct_optimization */
+    double reprojection_error_epsilon;    /* RANSAC: 15 in the reference */
+    int32_t use_graph;                    /* capture the forward into a hipGraph at the first call and replay it */
+} lt_alg_plan_config;
+int lt_plan_create_alg(const lt_alg_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out);
+int lt_plan_forward_alg(lt_plan* plan, const float* images, const float* proj, float* keypoints_3d, void* keypoints_2d, float* heatmaps,
+                        float* confidences, void* stream);
 int lt_plan_info(const lt_plan* plan, lt_plan_info_t* info);
 void lt_plan_destroy(lt_plan* plan);
 

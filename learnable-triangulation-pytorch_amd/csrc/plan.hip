@@ -1,14 +1,18 @@
 // Plan-level entry points of the C ABI ("whole-network plan entry points that own pre-packed weights and a hipGraph"):
-//   lt_plan_create_vol / lt_plan_forward_vol / lt_plan_info / lt_plan_destroy
+//   lt_plan_create_vol / lt_plan_forward_vol          VolumetricTriangulationNet
+//   lt_plan_create_alg / lt_plan_forward_alg          AlgebraicTriangulationNet (LT_MODEL_ALG) and RANSACTriangulationNet (LT_MODEL_RANSAC)
+//   lt_plan_info / lt_plan_destroy                    any plan
 // A non-Python host hands over the reference's state_dict (names + host fp32 arrays) and the model configuration once, and then calls the forward with
 // device images and host camera parameters: layer -> kernel selection, every batch threshold, the eval-BatchNorm fold, weight packing (GEMM layout,
 // MFMA fragment orders, parity phases of the transposed convolutions, split-K tap groups), buffer reuse and the captured hipGraph all live behind this
 // file -- the same recording lt_engine.py / mvn/models/*.py do when the Python modules record their plan, by the same kernel-selection rules (lt_sel_*,
 // select.hip: both hosts call them); tests/test_gpu_plan_abi.py holds the two against each other and against the reference's golden outputs.
 //
-// What it replaces in the reference (file:line): VolumetricTriangulationNet.__init__ / forward (mvn/models/triangulation.py:204-355), PoseResNet
-// (mvn/models/pose_resnet.py:57-318: Bottleneck / BasicBlock / Bottleneck_CAFFE, _make_layer, _make_deconv_layer, GlobalAveragePoolingHead), V2VModel
-// (mvn/models/v2v.py:7-180), Camera.update_after_resize / projection (mvn/utils/multiview.py:33-52), the cuboid of triangulation.py:281-341.
+// What it replaces in the reference (file:line): VolumetricTriangulationNet.__init__ / forward (mvn/models/triangulation.py:204-355),
+// AlgebraicTriangulationNet (:131-200) and RANSACTriangulationNet (:17-128) in eval mode, PoseResNet (mvn/models/pose_resnet.py:57-318: Bottleneck /
+// BasicBlock / Bottleneck_CAFFE, _make_layer, _make_deconv_layer, final_layer, GlobalAveragePoolingHead), V2VModel (mvn/models/v2v.py:7-180),
+// Camera.update_after_resize / projection (mvn/utils/multiview.py:33-52), the cuboid of triangulation.py:281-341.  All three models record their backbone
+// through the one record_backbone below.
 //
 // Host-only code (no kernel here): every launch goes through the kernel-level entry points of include/lt_hip.h.
 #include <math.h>
@@ -218,7 +222,10 @@ int make_conv_spec(const WT& w, const float* bias, const BN* bn, const int in[5]
 
 // =====================================================================================================================================
 struct lt_plan {
-    lt_vol_plan_config cfg;
+    lt_vol_plan_config cfg;                     // volumetric plans; the algebraic / RANSAC plans fill the fields they share (shape, dtype, use_graph)
+    int model = 0;                              // 0: volumetric plan, else LT_MODEL_ALG | LT_MODEL_RANSAC (acfg)
+    lt_alg_plan_config acfg = {};
+    const char* who = "lt_plan_create_vol";     // the entry point that builds the plan, for error messages
     int dtype = LT_F32, es = 4;                 // element type / size of activations and weights
     std::unordered_map<std::string, const lt_named_tensor*> sd;
     std::vector<void*> allocs;                  // every hipMalloc of the plan
@@ -242,12 +249,15 @@ struct lt_plan {
     // per-call pointers the pre / tail ops read
     const float* cur_images = nullptr;
     float* out_kp = nullptr; float* out_probs = nullptr; float* out_feats = nullptr;
+    const float* cur_proj = nullptr; void* out_kp2d = nullptr; float* out_hm = nullptr; float* out_conf = nullptr;          // algebraic / RANSAC plans
     // geometry block (fp32): proj B*NV*12 | pos B*3 | center B*3 | rot B*9 -- one H2D copy per forward from a ring of pinned blocks
     float* geo_dev = nullptr; float* geo_host[GEO_RING] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t geo_ev[GEO_RING] = {nullptr, nullptr, nullptr, nullptr};
     int geo_slot = 0; size_t n_geo = 0, o_pos = 0, o_cen = 0, o_rot = 0;
     // results
     Act feats, vol, logits, volc;
     float* coords = nullptr; float* kp = nullptr; float* probs = nullptr; void* sa_ws = nullptr;
+    Act algc;                                   // alg_confidences head output [1,1,1,N,J] fp32 (algebraic plans with use_confidences)
+    float* hm_nchw = nullptr; float* kp_hm = nullptr; int64_t* kp_i64 = nullptr;          // heatmaps N,J,h,w; soft-argmax N,J,2 (heatmap px); argmax N,J,2
     int hm_h = 0, hm_w = 0;
     int n_xr = 0, n_bneck = 0, n_bneck_ds = 0, n_cat2 = 0, n_halo2d = 0, n_pwchain = 0, n_stem = 0, n_splitk = 0, n_conv_skip = 0;
 
@@ -294,9 +304,9 @@ struct lt_plan {
     // ---- state dict ----------------------------------------------------------------------------------------------------------------
     int get(const std::string& name, WT& w, int nd_expect = 0) {
         auto it = sd.find(name);
-        LT_REQUIRE(it != sd.end(), LT_ERR_INVALID, "lt_plan_create_vol: state dict has no '%s'", name.c_str());
+        LT_REQUIRE(it != sd.end(), LT_ERR_INVALID, "%s: state dict has no '%s'", who, name.c_str());
         const lt_named_tensor* t = it->second;
-        LT_REQUIRE(t->data && t->ndim >= 1 && t->ndim <= 5 && (!nd_expect || t->ndim == nd_expect), LT_ERR_INVALID, "lt_plan_create_vol: '%s' has %d dimensions", name.c_str(), t->ndim);
+        LT_REQUIRE(t->data && t->ndim >= 1 && t->ndim <= 5 && (!nd_expect || t->ndim == nd_expect), LT_ERR_INVALID, "%s: '%s' has %d dimensions", who, name.c_str(), t->ndim);
         w.d = t->data; w.nd = t->ndim;
         for (int i = 0; i < t->ndim; ++i) w.s[i] = t->shape[i];
         return LT_OK;
@@ -304,7 +314,7 @@ struct lt_plan {
     bool has(const std::string& name) const { return sd.find(name) != sd.end(); }
     int get_vec(const std::string& name, int n, const float** out) {
         WT w; PL_TRY(get(name, w));
-        LT_REQUIRE(w.numel() == n, LT_ERR_INVALID, "lt_plan_create_vol: '%s' has %lld elements, expected %d", name.c_str(), (long long)w.numel(), n);
+        LT_REQUIRE(w.numel() == n, LT_ERR_INVALID, "%s: '%s' has %lld elements, expected %d", who, name.c_str(), (long long)w.numel(), n);
         *out = w.d;
         return LT_OK;
     }
@@ -734,19 +744,18 @@ struct lt_plan {
         return LT_OK;
     }
 
-    // PoseResNet.record without the (dead in the volumetric path) heatmap layer: stem, four stages, optional vol_confidences head, three 4x4 / stride-2 deconvolutions
-    int record_backbone(Act& feats256, Act& volconf) {
-        const int N = cfg.B * cfg.NV, Hh = cfg.H, W = cfg.W;
+    // PoseResNet.record: stem, four stages, the optional confidence head conf_head ("backbone.alg_confidences" / "backbone.vol_confidences", or null), three
+    // 4x4 / stride-2 deconvolutions (feats256) and, with want_heatmaps, final_layer (1x1 to J channels, fp32 output; dead in the volumetric path)
+    int record_backbone(int N, int Hh, int W, int num_layers, bool caffe, const char* conf_head, bool want_heatmaps, Act& feats256, Act& conf, Act& heatmaps) {
         int nb[4]; bool bott;
-        switch (cfg.num_layers) {
+        switch (num_layers) {
             case 18: bott = false; nb[0] = 2; nb[1] = 2; nb[2] = 2; nb[3] = 2; break;
             case 34: bott = false; nb[0] = 3; nb[1] = 4; nb[2] = 6; nb[3] = 3; break;
             case 50: bott = true; nb[0] = 3; nb[1] = 4; nb[2] = 6; nb[3] = 3; break;
             case 101: bott = true; nb[0] = 3; nb[1] = 4; nb[2] = 23; nb[3] = 3; break;
             case 152: bott = true; nb[0] = 3; nb[1] = 8; nb[2] = 36; nb[3] = 3; break;
-            default: set_error("lt_plan_create_vol: num_layers %d (18 / 34 / 50 / 101 / 152)", cfg.num_layers); return LT_ERR_INVALID;
+            default: set_error("%s: num_layers %d (18 / 34 / 50 / 101 / 152)", who, num_layers); return LT_ERR_INVALID;
         }
-        const bool caffe = cfg.style_caffe != 0;
         if (caffe) bott = true;          // the reference swaps in Bottleneck_CAFFE (expansion 4) at EVERY depth (pose_resnet.py:322-324)
         const int exp = bott ? 4 : 1;
         WT w1; BN bn1;
@@ -792,20 +801,27 @@ struct lt_plan {
                 y = z; t1 = t1n; have_t1 = !t1n.null();
             }
         }
-        volconf = Act();
-        if (cfg.aggregation == LT_AGG_CONF || cfg.aggregation == LT_AGG_CONF_NORM) PL_TRY(record_gap_head("backbone.vol_confidences", y, volconf));
+        conf = Act();
+        if (conf_head) PL_TRY(record_gap_head(conf_head, y, conf));
         for (int i = 0; i < 3; ++i) {
             WT dw; BN dbn;
             PL_TRY(get("backbone.deconv_layers." + std::to_string(3 * i) + ".weight", dw, 4));
             PL_TRY(get_bn("backbone.deconv_layers." + std::to_string(3 * i + 1), (int)dw.s[1], dbn));
             const float* db = nullptr;
             if (has("backbone.deconv_layers." + std::to_string(3 * i) + ".bias")) PL_TRY(get_vec("backbone.deconv_layers." + std::to_string(3 * i) + ".bias", (int)dw.s[1], &db));
-            LT_REQUIRE(dw.s[2] == 4 && dw.s[3] == 4, LT_ERR_UNSUPPORTED, "lt_plan_create_vol: only the 4x4 stride-2 deconvolution of the reference configs");
+            LT_REQUIRE(dw.s[2] == 4 && dw.s[3] == 4, LT_ERR_UNSUPPORTED, "%s: only the 4x4 stride-2 deconvolution of the reference configs", who);
             ConvOpt o; o.bias = db; o.bn = &dbn; o.stride = 2; o.pad = 1; o.transposed = true; o.relu = true;
             Act z; PL_TRY(conv(y, dw, o, z)); release(y);
             y = z;
         }
         feats256 = y;
+        heatmaps = Act();
+        if (want_heatmaps) {
+            WT fw; const float* fb;
+            PL_TRY(get("backbone.final_layer.weight", fw, 4)); PL_TRY(get_vec("backbone.final_layer.bias", (int)fw.s[0], &fb));
+            ConvOpt o; o.bias = fb; o.pad = fw.s[2] == 3 ? 1 : 0; o.out_f32 = true;          // pose_resnet.py: padding 1 for final_conv_kernel 3, else 0
+            PL_TRY(conv(y, fw, o, heatmaps));
+        }
         return LT_OK;
     }
 
@@ -889,8 +905,9 @@ struct lt_plan {
     // VolumetricTriangulationNet._build_plan
     int build() {
         const int B = cfg.B, NV = cfg.NV, V = cfg.volume_size, J = cfg.num_joints;
-        Act f256;
-        PL_TRY(record_backbone(f256, volc));
+        Act f256, no_hm;
+        const bool conf_head = cfg.aggregation == LT_AGG_CONF || cfg.aggregation == LT_AGG_CONF_NORM;
+        PL_TRY(record_backbone(B * NV, cfg.H, cfg.W, cfg.num_layers, cfg.style_caffe != 0, conf_head ? "backbone.vol_confidences" : nullptr, false, f256, volc, no_hm));
         WT pw; const float* pb;
         PL_TRY(get("process_features.0.weight", pw, 4)); PL_TRY(get_vec("process_features.0.bias", (int)pw.s[0], &pb));
         LT_REQUIRE(pw.s[0] == 32, LT_ERR_UNSUPPORTED, "lt_plan_create_vol: process_features has %d output channels (32)", (int)pw.s[0]);
@@ -933,6 +950,70 @@ struct lt_plan {
         return LT_OK;
     }
 
+    // AlgebraicTriangulationNet._build_plan / RANSACTriangulationNet._build_plan.  Captured: the backbone with final_layer (and the alg_confidences head),
+    // then the heatmaps to NCHW (ALG: lt_nhwc_to_nchw_f32; RANSAC: lt_heatmap_argmax_nchw_f32, which also writes the int64 argmax keypoints).  Tail, eager on
+    // every call because it reads the caller's proj and writes the caller's outputs: ALG lt_softargmax2d_fwd + lt_alg_tail_fwd, RANSAC lt_triangulate_ransac.
+    int build_alg() {
+        const lt_alg_plan_config& c = acfg;
+        const int B = c.B, NV = c.NV, N = B * NV, J = c.num_joints, Hh = c.H, W = c.W;
+        const bool ransac = c.model == LT_MODEL_RANSAC;
+        Act f256, hm;
+        PL_TRY(record_backbone(N, Hh, W, c.num_layers, c.style_caffe != 0, !ransac && c.use_confidences ? "backbone.alg_confidences" : nullptr, true, f256, algc, hm));
+        release(f256);
+        LT_REQUIRE(hm.c == J, LT_ERR_INVALID, "%s: backbone.final_layer has %d output channels, num_joints is %d", who, hm.c, J);
+        hm_h = hm.h; hm_w = hm.w;
+        const int h = hm_h, w = hm_w;
+        void* q;
+        PL_TRY(dev_alloc((size_t)N * J * h * w * 4, &q)); hm_nchw = (float*)q;
+        const float* hp = (const float*)hm.p; float* hn = hm_nchw; lt_plan* self = this;
+        if (ransac) {
+            PL_TRY(dev_alloc((size_t)N * J * 2 * 8, &q)); kp_i64 = (int64_t*)q;
+            const int ld = hm.c; int64_t* kpp = kp_i64;
+            ops.push_back([=](hipStream_t s) { return lt_heatmap_argmax_nchw_f32(hp, ld, hn, nullptr, kpp, N, J, h, w, Hh, W, s); });
+            // tail: every view pair as a hypothesis (pairs = NULL), as RANSACTriangulationNet.forward
+            const double eps = c.reprojection_error_epsilon; const int direct = c.direct_optimization ? 1 : 0;
+            ops.push_back([=](hipStream_t s) { return lt_triangulate_ransac(self->cur_proj, kpp, nullptr, 0, eps, direct, self->out_kp, nullptr, B, NV, J, s); });
+            ntail = 1;
+            return LT_OK;
+        }
+        ops.push_back([=](hipStream_t s) { return lt_nhwc_to_nchw_f32(LT_F32, hp, hn, N, J, h * w, J, s); });
+        PL_TRY(dev_alloc((size_t)N * J * 2 * 4, &q)); kp_hm = (float*)q;
+        PL_TRY(dev_alloc((size_t)N * J * h * w * 4, &q)); probs = (float*)q;
+        {   // tail op 1: integrate_tensor_2d, the normalised heatmaps straight into the caller's tensor
+            const float mult = (float)c.heatmap_multiplier; const int sm = c.heatmap_softmax ? 1 : 0; float* kh = kp_hm; float* pr = probs;
+            ops.push_back([=](hipStream_t s) { return lt_softargmax2d_fwd(hn, mult, sm, kh, self->out_hm ? self->out_hm : pr, N * J, h, w, s); });
+        }
+        {   // tail op 2: confidences normalised over the views, keypoints to image pixels, the DLT (triangulation.py:166-193)
+            const float sx = (float)((double)W / (double)w), sy = (float)((double)Hh / (double)h);          // torch.tensor([W / w, H / h], float32)
+            const float* kh = kp_hm; const float* cp = algc.null() ? nullptr : (const float*)algc.p; const int ldc = algc.null() ? J : algc.c;
+            ops.push_back([=](hipStream_t s) {
+                return lt_alg_tail_fwd(kh, cp, ldc, self->cur_proj, sx, sy, (float*)self->out_kp2d, self->out_conf, self->out_kp, B, NV, J, s);
+            });
+        }
+        ntail = 2;
+        return LT_OK;
+    }
+
+    // stream == NULL with use_graph: the plan's own stream, ordered behind what the default stream has queued so far (enter) and in front of what it gets next (leave)
+    int enter(hipStream_t& st, bool& detour) {
+        detour = st == nullptr && cfg.use_graph;
+        if (!detour) return LT_OK;
+        if (!own_stream) {
+            PL_HIP(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
+            for (int i = 0; i < 2; ++i) PL_HIP(hipEventCreateWithFlags(&own_ev[i], hipEventDisableTiming));
+        }
+        PL_HIP(hipEventRecord(own_ev[0], nullptr));
+        PL_HIP(hipStreamWaitEvent(own_stream, own_ev[0], 0));
+        st = own_stream;
+        return LT_OK;
+    }
+    int leave(hipStream_t st, bool detour) {
+        if (!detour) return LT_OK;
+        PL_HIP(hipEventRecord(own_ev[1], st));
+        PL_HIP(hipStreamWaitEvent(nullptr, own_ev[1], 0));
+        return LT_OK;
+    }
+
     int run(hipStream_t st) {
         const int nops = (int)ops.size();
         for (int i = 0; i < npre; ++i) PL_TRY(ops[i](st));
@@ -961,6 +1042,19 @@ struct lt_plan {
     }
 };
 
+namespace {
+// the caller's state dict by name, "module." stripped (DataParallel checkpoints, train.py:408-410); false (and the error set) for an unnamed entry
+bool load_state_dict(lt_plan* p, const lt_named_tensor* weights, int32_t nweights) {
+    for (int i = 0; i < nweights; ++i) {
+        if (!weights[i].name) { set_error("%s: weight %d has no name", p->who, i); return false; }
+        std::string n = weights[i].name;
+        if (n.rfind("module.", 0) == 0) n = n.substr(7);
+        p->sd[n] = &weights[i];
+    }
+    return true;
+}
+}  // namespace
+
 extern "C" int lt_plan_create_vol(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
     LT_REQUIRE(cfg && weights && plan_out && nweights > 0, LT_ERR_INVALID, "lt_plan_create_vol: null argument");
     LT_REQUIRE(cfg->dtype == LT_F32 || cfg->dtype == LT_BF16, LT_ERR_INVALID, "lt_plan_create_vol: dtype %d", cfg->dtype);
@@ -970,12 +1064,7 @@ extern "C" int lt_plan_create_vol(const lt_vol_plan_config* cfg, const lt_named_
     lt_plan* p = new lt_plan();
     p->cfg = *cfg;
     p->dtype = cfg->dtype; p->es = cfg->dtype == LT_F32 ? 4 : 2;
-    for (int i = 0; i < nweights; ++i) {
-        if (!weights[i].name) { delete p; set_error("lt_plan_create_vol: weight %d has no name", i); return LT_ERR_INVALID; }
-        std::string n = weights[i].name;
-        if (n.rfind("module.", 0) == 0) n = n.substr(7);          // DataParallel checkpoints (train.py:408-410)
-        p->sd[n] = &weights[i];
-    }
+    if (!load_state_dict(p, weights, nweights)) { delete p; return LT_ERR_INVALID; }
     const int rc = p->build();
     if (rc != LT_OK) { delete p; return rc; }
     p->sd.clear();          // the caller's host arrays are not referenced after this call
@@ -986,18 +1075,13 @@ extern "C" int lt_plan_create_vol(const lt_vol_plan_config* cfg, const lt_named_
 extern "C" int lt_plan_forward_vol(lt_plan* p, const float* images, const double* K_host, const double* R_host, const double* t_host, const double* base_points_host,
                                    const double* rot_host, float* keypoints_3d, float* volumes, float* features, float* coord_volumes, float* vol_confidences,
                                    void* stream) {
-    LT_REQUIRE(p && images && K_host && R_host && t_host && base_points_host && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_vol: null argument");
+    LT_REQUIRE(p, LT_ERR_INVALID, "lt_plan_forward_vol: null argument");
+    LT_REQUIRE(p->model == 0, LT_ERR_INVALID, "lt_plan_forward_vol: the plan is an %s plan of lt_plan_create_alg; run it with lt_plan_forward_alg",
+               p->model == LT_MODEL_RANSAC ? "LT_MODEL_RANSAC" : "LT_MODEL_ALG");
+    LT_REQUIRE(images && K_host && R_host && t_host && base_points_host && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_vol: null argument");
     hipStream_t st = (hipStream_t)stream;
-    const bool detour = st == nullptr && p->cfg.use_graph;
-    if (detour) {          // the plan's own stream, ordered behind what the default stream has queued so far
-        if (!p->own_stream) {
-            PL_HIP(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
-            for (int i = 0; i < 2; ++i) PL_HIP(hipEventCreateWithFlags(&p->own_ev[i], hipEventDisableTiming));
-        }
-        PL_HIP(hipEventRecord(p->own_ev[0], nullptr));
-        PL_HIP(hipStreamWaitEvent(p->own_stream, p->own_ev[0], 0));
-        st = p->own_stream;
-    }
+    bool detour;
+    PL_TRY(p->enter(st, detour));
     const int B = p->cfg.B, NV = p->cfg.NV, V = p->cfg.volume_size;
     // ---- host geometry in fp64 like the reference (triangulation.py:272-296): Camera.update_after_resize to the heatmap resolution, projection = K [R | t];
     // cuboid position = base - side / 2; rotation about the vertical axis (identity in eval mode); one pinned block, one H2D copy
@@ -1035,10 +1119,60 @@ extern "C" int lt_plan_forward_vol(lt_plan* p, const float* images, const double
         LT_REQUIRE(!p->volc.null(), LT_ERR_INVALID, "lt_plan_forward_vol: vol_confidences asked of a plan without the confidence head (aggregation %d)", p->cfg.aggregation);
         PL_HIP(hipMemcpyAsync(vol_confidences, p->volc.p, (size_t)B * NV * 32 * 4, hipMemcpyDeviceToDevice, st));          // RAW sigmoid outputs; 'conf_norm' divides by their sum over views
     }
-    if (detour) {          // ... and in front of what the default stream gets next
-        PL_HIP(hipEventRecord(p->own_ev[1], st));
-        PL_HIP(hipStreamWaitEvent(nullptr, p->own_ev[1], 0));
+    PL_TRY(p->leave(st, detour));
+    return LT_OK;
+}
+
+extern "C" int lt_plan_create_alg(const lt_alg_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
+    LT_REQUIRE(cfg && weights && plan_out && nweights > 0, LT_ERR_INVALID, "lt_plan_create_alg: null argument");
+    const lt_alg_plan_config& c = *cfg;
+    LT_REQUIRE(c.model == LT_MODEL_ALG || c.model == LT_MODEL_RANSAC, LT_ERR_INVALID, "lt_plan_create_alg: model %d (LT_MODEL_ALG | LT_MODEL_RANSAC)", c.model);
+    LT_REQUIRE(c.dtype == LT_F32 || c.dtype == LT_BF16, LT_ERR_INVALID, "lt_plan_create_alg: dtype %d", c.dtype);
+    LT_REQUIRE(c.B >= 1 && c.NV >= 2 && c.H >= 32 && c.W >= 32 && c.num_joints >= 1, LT_ERR_INVALID,
+               "lt_plan_create_alg: bad shape (B %d, NV %d, H %d, W %d, num_joints %d; at least 2 views to triangulate, 32 x 32 images)", c.B, c.NV, c.H, c.W, c.num_joints);
+    if (c.model == LT_MODEL_RANSAC) {
+        LT_REQUIRE(c.num_joints <= 32, LT_ERR_INVALID, "lt_plan_create_alg: num_joints %d > 32 (RANSAC's heatmap argmax)", c.num_joints);
+        LT_REQUIRE(c.NV <= 32, LT_ERR_INVALID, "lt_plan_create_alg: NV %d views (RANSAC: 2 <= NV <= 32)", c.NV);
     }
+    *plan_out = nullptr;
+    lt_plan* p = new lt_plan();
+    p->who = "lt_plan_create_alg";
+    p->model = c.model; p->acfg = c;
+    memset(&p->cfg, 0, sizeof(p->cfg));
+    p->cfg.dtype = c.dtype; p->cfg.num_layers = c.num_layers; p->cfg.style_caffe = c.style_caffe; p->cfg.num_joints = c.num_joints;
+    p->cfg.B = c.B; p->cfg.NV = c.NV; p->cfg.H = c.H; p->cfg.W = c.W; p->cfg.use_graph = c.use_graph;
+    p->dtype = c.dtype; p->es = c.dtype == LT_F32 ? 4 : 2;
+    if (!load_state_dict(p, weights, nweights)) { delete p; return LT_ERR_INVALID; }
+    // the heads this model reads besides the backbone, named before any device work
+    std::vector<std::string> heads = {"backbone.final_layer.weight", "backbone.final_layer.bias"};
+    if (c.model == LT_MODEL_ALG && c.use_confidences) heads.push_back("backbone.alg_confidences.head.4.weight");
+    for (const std::string& k : heads)
+        if (!p->has(k)) { set_error("lt_plan_create_alg: state dict has no '%s'", k.c_str()); delete p; return LT_ERR_INVALID; }
+    const int rc = p->build_alg();
+    if (rc != LT_OK) { delete p; return rc; }
+    p->sd.clear();          // the caller's host arrays are not referenced after this call
+    *plan_out = p;
+    return LT_OK;
+}
+
+extern "C" int lt_plan_forward_alg(lt_plan* p, const float* images, const float* proj, float* keypoints_3d, void* keypoints_2d, float* heatmaps,
+                                   float* confidences, void* stream) {
+    LT_REQUIRE(p, LT_ERR_INVALID, "lt_plan_forward_alg: null argument");
+    LT_REQUIRE(p->model != 0, LT_ERR_INVALID, "lt_plan_forward_alg: the plan is a volumetric plan of lt_plan_create_vol; run it with lt_plan_forward_vol");
+    LT_REQUIRE(images && proj && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_alg: null argument (images, proj and keypoints_3d are required)");
+    hipStream_t st = (hipStream_t)stream;
+    bool detour;
+    PL_TRY(p->enter(st, detour));
+    p->cur_images = images; p->cur_proj = proj; p->out_kp = keypoints_3d;
+    p->out_kp2d = keypoints_2d; p->out_hm = heatmaps; p->out_conf = confidences;
+    PL_TRY(p->run(st));
+    if (p->model == LT_MODEL_RANSAC) {          // the raw heatmaps and int64 keypoints the plan wrote, and the reference's zero confidences
+        const size_t nj = (size_t)p->acfg.B * p->acfg.NV * p->acfg.num_joints;
+        if (heatmaps) PL_HIP(hipMemcpyAsync(heatmaps, p->hm_nchw, nj * p->hm_h * p->hm_w * 4, hipMemcpyDeviceToDevice, st));
+        if (keypoints_2d) PL_HIP(hipMemcpyAsync(keypoints_2d, p->kp_i64, nj * 2 * 8, hipMemcpyDeviceToDevice, st));
+        if (confidences) PL_HIP(hipMemsetAsync(confidences, 0, nj * 4, st));
+    }
+    PL_TRY(p->leave(st, detour));
     return LT_OK;
 }
 

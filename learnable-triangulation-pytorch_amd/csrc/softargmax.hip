@@ -1,5 +1,5 @@
-// Soft-argmax reductions (3D: op.integrate_tensor_3d_with_coordinates, 2D: op.integrate_tensor_2d) and
-// the confidence-weighted DLT (multiview.triangulate_batch_of_points).
+// Soft-argmax reductions (3D: op.integrate_tensor_3d_with_coordinates, 2D: op.integrate_tensor_2d),
+// the confidence-weighted DLT (multiview.triangulate_batch_of_points) and the algebraic model's tail after the 2D soft-argmax.
 //
 // 3D soft-argmax is HBM-bound: read J x V^3 logits (twice: statistics, then normalise) and write the
 // J x V^3 probabilities the API returns.  One lane owns one voxel and walks the J joints with an online
@@ -380,25 +380,23 @@ __global__ __launch_bounds__(256) void sa2_kernel(const float* __restrict__ hm, 
 }
 
 // ---- DLT: one lane per (sample, joint) ----------------------------------------------------------
-__global__ void dlt_kernel(const float* __restrict__ proj, const float* __restrict__ pts, const float* __restrict__ conf,
-                           float* __restrict__ out, int B, int NV, int J) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= B * J) return;
-    const int b = g / J, j = g - b * J;
-    double Mx[4][4] = {};
-    for (int v = 0; v < NV; ++v) {  // rows of A, multiview.py:159-161, accumulated into A^T A
-        const float* P = proj + ((long long)b * NV + v) * 12;
-        const float* p = pts + (((long long)b * NV + v) * J + j) * 2;
-        const float c = conf ? conf[((long long)b * NV + v) * J + j] : 1.f;
-        for (int r = 0; r < 2; ++r) {
-            float arow[4];
-            for (int k = 0; k < 4; ++k) arow[k] = (P[8 + k] * p[r] - P[4 * r + k]) * c;  // fp32 like the reference
-            for (int i = 0; i < 4; ++i)
-                for (int k = 0; k < 4; ++k) Mx[i][k] += (double)arow[i] * (double)arow[k];
-        }
+// The per-lane routine every DLT kernel here shares (forward, algebraic tail, backward), so that they solve the same system with the same
+// instruction sequence.  dlt_accumulate: one view's two rows of A (multiview.py:159-161), fp32 like the reference, accumulated into A^T A in fp64.
+__device__ __forceinline__ void dlt_accumulate(double (&Mx)[4][4], const float* __restrict__ P, const float x, const float y, const float c) {
+    const float p[2] = {x, y};
+    for (int r = 0; r < 2; ++r) {
+        float arow[4];
+        for (int k = 0; k < 4; ++k) arow[k] = (P[8 + k] * p[r] - P[4 * r + k]) * c;  // fp32 like the reference
+        for (int i = 0; i < 4; ++i)
+            for (int k = 0; k < 4; ++k) Mx[i][k] += (double)arow[i] * (double)arow[k];
     }
-    // cyclic Jacobi on the symmetric 4x4; eigenvector of the smallest eigenvalue = last right singular vector
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+}
+
+// cyclic Jacobi on the symmetric 4x4 A^T A (diagonalised in place, eigenvectors in the columns of V); returns the column of the smallest
+// eigenvalue = the last right singular vector of A
+__device__ __forceinline__ int dlt_jacobi(double (&Mx)[4][4], double (&V)[4][4]) {
+    for (int i = 0; i < 4; ++i)
+        for (int k = 0; k < 4; ++k) V[i][k] = i == k ? 1.0 : 0.0;
     for (int sweep = 0; sweep < 16; ++sweep) {
         double off = 0;
         for (int p = 0; p < 4; ++p)
@@ -427,9 +425,58 @@ __global__ void dlt_kernel(const float* __restrict__ proj, const float* __restri
     int best = 0;
     for (int i = 1; i < 4; ++i)
         if (Mx[i][i] < Mx[best][best]) best = i;
+    return best;
+}
+
+// the DLT point of one (sample, joint) from its accumulated A^T A, dehomogenised
+__device__ __forceinline__ void dlt_solve(double (&Mx)[4][4], float* __restrict__ o) {
+    double V[4][4];
+    const int best = dlt_jacobi(Mx, V);
     const double wv = V[3][best];
-    float* o = out + (long long)g * 3;
     o[0] = (float)(V[0][best] / wv); o[1] = (float)(V[1][best] / wv); o[2] = (float)(V[2][best] / wv);
+}
+
+__global__ void dlt_kernel(const float* __restrict__ proj, const float* __restrict__ pts, const float* __restrict__ conf,
+                           float* __restrict__ out, int B, int NV, int J) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= B * J) return;
+    const int b = g / J, j = g - b * J;
+    double Mx[4][4] = {};
+    for (int v = 0; v < NV; ++v) {
+        const float* p = pts + (((long long)b * NV + v) * J + j) * 2;
+        const float c = conf ? conf[((long long)b * NV + v) * J + j] : 1.f;
+        dlt_accumulate(Mx, proj + ((long long)b * NV + v) * 12, p[0], p[1], c);
+    }
+    dlt_solve(Mx, out + (long long)g * 3);
+}
+
+// ---- algebraic tail (AlgebraicTriangulationNet, triangulation.py:166-193 after the 2D soft-argmax): one lane per (sample, joint) ------------
+// conf = raw / (sum over views) + 1e-5 (uniform raw = 1 without the confidence head), kp2d = soft-argmax * (W / w, H / h), then the DLT of
+// dlt_kernel on (kp2d, conf).  Every step is one IEEE rounding in the order of the Python host's torch ops (conf / conf.sum(1) + 1e-5,
+// kp2d * scale, lt_triangulate_dlt), with the explicit _rn intrinsics so that no contraction can merge two of them.  The sum over views
+// is torch's GPU reduction order: four interleaved partial sums (view v into sum v % 4), combined ((s0 + s1) + s2) + s3 -- plain view
+// order for up to four views.
+__global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
+                                float sx, float sy, float* __restrict__ kp2d, float* __restrict__ conf_out, float* __restrict__ kp3d, int B, int NV, int J) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= B * J) return;
+    const int b = g / J, j = g - b * J;
+    float part[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int v = 0; v < NV; ++v) {
+        const float c = conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f;
+        part[v & 3] = __fadd_rn(part[v & 3], c);
+    }
+    const float sum = __fadd_rn(__fadd_rn(__fadd_rn(part[0], part[1]), part[2]), part[3]);
+    double Mx[4][4] = {};
+    for (int v = 0; v < NV; ++v) {
+        const long long i = ((long long)b * NV + v) * J + j;
+        const float c = __fadd_rn(__fdiv_rn(conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f, sum), 1e-5f);
+        const float x = __fmul_rn(kp_hm[i * 2], sx), y = __fmul_rn(kp_hm[i * 2 + 1], sy);
+        if (conf_out) conf_out[i] = c;
+        if (kp2d) { kp2d[i * 2] = x; kp2d[i * 2 + 1] = y; }
+        dlt_accumulate(Mx, proj + ((long long)b * NV + v) * 12, x, y, c);
+    }
+    dlt_solve(Mx, kp3d + (long long)g * 3);
 }
 
 // ---- backward of the 2D soft-argmax and of the DLT (training of the algebraic model, train.py:189-236) ---------------------------------------
@@ -470,36 +517,12 @@ __global__ void dlt_bwd_kernel(const float* __restrict__ proj, const float* __re
     const int b = g / J, j = g - b * J;
     double Mx[4][4] = {};
     for (int v = 0; v < NV; ++v) {
-        const float* P = proj + ((long long)b * NV + v) * 12;
         const float* p = pts + (((long long)b * NV + v) * J + j) * 2;
         const float c = conf ? conf[((long long)b * NV + v) * J + j] : 1.f;
-        for (int r = 0; r < 2; ++r) {
-            float arow[4];
-            for (int k = 0; k < 4; ++k) arow[k] = (P[8 + k] * p[r] - P[4 * r + k]) * c;
-            for (int i = 0; i < 4; ++i)
-                for (int k = 0; k < 4; ++k) Mx[i][k] += (double)arow[i] * (double)arow[k];
-        }
+        dlt_accumulate(Mx, proj + ((long long)b * NV + v) * 12, p[0], p[1], c);
     }
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 16; ++sweep) {          // the forward's cyclic Jacobi
-        double off = 0;
-        for (int p = 0; p < 4; ++p)
-            for (int q = p + 1; q < 4; ++q) off += Mx[p][q] * Mx[p][q];
-        if (off < 1e-300) break;
-        for (int p = 0; p < 4; ++p)
-            for (int q = p + 1; q < 4; ++q) {
-                if (Mx[p][q] == 0.0) continue;
-                const double theta = (Mx[q][q] - Mx[p][p]) / (2.0 * Mx[p][q]);
-                const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-                for (int k = 0; k < 4; ++k) { const double akp = Mx[k][p], akq = Mx[k][q]; Mx[k][p] = cs * akp - sn * akq; Mx[k][q] = sn * akp + cs * akq; }
-                for (int k = 0; k < 4; ++k) { const double apk = Mx[p][k], aqk = Mx[q][k]; Mx[p][k] = cs * apk - sn * aqk; Mx[q][k] = sn * apk + cs * aqk; }
-                for (int k = 0; k < 4; ++k) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = cs * vkp - sn * vkq; V[k][q] = sn * vkp + cs * vkq; }
-            }
-    }
-    int best = 0;
-    for (int i = 1; i < 4; ++i)
-        if (Mx[i][i] < Mx[best][best]) best = i;
+    double V[4][4];
+    const int best = dlt_jacobi(Mx, V);          // the forward's cyclic Jacobi
     const double lam = Mx[best][best];
     double vv[4], gv[4], wv[4] = {0, 0, 0, 0};
     for (int k = 0; k < 4; ++k) vv[k] = V[k][best];
@@ -608,5 +631,16 @@ extern "C" int lt_triangulate_dlt(const float* proj, const float* points, const 
     LT_REQUIRE(proj && points && out && B >= 1 && NV >= 2 && J >= 1, LT_ERR_INVALID, "lt_triangulate_dlt: bad argument");
     hipLaunchKernelGGL(dlt_kernel, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, proj, points, conf, out, B, NV, J);
     LT_CHECK_LAUNCH("lt_triangulate_dlt");
+    return LT_OK;
+}
+
+extern "C" int lt_alg_tail_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                               float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV, int32_t J, void* stream) {
+    LT_REQUIRE(keypoints_hm && proj && keypoints_3d, LT_ERR_INVALID, "lt_alg_tail_fwd: null argument");
+    LT_REQUIRE(B >= 1 && NV >= 2 && J >= 1, LT_ERR_INVALID, "lt_alg_tail_fwd: bad shape (B %d, NV %d, J %d)", B, NV, J);
+    LT_REQUIRE(!conf_raw || ld_conf >= J, LT_ERR_INVALID, "lt_alg_tail_fwd: ld_conf %d < J %d", ld_conf, J);
+    hipLaunchKernelGGL(alg_tail_kernel, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y,
+                       keypoints_2d, confidences, keypoints_3d, B, NV, J);
+    LT_CHECK_LAUNCH("lt_alg_tail_fwd");
     return LT_OK;
 }

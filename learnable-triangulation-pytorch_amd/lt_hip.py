@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("LT_HIP_LIB") or os.path.join(HERE, "lib", "liblt_hip.
 
 LT_F32, LT_BF16, LT_FP8 = 0, 1, 2
 AGG = {"sum": 0, "max": 1, "softmax": 2, "conf": 3, "conf_norm": 4}
+LT_MODEL_ALG, LT_MODEL_RANSAC = 1, 2          # lt_alg_plan_config.model
 EPI_RELU_PRE, EPI_RELU_POST, EPI_STORE_F32, EPI_SIGMOID = 1, 2, 4, 8
 EPI_RES_F32 = 64
 BN_FROZEN = 32
@@ -102,6 +103,12 @@ class VolPlanConfig(C.Structure):
                 ("transfer_cmu_to_human36m", i32), ("use_graph", i32)]
 
 
+class AlgPlanConfig(C.Structure):
+    _fields_ = [("model", i32), ("dtype", i32), ("num_layers", i32), ("style_caffe", i32), ("num_joints", i32), ("B", i32), ("NV", i32), ("H", i32),
+                ("W", i32), ("use_confidences", i32), ("heatmap_softmax", i32), ("heatmap_multiplier", C.c_double), ("direct_optimization", i32),
+                ("reprojection_error_epsilon", C.c_double), ("use_graph", i32)]
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("launches", i32), ("heatmap_h", i32), ("heatmap_w", i32), ("flops", C.c_double), ("bytes_allocated", C.c_int64),
                 ("n_expand_reduce", i32), ("n_bottleneck", i32), ("n_bottleneck_ds", i32), ("n_conv_cat2", i32), ("n_conv2d_halo", i32), ("n_pwchain", i32),
@@ -112,6 +119,8 @@ class PlanInfo(C.Structure):
 SIGNATURES = {
     "lt_plan_create_vol": (C.c_int, [C.POINTER(VolPlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
     "lt_plan_forward_vol": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "lt_plan_create_alg": (C.c_int, [C.POINTER(AlgPlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
+    "lt_plan_forward_alg": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),
     "lt_plan_destroy": (None, [vp]),
     "lt_last_error": (C.c_char_p, []),
@@ -153,6 +162,7 @@ SIGNATURES = {
     "lt_softargmax3d_fwd": (C.c_int, [vp, vp, f32, i32, i32, i32, vp, vp, i32, i32, i64, vp, vp]),
     "lt_softargmax2d_fwd": (C.c_int, [vp, f32, i32, vp, vp, i32, i32, i32, vp]),
     "lt_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "lt_alg_tail_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
     "lt_heatmap_argmax_nchw_f32": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "lt_triangulate_ransac": (C.c_int, [vp, vp, vp, i32, C.c_double, i32, vp, vp, i32, i32, i32, vp]),
     "lt_bn_act_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]),

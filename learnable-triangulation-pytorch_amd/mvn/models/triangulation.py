@@ -758,16 +758,16 @@ class AlgebraicTriangulationNet(_PlannedNet):
                                         P["x_in"].t.shape[-1], st), "lt_nchw_to_nhwc")
         P["plan"].run_eager(st)
         heatmaps = P["probs"].reshape(B, NV, J, h, w).clone()
-        kp2d = P["kp2d"].reshape(B, NV, J, 2)
-        if P["algc"] is not None:
-            conf = P["algc"].t.reshape(B, NV, J).float()
-        else:
-            conf = torch.ones(B, NV, J, dtype=torch.float32, device=device)
-        # tiny (B*NV*J) host-style glue, reference :173-184
-        conf = conf / conf.sum(dim=1, keepdim=True) + 1e-5
-        scale = torch.tensor([W / w, Hh / h], dtype=torch.float32, device=device)
-        kp2d = kp2d * scale
-        kp3d = multiview.triangulate_batch_of_points(proj_matricies.to(device), kp2d, confidences_batch=conf)
+        # reference :173-193 in one lt_alg_tail_fwd launch: confidences normalised over the views + 1e-5, keypoints to image pixels, the DLT --
+        # bit-identical to conf / conf.sum(1) + 1e-5, kp2d * scale, triangulate_batch_of_points (the training path keeps those autograd ops)
+        algc = P["algc"]
+        proj = proj_matricies.to(device, torch.float32).contiguous()
+        kp2d = torch.empty(B, NV, J, 2, dtype=torch.float32, device=device)
+        conf = torch.empty(B, NV, J, dtype=torch.float32, device=device)
+        kp3d = torch.empty(B, J, 3, dtype=torch.float32, device=device)
+        H.check(H.lib().lt_alg_tail_fwd(P["kp2d"].data_ptr(), None if algc is None else algc.t.data_ptr(), J if algc is None else algc.t.shape[-1],
+                                        proj.data_ptr(), W / w, Hh / h, kp2d.data_ptr(), conf.data_ptr(), kp3d.data_ptr(), B, NV, J, st),
+                "lt_alg_tail_fwd")
         return kp3d, kp2d, heatmaps, conf
 
 
