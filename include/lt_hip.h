@@ -303,7 +303,7 @@ int lt_softargmax2d_fwd(const float* heatmaps, float mult, int32_t softmax, floa
 /* Backward of the two ops above and of lt_triangulate_dlt (training of AlgebraicTriangulationNet, train.py:189-236): what autograd derives in the
  * reference through softmax / sums (op.py:23-45) and through torch.svd (multiview.py:163).  lt_softargmax2d_bwd: probs / coords are the forward's
  * outputs, grad_coords N*J,2 -> grad_heatmaps (both modes; a gradient on the returned heatmaps is not supported).  lt_triangulate_dlt_bwd:
- * grad_out B,J,3 -> grad_points B,NV,J,2 and grad_conf B,NV,J (may be NULL); fp64 inside, the forward's Jacobi eigen-decomposition recomputed. */
+ * grad_out B,J,3 -> grad_points B,NV,J,2 and grad_conf B,NV,J (may be NULL); fp64 inside, the forward's SVD recomputed. */
 int lt_softargmax2d_bwd(const float* probs, const float* coords, const float* grad_coords, float mult, int32_t softmax, float* grad_heatmaps,
                         int32_t NJ, int32_t h, int32_t w, void* stream);
 int lt_triangulate_dlt_bwd(const float* proj, const float* points, const float* conf, const float* grad_out, float* grad_points, float* grad_conf,
@@ -469,7 +469,7 @@ int lt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
 
 /* multiview.triangulate_batch_of_points (mvn/utils/multiview.py:141-183): confidence-weighted DLT.
  * proj B,NV,3,4; points B,NV,J,2; conf B,NV,J or NULL; out B,J,3.  Smallest right singular vector
- * of the (2NV x 4) system by Jacobi eigen-iteration on A^T A in fp64. */
+ * of the (2NV x 4) system in fp64: rows formed in fp64 from the fp32 inputs, Givens QR, one-sided Jacobi SVD of R. */
 int lt_triangulate_dlt(const float* proj, const float* points, const float* conf, float* out, int32_t B, int32_t NV,
                        int32_t J, void* stream);
 /* AlgebraicTriangulationNet after the 2D soft-argmax (reference triangulation.py:166-193), every (sample, joint) in one launch:

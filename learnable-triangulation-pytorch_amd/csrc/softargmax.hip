@@ -379,59 +379,69 @@ __global__ __launch_bounds__(256) void sa2_kernel(const float* __restrict__ hm, 
         }
 }
 
-// ---- DLT: one lane per (sample, joint) ----------------------------------------------------------
+// ---- DLT: one lane per (sample, joint) ----------------------------------------------------------------------------------------------------
 // The per-lane routine every DLT kernel here shares (forward, algebraic tail, backward), so that they solve the same system with the same
-// instruction sequence.  dlt_accumulate: one view's two rows of A (multiview.py:159-161), fp32 like the reference, accumulated into A^T A in fp64.
-__device__ __forceinline__ void dlt_accumulate(double (&Mx)[4][4], const float* __restrict__ P, const float x, const float y, const float c) {
-    const float p[2] = {x, y};
+// instruction sequence.  dlt_accumulate: one view's two rows of A (multiview.py:159-161), c (x P[2,:] - P[r,:]), formed in fp64 from the fp32
+// inputs (the product of two fp32 values is exact in fp64; the reference rounds every step to fp32, which costs up to u32 |x P[2,:]| where
+// the subtraction cancels), and rotated into the upper-triangular R of A = QR (Givens).  The solve works on R, i.e. on A itself as the
+// reference's torch.svd(A) does: the normal matrix A^T A would square A's condition number (pixel-space rows, far points, confidences
+// down to 1e-5 reach kappa(A) ~ 1e8, where u64 kappa^2 exceeds what fp32 inputs can explain).
+__device__ __forceinline__ void dlt_accumulate(double (&R)[4][4], const float* __restrict__ P, const float x, const float y, const float c) {
+    const double p[2] = {(double)x, (double)y};
     for (int r = 0; r < 2; ++r) {
-        float arow[4];
-        for (int k = 0; k < 4; ++k) arow[k] = (P[8 + k] * p[r] - P[4 * r + k]) * c;  // fp32 like the reference
-        for (int i = 0; i < 4; ++i)
-            for (int k = 0; k < 4; ++k) Mx[i][k] += (double)arow[i] * (double)arow[k];
+        double a[4];
+        for (int k = 0; k < 4; ++k) a[k] = ((double)P[8 + k] * p[r] - (double)P[4 * r + k]) * (double)c;
+        for (int k = 0; k < 4; ++k) {          // Givens: rotate the row into R
+            if (a[k] == 0.0) continue;
+            const double h = sqrt(R[k][k] * R[k][k] + a[k] * a[k]);
+            const double cs = R[k][k] / h, sn = a[k] / h;
+            R[k][k] = h;
+            for (int m = k + 1; m < 4; ++m) {
+                const double rk = R[k][m], am = a[m];
+                R[k][m] = cs * rk + sn * am;
+                a[m] = cs * am - sn * rk;
+            }
+        }
     }
 }
 
-// cyclic Jacobi on the symmetric 4x4 A^T A (diagonalised in place, eigenvectors in the columns of V); returns the column of the smallest
-// eigenvalue = the last right singular vector of A
-__device__ __forceinline__ int dlt_jacobi(double (&Mx)[4][4], double (&V)[4][4]) {
+// one-sided Jacobi SVD of R (its columns orthogonalised in place): right singular vectors in the columns of V, squared singular values
+// (the eigenvalues of A^T A) in lam; returns the column of the smallest = the last right singular vector of A
+__device__ __forceinline__ int dlt_svd(double (&U)[4][4], double (&V)[4][4], double (&lam)[4]) {
     for (int i = 0; i < 4; ++i)
         for (int k = 0; k < 4; ++k) V[i][k] = i == k ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 16; ++sweep) {
-        double off = 0;
-        for (int p = 0; p < 4; ++p)
-            for (int q = p + 1; q < 4; ++q) off += Mx[p][q] * Mx[p][q];
-        if (off < 1e-300) break;
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
         for (int p = 0; p < 4; ++p)
             for (int q = p + 1; q < 4; ++q) {
-                if (Mx[p][q] == 0.0) continue;
-                const double theta = (Mx[q][q] - Mx[p][p]) / (2.0 * Mx[p][q]);
-                const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+                double al = 0, be = 0, ga = 0;
+                for (int k = 0; k < 4; ++k) { al += U[k][p] * U[k][p]; be += U[k][q] * U[k][q]; ga += U[k][p] * U[k][q]; }
+                if (ga == 0.0 || !(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
                 for (int k = 0; k < 4; ++k) {
-                    const double akp = Mx[k][p], akq = Mx[k][q];
-                    Mx[k][p] = cs * akp - sn * akq; Mx[k][q] = sn * akp + cs * akq;
-                }
-                for (int k = 0; k < 4; ++k) {
-                    const double apk = Mx[p][k], aqk = Mx[q][k];
-                    Mx[p][k] = cs * apk - sn * aqk; Mx[q][k] = sn * apk + cs * aqk;
-                }
-                for (int k = 0; k < 4; ++k) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = cs * vkp - sn * vkq; V[k][q] = sn * vkp + cs * vkq;
+                    const double up = U[k][p], uq = U[k][q];
+                    U[k][p] = cs * up - sn * uq; U[k][q] = sn * up + cs * uq;
+                    const double vp = V[k][p], vq = V[k][q];
+                    V[k][p] = cs * vp - sn * vq; V[k][q] = sn * vp + cs * vq;
                 }
             }
+        if (!rotated) break;
     }
     int best = 0;
-    for (int i = 1; i < 4; ++i)
-        if (Mx[i][i] < Mx[best][best]) best = i;
+    for (int p = 0; p < 4; ++p) {
+        lam[p] = U[0][p] * U[0][p] + U[1][p] * U[1][p] + U[2][p] * U[2][p] + U[3][p] * U[3][p];
+        if (lam[p] < lam[best]) best = p;
+    }
     return best;
 }
 
-// the DLT point of one (sample, joint) from its accumulated A^T A, dehomogenised
-__device__ __forceinline__ void dlt_solve(double (&Mx)[4][4], float* __restrict__ o) {
-    double V[4][4];
-    const int best = dlt_jacobi(Mx, V);
+// the DLT point of one (sample, joint) from its R, dehomogenised
+__device__ __forceinline__ void dlt_solve(double (&R)[4][4], float* __restrict__ o) {
+    double V[4][4], lam[4];
+    const int best = dlt_svd(R, V, lam);
     const double wv = V[3][best];
     o[0] = (float)(V[0][best] / wv); o[1] = (float)(V[1][best] / wv); o[2] = (float)(V[2][best] / wv);
 }
@@ -441,13 +451,13 @@ __global__ void dlt_kernel(const float* __restrict__ proj, const float* __restri
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= B * J) return;
     const int b = g / J, j = g - b * J;
-    double Mx[4][4] = {};
+    double R[4][4] = {};  // R of A = QR, grown one view at a time
     for (int v = 0; v < NV; ++v) {
         const float* p = pts + (((long long)b * NV + v) * J + j) * 2;
         const float c = conf ? conf[((long long)b * NV + v) * J + j] : 1.f;
-        dlt_accumulate(Mx, proj + ((long long)b * NV + v) * 12, p[0], p[1], c);
+        dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, p[0], p[1], c);
     }
-    dlt_solve(Mx, out + (long long)g * 3);
+    dlt_solve(R, out + (long long)g * 3);
 }
 
 // ---- algebraic tail (AlgebraicTriangulationNet, triangulation.py:166-193 after the 2D soft-argmax): one lane per (sample, joint) ------------
@@ -467,16 +477,16 @@ __global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __
         part[v & 3] = __fadd_rn(part[v & 3], c);
     }
     const float sum = __fadd_rn(__fadd_rn(__fadd_rn(part[0], part[1]), part[2]), part[3]);
-    double Mx[4][4] = {};
+    double R[4][4] = {};  // R of A = QR, grown one view at a time
     for (int v = 0; v < NV; ++v) {
         const long long i = ((long long)b * NV + v) * J + j;
         const float c = __fadd_rn(__fdiv_rn(conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f, sum), 1e-5f);
         const float x = __fmul_rn(kp_hm[i * 2], sx), y = __fmul_rn(kp_hm[i * 2 + 1], sy);
         if (conf_out) conf_out[i] = c;
         if (kp2d) { kp2d[i * 2] = x; kp2d[i * 2 + 1] = y; }
-        dlt_accumulate(Mx, proj + ((long long)b * NV + v) * 12, x, y, c);
+        dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, x, y, c);
     }
-    dlt_solve(Mx, kp3d + (long long)g * 3);
+    dlt_solve(R, kp3d + (long long)g * 3);
 }
 
 // ---- backward of the 2D soft-argmax and of the DLT (training of the algebraic model, train.py:189-236) ---------------------------------------
@@ -515,15 +525,15 @@ __global__ void dlt_bwd_kernel(const float* __restrict__ proj, const float* __re
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= B * J) return;
     const int b = g / J, j = g - b * J;
-    double Mx[4][4] = {};
+    double R[4][4] = {};  // R of A = QR, grown one view at a time
     for (int v = 0; v < NV; ++v) {
         const float* p = pts + (((long long)b * NV + v) * J + j) * 2;
         const float c = conf ? conf[((long long)b * NV + v) * J + j] : 1.f;
-        dlt_accumulate(Mx, proj + ((long long)b * NV + v) * 12, p[0], p[1], c);
+        dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, p[0], p[1], c);
     }
-    double V[4][4];
-    const int best = dlt_jacobi(Mx, V);          // the forward's cyclic Jacobi
-    const double lam = Mx[best][best];
+    double V[4][4], ev[4];
+    const int best = dlt_svd(R, V, ev);         // the forward's solve: eigenvectors of A^T A = right singular vectors, eigenvalues = sigma^2
+    const double lam = ev[best];
     double vv[4], gv[4], wv[4] = {0, 0, 0, 0};
     for (int k = 0; k < 4; ++k) vv[k] = V[k][best];
     const double gX[3] = {(double)gout[g * 3], (double)gout[g * 3 + 1], (double)gout[g * 3 + 2]};
@@ -533,7 +543,7 @@ __global__ void dlt_bwd_kernel(const float* __restrict__ proj, const float* __re
         if (i == best) continue;
         double dot = 0;
         for (int k = 0; k < 4; ++k) dot += V[k][i] * gv[k];
-        const double f = dot / (lam - Mx[i][i]);
+        const double f = dot / (lam - ev[i]);
         for (int k = 0; k < 4; ++k) wv[k] += V[k][i] * f;
     }
     for (int v = 0; v < NV; ++v) {
@@ -544,7 +554,7 @@ __global__ void dlt_bwd_kernel(const float* __restrict__ proj, const float* __re
         double gc = 0;
         for (int r = 0; r < 2; ++r) {
             double raw[4], arow[4], av = 0, aw = 0;
-            for (int k = 0; k < 4; ++k) { raw[k] = (double)(P[8 + k] * p[r] - P[4 * r + k]); arow[k] = raw[k] * c; av += arow[k] * vv[k]; aw += arow[k] * wv[k]; }
+            for (int k = 0; k < 4; ++k) { raw[k] = (double)P[8 + k] * (double)p[r] - (double)P[4 * r + k]; arow[k] = raw[k] * c; av += arow[k] * vv[k]; aw += arow[k] * wv[k]; }
             double gp = 0;
             for (int k = 0; k < 4; ++k) {
                 const double ga = aw * vv[k] + av * wv[k];          // dL/dA[v,r,k] = (A (w v^T + v w^T))[row][k]

@@ -6,6 +6,11 @@ geometry -- the same arithmetic types the reference uses.  Every function cites 
 /root/reference (paths relative to that root).
 
 Pinned by tests/golden/*.npz = outputs of the reference itself (oracle/make_golden.py).
+
+``dtype=torch.float64`` (every function below that computes takes it) is the TRUTH mode: the inputs the reference defines in fp32
+(weights, images, the fp32 projection matrices and coordinate volumes) are promoted as they are and everything after them runs in
+fp64 -- voxel projection, bilinear sampling, DLT rows included (tests/golden/truth_*.npz).  The default (None) is the reference's
+arithmetic as before: inputs as given, the tensors the functions create in fp32.
 """
 import math
 
@@ -74,19 +79,24 @@ def coord_volume(base_point, cuboid_side, V, theta=0.0, axis=(0, 0, 1), cmu_tran
 # --------------------------------------------------------------------------------------------
 # functional ops
 # --------------------------------------------------------------------------------------------
-def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, method="sum", vol_confidences=None):
+def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, method="sum", vol_confidences=None, dtype=None):
     """mvn/utils/op.py:99-166 + mvn/utils/multiview.py:55-110, vectorised over views.
 
     heatmaps (B,NV,C,h,w), proj (B,NV,3,4), coord_volumes (B,V,V,V,3) -> (B,C,V,V,V).
     Quirks kept: x normalised by h and y by w (op.py:128-129); align_corners=True; zero padding;
     z<=0 samples zeroed AFTER sampling and still entering the view softmax (op.py:141,157-162).
     """
+    if dtype is not None:
+        heatmaps, proj_matricies, coord_volumes = heatmaps.to(dtype), proj_matricies.to(dtype), coord_volumes.to(dtype)
+        if vol_confidences is not None:
+            vol_confidences = vol_confidences.to(dtype)
+    dt = dtype or torch.float32
     B, NV, C, h, w = heatmaps.shape
     vshape = tuple(coord_volumes.shape[1:4])
-    out = torch.zeros(B, C, *vshape)
+    out = torch.zeros(B, C, *vshape, dtype=dt)
     for b in range(B):
         X = coord_volumes[b].reshape(-1, 3)
-        Xh = torch.cat([X, torch.ones(X.shape[0], 1)], dim=1)
+        Xh = torch.cat([X, torch.ones(X.shape[0], 1, dtype=dt)], dim=1)
         per_view = []
         for v in range(NV):
             p = Xh @ proj_matricies[b, v].t()
@@ -116,8 +126,10 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, method="sum", vo
     return out
 
 
-def integrate_tensor_3d_with_coordinates(volumes, coord_volumes, softmax=True):
+def integrate_tensor_3d_with_coordinates(volumes, coord_volumes, softmax=True, dtype=None):
     """mvn/utils/op.py:84-96: softmax (or ReLU) over all voxels, then expectation of the coords."""
+    if dtype is not None:
+        volumes, coord_volumes = volumes.to(dtype), coord_volumes.to(dtype)
     B, J = volumes.shape[:2]
     flat = volumes.reshape(B, J, -1)
     flat = torch.softmax(flat, dim=2) if softmax else torch.relu(flat)
@@ -125,31 +137,39 @@ def integrate_tensor_3d_with_coordinates(volumes, coord_volumes, softmax=True):
     return coords, flat.reshape(volumes.shape)
 
 
-def integrate_tensor_2d(heatmaps, softmax=True):
+def integrate_tensor_2d(heatmaps, softmax=True, dtype=None):
     """mvn/utils/op.py:11-47: 2D soft-argmax; x first, then y."""
+    if dtype is not None:
+        heatmaps = heatmaps.to(dtype)
+    dt = dtype or torch.float32
     N, J, h, w = heatmaps.shape
     flat = heatmaps.reshape(N, J, -1)
     flat = torch.softmax(flat, dim=2) if softmax else torch.relu(flat)
     hm = flat.reshape(N, J, h, w)
     mass_x = hm.sum(dim=2)
     mass_y = hm.sum(dim=3)
-    x = (mass_x * torch.arange(w, dtype=torch.float32)).sum(dim=2, keepdim=True)
-    y = (mass_y * torch.arange(h, dtype=torch.float32)).sum(dim=2, keepdim=True)
+    x = (mass_x * torch.arange(w, dtype=dt)).sum(dim=2, keepdim=True)
+    y = (mass_y * torch.arange(h, dtype=dt)).sum(dim=2, keepdim=True)
     if not softmax:
         x = x / mass_x.sum(dim=2, keepdim=True)
         y = y / mass_y.sum(dim=2, keepdim=True)
     return torch.cat([x, y], dim=2), hm
 
 
-def triangulate_batch_of_points(proj_matricies, points, confidences=None):
+def triangulate_batch_of_points(proj_matricies, points, confidences=None, dtype=None):
     """mvn/utils/multiview.py:141-183: per (sample, joint) confidence-weighted DLT via SVD."""
+    if dtype is not None:
+        proj_matricies, points = proj_matricies.to(dtype), points.to(dtype)
+        if confidences is not None:
+            confidences = confidences.to(dtype)
+    dt = dtype or torch.float32
     B, NV, J = points.shape[:3]
-    out = torch.zeros(B, J, 3)
+    out = torch.zeros(B, J, 3, dtype=dt)
     for b in range(B):
         P = proj_matricies[b]
         for j in range(J):
             pt = points[b, :, j, :]
-            c = confidences[b, :, j] if confidences is not None else torch.ones(NV)
+            c = confidences[b, :, j] if confidences is not None else torch.ones(NV, dtype=dt)
             A = P[:, 2:3].expand(NV, 2, 4) * pt.reshape(NV, 2, 1) - P[:, :2]
             A = A * c.reshape(-1, 1, 1)
             _, _, vh = torch.svd(A.reshape(-1, 4))
@@ -166,12 +186,20 @@ def _bn(sd, p, x):
                         sd[p + ".bias"], False, 0.1, BN_EPS)
 
 
-def pose_resnet(sd, x, num_layers, prefix="backbone.", caffe=False):
+def _promote(sd, dtype):
+    """The state dict with its floating tensors in ``dtype`` (as it is without one)."""
+    if dtype is None:
+        return sd
+    return {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+def pose_resnet(sd, x, num_layers, prefix="backbone.", caffe=False, dtype=None):
     """PoseResNet.forward, mvn/models/pose_resnet.py:293-318 (eval mode).  caffe=True: config.style == 'caffe'
     (pose_resnet.py:322-324, Bottleneck_CAFFE :98-137: bottleneck blocks at every depth, the block stride on the first 1x1).
 
     Returns (heatmaps, features, alg_confidences|None, vol_confidences|None).
     """
+    sd, x = _promote(sd, dtype), (x if dtype is None else x.to(dtype))
     kind, blocks = RESNET_SPEC[num_layers]
     if caffe:
         kind = "bottleneck"
@@ -216,24 +244,42 @@ def pose_resnet(sd, x, num_layers, prefix="backbone.", caffe=False):
     return hm, feats, alg_c, vol_c
 
 
+SLAB_BYTES = 1 << 30
+
+
+def _conv3d(x, w, b, padding=0):
+    """F.conv3d (stride 1).  fp64 has no oneDNN path on torch-CPU and slow_conv3d unfolds the whole input (184 GB for V2V's 7^3 front
+    layer at 8 x 64^3): in fp64 a k > 1 kernel runs one sample at a time, in output-depth slabs whose unfolded input stays near SLAB_BYTES."""
+    k = w.shape[-1]
+    if x.dtype != torch.float64 or k == 1:
+        return F.conv3d(x, w, b, 1, padding)
+    xp = F.pad(x, (padding,) * 6)
+    D = xp.shape[2] - k + 1
+    plane = w.shape[1] * k ** 3 * (xp.shape[3] - k + 1) * (xp.shape[4] - k + 1) * x.element_size()
+    step = max(1, min(D, SLAB_BYTES // plane))
+    return torch.cat([torch.cat([F.conv3d(xp[n:n + 1, :, d0:min(D, d0 + step) + k - 1], w, b) for d0 in range(0, D, step)], 2)
+                      for n in range(x.shape[0])], 0)
+
+
 def _res3d(sd, p, x):  # v2v.py:20-42
-    o = F.relu(_bn(sd, p + ".res_branch.1", F.conv3d(x, sd[p + ".res_branch.0.weight"], sd[p + ".res_branch.0.bias"], 1, 1)))
-    o = _bn(sd, p + ".res_branch.4", F.conv3d(o, sd[p + ".res_branch.3.weight"], sd[p + ".res_branch.3.bias"], 1, 1))
+    o = F.relu(_bn(sd, p + ".res_branch.1", _conv3d(x, sd[p + ".res_branch.0.weight"], sd[p + ".res_branch.0.bias"], 1)))
+    o = _bn(sd, p + ".res_branch.4", _conv3d(o, sd[p + ".res_branch.3.weight"], sd[p + ".res_branch.3.bias"], 1))
     if (p + ".skip_con.0.weight") in sd:
-        x = _bn(sd, p + ".skip_con.1", F.conv3d(x, sd[p + ".skip_con.0.weight"], sd[p + ".skip_con.0.bias"]))
+        x = _bn(sd, p + ".skip_con.1", _conv3d(x, sd[p + ".skip_con.0.weight"], sd[p + ".skip_con.0.bias"]))
     return F.relu(o + x)
 
 
 def _basic3d(sd, p, x, k):  # v2v.py:7-17
-    return F.relu(_bn(sd, p + ".block.1", F.conv3d(x, sd[p + ".block.0.weight"], sd[p + ".block.0.bias"], 1, (k - 1) // 2)))
+    return F.relu(_bn(sd, p + ".block.1", _conv3d(x, sd[p + ".block.0.weight"], sd[p + ".block.0.bias"], (k - 1) // 2)))
 
 
 def _up3d(sd, p, x):  # v2v.py:54-66
     return F.relu(_bn(sd, p + ".block.1", F.conv_transpose3d(x, sd[p + ".block.0.weight"], sd[p + ".block.0.bias"], 2)))
 
 
-def v2v(sd, x, prefix="volume_net."):
+def v2v(sd, x, prefix="volume_net.", dtype=None):
     """V2VModel.forward, mvn/models/v2v.py:164-169 with EncoderDecorder.forward :103-138."""
+    sd, x = _promote(sd, dtype), (x if dtype is None else x.to(dtype))
     x = _basic3d(sd, prefix + "front_layers.0", x, 7)
     for i in (1, 2, 3):
         x = _res3d(sd, prefix + "front_layers.%d" % i, x)
@@ -251,7 +297,7 @@ def v2v(sd, x, prefix="volume_net."):
     x = _res3d(sd, prefix + "back_layers.0", x)
     x = _basic3d(sd, prefix + "back_layers.1", x, 1)
     x = _basic3d(sd, prefix + "back_layers.2", x, 1)
-    return F.conv3d(x, sd[prefix + "output_layer.weight"], sd[prefix + "output_layer.bias"])
+    return _conv3d(x, sd[prefix + "output_layer.weight"], sd[prefix + "output_layer.bias"])
 
 
 # --------------------------------------------------------------------------------------------
@@ -266,7 +312,7 @@ def base_points_from_batch(pred_keypoints_3d, kind):
 
 
 @torch.no_grad()
-def volumetric_forward(sd, config, images, K, R, t, pred_keypoints_3d, thetas=None, stages=False):
+def volumetric_forward(sd, config, images, K, R, t, pred_keypoints_3d, thetas=None, stages=False, dtype=None):
     """VolumetricTriangulationNet.forward, mvn/models/triangulation.py:245-355 (eval; theta given).
 
     images (B,NV,3,H,W); K,R,t per view at image resolution, shared by all samples
@@ -275,9 +321,10 @@ def volumetric_forward(sd, config, images, K, R, t, pred_keypoints_3d, thetas=No
     base_points and -- with stages=True -- the unprojected volume and the V2V logits.
     """
     m = config.model
+    sd = _promote(sd, dtype)
     B, NV = images.shape[:2]
     H, W = images.shape[3:]
-    hm, feats, _, vol_c = pose_resnet(sd, images.reshape(-1, 3, H, W), m.backbone.num_layers)
+    hm, feats, _, vol_c = pose_resnet(sd, images.reshape(-1, 3, H, W), m.backbone.num_layers, dtype=dtype)
     hshape = tuple(hm.shape[2:])
     feats = feats.reshape(B, NV, *feats.shape[1:])
     if vol_c is not None:
@@ -294,9 +341,9 @@ def volumetric_forward(sd, config, images, K, R, t, pred_keypoints_3d, thetas=No
                       for b in range(B)])
     f = F.conv2d(feats.reshape(-1, *feats.shape[2:]), sd["process_features.0.weight"], sd["process_features.0.bias"])
     f = f.reshape(B, NV, *f.shape[1:])
-    unproj = unproject_heatmaps(f, P, cv, m.volume_aggregation_method, vol_c)
-    logits = v2v(sd, unproj)
-    kp, vols = integrate_tensor_3d_with_coordinates(logits * m.volume_multiplier, cv, softmax=m.volume_softmax)
+    unproj = unproject_heatmaps(f, P, cv, m.volume_aggregation_method, vol_c, dtype=dtype)
+    logits = v2v(sd, unproj, dtype=dtype)
+    kp, vols = integrate_tensor_3d_with_coordinates(logits * m.volume_multiplier, cv, softmax=m.volume_softmax, dtype=dtype)
     out = {"keypoints_3d": kp, "features": f, "volumes": vols, "vol_confidences": vol_c,
            "coord_volumes": cv, "base_points": torch.from_numpy(base).float(), "proj": P}
     if stages:
@@ -306,7 +353,7 @@ def volumetric_forward(sd, config, images, K, R, t, pred_keypoints_3d, thetas=No
 
 
 @torch.no_grad()
-def algebraic_forward(sd, config, images, K, R, t):
+def algebraic_forward(sd, config, images, K, R, t, dtype=None):
     """AlgebraicTriangulationNet.forward, mvn/models/triangulation.py:149-200 (eval).
 
     The projection matrices are the IMAGE-resolution ones the caller passes to forward
@@ -315,11 +362,11 @@ def algebraic_forward(sd, config, images, K, R, t):
     m = config.model
     B, NV = images.shape[:2]
     H, W = images.shape[3:]
-    hm, _, alg_c, _ = pose_resnet(sd, images.reshape(-1, 3, H, W), m.backbone.num_layers)
+    hm, _, alg_c, _ = pose_resnet(sd, images.reshape(-1, 3, H, W), m.backbone.num_layers, dtype=dtype)
     J = hm.shape[1]
     if alg_c is None:
-        alg_c = torch.ones(B * NV, J)
-    kp2d, hm_sm = integrate_tensor_2d(hm * m.heatmap_multiplier, m.heatmap_softmax)
+        alg_c = torch.ones(B * NV, J, dtype=dtype or torch.float32)
+    kp2d, hm_sm = integrate_tensor_2d(hm * m.heatmap_multiplier, m.heatmap_softmax, dtype=dtype)
     h, w = hm.shape[2:]
     kp2d = kp2d.reshape(B, NV, J, 2)
     alg_c = alg_c.reshape(B, NV, J)
@@ -327,6 +374,6 @@ def algebraic_forward(sd, config, images, K, R, t):
     kp2d = torch.stack([kp2d[..., 0] * (W / w), kp2d[..., 1] * (H / h)], dim=-1)
     K, R, t = (np.broadcast_to(a, (B,) + a.shape[-3:]) if a.ndim == 3 else a for a in (K, R, t))
     P = torch.from_numpy(np.asarray(K, np.float64) @ np.concatenate([R, t], axis=-1)).float()
-    kp3d = triangulate_batch_of_points(P, kp2d, alg_c)
+    kp3d = triangulate_batch_of_points(P, kp2d, alg_c, dtype=dtype)
     return {"keypoints_3d": kp3d, "keypoints_2d": kp2d, "heatmaps": hm_sm.reshape(B, NV, J, h, w),
             "alg_confidences": alg_c, "proj": P}
