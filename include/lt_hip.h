@@ -500,6 +500,21 @@ int lt_heatmap_argmax_nchw_f32(const float* heatmaps, int32_t ld, float* heatmap
 int lt_triangulate_ransac(const float* proj, const int64_t* points, const int32_t* pairs, int32_t n_iters, double eps, int32_t direct_opt,
                           float* out_kp3d, uint8_t* out_inliers, int32_t B, int32_t NV, int32_t J, void* stream);
 
+/* Per-view image preparation of the reference dataset (mvn/datasets/human36m.py:116-189, mvn/utils/img.py) for a ragged batch of N
+ * views in one launch: crop to the bbox with zero fill outside the region (PIL crop), cv2.resize(INTER_AREA) of the uint8 crop to
+ * H x W, reproduced branch by branch on 8UC3 (identity, integer factors, general area downscale bit-exact; any upscaled axis is
+ * OpenCV's fixed-point bilinear "area mode" with its scalar rounding), then out[n,c,y,x] = lut[c*256 + v] (lut 3 x 256 fp32, e.g. the
+ * fp32 of normalize_image) or (float)v when lut is NULL.  Channel order is kept.
+ *   src      flat uint8 buffer of HWC 3-channel pixels, src_bytes long;
+ *   desc     N x 8 int64: byte offset into src, region height, width, row pitch in bytes, bbox left, upper, right, lower relative to the
+ *            region (may lie partly or wholly outside it; a region already cropped to bbox and frame, with the bbox shifted, gives the
+ *            same output);
+ *   desc_host the same N x 8 records on the host, or NULL: when given, an empty bbox, a region past src_bytes or a bad pitch is
+ *            LT_ERR_INVALID before anything is enqueued (without it the device trusts desc; an empty bbox writes zeros);
+ *   out      N x 3 x H x W fp32.  W <= 2048, N <= 65535. */
+int lt_crop_resize_u8(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int32_t N, int32_t H, int32_t W,
+                      const float* lut, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Chain of up to LT_PWCHAIN_MAX pointwise (1x1x1) convolutions evaluated per voxel without the
  * intermediate activations leaving the registers:  y = L_n(...L_1(x)),

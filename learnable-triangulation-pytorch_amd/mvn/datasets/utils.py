@@ -19,12 +19,17 @@ def make_collate_fn(randomize_n_views=True, min_n_views=10, max_n_views=31):
             print("All items in batch are None")
             return None
         batch = dict()
-        total_n_views = min(len(item["images"]) for item in items)
+        key = "images" if "images" in items[0] else "frames"        # "frames" + "bboxes": deferred pixel work (prepare_batch_frames)
+        total_n_views = min(len(item[key]) for item in items)
         indexes = np.arange(total_n_views)
         if randomize_n_views:
             n_views = np.random.randint(min_n_views, min(total_n_views, max_n_views) + 1)
             indexes = np.random.choice(np.arange(total_n_views), size=n_views, replace=False)
-        batch["images"] = np.stack([np.stack([item["images"][i] for item in items], axis=0) for i in indexes], axis=0).swapaxes(0, 1)
+        if key == "images":
+            batch["images"] = np.stack([np.stack([item["images"][i] for item in items], axis=0) for i in indexes], axis=0).swapaxes(0, 1)
+        else:
+            batch["frames"] = [[item["frames"][i] for item in items] for i in indexes]       # list[NV] of list[B] of uint8 (h, w, 3)
+            batch["bboxes"] = np.array([[item["bboxes"][i] for item in items] for i in indexes]).swapaxes(0, 1)   # (B, NV, 4)
         batch["detections"] = np.array([[item["detections"][i] for item in items] for i in indexes]).swapaxes(0, 1)
         batch["cameras"] = [[item["cameras"][i] for item in items] for i in indexes]
         batch["keypoints_3d"] = [item["keypoints_3d"] for item in items]
@@ -81,9 +86,65 @@ def prepare_batch(batch, device, config=None, is_train=True):
     else:
         dev = torch.from_numpy(np.ascontiguousarray(images)).float()
     images_batch = dev.permute(0, 1, 4, 2, 3).contiguous()   # BxNVxHxWxC -> BxNVxCxHxW (reference img.py:95-98 per view)
+    return (images_batch,) + _targets(batch, device)
+
+
+def _targets(batch, device):
     kp = np.stack(batch["keypoints_3d"], axis=0)
     keypoints_3d_batch_gt = torch.from_numpy(kp[:, :, :3]).float().to(device)
     keypoints_3d_validity_batch_gt = torch.from_numpy(kp[:, :, 3:]).float().to(device)
     proj = np.stack([np.stack([camera.projection for camera in camera_batch], axis=0) for camera_batch in batch["cameras"]], axis=0)
     proj_matricies_batch = torch.from_numpy(np.ascontiguousarray(proj.swapaxes(0, 1))).float().to(device)   # (B, NV, 3, 4)
-    return images_batch, keypoints_3d_batch_gt, keypoints_3d_validity_batch_gt, proj_matricies_batch
+    return keypoints_3d_batch_gt, keypoints_3d_validity_batch_gt, proj_matricies_batch
+
+
+def prepare_batch_frames(batch, device, image_shape, norm_image=True):
+    """prepare_batch for a batch of deferred items (Human36MMultiViewDataset(defer_image_ops=True) collated by make_collate_fn):
+    batch["frames"] list[NV] of list[B] uint8 (h, w, 3) frames of any sizes, batch["bboxes"] (B, NV, 4) crop boxes in frame
+    coordinates.  Only the bytes of bbox & frame travel: the host packs them, with the view descriptors in front, into one pinned
+    block (same ring discipline as prepare_batch), one asynchronous H2D copy moves it, and one lt_crop_resize_u8 launch crops,
+    resizes (INTER_AREA) and normalises every view.  Returns the same 4-tuple as prepare_batch; the images are bitwise what
+    prepare_batch gives for the CPU-prepared items (normalize_image(resize_image(crop_image(...))) cast to fp32)."""
+    from mvn.utils import img
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("prepare_batch_frames runs the crop / resize / normalise kernel: device must be a GPU (got %s)" % device)
+    frames, bboxes = batch["frames"], np.asarray(batch["bboxes"], dtype=np.int64)
+    nv, bs = len(frames), len(frames[0])
+    n = bs * nv
+    desc = np.zeros((n, img.DESC_FIELDS), np.int64)
+    regions = []
+    off = 0
+    for b in range(bs):                      # view n = b * NV + v: the (B, NV) order of the output
+        for v in range(nv):
+            f = frames[v][b]
+            h, w = f.shape[:2]
+            l, u, r, lo = (int(x) for x in bboxes[b, v])
+            x0, x1, y0, y1 = min(max(l, 0), w), min(max(r, 0), w), min(max(u, 0), h), min(max(lo, 0), h)
+            x1, y1 = max(x1, x0), max(y1, y0)
+            reg = f[y0:y1, x0:x1]
+            desc[b * nv + v] = (off, y1 - y0, x1 - x0, 3 * (x1 - x0), l - x0, u - y0, r - x0, lo - y0)
+            regions.append(reg)
+            off += reg.size
+    head = desc.nbytes
+    total = head + off
+    cap = 1 << max(20, (total - 1).bit_length())          # power-of-two blocks: one ring serves batches of similar byte counts
+    slot = _pinned((cap,), torch.uint8)
+    stage, ev = slot
+    if ev is not None:
+        ev.synchronize()
+    host = stage.numpy()
+    host[:head] = desc.view(np.uint8).reshape(-1)
+    for i, reg in enumerate(regions):
+        if reg.size:
+            o = head + int(desc[i, 0])
+            host[o:o + reg.size].reshape(reg.shape)[...] = reg
+    dev = stage[:total].to(device, non_blocking=True)
+    slot[1] = torch.cuda.Event()
+    slot[1].record(torch.cuda.current_stream(device))
+    H, W = int(image_shape[0]), int(image_shape[1])
+    out = torch.empty((bs, nv, 3, H, W), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        lut = img.normalize_lut(device) if norm_image else None
+        img.launch_crop_resize(dev[head:], dev[:head].view(torch.int64).view(n, img.DESC_FIELDS), desc, (H, W), lut, out.view(n, 3, H, W))
+    return (out,) + _targets(batch, device)
