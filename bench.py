@@ -13,7 +13,11 @@ through the reference-shaped module API (VolumetricTriangulationNet.forward) who
 independent units, so ranks shard the batch with NO data-path collective (weak scaling); the only communication is the
 barrier + MAX-reduce of the timing (on device tensors).  Rank 0 prints ONE JSON line.
 
-Besides the driver contract the line carries
+A plain run measures the headline alone: it sets up, warms up, times the K steps, writes the outputs if ``--dump-outputs`` is given
+and prints the line.  Everything else below -- the CPU baseline and parity, the per-kernel roofline with its PMC passes and the shader
+clock, the fp32 parity-mode leg, the batch sweep, the config-4 and training child legs -- runs only with ``--full``.
+
+With ``--full`` the line also carries
   roofline      the dominant kernel family (convolutions on MFMA): algorithmic FLOP per step (2*MAC of every conv launch) /
                 summed launch durations, measured with hipEvent pairs around every launch on the launch stream (eager pass
                 after the timed region); ``traffic`` = HBM bytes per step of the same launches from the committed rocprofv3
@@ -210,12 +214,12 @@ def pmc_leg(args, timeout_s=90, train=False, keep_per_kernel=False):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pmc_summary
     out = tempfile.mkdtemp(prefix="lt_pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-profile", "--no-extras", "--no-graph",
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--no-graph",          # plain runs: nothing but the steps
              "--preroll-s", "0", "--batch", str(args.batch), "--views", str(args.views), "--volume", str(args.volume), "--image", str(args.image),
              "--layers", str(args.layers), "--dtype", args.dtype]
     nsteps = 3                     # forwards per pass: 2 setup + 1 timed
     if train:                      # training step: 2 warm-up steps (the first one records the tape) + 1 timed
-        child += ["--train", "--train-dtype", args.train_dtype, "--no-pmc-leg"]
+        child += ["--train", "--train-dtype", args.train_dtype]
     env = dict(os.environ, TMPDIR="/tmp")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LT_BENCH_SELF_LAUNCHED"):
         env.pop(k, None)
@@ -340,10 +344,10 @@ def _train_short(t):
     return o
 
 
-def compact_line(res):
+def compact_line(res, full=True):
     """The ONE stdout line (driver contract), <= 4 KB (4.0 KB on round 5's final record): every headline figure, one-number summaries of every leg; the full records of the legs go to
     stderr (one ``# leg <name>: {json}`` line each, as they finish) and to gpurun_out/bench_full.json (VERDICT r4 "next" 3: the 14 KB line of round 4 did
-    not fit the driver's 8 KB tail)."""
+    not fit the driver's 8 KB tail).  ``full=False``: the line of a plain run, which writes no full record."""
     out = {k: res[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config") if k in res}
     out["value"], out["ms_per_step"] = _r(res["value"], 6), _r(res["ms_per_step"], 6)
     if res.get("n_gpus", 1) > 1:
@@ -399,6 +403,8 @@ def compact_line(res):
                                "kind_note": "oracle/ = the reference's ATen ops, pinned at 0.0 on all 88 stages (tests/golden)"}
     if res.get("dumped_outputs"):
         out["dumped_outputs"] = res["dumped_outputs"]["dir"]
+    if not full:
+        return out
     out["full_record"] = "stderr '# leg ...' lines; gpurun_out/bench_full.json"
     return out
 
@@ -863,22 +869,30 @@ def main():
                     "(same weights, batch, rotations): the loss curves side by side, its own JSON line")
     ap.add_argument("--trajectory-precisions", default="fp32,fp32_bf16_images,act16,fp8v2v")
     ap.add_argument("--full-line", action="store_true", help="print the full record on stdout instead of the compact line (child legs are run this way)")
-    ap.add_argument("--force-pmc-leg", action="store_true", help="measure roofline.traffic live even with --no-extras (the config-4 child leg of the default run)")
+    ap.add_argument("--force-pmc-leg", action="store_true", help="measure roofline.traffic live even with --no-extras (the config-4 child leg of a --full run)")
     ap.add_argument("--no-pmc-leg", action="store_true", help="do not measure roofline.traffic live (rocprofv3 child runs, ~1 min); use the committed PMC file")
-    ap.add_argument("--no-legs", action="store_true", help="skip the config-4 and training legs of the default (config 2, N = 1) run")
+    ap.add_argument("--no-legs", action="store_true", help="skip the config-4 and training legs of a --full run (config 2, N = 1)")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0, help="CPU baseline leg: timed forwards of sample 0 until this many seconds (at least one)")
     ap.add_argument("--cpu-parity-samples", type=int, default=2, help="samples of the timed batch the CPU oracle evaluates as parity references")
     ap.add_argument("--fp32-parity-batch", type=int, default=0, help="with --no-extras: also run this many samples through the exact-fp32 kernel set and report their "
-                    "parity (the config-4 child leg of the default run: the driver line then shows config 4 inside the tolerance)")
+                    "parity (the config-4 child leg of a --full run: the --full line then shows config 4 inside the tolerance)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the arrays the last timed step returned (rank 0's "
                     "shard) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: small outputs whole, large ones as a fixed seeded sample of "
                     "their elements (see dump_outputs).  Forward runs only")
+    ap.add_argument("--full", action="store_true", help="measure everything besides the headline: the CPU baseline and parity, the per-kernel roofline (live PMC "
+                    "passes, shader clock), the fp32 parity-mode leg, the batch sweep, the config-4 and training child legs, the live PMC figures of --train.  "
+                    "Without it a run sets up, warms up, times the steps, dumps (--dump-outputs) and prints the line; the --no-* options above subtract from --full")
     ap.add_argument("--stub-cpu", action="store_true", help="TEST ONLY: gloo backend, no GPU, step() is a sleep (exercises launcher + timing plumbing)")
     ap.add_argument("--preflight", action="store_true", help="N-GPU sanity run before a scaling session (VERDICT r5 'next' 7): communicator census (ranks, distinct "
                     "devices, RCCL version), ONE timed 64 MB all-reduce, ONE data-parallel training step with the replicas checked identical, then exit with its own JSON line")
     args = ap.parse_args()
     if args.dump_outputs and (args.train or args.train_trajectory or args.preflight or args.stub_cpu):
         ap.error("--dump-outputs writes what the timed forward returns: not with --train, --train-trajectory, --preflight or --stub-cpu")
+    if not args.full:
+        # a plain run: the headline and nothing else (no CPU leg, no profiled passes, no PMC child runs, no extra legs)
+        if args.ops_json or args.force_pmc_leg or args.fp32_parity_batch:
+            ap.error("--ops-json, --force-pmc-leg and --fp32-parity-batch measure more than the headline: they need --full")
+        args.no_cpu_baseline = args.no_profile = args.no_extras = args.no_pmc_leg = True
     if not args.batch:
         # 64 samples (256 images) per GPU per step from round 4 on: two full rounds of 288-row tiles on the 256 CUs and half the per-sample share of the
         # ~220 launches' fixed cost (+3 % over 32 samples; 48 samples = 1.5 rounds is slower than either); rounds 1-3 timed 32, which stays in batch_sweep
@@ -976,7 +990,8 @@ def main():
     t_pre = time.perf_counter()
     while time.perf_counter() - t_pre < args.preroll_s:
         out = step(); torch.cuda.synchronize()
-    sampler = ClockSampler(local) if (world == 1 and rank == 0 and os.environ.get("LT_BENCH_NO_CLOCKS") != "1") else None
+    # (the clocks go on the roofline block only: no sampler where no roofline is computed)
+    sampler = ClockSampler(local) if (world == 1 and rank == 0 and not args.no_profile and os.environ.get("LT_BENCH_NO_CLOCKS") != "1") else None
     for _ in range(args.warmup):
         out = step()
     t_w0 = time.time()
@@ -1124,27 +1139,27 @@ def main():
                 del out
                 model.invalidate_plans()
                 torch.cuda.empty_cache()
-                result["config4"] = sub_leg(["--views", "8", "--volume", "128", "--batch", "16", "--steps", "8", "--warmup", "3", "--no-extras", "--full-line",
+                result["config4"] = sub_leg(["--full", "--views", "8", "--volume", "128", "--batch", "16", "--steps", "8", "--warmup", "3", "--no-extras", "--full-line",
                                              "--cpu-budget-s", "1", "--cpu-parity-samples", "1", "--preroll-s", "0.3", "--force-pmc-leg", "--fp32-parity-batch", "2"], 600)
                 emit_detail("config4", result["config4"])
                 # (live PMC passes -- three profiled child runs that each re-record the tape, ~90 s -- on ONE training leg: the act16 one)
-                result["train"] = sub_leg(["--train", "--batch", "4", "--steps", "8", "--warmup", "2", "--no-pmc-leg"], 600)
+                result["train"] = sub_leg(["--full", "--train", "--batch", "4", "--steps", "8", "--warmup", "2", "--no-pmc-leg"], 600)
                 # config 5's reduced-precision step as BASELINE names it: 16-bit activations (bf16) + bf16 MFMA for every convolution product (train_precision
                 # "act16"), and the same with V2V's 3x3x3 convolutions on the fp8 MFMA ("fp8v2v"); fp32 BatchNorm statistics, master weights, optimiser.
                 # Not parity modes -- their loss values are printed next to the fp32 leg's, same seeds.  (Round 3's "bf16" mode -- bf16 MFMA over fp32
                 # activations -- is still selectable: --train-dtype bf16.)
-                result["train_mixed"] = sub_leg(["--train", "--train-dtype", "act16", "--batch", "8", "--steps", "6", "--warmup", "2"], 600)
-                result["train_mixed_b16"] = sub_leg(["--train", "--train-dtype", "act16", "--batch", "16", "--steps", "5", "--warmup", "2", "--no-pmc-leg"], 600)
+                result["train_mixed"] = sub_leg(["--full", "--train", "--train-dtype", "act16", "--batch", "8", "--steps", "6", "--warmup", "2"], 600)
+                result["train_mixed_b16"] = sub_leg(["--full", "--train", "--train-dtype", "act16", "--batch", "16", "--steps", "5", "--warmup", "2", "--no-pmc-leg"], 600)
                 # 32 samples per GPU per step: 147 GB of the 288 GB -- the batch this memory is for (the step's ~620 dependent launches per direction are
                 # latency-bound at 8 samples: 32 images per BatchNorm layer; DESIGN.md "Round 5")
-                result["train_mixed_b32"] = sub_leg(["--train", "--train-dtype", "act16", "--batch", "32", "--steps", "4", "--warmup", "2", "--no-pmc-leg"], 900)
+                result["train_mixed_b32"] = sub_leg(["--full", "--train", "--train-dtype", "act16", "--batch", "32", "--steps", "4", "--warmup", "2", "--no-pmc-leg"], 900)
                 # 'fp8v2v' (act16 + e4m3 V2V convolutions) is NOT a default timing leg any more (VERDICT r4 "next" 1: faster than act16 or out): measured at
                 # 139.1 vs 143.6 samples/s -- V2V's 3x3x3 layers at 32-128 channels are not MFMA-bound (the fp8 halo kernel: 99 us vs bf16's 104), so
                 # e4m3 operands cannot pay for their amax / quantise passes.  Still selectable (--train --train-dtype fp8v2v), gated as a whole step
                 # (tests/test_gpu_train.py) and part of the trajectory leg below.
                 result["train_fp8v2v_note"] = "not timed by default: slower than act16 (139.1 vs 143.6 samples/s, round 5) -- bench.py --train --train-dtype fp8v2v"
                 # the SAME run in the three precisions: identical weights, one fixed batch of 4 samples, identical rotations, 20 Adam updates (VERDICT r4 "next" 1b)
-                result["train_trajectory"] = sub_leg(["--train-trajectory", "--batch", "4", "--steps", "20"], 900)
+                result["train_trajectory"] = sub_leg(["--full", "--train-trajectory", "--batch", "4", "--steps", "20"], 900)
                 for k in ("train", "train_mixed", "train_mixed_b16", "train_mixed_b32", "train_trajectory"):
                     emit_detail(k, result[k])
         if cpu_base is not None:
@@ -1152,13 +1167,13 @@ def main():
     barrier()
     if rank == 0:
         emit_detail("full", result)
-        if not args.full_line and not args.no_extras:          # (the default run only: the child legs would overwrite it)
+        if not args.full_line and not args.no_extras:          # (the top-level --full run only: the child legs would overwrite it)
             try:
                 os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
                 json.dump(result, open(os.path.join(ROOT, "gpurun_out", "bench_full.json"), "w"), indent=1)
             except OSError:
                 pass
-        print(json.dumps(result if args.full_line else compact_line(result)))
+        print(json.dumps(result if args.full_line else compact_line(result, full=args.full)))
     lt_dist.shutdown()
 
 

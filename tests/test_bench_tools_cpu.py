@@ -157,3 +157,25 @@ def test_dump_outputs_writes_the_forward_tuple_within_budget(tmp_path):
         assert np.array_equal(np.load(str(tmp_path / "a" / (n + ".npy"))), np.load(str(tmp_path / "b" / (n + ".npy")))), n
     fs = np.load(str(tmp_path / "a" / "features.npy"))
     assert np.isin(fs, feats.float().numpy().ravel()).all()
+
+
+def test_plain_line_carries_the_headline_and_points_to_no_full_record():
+    """compact_line(full=False) is the line of a plain run, which writes no full record: the same line as compact_line() of the same record, headline
+    figures included, less the ``full_record`` pointer and nothing else.  (That a plain run computes none of the --full blocks is tests/test_gpu_bench.py's.)"""
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r06_bench_bf16_full_record.json")))
+    with_pointer, plain = bench.compact_line(full), bench.compact_line(full, full=False)
+    assert "full_record" in with_pointer and "full_record" not in plain
+    assert plain == {k: v for k, v in with_pointer.items() if k != "full_record"}
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert plain[k] == full[k] or abs(plain[k] - full[k]) <= 1e-5 * abs(full[k]), k
+
+
+@pytest.mark.parametrize("extra", [["--ops-json", "ops.json"], ["--force-pmc-leg"], ["--fp32-parity-batch", "2"]])
+def test_options_that_measure_more_than_the_headline_need_full(extra):
+    """--ops-json / --force-pmc-leg / --fp32-parity-batch ask for what only a --full run measures: without --full the command is refused up front
+    (before any GPU work) instead of silently printing a line without it."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"] + extra, capture_output=True, text=True,
+                       timeout=300, cwd=ROOT, env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
+    assert r.returncode == 2 and "need --full" in r.stderr, r.stderr[-1000:]

@@ -19,7 +19,7 @@ tests_all)
   echo "all rc=$?"; tail -8 $OUT/test_all.log
   ;;
 bench)        # the driver's command
-  timeout 1500 python bench.py --ops-json $OUT/bench_ops_bf16.json > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err
+  timeout 1500 python bench.py --full --ops-json $OUT/bench_ops_bf16.json > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err
   echo "bench rc=$?"; python - <<PY
 import json
 try:

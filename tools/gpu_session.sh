@@ -33,11 +33,11 @@ tests)
 train)
   # BASELINE config 5 in its present form: fp32 training step (fwd + bwd + Adam) at 4 and 8 samples per step, and its kernel profile
   for B in 4 8; do
-    timeout 600 python bench.py --train --steps 10 --warmup 3 --batch $B > $OUT/bench_train_b$B.json 2> $OUT/bench_train_b$B.err
+    timeout 600 python bench.py --full --train --steps 10 --warmup 3 --batch $B > $OUT/bench_train_b$B.json 2> $OUT/bench_train_b$B.err
     echo "bench train B=$B rc=$?" | tee -a $OUT/session.log; cat $OUT/bench_train_b$B.json | tee -a $OUT/session.log
   done
   for B in 4 8; do
-    timeout 600 python bench.py --train --train-dtype bf16 --steps 10 --warmup 3 --batch $B > $OUT/bench_train_bf16mma_b$B.json 2> $OUT/bench_train_bf16mma_b$B.err
+    timeout 600 python bench.py --full --train --train-dtype bf16 --steps 10 --warmup 3 --batch $B > $OUT/bench_train_bf16mma_b$B.json 2> $OUT/bench_train_bf16mma_b$B.err
     echo "bench train bf16-MFMA B=$B rc=$?" | tee -a $OUT/session.log; cat $OUT/bench_train_bf16mma_b$B.json | tee -a $OUT/session.log
   done
   rm -rf $OUT/prof_train
@@ -50,12 +50,12 @@ smoke)
   ;;
 bench)
   # the driver's command; the line carries the fp32 parity-mode leg, the parity block and the batch sweep
-  timeout 900 python bench.py --ops-json $OUT/bench_ops_bf16.json > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err
+  timeout 900 python bench.py --full --ops-json $OUT/bench_ops_bf16.json > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err
   echo "bench bf16 rc=$?" | tee -a $OUT/session.log; cat $OUT/bench_bf16.json | tee -a $OUT/session.log; tail -3 $OUT/bench_bf16.err
   ;;
 c4)
   # BASELINE config 4: 8 views, 128^3 voxels (B = 8 per step by default)
-  timeout 900 python bench.py --views 8 --volume 128 --steps 10 --warmup 3 --ops-json $OUT/bench_ops_c4.json > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+  timeout 900 python bench.py --full --views 8 --volume 128 --steps 10 --warmup 3 --ops-json $OUT/bench_ops_c4.json > $OUT/bench_c4.json 2> $OUT/bench_c4.err
   echo "bench c4 rc=$?" | tee -a $OUT/session.log; cat $OUT/bench_c4.json | tee -a $OUT/session.log; tail -3 $OUT/bench_c4.err
   ;;
 prof)
@@ -103,7 +103,7 @@ abenv)
         LIB_*) E="LT_HIP_LIB=$PWD/learnable-triangulation-pytorch_amd/lib/liblt_hip_${v#LIB_}.so" ;;
         *) E="$v=1" ;;
       esac
-      env $E timeout 600 python bench.py --no-cpu-baseline --no-profile --steps 10 --warmup 3 > $OUT/ab_${v}_$round.json 2> $OUT/ab_${v}_$round.err
+      env $E timeout 600 python bench.py --full --no-cpu-baseline --no-profile --steps 10 --warmup 3 > $OUT/ab_${v}_$round.json 2> $OUT/ab_${v}_$round.err
       echo "ab $v round $round: $(python -c "import json;d=json.load(open('$OUT/ab_${v}_$round.json'));print('%.1f samples/s %.2f ms/step'%(d['value'],d['ms_per_step']))")" | tee -a $OUT/session.log
     done
   done
@@ -137,18 +137,18 @@ tracehalo)
 nst)
   # A/B: 2-stage vs 3-stage LDS-DMA ring in the v2 conv kernels
   for n in 2 3; do
-    LT_CONV_NST=$n timeout 600 python bench.py --no-cpu-baseline --steps 10 --warmup 3 --ops-json $OUT/bench_ops_bf16_nst$n.json > $OUT/bench_bf16_nst$n.json 2> $OUT/bench_bf16_nst$n.err
+    LT_CONV_NST=$n timeout 600 python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 --ops-json $OUT/bench_ops_bf16_nst$n.json > $OUT/bench_bf16_nst$n.json 2> $OUT/bench_bf16_nst$n.err
     echo "bench nst=$n rc=$?" | tee -a $OUT/session.log; cut -c1-140 $OUT/bench_bf16_nst$n.json | tee -a $OUT/session.log
   done
   ;;
 ab)
   # A/B: v1 (register staged) vs v2 (LDS-DMA) conv kernels, and batch-size sweep
   if [ -n "${WITH_V1:-}" ]; then
-  LT_CONV_V1=1 timeout 600 python bench.py --no-cpu-baseline --steps 10 --warmup 3 --ops-json $OUT/bench_ops_bf16_v1.json > $OUT/bench_bf16_v1.json 2> $OUT/bench_bf16_v1.err
+  LT_CONV_V1=1 timeout 600 python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 --ops-json $OUT/bench_ops_bf16_v1.json > $OUT/bench_bf16_v1.json 2> $OUT/bench_bf16_v1.err
   echo "bench v1 rc=$?" | tee -a $OUT/session.log; cut -c1-400 $OUT/bench_bf16_v1.json | tee -a $OUT/session.log
   fi
   for b in 1 4 16 32; do
-    timeout 600 python bench.py --no-cpu-baseline --no-profile --steps 10 --warmup 3 --batch $b > $OUT/bench_bf16_b$b.json 2> $OUT/bench_bf16_b$b.err
+    timeout 600 python bench.py --full --no-cpu-baseline --no-profile --steps 10 --warmup 3 --batch $b > $OUT/bench_bf16_b$b.json 2> $OUT/bench_bf16_b$b.err
     echo "bench B=$b rc=$?" | tee -a $OUT/session.log; cut -c1-330 $OUT/bench_bf16_b$b.json | tee -a $OUT/session.log
   done
   ;;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-layer diff of two `bench.py --ops-json` tables (same plan, two library variants): where did the time move?
+"""Per-layer diff of two `bench.py --full --ops-json` tables (same plan, two library variants): where did the time move?
 Usage: python tools/ops_diff.py A.json B.json [--top 25]"""
 import collections
 import json

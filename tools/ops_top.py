@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Aggregate a bench.py --ops-json file by layer label: time, launches, TFLOP/s and algorithmic GB/s per group."""
+"""Aggregate a bench.py --full --ops-json file by layer label: time, launches, TFLOP/s and algorithmic GB/s per group."""
 import collections
 import json
 import sys

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """The CURRENT state of the bf16 forward as one markdown table (VERDICT r5 "next" 8): which kernel runs which group of layers, how long it
-takes and at what fraction of its roof, at 64 / 8 / 1 samples per step -- generated from ``bench.py --batch B --ops-json`` files (an event pair around
+takes and at what fraction of its roof, at 64 / 8 / 1 samples per step -- generated from ``bench.py --full --batch B --ops-json`` files (an event pair around
 every launch of the recorded plan):
 
     python tools/plan_table.py profiles/r06_bench_ops_bf16_b64.json profiles/r06_bench_ops_bf16_b8.json profiles/r06_bench_ops_bf16_b1.json

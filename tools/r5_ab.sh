@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_kernels.py -m gpu -q --tb=short -p n
 timeout 900 python -m pytest tests/test_gpu_models.py -m gpu -q --tb=short -p no:cacheprovider 2>&1 | tail -3
 for v in on off on off; do
   E="LT_X=1"; [ $v = off ] && E="$V=1"
-  env $E timeout 600 python bench.py --no-extras --no-cpu-baseline --no-pmc-leg --ops-json $OUT/ab_ops_$v.json > $OUT/ab_bench_$v.json 2> $OUT/ab_bench_$v.err
+  env $E timeout 600 python bench.py --full --no-extras --no-cpu-baseline --no-pmc-leg --ops-json $OUT/ab_ops_$v.json > $OUT/ab_bench_$v.json 2> $OUT/ab_bench_$v.err
   echo "bench $v ($E) rc=$?"; python -c "import json;d=json.load(open('$OUT/ab_bench_$v.json'));print('$v', d['value'], d['ms_per_step'], d['roofline']['frac'])"
 done
 python - <<'PY'

@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_models.py -m gpu -q --tb=short -p no
 for rep in 1 2; do
 for v in off on; do
   E="LT_X=1"; [ $v = off ] && E="${1:-LT_DECONV_NO_H2D}=1"
-  env $E timeout 600 python bench.py --no-extras --no-cpu-baseline --no-pmc-leg --ops-json $OUT/h2d_ops_$v.json > $OUT/h2d_bench_$v.json 2> $OUT/h2d_bench_$v.err
+  env $E timeout 600 python bench.py --full --no-extras --no-cpu-baseline --no-pmc-leg --ops-json $OUT/h2d_ops_$v.json > $OUT/h2d_bench_$v.json 2> $OUT/h2d_bench_$v.err
   echo "bench $v ($E) rc=$?  $(python -c "import json;d=json.load(open('$OUT/h2d_bench_$v.json'));print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"
 done
 done

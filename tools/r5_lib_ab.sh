@@ -8,7 +8,7 @@ L=$R/learnable-triangulation-pytorch_amd/lib
 for rep in 1 2; do
   for v in base "$@"; do
     lib=$L/liblt_hip.so; [ $v != base ] && lib=$L/liblt_hip_$v.so
-    LT_HIP_LIB=$lib timeout 600 python bench.py --no-extras --no-cpu-baseline --no-pmc-leg --ops-json $OUT/lab_ops_${v}.json > $OUT/lab_bench_${v}_$rep.json 2> $OUT/lab_bench_${v}_$rep.err
+    LT_HIP_LIB=$lib timeout 600 python bench.py --full --no-extras --no-cpu-baseline --no-pmc-leg --ops-json $OUT/lab_ops_${v}.json > $OUT/lab_bench_${v}_$rep.json 2> $OUT/lab_bench_${v}_$rep.err
     echo "bench $v rep $rep rc=$?  $(python -c "import json;d=json.load(open('$OUT/lab_bench_${v}_$rep.json'));print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"
   done
 done

@@ -14,7 +14,7 @@ smoke)
   timeout 600 python __graft_entry__.py smoke > $OUT/v_smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $OUT/v_smoke.log
   ;;
 bench)
-  timeout 1800 python bench.py --ops-json $OUT/v_bench_ops.json > $OUT/v_bench.json 2> $OUT/v_bench.err
+  timeout 1800 python bench.py --full --ops-json $OUT/v_bench_ops.json > $OUT/v_bench.json 2> $OUT/v_bench.err
   echo "bench rc=$?"; wc -c $OUT/v_bench.json; cat $OUT/v_bench.json
   ;;
 prof)

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out; mkdir -p $OUT; cd $R
 export PYTHONDONTWRITEBYTECODE=1
 timeout 900 python -m pytest tests/test_gpu_kernels.py -m gpu -q --tb=short -p no:cacheprovider -x -k "halo or conv_all_tiles" 2>&1 | tail -3
 for v in 0 1 9; do
-  LT_HALO_F3=$v timeout 600 python bench.py --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/f3_ops_$v.json > $OUT/f3_$v.json 2> $OUT/f3_$v.err
+  LT_HALO_F3=$v timeout 600 python bench.py --full --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/f3_ops_$v.json > $OUT/f3_$v.json 2> $OUT/f3_$v.err
 done
 python - <<'PY'
 import json

@@ -3,7 +3,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out; mkdir -p $OUT; cd $R
 export PYTHONDONTWRITEBYTECODE=1
 for i in 1 2; do
-timeout 600 python bench.py --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/f32b_ops.json > $OUT/f32b.json 2> $OUT/f32b.err
+timeout 600 python bench.py --full --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/f32b_ops.json > $OUT/f32b.json 2> $OUT/f32b.err
 python -c "
 import json; d=json.load(open('gpurun_out/f32b.json')); print('fp32 forward %.1f samples/s, %.3f' % (d['value'], d['roofline']['frac']))"
 done

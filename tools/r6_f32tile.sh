@@ -4,7 +4,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out; mkdir -p $OUT; cd $R
 export PYTHONDONTWRITEBYTECODE=1
 for t in 0 2 5; do
-  timeout 600 python bench.py --dtype fp32 --tile $t --no-cpu-baseline --no-extras --no-pmc-leg --steps 3 --warmup 1 --full-line --ops-json $OUT/ft_ops_$t.json > $OUT/ft_$t.json 2> $OUT/ft_$t.err
+  timeout 600 python bench.py --full --dtype fp32 --tile $t --no-cpu-baseline --no-extras --no-pmc-leg --steps 3 --warmup 1 --full-line --ops-json $OUT/ft_ops_$t.json > $OUT/ft_$t.json 2> $OUT/ft_$t.err
 done
 python - <<'PY'
 import json, re, collections

@@ -6,8 +6,8 @@ export PYTHONDONTWRITEBYTECODE=1
 timeout 900 python -m pytest tests/test_gpu_kernels.py -m gpu -q --tb=short -p no:cacheprovider -x -k "halo" 2>&1 | tail -5
 timeout 1200 python -m pytest tests/test_gpu_models.py tests/test_gpu_plan_abi.py -m gpu -q --tb=short -p no:cacheprovider -x -k "fp32 or golden or f32" 2>&1 | tail -5
 for i in 1 2; do
-  timeout 600 python bench.py --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/f7_ops_new.json > $OUT/f7_new.json 2> $OUT/f7_new.err
-  LT_HALO_NO_F7=1 timeout 600 python bench.py --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/f7_ops_old.json > $OUT/f7_old.json 2> $OUT/f7_old.err
+  timeout 600 python bench.py --full --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/f7_ops_new.json > $OUT/f7_new.json 2> $OUT/f7_new.err
+  LT_HALO_NO_F7=1 timeout 600 python bench.py --full --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/f7_ops_old.json > $OUT/f7_old.json 2> $OUT/f7_old.err
   python - <<'PY'
 import json
 for t in ("new", "old"):

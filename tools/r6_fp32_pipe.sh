@@ -9,7 +9,7 @@ timeout 600 python tools/trace_kstep.py --dtype fp32 --batch 64 --only "rn l3,rn
 L=$R/learnable-triangulation-pytorch_amd/lib
 for v in pipe nopipe pipe nopipe; do
   E="LT_X=1"; [ $v = nopipe ] && E="LT_HIP_LIB=$L/liblt_hip_nopipe.so"
-  env $E timeout 600 python bench.py --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/ab_ops_fp32_$v.json > $OUT/ab_fp32_$v.json 2> $OUT/ab_fp32_$v.err
+  env $E timeout 600 python bench.py --full --dtype fp32 --no-cpu-baseline --no-extras --no-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/ab_ops_fp32_$v.json > $OUT/ab_fp32_$v.json 2> $OUT/ab_fp32_$v.err
   echo "fp32 $v rc=$?: $(python -c "import json;d=json.load(open('$OUT/ab_fp32_$v.json'));print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"
 done
 python tools/ops_top.py $OUT/ab_ops_fp32_pipe.json 12

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_models.py -m gpu -q --tb=short -p no
 timeout 900 python -m pytest tests/test_gpu_kernels.py -m gpu -q --tb=short -p no:cacheprovider -k "expand_reduce or conv2d_halo or deconv4x4" > $OUT/test_kernels_xr.log 2>&1; echo "kernels xr rc=$?"; tail -3 $OUT/test_kernels_xr.log
 timeout 1500 python -m pytest tests/test_gpu_train.py -m gpu -q --tb=short -p no:cacheprovider > $OUT/test_train.log 2>&1; echo "train rc=$?"; tail -8 $OUT/test_train.log
 for v in 3 4 3 4; do
-  LT_XR_NPB=$v timeout 600 python bench.py --no-extras --no-cpu-baseline --no-pmc-leg --ops-json $OUT/ab_ops_npb$v.json > $OUT/ab_npb$v.json 2> $OUT/ab_npb$v.err
+  LT_XR_NPB=$v timeout 600 python bench.py --full --no-extras --no-cpu-baseline --no-pmc-leg --ops-json $OUT/ab_ops_npb$v.json > $OUT/ab_npb$v.json 2> $OUT/ab_npb$v.err
   echo "xr npb=$v rc=$?: $(python -c "import json;d=json.load(open('$OUT/ab_npb$v.json'));print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"
 done
 python tools/ops_top.py $OUT/ab_ops_npb3.json 3; python tools/ops_top.py $OUT/ab_ops_npb4.json 3

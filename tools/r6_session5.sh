@@ -11,5 +11,5 @@ find $OUT/prof_train -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT
 rm -rf $OUT/prof_train
 cd $R
 bash tools/r6_train_pmc.sh 2>&1 | tail -30
-timeout 600 python bench.py --dtype fp32 --no-cpu-baseline --no-extras --force-pmc-leg --steps 5 --warmup 2 --full-line > $OUT/bench_fp32_pmc.json 2> $OUT/bench_fp32_pmc.err; echo "fp32 pmc rc=$?"
+timeout 600 python bench.py --full --dtype fp32 --no-cpu-baseline --no-extras --force-pmc-leg --steps 5 --warmup 2 --full-line > $OUT/bench_fp32_pmc.json 2> $OUT/bench_fp32_pmc.err; echo "fp32 pmc rc=$?"
 python -c "import json;d=json.load(open('$OUT/bench_fp32_pmc.json'));print(d['value'], json.dumps(d['roofline']))"

@@ -26,7 +26,7 @@ smoke)
   timeout 600 python __graft_entry__.py smoke > $OUT/v_smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $OUT/v_smoke.log
   ;;
 bench)
-  timeout 2400 python bench.py --ops-json $OUT/v_bench_ops.json > $OUT/v_bench.json 2> $OUT/v_bench.err
+  timeout 2400 python bench.py --full --ops-json $OUT/v_bench_ops.json > $OUT/v_bench.json 2> $OUT/v_bench.err
   echo "bench rc=$?"; wc -c $OUT/v_bench.json; cat $OUT/v_bench.json
   ;;
 prof)
@@ -57,7 +57,7 @@ trainpmc)
   bash tools/r6_train_pmc.sh 2>&1 | tail -12
   ;;
 fp32)
-  timeout 600 python bench.py --dtype fp32 --no-cpu-baseline --no-extras --force-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/v_bench_ops_fp32.json > $OUT/v_bench_fp32.json 2> $OUT/v_bench_fp32.err; echo "fp32 rc=$?"
+  timeout 600 python bench.py --full --dtype fp32 --no-cpu-baseline --no-extras --force-pmc-leg --steps 5 --warmup 2 --full-line --ops-json $OUT/v_bench_ops_fp32.json > $OUT/v_bench_fp32.json 2> $OUT/v_bench_fp32.err; echo "fp32 rc=$?"
   python -c "import json;d=json.load(open('$OUT/v_bench_fp32.json'));print(d['value'], json.dumps(d['roofline']))"
   ;;
 esac
