@@ -515,6 +515,26 @@ int lt_triangulate_ransac(const float* proj, const int64_t* points, const int32_
 int lt_crop_resize_u8(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int32_t N, int32_t H, int32_t W,
                       const float* lut, float* out, void* stream);
 
+/* lt_crop_resize_u8 with on-the-fly lens undistortion in front, for views cut from raw (distorted) frames: crop pixel (y, x) of a view is
+ * pixel (upper + y, left + x) of cv2.remap(frame, map1, map2, INTER_CUBIC) (OpenCV 4.x, 8UC3, constant border 0: 4 x 4 taps from
+ * (map1.x - 1, map1.y - 1), 15-bit fixed-point Keys weights A = -0.75 of initInterTab2D indexed by map2, taps outside the frame read 0,
+ * saturate_u8((sum + (1 << 14)) >> 15)), zero where the bbox leaves the frame; then the same INTER_AREA branches and LUT as
+ * lt_crop_resize_u8, one launch for N views.  The maps are built on the host (mvn/utils/img.py:undistort_maps) and only read here.
+ *   src      flat uint8 buffer of HWC 3-channel source windows, src_bytes long;
+ *   desc     N x 14 int64 per view: [0] byte offset of the source window into src, [1] window height, [2] width, [3] row pitch in
+ *            bytes, [4] window x0, [5] y0 in the frame (the window lies inside the frame and must hold every in-frame tap of the
+ *            bbox's pixels: mvn/utils/img.py:source_window; a tap outside the window reads 0), [6] frame height, [7] frame width (the
+ *            remap's border), [8] bbox left, [9] upper, [10] right, [11] lower in frame coordinates (may leave the frame), [12] byte
+ *            offset of the view's map into maps (a multiple of 8), [13] map row pitch in entries (>= frame width);
+ *   maps     int16 blocks, 8-byte aligned, maps_bytes long: entry (y, x) of a map = maps[offset / 2 + 4 * (y * pitch + x) + 0..3] =
+ *            (map1 x, map1 y, map2, 0) of frame pixel (y, x) (mvn/utils/img.py:device_map); a map covers the whole frame;
+ *   desc_host the same N x 14 records on the host, or NULL: when given, an empty bbox, a bad frame size, a window outside the frame or
+ *            past src_bytes, a bad pitch, or a map past maps_bytes is LT_ERR_INVALID before anything is enqueued (without it the
+ *            device trusts desc; an empty bbox writes zeros);
+ *   out      N x 3 x H x W fp32.  W <= 2048, N <= 65535, frame sides <= 32767. */
+int lt_undistort_crop_resize_u8(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, const int16_t* maps,
+                                int64_t maps_bytes, int32_t N, int32_t H, int32_t W, const float* lut, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Chain of up to LT_PWCHAIN_MAX pointwise (1x1x1) convolutions evaluated per voxel without the
  * intermediate activations leaving the registers:  y = L_n(...L_1(x)),

@@ -166,6 +166,7 @@ SIGNATURES = {
     "lt_heatmap_argmax_nchw_f32": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "lt_triangulate_ransac": (C.c_int, [vp, vp, vp, i32, C.c_double, i32, vp, vp, i32, i32, i32, vp]),
     "lt_crop_resize_u8": (C.c_int, [vp, i64, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "lt_undistort_crop_resize_u8": (C.c_int, [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]),
     "lt_bn_act_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]),
     "lt_bn_act_bwd_workspace": (C.c_size_t, [i64, i32]),
     "lt_bn_act_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, f32, i32, vp, vp]),

@@ -9,6 +9,15 @@ parity with a cv2 run holds only for losslessly stored frames.
 view) and ``bboxes`` (the crop box the CPU path would use, frame coordinates) instead of ``images``; cameras,
 ``image_shapes_before_resize``, ``detections`` and ``keypoints_3d`` are exactly those of the CPU path.  Collate such items with
 ``make_collate_fn`` and upload them with ``prepare_batch_frames`` (one kernel launch crops, resizes and normalises every view).
+
+``undistort_on_the_fly=True`` (with ``undistort_images=True``) reads the raw ``imageSequence/`` frames and undistorts each view's
+crop as it is prepared, instead of reading the ``imageSequence-undistorted/`` copies the reference's offline pass
+(human36m_preprocessing/undistort-h36m.py) writes: the view is the bbox crop of cv2.remap(raw frame, maps, INTER_CUBIC) with that
+pass's maps (mvn/utils/img.py:undistort_maps, built once per camera and frame size).  Cameras, shapes, detections and targets are
+those of the ``undistort_images=True`` file path.  The pixels are the remap of the decoded raw frame, so they differ from the
+offline pass's output by the JPEG generation that pass adds when it writes its copy.  With ``defer_image_ops`` the item also carries
+``undistort``: per view (K (3, 3) float32 and dist (5,) float32 of the labels file, (frame height, frame width)), the key of the
+camera's maps, and ``prepare_batch_frames`` runs the undistortion in its one launch.
 """
 import os
 from collections import defaultdict
@@ -18,7 +27,7 @@ from PIL import Image
 from torch.utils.data import Dataset
 
 from mvn.datasets import evaluation
-from mvn.utils.img import crop_image, normalize_image, resize_image, scale_bbox
+from mvn.utils.img import crop_image, normalize_image, resize_image, scale_bbox, undistort_crop_u8, undistort_maps
 from mvn.utils.multiview import Camera
 
 try:
@@ -42,13 +51,14 @@ def imread_bgr(path):
 class Human36MMultiViewDataset(Dataset):
     """Human3.6M for multi-view tasks.  ``labels_path``: the 'human36m-multiview-labels-*.npy' dict; ``h36m_root``: its 'processed/'
     image tree.  ``kind`` 'mpii' (16 joints) or 'human36m' (17); ``ignore_cameras``: camera indices to drop;
-    ``retain_every_n_frames_in_test``: keep every n-th test frame; ``defer_image_ops``: see the module docstring."""
+    ``retain_every_n_frames_in_test``: keep every n-th test frame; ``defer_image_ops``, ``undistort_on_the_fly``: see the module
+    docstring."""
 
     def __init__(self, h36m_root='/Vol1/dbstore/datasets/Human3.6M/processed/',
                  labels_path='/Vol1/dbstore/datasets/Human3.6M/extra/human36m-multiview-labels-SSDbboxes.npy',
                  pred_results_path=None, image_shape=(256, 256), train=False, test=False, retain_every_n_frames_in_test=1,
                  with_damaged_actions=False, cuboid_side=2000.0, scale_bbox=1.5, norm_image=True, kind="mpii", undistort_images=False,
-                 ignore_cameras=[], crop=True, defer_image_ops=False):
+                 ignore_cameras=[], crop=True, defer_image_ops=False, undistort_on_the_fly=False):
         assert train or test, "`Human36MMultiViewDataset` must be constructed with at least one of `test=True` / `train=True`"
         assert kind in ("mpii", "human36m")
         self.h36m_root = h36m_root
@@ -64,6 +74,11 @@ class Human36MMultiViewDataset(Dataset):
         self.defer_image_ops = defer_image_ops
         if defer_image_ops:
             assert self.image_shape is not None, "defer_image_ops needs an image_shape (the kernel's output size)"
+        if undistort_on_the_fly and not undistort_images:
+            raise ValueError("undistort_on_the_fly=True undistorts raw frames in place of the undistort_images=True files: "
+                             "it needs undistort_images=True")
+        self.undistort_on_the_fly = undistort_on_the_fly
+        self._maps = {}
 
         self.labels = np.load(labels_path, allow_pickle=True).item()
         n_cameras = len(self.labels['camera_names'])
@@ -99,8 +114,20 @@ class Human36MMultiViewDataset(Dataset):
         return len(self.labels['table'])
 
     def image_path(self, subject, action, camera_name, frame_idx):
-        folder = 'imageSequence' + ('-undistorted' if self.undistort_images else '')
+        folder = 'imageSequence' + ('-undistorted' if self.undistort_images and not self.undistort_on_the_fly else '')
         return os.path.join(self.h36m_root, subject, action, folder, camera_name, 'img_%06d.jpg' % (frame_idx + 1))
+
+    def undistort_key(self, cam, frame_hw):
+        """(K, dist, (h, w)) of a labels-file camera: what the camera's undistortion maps depend on."""
+        return (np.array(cam['K'], dtype=np.float32), np.array(cam['dist'], dtype=np.float32).reshape(-1), tuple(int(x) for x in frame_hw))
+
+    def undistortion_maps(self, key):
+        """undistort_maps of a camera and frame size, built once per dataset (worker) and kept."""
+        K, dist, (h, w) = key
+        k = (K.tobytes(), dist.tobytes(), h, w)
+        if k not in self._maps:
+            self._maps[k] = undistort_maps(K, dist, h, w)
+        return self._maps[k]
 
     def __getitem__(self, idx):
         sample = defaultdict(list)
@@ -132,8 +159,13 @@ class Human36MMultiViewDataset(Dataset):
                 sample['image_shapes_before_resize'].append(shape_before_resize)
                 sample['frames'].append(image)
                 sample['bboxes'].append(tuple(int(x) for x in crop_box))
+                if self.undistort_on_the_fly:
+                    sample['undistort'].append(self.undistort_key(cam, image.shape[:2]))
             else:
-                if self.crop:
+                if self.undistort_on_the_fly:
+                    maps = self.undistortion_maps(self.undistort_key(cam, image.shape[:2]))
+                    image = undistort_crop_u8(image, maps, tuple(int(x) for x in crop_box))
+                elif self.crop:
                     image = crop_image(image, bbox)
                 if self.image_shape is not None:
                     shape_before_resize = image.shape[:2]

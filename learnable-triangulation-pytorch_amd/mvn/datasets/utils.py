@@ -30,6 +30,8 @@ def make_collate_fn(randomize_n_views=True, min_n_views=10, max_n_views=31):
         else:
             batch["frames"] = [[item["frames"][i] for item in items] for i in indexes]       # list[NV] of list[B] of uint8 (h, w, 3)
             batch["bboxes"] = np.array([[item["bboxes"][i] for item in items] for i in indexes]).swapaxes(0, 1)   # (B, NV, 4)
+            if "undistort" in items[0]:      # undistort_on_the_fly: per view (K, dist, frame (h, w)), the key of its camera's maps
+                batch["undistort"] = [[item["undistort"][i] for item in items] for i in indexes]
         batch["detections"] = np.array([[item["detections"][i] for item in items] for i in indexes]).swapaxes(0, 1)
         batch["cameras"] = [[item["cameras"][i] for item in items] for i in indexes]
         batch["keypoints_3d"] = [item["keypoints_3d"] for item in items]
@@ -104,7 +106,12 @@ def prepare_batch_frames(batch, device, image_shape, norm_image=True):
     coordinates.  Only the bytes of bbox & frame travel: the host packs them, with the view descriptors in front, into one pinned
     block (same ring discipline as prepare_batch), one asynchronous H2D copy moves it, and one lt_crop_resize_u8 launch crops,
     resizes (INTER_AREA) and normalises every view.  Returns the same 4-tuple as prepare_batch; the images are bitwise what
-    prepare_batch gives for the CPU-prepared items (normalize_image(resize_image(crop_image(...))) cast to fp32)."""
+    prepare_batch gives for the CPU-prepared items (normalize_image(resize_image(crop_image(...))) cast to fp32).
+
+    A batch that carries "undistort" (undistort_on_the_fly=True items: per view the (K, dist, frame (h, w)) of its camera) is
+    undistorted on the way: each camera's maps are built once and kept on the device (DeviceMapCache), only the source window of
+    every view travels (mvn/utils/img.py:source_window), and one lt_undistort_crop_resize_u8 launch remaps, crops, resizes and
+    normalises every view -- bitwise what prepare_batch gives for the CPU-prepared undistort_on_the_fly=True items."""
     from mvn.utils import img
     device = torch.device(device)
     if device.type != "cuda":
@@ -112,6 +119,20 @@ def prepare_batch_frames(batch, device, image_shape, norm_image=True):
     frames, bboxes = batch["frames"], np.asarray(batch["bboxes"], dtype=np.int64)
     nv, bs = len(frames), len(frames[0])
     n = bs * nv
+    H, W = int(image_shape[0]), int(image_shape[1])
+    out = torch.empty((bs, nv, 3, H, W), dtype=torch.float32, device=device)
+    if batch.get("undistort") is not None:
+        und = batch["undistort"]
+        cache = _map_cache(device)
+        views = [frames[v][b] for b in range(bs) for v in range(nv)]        # view n = b * NV + v: the (B, NV) order of the output
+        views_maps = [cache.get(und[v][b]) for b in range(bs) for v in range(nv)]
+        desc, regions, off = img.undistort_descriptors(views, bboxes.reshape(n, 4), views_maps)
+        dev, head = _upload(desc, regions, off, device)
+        with torch.cuda.device(device):
+            lut = img.normalize_lut(device) if norm_image else None
+            img.launch_undistort_crop_resize(dev[head:], dev[:head].view(torch.int64).view(n, img.UNDIST_DESC_FIELDS), desc, cache.arena,
+                                             (H, W), lut, out.view(n, 3, H, W))
+        return (out,) + _targets(batch, device)
     desc = np.zeros((n, img.DESC_FIELDS), np.int64)
     regions = []
     off = 0
@@ -126,6 +147,16 @@ def prepare_batch_frames(batch, device, image_shape, norm_image=True):
             desc[b * nv + v] = (off, y1 - y0, x1 - x0, 3 * (x1 - x0), l - x0, u - y0, r - x0, lo - y0)
             regions.append(reg)
             off += reg.size
+    dev, head = _upload(desc, regions, off, device)
+    with torch.cuda.device(device):
+        lut = img.normalize_lut(device) if norm_image else None
+        img.launch_crop_resize(dev[head:], dev[:head].view(torch.int64).view(n, img.DESC_FIELDS), desc, (H, W), lut, out.view(n, 3, H, W))
+    return (out,) + _targets(batch, device)
+
+
+def _upload(desc, regions, off, device):
+    """descriptors + the pixel regions they point at (desc[:, 0] = byte offset of each region after the descriptors) -> one pinned
+    block of the staging ring and one asynchronous H2D copy.  Returns (device uint8 tensor, byte length of the descriptors)."""
     head = desc.nbytes
     total = head + off
     cap = 1 << max(20, (total - 1).bit_length())          # power-of-two blocks: one ring serves batches of similar byte counts
@@ -142,9 +173,40 @@ def prepare_batch_frames(batch, device, image_shape, norm_image=True):
     dev = stage[:total].to(device, non_blocking=True)
     slot[1] = torch.cuda.Event()
     slot[1].record(torch.cuda.current_stream(device))
-    H, W = int(image_shape[0]), int(image_shape[1])
-    out = torch.empty((bs, nv, 3, H, W), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        lut = img.normalize_lut(device) if norm_image else None
-        img.launch_crop_resize(dev[head:], dev[:head].view(torch.int64).view(n, img.DESC_FIELDS), desc, (H, W), lut, out.view(n, 3, H, W))
-    return (out,) + _targets(batch, device)
+    return dev, head
+
+
+class DeviceMapCache:
+    """Undistortion maps of every camera seen so far, resident on one device: one int16 arena of mvn/utils/img.py:device_map blocks
+    (8 bytes per frame pixel, about 8 MB for a 1000 x 1000 camera), keyed by (K, dist, frame h, w).  A new camera builds its maps on
+    the host (img.undistort_maps), appends them to the arena (a reallocation on the current stream, so launches already queued keep
+    reading the old arena) and keeps map1 and its monotonicity for the source windows."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.arena = None
+        self.entries = {}
+
+    def get(self, key):
+        """key (K, dist, (h, w)) -> (map1, monotone, byte offset in the arena, row pitch in entries)."""
+        from mvn.utils import img
+        K, dist, (h, w) = key
+        K, dist = np.asarray(K, dtype=np.float32), np.asarray(dist, dtype=np.float32).reshape(-1)
+        k = (K.tobytes(), dist.tobytes(), int(h), int(w))
+        if k not in self.entries:
+            maps = img.undistort_maps(K, dist, int(h), int(w))
+            block = torch.from_numpy(img.device_map(maps).reshape(-1)).to(self.device)
+            off = 0 if self.arena is None else self.arena.numel() * 2
+            self.arena = block if self.arena is None else torch.cat([self.arena, block])
+            self.entries[k] = (maps[0], img.map_is_monotone(maps[0]), off, int(w))
+        return self.entries[k]
+
+
+_map_caches = {}
+
+
+def _map_cache(device):
+    device = torch.device(device)
+    if device not in _map_caches:
+        _map_caches[device] = DeviceMapCache(device)
+    return _map_caches[device]
