@@ -51,12 +51,16 @@ def conv_chunk_samples(N, per_sample):
     return nc
 
 
+def esize(dtype):
+    return torch.empty((), dtype=dtype).element_size()
+
+
 def k_step_of(dtype):
-    return 128 // torch.empty((), dtype=dtype).element_size()  # elements per 128-byte K step: 32 fp32 / 64 bf16 / 128 fp8
+    return 128 // esize(dtype)  # elements per 128-byte K step: 32 fp32 / 64 bf16 / 128 fp8
 
 
 def min_cin_of(dtype):
-    return 16 // torch.empty((), dtype=dtype).element_size()   # one 16-byte vector per pixel
+    return 16 // esize(dtype)   # one 16-byte vector per pixel
 
 
 @dataclass
@@ -207,6 +211,13 @@ def make_conv_spec(weight, bias, bn, in_shape, stride, pad, dtype, transposed=Fa
     return spec
 
 
+def stage_images(x, act, stream):
+    """The caller's images ``x`` (N,C,H,W), fp32 and contiguous, into a plan's channels-last input ``act`` [N,1,H,W,c_pad] on ``stream``: one lt_nchw_to_nhwc pass
+    that rounds to the Act's element type and zero-fills the padded channels."""
+    N, Cc, Hh, W = x.shape
+    H.check(H.lib().lt_nchw_to_nhwc(H.dtype_code(act.t.dtype), x.data_ptr(), act.t.data_ptr(), N, Cc, Hh * W, act.t.shape[-1], stream), "lt_nchw_to_nhwc")
+
+
 class Act:
     """A channels-last activation: tensor [N, D, H, W, C] (D == 1 for 2D maps)."""
     __slots__ = ("t", "pooled")
@@ -220,7 +231,23 @@ class Act:
         return tuple(self.t.shape)
 
 
-class PlanBuilder:
+class Recorder:
+    """What a module's ``record(b, ...)`` may call on ``b``.  PlanBuilder (below) records an inference plan; lt_train.TrainTape runs and records a training
+    step.  Both provide ``alloc / release / const / conv / maxpool / global_avgpool`` and the attributes ``dtype`` and ``live_weights``.  A fused launch is
+    an OFFER of the recorder: ``record()`` asks ``can_<launch>(...)`` and only then calls ``<launch>(...)``.  The defaults here decline every offer, so a
+    recorder that has to see each layer on its own (the training tape: its backward needs the inner activations) gets it by defining nothing, and a new
+    fused launch is one more default here plus its rule in PlanBuilder."""
+
+    dtype = torch.float32
+    live_weights = False          # True: the weights are re-read from the Parameters at every run, nothing derived from their build-time values may be baked in
+
+    def _declines(self, *a, **k):
+        return False
+
+    can_conv_skip = can_conv_cat2 = can_chain_pointwise = can_bottleneck = can_bottleneck_ds = can_expand_reduce = can_stem_pool = _declines
+
+
+class PlanBuilder(Recorder):
     """Records liblt_hip launches; buffers are reused by exact byte size once released."""
 
     def __init__(self, device, dtype, tile_override=0, dry_run=False, stages=0):
@@ -230,8 +257,7 @@ class PlanBuilder:
         self.dry_run = dry_run
         if self.device.type != "cuda" and not dry_run:
             raise RuntimeError("liblt_hip plans run on the GPU only (device=%s); there is no CPU fallback" % device)
-        if not dry_run:
-            H.lib()
+        self.lib = None if dry_run else H.lib()          # what the recorded launches call; a dry-run plan never launches
         self.dtype = dtype
         self.code = H.dtype_code(dtype)
         # element type of outputs / residuals that are not fp32: the plan's own, except that fp8 (an OPERAND type of lt_conv_fwd only) stores bf16
@@ -258,7 +284,7 @@ class PlanBuilder:
     # ---- memory ---------------------------------------------------------------------------
     def alloc(self, shape, dtype=None):
         dtype = dtype or self.dtype
-        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+        n = int(np.prod(shape)) * esize(dtype)
         lst = self.pool.get((n, dtype))
         if lst:
             t = lst.pop().view(*shape)
@@ -289,10 +315,15 @@ class PlanBuilder:
         self.last_info = info or {}        # lt_train.TrainTape reads the device buffers of the op it has just recorded
         self.ops.append((fn, meta))
 
+    def _fusable(self):
+        """This builder may record a fused launch over build-time weights: they are not live, and no tile has been forced on lt_conv_fwd (tools, A/B runs).
+        Whether the plan's dtype has the kernel is the lt_sel_* rule's own first test."""
+        return not (self.live_weights or self.tile_override)
+
     def can_conv_skip(self, x_shape, weight, skip_shape, skip_weight):
         """True when lt_conv_skip_fwd covers this convolution + computed residual: the second 3x3x3 convolution (32 -> 32) of a Res3DBlock whose skip
         connection is a 1x1x1 convolution of a 16-channel tensor (v2v.py:20-42, :76), over build-time weights (lt_sel_conv_skip)."""
-        if self.out_dtype != torch.bfloat16 or self.live_weights or self.tile_override:
+        if not self._fusable():
             return False
         return bool(H.lib().lt_sel_conv_skip(self.code, H.dims(x_shape), H.wshape(weight), H.dims(skip_shape), H.wshape(skip_weight)))
 
@@ -327,6 +358,30 @@ class PlanBuilder:
         name = "lt_conv_pack_weights32" if layout == 3 else "lt_conv_pack_weights"
         return lambda sp, dp, a=(spec.cout_pad, spec.k_pad): H.check(getattr(H.lib(), name)(sp, *a, dp, H.cur_stream()), name)
 
+    def _frag_copy(self, wdev, layout, spec, ntaps):
+        """(copy, pack): the uploaded [cout_pad][k_pad] weights ``wdev`` of one phase of ``spec`` in fragment layout ``layout``, packed once, here (a dry-run
+        plan's copy stays uninitialised), and the packer that filled it."""
+        wfr = torch.empty_like(wdev)
+        pack = self._frag_packer(layout, spec, ntaps)
+        if not self.dry_run:
+            pack(wdev.data_ptr(), wfr.data_ptr())
+        self.keep.append(wfr)
+        return wfr, pack
+
+    def _pack_layer(self, weight, bn, in_shape, pad, flags):
+        """One bias-free stride-1 convolution + BatchNorm inside a fused block launch (the twin of pack_block_layer, csrc/plan.hip): uploads its weights in
+        the fragment order of the 32x32x16 MFMA (layout 2), its scale and its shift, and counts its flops.  Returns (spec, weights, scale, shift), the last
+        three as the device pointers the block descriptors hold."""
+        spec = make_conv_spec(weight, None, bn, in_shape, 1, pad, self.dtype, False, flags)
+        ph = spec.phases[0]
+        ntaps = int(ph.taps.shape[0])
+        assert spec.cout_pad == spec.Cout and spec.k_pad == ntaps * spec.Cin, (spec.cout_pad, spec.k_pad)          # the kernels read unpadded matrices
+        wdev = self.const(ph.weight, self.dtype)
+        sc, sh = self.const(spec.scale), self.const(spec.shift)
+        wfr, _ = self._frag_copy(wdev, 2, spec, ntaps)
+        self.flops += 2 * spec.N * spec.Ho * spec.Wo * spec.Cout * ntaps * spec.Cin
+        return spec, wfr.data_ptr(), sc.data_ptr(), sh.data_ptr()
+
     def conv(self, x, weight, bias=None, bn=None, stride=1, pad=0, transposed=False, relu=False, relu_pre=False,
              residual=None, out_f32=False, out=None, sigmoid=False, output_padding=0, residual_f32=False, skip=None):
         """x: Act.  Returns the output Act [N, OD, OH, OW, Cout].  ``residual_f32`` (bf16 plans, with ``out_f32``): the residual is an fp32 tensor
@@ -345,13 +400,10 @@ class PlanBuilder:
             # the skip branch's BatchNorm: scale into its weights (fp32 product, ONE bf16 rounding), (bias * scale + shift) into this convolution's shift
             wfold = (ss.phases[0].weight * ss.scale[:, None]).to(self.dtype)
             spec.shift = spec.shift + ss.bias * ss.scale + ss.shift
-            wsk = self.const(wfold, self.dtype)
-            wfr = torch.empty(32 * 16, dtype=self.dtype, device=wsk.device)
-            if not self.dry_run:
-                H.check(H.lib().lt_conv_pack_weights_t32(wsk.data_ptr(), 32, ss.k_pad, 16, 1, wfr.data_ptr(), H.cur_stream()), "lt_conv_pack_weights_t32")
+            wfr, _ = self._frag_copy(self.const(wfold, self.dtype), 2, ss, 1)          # 32 x 16 (can_conv_skip: a 16-channel skip input)
             sk = H.ConvSkip()
             sk.x, sk.cin, sk.weight_frag = sx.t.data_ptr(), 16, wfr.data_ptr()
-            self.keep += [wfr, sx.t, sk]
+            self.keep += [sx.t, sk]
             skip_info = {"x": sx, "w": wfold[:, :16].float(), "desc": sk}
         S = self.splitk_slices(spec, weight, transposed, out_f32, sigmoid, out)
         if S > 1:
@@ -372,10 +424,7 @@ class PlanBuilder:
             tdev = self.const(ph.taps)
             d.phase[i].weight = wdev.data_ptr(); d.phase[i].taps = tdev.data_ptr()
             if layout and not self.dry_run:
-                wfr = torch.empty_like(wdev)
-                pack = self._frag_packer(layout, spec, int(ph.taps.shape[0]))
-                pack(wdev.data_ptr(), wfr.data_ptr())
-                self.keep.append(wfr)
+                wfr, pack = self._frag_copy(wdev, layout, spec, int(ph.taps.shape[0]))
                 wfrags.append((i, wfr, pack))
                 d.phase[i].weight_frag, d.phase[i].weight_frag_layout = wfr.data_ptr(), layout
         bi, sc, sh = self.const(spec.bias), self.const(spec.scale), self.const(spec.shift)
@@ -383,11 +432,10 @@ class PlanBuilder:
         macs = spec.N * spec.Do * spec.Ho * spec.Wo * spec.Cout * sum(int(p.taps.shape[0]) for p in spec.phases) * (
             weight.shape[1] if not transposed else weight.shape[0])
         self.flops += 2 * macs
-        lib = None if self.dry_run else H.lib()
         ksz = "x".join(str(k) for k in weight.shape[2:])
         label = "%s%s %d->%d @%s" % ("deconv" if transposed else "conv", ksz, spec.Cin, spec.Cout,
                                      "x".join(str(v) for v in (spec.N, spec.Do, spec.Ho, spec.Wo)))
-        esz = torch.empty((), dtype=self.dtype).element_size()
+        esz = esize(self.dtype)
         nbytes = (x.t.numel() + y.t.numel() + (residual.t.numel() if residual is not None else 0)) * esz + \
             sum(p.weight.numel() for p in spec.phases) * esz
         info = {"spec": spec, "x": x, "y": y, "res": residual, "wdev": wdevs, "bias_dev": bi, "scale_dev": sc, "shift_dev": sh, "desc": d, "wfrag": wfrags}
@@ -397,19 +445,19 @@ class PlanBuilder:
             nbytes += skip_info["x"].t.numel() * esz
             info["skip"] = skip_info
             self._add(lambda s, d=d, xp=x.t.data_ptr(), bip=bi.data_ptr(), scp=sc.data_ptr(), shp=sh.data_ptr(), sk=skip_info["desc"], yp=y.t.data_ptr():
-                      H.check(lib.lt_conv_skip_fwd(C.byref(d), xp, bip, scp, shp, C.byref(sk), yp, s), "lt_conv_skip_fwd"),
+                      H.check(self.lib.lt_conv_skip_fwd(C.byref(d), xp, bip, scp, shp, C.byref(sk), yp, s), "lt_conv_skip_fwd"),
                       "conv", label + " + skip conv1x1x1 16->32", 2 * macs, nbytes, info)
             return y
         self._add(lambda s, d=d, xp=x.t.data_ptr(), bip=bi.data_ptr(), scp=sc.data_ptr(), shp=sh.data_ptr(),
                   rp=H.ptr(residual.t) if residual is not None else None, yp=y.t.data_ptr():
-                  H.check(lib.lt_conv_fwd(C.byref(d), xp, bip, scp, shp, rp, yp, s), "lt_conv_fwd"),
+                  H.check(self.lib.lt_conv_fwd(C.byref(d), xp, bip, scp, shp, rp, yp, s), "lt_conv_fwd"),
                   "conv", label, 2 * macs, nbytes, info)
         return y
 
     # ---- last 1x1 convolution of a Bottleneck + its downsample branch as ONE pointwise convolution over two sources ---------------------------------
     def can_conv_cat2(self, t2_shape, w_expand, x_shape, w_down, stride_down):
         """True when lt_conv_cat2_fwd covers  relu(bn3(conv1x1(t2)) + bn_d(conv1x1_d(x), stride s)) over build-time weights (lt_sel_conv_cat2)."""
-        if self.out_dtype != torch.bfloat16 or self.live_weights or self.tile_override:
+        if not self._fusable():
             return False
         return bool(H.lib().lt_sel_conv_cat2(self.code, H.dims(t2_shape), H.wshape(w_expand), H.dims(x_shape), H.wshape(w_down), stride_down))
 
@@ -431,34 +479,24 @@ class PlanBuilder:
         spec.phases.append(ConvPhaseSpec(wcat.float(), s3.phases[0].taps, (0, 0, 0)))
         y = self.alloc((N, 1, Ho, Wo, Cc))
         self.keep += [t2.t, x.t]
-        d = H.ConvDesc()
-        d.dtype = self.code
-        d.N, d.D, d.H, d.W, d.Cin = N, 1, Ho, Wo, P
-        d.Do, d.Ho, d.Wo = 1, Ho, Wo
-        d.stride = H.i3((1, 1, 1)); d.pad = H.i3((0, 0, 0))
-        d.OD, d.OH, d.OW = 1, Ho, Wo
-        d.out_stride = H.i3((1, 1, 1))
-        d.Cout, d.ldc, d.cout_pad, d.k_pad = Cc, Cc, Cc, kp
-        d.nphase, d.flags, d.tile, d.stages = 1, spec.flags, 0, 0
+        d = self._desc(spec)
+        d.Cin, d.tile, d.stages = P, 0, 0          # the first source's channels; the second source is c2's
         wdev = self.const(wcat, self.dtype)
         tdev = self.const(s3.phases[0].taps)
-        wfr = torch.empty_like(wdev)
-        lib = None if self.dry_run else H.lib()
-        if not self.dry_run:
-            H.check(lib.lt_conv_pack_weights32(wdev.data_ptr(), Cc, kp, wfr.data_ptr(), H.cur_stream()), "lt_conv_pack_weights32")
-        d.phase[0].weight, d.phase[0].taps, d.phase[0].ntaps, d.phase[0].out_off = wdev.data_ptr(), tdev.data_ptr(), 1, H.i3((0, 0, 0))
+        wfr, _ = self._frag_copy(wdev, 3, spec, 1)
+        d.phase[0].weight, d.phase[0].taps = wdev.data_ptr(), tdev.data_ptr()
         d.phase[0].weight_frag, d.phase[0].weight_frag_layout = wfr.data_ptr(), 3
         c2 = H.ConvCat2()
         c2.x, c2.cin, c2.H, c2.W, c2.stride = x.t.data_ptr(), Cin2, x.shape[2], x.shape[3], stride_down
         bi, sh = self.const(spec.bias), self.const(spec.shift)
-        self.keep += [wfr, d, c2]
+        self.keep += [d, c2]
         macs = N * Ho * Wo * Cc * kp
         self.flops += 2 * macs
         esz = t2.t.element_size()
         nbytes = (t2.t.numel() + N * Ho * Wo * Cin2 + y.t.numel() + wcat.numel()) * esz
         label = "conv1x1 %d+%d->%d @%s (expand + stride-%d downsample)" % (P, Cin2, Cc, "x".join(str(v) for v in (N, 1, Ho, Wo)), stride_down)
         self._add(lambda s, d=d, xp=t2.t.data_ptr(), c2=c2, bip=bi.data_ptr(), shp=sh.data_ptr(), yp=y.t.data_ptr():
-                  H.check(lib.lt_conv_cat2_fwd(C.byref(d), xp, C.byref(c2), bip, None, shp, None, yp, s), "lt_conv_cat2_fwd"),
+                  H.check(self.lib.lt_conv_cat2_fwd(C.byref(d), xp, C.byref(c2), bip, None, shp, None, yp, s), "lt_conv_cat2_fwd"),
                   "conv", label, 2 * macs, nbytes, {"cat2": True, "spec": spec, "x": t2, "x2": x, "stride2": stride_down, "y": y})
         return y
 
@@ -466,7 +504,7 @@ class PlanBuilder:
     def splitk_slices(self, spec, weight, transposed, out_f32, sigmoid, out):
         """Number of tap groups S the reduction of this convolution is cut into (1 = not split; lt_sel_splitk_slices): V2V's 3 x 3 x 3 128 -> 128
         layers at the 8^3 / 4^3 / 2^3 levels (v2v.py:78-90) in bf16 plans over build-time weights."""
-        if self.live_weights or out is not None or self.tile_override:
+        if not self._fusable() or out is not None:
             return 1
         d = self._desc(spec)
         d.flags |= (H.EPI_STORE_F32 if out_f32 else 0) | (H.EPI_SIGMOID if sigmoid else 0)
@@ -505,17 +543,16 @@ class PlanBuilder:
         self.keep.append(d)
         macs = rows * spec.Cout * ntaps * weight.shape[1]
         self.flops += 2 * macs
-        lib = None if self.dry_run else H.lib()
         label = "conv3x3x3 %d->%d @%s" % (Cin, spec.Cout, "x".join(str(v) for v in (spec.N, spec.Do, spec.Ho, spec.Wo)))
         esz = x.t.element_size()
         self._add(lambda s, d=d, xp=x.t.data_ptr(), bip=ibi.data_ptr(), scp=isc.data_ptr(), shp=ish.data_ptr(), yp=part.t.data_ptr():
-                  H.check(lib.lt_conv_fwd(C.byref(d), xp, bip, scp, shp, None, yp, s), "lt_conv_fwd(split-K)"),
+                  H.check(self.lib.lt_conv_fwd(C.byref(d), xp, bip, scp, shp, None, yp, s), "lt_conv_fwd(split-K)"),
                   "conv", label + " split-K x%d" % S, 2 * macs, x.t.numel() * esz + part.t.numel() * 4 + sum(p.weight.numel() for p in pspec.phases) * esz,
                   {"spec": pspec, "x": x, "y": part, "res": None, "wdev": wdevs, "bias_dev": ibi})
         R = spec.Do * spec.Ho * spec.Wo
         self._add(lambda s, pp=part.t.data_ptr(), bip=bi.data_ptr(), scp=sc.data_ptr(), shp=sh.data_ptr(),
                   rp=H.ptr(residual.t) if residual is not None else None, yp=y.t.data_ptr(), a=(S, spec.N, R, spec.Cout, spec.flags):
-                  H.check(lib.lt_splitk_reduce(self.code, pp, a[0], a[1], a[2], a[3], bip, scp, shp, rp, yp, a[4], s), "lt_splitk_reduce"),
+                  H.check(self.lib.lt_splitk_reduce(self.code, pp, a[0], a[1], a[2], a[3], bip, scp, shp, rp, yp, a[4], s), "lt_splitk_reduce"),
                   "conv", label + " split-K reduce", 0, part.t.numel() * 4 + (y.t.numel() + (residual.t.numel() if residual is not None else 0)) * esz,
                   {"splitk_reduce": True, "spec": spec, "S": S, "part": part, "res": residual, "y": y})
         self.release(part)
@@ -560,17 +597,16 @@ class PlanBuilder:
         self.keep.append(x.t)
         self.keep.append(d)
         self.flops += flops
-        lib = None if self.dry_run else H.lib()
         label = "pwchain " + "->".join(str(c) for c in [32] + [sp.Cout for sp in specs]) + " @" + "x".join(str(v) for v in (N, D, Hh, W))
         nbytes = x.t.numel() * x.t.element_size() + y.t.numel() * 4
-        self._add(lambda s, d=d, xp=x.t.data_ptr(), yp=y.t.data_ptr(): H.check(lib.lt_pwchain_fwd(C.byref(d), xp, yp, s), "lt_pwchain_fwd"),
+        self._add(lambda s, d=d, xp=x.t.data_ptr(), yp=y.t.data_ptr(): H.check(self.lib.lt_pwchain_fwd(C.byref(d), xp, yp, s), "lt_pwchain_fwd"),
                   "pwchain", label, flops, nbytes, {"specs": specs, "x": x, "y": y})
         return y
 
     # ---- whole identity Bottleneck block in one launch (ResNet layer1 / layer2) -----------------------------------------------------
     def can_bottleneck(self, x, convs, strides):
         """True when lt_bottleneck_fwd covers the identity block (no downsample: the caller checks) over build-time weights (lt_sel_bottleneck)."""
-        if self.live_weights or self.tile_override or len(convs) != 3:
+        if not self._fusable() or len(convs) != 3:
             return False
         return bool(H.lib().lt_sel_bottleneck(self.code, H.dims(x.shape), (H.WShape * 3)(*map(H.wshape, convs)), H.i3(strides)))
 
@@ -579,44 +615,41 @@ class PlanBuilder:
         stay in LDS).  convs: the three Conv2d weights, bns: their BatchNorm tuples.  Returns the output Act (a new buffer: the kernel
         cannot run in place)."""
         assert self.can_bottleneck(x, convs, (1, 1, 1))
-        N, _, Hh, W, Cc = x.shape
-        P = convs[0].shape[0]
-        specs = []
-        shape = x.shape
-        for i, (w, bn) in enumerate(zip(convs, bns)):
-            spec = make_conv_spec(w, None, bn, shape, 1, 1 if i == 1 else 0, self.dtype, False, H.EPI_RELU_POST)
+        return self._bneck(x, convs, bns)
+
+    def _bneck(self, x, convs, bns, down=None):
+        """The body of ``bottleneck`` and, with ``down`` = (weight, BatchNorm tuple) of the downsample branch as a fourth layer, of ``bottleneck_ds``."""
+        N, _, Hh, W, Cin = x.shape
+        P, Cc = convs[0].shape[0], convs[2].shape[0]
+        y = self.alloc((N, 1, Hh, W, Cc))
+        if down is None:
+            d = H.BneckDesc()
+            d.dtype, d.N, d.H, d.W, d.C, d.P = self.code, N, Hh, W, Cc, P
+        else:
+            d = H.BneckDsDesc()
+            d.dtype, d.N, d.H, d.W, d.Cin, d.P, d.C = self.code, N, Hh, W, Cin, P, Cc
+        flops0, specs, shape = self.flops, [], x.shape
+        for i, (w, bn) in enumerate(zip(convs, bns)):          # 1x1 reduce, 3x3, 1x1 expand: each reads the one before it
+            spec, d.weight[i], d.scale[i], d.shift[i] = self._pack_layer(w, bn, shape, 1 if i == 1 else 0, H.EPI_RELU_POST)
             specs.append(spec)
             shape = (N, 1, Hh, W, spec.Cout)
-        y = self.alloc((N, 1, Hh, W, Cc))
-        d = H.BneckDesc()
-        d.dtype, d.N, d.H, d.W, d.C, d.P = self.code, N, Hh, W, Cc, P
-        lib = None if self.dry_run else H.lib()
-        flops = 0
-        for i, spec in enumerate(specs):
-            wdev = self.const(spec.phases[0].weight, self.dtype)
-            assert spec.cout_pad == spec.Cout and spec.k_pad == spec.phases[0].taps.shape[0] * spec.Cin, (spec.cout_pad, spec.k_pad)
-            sc, sh = self.const(spec.scale), self.const(spec.shift)
-            wfr = torch.empty_like(wdev)
-            if not self.dry_run:
-                H.check(lib.lt_conv_pack_weights_t32(wdev.data_ptr(), spec.cout_pad, spec.k_pad, spec.Cin, int(spec.phases[0].taps.shape[0]),
-                                                     wfr.data_ptr(), H.cur_stream()), "lt_conv_pack_weights_t32")
-            self.keep.append(wfr)
-            d.weight[i], d.bias[i], d.scale[i], d.shift[i] = wfr.data_ptr(), None, sc.data_ptr(), sh.data_ptr()
-            flops += 2 * N * Hh * W * spec.Cout * spec.phases[0].taps.shape[0] * spec.Cin
-        self.keep.append(x.t)
-        self.keep.append(d)
-        self.flops += flops
+        if down is not None:                                   # the downsample branch reads x; the ReLU follows the sum
+            spec, d.weight[3], d.scale[3], d.shift[3] = self._pack_layer(*down, x.shape, 0, 0)
+            specs.append(spec)
+        self.keep += [x.t, d]
+        flops = self.flops - flops0
         esz = x.t.element_size()
         nbytes = (x.t.numel() + y.t.numel()) * esz + sum(sp.phases[0].weight.numel() for sp in specs) * esz
-        label = "bneck %d->%d->%d @%s" % (Cc, P, Cc, "x".join(str(v) for v in (N, 1, Hh, W)))
-        self._add(lambda s, d=d, xp=x.t.data_ptr(), yp=y.t.data_ptr(): H.check(lib.lt_bottleneck_fwd(C.byref(d), xp, yp, s), "lt_bottleneck_fwd"),
-                  "conv", label, flops, nbytes, {"bneck": True, "specs": specs, "x": x, "y": y})
+        name, fwd = ("bneck", "lt_bottleneck_fwd") if down is None else ("bneck-ds", "lt_bottleneck_ds_fwd")
+        label = "%s %d->%d->%d @%s" % (name, Cin, P, Cc, "x".join(str(v) for v in (N, 1, Hh, W)))
+        self._add(lambda s, d=d, xp=x.t.data_ptr(), yp=y.t.data_ptr(): H.check(getattr(self.lib, fwd)(C.byref(d), xp, yp, s), fwd),
+                  "conv", label, flops, nbytes, {name.replace("-", "_"): True, "specs": specs, "x": x, "y": y})
         return y
 
     # ---- the first Bottleneck of ResNet layer1 (downsample branch, stride 1) in one launch --------------------------------------------------
     def can_bottleneck_ds(self, x, convs, strides, w_down, stride_down):
         """True when lt_bottleneck_ds_fwd covers the block with its downsample branch over build-time weights (lt_sel_bottleneck_ds)."""
-        if self.live_weights or self.tile_override or len(convs) != 3:
+        if not self._fusable() or len(convs) != 3:
             return False
         return bool(H.lib().lt_sel_bottleneck_ds(self.code, H.dims(x.shape), (H.WShape * 3)(*map(H.wshape, convs)), H.i3(strides), H.wshape(w_down),
                                                   stride_down))
@@ -625,46 +658,12 @@ class PlanBuilder:
         """relu(bn3(conv1x1(relu(bn2(conv3x3(relu(bn1(conv1x1(x)))))))) + bn_d(conv1x1_d(x))) in ONE launch (lt_bottleneck_ds_fwd): the two bottleneck-width
         tensors stay in LDS and the downsample branch is computed from the tile of x that is there already.  Returns the output Act."""
         assert self.can_bottleneck_ds(x, convs, (1, 1, 1), w_down, 1)
-        N, _, Hh, W, Cin = x.shape
-        P, Cc = convs[0].shape[0], convs[2].shape[0]
-        specs = []
-        shape = x.shape
-        for i, (w, bn) in enumerate(zip(convs, bns)):
-            spec = make_conv_spec(w, None, bn, shape, 1, 1 if i == 1 else 0, self.dtype, False, H.EPI_RELU_POST)
-            specs.append(spec)
-            shape = (N, 1, Hh, W, spec.Cout)
-        specs.append(make_conv_spec(w_down, None, bn_down, x.shape, 1, 0, self.dtype, False, 0))
-        y = self.alloc((N, 1, Hh, W, Cc))
-        d = H.BneckDsDesc()
-        d.dtype, d.N, d.H, d.W, d.Cin, d.P, d.C = self.code, N, Hh, W, Cin, P, Cc
-        lib = None if self.dry_run else H.lib()
-        flops = 0
-        for i, spec in enumerate(specs):
-            wdev = self.const(spec.phases[0].weight, self.dtype)
-            assert spec.cout_pad == spec.Cout and spec.k_pad == spec.phases[0].taps.shape[0] * spec.Cin, (spec.cout_pad, spec.k_pad)
-            assert not bool(spec.bias.any()), "ResNet convolutions carry no bias"
-            sc, sh = self.const(spec.scale), self.const(spec.shift)
-            wfr = torch.empty_like(wdev)
-            if not self.dry_run:
-                H.check(lib.lt_conv_pack_weights_t32(wdev.data_ptr(), spec.cout_pad, spec.k_pad, spec.Cin, int(spec.phases[0].taps.shape[0]),
-                                                     wfr.data_ptr(), H.cur_stream()), "lt_conv_pack_weights_t32")
-            self.keep.append(wfr)
-            d.weight[i], d.scale[i], d.shift[i] = wfr.data_ptr(), sc.data_ptr(), sh.data_ptr()
-            flops += 2 * N * Hh * W * spec.Cout * spec.phases[0].taps.shape[0] * spec.Cin
-        self.keep.append(x.t)
-        self.keep.append(d)
-        self.flops += flops
-        esz = x.t.element_size()
-        nbytes = (x.t.numel() + y.t.numel()) * esz + sum(sp.phases[0].weight.numel() for sp in specs) * esz
-        label = "bneck-ds %d->%d->%d @%s" % (Cin, P, Cc, "x".join(str(v) for v in (N, 1, Hh, W)))
-        self._add(lambda s, d=d, xp=x.t.data_ptr(), yp=y.t.data_ptr(): H.check(lib.lt_bottleneck_ds_fwd(C.byref(d), xp, yp, s), "lt_bottleneck_ds_fwd"),
-                  "conv", label, flops, nbytes, {"bneck_ds": True, "specs": specs, "x": x, "y": y})
-        return y
+        return self._bneck(x, convs, bns, (w_down, bn_down))
 
     # ---- the seam between two identity Bottleneck blocks in one launch (ResNet layer3): expand of block i + reduce of block i + 1 -----------
     def can_expand_reduce(self, t2, res, w_expand, w_reduce):
         """True when lt_expand_reduce_fwd covers the seam between two identity Bottlenecks over build-time weights (lt_sel_expand_reduce)."""
-        if self.live_weights or self.tile_override:
+        if not self._fusable():
             return False
         return bool(H.lib().lt_sel_expand_reduce(self.code, H.dims(t2.shape), H.dims(res.shape), H.wshape(w_expand), H.wshape(w_reduce)))
 
@@ -674,33 +673,22 @@ class PlanBuilder:
         assert self.can_expand_reduce(t2, res, w_expand, w_reduce)
         N, _, Hh, W, P = t2.shape
         Cc = res.shape[-1]
-        s3 = make_conv_spec(w_expand, None, bn_expand, t2.shape, 1, 0, self.dtype, False, H.EPI_RELU_POST)
-        s1 = make_conv_spec(w_reduce, None, bn_reduce, res.shape, 1, 0, self.dtype, False, H.EPI_RELU_POST)
         y = self.alloc((N, 1, Hh, W, Cc))
         t1 = self.alloc((N, 1, Hh, W, P))
         d = H.XrDesc()
         d.dtype, d.C, d.P, d.M = self.code, Cc, P, N * Hh * W
-        lib = None if self.dry_run else H.lib()
-        flops = 0
-        for i, spec in enumerate((s3, s1)):
-            assert spec.cout_pad == spec.Cout and spec.k_pad == spec.Cin and not bool(spec.bias.any()), (spec.cout_pad, spec.k_pad)
-            wdev = self.const(spec.phases[0].weight, self.dtype)
-            sc, sh = self.const(spec.scale), self.const(spec.shift)
-            wfr = torch.empty_like(wdev)
-            if not self.dry_run:
-                H.check(lib.lt_conv_pack_weights_t32(wdev.data_ptr(), spec.cout_pad, spec.k_pad, spec.Cin, 1, wfr.data_ptr(), H.cur_stream()), "lt_conv_pack_weights_t32")
-            self.keep += [wfr, sc, sh]
-            d.weight[i], d.scale[i], d.shift[i] = wfr.data_ptr(), sc.data_ptr(), sh.data_ptr()
-            flops += 2 * N * Hh * W * spec.Cout * spec.Cin
+        flops0 = self.flops
+        s3, d.weight[0], d.scale[0], d.shift[0] = self._pack_layer(w_expand, bn_expand, t2.shape, 0, H.EPI_RELU_POST)
+        s1, d.weight[1], d.scale[1], d.shift[1] = self._pack_layer(w_reduce, bn_reduce, res.shape, 0, H.EPI_RELU_POST)
         packed = self.const(torch.cat([s3.scale, s3.shift, s1.scale, s1.shift]))          # the four tables back to back: one LDS-DMA in the kernel's prologue
         d.consts = packed.data_ptr()
-        self.keep += [t2.t, res.t, d, packed]
-        self.flops += flops
+        self.keep += [t2.t, res.t, d]
+        flops = self.flops - flops0
         esz = t2.t.element_size()
         nbytes = (t2.t.numel() + res.t.numel() + y.t.numel() + t1.t.numel() + 2 * Cc * P) * esz
         label = "xr expand %d->%d + reduce %d->%d @%s" % (P, Cc, Cc, P, "x".join(str(v) for v in (N, 1, Hh, W)))
         self._add(lambda s, d=d, a=t2.t.data_ptr(), r=res.t.data_ptr(), yp=y.t.data_ptr(), tp=t1.t.data_ptr():
-                  H.check(lib.lt_expand_reduce_fwd(C.byref(d), a, r, yp, tp, s), "lt_expand_reduce_fwd"),
+                  H.check(self.lib.lt_expand_reduce_fwd(C.byref(d), a, r, yp, tp, s), "lt_expand_reduce_fwd"),
                   "conv", label, flops, nbytes, {"xr": True, "specs": [s3, s1], "x": t2, "res": res, "y": y, "t1": t1})
         return y, t1
 
@@ -724,11 +712,10 @@ class PlanBuilder:
         y = self.alloc((N, 1, Hp, Wp, 64))
         wdev = self.const(spec.phases[0].weight, self.dtype)
         bi, sc, sh = self.const(spec.bias), self.const(spec.scale), self.const(spec.shift)
-        lib = None if self.dry_run else H.lib()
         # the kernel reads its weights in MFMA fragment order: packed once, here (on the plan's device, legacy stream)
-        wpk = torch.empty(57344 if self.dry_run else lib.lt_stem_packed_bytes(), dtype=torch.uint8, device=self.device)
+        wpk = torch.empty(57344 if self.dry_run else self.lib.lt_stem_packed_bytes(), dtype=torch.uint8, device=self.device)
         if not self.dry_run:
-            H.check(lib.lt_stem_pack_weights(wdev.data_ptr(), spec.k_pad, wpk.data_ptr(), H.cur_stream()), "lt_stem_pack_weights")
+            H.check(self.lib.lt_stem_pack_weights(wdev.data_ptr(), spec.k_pad, wpk.data_ptr(), H.cur_stream()), "lt_stem_pack_weights")
             torch.cuda.current_stream().synchronize()
         d = H.StemDesc()
         d.dtype, d.N, d.H, d.W, d.Cin, d.Cout = self.code, N, Hh, W, (3 if image_cell is not None else 8), 64
@@ -744,12 +731,12 @@ class PlanBuilder:
             def launch(s, d=d, yp=y.t.data_ptr(), cell=image_cell):
                 if not cell.get("ptr"):
                     raise RuntimeError("stem_pool: the plan reads the caller's images; set image_cell['ptr'] before Plan.run")
-                H.check(lib.lt_stem_pool_fwd(C.byref(d), cell["ptr"], yp, s), "lt_stem_pool_fwd")
+                H.check(self.lib.lt_stem_pool_fwd(C.byref(d), cell["ptr"], yp, s), "lt_stem_pool_fwd")
             nbytes = N * 3 * Hh * W * 4 + y.t.numel() * esz + spec.phases[0].weight.numel() * esz
             self.npre += 1
         else:
             def launch(s, d=d, xp=x.t.data_ptr(), yp=y.t.data_ptr()):
-                H.check(lib.lt_stem_pool_fwd(C.byref(d), xp, yp, s), "lt_stem_pool_fwd")
+                H.check(self.lib.lt_stem_pool_fwd(C.byref(d), xp, yp, s), "lt_stem_pool_fwd")
             nbytes = (x.t.numel() + y.t.numel()) * esz + spec.phases[0].weight.numel() * esz
         self._add(launch, "stem", "stem conv7x7/2+pool3x3/2 %d->64 @%s" % (d.Cin, "x".join(str(v) for v in (N, Hh, W))), flops, nbytes,
                   {"spec": spec, "x": x, "y": y})
@@ -763,9 +750,8 @@ class PlanBuilder:
         od = [(dim + 2 * pp[i] - kk[i]) // ss[i] + 1 for i, dim in enumerate((D, Hh, W))]
         y = self.alloc((N, od[0], od[1], od[2], Cc))
         self.keep.append(x.t)
-        lib = None if self.dry_run else H.lib()
         self._add(lambda st, xp=x.t.data_ptr(), yp=y.t.data_ptr(), a=(N, D, Hh, W, Cc), kk=H.i3(kk), ss=H.i3(ss), pp=H.i3(pp):
-                  H.check(lib.lt_maxpool_fwd(self.code, xp, yp, a[0], a[1], a[2], a[3], a[4], kk, ss, pp, st), "lt_maxpool_fwd"),
+                  H.check(self.lib.lt_maxpool_fwd(self.code, xp, yp, a[0], a[1], a[2], a[3], a[4], kk, ss, pp, st), "lt_maxpool_fwd"),
                   "maxpool", "maxpool%dd k%d @%s" % (nd, k, "x".join(map(str, x.shape))), 0,
                   (x.t.numel() + y.t.numel()) * x.t.element_size(), {"x": x, "y": y, "k": kk, "s": ss, "p": pp})
         return y
@@ -775,9 +761,8 @@ class PlanBuilder:
         N, D, Hh, W, Cc = x.shape
         y = self.alloc((1, 1, 1, N, Cc))
         self.keep.append(x.t)
-        lib = None if self.dry_run else H.lib()
         self._add(lambda st, xp=x.t.data_ptr(), yp=y.t.data_ptr(), a=(N, D * Hh * W, Cc):
-                  H.check(lib.lt_global_avgpool(self.code, xp, yp, a[0], a[1], a[2], st), "lt_global_avgpool"), "avgpool", "global_avgpool",
+                  H.check(self.lib.lt_global_avgpool(self.code, xp, yp, a[0], a[1], a[2], st), "lt_global_avgpool"), "avgpool", "global_avgpool",
                   info={"x": x, "y": y})
         return y
 

@@ -32,9 +32,9 @@ import lt_hip as H
 BN_EPS = 1e-5
 
 
-class TrainTape:
-    """PlanBuilder-shaped object for ``record()`` (conv / maxpool / alloc / release).  RECORD ONCE, REPLAY EVERY STEP: while the
-    modules' ``record()`` methods run, every launch is executed AND appended to ``fwd_ops``; the first backward walks the layers in
+class TrainTape(E.Recorder):
+    """The lt_engine.Recorder of a training step: it takes none of the fused launches a Recorder may offer (the backward needs every layer's own
+    activations), so ``record()`` walks it layer by layer.  RECORD ONCE, REPLAY EVERY STEP: while the modules' ``record()`` methods run, every launch is executed AND appended to ``fwd_ops``; the first backward walks the layers in
     reverse the same way into ``bwd_ops``.  Every buffer (activations, gradients, GEMM-layout weights, workspaces, the flat arena of
     parameter gradients) is allocated during recording and lives as long as the tape, so a later step is two loops over closures of
     raw pointers -- no allocation, no host-side weight handling, no synchronisation.  The weights are LIVE: each layer's first op is
@@ -45,7 +45,7 @@ class TrainTape:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("training runs on the GPU only (device=%s); there is no CPU fallback" % device)
-        self.dtype, self.code, self.dry_run = torch.float32, H.LT_F32, False
+        self.dtype, self.code, self.dry_run, self.live_weights = torch.float32, H.LT_F32, False, True
         self.pb = E.PlanBuilder(device, torch.float32)          # builds the lt_conv_fwd descriptors
         # mixed precision: the convolutions (forward and input gradients) take bf16 COPIES of their operands to the bf16 MFMA and store
         # fp32 (LT_EPI_STORE_F32); activations, BatchNorm, weight gradients, optimiser stay fp32 (the master weights are the Parameters)
@@ -151,7 +151,7 @@ class TrainTape:
         lib = H.lib()
         x8, sx = self._fp8_of(x)
         y = self.pb8.conv(x8, torch.zeros(idx.shape), None, None, **kw)
-        fn, info = self.pb8.ops[-1][0], self.pb8.last_info
+        info = self.pb8.last_info
         spec_idx = E.make_conv_spec(idx, None, None, x.shape, kw.get("stride", 1), kw.get("pad", 0), torch.float8_e4m3fn)
         assert len(spec_idx.phases) == len(info["wdev"]) == 1
         wam, sw = self._q_slot(), self._q_slot()
@@ -164,17 +164,13 @@ class TrainTape:
         self.keep += [imap, wdev]
         self.do(lambda st: H.check(lib.lt_gather_f32_fp8(wparam.data_ptr(), imap.data_ptr(), wdev.data_ptr(), n8, wam.data_ptr(), sw.data_ptr(), st), "lt_gather_f32_fp8"),
                 "gather fp8")
-        sc, sh = info["scale_dev"], info["shift_dev"]
+        sc = info["scale_dev"]
         nsc = sc.numel()
         self.do(lambda st: H.check(lib.lt_scale_product(sc.data_ptr(), nsc, sx.data_ptr(), sw.data_ptr(), st), "lt_scale_product"), "scale")
-        if bias is not None:          # (acc * sx sw) + bias: the bias rides in the epilogue's shift
-            bmap = torch.full((sh.numel(),), -1, dtype=torch.int32)
-            bmap[:bias.numel()] = torch.arange(bias.numel(), dtype=torch.int32)
-            self._gather(bias, bmap.to(self.device), sh, "w")
-        self.do(fn, ("dgrad fp8 " if self._cur is self.bwd_ops else "conv fp8 ") + self.pb8.ops[-1][1]["label"])
+        self._bind(self.pb8, None, None, bias, "shift_dev", "fp8 ")          # (acc * sx sw) + bias: the bias rides in the epilogue's shift
         return y
 
-    # ---- PlanBuilder surface -------------------------------------------------------------------------------------------------
+    # ---- Recorder surface ----------------------------------------------------------------------------------------------------
     def alloc(self, shape, dtype=None):
         return E.Act(torch.empty(shape, dtype=dtype or self.adt, device=self.device))
 
@@ -183,15 +179,6 @@ class TrainTape:
 
     def const(self, t, dtype=None):
         return t.to(device=self.device, dtype=dtype or t.dtype).contiguous()
-
-    def can_stem_pool(self, *a, **k):
-        return False
-
-    def can_chain_pointwise(self, *a, **k):
-        return False
-
-    def can_bottleneck(self, *a, **k):     # the training tape records every layer on its own (its backward needs the inner activations)
-        return False
 
     def global_avgpool(self, x):
         """Mean over the map of every sample (GlobalAveragePoolingHead, pose_resnet.py:166-168): x Act [N,1,H,W,C] -> Act [1,1,1,N,C]; backward
@@ -298,6 +285,34 @@ class TrainTape:
             return E.Act(t16)
         return E.Act(e[1])
 
+    @staticmethod
+    def _index_spec(idx, x, kw):
+        """The bf16 spec of the convolution ``kw`` over ``x`` with the indices ``idx`` as its weights: every phase's matrix says which element of the
+        Parameter each slot of the GEMM layout holds (0 = padding)."""
+        return E.make_conv_spec(idx, None, None, x.shape, kw.get("stride", 1), kw.get("pad", 0), torch.bfloat16, kw.get("transposed", False), 0,
+                                kw.get("output_padding", 0))
+
+    def _bind(self, pb, spec_idx, wparam, bias, bias_into="bias_dev", tag=""):
+        """Binds the live Parameters to what ``pb`` uploaded for the convolution it has just recorded, then records (= runs) its launch: ``wparam`` gathered
+        through the index maps of ``spec_idx`` (None: the maps are what the weight buffers hold) into every phase's GEMM layout and into the fragment-order
+        copies the fast kernels read (live_frag), ``bias`` into the epilogue table ``bias_into``.  ``wparam`` None: the caller has filled the weights itself."""
+        fn, info = pb.ops[-1][0], pb.last_info
+        if wparam is not None:
+            maps = info["wdev"] if spec_idx is None else [ph.weight for ph in spec_idx.phases]
+            assert len(maps) == len(info["wdev"])
+            for m, wdev in zip(maps, info["wdev"]):
+                assert tuple(m.shape) == tuple(wdev.shape)
+                self._gather(wparam, (m.round().to(torch.int32) - 1).contiguous().to(self.device), wdev, "w")
+            for pi, wfr, pack in info.get("wfrag", ()):
+                self._gather(wparam, self._frag_index_map(maps[pi], pack), wfr.reshape(-1), "w")
+                self.n_frag_layers = getattr(self, "n_frag_layers", 0) + 1
+        if bias is not None:
+            dst = info[bias_into]
+            bmap = torch.full((dst.numel(),), -1, dtype=torch.int32)
+            bmap[:bias.numel()] = torch.arange(bias.numel(), dtype=torch.int32)
+            self._gather(bias, bmap.to(self.device), dst, "w")
+        self.do(fn, ("dgrad " if self._cur is self.bwd_ops else "conv ") + tag + pb.ops[-1][1]["label"])
+
     def _live_conv(self, x, wparam, wt=None, bias=None, out_f32=None, **kw):
         """lt_conv_fwd over the CURRENT values of ``wparam`` (optionally seen through the view transform ``wt``: the transposed / flipped
         filter of an input gradient) and of ``bias``."""
@@ -314,22 +329,7 @@ class TrainTape:
             # bf16 in, bf16 out (fp32 for the logits layer, ``out_f32``) through the ordinary epilogue of whichever bf16 kernel lt_conv_fwd picks:
             # activation flags and a bf16 residual (the input gradient that is already there) apply in the reference's order inside the kernel
             y = self.pbh.conv(x, torch.zeros(idx.shape), bias, None, out_f32=out_f32, **kw)
-            fn, info = self.pbh.ops[-1][0], self.pbh.last_info
-            spec_idx = E.make_conv_spec(idx, None, None, x.shape, kw.get("stride", 1), kw.get("pad", 0), torch.bfloat16, kw.get("transposed", False), 0,
-                                        kw.get("output_padding", 0))
-            assert len(spec_idx.phases) == len(info["wdev"])
-            for ph, wdev in zip(spec_idx.phases, info["wdev"]):
-                assert tuple(ph.weight.shape) == tuple(wdev.shape)
-                self._gather(wparam, (ph.weight.round().to(torch.int32) - 1).contiguous().to(self.device), wdev, "w")      # fp32 Parameter -> bf16 GEMM layout
-            for pi, wfr, pack in info.get("wfrag", ()):          # ... and into the fragment-order copy the fast kernels read (live_frag)
-                self._gather(wparam, self._frag_index_map(spec_idx.phases[pi].weight, pack), wfr.reshape(-1), "w")
-                self.n_frag_layers = getattr(self, "n_frag_layers", 0) + 1
-            if bias is not None:
-                bi = info["bias_dev"]
-                bmap = torch.full((bi.numel(),), -1, dtype=torch.int32)
-                bmap[:bias.numel()] = torch.arange(bias.numel(), dtype=torch.int32)
-                self._gather(bias, bmap.to(self.device), bi, "w")
-            self.do(fn, ("dgrad " if self._cur is self.bwd_ops else "conv ") + self.pbh.ops[-1][1]["label"])
+            self._bind(self.pbh, self._index_spec(idx, x, kw), wparam, bias)
             return y
         if self.mixed:
             residual = kw.pop("residual", None)
@@ -338,8 +338,7 @@ class TrainTape:
                 # relu(v + res).  No layer of these networks takes this path (the residual convolutions carry BatchNorm); refuse it loudly.
                 raise NotImplementedError("mixed precision: a BatchNorm-less convolution with both an activation and a residual")
             x16 = self._bf16_of(x)
-            spec_idx = E.make_conv_spec(idx, None, None, x16.shape, kw.get("stride", 1), kw.get("pad", 0), torch.bfloat16, kw.get("transposed", False), 0,
-                                        kw.get("output_padding", 0))
+            spec_idx = self._index_spec(idx, x16, kw)
             # the fp32 gradient that is already there rides in the epilogue (LT_EPI_RES_F32) -- except on the 3^3 32 -> 32 layers, whose column-walk
             # kernel has no fp32 residual path and is worth more than the saved pass (LT_TRAIN_NO_FUSED_RES=1: always the separate pass)
             col_walk = tuple(idx.shape) == (32, 32, 3, 3, 3) and kw.get("stride", 1) == 1 and not kw.get("transposed", False)
@@ -347,32 +346,14 @@ class TrainTape:
             if fuse_res:
                 kw = dict(kw, residual=residual, residual_f32=True)
             y = self.pbh.conv(x16, torch.zeros(idx.shape), bias, None, out_f32=out_f32, **kw)
-            fn, info = self.pbh.ops[-1][0], self.pbh.last_info
-            assert len(spec_idx.phases) == len(info["wdev"])
-            for ph, wdev in zip(spec_idx.phases, info["wdev"]):
-                assert tuple(ph.weight.shape) == tuple(wdev.shape)
-                self._gather(wparam, (ph.weight.round().to(torch.int32) - 1).contiguous().to(self.device), wdev, "w")      # fp32 Parameter -> bf16 GEMM layout
-            if bias is not None:
-                bi = info["bias_dev"]
-                bmap = torch.full((bi.numel(),), -1, dtype=torch.int32)
-                bmap[:bias.numel()] = torch.arange(bias.numel(), dtype=torch.int32)
-                self._gather(bias, bmap.to(self.device), bi, "w")
-            self.do(fn, ("dgrad " if self._cur is self.bwd_ops else "conv ") + self.pbh.ops[-1][1]["label"])
+            self._bind(self.pbh, spec_idx, wparam, bias)
             if residual is not None and not fuse_res:
                 yt, rt = y.t, residual.t
                 n_add = yt.numel()
                 self.do(lambda st: H.check(H.lib().lt_add_f32(yt.data_ptr(), rt.data_ptr(), n_add, st), "lt_add_f32"), "add")
             return y
-        y = self.pb.conv(x, idx, bias, None, **kw)
-        fn, info = self.pb.ops[-1][0], self.pb.last_info
-        for wdev in info["wdev"]:
-            self._gather(wparam, (wdev.round().to(torch.int32) - 1).contiguous(), wdev, "w")
-        if bias is not None:
-            bi = info["bias_dev"]
-            bmap = torch.full((bi.numel(),), -1, dtype=torch.int32)
-            bmap[:bias.numel()] = torch.arange(bias.numel(), dtype=torch.int32)
-            self._gather(bias, bmap.to(self.device), bi, "w")
-        self.do(fn, ("dgrad " if self._cur is self.bwd_ops else "conv ") + self.pb.ops[-1][1]["label"])
+        y = self.pb.conv(x, idx, bias, None, **kw)          # the fp32 builder uploads the INDICES: each weight buffer holds its own map until the first gather
+        self._bind(self.pb, None, wparam, bias)
         return y
 
     # ---- layers --------------------------------------------------------------------------------------------------------------

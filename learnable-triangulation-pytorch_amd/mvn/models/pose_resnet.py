@@ -61,7 +61,7 @@ class ResidualBlock(nn.Module):
             convs = [self.conv1.weight, self.conv2.weight, self.conv3.weight]
             if b.can_bottleneck(x, convs, self.strides):
                 return b.bottleneck(x, convs, [bn_tuple(self.bn1), bn_tuple(self.bn2), bn_tuple(self.bn3)])
-        if (self.kind == "bottleneck" and self.downsample is not None and t1 is None and next_block is None and hasattr(b, "can_bottleneck_ds")):
+        if self.kind == "bottleneck" and self.downsample is not None and t1 is None and next_block is None:
             # the first block of layer1 (downsample branch, stride 1) in bf16 plans: one launch, the residual branch computed from the tile of x in LDS
             convs = [self.conv1.weight, self.conv2.weight, self.conv3.weight]
             if b.can_bottleneck_ds(x, convs, self.strides, self.downsample[0].weight, self.downsample[0].stride[0]):
@@ -80,7 +80,7 @@ class ResidualBlock(nn.Module):
             y = b.conv(t2, self.conv3.weight, None, bn_tuple(self.bn3), stride=1, pad=0, relu=True, residual=x)
             b.release(t2)
             return (y, None) if next_block is not None else y
-        if self.kind == "bottleneck" and self.downsample is not None and hasattr(b, "can_conv_cat2"):
+        if self.kind == "bottleneck" and self.downsample is not None:
             # first block of layer2-4 in bf16 plans: the expand and the (strided) downsample branch are ONE pointwise convolution over [t2 | x] (lt_conv_cat2_fwd)
             ds, sds = self.downsample[0], self.downsample[0].stride[0]
             Ho, Wo = (x.shape[2] - 1) // sds + 1, (x.shape[3] - 1) // sds + 1
@@ -190,9 +190,9 @@ class PoseResNet(E.PlanCache):
             for bi, blk in enumerate(blocks):
                 nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
                 # a run of identity bottleneck blocks whose seams lt_expand_reduce_fwd covers (ResNet layer3, bf16 plans): expand(i) + reduce(i + 1) in one launch
-                chain = (nxt is not None and blk.is_identity_bottleneck() and nxt.is_identity_bottleneck() and hasattr(b, "can_expand_reduce") and
+                chain = (nxt is not None and blk.is_identity_bottleneck() and nxt.is_identity_bottleneck() and
                          tuple(blk.conv3.weight.shape[:2]) == (1024, 256) and tuple(nxt.conv1.weight.shape[:2]) == (256, 1024) and b.dtype == torch.bfloat16 and
-                         not getattr(b, "live_weights", False))
+                         not b.live_weights)
                 if chain:
                     z, t1n = blk.record(b, y, t1=t1, next_block=nxt)
                 elif t1 is not None:
@@ -230,7 +230,7 @@ class PoseResNet(E.PlanCache):
             raise NotImplementedError("training runs through VolumetricTriangulationNet, whose step is recorded as a whole (lt_train.py); "
                                       "the stand-alone forward of this module is inference only: call .eval()")
         key = (tuple(x.shape), self.compute_dtype, x.device)
-        N, Cc, Hh, W = x.shape
+        N, _, Hh, W = x.shape
 
         def build():
             b = E.PlanBuilder(x.device, self.compute_dtype)
@@ -242,17 +242,11 @@ class PoseResNet(E.PlanCache):
             P = self._plan_for(key, build)
             plan, inp, (hm, feats, alg, vol) = P["plan"], P["inp"], P["outs"]
             st = torch.cuda.current_stream(x.device).cuda_stream
-            xin = x.float().contiguous()
-            H.check(H.lib().lt_nchw_to_nhwc(plan_dtype_code(self.compute_dtype), xin.data_ptr(), inp.t.data_ptr(), N, Cc, Hh * W,
-                                            inp.t.shape[-1], st), "lt_nchw_to_nhwc")
+            E.stage_images(x.float().contiguous(), inp, st)
             plan.run_eager(st)
             to_nchw = lambda a: a.t[:, 0].permute(0, 3, 1, 2).to(torch.float32, copy=True)
             conf = lambda a: None if a is None else a.t.reshape(N, -1).clone()
             return to_nchw(hm), to_nchw(feats), conf(alg), conf(vol)
-
-
-def plan_dtype_code(dt):
-    return H.dtype_code(dt)
 
 
 def get_pose_net(config, device="cuda:0"):

@@ -88,7 +88,7 @@ class _VolTrainPlan:
             tape.no_grad_ids.add(id(self.x_in))
         tape = self.tape
         ac = tape.acode          # element type of the activations: fp32, or bf16 in the 16-bit-activation step
-        H.check(lib.lt_nchw_to_nhwc(ac, x.data_ptr(), self.x_in.t.data_ptr(), B * NV, 3, Hh * W, self.x_in.t.shape[-1], st), "lt_nchw_to_nhwc")
+        E.stage_images(x, self.x_in, st)
         if first:
             # layers in front of the unprojection (its launch needs the map size, the geometry block the launch reads needs the maps' size too)
             _, feats256, _, volc = model.backbone.record(tape, self.x_in, want_heatmaps=False)
@@ -263,7 +263,7 @@ class _AlgTrainPlan:
             self.x_in = tape.alloc((N, 1, Hh, W, E.min_cin_of(torch.bfloat16 if mixed else torch.float32)))
             tape.no_grad_ids.add(id(self.x_in))
         tape = self.tape
-        H.check(lib.lt_nchw_to_nhwc(tape.acode, x.data_ptr(), self.x_in.t.data_ptr(), N, 3, Hh * W, self.x_in.t.shape[-1], st), "lt_nchw_to_nhwc")
+        E.stage_images(x, self.x_in, st)
         if first:
             hm, _, algc, _ = model.backbone.record(tape, self.x_in, want_heatmaps=True)
             self.hm, self.algc = hm, algc
@@ -347,6 +347,14 @@ class _PlannedNet(E.PlanCache):
         self.compute_dtype = dtype
         return self
 
+    def _open_plan(self, N, Hh, W, device, dry_run=False):
+        """(builder, input Act): every plan starts with its builder and the channels-last map [N,1,H,W,c_pad] that forward() stages the caller's N images into
+        (E.stage_images); the map is never handed back to the builder's pool."""
+        b = E.PlanBuilder(device, self.compute_dtype, self.tile_override, dry_run=dry_run)
+        x_in = b.alloc((N, 1, Hh, W, E.min_cin_of(self.compute_dtype)))
+        x_in.pooled = False
+        return b, x_in
+
     def _side_stream(self, device):
         if self._stream is None or self._stream.device != device:
             self._stream = torch.cuda.Stream(device=device)
@@ -384,12 +392,9 @@ class VolumetricTriangulationNet(_PlannedNet):
 
     # ---------------------------------------------------------------------------------------
     def _build_plan(self, B, NV, Hh, W, device, dry_run=False):
-        dt = self.compute_dtype
         V, J = self.volume_size, self.num_joints
-        b = E.PlanBuilder(device, dt, self.tile_override, dry_run=dry_run)
-        lib = None if dry_run else H.lib()
-        x_in = b.alloc((B * NV, 1, Hh, W, E.min_cin_of(dt)))
-        x_in.pooled = False
+        b, x_in = self._open_plan(B * NV, Hh, W, device, dry_run)
+        lib = b.lib
         # the 1x1 heatmap head is dead in the volumetric path: only its SHAPE is used (reference :264)
         # bf16 plans: the fused stem reads the caller's fp32 images (pointer handed over per forward through this cell)
         image_cell = {"ptr": None, "ref": None}
@@ -419,7 +424,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         if volc is not None:
             conf = volc.t.reshape(B, NV, 32)   # 'conf_norm' is normalised inside the kernel (LT_AGG_CONF_NORM)
         vol = b.alloc((B, V, V, V, 32))
-        esz = torch.empty((), dtype=dt).element_size()
+        esz = E.esize(self.compute_dtype)
         agg = H.AGG[self.volume_aggregation_method]
         # ONE launch: the voxel centres are computed in registers from (position, centre, rotation, step) and written to the returned
         # coordinate tensor on the way (reference :298-339 + op.py:99-166); configurations without a fused kernel run
@@ -617,8 +622,7 @@ class VolumetricTriangulationNet(_PlannedNet):
             if P["image_cell"] is not None:     # the plan's first op reads the images where they are
                 P["image_cell"]["ptr"], P["image_cell"]["ref"] = x.data_ptr(), x
             else:
-                H.check(H.lib().lt_nchw_to_nhwc(H.dtype_code(self.compute_dtype), x.data_ptr(), P["x_in"].t.data_ptr(), B * NV, 3, Hh * W,
-                                                P["x_in"].t.shape[-1], st), "lt_nchw_to_nhwc")
+                E.stage_images(x, P["x_in"], st)
             plan = P["plan"]
             if self.use_graph and not P["captured"]:
                 plan.run_eager(st)          # warm-up launch outside capture (sets func attributes, loads code objects)
@@ -662,11 +666,8 @@ class AlgebraicTriangulationNet(_PlannedNet):
         self.heatmap_multiplier = m.heatmap_multiplier
 
     def _build_plan(self, B, NV, Hh, W, device):
-        dt = self.compute_dtype
-        b = E.PlanBuilder(device, dt, self.tile_override)
-        lib = H.lib()
-        x_in = b.alloc((B * NV, 1, Hh, W, E.min_cin_of(dt)))
-        x_in.pooled = False
+        b, x_in = self._open_plan(B * NV, Hh, W, device)
+        lib = b.lib
         hm, feats, algc, _ = self.backbone.record(b, x_in, want_heatmaps=True)
         b.release(feats)
         N = B * NV
@@ -753,9 +754,7 @@ class AlgebraicTriangulationNet(_PlannedNet):
     def _run(self, P, images, proj_matricies, B, NV, Hh, W, device):
         h, w = P["hw"]; J = P["J"]
         st = torch.cuda.current_stream(device).cuda_stream
-        x = images.reshape(B * NV, 3, Hh, W).float().contiguous()
-        H.check(H.lib().lt_nchw_to_nhwc(H.dtype_code(self.compute_dtype), x.data_ptr(), P["x_in"].t.data_ptr(), B * NV, 3, Hh * W,
-                                        P["x_in"].t.shape[-1], st), "lt_nchw_to_nhwc")
+        E.stage_images(images.reshape(B * NV, 3, Hh, W).float().contiguous(), P["x_in"], st)
         P["plan"].run_eager(st)
         heatmaps = P["probs"].reshape(B, NV, J, h, w).clone()
         # reference :173-193 in one lt_alg_tail_fwd launch: confidences normalised over the views + 1e-5, keypoints to image pixels, the DLT --
@@ -788,10 +787,8 @@ class RANSACTriangulationNet(_PlannedNet):
         self.reprojection_error_epsilon = 15
 
     def _build_plan(self, B, NV, Hh, W, device):
-        b = E.PlanBuilder(device, self.compute_dtype, self.tile_override)
-        lib = H.lib()
-        x_in = b.alloc((B * NV, 1, Hh, W, E.min_cin_of(self.compute_dtype)))
-        x_in.pooled = False
+        b, x_in = self._open_plan(B * NV, Hh, W, device)
+        lib = b.lib
         hm, feats, _, _ = self.backbone.record(b, x_in, want_heatmaps=True)
         b.release(feats)
         N = B * NV
@@ -823,9 +820,7 @@ class RANSACTriangulationNet(_PlannedNet):
             P = self._plan_for(key, lambda: self._build_plan(B, NV, Hh, W, device))
             h, w = P["hw"]; J = P["J"]
             st = torch.cuda.current_stream(device).cuda_stream
-            x = images.reshape(B * NV, 3, Hh, W).float().contiguous()
-            H.check(H.lib().lt_nchw_to_nhwc(H.dtype_code(self.compute_dtype), x.data_ptr(), P["x_in"].t.data_ptr(), B * NV, 3, Hh * W,
-                                            P["x_in"].t.shape[-1], st), "lt_nchw_to_nhwc")
+            E.stage_images(images.reshape(B * NV, 3, Hh, W).float().contiguous(), P["x_in"], st)
             P["plan"].run_eager(st)
             heatmaps = P["hm"].reshape(B, NV, J, h, w).clone()
             kp2d = P["kp2d"].reshape(B, NV, J, 2).clone()
