@@ -282,6 +282,15 @@ int lt_unproject_fwd(int32_t dtype, const void* feats, const float* proj, const 
 int lt_unproject_grid_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                           float step, int32_t cmu_transfer, float* coords_out, const float* conf, void* out, int32_t B, int32_t NV,
                           int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream);
+/* The seam of the cascade (lt_plan_forward_cascade, CascadeTriangulationNet): the pelvis and cuboid algebra of VolumetricTriangulationNet.forward
+ * (triangulation.py:284-296) on joints that are already on the device, bit-identical to what the host route writes into a plan's geometry block.
+ *   keypoints_3d: DEVICE (B, J, 3) fp32.  kind LT_KIND_MPII: base = joint 6; LT_KIND_COCO: base = (joint 11 + joint 12) / 2, added and halved in fp32.
+ *   base is promoted to fp64; position = base - cuboid_side / 2 in fp64; center = fp32(base), pos = fp32(position): DEVICE (B, 3) fp32 each, the
+ *   pos / center arguments of lt_unproject_grid_fwd and lt_coord_volumes.  One lane per (sample, axis).
+ * J < 7 (mpii) / 13 (coco), B < 1, an unknown kind or a null pointer is LT_ERR_INVALID before anything is enqueued. */
+enum { LT_KIND_MPII = 0, LT_KIND_COCO = 1 };
+int lt_cuboid_from_keypoints(const float* keypoints_3d, int32_t B, int32_t J, int32_t kind, double cuboid_side, float* pos, float* center,
+                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * op.integrate_tensor_3d_with_coordinates (mvn/utils/op.py:84-96):
@@ -771,6 +780,31 @@ typedef struct lt_alg_plan_config {
 int lt_plan_create_alg(const lt_alg_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out);
 int lt_plan_forward_alg(lt_plan* plan, const float* images, const float* proj, float* keypoints_3d, void* keypoints_2d, float* heatmaps,
                         float* confidences, void* stream);
+/* The cascade: the reference's two-stage evaluation route (an algebraic run writes pred_results_path, the volumetric run centres its cuboid on that
+ * pelvis; eval/human36m_vol_softmax.yaml, use_gt_pelvis: false) as ONE forward.  The plan holds an algebraic and a volumetric plan of the same input shape;
+ * the algebraic stage's joints stay on the device, lt_cuboid_from_keypoints turns them into the volumetric plan's cuboid origins behind the geometry copy
+ * on the same stream: nothing between the stages waits for the GPU or copies to the host.
+ * lt_plan_create_cascade: cfg.alg.model must be LT_MODEL_ALG; cfg.vol's B, NV, H, W must equal cfg.alg's; kind LT_KIND_MPII | LT_KIND_COCO with
+ *   alg.num_joints >= 7 / 13.  Any of these wrong (and every config error of the two create calls) is LT_ERR_INVALID before any device call.
+ *   alg_weights / vol_weights: the two state dicts, as for lt_plan_create_alg / lt_plan_create_vol (the reference's checkpoints are separate networks).
+ * lt_plan_forward_cascade: images DEVICE (B, NV, 3, H, W) fp32; cameras HOST fp64 at IMAGE resolution as for lt_plan_forward_vol, given once: the call
+ *   forms the algebraic stage's K [R | t] in fp64 and rounds it to fp32 (datasets/utils.py:prepare_batch) and the heatmap-resolution projections as
+ *   lt_plan_forward_vol does.  rot_host as lt_plan_forward_vol (NULL = identity).  Outputs, DEVICE fp32, on `stream`: keypoints_3d (B, J, 3) of the
+ *   volumetric stage [required]; alg_keypoints_3d (B, J_alg, 3) of the algebraic stage and base_points (B, 3), the pelvis the cuboid is centred on
+ *   (NULL: kept in plan buffers); volumes, features, coord_volumes, vol_confidences as lt_plan_forward_vol.  Both stages run with use_graph as their
+ *   configs say.  The result is bit-identical to lt_plan_forward_alg, a copy of its joints to the host, and lt_plan_forward_vol on them.
+ * lt_plan_info on a cascade plan sums both stages (heatmap size and logits: the volumetric stage's); lt_plan_forward_vol / lt_plan_forward_alg on a
+ * cascade plan, and lt_plan_forward_cascade on any other plan, are LT_ERR_INVALID. */
+typedef struct lt_cascade_plan_config {
+    lt_alg_plan_config alg;               /* model must be LT_MODEL_ALG */
+    lt_vol_plan_config vol;               /* B, NV, H, W must equal alg's */
+    int32_t kind;                         /* config.model.kind of the volumetric model: LT_KIND_MPII | LT_KIND_COCO */
+} lt_cascade_plan_config;
+int lt_plan_create_cascade(const lt_cascade_plan_config* cfg, const lt_named_tensor* alg_weights, int32_t n_alg, const lt_named_tensor* vol_weights,
+                           int32_t n_vol, lt_plan** plan_out);
+int lt_plan_forward_cascade(lt_plan* plan, const float* images, const double* K_host, const double* R_host, const double* t_host, const double* rot_host,
+                            float* keypoints_3d, float* alg_keypoints_3d, float* base_points, float* volumes, float* features, float* coord_volumes,
+                            float* vol_confidences, void* stream);
 int lt_plan_info(const lt_plan* plan, lt_plan_info_t* info);
 void lt_plan_destroy(lt_plan* plan);
 

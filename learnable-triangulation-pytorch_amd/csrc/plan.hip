@@ -1,6 +1,7 @@
 // Plan-level entry points of the C ABI ("whole-network plan entry points that own pre-packed weights and a hipGraph"):
 //   lt_plan_create_vol / lt_plan_forward_vol          VolumetricTriangulationNet
 //   lt_plan_create_alg / lt_plan_forward_alg          AlgebraicTriangulationNet (LT_MODEL_ALG) and RANSACTriangulationNet (LT_MODEL_RANSAC)
+//   lt_plan_create_cascade / lt_plan_forward_cascade  the algebraic plan's pelvis -> the volumetric plan's cuboid, on the device (CascadeTriangulationNet)
 //   lt_plan_info / lt_plan_destroy                    any plan
 // A non-Python host hands over the reference's state_dict (names + host fp32 arrays) and the model configuration once, and then calls the forward with
 // device images and host camera parameters: layer -> kernel selection, every batch threshold, the eval-BatchNorm fold, weight packing (GEMM layout,
@@ -49,6 +50,7 @@ namespace {
 
 constexpr float BN_EPS = 1e-5f;
 constexpr int GEO_RING = 4;
+constexpr int MODEL_CASCADE = 3;          // lt_plan::model of a cascade plan (not a value of lt_alg_plan_config.model)
 
 unsigned short bf16_rne(float f) {          // torch's float -> bfloat16 (round to nearest even, NaN kept quiet)
     unsigned u;
@@ -223,7 +225,7 @@ int make_conv_spec(const WT& w, const float* bias, const BN* bn, const int in[5]
 // =====================================================================================================================================
 struct lt_plan {
     lt_vol_plan_config cfg;                     // volumetric plans; the algebraic / RANSAC plans fill the fields they share (shape, dtype, use_graph)
-    int model = 0;                              // 0: volumetric plan, else LT_MODEL_ALG | LT_MODEL_RANSAC (acfg)
+    int model = 0;                              // 0: volumetric plan, LT_MODEL_ALG | LT_MODEL_RANSAC (acfg), or MODEL_CASCADE (sub_alg + sub_vol)
     lt_alg_plan_config acfg = {};
     const char* who = "lt_plan_create_vol";     // the entry point that builds the plan, for error messages
     int dtype = LT_F32, es = 4;                 // element type / size of activations and weights
@@ -259,6 +261,10 @@ struct lt_plan {
     Act algc;                                   // alg_confidences head output [1,1,1,N,J] fp32 (algebraic plans with use_confidences)
     float* hm_nchw = nullptr; float* kp_hm = nullptr; int64_t* kp_i64 = nullptr;          // heatmaps N,J,h,w; soft-argmax N,J,2 (heatmap px); argmax N,J,2
     int hm_h = 0, hm_w = 0;
+    // cascade plans: the two stages, the algebraic stage's image-resolution projections (pinned ring + device copy; the slots and their events are
+    // sub_vol's geometry ring's: its copy is queued behind this one on the same stream) and its joints when the caller does not ask for them
+    lt_plan* sub_alg = nullptr; lt_plan* sub_vol = nullptr; int kind = 0;
+    float* cproj_dev = nullptr; float* cproj_host[GEO_RING] = {nullptr, nullptr, nullptr, nullptr}; float* ckp_alg = nullptr;
     int n_xr = 0, n_bneck = 0, n_bneck_ds = 0, n_cat2 = 0, n_halo2d = 0, n_pwchain = 0, n_stem = 0, n_splitk = 0, n_conv_skip = 0;
 
     ~lt_plan() {
@@ -267,6 +273,9 @@ struct lt_plan {
         for (int i = 0; i < 2; ++i) if (own_ev[i]) (void)hipEventDestroy(own_ev[i]);
         for (void* p : allocs) (void)hipFree(p);
         for (int i = 0; i < GEO_RING; ++i) { if (geo_host[i]) (void)hipHostFree(geo_host[i]); if (geo_ev[i]) (void)hipEventDestroy(geo_ev[i]); }
+        for (int i = 0; i < GEO_RING; ++i) if (cproj_host[i]) (void)hipHostFree(cproj_host[i]);
+        delete sub_alg;
+        delete sub_vol;
     }
 
     // ---- memory ------------------------------------------------------------------------------------------------------------------
@@ -519,6 +528,8 @@ struct lt_plan {
             const bool last = i + 1 == L.size();
             const int fl = (L[i].relu ? LT_EPI_RELU_POST : 0) | (last ? LT_EPI_STORE_F32 : 0);
             ConvSpec sp; PL_TRY(make_conv_spec(L[i].w, L[i].bias, L[i].bn, shape, 1, 0, es, false, fl, 0, sp));
+            // lt_pwchain_fwd reads [32][k_pad] weights and 32 epilogue constants per layer: a last layer of <= 16 channels is packed with 16 rows, pad it
+            if (sp.cout_pad < 32) { sp.ph[0].w.resize((size_t)32 * sp.k_pad, 0.f); sp.bias.resize(32, 0.f); sp.scale.resize(32, 0.f); sp.shift.resize(32, 0.f); }
             const void* wdev; PL_TRY(upload_w(sp.ph[0].w, &wdev));
             const float *bi, *sc, *sh;
             PL_TRY(upload_f32(sp.bias, &bi)); PL_TRY(upload_f32(sp.scale, &sc)); PL_TRY(upload_f32(sp.shift, &sh));
@@ -1014,6 +1025,51 @@ struct lt_plan {
         return LT_OK;
     }
 
+    // ---- host geometry in fp64 like the reference (triangulation.py:272-296): Camera.update_after_resize to the heatmap resolution, projection = K [R | t];
+    // cuboid position = base - side / 2; rotation about the vertical axis (identity in eval mode); one pinned block, one H2D copy.  base_points_host NULL
+    // (cascade plans): the pos / center ranges are left for lt_cuboid_from_keypoints, which the caller enqueues behind the copy.  proj_img (cascade plans,
+    // the ring slot's block): K [R | t] at IMAGE resolution rounded to fp32, the algebraic stage's proj_matricies_batch.
+    int stage_geometry(const double* K_host, const double* R_host, const double* t_host, const double* base_points_host, const double* rot_host, hipStream_t st,
+                       float* const* proj_img_ring = nullptr) {
+        const int B = cfg.B, NV = cfg.NV;
+        const int slot = geo_slot = (geo_slot + 1) % GEO_RING;
+        if (geo_ev[slot]) PL_HIP(hipEventSynchronize(geo_ev[slot]));          // the copy that last read this slot (GEO_RING forwards ago) has completed
+        else PL_HIP(hipEventCreateWithFlags(&geo_ev[slot], hipEventDisableTiming));
+        float* gh = geo_host[slot];
+        float* pi = proj_img_ring ? proj_img_ring[slot] : nullptr;
+        const double sx = (double)hm_w / (double)cfg.W, sy = (double)hm_h / (double)cfg.H;
+        for (int i = 0; i < B * NV; ++i) {
+            double K[9];
+            for (int k = 0; k < 9; ++k) K[k] = K_host[(size_t)i * 9 + k];
+            const double* R = R_host + (size_t)i * 9; const double* t = t_host + (size_t)i * 3;
+            if (pi)
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 4; ++c) {
+                        double acc = 0.0;
+                        for (int k = 0; k < 3; ++k) acc += K[r * 3 + k] * (c < 3 ? R[k * 3 + c] : t[k]);
+                        pi[(size_t)i * 12 + r * 4 + c] = (float)acc;
+                    }
+            K[0] *= sx; K[4] *= sy; K[2] *= sx; K[5] *= sy;
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 4; ++c) {
+                    double acc = 0.0;
+                    for (int k = 0; k < 3; ++k) acc += K[r * 3 + k] * (c < 3 ? R[k * 3 + c] : t[k]);
+                    gh[(size_t)i * 12 + r * 4 + c] = (float)acc;
+                }
+        }
+        const double half = (double)cfg.cuboid_side / 2.0;
+        for (int b = 0; b < B; ++b) {
+            for (int k = 0; k < 3 && base_points_host; ++k) {
+                gh[o_pos + 3 * b + k] = (float)(base_points_host[3 * b + k] - half);
+                gh[o_cen + 3 * b + k] = (float)base_points_host[3 * b + k];
+            }
+            for (int k = 0; k < 9; ++k) gh[o_rot + 9 * b + k] = rot_host ? (float)rot_host[9 * b + k] : ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f);
+        }
+        PL_HIP(hipMemcpyAsync(geo_dev, gh, n_geo * 4, hipMemcpyHostToDevice, st));
+        PL_HIP(hipEventRecord(geo_ev[slot], st));
+        return LT_OK;
+    }
+
     int run(hipStream_t st) {
         const int nops = (int)ops.size();
         for (int i = 0; i < npre; ++i) PL_TRY(ops[i](st));
@@ -1055,13 +1111,30 @@ bool load_state_dict(lt_plan* p, const lt_named_tensor* weights, int32_t nweight
 }
 }  // namespace
 
-extern "C" int lt_plan_create_vol(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
-    LT_REQUIRE(cfg && weights && plan_out && nweights > 0, LT_ERR_INVALID, "lt_plan_create_vol: null argument");
-    LT_REQUIRE(cfg->dtype == LT_F32 || cfg->dtype == LT_BF16, LT_ERR_INVALID, "lt_plan_create_vol: dtype %d", cfg->dtype);
-    LT_REQUIRE(cfg->B >= 1 && cfg->NV >= 1 && cfg->H >= 32 && cfg->W >= 32 && cfg->volume_size >= 2 && cfg->num_joints >= 1, LT_ERR_INVALID, "lt_plan_create_vol: bad shape");
-    LT_REQUIRE(cfg->aggregation >= LT_AGG_SUM && cfg->aggregation <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "lt_plan_create_vol: aggregation %d", cfg->aggregation);
-    *plan_out = nullptr;
+namespace {
+// the configuration checks of the create calls, before any device call; who: the entry point, for the message
+int check_vol_config(const lt_vol_plan_config* cfg, const char* who) {
+    LT_REQUIRE(cfg->dtype == LT_F32 || cfg->dtype == LT_BF16, LT_ERR_INVALID, "%s: dtype %d", who, cfg->dtype);
+    LT_REQUIRE(cfg->B >= 1 && cfg->NV >= 1 && cfg->H >= 32 && cfg->W >= 32 && cfg->volume_size >= 2 && cfg->num_joints >= 1, LT_ERR_INVALID, "%s: bad shape", who);
+    LT_REQUIRE(cfg->aggregation >= LT_AGG_SUM && cfg->aggregation <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "%s: aggregation %d", who, cfg->aggregation);
+    return LT_OK;
+}
+int check_alg_config(const lt_alg_plan_config& c, const char* who) {
+    LT_REQUIRE(c.model == LT_MODEL_ALG || c.model == LT_MODEL_RANSAC, LT_ERR_INVALID, "%s: model %d (LT_MODEL_ALG | LT_MODEL_RANSAC)", who, c.model);
+    LT_REQUIRE(c.dtype == LT_F32 || c.dtype == LT_BF16, LT_ERR_INVALID, "%s: dtype %d", who, c.dtype);
+    LT_REQUIRE(c.B >= 1 && c.NV >= 2 && c.H >= 32 && c.W >= 32 && c.num_joints >= 1, LT_ERR_INVALID,
+               "%s: bad shape (B %d, NV %d, H %d, W %d, num_joints %d; at least 2 views to triangulate, 32 x 32 images)", who, c.B, c.NV, c.H, c.W, c.num_joints);
+    if (c.model == LT_MODEL_RANSAC) {
+        LT_REQUIRE(c.num_joints <= 32, LT_ERR_INVALID, "%s: num_joints %d > 32 (RANSAC's heatmap argmax)", who, c.num_joints);
+        LT_REQUIRE(c.NV <= 32, LT_ERR_INVALID, "%s: NV %d views (RANSAC: 2 <= NV <= 32)", who, c.NV);
+    }
+    return LT_OK;
+}
+
+// a checked configuration + a state dict -> a recorded plan
+int make_vol_plan(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, const char* who, lt_plan** plan_out) {
     lt_plan* p = new lt_plan();
+    p->who = who;
     p->cfg = *cfg;
     p->dtype = cfg->dtype; p->es = cfg->dtype == LT_F32 ? 4 : 2;
     if (!load_state_dict(p, weights, nweights)) { delete p; return LT_ERR_INVALID; }
@@ -1071,47 +1144,57 @@ extern "C" int lt_plan_create_vol(const lt_vol_plan_config* cfg, const lt_named_
     *plan_out = p;
     return LT_OK;
 }
+// the heads an algebraic / RANSAC model reads besides the backbone, named before any device work
+int check_alg_heads(const lt_alg_plan_config& c, const lt_named_tensor* weights, int32_t nweights, const char* who) {
+    lt_plan probe;
+    probe.who = who;
+    if (!load_state_dict(&probe, weights, nweights)) return LT_ERR_INVALID;
+    std::vector<std::string> heads = {"backbone.final_layer.weight", "backbone.final_layer.bias"};
+    if (c.model == LT_MODEL_ALG && c.use_confidences) heads.push_back("backbone.alg_confidences.head.4.weight");
+    for (const std::string& k : heads) LT_REQUIRE(probe.has(k), LT_ERR_INVALID, "%s: state dict has no '%s'", who, k.c_str());
+    return LT_OK;
+}
+int make_alg_plan(const lt_alg_plan_config& c, const lt_named_tensor* weights, int32_t nweights, const char* who, lt_plan** plan_out) {
+    PL_TRY(check_alg_heads(c, weights, nweights, who));
+    lt_plan* p = new lt_plan();
+    p->who = who;
+    p->model = c.model; p->acfg = c;
+    memset(&p->cfg, 0, sizeof(p->cfg));
+    p->cfg.dtype = c.dtype; p->cfg.num_layers = c.num_layers; p->cfg.style_caffe = c.style_caffe; p->cfg.num_joints = c.num_joints;
+    p->cfg.B = c.B; p->cfg.NV = c.NV; p->cfg.H = c.H; p->cfg.W = c.W; p->cfg.use_graph = c.use_graph;
+    p->dtype = c.dtype; p->es = c.dtype == LT_F32 ? 4 : 2;
+    if (!load_state_dict(p, weights, nweights)) { delete p; return LT_ERR_INVALID; }
+    const int rc = p->build_alg();
+    if (rc != LT_OK) { delete p; return rc; }
+    p->sd.clear();          // the caller's host arrays are not referenced after this call
+    *plan_out = p;
+    return LT_OK;
+}
+const char* plan_kind_name(const lt_plan* p) {
+    return p->model == 0 ? "a volumetric plan of lt_plan_create_vol" : p->model == MODEL_CASCADE ? "a cascade plan of lt_plan_create_cascade"
+           : p->model == LT_MODEL_RANSAC ? "an LT_MODEL_RANSAC plan of lt_plan_create_alg" : "an LT_MODEL_ALG plan of lt_plan_create_alg";
+}
+}  // namespace
+
+extern "C" int lt_plan_create_vol(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
+    LT_REQUIRE(cfg && weights && plan_out && nweights > 0, LT_ERR_INVALID, "lt_plan_create_vol: null argument");
+    PL_TRY(check_vol_config(cfg, "lt_plan_create_vol"));
+    *plan_out = nullptr;
+    return make_vol_plan(cfg, weights, nweights, "lt_plan_create_vol", plan_out);
+}
 
 extern "C" int lt_plan_forward_vol(lt_plan* p, const float* images, const double* K_host, const double* R_host, const double* t_host, const double* base_points_host,
                                    const double* rot_host, float* keypoints_3d, float* volumes, float* features, float* coord_volumes, float* vol_confidences,
                                    void* stream) {
     LT_REQUIRE(p, LT_ERR_INVALID, "lt_plan_forward_vol: null argument");
-    LT_REQUIRE(p->model == 0, LT_ERR_INVALID, "lt_plan_forward_vol: the plan is an %s plan of lt_plan_create_alg; run it with lt_plan_forward_alg",
-               p->model == LT_MODEL_RANSAC ? "LT_MODEL_RANSAC" : "LT_MODEL_ALG");
+    LT_REQUIRE(p->model == 0, LT_ERR_INVALID, "lt_plan_forward_vol: the plan is %s; run it with %s", plan_kind_name(p),
+               p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_alg");
     LT_REQUIRE(images && K_host && R_host && t_host && base_points_host && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_vol: null argument");
     hipStream_t st = (hipStream_t)stream;
     bool detour;
     PL_TRY(p->enter(st, detour));
     const int B = p->cfg.B, NV = p->cfg.NV, V = p->cfg.volume_size;
-    // ---- host geometry in fp64 like the reference (triangulation.py:272-296): Camera.update_after_resize to the heatmap resolution, projection = K [R | t];
-    // cuboid position = base - side / 2; rotation about the vertical axis (identity in eval mode); one pinned block, one H2D copy
-    const int slot = p->geo_slot = (p->geo_slot + 1) % GEO_RING;
-    if (p->geo_ev[slot]) PL_HIP(hipEventSynchronize(p->geo_ev[slot]));          // the copy that last read this slot (GEO_RING forwards ago) has completed
-    else PL_HIP(hipEventCreateWithFlags(&p->geo_ev[slot], hipEventDisableTiming));
-    float* gh = p->geo_host[slot];
-    const double sx = (double)p->hm_w / (double)p->cfg.W, sy = (double)p->hm_h / (double)p->cfg.H;
-    for (int i = 0; i < B * NV; ++i) {
-        double K[9];
-        for (int k = 0; k < 9; ++k) K[k] = K_host[(size_t)i * 9 + k];
-        K[0] *= sx; K[4] *= sy; K[2] *= sx; K[5] *= sy;
-        const double* R = R_host + (size_t)i * 9; const double* t = t_host + (size_t)i * 3;
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c) {
-                double acc = 0.0;
-                for (int k = 0; k < 3; ++k) acc += K[r * 3 + k] * (c < 3 ? R[k * 3 + c] : t[k]);
-                gh[(size_t)i * 12 + r * 4 + c] = (float)acc;
-            }
-    }
-    const double half = (double)p->cfg.cuboid_side / 2.0;
-    for (int b = 0; b < B; ++b) {
-        for (int k = 0; k < 3; ++k) {
-            gh[p->o_pos + 3 * b + k] = (float)(base_points_host[3 * b + k] - half);
-            gh[p->o_cen + 3 * b + k] = (float)base_points_host[3 * b + k];
-        }
-        for (int k = 0; k < 9; ++k) gh[p->o_rot + 9 * b + k] = rot_host ? (float)rot_host[9 * b + k] : ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f);
-    }
-    PL_HIP(hipMemcpyAsync(p->geo_dev, gh, p->n_geo * 4, hipMemcpyHostToDevice, st));
-    PL_HIP(hipEventRecord(p->geo_ev[slot], st));
+    PL_TRY(p->stage_geometry(K_host, R_host, t_host, base_points_host, rot_host, st));
     p->cur_images = images; p->out_kp = keypoints_3d; p->out_probs = volumes; p->out_feats = features;
     PL_TRY(p->run(st));
     if (coord_volumes) PL_HIP(hipMemcpyAsync(coord_volumes, p->coords, (size_t)B * V * V * V * 3 * 4, hipMemcpyDeviceToDevice, st));
@@ -1125,40 +1208,16 @@ extern "C" int lt_plan_forward_vol(lt_plan* p, const float* images, const double
 
 extern "C" int lt_plan_create_alg(const lt_alg_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
     LT_REQUIRE(cfg && weights && plan_out && nweights > 0, LT_ERR_INVALID, "lt_plan_create_alg: null argument");
-    const lt_alg_plan_config& c = *cfg;
-    LT_REQUIRE(c.model == LT_MODEL_ALG || c.model == LT_MODEL_RANSAC, LT_ERR_INVALID, "lt_plan_create_alg: model %d (LT_MODEL_ALG | LT_MODEL_RANSAC)", c.model);
-    LT_REQUIRE(c.dtype == LT_F32 || c.dtype == LT_BF16, LT_ERR_INVALID, "lt_plan_create_alg: dtype %d", c.dtype);
-    LT_REQUIRE(c.B >= 1 && c.NV >= 2 && c.H >= 32 && c.W >= 32 && c.num_joints >= 1, LT_ERR_INVALID,
-               "lt_plan_create_alg: bad shape (B %d, NV %d, H %d, W %d, num_joints %d; at least 2 views to triangulate, 32 x 32 images)", c.B, c.NV, c.H, c.W, c.num_joints);
-    if (c.model == LT_MODEL_RANSAC) {
-        LT_REQUIRE(c.num_joints <= 32, LT_ERR_INVALID, "lt_plan_create_alg: num_joints %d > 32 (RANSAC's heatmap argmax)", c.num_joints);
-        LT_REQUIRE(c.NV <= 32, LT_ERR_INVALID, "lt_plan_create_alg: NV %d views (RANSAC: 2 <= NV <= 32)", c.NV);
-    }
+    PL_TRY(check_alg_config(*cfg, "lt_plan_create_alg"));
     *plan_out = nullptr;
-    lt_plan* p = new lt_plan();
-    p->who = "lt_plan_create_alg";
-    p->model = c.model; p->acfg = c;
-    memset(&p->cfg, 0, sizeof(p->cfg));
-    p->cfg.dtype = c.dtype; p->cfg.num_layers = c.num_layers; p->cfg.style_caffe = c.style_caffe; p->cfg.num_joints = c.num_joints;
-    p->cfg.B = c.B; p->cfg.NV = c.NV; p->cfg.H = c.H; p->cfg.W = c.W; p->cfg.use_graph = c.use_graph;
-    p->dtype = c.dtype; p->es = c.dtype == LT_F32 ? 4 : 2;
-    if (!load_state_dict(p, weights, nweights)) { delete p; return LT_ERR_INVALID; }
-    // the heads this model reads besides the backbone, named before any device work
-    std::vector<std::string> heads = {"backbone.final_layer.weight", "backbone.final_layer.bias"};
-    if (c.model == LT_MODEL_ALG && c.use_confidences) heads.push_back("backbone.alg_confidences.head.4.weight");
-    for (const std::string& k : heads)
-        if (!p->has(k)) { set_error("lt_plan_create_alg: state dict has no '%s'", k.c_str()); delete p; return LT_ERR_INVALID; }
-    const int rc = p->build_alg();
-    if (rc != LT_OK) { delete p; return rc; }
-    p->sd.clear();          // the caller's host arrays are not referenced after this call
-    *plan_out = p;
-    return LT_OK;
+    return make_alg_plan(*cfg, weights, nweights, "lt_plan_create_alg", plan_out);
 }
 
 extern "C" int lt_plan_forward_alg(lt_plan* p, const float* images, const float* proj, float* keypoints_3d, void* keypoints_2d, float* heatmaps,
                                    float* confidences, void* stream) {
     LT_REQUIRE(p, LT_ERR_INVALID, "lt_plan_forward_alg: null argument");
-    LT_REQUIRE(p->model != 0, LT_ERR_INVALID, "lt_plan_forward_alg: the plan is a volumetric plan of lt_plan_create_vol; run it with lt_plan_forward_vol");
+    LT_REQUIRE(p->model == LT_MODEL_ALG || p->model == LT_MODEL_RANSAC, LT_ERR_INVALID, "lt_plan_forward_alg: the plan is %s; run it with %s", plan_kind_name(p),
+               p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_vol");
     LT_REQUIRE(images && proj && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_alg: null argument (images, proj and keypoints_3d are required)");
     hipStream_t st = (hipStream_t)stream;
     bool detour;
@@ -1176,9 +1235,94 @@ extern "C" int lt_plan_forward_alg(lt_plan* p, const float* images, const float*
     return LT_OK;
 }
 
+extern "C" int lt_plan_create_cascade(const lt_cascade_plan_config* cfg, const lt_named_tensor* alg_weights, int32_t n_alg, const lt_named_tensor* vol_weights,
+                                      int32_t n_vol, lt_plan** plan_out) {
+    const char* who = "lt_plan_create_cascade";
+    LT_REQUIRE(cfg && alg_weights && vol_weights && plan_out && n_alg > 0 && n_vol > 0, LT_ERR_INVALID, "%s: null argument", who);
+    const lt_alg_plan_config& a = cfg->alg; const lt_vol_plan_config& v = cfg->vol;
+    PL_TRY(check_alg_config(a, who));
+    LT_REQUIRE(a.model == LT_MODEL_ALG, LT_ERR_INVALID, "%s: alg.model %d (the pelvis comes from LT_MODEL_ALG; LT_MODEL_RANSAC is not a stage of the cascade)", who, a.model);
+    PL_TRY(check_vol_config(&v, who));
+    LT_REQUIRE(v.B == a.B && v.NV == a.NV && v.H == a.H && v.W == a.W, LT_ERR_INVALID,
+               "%s: vol.B %d, vol.NV %d, vol.H %d, vol.W %d differ from alg.B %d, alg.NV %d, alg.H %d, alg.W %d (both stages read the same images)", who, v.B, v.NV, v.H,
+               v.W, a.B, a.NV, a.H, a.W);
+    LT_REQUIRE(cfg->kind == LT_KIND_MPII || cfg->kind == LT_KIND_COCO, LT_ERR_INVALID, "%s: kind %d (LT_KIND_MPII | LT_KIND_COCO)", who, cfg->kind);
+    const int need = cfg->kind == LT_KIND_COCO ? 13 : 7;
+    LT_REQUIRE(a.num_joints >= need, LT_ERR_INVALID, "%s: alg.num_joints %d, kind '%s' reads joint %d", who, a.num_joints, cfg->kind == LT_KIND_COCO ? "coco" : "mpii", need - 1);
+    PL_TRY(check_alg_heads(a, alg_weights, n_alg, who));
+    *plan_out = nullptr;
+    lt_plan* p = new lt_plan();
+    p->who = who; p->model = MODEL_CASCADE; p->kind = cfg->kind;
+    p->cfg = v; p->acfg = a;
+    p->cfg.use_graph = (a.use_graph || v.use_graph) ? 1 : 0;          // enter(): a stage that captures cannot run on the legacy default stream
+    p->dtype = v.dtype; p->es = v.dtype == LT_F32 ? 4 : 2;
+    int rc = make_alg_plan(a, alg_weights, n_alg, who, &p->sub_alg);
+    if (rc == LT_OK) rc = make_vol_plan(&v, vol_weights, n_vol, who, &p->sub_vol);
+    auto finish = [&]() -> int {
+        const size_t nproj = (size_t)a.B * a.NV * 12 * 4;
+        void* q;
+        PL_TRY(p->dev_alloc(nproj, &q)); p->cproj_dev = (float*)q;
+        PL_TRY(p->dev_alloc((size_t)a.B * a.num_joints * 3 * 4, &q)); p->ckp_alg = (float*)q;
+        for (int i = 0; i < GEO_RING; ++i) PL_HIP(hipHostMalloc((void**)&p->cproj_host[i], nproj, hipHostMallocDefault));
+        return LT_OK;
+    };
+    if (rc == LT_OK) rc = finish();
+    if (rc != LT_OK) { delete p; return rc; }
+    *plan_out = p;
+    return LT_OK;
+}
+
+extern "C" int lt_plan_forward_cascade(lt_plan* p, const float* images, const double* K_host, const double* R_host, const double* t_host, const double* rot_host,
+                                       float* keypoints_3d, float* alg_keypoints_3d, float* base_points, float* volumes, float* features, float* coord_volumes,
+                                       float* vol_confidences, void* stream) {
+    LT_REQUIRE(p, LT_ERR_INVALID, "lt_plan_forward_cascade: null argument");
+    LT_REQUIRE(p->model == MODEL_CASCADE, LT_ERR_INVALID, "lt_plan_forward_cascade: the plan is %s; run it with %s", plan_kind_name(p),
+               p->model == 0 ? "lt_plan_forward_vol" : "lt_plan_forward_alg");
+    LT_REQUIRE(images && K_host && R_host && t_host && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_cascade: null argument (images, K, R, t and keypoints_3d are required)");
+    lt_plan* A = p->sub_alg; lt_plan* Vp = p->sub_vol;
+    LT_REQUIRE(!vol_confidences || !Vp->volc.null(), LT_ERR_INVALID,
+               "lt_plan_forward_cascade: vol_confidences asked of a plan without the confidence head (aggregation %d)", Vp->cfg.aggregation);
+    hipStream_t st = (hipStream_t)stream;
+    bool detour;
+    PL_TRY(p->enter(st, detour));
+    const int B = Vp->cfg.B, NV = Vp->cfg.NV, V = Vp->cfg.volume_size;
+    // cameras once: the volumetric stage's block (projections at heatmap resolution, rotations; pos / center are the seam kernel's) and the algebraic
+    // stage's projections at image resolution, two H2D copies out of the same ring slot; the slot's event is re-recorded behind the second
+    PL_TRY(Vp->stage_geometry(K_host, R_host, t_host, nullptr, rot_host, st, p->cproj_host));
+    PL_HIP(hipMemcpyAsync(p->cproj_dev, p->cproj_host[Vp->geo_slot], (size_t)B * NV * 12 * 4, hipMemcpyHostToDevice, st));
+    PL_HIP(hipEventRecord(Vp->geo_ev[Vp->geo_slot], st));
+    // stage 1: lt_plan_forward_alg's launches
+    float* kp_alg = alg_keypoints_3d ? alg_keypoints_3d : p->ckp_alg;
+    A->cur_images = images; A->cur_proj = p->cproj_dev; A->out_kp = kp_alg; A->out_kp2d = nullptr; A->out_hm = nullptr; A->out_conf = nullptr;
+    PL_TRY(A->run(st));
+    // the seam: joints -> cuboid origin and centre, straight into the block lt_unproject_grid_fwd reads
+    PL_TRY(lt_cuboid_from_keypoints(kp_alg, B, p->acfg.num_joints, p->kind, Vp->cfg.cuboid_side, Vp->geo_dev + Vp->o_pos, Vp->geo_dev + Vp->o_cen, st));
+    if (base_points) PL_HIP(hipMemcpyAsync(base_points, Vp->geo_dev + Vp->o_cen, (size_t)B * 3 * 4, hipMemcpyDeviceToDevice, st));
+    // stage 2: lt_plan_forward_vol's launches
+    Vp->cur_images = images; Vp->out_kp = keypoints_3d; Vp->out_probs = volumes; Vp->out_feats = features;
+    PL_TRY(Vp->run(st));
+    if (coord_volumes) PL_HIP(hipMemcpyAsync(coord_volumes, Vp->coords, (size_t)B * V * V * V * 3 * 4, hipMemcpyDeviceToDevice, st));
+    if (vol_confidences) PL_HIP(hipMemcpyAsync(vol_confidences, Vp->volc.p, (size_t)B * NV * 32 * 4, hipMemcpyDeviceToDevice, st));
+    PL_TRY(p->leave(st, detour));
+    return LT_OK;
+}
+
 extern "C" int lt_plan_info(const lt_plan* p, lt_plan_info_t* info) {
     LT_REQUIRE(p && info, LT_ERR_INVALID, "lt_plan_info: null argument");
     memset(info, 0, sizeof(*info));
+    if (p->model == MODEL_CASCADE) {          // both stages' launches, flops, memory and census; heatmap size and logits: the volumetric stage's
+        lt_plan_info_t a;
+        PL_TRY(lt_plan_info(p->sub_vol, info));
+        PL_TRY(lt_plan_info(p->sub_alg, &a));
+        info->launches += a.launches + 1;
+        info->flops += a.flops; info->bytes_allocated += a.bytes_allocated + (int64_t)p->bytes_alloc;
+        info->n_expand_reduce += a.n_expand_reduce; info->n_bottleneck += a.n_bottleneck; info->n_bottleneck_ds += a.n_bottleneck_ds; info->n_conv_cat2 += a.n_conv_cat2;
+        info->n_conv2d_halo += a.n_conv2d_halo; info->n_pwchain += a.n_pwchain; info->n_stem_pool += a.n_stem_pool; info->n_splitk += a.n_splitk;
+        info->n_conv_skip += a.n_conv_skip;
+        info->graph_captured = (!p->sub_alg->cfg.use_graph || a.graph_captured) && (!p->sub_vol->cfg.use_graph || info->graph_captured) &&
+                               (p->sub_alg->cfg.use_graph || p->sub_vol->cfg.use_graph) ? 1 : 0;
+        return LT_OK;
+    }
     info->launches = (int32_t)p->ops.size();
     info->heatmap_h = p->hm_h; info->heatmap_w = p->hm_w;
     info->flops = p->flops; info->bytes_allocated = (int64_t)p->bytes_alloc;

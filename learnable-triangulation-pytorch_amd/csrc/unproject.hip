@@ -552,3 +552,37 @@ extern "C" int lt_rotate_points(const float* x, const float* rot, float* y, int6
     LT_CHECK_LAUNCH("lt_rotate_points");
     return LT_OK;
 }
+
+// ---- the seam of the cascade: the algebraic model's joints -> the volumetric cuboid, on the device ----------------------------------------
+namespace {
+// VolumetricTriangulationNet._host_geometry's pelvis and cuboid algebra (triangulation.py:284-296 of the reference), step for step and type for type:
+// base in fp32 (joint 6, or the fp32 mean of joints 11 and 12), promoted to fp64; position = base - side / 2 in fp64; both rounded to fp32.
+// One lane per (sample, axis).
+__global__ void cuboid_from_keypoints_kernel(const float* __restrict__ kp, int n, int J, int coco, double half, float* __restrict__ pos,
+                                             float* __restrict__ center) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const int b = g / 3, k = g - 3 * b;
+    const float* s = kp + (size_t)b * J * 3 + k;
+    float base32;
+    if (coco) base32 = __fdiv_rn(__fadd_rn(s[11 * 3], s[12 * 3]), 2.0f);
+    else base32 = s[6 * 3];
+    const double base = (double)base32;
+    center[g] = (float)base;
+    pos[g] = (float)__dsub_rn(base, half);
+}
+}  // namespace
+
+extern "C" int lt_cuboid_from_keypoints(const float* keypoints_3d, int32_t B, int32_t J, int32_t kind, double cuboid_side, float* pos, float* center,
+                                        void* stream) {
+    LT_REQUIRE(keypoints_3d && pos && center, LT_ERR_INVALID, "lt_cuboid_from_keypoints: null argument (keypoints_3d, pos and center are required)");
+    LT_REQUIRE(kind == LT_KIND_MPII || kind == LT_KIND_COCO, LT_ERR_INVALID, "lt_cuboid_from_keypoints: kind %d (LT_KIND_MPII | LT_KIND_COCO)", kind);
+    LT_REQUIRE(B >= 1 && (long long)B * 3 < (1ll << 31), LT_ERR_INVALID, "lt_cuboid_from_keypoints: B %d", B);
+    const int need = kind == LT_KIND_COCO ? 13 : 7;
+    LT_REQUIRE(J >= need, LT_ERR_INVALID, "lt_cuboid_from_keypoints: J %d joints, kind '%s' reads joint %d", J, kind == LT_KIND_COCO ? "coco" : "mpii", need - 1);
+    const int n = B * 3;
+    hipLaunchKernelGGL(cuboid_from_keypoints_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, keypoints_3d, n, J,
+                       kind == LT_KIND_COCO ? 1 : 0, cuboid_side / 2.0, pos, center);
+    LT_CHECK_LAUNCH("lt_cuboid_from_keypoints");
+    return LT_OK;
+}

@@ -580,8 +580,11 @@ class PlanBuilder(Recorder):
             flags = (H.EPI_RELU_POST if relu else 0) | (H.EPI_STORE_F32 if last else 0)
             spec = make_conv_spec(w, bias, bn, shape, 1, 0, self.dtype, False, flags)
             specs.append(spec)
-            wdev = self.const(spec.phases[0].weight, self.dtype)
-            bi, sc, sh = self.const(spec.bias), self.const(spec.scale), self.const(spec.shift)
+            # lt_pwchain_fwd reads [32][k_pad] weights and 32 epilogue constants per layer (include/lt_hip.h); a last layer of <= 16 channels is packed
+            # with 16 rows (cout_pad_of): pad it, or the kernel reads 2 KB past the weights' allocation
+            rows = lambda t: t if t.shape[0] >= 32 else torch.cat([t, t.new_zeros((32 - t.shape[0],) + tuple(t.shape[1:]))])
+            wdev = self.const(rows(spec.phases[0].weight), self.dtype)
+            bi, sc, sh = self.const(rows(spec.bias)), self.const(rows(spec.scale)), self.const(rows(spec.shift))
             d.cout[i], d.k_pad[i], d.flags[i] = spec.Cout, spec.k_pad, flags
             d.weight[i], d.bias[i], d.scale[i], d.shift[i] = wdev.data_ptr(), bi.data_ptr(), sc.data_ptr(), sh.data_ptr()
             flops += 2 * d.rows * spec.Cout * w.shape[1]

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("LT_HIP_LIB") or os.path.join(HERE, "lib", "liblt_hip.
 LT_F32, LT_BF16, LT_FP8 = 0, 1, 2
 AGG = {"sum": 0, "max": 1, "softmax": 2, "conf": 3, "conf_norm": 4}
 LT_MODEL_ALG, LT_MODEL_RANSAC = 1, 2          # lt_alg_plan_config.model
+LT_KIND_MPII, LT_KIND_COCO = 0, 1             # lt_cuboid_from_keypoints, lt_cascade_plan_config.kind
+KIND = {"mpii": LT_KIND_MPII, "coco": LT_KIND_COCO}
 EPI_RELU_PRE, EPI_RELU_POST, EPI_STORE_F32, EPI_SIGMOID = 1, 2, 4, 8
 EPI_RES_F32 = 64
 BN_FROZEN = 32
@@ -109,6 +111,10 @@ class AlgPlanConfig(C.Structure):
                 ("reprojection_error_epsilon", C.c_double), ("use_graph", i32)]
 
 
+class CascadePlanConfig(C.Structure):
+    _fields_ = [("alg", AlgPlanConfig), ("vol", VolPlanConfig), ("kind", i32)]
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("launches", i32), ("heatmap_h", i32), ("heatmap_w", i32), ("flops", C.c_double), ("bytes_allocated", C.c_int64),
                 ("n_expand_reduce", i32), ("n_bottleneck", i32), ("n_bottleneck_ds", i32), ("n_conv_cat2", i32), ("n_conv2d_halo", i32), ("n_pwchain", i32),
@@ -121,6 +127,8 @@ SIGNATURES = {
     "lt_plan_forward_vol": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_create_alg": (C.c_int, [C.POINTER(AlgPlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
     "lt_plan_forward_alg": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "lt_plan_create_cascade": (C.c_int, [C.POINTER(CascadePlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
+    "lt_plan_forward_cascade": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),
     "lt_plan_destroy": (None, [vp]),
     "lt_last_error": (C.c_char_p, []),
@@ -158,6 +166,7 @@ SIGNATURES = {
     "lt_rotate_points": (C.c_int, [vp, vp, vp, i64, vp]),
     "lt_unproject_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_unproject_grid_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "lt_cuboid_from_keypoints": (C.c_int, [vp, i32, i32, i32, C.c_double, vp, vp, vp]),
     "lt_softargmax3d_workspace": (C.c_size_t, [i32, i32, i64]),
     "lt_softargmax3d_fwd": (C.c_int, [vp, vp, f32, i32, i32, i32, vp, vp, i32, i32, i64, vp, vp]),
     "lt_softargmax2d_fwd": (C.c_int, [vp, f32, i32, vp, vp, i32, i32, i32, vp]),

@@ -4,6 +4,9 @@
     AlgebraicTriangulationNet(config, device).forward(images, proj_matricies, batch)
     RANSACTriangulationNet(config, device).forward(images, proj_matricies, batch)
 
+and, beyond the reference, ``CascadeTriangulationNet(alg_net, vol_net)``: its two-stage evaluation route (the algebraic model's pelvis centres the
+volumetric cuboid) as one forward with the pelvis kept on the GPU.
+
 Same constructor side effects on ``config``, same ``state_dict()`` keys, same return tuples.  The whole
 forward is ONE recorded plan of liblt_hip launches per input shape, captured into a hipGraph:
 
@@ -464,19 +467,13 @@ class VolumetricTriangulationNet(_PlannedNet):
                 "probs": probs, "conf": conf, "logits": logits, "vol": vol, "hw": (h, w), "offs": (o_pos, o_cen, o_rot),
                 "captured": False}
 
-    def _host_geometry(self, batch, B, image_shape, P):
-        """numpy fp64 camera / cuboid algebra of the reference (:272-296, :318-328), vectorised; fills the plan's pinned
-        geometry block (fp32: projections, cuboid origins, centres, rotations).  Returns (position, base, sides)."""
+    def _host_cameras(self, batch, B, image_shape, P):
+        """The camera half of the host geometry (reference :272-279, :318-328): fills the projections and rotations of the next slot of the plan's
+        pinned geometry ring and makes it ``P["geo_host"]``; the slot's cuboid origins and centres are the caller's to fill (``_host_geometry``)
+        or to leave to ``lt_cuboid_from_keypoints`` behind the copy (``CascadeTriangulationNet``)."""
         h, w = P["hw"]
         K, R, t = multiview.stack_cameras(batch["cameras"])
         proj = multiview.resized_projections(K, R, t, image_shape, (h, w))
-        kp3d = batch["keypoints_3d"] if self.use_gt_pelvis else batch["pred_keypoints_3d"]
-        base = np.empty((B, 3), dtype=np.float64)
-        for i in range(B):
-            k3 = np.asarray(kp3d[i])
-            base[i] = (k3[11, :3] + k3[12, :3]) / 2 if self.kind == "coco" else k3[6, :3]
-        sides = np.array([self.cuboid_side] * 3)
-        position = base - sides / 2
         axis = [0, 1, 0] if self.kind == "coco" else [0, 0, 1]
         rot = np.empty((B, 9))
         for i in range(B):
@@ -489,9 +486,23 @@ class VolumetricTriangulationNet(_PlannedNet):
             ev.synchronize()         # the copy that last read this slot (GEO_RING forwards ago) has completed
         gh = P["geo_host"] = P["geo_ring"][slot]
         gh[:o_pos] = torch.from_numpy(proj.astype(np.float32).reshape(-1))
+        gh[o_rot:] = torch.from_numpy(rot.astype(np.float32).reshape(-1))
+        return gh
+
+    def _host_geometry(self, batch, B, image_shape, P):
+        """numpy fp64 camera / cuboid algebra of the reference (:272-296, :318-328), vectorised; fills the plan's pinned
+        geometry block (fp32: projections, cuboid origins, centres, rotations).  Returns (position, base, sides)."""
+        kp3d = batch["keypoints_3d"] if self.use_gt_pelvis else batch["pred_keypoints_3d"]
+        base = np.empty((B, 3), dtype=np.float64)
+        for i in range(B):
+            k3 = np.asarray(kp3d[i])
+            base[i] = (k3[11, :3] + k3[12, :3]) / 2 if self.kind == "coco" else k3[6, :3]
+        sides = np.array([self.cuboid_side] * 3)
+        position = base - sides / 2
+        gh = self._host_cameras(batch, B, image_shape, P)
+        o_pos, o_cen, o_rot = P["offs"]
         gh[o_pos:o_cen] = torch.from_numpy(position.astype(np.float32).reshape(-1))
         gh[o_cen:o_rot] = torch.from_numpy(base.astype(np.float32).reshape(-1))
-        gh[o_rot:] = torch.from_numpy(rot.astype(np.float32).reshape(-1))
         return position, base, sides
 
     # ---------------------------------------------------------------------------------------
@@ -589,7 +600,8 @@ class VolumetricTriangulationNet(_PlannedNet):
         cuboids = [volumetric.Cuboid3D(position[i], sides) for i in range(images.shape[0])]
         return kp, feats, probs, plan.conf_out, cuboids, coords, base_points
 
-    def _forward_chunk(self, images, batch, lo, hi):
+    def _chunk_plan(self, images, batch, lo, hi):
+        """Samples lo .. hi of the call and the plan of that shape: (images, batch, B, P)."""
         device = images.device
         NV = images.shape[1]
         Hh, W = images.shape[3:]
@@ -605,49 +617,72 @@ class VolumetricTriangulationNet(_PlannedNet):
                float(self.volume_multiplier), bool(self.volume_softmax), self.volume_aggregation_method,
                bool(self.transfer_cmu_to_human36m), self.tile_override, self.num_joints)
         P = self._plan_for(key, lambda: self._build_plan(B, NV, Hh, W, device))
+        return images, batch, B, P
+
+    @staticmethod
+    def _plan_images(images, B, NV):
+        x = images.reshape(B * NV, 3, images.shape[3], images.shape[4])
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.float().contiguous()
+        return x
+
+    @staticmethod
+    def _copy_geometry(P, side):
+        """On the side stream: the filled ring slot to the plan's device block, and the event that frees the slot."""
+        P["geo"].copy_(P["geo_host"], non_blocking=True)
+        ev = P["geo_events"][P["geo_slot"]] = P["geo_events"][P["geo_slot"]] or torch.cuda.Event()
+        ev.record(side)
+
+    def _replay(self, P, x, B, NV, side, cur):
+        """On the side stream, behind the geometry: the plan's launches.  Returns (kp, feats, probs, conf, coords, base_points)."""
+        device = x.device
         h, w = P["hw"]
+        st = side.cuda_stream
+        if P["image_cell"] is not None:     # the plan's first op reads the images where they are
+            P["image_cell"]["ptr"], P["image_cell"]["ref"] = x.data_ptr(), x
+        else:
+            E.stage_images(x, P["x_in"], st)
+        plan = P["plan"]
+        if self.use_graph and not P["captured"]:
+            plan.run_eager(st)          # warm-up launch outside capture (sets func attributes, loads code objects)
+            side.synchronize()
+            plan.capture(st)
+            P["captured"] = True
+        kp, probs, coords = P["kp"], P["probs"], P["coords"]
+        if self.copy_outputs:       # fresh result tensors like the reference's: the tail ops write them directly
+            kp, probs = torch.empty_like(kp), torch.empty_like(probs)
+            feats = torch.empty(B, NV, 32, h, w, dtype=torch.float32, device=device)
+            plan.run(st, (kp, probs, feats))
+        else:
+            plan.run(st)
+            feats = P["feats"].t.reshape(B, NV, h, w, 32).permute(0, 1, 4, 2, 3)
+        conf = P["conf"]
+        o_pos, o_cen, o_rot = P["offs"]
+        base_points = P["geo"][o_cen:o_rot].reshape(B, 3).clone()    # fp32(base), from the block that was just copied in
+        if self.copy_outputs:
+            coords = coords.clone()
+            conf = None if conf is None else conf.clone()
+        if conf is not None and self.volume_aggregation_method == "conf_norm":
+            conf = conf / conf.sum(dim=1, keepdim=True)   # the RETURNED confidences are the normalised ones (reference :268-269, :355)
+        for t in (kp, probs, coords, feats, base_points, conf):
+            if t is not None:
+                t.record_stream(cur)     # allocated on the side stream, handed to the caller's stream
+        return kp, feats, probs, conf, coords, base_points
+
+    def _forward_chunk(self, images, batch, lo, hi):
+        device = images.device
+        NV = images.shape[1]
+        Hh, W = images.shape[3:]
+        images, batch, B, P = self._chunk_plan(images, batch, lo, hi)
         position, base, sides = self._host_geometry(batch, B, (Hh, W), P)
         # ---- device side ----
         cur = torch.cuda.current_stream(device)
         side = self._side_stream(device)
         side.wait_stream(cur)
-        x = images.reshape(B * NV, 3, Hh, W)
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
+        x = self._plan_images(images, B, NV)
         with torch.cuda.stream(side):
-            st = side.cuda_stream
-            P["geo"].copy_(P["geo_host"], non_blocking=True)
-            ev = P["geo_events"][P["geo_slot"]] = P["geo_events"][P["geo_slot"]] or torch.cuda.Event()
-            ev.record(side)
-            if P["image_cell"] is not None:     # the plan's first op reads the images where they are
-                P["image_cell"]["ptr"], P["image_cell"]["ref"] = x.data_ptr(), x
-            else:
-                E.stage_images(x, P["x_in"], st)
-            plan = P["plan"]
-            if self.use_graph and not P["captured"]:
-                plan.run_eager(st)          # warm-up launch outside capture (sets func attributes, loads code objects)
-                side.synchronize()
-                plan.capture(st)
-                P["captured"] = True
-            kp, probs, coords = P["kp"], P["probs"], P["coords"]
-            if self.copy_outputs:       # fresh result tensors like the reference's: the tail ops write them directly
-                kp, probs = torch.empty_like(kp), torch.empty_like(probs)
-                feats = torch.empty(B, NV, 32, h, w, dtype=torch.float32, device=device)
-                plan.run(st, (kp, probs, feats))
-            else:
-                plan.run(st)
-                feats = P["feats"].t.reshape(B, NV, h, w, 32).permute(0, 1, 4, 2, 3)
-            conf = P["conf"]
-            o_pos, o_cen, o_rot = P["offs"]
-            base_points = P["geo"][o_cen:o_rot].reshape(B, 3).clone()    # fp32(base), from the block that was just copied in
-            if self.copy_outputs:
-                coords = coords.clone()
-                conf = None if conf is None else conf.clone()
-            if conf is not None and self.volume_aggregation_method == "conf_norm":
-                conf = conf / conf.sum(dim=1, keepdim=True)   # the RETURNED confidences are the normalised ones (reference :268-269, :355)
-            for t in (kp, probs, coords, feats, base_points, conf):
-                if t is not None:
-                    t.record_stream(cur)     # allocated on the side stream, handed to the caller's stream
+            self._copy_geometry(P, side)
+            kp, feats, probs, conf, coords, base_points = self._replay(P, x, B, NV, side, cur)
         x.record_stream(side)
         cur.wait_stream(side)
         cuboids = [volumetric.Cuboid3D(position[i], sides) for i in range(B)]
@@ -842,3 +877,111 @@ class RANSACTriangulationNet(_PlannedNet):
         pts = torch.as_tensor(np.asarray(points).astype(np.int64)).to(dev)[None, :, None, :]
         kp, inl = multiview.triangulate_ransac_batch(P, pts, None, reprojection_error_epsilon, direct_optimization, return_inliers=True)
         return kp[0, 0].double().cpu().numpy(), np.nonzero(inl[0, 0].cpu().numpy())[0]
+
+
+class _LazyCuboids:
+    """The ``cuboids`` of a cascade forward: a sequence of ``Cuboid3D(position, sides)`` whose positions are on the GPU until somebody looks.  The
+    first access copies the (B, 3) centres to the host -- THAT access waits for the GPU -- and builds the items as ``VolumetricTriangulationNet``
+    does: position = fp64(centre) - sides / 2."""
+
+    def __init__(self, base_points, cuboid_side):
+        self._base, self._side, self._items = base_points, cuboid_side, None
+
+    def _build(self):
+        if self._items is None:
+            base = self._base.detach().cpu().numpy().astype(np.float64)
+            sides = np.array([self._side] * 3)
+            position = base - sides / 2
+            self._items = [volumetric.Cuboid3D(position[i], sides) for i in range(len(position))]
+            self._base = None
+        return self._items
+
+    def __len__(self):
+        return len(self._base) if self._items is None else len(self._items)
+
+    def __getitem__(self, i):
+        return self._build()[i]
+
+    def __iter__(self):
+        return iter(self._build())
+
+
+class CascadeTriangulationNet(nn.Module):
+    """The reference's two-stage evaluation route as ONE forward: its published volumetric numbers centre the cuboid on the pelvis an earlier run
+    of the algebraic model wrote to disk (``pred_results_path``, ``use_gt_pelvis: false`` in eval/human36m_vol_softmax.yaml).  Here the algebraic
+    stage's joints stay on the GPU: ``lt_cuboid_from_keypoints`` turns them into the volumetric plan's cuboid origins behind the geometry copy, so
+    nothing between the two stages waits for the GPU or copies to the host.  Bit-identical to running ``alg``, copying its joints to the host and
+    running ``vol`` with them as ``batch["pred_keypoints_3d"]``.
+
+    ``alg`` / ``vol`` are the two existing modules (state-dict keys ``alg.*`` / ``vol.*``; each loads a reference checkpoint as it does alone), with
+    their own ``compute_dtype`` / ``use_graph`` / ``copy_outputs``.  Inference only."""
+
+    def __init__(self, alg_net, vol_net):
+        super().__init__()
+        if not isinstance(alg_net, AlgebraicTriangulationNet) or not isinstance(vol_net, VolumetricTriangulationNet):
+            raise TypeError("CascadeTriangulationNet(alg_net, vol_net) takes an AlgebraicTriangulationNet and a VolumetricTriangulationNet")
+        if vol_net.kind not in H.KIND:
+            raise ValueError("CascadeTriangulationNet: vol_net.kind %r ('mpii' | 'coco')" % (vol_net.kind,))
+        need = 13 if vol_net.kind == "coco" else 7
+        J = alg_net.backbone.final_layer.out_channels
+        if J < need:
+            raise ValueError("CascadeTriangulationNet: the algebraic model has %d joints, kind '%s' reads joint %d" % (J, vol_net.kind, need - 1))
+        self.alg, self.vol = alg_net, vol_net
+
+    def forward(self, images, proj_matricies, batch):
+        """images (B,NV,3,H,W) fp32 on the GPU; ``proj_matricies`` (B,NV,3,4) at image resolution for the algebraic stage; ``batch`` needs only
+        ``cameras`` (``pred_keypoints_3d`` / ``keypoints_3d`` are ignored).  Returns ``(vol_outputs, alg_outputs)``: the 7-tuple of
+        ``VolumetricTriangulationNet.forward`` and the 4-tuple of ``AlgebraicTriangulationNet.forward``, same shapes and dtypes.  ``base_points``
+        is read from the device block; ``cuboids`` is a sequence that builds its ``Cuboid3D`` items on first access, and that access
+        synchronises with the GPU (the forward itself never does, beyond what the two models' forwards do at their first call of a shape)."""
+        H.require_gpu(images, "images")
+        if _bn_in_train_mode(self):
+            raise NotImplementedError("CascadeTriangulationNet runs in eval() only: train the two stages on their own (the reference trains the "
+                                      "volumetric model on pelvises read from a results file)")
+        vol = self.vol
+        alg_out = self.alg(images, proj_matricies, batch)
+        kp_alg = alg_out[0]
+        _sync_buffers_before_eval(vol)
+        B, NV = images.shape[:2]
+        cap = vol.max_samples_per_launch(NV, images.shape[3], images.shape[4])
+        n = -(-B // cap)
+        size = -(-B // n)            # the sub-batches of VolumetricTriangulationNet.forward
+        parts = []
+        with torch.cuda.device(images.device):
+            for lo in range(0, B, size):
+                parts.append(self._vol_chunk(images, batch, kp_alg, lo, min(B, lo + size)))
+        if len(parts) == 1:
+            kp, feats, probs, conf, coords, base_points = parts[0]
+        else:
+            cat = lambda i: torch.cat([p[i] for p in parts], dim=0)
+            kp, feats, probs, conf, coords, base_points = cat(0), cat(1), cat(2), None if parts[0][3] is None else cat(3), cat(4), cat(5)
+        cuboids = _LazyCuboids(base_points, vol.cuboid_side)
+        return (kp, feats, probs, conf, cuboids, coords, base_points), alg_out
+
+    def _vol_chunk(self, images, batch, kp_alg, lo, hi):
+        """VolumetricTriangulationNet._forward_chunk with the pelvis taken on the device: the camera half of the geometry block from the host, its
+        cuboid origins and centres from ``lt_cuboid_from_keypoints`` on the side stream behind the block's copy."""
+        vol = self.vol
+        device = images.device
+        NV = images.shape[1]
+        Hh, W = images.shape[3:]
+        images, batch, B, P = vol._chunk_plan(images, batch, lo, hi)
+        vol._host_cameras(batch, B, (Hh, W), P)
+        kp_alg = kp_alg[lo:hi]
+        if kp_alg.dtype != torch.float32 or not kp_alg.is_contiguous():
+            kp_alg = kp_alg.float().contiguous()
+        cur = torch.cuda.current_stream(device)
+        side = vol._side_stream(device)
+        side.wait_stream(cur)          # behind the algebraic stage: its joints are complete when the seam kernel starts
+        x = vol._plan_images(images, B, NV)
+        o_pos, o_cen, _ = P["offs"]
+        gp = P["geo"].data_ptr()
+        with torch.cuda.stream(side):
+            vol._copy_geometry(P, side)
+            H.check(H.lib().lt_cuboid_from_keypoints(kp_alg.data_ptr(), B, kp_alg.shape[1], H.KIND[vol.kind], float(vol.cuboid_side), gp + 4 * o_pos, gp + 4 * o_cen,
+                                                     side.cuda_stream), "lt_cuboid_from_keypoints")
+            out = vol._replay(P, x, B, NV, side, cur)
+        kp_alg.record_stream(side)
+        x.record_stream(side)
+        cur.wait_stream(side)
+        return out

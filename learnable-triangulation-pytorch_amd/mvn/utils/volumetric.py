@@ -14,6 +14,22 @@ class Cuboid3D:
         self.sides = sides
 
 
+def cuboid_from_keypoints(kp, kind, cuboid_side):
+    """The pelvis and cuboid algebra of ``VolumetricTriangulationNet.forward`` (reference :284-296) on fp32 joints ``kp`` (B, J, 3): the CPU statement
+    of liblt_hip's ``lt_cuboid_from_keypoints``, bit for bit.  base = joint 6 ('mpii') or (joint 11 + joint 12) / 2 ('coco', added and halved in
+    fp32), promoted to fp64; position = base - cuboid_side / 2 in fp64.  Returns (pos, center): fp32(position), fp32(base), (B, 3) each."""
+    kp = np.asarray(kp, dtype=np.float32)
+    need = 13 if kind == "coco" else 7
+    if kp.ndim != 3 or kp.shape[0] < 1 or kp.shape[1] < need or kp.shape[2] < 3:
+        raise ValueError("cuboid_from_keypoints: keypoints of shape %s, kind '%s' reads joint %d of (B, J, 3)" % (kp.shape, kind, need - 1))
+    base = np.empty((kp.shape[0], 3), dtype=np.float64)
+    for i in range(kp.shape[0]):
+        base[i] = (kp[i, 11, :3] + kp[i, 12, :3]) / 2 if kind == "coco" else kp[i, 6, :3]
+    sides = np.array([cuboid_side] * 3)
+    position = base - sides / 2
+    return position.astype(np.float32), base.astype(np.float32)
+
+
 def get_rotation_matrix(axis, theta):
     """Counter-clockwise rotation by theta about axis, Euler-Rodrigues form (reference :87-99), fp64."""
     ax = np.asarray(axis, dtype=np.float64)
