@@ -282,6 +282,19 @@ int lt_unproject_fwd(int32_t dtype, const void* feats, const float* proj, const 
 int lt_unproject_grid_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                           float step, int32_t cmu_transfer, float* coords_out, const float* conf, void* out, int32_t B, int32_t NV,
                           int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream);
+/* lt_unproject_fwd / lt_unproject_grid_fwd over the VALID views of every sample: view_mask is DEVICE (B, NV) uint8, non-zero = valid.  Sample b
+ * gets what the unmasked entry gives for its views {v : view_mask[b][v]} alone, in increasing v: a masked view's feature map is never read
+ * (NaN there cannot leak), it is not projected into, and it takes no part in the sum, the max, the softmax's max or denominator, the conf sum
+ * or conf_norm's normaliser.  A sample without a valid view writes zeros.  fp32 and every generic configuration: bit-identical to the
+ * unmasked entry on the compacted views; the fused bf16 kernel (C = 32, 4 or 8 views, view softmax, bricked volume) keeps its own masked
+ * variant, whose arithmetic and order with an all-ones mask are exactly the unmasked kernel's, and in which a masked view costs no loads,
+ * no blend and no exp2 (the mask is uniform over a workgroup: one scalar branch per view).  A null view_mask is LT_ERR_INVALID. */
+int lt_unproject_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                            void* out, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2, int32_t agg,
+                            void* stream);
+int lt_unproject_grid_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
+                                 float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask, void* out,
+                                 int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream);
 /* The seam of the cascade (lt_plan_forward_cascade, CascadeTriangulationNet): the pelvis and cuboid algebra of VolumetricTriangulationNet.forward
  * (triangulation.py:284-296) on joints that are already on the device, bit-identical to what the host route writes into a plan's geometry block.
  *   keypoints_3d: DEVICE (B, J, 3) fp32.  kind LT_KIND_MPII: base = joint 6; LT_KIND_COCO: base = (joint 11 + joint 12) / 2, added and halved in fp32.
@@ -492,6 +505,16 @@ int lt_triangulate_dlt(const float* proj, const float* points, const float* conf
  * interleaved partial sums, view v into partial v % 4; plain view order up to four views).  NV >= 2. */
 int lt_alg_tail_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
                     float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV, int32_t J, void* stream);
+/* lt_alg_tail_fwd over the VALID views of every sample (view_mask: DEVICE (B, NV) uint8, non-zero = valid; NULL is LT_ERR_INVALID):
+ *   confidences = raw / (sum of raw over the valid views) + 1e-5 for a valid view, exactly 0 for a masked one; the k-th valid view goes into
+ *                 partial k % 4 of the view sum, i.e. what lt_alg_tail_fwd does on the compacted views;
+ *   keypoints_2d is written for every view (a masked view's value is unspecified: its keypoints_hm times the scale);
+ *   keypoints_3d = the DLT over the rows of the valid views only, in increasing v: a masked view's keypoints and projection matrix do not
+ *                  enter the system, so NaN there cannot leak.  Bit-identical to lt_alg_tail_fwd on the compacted views.
+ * A sample with fewer than two valid views gets NaN joints (the model and plan layers refuse such a mask before launching). */
+int lt_alg_tail_masked_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                           const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV,
+                           int32_t J, void* stream);
 
 /* RANSACTriangulationNet (reference mvn/models/triangulation.py:17-128), 2D part: the backbone's N,h,w,(ld) fp32 heatmaps ->
  * heatmaps_nchw N,J,h,w (the raw heatmaps the model returns, bit-identical to lt_nhwc_to_nchw_f32) and, in the same pass, the argmax
@@ -805,6 +828,17 @@ int lt_plan_create_cascade(const lt_cascade_plan_config* cfg, const lt_named_ten
 int lt_plan_forward_cascade(lt_plan* plan, const float* images, const double* K_host, const double* R_host, const double* t_host, const double* rot_host,
                             float* keypoints_3d, float* alg_keypoints_3d, float* base_points, float* volumes, float* features, float* coord_volumes,
                             float* vol_confidences, void* stream);
+/* Per-sample view masks: mask_host is HOST (B, NV) uint8, non-zero = the view is there, NULL = all valid.  Sample b of every later forward gets what
+ * the plan gives for that sample on its valid views alone: the gather skips masked views (lt_unproject_grid_masked_fwd), the algebraic tail normalises
+ * the confidences over the valid views and forms the DLT from their rows (lt_alg_tail_masked_fwd: masked confidences are 0); a cascade plan applies the
+ * one mask to both stages.  Features, heatmaps and 2D keypoints of masked views are unspecified; the backbone still runs on them.
+ *   The FIRST call must come before the plan's first forward: it makes the plan a masked plan (what is launched and captured is chosen there);
+ *   afterwards a first call is LT_ERR_INVALID.  Later calls replace the mask; it persists until replaced.  The mask travels with the geometry
+ *   block's copy (volumetric / cascade plans: same pinned ring, same hipMemcpyAsync) or, for algebraic plans, by one small copy of its own when it
+ *   has changed -- outside the captured graph, so a new mask on a captured plan is just another forward.
+ *   LT_ERR_INVALID (the message names the sample): a sample without a valid view (volumetric plans) or with fewer than two (algebraic, cascade).
+ *   LT_ERR_UNSUPPORTED: an LT_MODEL_RANSAC plan.  Results are bit-identical to the Python host's forward with batch["view_mask"]. */
+int lt_plan_set_view_mask(lt_plan* plan, const uint8_t* mask_host);
 int lt_plan_info(const lt_plan* plan, lt_plan_info_t* info);
 void lt_plan_destroy(lt_plan* plan);
 

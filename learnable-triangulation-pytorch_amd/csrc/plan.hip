@@ -265,6 +265,15 @@ struct lt_plan {
     // sub_vol's geometry ring's: its copy is queued behind this one on the same stream) and its joints when the caller does not ask for them
     lt_plan* sub_alg = nullptr; lt_plan* sub_vol = nullptr; int kind = 0;
     float* cproj_dev = nullptr; float* cproj_host[GEO_RING] = {nullptr, nullptr, nullptr, nullptr}; float* ckp_alg = nullptr;
+    // per-sample view masks (lt_plan_set_view_mask).  masked: the gather / the algebraic tail run their masked entry points, chosen before the first forward
+    // (what the graph captures).  mask_cur: the host (B, NV) mask, kept until replaced.  Volumetric plans carry it at the end of the geometry block (o_mask:
+    // offset in floats; same ring slot, same copy); algebraic plans have no such block: a ring of their own, copied when the mask has changed; the algebraic
+    // stage of a cascade reads the volumetric stage's block.
+    bool masked = false, ran = false, mask_dirty = false;
+    std::vector<uint8_t> mask_cur;
+    const uint8_t* mask_dev = nullptr; size_t o_mask = 0;
+    uint8_t* amask_dev = nullptr; uint8_t* amask_host[GEO_RING] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t amask_ev[GEO_RING] = {nullptr, nullptr, nullptr, nullptr};
+    int amask_slot = 0;
     int n_xr = 0, n_bneck = 0, n_bneck_ds = 0, n_cat2 = 0, n_halo2d = 0, n_pwchain = 0, n_stem = 0, n_splitk = 0, n_conv_skip = 0;
 
     ~lt_plan() {
@@ -274,6 +283,7 @@ struct lt_plan {
         for (void* p : allocs) (void)hipFree(p);
         for (int i = 0; i < GEO_RING; ++i) { if (geo_host[i]) (void)hipHostFree(geo_host[i]); if (geo_ev[i]) (void)hipEventDestroy(geo_ev[i]); }
         for (int i = 0; i < GEO_RING; ++i) if (cproj_host[i]) (void)hipHostFree(cproj_host[i]);
+        for (int i = 0; i < GEO_RING; ++i) { if (amask_host[i]) (void)hipHostFree(amask_host[i]); if (amask_ev[i]) (void)hipEventDestroy(amask_ev[i]); }
         delete sub_alg;
         delete sub_vol;
     }
@@ -935,9 +945,15 @@ struct lt_plan {
         const float step = (float)(cfg.cuboid_side / (double)(V - 1));          // float(np.float32(side / (V - 1))): the fp64 quotient rounded once
         {
             const int dt = dtype, agg = cfg.aggregation, cmu = cfg.transfer_cmu_to_human36m ? 1 : 0, h = hm_h, w = hm_w;
-            const float* gp = geo_dev; const size_t op = o_pos, oc = o_cen, orr = o_rot;
+            const size_t op = o_pos, oc = o_cen, orr = o_rot; lt_plan* self = this;
             const void* fp = feats.p; float* cp = coords; void* vp = vol.p; const float* confp = volc.null() ? nullptr : (const float*)volc.p;
-            ops.push_back([=](hipStream_t s) { return lt_unproject_grid_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, vp, B, NV, 32, h, w, V, agg, s); });
+            // the block's address is read when the op runs: a masked plan (lt_plan_set_view_mask, before the first forward) has moved it to a block with the mask behind
+            ops.push_back([=](hipStream_t s) {
+                const float* gp = self->geo_dev;
+                if (self->masked)
+                    return lt_unproject_grid_masked_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, self->mask_dev, vp, B, NV, 32, h, w, V, agg, s);
+                return lt_unproject_grid_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, vp, B, NV, 32, h, w, V, agg, s);
+            });
         }
         PL_TRY(record_v2v(vol, logits));
         void* k; PL_TRY(dev_alloc((size_t)B * J * 3 * 4, &k)); kp = (float*)k;
@@ -998,6 +1014,8 @@ struct lt_plan {
             const float sx = (float)((double)W / (double)w), sy = (float)((double)Hh / (double)h);          // torch.tensor([W / w, H / h], float32)
             const float* kh = kp_hm; const float* cp = algc.null() ? nullptr : (const float*)algc.p; const int ldc = algc.null() ? J : algc.c;
             ops.push_back([=](hipStream_t s) {
+                if (self->masked)
+                    return lt_alg_tail_masked_fwd(kh, cp, ldc, self->cur_proj, sx, sy, self->mask_dev, (float*)self->out_kp2d, self->out_conf, self->out_kp, B, NV, J, s);
                 return lt_alg_tail_fwd(kh, cp, ldc, self->cur_proj, sx, sy, (float*)self->out_kp2d, self->out_conf, self->out_kp, B, NV, J, s);
             });
         }
@@ -1065,8 +1083,57 @@ struct lt_plan {
             }
             for (int k = 0; k < 9; ++k) gh[o_rot + 9 * b + k] = rot_host ? (float)rot_host[9 * b + k] : ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f);
         }
+        if (masked) memcpy((uint8_t*)(gh + o_mask), mask_cur.data(), (size_t)B * NV);          // rides in the same block: one copy
         PL_HIP(hipMemcpyAsync(geo_dev, gh, n_geo * 4, hipMemcpyHostToDevice, st));
         PL_HIP(hipEventRecord(geo_ev[slot], st));
+        return LT_OK;
+    }
+
+    // volumetric plans, first lt_plan_set_view_mask: the geometry block and its pinned ring again, with B*NV mask bytes (whole words) behind the floats.
+    // Everything new is allocated first and the plan is changed only when all of it exists: a failure leaves the plan as it was (unmasked, usable).  The
+    // old block and ring are freed -- no forward has run, nothing is queued on them -- so lt_plan_info reports what the plan holds.
+    int grow_geometry_for_mask() {
+        const size_t n_new = n_geo + ((size_t)cfg.B * cfg.NV + 3) / 4;
+        void* g = nullptr; float* ring[GEO_RING] = {nullptr, nullptr, nullptr, nullptr};
+        auto acquire = [&]() -> int {
+            PL_HIP(hipMalloc(&g, n_new * 4));
+            PL_HIP(hipMemset(g, 0, n_new * 4));
+            for (int i = 0; i < GEO_RING; ++i) { PL_HIP(hipHostMalloc((void**)&ring[i], n_new * 4, hipHostMallocDefault)); memset(ring[i], 0, n_new * 4); }
+            return LT_OK;
+        };
+        const int rc = acquire();
+        if (rc != LT_OK) {
+            if (g) (void)hipFree(g);
+            for (int i = 0; i < GEO_RING; ++i) if (ring[i]) (void)hipHostFree(ring[i]);
+            return rc;
+        }
+        for (size_t i = 0; i < allocs.size(); ++i)
+            if (allocs[i] == (void*)geo_dev) { allocs.erase(allocs.begin() + (long)i); break; }
+        (void)hipFree(geo_dev);
+        bytes_alloc += (n_new - n_geo) * 4;
+        allocs.push_back(g);
+        for (int i = 0; i < GEO_RING; ++i) { if (geo_host[i]) (void)hipHostFree(geo_host[i]); geo_host[i] = ring[i]; }
+        geo_dev = (float*)g; o_mask = n_geo; n_geo = n_new;
+        mask_dev = (const uint8_t*)(geo_dev + o_mask);
+        return LT_OK;
+    }
+    // algebraic plans, first lt_plan_set_view_mask: the mask's device block and its pinned ring
+    int alloc_alg_mask() {
+        const size_t n = (size_t)cfg.B * cfg.NV;
+        for (int i = 0; i < GEO_RING; ++i) if (!amask_host[i]) PL_HIP(hipHostMalloc((void**)&amask_host[i], n, hipHostMallocDefault));          // a retry after a failure keeps what it has
+        void* q; PL_TRY(dev_alloc(n, &q)); amask_dev = (uint8_t*)q; mask_dev = amask_dev;
+        return LT_OK;
+    }
+    // algebraic plans, per forward: a changed mask to the device through the ring (a slot is rewritten only after its last copy has completed)
+    int stage_alg_mask(hipStream_t st) {
+        if (!masked || !amask_dev || !mask_dirty) return LT_OK;
+        const int slot = amask_slot = (amask_slot + 1) % GEO_RING;
+        if (amask_ev[slot]) PL_HIP(hipEventSynchronize(amask_ev[slot]));
+        else PL_HIP(hipEventCreateWithFlags(&amask_ev[slot], hipEventDisableTiming));
+        memcpy(amask_host[slot], mask_cur.data(), mask_cur.size());
+        PL_HIP(hipMemcpyAsync(amask_dev, amask_host[slot], mask_cur.size(), hipMemcpyHostToDevice, st));
+        PL_HIP(hipEventRecord(amask_ev[slot], st));
+        mask_dirty = false;
         return LT_OK;
     }
 
@@ -1194,6 +1261,7 @@ extern "C" int lt_plan_forward_vol(lt_plan* p, const float* images, const double
     bool detour;
     PL_TRY(p->enter(st, detour));
     const int B = p->cfg.B, NV = p->cfg.NV, V = p->cfg.volume_size;
+    p->ran = true;
     PL_TRY(p->stage_geometry(K_host, R_host, t_host, base_points_host, rot_host, st));
     p->cur_images = images; p->out_kp = keypoints_3d; p->out_probs = volumes; p->out_feats = features;
     PL_TRY(p->run(st));
@@ -1222,6 +1290,8 @@ extern "C" int lt_plan_forward_alg(lt_plan* p, const float* images, const float*
     hipStream_t st = (hipStream_t)stream;
     bool detour;
     PL_TRY(p->enter(st, detour));
+    p->ran = true;
+    PL_TRY(p->stage_alg_mask(st));
     p->cur_images = images; p->cur_proj = proj; p->out_kp = keypoints_3d;
     p->out_kp2d = keypoints_2d; p->out_hm = heatmaps; p->out_conf = confidences;
     PL_TRY(p->run(st));
@@ -1286,6 +1356,7 @@ extern "C" int lt_plan_forward_cascade(lt_plan* p, const float* images, const do
     bool detour;
     PL_TRY(p->enter(st, detour));
     const int B = Vp->cfg.B, NV = Vp->cfg.NV, V = Vp->cfg.volume_size;
+    p->ran = true;
     // cameras once: the volumetric stage's block (projections at heatmap resolution, rotations; pos / center are the seam kernel's) and the algebraic
     // stage's projections at image resolution, two H2D copies out of the same ring slot; the slot's event is re-recorded behind the second
     PL_TRY(Vp->stage_geometry(K_host, R_host, t_host, nullptr, rot_host, st, p->cproj_host));
@@ -1304,6 +1375,40 @@ extern "C" int lt_plan_forward_cascade(lt_plan* p, const float* images, const do
     if (coord_volumes) PL_HIP(hipMemcpyAsync(coord_volumes, Vp->coords, (size_t)B * V * V * V * 3 * 4, hipMemcpyDeviceToDevice, st));
     if (vol_confidences) PL_HIP(hipMemcpyAsync(vol_confidences, Vp->volc.p, (size_t)B * NV * 32 * 4, hipMemcpyDeviceToDevice, st));
     PL_TRY(p->leave(st, detour));
+    return LT_OK;
+}
+
+extern "C" int lt_plan_set_view_mask(lt_plan* p, const uint8_t* mask_host) {
+    const char* who = "lt_plan_set_view_mask";
+    LT_REQUIRE(p, LT_ERR_INVALID, "%s: null plan", who);
+    LT_REQUIRE(p->model != LT_MODEL_RANSAC, LT_ERR_UNSUPPORTED, "%s: the plan is %s; RANSAC takes no view mask (its inlier search drops views per joint)", who,
+               plan_kind_name(p));
+    const int B = p->cfg.B, NV = p->cfg.NV;
+    const int need = p->model == 0 ? 1 : 2;          // the DLT of the algebraic model (and of the cascade's first stage) needs two views
+    std::vector<uint8_t> m((size_t)B * NV, 1);
+    for (size_t i = 0; mask_host && i < m.size(); ++i) m[i] = mask_host[i] ? 1 : 0;
+    for (int b = 0; b < B; ++b) {
+        int n = 0;
+        for (int v = 0; v < NV; ++v) n += m[(size_t)b * NV + v];
+        LT_REQUIRE(n >= need, LT_ERR_INVALID, "%s: sample %d has %d valid view%s, at least %d needed (%s)", who, b, n, n == 1 ? "" : "s", need, plan_kind_name(p));
+    }
+    if (!p->masked) {
+        LT_REQUIRE(!p->ran, LT_ERR_INVALID, "%s: the first call must come before the plan's first forward (the recorded and captured launches are chosen "
+                   "there); create a new plan for masked forwards", who);
+        if (p->model == MODEL_CASCADE) {
+            PL_TRY(p->sub_vol->grow_geometry_for_mask());
+            p->sub_alg->mask_dev = p->sub_vol->mask_dev;          // the algebraic stage reads the volumetric stage's block: one copy for both
+            p->sub_vol->masked = p->sub_alg->masked = true;
+        } else if (p->model == 0) {
+            PL_TRY(p->grow_geometry_for_mask());
+        } else {
+            PL_TRY(p->alloc_alg_mask());
+        }
+        p->masked = true;
+    }
+    lt_plan* holder = p->model == MODEL_CASCADE ? p->sub_vol : p;
+    holder->mask_cur = m;
+    holder->mask_dirty = true;
     return LT_OK;
 }
 

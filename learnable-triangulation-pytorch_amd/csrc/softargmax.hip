@@ -386,6 +386,8 @@ __global__ __launch_bounds__(256) void sa2_kernel(const float* __restrict__ hm, 
 // the subtraction cancels), and rotated into the upper-triangular R of A = QR (Givens).  The solve works on R, i.e. on A itself as the
 // reference's torch.svd(A) does: the normal matrix A^T A would square A's condition number (pixel-space rows, far points, confidences
 // down to 1e-5 reach kappa(A) ~ 1e8, where u64 kappa^2 exceeds what fp32 inputs can explain).
+// INVARIANT callers rely on: a row of zeros (confidence 0 with a finite point and matrix) leaves R untouched -- every a[k] == 0.0 takes the `continue` --
+// so a view given weight 0 is, bit for bit, a view that is not there (multiview.triangulate_batch_of_points(view_mask=) masks views this way).
 __device__ __forceinline__ void dlt_accumulate(double (&R)[4][4], const float* __restrict__ P, const float x, const float y, const float c) {
     const double p[2] = {(double)x, (double)y};
     for (int r = 0; r < 2; ++r) {
@@ -487,6 +489,44 @@ __global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __
         dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, x, y, c);
     }
     dlt_solve(R, kp3d + (long long)g * 3);
+}
+
+// The same over the valid views of each sample (mask: (B, NV), non-zero = valid): alg_tail_kernel on the compacted views, step for step -- the
+// k-th VALID view goes into partial k % 4, the rows of the valid views enter R in view order.  A masked view gets confidence 0 and its 2D
+// keypoint is passed through to kp2d only (never into the system, so NaN there stays there); fewer than two valid views: NaN joints.
+__global__ void alg_tail_masked_kernel(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
+                                       float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
+                                       float* __restrict__ kp3d, int B, int NV, int J) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= B * J) return;
+    const int b = g / J, j = g - b * J;
+    const uint8_t* mk = mask + (long long)b * NV;
+    float part[4] = {0.f, 0.f, 0.f, 0.f};
+    int nvalid = 0;
+    for (int v = 0; v < NV; ++v) {
+        if (!mk[v]) continue;
+        const float c = conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f;
+        part[nvalid & 3] = __fadd_rn(part[nvalid & 3], c);
+        ++nvalid;
+    }
+    const float sum = __fadd_rn(__fadd_rn(__fadd_rn(part[0], part[1]), part[2]), part[3]);
+    double R[4][4] = {};  // R of A = QR, grown one valid view at a time
+    for (int v = 0; v < NV; ++v) {
+        const long long i = ((long long)b * NV + v) * J + j;
+        if (!mk[v]) {
+            if (conf_out) conf_out[i] = 0.f;
+            if (kp2d) { kp2d[i * 2] = __fmul_rn(kp_hm[i * 2], sx); kp2d[i * 2 + 1] = __fmul_rn(kp_hm[i * 2 + 1], sy); }
+            continue;
+        }
+        const float c = __fadd_rn(__fdiv_rn(conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f, sum), 1e-5f);
+        const float x = __fmul_rn(kp_hm[i * 2], sx), y = __fmul_rn(kp_hm[i * 2 + 1], sy);
+        if (conf_out) conf_out[i] = c;
+        if (kp2d) { kp2d[i * 2] = x; kp2d[i * 2 + 1] = y; }
+        dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, x, y, c);
+    }
+    float* o = kp3d + (long long)g * 3;
+    if (nvalid < 2) { o[0] = o[1] = o[2] = __int_as_float(0x7fc00000); return; }
+    dlt_solve(R, o);
 }
 
 // ---- backward of the 2D soft-argmax and of the DLT (training of the algebraic model, train.py:189-236) ---------------------------------------
@@ -652,5 +692,18 @@ extern "C" int lt_alg_tail_fwd(const float* keypoints_hm, const float* conf_raw,
     hipLaunchKernelGGL(alg_tail_kernel, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y,
                        keypoints_2d, confidences, keypoints_3d, B, NV, J);
     LT_CHECK_LAUNCH("lt_alg_tail_fwd");
+    return LT_OK;
+}
+
+extern "C" int lt_alg_tail_masked_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                                      const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV,
+                                      int32_t J, void* stream) {
+    LT_REQUIRE(keypoints_hm && proj && keypoints_3d, LT_ERR_INVALID, "lt_alg_tail_masked_fwd: null argument");
+    LT_REQUIRE(view_mask, LT_ERR_INVALID, "lt_alg_tail_masked_fwd: null view_mask");
+    LT_REQUIRE(B >= 1 && NV >= 2 && J >= 1, LT_ERR_INVALID, "lt_alg_tail_masked_fwd: bad shape (B %d, NV %d, J %d)", B, NV, J);
+    LT_REQUIRE(!conf_raw || ld_conf >= J, LT_ERR_INVALID, "lt_alg_tail_masked_fwd: ld_conf %d < J %d", ld_conf, J);
+    hipLaunchKernelGGL(alg_tail_masked_kernel, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x,
+                       scale_y, view_mask, keypoints_2d, confidences, keypoints_3d, B, NV, J);
+    LT_CHECK_LAUNCH("lt_alg_tail_masked_fwd");
     return LT_OK;
 }

@@ -110,6 +110,11 @@ struct UnprojArgs {
     const float* g_pos; const float* g_center; const float* g_rot;
     float g_step; int g_cmu; float* coords_out;
 };
+// the masked entries' kernels get the mask behind the same arguments; the unmasked kernels keep UnprojArgs as their whole argument block
+struct UnprojMaskedArgs : UnprojArgs {
+    const uint8_t* mask;  // (B, NV), non-zero = the view is valid
+};
+template <bool MASKED> using UnprojArgsOf = std::conditional_t<MASKED, UnprojMaskedArgs, UnprojArgs>;
 
 // Brick (bi, bj, bk) of chunk c of a sample.  Raster order (k fastest) makes every 4-voxel i-slab of bricks sweep the WHOLE projected cube in every view:
 // at 8 views the per-slab working set (2.7 MB of feature rows) plus the output stream does not fit the 4 MB L2 of the XCD the sample is pinned to, and the
@@ -183,8 +188,18 @@ __device__ __forceinline__ void sample_view(const T* __restrict__ fmap, const fl
     for (int e = 0; e < CH; ++e) val[e] = t00[e] * nw + t01[e] * ne + t10[e] * sw + t11[e] * se;
 }
 
-template <typename T, int CH, bool SMALL_NV>
-__global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgs a) {
+// does view v take part?  Without a mask: constant true, so the unmasked instantiations compile to what they did before the mask existed
+template <bool MASKED, bool BITS>
+__device__ __forceinline__ bool view_on(unsigned mbits, const uint8_t* __restrict__ mk, int v) {
+    if constexpr (!MASKED) return true;
+    else if constexpr (BITS) return ((mbits >> v) & 1u) != 0;
+    else return mk[v] != 0;
+}
+
+// MASKED: the views {v : mask[b][v]} of sample b alone, visited in increasing v -- exactly the unmasked arithmetic on the compacted views (a
+// masked view is never sampled; no valid view at all: zeros).  The mask of a sample is uniform over its workgroups: SMALL_NV keeps it as bits.
+template <typename T, int CH, bool SMALL_NV, bool MASKED = false>
+__global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKED> a) {
     constexpr bool FAST = sizeof(T) == 2;
     const int tpv = a.C / CH;  // lanes per voxel
     // workgroup -> (sample, chunk); XCD-pinned when B % 8 == 0 (block b runs on XCD b % 8)
@@ -204,6 +219,15 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgs a) {
     T* out = (T*)a.out + (long long)b * nvox * a.C;
     int bi = 0, bj = 0, bk = 0;
     if (a.bricked) brick_of(a, chunk, bi, bj, bk);
+    const uint8_t* mk = nullptr;
+    unsigned mbits = ~0u;
+    if constexpr (MASKED) {
+        mk = a.mask + (long long)b * a.NV;
+        if (SMALL_NV) {
+            mbits = 0;
+            for (int v = 0; v < a.NV; ++v) mbits |= (mk[v] ? 1u : 0u) << v;
+        }
+    }
     const int items = 256 * tpv;
     for (int q = threadIdx.x; q < items; q += 256) {
         const int vb = q / tpv;            // voxel within the chunk, 0..255
@@ -218,38 +242,54 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgs a) {
             float vals[8][CH];
 #pragma unroll
             for (int v = 0; v < 8; ++v)
-                if (v < a.NV) sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, vals[v]);
+                if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, vals[v]);
 #pragma unroll
             for (int e = 0; e < CH; ++e) {
                 float r;
                 if (a.agg == LT_AGG_SOFTMAX) {
-                    float m = vals[0][e];
+                    float m;
+                    if constexpr (MASKED) {          // the first valid view starts the max, as view 0 does below
+                        bool have = false;
+                        m = 0.f;
 #pragma unroll
-                    for (int v = 1; v < 8; ++v) if (v < a.NV) m = fmaxf(m, vals[v][e]);
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) { m = have ? fmaxf(m, vals[v][e]) : vals[v][e]; have = true; }
+                    } else {
+                        m = vals[0][e];
+#pragma unroll
+                        for (int v = 1; v < 8; ++v) if (v < a.NV) m = fmaxf(m, vals[v][e]);
+                    }
                     // sum_v x_v softmax_v(x) = (sum_v x_v e_v) / (sum_v e_v): one division per channel
                     float s = 0.f, tt = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV) { const float ex = exp_<FAST>(vals[v][e] - m); s += ex; tt += vals[v][e] * ex; }
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) { const float ex = exp_<FAST>(vals[v][e] - m); s += ex; tt += vals[v][e] * ex; }
                     r = div_<FAST>(tt, s);
                 } else if (a.agg == LT_AGG_MAX) {
-                    r = vals[0][e];
+                    if constexpr (MASKED) {
+                        bool have = false;
+                        r = 0.f;
 #pragma unroll
-                    for (int v = 1; v < 8; ++v) if (v < a.NV) r = fmaxf(r, vals[v][e]);
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) { r = have ? fmaxf(r, vals[v][e]) : vals[v][e]; have = true; }
+                    } else {
+                        r = vals[0][e];
+#pragma unroll
+                        for (int v = 1; v < 8; ++v) if (v < a.NV) r = fmaxf(r, vals[v][e]);
+                    }
                 } else if (a.agg == LT_AGG_CONF || a.agg == LT_AGG_CONF_NORM) {
                     float cs = 1.f;
                     if (a.agg == LT_AGG_CONF_NORM) {
                         cs = 0.f;
 #pragma unroll
-                        for (int v = 0; v < 8; ++v) if (v < a.NV) cs += a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) cs += a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
                     }
                     r = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV) r += vals[v][e] * __fdiv_rn(a.conf[((long long)b * a.NV + v) * a.C + c0 + e], cs);
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) r += vals[v][e] * __fdiv_rn(a.conf[((long long)b * a.NV + v) * a.C + c0 + e], cs);
                 } else {
                     r = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV) r += vals[v][e];
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) r += vals[v][e];
                 }
+                if constexpr (MASKED) if (mbits == 0) r = 0.f;   // no valid view
                 res[e] = r;
             }
         } else {  // any NV: recompute the samples instead of storing them (softmax needs the max first)
@@ -259,17 +299,22 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgs a) {
                 m[e] = -INFINITY; s[e] = 0.f; acc[e] = 0.f; cs[e] = 1.f;
                 if (a.agg == LT_AGG_CONF_NORM) {
                     cs[e] = 0.f;
-                    for (int v = 0; v < a.NV; ++v) cs[e] += a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
+                    for (int v = 0; v < a.NV; ++v) if (view_on<MASKED, SMALL_NV>(mbits, mk, v)) cs[e] += a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
                 }
             }
+            bool any = !MASKED;
+            if constexpr (MASKED)
+                for (int v = 0; v < a.NV; ++v) any = any || view_on<MASKED, SMALL_NV>(mbits, mk, v);
             if (a.agg == LT_AGG_SOFTMAX || a.agg == LT_AGG_MAX)
                 for (int v = 0; v < a.NV; ++v) {
+                    if (!view_on<MASKED, SMALL_NV>(mbits, mk, v)) continue;
                     sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, val);
 #pragma unroll
                     for (int e = 0; e < CH; ++e) m[e] = fmaxf(m[e], val[e]);
                 }
             if (a.agg != LT_AGG_MAX)
                 for (int v = 0; v < a.NV; ++v) {
+                    if (!view_on<MASKED, SMALL_NV>(mbits, mk, v)) continue;
                     sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, val);
 #pragma unroll
                     for (int e = 0; e < CH; ++e) {
@@ -281,7 +326,7 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgs a) {
                 }
 #pragma unroll
             for (int e = 0; e < CH; ++e)
-                res[e] = a.agg == LT_AGG_MAX ? m[e] : (a.agg == LT_AGG_SOFTMAX ? __fdiv_rn(acc[e], s[e]) : acc[e]);
+                res[e] = !any ? 0.f : (a.agg == LT_AGG_MAX ? m[e] : (a.agg == LT_AGG_SOFTMAX ? __fdiv_rn(acc[e], s[e]) : acc[e]));
         }
         ChVec<T, CH>::st(out + vox * a.C + c0, res);
     }
@@ -315,8 +360,14 @@ __device__ __forceinline__ f32x2_t pk_fma(f32x2_t a, f32x2_t b, f32x2_t c) { ret
 // (round 6, measured and not kept: the 8-view instantiation takes 152 VGPRs = 3 waves per SIMD; capped at 128 = 4 waves with __launch_bounds__(256, 4) --
 //  4 registers of loop invariants in scratch -- it ran 3.72-3.75 ms against 3.62-3.67 ms at BASELINE config 4, and with MORE memory traffic (3.09 vs 2.80 GB):
 //  the kernel is bound by VALU issue + the gather path together (valu_issue_frac 0.44-0.45), and a fourth wave adds neither.)
-template <int NVL, bool GRID>
-__global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgs a) {
+// MASKED: a sample's mask is the same in every lane of its workgroups, so it is read once, into a scalar register as bits, and every view is one
+// scalar branch: a masked view issues no loads, no blend and no exp2, and leaves its val[] registers untouched.  The softmax walks the views
+// outermost there (one branch per view instead of one per view and channel pair); per channel the operations and their order are those of
+// the unmasked kernel on the valid views, so an all-ones mask gives its bits (the max starts from -inf where the unmasked kernel starts from view 0:
+// the same value unless EVERY valid view's sample is NaN, and then both write NaN).  (The lanes still project into their masked views: which
+// lane owns a view varies over the quad, and the 30 instructions are not worth a divergent branch.)
+template <int NVL, bool GRID, bool MASKED = false>
+__global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MASKED> a) {
     typedef bf16_t T;
     constexpr int C = 32, NV = 4 * NVL;
     int b, chunk;
@@ -350,6 +401,13 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgs a) {
         for (int i = 0; i < 9; ++i) gR[i] = a.g_rot[9 * b + i];
     }
     const float inv_h = __builtin_amdgcn_rcpf((float)h), inv_w = __builtin_amdgcn_rcpf((float)w);
+    unsigned mbits = (1u << NV) - 1u;
+    if constexpr (MASKED) {
+        mbits = 0;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) mbits |= (a.mask[(long long)b * NV + v] ? 1u : 0u) << v;
+        mbits = __builtin_amdgcn_readfirstlane(mbits);
+    }
 
 #pragma unroll 1
     for (int it = 0; it < 4; ++it) {
@@ -399,6 +457,7 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgs a) {
         f32x2_t val[NV][4];                               // [view][channel pair] of this lane's 8 channels
         auto view = [&](auto vc) {
             constexpr int V = decltype(vc)::value, Q = V & 3, S = V >> 2;
+            if constexpr (MASKED) if (!((mbits >> V) & 1u)) return;
             const int p00 = quad_bcast_i<Q>(o00[S]), p01 = quad_bcast_i<Q>(o01[S]), p10 = quad_bcast_i<Q>(o10[S]), p11 = quad_bcast_i<Q>(o11[S]);
             const float w00 = quad_bcast_f<Q>(k00[S]), w01 = quad_bcast_f<Q>(k01[S]), w10 = quad_bcast_f<Q>(k10[S]), w11 = quad_bcast_f<Q>(k11[S]);
             const uint4 t00 = *(const uint4*)(feats + p00 + qv * 8), t01 = *(const uint4*)(feats + p01 + qv * 8);
@@ -419,6 +478,35 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgs a) {
 
         // ---- softmax over the views per channel: sum_v x_v softmax_v(x) = (sum_v x_v e_v) / (sum_v e_v) ----
         unsigned o[4];
+        if constexpr (MASKED) {
+            if (mbits == 0) {                             // no valid view: zeros
+                *(uint4*)(out + vox * C + qv * 8) = make_uint4(0u, 0u, 0u, 0u);
+                continue;
+            }
+            const f32x2_t L2E = {1.4426950408889634f, 1.4426950408889634f};
+            f32x2_t m[4], s[4], tt[4];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) { m[d] = f32x2_t{-INFINITY, -INFINITY}; s[d] = f32x2_t{0.f, 0.f}; tt[d] = f32x2_t{0.f, 0.f}; }
+            static_for_views<0, NV>([&](auto vc) {       // fmaxf(-inf, x) = x: the first valid view starts the max, as view 0 does below
+                constexpr int V = decltype(vc)::value;
+                if (!((mbits >> V) & 1u)) return;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) { m[d][0] = fmaxf(m[d][0], val[V][d][0]); m[d][1] = fmaxf(m[d][1], val[V][d][1]); }
+            });
+            static_for_views<0, NV>([&](auto vc) {
+                constexpr int V = decltype(vc)::value;
+                if (!((mbits >> V) & 1u)) return;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    const f32x2_t dl = pk_fma(val[V][d], L2E, -(m[d] * L2E));   // (x - m) log2(e)
+                    const f32x2_t ex = {__builtin_amdgcn_exp2f(dl[0]), __builtin_amdgcn_exp2f(dl[1])};
+                    s[d] += ex;
+                    tt[d] = pk_fma(val[V][d], ex, tt[d]);
+                }
+            });
+#pragma unroll
+            for (int d = 0; d < 4; ++d) o[d] = pack_bf16x2(tt[d][0] * __builtin_amdgcn_rcpf(s[d][0]), tt[d][1] * __builtin_amdgcn_rcpf(s[d][1]));
+        } else {
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             f32x2_t m = val[0][d];
@@ -435,13 +523,21 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgs a) {
             }
             o[d] = pack_bf16x2(tt[0] * __builtin_amdgcn_rcpf(s[0]), tt[1] * __builtin_amdgcn_rcpf(s[1]));
         }
+        }
         *(uint4*)(out + vox * C + qv * 8) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
 
 template <typename T, int CH>
-int launch_unproject(const UnprojArgs& a, hipStream_t st) {
+int launch_unproject(const UnprojMaskedArgs& m, hipStream_t st) {
+    const UnprojArgs& a = m;
     const unsigned grid = (unsigned)((long long)a.B * a.chunks);
+    if (m.mask) {
+        if (a.NV <= 8) hipLaunchKernelGGL((unproject_kernel<T, CH, true, true>), dim3(grid), dim3(256), 0, st, m);
+        else hipLaunchKernelGGL((unproject_kernel<T, CH, false, true>), dim3(grid), dim3(256), 0, st, m);
+        LT_CHECK_LAUNCH("lt_unproject_masked_fwd");
+        return LT_OK;
+    }
     if (a.NV <= 8) hipLaunchKernelGGL((unproject_kernel<T, CH, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((unproject_kernel<T, CH, false>), dim3(grid), dim3(256), 0, st, a);
     LT_CHECK_LAUNCH("lt_unproject_fwd");
@@ -462,8 +558,9 @@ extern "C" int lt_coord_volumes(const float* pos, const float* center, const flo
 }
 
 namespace {
-// fills the launch geometry and picks the kernel; a.coords (read) or the a.g_* grid description must be set by the caller
-int unproject_dispatch(UnprojArgs& a, int dtype, bool grid, hipStream_t st) {
+// fills the launch geometry and picks the kernel; a.coords (read) or the a.g_* grid description must be set by the caller.  a.mask set: the masked
+// instantiation of the SAME kernel the unmasked call takes (a masked plan never leaves the quad kernel for the generic one).
+int unproject_dispatch(UnprojMaskedArgs& a, int dtype, bool grid, hipStream_t st) {
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
     a.bricked = (a.v0 % 4 == 0 && a.v1 % 4 == 0 && a.v2 % 16 == 0) ? 1 : 0;
     a.blocked = (a.bricked && a.v0 % 32 == 0 && a.v1 % 32 == 0 && a.v2 % 32 == 0 && !env_on("LT_UNPROJ_RASTER")) ? 1 : 0;          // LT_UNPROJ_RASTER=1: the old order (A/B)
@@ -475,13 +572,25 @@ int unproject_dispatch(UnprojArgs& a, int dtype, bool grid, hipStream_t st) {
     const bool no_q4 = env_on("LT_UNPROJ_NO_Q4");       // A/B, read per call
     const bool quad = dtype == LT_BF16 && a.C == 32 && (a.NV == 4 || a.NV == 8) && a.bricked && a.agg == LT_AGG_SOFTMAX && !no_q4 &&
                       (long long)a.NV * a.h * a.w * a.C < (1ll << 30);
-    if (quad) {
+    if (quad && a.mask) {
         if (a.NV == 4) {
-            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<1, true>), dim3(nblk), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((unproject_qn_kernel<1, false>), dim3(nblk), dim3(256), 0, st, a);
+            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<1, true, true>), dim3(nblk), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((unproject_qn_kernel<1, false, true>), dim3(nblk), dim3(256), 0, st, a);
         } else {
-            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<2, true>), dim3(nblk), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((unproject_qn_kernel<2, false>), dim3(nblk), dim3(256), 0, st, a);
+            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<2, true, true>), dim3(nblk), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((unproject_qn_kernel<2, false, true>), dim3(nblk), dim3(256), 0, st, a);
+        }
+        LT_CHECK_LAUNCH("lt_unproject_masked_fwd(quad)");
+        return LT_OK;
+    }
+    if (quad) {
+        const UnprojArgs& u = a;
+        if (a.NV == 4) {
+            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<1, true>), dim3(nblk), dim3(256), 0, st, u);
+            else hipLaunchKernelGGL((unproject_qn_kernel<1, false>), dim3(nblk), dim3(256), 0, st, u);
+        } else {
+            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<2, true>), dim3(nblk), dim3(256), 0, st, u);
+            else hipLaunchKernelGGL((unproject_qn_kernel<2, false>), dim3(nblk), dim3(256), 0, st, u);
         }
         LT_CHECK_LAUNCH("lt_unproject_fwd(quad)");
         return LT_OK;
@@ -512,8 +621,24 @@ extern "C" int lt_unproject_fwd(int32_t dtype, const void* feats, const float* p
     LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "lt_unproject_fwd: LT_AGG_CONF* needs confidences");
     LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_INVALID, "lt_unproject_fwd: bad shape");
     LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_fwd: feature maps too large");
-    UnprojArgs a = {};
+    UnprojMaskedArgs a = {};
     a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out;
+    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = v0; a.v1 = v1; a.v2 = v2; a.agg = agg;
+    return unproject_dispatch(a, dtype, false, (hipStream_t)stream);
+}
+
+extern "C" int lt_unproject_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                                       void* out, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2, int32_t agg,
+                                       void* stream) {
+    LT_REQUIRE(feats && proj && coords && out, LT_ERR_INVALID, "lt_unproject_masked_fwd: null argument");
+    LT_REQUIRE(view_mask, LT_ERR_INVALID, "lt_unproject_masked_fwd: null view_mask");
+    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "lt_unproject_masked_fwd: bad dtype %d", dtype);
+    LT_REQUIRE(agg >= LT_AGG_SUM && agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "lt_unproject_masked_fwd: unknown aggregation %d", agg);
+    LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "lt_unproject_masked_fwd: LT_AGG_CONF* needs confidences");
+    LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_INVALID, "lt_unproject_masked_fwd: bad shape");
+    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_masked_fwd: feature maps too large");
+    UnprojMaskedArgs a = {};
+    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out; a.mask = view_mask;
     a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = v0; a.v1 = v1; a.v2 = v2; a.agg = agg;
     return unproject_dispatch(a, dtype, false, (hipStream_t)stream);
 }
@@ -527,8 +652,25 @@ extern "C" int lt_unproject_grid_fwd(int32_t dtype, const void* feats, const flo
     LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "lt_unproject_grid_fwd: LT_AGG_CONF* needs confidences");
     LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && V >= 2, LT_ERR_INVALID, "lt_unproject_grid_fwd: bad shape");
     LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_grid_fwd: feature maps too large");
-    UnprojArgs a = {};
+    UnprojMaskedArgs a = {};
     a.feats = feats; a.proj = proj; a.coords = nullptr; a.conf = conf; a.out = out;
+    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = V; a.v1 = V; a.v2 = V; a.agg = agg;
+    a.g_pos = pos; a.g_center = center; a.g_rot = rot; a.g_step = step; a.g_cmu = cmu_transfer; a.coords_out = coords_out;
+    return unproject_dispatch(a, dtype, true, (hipStream_t)stream);
+}
+
+extern "C" int lt_unproject_grid_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
+                                            float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask, void* out,
+                                            int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream) {
+    LT_REQUIRE(feats && proj && pos && center && rot && coords_out && out, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: null argument");
+    LT_REQUIRE(view_mask, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: null view_mask");
+    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: bad dtype %d", dtype);
+    LT_REQUIRE(agg >= LT_AGG_SUM && agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: unknown aggregation %d", agg);
+    LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: LT_AGG_CONF* needs confidences");
+    LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && V >= 2, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: bad shape");
+    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_grid_masked_fwd: feature maps too large");
+    UnprojMaskedArgs a = {};
+    a.feats = feats; a.proj = proj; a.coords = nullptr; a.conf = conf; a.out = out; a.mask = view_mask;
     a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = V; a.v1 = V; a.v2 = V; a.agg = agg;
     a.g_pos = pos; a.g_center = center; a.g_rot = rot; a.g_step = step; a.g_cmu = cmu_transfer; a.coords_out = coords_out;
     return unproject_dispatch(a, dtype, true, (hipStream_t)stream);

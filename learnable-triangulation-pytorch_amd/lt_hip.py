@@ -129,6 +129,7 @@ SIGNATURES = {
     "lt_plan_forward_alg": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_create_cascade": (C.c_int, [C.POINTER(CascadePlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
     "lt_plan_forward_cascade": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "lt_plan_set_view_mask": (C.c_int, [vp, vp]),
     "lt_plan_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),
     "lt_plan_destroy": (None, [vp]),
     "lt_last_error": (C.c_char_p, []),
@@ -166,12 +167,15 @@ SIGNATURES = {
     "lt_rotate_points": (C.c_int, [vp, vp, vp, i64, vp]),
     "lt_unproject_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_unproject_grid_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "lt_unproject_masked_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "lt_unproject_grid_masked_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_cuboid_from_keypoints": (C.c_int, [vp, i32, i32, i32, C.c_double, vp, vp, vp]),
     "lt_softargmax3d_workspace": (C.c_size_t, [i32, i32, i64]),
     "lt_softargmax3d_fwd": (C.c_int, [vp, vp, f32, i32, i32, i32, vp, vp, i32, i32, i64, vp, vp]),
     "lt_softargmax2d_fwd": (C.c_int, [vp, f32, i32, vp, vp, i32, i32, i32, vp]),
     "lt_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_alg_tail_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
+    "lt_alg_tail_masked_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_heatmap_argmax_nchw_f32": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "lt_triangulate_ransac": (C.c_int, [vp, vp, vp, i32, C.c_double, i32, vp, vp, i32, i32, i32, vp]),
     "lt_crop_resize_u8": (C.c_int, [vp, i64, vp, vp, i32, i32, i32, vp, vp, vp]),

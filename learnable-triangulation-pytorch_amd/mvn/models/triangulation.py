@@ -60,6 +60,15 @@ def _sync_buffers_before_eval(model):
         model.__dict__["_buffers_stale"] = False
 
 
+def _batch_view_mask(batch, B, NV, min_valid, who):
+    """``batch["view_mask"]`` as a checked host (B, NV) uint8 array, or None when the batch has none.  ValueError for another shape or a sample with
+    fewer than ``min_valid`` valid views -- raised before anything is launched."""
+    vm = batch.get("view_mask") if isinstance(batch, dict) else None
+    if vm is None:
+        return None
+    return op.view_mask_host(vm, B, NV, min_valid=min_valid, what="%s: batch['view_mask']" % who)
+
+
 class _VolTrainPlan:
     """The training step of VolumetricTriangulationNet for one input shape, recorded once and replayed (lt_train.TrainTape): the first
     forward / backward run the layers while recording them; later steps re-launch the recorded closures over the same buffers.  What
@@ -394,7 +403,10 @@ class VolumetricTriangulationNet(_PlannedNet):
                                   "bfloat16": torch.bfloat16}[str(m.compute_dtype)]
 
     # ---------------------------------------------------------------------------------------
-    def _build_plan(self, B, NV, Hh, W, device, dry_run=False):
+    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False):
+        """masked: the plan of forwards with ``batch["view_mask"]`` -- the same launch list with lt_unproject_grid_masked_fwd in the gather's place; the
+        (B, NV) uint8 mask rides at the end of the geometry block (same pinned ring, same copy), outside the captured graph's baked pointers like the
+        rest of the block, so a new mask on a captured plan is just another forward."""
         V, J = self.volume_size, self.num_joints
         b, x_in = self._open_plan(B * NV, Hh, W, device, dry_run)
         lib = b.lib
@@ -410,7 +422,8 @@ class VolumetricTriangulationNet(_PlannedNet):
         feats.pooled = False
         h, w = feats.shape[2], feats.shape[3]
         # geometry block (fp32, one H2D copy per forward): proj B*NV*12 | pos B*3 | center B*3 | rot B*9
-        n_geo = B * NV * 12 + B * 15
+        o_mask = B * NV * 12 + B * 15          # masked plans: B*NV mask bytes behind the floats (whole words)
+        n_geo = o_mask + ((B * NV + 3) // 4 if masked else 0)
         geo = torch.zeros(n_geo, dtype=torch.float32, device=device)
         # pinned staging RING: forward N+1 fills the next slot while forward N's copy may still be queued; a slot is rewritten only
         # after the event recorded behind its last copy has completed (forward never blocks on the GPU otherwise)
@@ -432,12 +445,18 @@ class VolumetricTriangulationNet(_PlannedNet):
         # ONE launch: the voxel centres are computed in registers from (position, centre, rotation, step) and written to the returned
         # coordinate tensor on the way (reference :298-339 + op.py:99-166); configurations without a fused kernel run
         # lt_coord_volumes + the generic gather inside the same call
-        b.custom(lambda st: H.check(lib.lt_unproject_grid_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                              coords.data_ptr(), H.ptr(conf), vol.t.data_ptr(), B, NV, 32, h, w, V, agg, st),
-                                    "lt_unproject_grid_fwd"),
+        if masked:
+            unproject = lambda st: H.check(lib.lt_unproject_grid_masked_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
+                                                                            coords.data_ptr(), H.ptr(conf), gp + 4 * o_mask, vol.t.data_ptr(), B, NV, 32, h, w, V,
+                                                                            agg, st), "lt_unproject_grid_masked_fwd")
+        else:
+            unproject = lambda st: H.check(lib.lt_unproject_grid_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
+                                                                     coords.data_ptr(), H.ptr(conf), vol.t.data_ptr(), B, NV, 32, h, w, V, agg, st),
+                                           "lt_unproject_grid_fwd")
+        b.custom(unproject,
                  "unproject", nbytes=(B * NV * h * w * 32 + B * V ** 3 * 32) * esz + B * V ** 3 * 12,   # feats once + volume once + the returned coords
                  info={"feats": feats, "geo": geo, "coords": coords, "conf": conf, "vol": vol, "agg": self.volume_aggregation_method, "NV": NV,
-                       "offs": (o_pos, o_cen, o_rot), "step": step, "cmu": cmu})
+                       "offs": (o_pos, o_cen, o_rot), "step": step, "cmu": cmu, "masked": masked})
         logits = self.volume_net.record(b, vol)
         kp = torch.empty(B, J, 3, dtype=torch.float32, device=device)
         probs = torch.empty(B, J, V, V, V, dtype=torch.float32, device=device)
@@ -465,7 +484,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         return {"plan": plan, "x_in": x_in, "image_cell": image_cell, "feats": feats, "geo": geo, "geo_host": geo_host, "geo_ring": geo_ring,
                 "geo_events": [None] * len(geo_ring), "geo_slot": 0, "coords": coords, "kp": kp,
                 "probs": probs, "conf": conf, "logits": logits, "vol": vol, "hw": (h, w), "offs": (o_pos, o_cen, o_rot),
-                "captured": False}
+                "captured": False, "masked": masked, "o_mask": o_mask}
 
     def _host_cameras(self, batch, B, image_shape, P):
         """The camera half of the host geometry (reference :272-279, :318-328): fills the projections and rotations of the next slot of the plan's
@@ -486,7 +505,9 @@ class VolumetricTriangulationNet(_PlannedNet):
             ev.synchronize()         # the copy that last read this slot (GEO_RING forwards ago) has completed
         gh = P["geo_host"] = P["geo_ring"][slot]
         gh[:o_pos] = torch.from_numpy(proj.astype(np.float32).reshape(-1))
-        gh[o_rot:] = torch.from_numpy(rot.astype(np.float32).reshape(-1))
+        gh[o_rot:o_rot + 9 * B] = torch.from_numpy(rot.astype(np.float32).reshape(-1))
+        if P.get("masked"):
+            gh.view(torch.uint8)[4 * P["o_mask"]:4 * P["o_mask"] + B * len(batch["cameras"])] = torch.from_numpy(batch["view_mask"].reshape(-1))
         return gh
 
     def _host_geometry(self, batch, B, image_shape, P):
@@ -523,11 +544,16 @@ class VolumetricTriangulationNet(_PlannedNet):
         Asynchronous like the reference's CUDA forward: nothing here waits for the GPU (results are ordered on the current
         stream).  One plan per batch shape whatever its size: BASELINE config 4 at 32 samples (2^31 elements per 32-channel volume) is ONE plan and one
         captured graph -- the convolution entry points walk such tensors in sample chunks (``max_samples_per_launch``)."""
+        B, NV = images.shape[:2]
+        vm = _batch_view_mask(batch, B, NV, 1, "VolumetricTriangulationNet")          # optional (B, NV) validity mask: refused before any launch
+        if vm is not None:
+            if _bn_in_train_mode(self):
+                raise NotImplementedError("VolumetricTriangulationNet: batch['view_mask'] is inference only (there is no masked backward); call eval() first")
+            batch = dict(batch, view_mask=vm)
         H.require_gpu(images, "images")
         if _bn_in_train_mode(self):          # any BatchNorm module in train(): the training step (modules left in eval() keep frozen statistics)
             return self._forward_train(images, batch)
         _sync_buffers_before_eval(self)
-        B, NV = images.shape[:2]
         cap = self.max_samples_per_launch(NV, images.shape[3], images.shape[4])
         if B <= cap:
             with torch.cuda.device(images.device):
@@ -611,13 +637,19 @@ class VolumetricTriangulationNet(_PlannedNet):
             for k in ("keypoints_3d", "pred_keypoints_3d"):
                 if k in batch:
                     batch[k] = batch[k][lo:hi]
+            if batch.get("view_mask") is not None:
+                batch["view_mask"] = np.ascontiguousarray(batch["view_mask"][lo:hi])
         B = hi - lo
-        # everything a plan bakes in besides the weights (those: the fingerprint inside _plan_for)
-        key = (B, NV, Hh, W, self.compute_dtype, device, self.use_graph, self.volume_size, float(self.cuboid_side),
-               float(self.volume_multiplier), bool(self.volume_softmax), self.volume_aggregation_method,
-               bool(self.transfer_cmu_to_human36m), self.tile_override, self.num_joints)
-        P = self._plan_for(key, lambda: self._build_plan(B, NV, Hh, W, device))
+        masked = batch.get("view_mask") is not None
+        # the key: everything a plan bakes in besides the weights (those: the fingerprint inside _plan_for)
+        P = self._plan_for(self._plan_key(B, NV, Hh, W, device, masked), lambda: self._build_plan(B, NV, Hh, W, device, masked=masked))
         return images, batch, B, P
+
+    def _plan_key(self, B, NV, Hh, W, device, masked=False):
+        """Everything a plan bakes in besides the weights; ``masked``: the plan records the masked gather (forwards without a mask keep their plan)."""
+        return (B, NV, Hh, W, self.compute_dtype, device, self.use_graph, self.volume_size, float(self.cuboid_side),
+                float(self.volume_multiplier), bool(self.volume_softmax), self.volume_aggregation_method,
+                bool(self.transfer_cmu_to_human36m), self.tile_override, self.num_joints, masked)
 
     @staticmethod
     def _plan_images(images, B, NV):
@@ -633,8 +665,9 @@ class VolumetricTriangulationNet(_PlannedNet):
         ev = P["geo_events"][P["geo_slot"]] = P["geo_events"][P["geo_slot"]] or torch.cuda.Event()
         ev.record(side)
 
-    def _replay(self, P, x, B, NV, side, cur):
-        """On the side stream, behind the geometry: the plan's launches.  Returns (kp, feats, probs, conf, coords, base_points)."""
+    def _replay(self, P, x, B, NV, side, cur, view_mask=None):
+        """On the side stream, behind the geometry: the plan's launches.  Returns (kp, feats, probs, conf, coords, base_points).  view_mask (masked
+        plans): the host mask of this forward, for the returned conf_norm confidences."""
         device = x.device
         h, w = P["hw"]
         st = side.cuda_stream
@@ -663,6 +696,9 @@ class VolumetricTriangulationNet(_PlannedNet):
             coords = coords.clone()
             conf = None if conf is None else conf.clone()
         if conf is not None and self.volume_aggregation_method == "conf_norm":
+            if view_mask is not None:          # normalised over the valid views, a masked view's entries 0 (an all-ones mask: the same bits)
+                on = torch.from_numpy(view_mask).to(device, non_blocking=True).bool()[:, :, None]
+                conf = torch.where(on, conf, torch.zeros((), dtype=conf.dtype, device=device))
             conf = conf / conf.sum(dim=1, keepdim=True)   # the RETURNED confidences are the normalised ones (reference :268-269, :355)
         for t in (kp, probs, coords, feats, base_points, conf):
             if t is not None:
@@ -682,7 +718,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         x = self._plan_images(images, B, NV)
         with torch.cuda.stream(side):
             self._copy_geometry(P, side)
-            kp, feats, probs, conf, coords, base_points = self._replay(P, x, B, NV, side, cur)
+            kp, feats, probs, conf, coords, base_points = self._replay(P, x, B, NV, side, cur, batch.get("view_mask"))
         x.record_stream(side)
         cur.wait_stream(side)
         cuboids = [volumetric.Cuboid3D(position[i], sides) for i in range(B)]
@@ -700,8 +736,10 @@ class AlgebraicTriangulationNet(_PlannedNet):
         self.heatmap_softmax = m.heatmap_softmax
         self.heatmap_multiplier = m.heatmap_multiplier
 
-    def _build_plan(self, B, NV, Hh, W, device):
-        b, x_in = self._open_plan(B * NV, Hh, W, device)
+    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False):
+        """masked: the plan of forwards with ``batch["view_mask"]`` -- the same launches, plus the mask's device block and its pinned staging ring (the
+        tail after the plan is then lt_alg_tail_masked_fwd)."""
+        b, x_in = self._open_plan(B * NV, Hh, W, device, dry_run)
         lib = b.lib
         hm, feats, algc, _ = self.backbone.record(b, x_in, want_heatmaps=True)
         b.release(feats)
@@ -716,22 +754,32 @@ class AlgebraicTriangulationNet(_PlannedNet):
                                     "lt_softargmax2d_fwd"))
         plan = b.finish()
         plan.keep += [hm_nchw, kp2d, probs]
-        return {"plan": plan, "x_in": x_in, "kp2d": kp2d, "probs": probs, "algc": algc, "hw": (h, w), "J": J}
+        P = {"plan": plan, "x_in": x_in, "kp2d": kp2d, "probs": probs, "algc": algc, "hw": (h, w), "J": J, "masked": masked}
+        if masked:
+            ring = [torch.zeros(N, dtype=torch.uint8) for _ in range(1 if dry_run else GEO_RING)]
+            P.update({"mask": torch.zeros(N, dtype=torch.uint8, device=device), "mask_ring": ring if dry_run else [r.pin_memory() for r in ring],
+                      "mask_events": [None] * len(ring), "mask_slot": 0})
+        return P
 
     def forward(self, images, proj_matricies, batch):
         """Returns (keypoints_3d (B,J,3), keypoints_2d (B,NV,J,2) in image pixels, heatmaps (B,NV,J,h,w) after
         softmax, alg_confidences (B,NV,J)) -- reference :149-200."""
+        device = images.device
+        B, NV = images.shape[:2]
+        Hh, W = images.shape[3:]
+        vm = _batch_view_mask(batch, B, NV, 2, "AlgebraicTriangulationNet")          # optional (B, NV) validity mask: refused before any launch
+        if vm is not None and _bn_in_train_mode(self):
+            raise NotImplementedError("AlgebraicTriangulationNet: batch['view_mask'] is inference only (there is no masked backward); call eval() first")
         H.require_gpu(images, "images")
         if _bn_in_train_mode(self):
             return self._forward_train(images, proj_matricies)
         _sync_buffers_before_eval(self)
-        device = images.device
-        B, NV = images.shape[:2]
-        Hh, W = images.shape[3:]
-        key = (B, NV, Hh, W, self.compute_dtype, device, float(self.heatmap_multiplier), bool(self.heatmap_softmax), self.tile_override)
         with torch.cuda.device(device):
-            P = self._plan_for(key, lambda: self._build_plan(B, NV, Hh, W, device))
-            return self._run(P, images, proj_matricies, B, NV, Hh, W, device)
+            P = self._plan_for(self._plan_key(B, NV, Hh, W, device, vm is not None), lambda: self._build_plan(B, NV, Hh, W, device, masked=vm is not None))
+            return self._run(P, images, proj_matricies, B, NV, Hh, W, device, vm)
+
+    def _plan_key(self, B, NV, Hh, W, device, masked=False):
+        return (B, NV, Hh, W, self.compute_dtype, device, float(self.heatmap_multiplier), bool(self.heatmap_softmax), self.tile_override, masked)
 
     def _forward_train(self, images, proj_matricies):
         """Training mode (round 3; the reference's loop for model_type "alg", train.py:189-236): the backbone -- heatmap head and, with
@@ -786,9 +834,18 @@ class AlgebraicTriangulationNet(_PlannedNet):
         kp3d = multiview.triangulate_batch_of_points(proj_matricies.to(device), kp2d, confidences_batch=conf)
         return kp3d, kp2d, heatmaps.reshape(B, NV, J, h, w), conf
 
-    def _run(self, P, images, proj_matricies, B, NV, Hh, W, device):
+    def _run(self, P, images, proj_matricies, B, NV, Hh, W, device, view_mask=None):
         h, w = P["hw"]; J = P["J"]
         st = torch.cuda.current_stream(device).cuda_stream
+        if view_mask is not None:          # the mask to its device block through the plan's pinned ring (a slot is rewritten only after its last copy has completed)
+            slot = P["mask_slot"] = (P["mask_slot"] + 1) % len(P["mask_ring"])
+            ev = P["mask_events"][slot]
+            if ev is not None:
+                ev.synchronize()
+            P["mask_ring"][slot].copy_(torch.from_numpy(view_mask.reshape(-1)))
+            P["mask"].copy_(P["mask_ring"][slot], non_blocking=True)
+            ev = P["mask_events"][slot] = ev or torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(device))
         E.stage_images(images.reshape(B * NV, 3, Hh, W).float().contiguous(), P["x_in"], st)
         P["plan"].run_eager(st)
         heatmaps = P["probs"].reshape(B, NV, J, h, w).clone()
@@ -799,6 +856,11 @@ class AlgebraicTriangulationNet(_PlannedNet):
         kp2d = torch.empty(B, NV, J, 2, dtype=torch.float32, device=device)
         conf = torch.empty(B, NV, J, dtype=torch.float32, device=device)
         kp3d = torch.empty(B, J, 3, dtype=torch.float32, device=device)
+        if view_mask is not None:          # the same tail over the valid views of each sample; masked confidences are 0
+            H.check(H.lib().lt_alg_tail_masked_fwd(P["kp2d"].data_ptr(), None if algc is None else algc.t.data_ptr(), J if algc is None else algc.t.shape[-1],
+                                                   proj.data_ptr(), W / w, Hh / h, P["mask"].data_ptr(), kp2d.data_ptr(), conf.data_ptr(), kp3d.data_ptr(),
+                                                   B, NV, J, st), "lt_alg_tail_masked_fwd")
+            return kp3d, kp2d, heatmaps, conf
         H.check(H.lib().lt_alg_tail_fwd(P["kp2d"].data_ptr(), None if algc is None else algc.t.data_ptr(), J if algc is None else algc.t.shape[-1],
                                         proj.data_ptr(), W / w, Hh / h, kp2d.data_ptr(), conf.data_ptr(), kp3d.data_ptr(), B, NV, J, st),
                 "lt_alg_tail_fwd")
@@ -842,6 +904,8 @@ class RANSACTriangulationNet(_PlannedNet):
     def forward(self, images, proj_matricies, batch):
         """Returns (keypoints_3d (B,J,3) fp32, keypoints_2d (B,NV,J,2) int64 image pixels, raw heatmaps (B,NV,J,h,w), confidences
         (B,NV,J) zeros) -- reference :27-73."""
+        if isinstance(batch, dict) and batch.get("view_mask") is not None:
+            raise NotImplementedError("RANSACTriangulationNet takes no batch['view_mask']: its inlier search already drops views per joint")
         H.require_gpu(images, "images")
         if _bn_in_train_mode(self):
             raise NotImplementedError("RANSACTriangulationNet runs in eval() only: its triangulation carries no gradient (the reference "
@@ -934,15 +998,19 @@ class CascadeTriangulationNet(nn.Module):
         ``VolumetricTriangulationNet.forward`` and the 4-tuple of ``AlgebraicTriangulationNet.forward``, same shapes and dtypes.  ``base_points``
         is read from the device block; ``cuboids`` is a sequence that builds its ``Cuboid3D`` items on first access, and that access
         synchronises with the GPU (the forward itself never does, beyond what the two models' forwards do at their first call of a shape)."""
-        H.require_gpu(images, "images")
-        if _bn_in_train_mode(self):
+        B, NV = images.shape[:2]
+        vm = _batch_view_mask(batch, B, NV, 2, "CascadeTriangulationNet")          # the one mask for both stages, refused before any launch
+        if vm is not None:
+            batch = dict(batch, view_mask=vm)
+        if not _bn_in_train_mode(self):
+            H.require_gpu(images, "images")
+        else:
             raise NotImplementedError("CascadeTriangulationNet runs in eval() only: train the two stages on their own (the reference trains the "
                                       "volumetric model on pelvises read from a results file)")
         vol = self.vol
         alg_out = self.alg(images, proj_matricies, batch)
         kp_alg = alg_out[0]
         _sync_buffers_before_eval(vol)
-        B, NV = images.shape[:2]
         cap = vol.max_samples_per_launch(NV, images.shape[3], images.shape[4])
         n = -(-B // cap)
         size = -(-B // n)            # the sub-batches of VolumetricTriangulationNet.forward
@@ -980,7 +1048,7 @@ class CascadeTriangulationNet(nn.Module):
             vol._copy_geometry(P, side)
             H.check(H.lib().lt_cuboid_from_keypoints(kp_alg.data_ptr(), B, kp_alg.shape[1], H.KIND[vol.kind], float(vol.cuboid_side), gp + 4 * o_pos, gp + 4 * o_cen,
                                                      side.cuda_stream), "lt_cuboid_from_keypoints")
-            out = vol._replay(P, x, B, NV, side, cur)
+            out = vol._replay(P, x, B, NV, side, cur, batch.get("view_mask"))
         kp_alg.record_stream(side)
         x.record_stream(side)
         cur.wait_stream(side)

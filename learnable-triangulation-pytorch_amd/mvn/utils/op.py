@@ -45,11 +45,46 @@ def build_coord_volumes(base_points, cuboid_side, volume_size, thetas=None, axis
     return out
 
 
-def _unproject_launch(feats_cl, P, cv, conf, method):
-    """feats_cl (B,NV,h,w,C) contiguous channels-last -> (B,v0,v1,v2,C) channels-last, same dtype."""
+def view_mask_host(view_mask, B, NV, min_valid=0, what="view_mask"):
+    """A (B, NV) validity mask (bool / uint8 / any integer tensor or array, non-zero = valid) as a C-contiguous host uint8 array of 0 / 1.
+    ValueError on another shape, or when a sample has fewer than ``min_valid`` valid views (the message names the first such sample)."""
+    m = view_mask.detach().cpu().numpy() if torch.is_tensor(view_mask) else np.asarray(view_mask)
+    if m.dtype.kind not in "biu":
+        raise TypeError("%s must be a bool or integer (B, NV) mask, got dtype %s" % (what, m.dtype))
+    if m.shape != (B, NV):
+        raise ValueError("%s must have shape (B, NV) = (%d, %d), got %s" % (what, B, NV, tuple(m.shape)))
+    m = np.ascontiguousarray((m != 0).astype(np.uint8))
+    valid = m.sum(axis=1)
+    if (valid < min_valid).any():
+        b = int(np.argmax(valid < min_valid))
+        raise ValueError("%s: sample %d has %d valid view%s, at least %d needed" % (what, b, int(valid[b]), "" if valid[b] == 1 else "s", min_valid))
+    return m
+
+
+def _view_mask_device(view_mask, B, NV, device):
+    """The mask as a (B, NV) uint8 device tensor for the masked entry points (a device tensor of the right form is used as it is)."""
+    if torch.is_tensor(view_mask) and view_mask.is_cuda:
+        if tuple(view_mask.shape) != (B, NV):
+            raise ValueError("view_mask must have shape (B, NV) = (%d, %d), got %s" % (B, NV, tuple(view_mask.shape)))
+        if view_mask.dtype == torch.uint8:
+            return view_mask.to(device).contiguous()
+        if view_mask.dtype == torch.bool or not view_mask.dtype.is_floating_point:
+            return (view_mask != 0).to(device, torch.uint8).contiguous()
+        raise TypeError("view_mask must be a bool or integer (B, NV) mask, got dtype %s" % view_mask.dtype)
+    return torch.from_numpy(view_mask_host(view_mask, B, NV)).to(device)
+
+
+def _unproject_launch(feats_cl, P, cv, conf, method, mask=None):
+    """feats_cl (B,NV,h,w,C) contiguous channels-last -> (B,v0,v1,v2,C) channels-last, same dtype.  mask: (B,NV) uint8 device tensor
+    (lt_unproject_masked_fwd) or None."""
     B, NV, h, w, Cc = feats_cl.shape
     v0, v1, v2 = cv.shape[1:4]
     out = torch.empty(B, v0, v1, v2, Cc, dtype=feats_cl.dtype, device=feats_cl.device)
+    if mask is not None:
+        H.check(H.lib().lt_unproject_masked_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), mask.data_ptr(),
+                                                out.data_ptr(), B, NV, Cc, h, w, v0, v1, v2, H.AGG["conf"] if conf is not None else H.AGG[method],
+                                                H.cur_stream()), "lt_unproject_masked_fwd")
+        return out
     H.check(H.lib().lt_unproject_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), out.data_ptr(),
                                      B, NV, Cc, h, w, v0, v1, v2, H.AGG["conf"] if conf is not None else H.AGG[method], H.cur_stream()), "lt_unproject_fwd")
     return out
@@ -87,10 +122,14 @@ class _UnprojectFn(torch.autograd.Function):
         return gfeats.permute(0, 1, 4, 2, 3).to(feats.dtype), None, None, gconf, None
 
 
-def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="sum", vol_confidences=None):
+def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="sum", vol_confidences=None, view_mask=None):
     """heatmaps (B,NV,C,h,w), proj_matricies (B,NV,3,4), coord_volumes (B,V0,V1,V2,3),
     vol_confidences (B,NV,C) for 'conf*' -> volumes (B,C,V0,V1,V2).  Reference: op.py:99-166.  Differentiable with respect to the
-    heatmaps and the confidences (lt_unproject_bwd) whenever one of them requires grad."""
+    heatmaps and the confidences (lt_unproject_bwd) whenever one of them requires grad.
+
+    view_mask: optional (B,NV) bool / uint8 tensor or array, non-zero = the view is there.  Sample b then gets what this function gives for its
+    valid views alone (lt_unproject_masked_fwd: masked views are never read; a sample without a valid view gets zeros).  Inference only:
+    with inputs that require grad it raises NotImplementedError.  None takes exactly the unmasked path."""
     if volume_aggregation_method not in _METHODS:
         raise ValueError("Unknown volume_aggregation_method: {}".format(volume_aggregation_method))
     H.require_gpu(heatmaps, "heatmaps")
@@ -100,6 +139,11 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
     conf = None
     if volume_aggregation_method.startswith("conf"):
         conf = vol_confidences.to(heatmaps.device, torch.float32).contiguous()
+    if view_mask is not None:
+        if torch.is_grad_enabled() and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad)):
+            raise NotImplementedError("unproject_heatmaps: view_mask is inference only (no masked backward); call it under torch.no_grad()")
+        mask = _view_mask_device(view_mask, heatmaps.shape[0], heatmaps.shape[1], heatmaps.device)
+        return _unproject_launch(_as_channels_last(heatmaps, 2), P, cv, conf, volume_aggregation_method, mask).permute(0, 4, 1, 2, 3)
     if torch.is_grad_enabled() and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad)):
         return _UnprojectFn.apply(heatmaps, P, cv, conf, volume_aggregation_method)
     return _unproject_launch(_as_channels_last(heatmaps, 2), P, cv, conf, volume_aggregation_method).permute(0, 4, 1, 2, 3)
