@@ -49,8 +49,44 @@ namespace {
     } while (0)
 
 constexpr float BN_EPS = 1e-5f;
-constexpr int GEO_RING = 4;
+constexpr int GEO_RING = 4;          // slots of a StagingRing: forwards the host may run ahead of the GPU
 constexpr int MODEL_CASCADE = 3;          // lt_plan::model of a cascade plan (not a value of lt_alg_plan_config.model)
+
+// The one staging ring of the plans: GEO_RING pinned host blocks behind asynchronous H2D copies.  acquire() advances to the next slot, waits for the event
+// recorded behind that slot's last copy (GEO_RING uses ago) and hands out its block; the caller fills it, enqueues its copy and calls commit(), which records
+// the slot's event behind it -- this order is what keeps forward i+1's bytes out of forward i's queued copy.  Events are created at a slot's first commit:
+// the first GEO_RING uses never wait.  Owns its blocks and events.
+struct StagingRing {
+    void* host[GEO_RING] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t ev[GEO_RING] = {nullptr, nullptr, nullptr, nullptr};
+    int slot = 0;
+    StagingRing() = default;
+    StagingRing(const StagingRing&) = delete;
+    StagingRing& operator=(const StagingRing&) = delete;
+    ~StagingRing() {
+        for (int i = 0; i < GEO_RING; ++i) { if (host[i]) (void)hipHostFree(host[i]); if (ev[i]) (void)hipEventDestroy(ev[i]); }
+    }
+    // the blocks that are not there yet, zeroed (a retry after a failure keeps what it has)
+    int alloc(size_t bytes) {
+        for (int i = 0; i < GEO_RING; ++i)
+            if (!host[i]) { PL_HIP(hipHostMalloc(&host[i], bytes, hipHostMallocDefault)); memset(host[i], 0, bytes); }
+        return LT_OK;
+    }
+    int acquire(void** block) {
+        slot = (slot + 1) % GEO_RING;
+        if (ev[slot]) PL_HIP(hipEventSynchronize(ev[slot]));          // the copy that last read this slot has completed
+        *block = host[slot];
+        return LT_OK;
+    }
+    int commit(hipStream_t st) {
+        if (!ev[slot]) PL_HIP(hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming));
+        PL_HIP(hipEventRecord(ev[slot], st));
+        return LT_OK;
+    }
+    void swap(StagingRing& o) {
+        for (int i = 0; i < GEO_RING; ++i) { std::swap(host[i], o.host[i]); std::swap(ev[i], o.ev[i]); }
+        std::swap(slot, o.slot);
+    }
+};
 
 unsigned short bf16_rne(float f) {          // torch's float -> bfloat16 (round to nearest even, NaN kept quiet)
     unsigned u;
@@ -253,18 +289,18 @@ struct lt_plan {
     float* out_kp = nullptr; float* out_probs = nullptr; float* out_feats = nullptr;
     const float* cur_proj = nullptr; void* out_kp2d = nullptr; float* out_hm = nullptr; float* out_conf = nullptr;          // algebraic / RANSAC plans
     // geometry block (fp32): proj B*NV*12 | pos B*3 | center B*3 | rot B*9 -- one H2D copy per forward from a ring of pinned blocks
-    float* geo_dev = nullptr; float* geo_host[GEO_RING] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t geo_ev[GEO_RING] = {nullptr, nullptr, nullptr, nullptr};
-    int geo_slot = 0; size_t n_geo = 0, o_pos = 0, o_cen = 0, o_rot = 0;
+    float* geo_dev = nullptr; StagingRing geo; size_t n_geo = 0, o_pos = 0, o_cen = 0, o_rot = 0;
     // results
     Act feats, vol, logits, volc;
     float* coords = nullptr; float* kp = nullptr; float* probs = nullptr; void* sa_ws = nullptr;
     Act algc;                                   // alg_confidences head output [1,1,1,N,J] fp32 (algebraic plans with use_confidences)
     float* hm_nchw = nullptr; float* kp_hm = nullptr; int64_t* kp_i64 = nullptr;          // heatmaps N,J,h,w; soft-argmax N,J,2 (heatmap px); argmax N,J,2
     int hm_h = 0, hm_w = 0;
-    // cascade plans: the two stages, the algebraic stage's image-resolution projections (pinned ring + device copy; the slots and their events are
-    // sub_vol's geometry ring's: its copy is queued behind this one on the same stream) and its joints when the caller does not ask for them
+    // cascade plans: the two stages, the algebraic stage's image-resolution projections (pinned ring + device copy; the ring turns with sub_vol's geometry
+    // ring and is guarded by that ring's events, re-recorded behind this copy: it is never committed itself, so it never waits) and its joints when the
+    // caller does not ask for them
     lt_plan* sub_alg = nullptr; lt_plan* sub_vol = nullptr; int kind = 0;
-    float* cproj_dev = nullptr; float* cproj_host[GEO_RING] = {nullptr, nullptr, nullptr, nullptr}; float* ckp_alg = nullptr;
+    float* cproj_dev = nullptr; StagingRing cproj; float* ckp_alg = nullptr;
     // per-sample view masks (lt_plan_set_view_mask).  masked: the gather / the algebraic tail run their masked entry points, chosen before the first forward
     // (what the graph captures).  mask_cur: the host (B, NV) mask, kept until replaced.  Volumetric plans carry it at the end of the geometry block (o_mask:
     // offset in floats; same ring slot, same copy); algebraic plans have no such block: a ring of their own, copied when the mask has changed; the algebraic
@@ -272,8 +308,7 @@ struct lt_plan {
     bool masked = false, ran = false, mask_dirty = false;
     std::vector<uint8_t> mask_cur;
     const uint8_t* mask_dev = nullptr; size_t o_mask = 0;
-    uint8_t* amask_dev = nullptr; uint8_t* amask_host[GEO_RING] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t amask_ev[GEO_RING] = {nullptr, nullptr, nullptr, nullptr};
-    int amask_slot = 0;
+    uint8_t* amask_dev = nullptr; StagingRing amask;
     int n_xr = 0, n_bneck = 0, n_bneck_ds = 0, n_cat2 = 0, n_halo2d = 0, n_pwchain = 0, n_stem = 0, n_splitk = 0, n_conv_skip = 0;
 
     ~lt_plan() {
@@ -281,9 +316,6 @@ struct lt_plan {
         if (own_stream) (void)hipStreamDestroy(own_stream);
         for (int i = 0; i < 2; ++i) if (own_ev[i]) (void)hipEventDestroy(own_ev[i]);
         for (void* p : allocs) (void)hipFree(p);
-        for (int i = 0; i < GEO_RING; ++i) { if (geo_host[i]) (void)hipHostFree(geo_host[i]); if (geo_ev[i]) (void)hipEventDestroy(geo_ev[i]); }
-        for (int i = 0; i < GEO_RING; ++i) if (cproj_host[i]) (void)hipHostFree(cproj_host[i]);
-        for (int i = 0; i < GEO_RING; ++i) { if (amask_host[i]) (void)hipHostFree(amask_host[i]); if (amask_ev[i]) (void)hipEventDestroy(amask_ev[i]); }
         delete sub_alg;
         delete sub_vol;
     }
@@ -939,7 +971,7 @@ struct lt_plan {
         // geometry block + its pinned staging ring
         n_geo = (size_t)B * NV * 12 + (size_t)B * 15; o_pos = (size_t)B * NV * 12; o_cen = o_pos + 3 * B; o_rot = o_pos + 6 * B;
         void* g; PL_TRY(dev_alloc(n_geo * 4, &g)); geo_dev = (float*)g;
-        for (int i = 0; i < GEO_RING; ++i) { PL_HIP(hipHostMalloc((void**)&geo_host[i], n_geo * 4, hipHostMallocDefault)); }
+        PL_TRY(geo.alloc(n_geo * 4));
         void* c; PL_TRY(dev_alloc((size_t)B * V * V * V * 3 * 4, &c)); coords = (float*)c;
         PL_TRY(alloc(B, V, V, V, 32, es, vol));
         const float step = (float)(cfg.cuboid_side / (double)(V - 1));          // float(np.float32(side / (V - 1))): the fp64 quotient rounded once
@@ -1046,15 +1078,12 @@ struct lt_plan {
     // ---- host geometry in fp64 like the reference (triangulation.py:272-296): Camera.update_after_resize to the heatmap resolution, projection = K [R | t];
     // cuboid position = base - side / 2; rotation about the vertical axis (identity in eval mode); one pinned block, one H2D copy.  base_points_host NULL
     // (cascade plans): the pos / center ranges are left for lt_cuboid_from_keypoints, which the caller enqueues behind the copy.  proj_img (cascade plans,
-    // the ring slot's block): K [R | t] at IMAGE resolution rounded to fp32, the algebraic stage's proj_matricies_batch.
+    // its block of this forward): K [R | t] at IMAGE resolution rounded to fp32, the algebraic stage's proj_matricies_batch.
     int stage_geometry(const double* K_host, const double* R_host, const double* t_host, const double* base_points_host, const double* rot_host, hipStream_t st,
-                       float* const* proj_img_ring = nullptr) {
+                       float* pi = nullptr) {
         const int B = cfg.B, NV = cfg.NV;
-        const int slot = geo_slot = (geo_slot + 1) % GEO_RING;
-        if (geo_ev[slot]) PL_HIP(hipEventSynchronize(geo_ev[slot]));          // the copy that last read this slot (GEO_RING forwards ago) has completed
-        else PL_HIP(hipEventCreateWithFlags(&geo_ev[slot], hipEventDisableTiming));
-        float* gh = geo_host[slot];
-        float* pi = proj_img_ring ? proj_img_ring[slot] : nullptr;
+        void* blk; PL_TRY(geo.acquire(&blk));
+        float* gh = (float*)blk;
         const double sx = (double)hm_w / (double)cfg.W, sy = (double)hm_h / (double)cfg.H;
         for (int i = 0; i < B * NV; ++i) {
             double K[9];
@@ -1085,8 +1114,7 @@ struct lt_plan {
         }
         if (masked) memcpy((uint8_t*)(gh + o_mask), mask_cur.data(), (size_t)B * NV);          // rides in the same block: one copy
         PL_HIP(hipMemcpyAsync(geo_dev, gh, n_geo * 4, hipMemcpyHostToDevice, st));
-        PL_HIP(hipEventRecord(geo_ev[slot], st));
-        return LT_OK;
+        return geo.commit(st);
     }
 
     // volumetric plans, first lt_plan_set_view_mask: the geometry block and its pinned ring again, with B*NV mask bytes (whole words) behind the floats.
@@ -1094,17 +1122,15 @@ struct lt_plan {
     // old block and ring are freed -- no forward has run, nothing is queued on them -- so lt_plan_info reports what the plan holds.
     int grow_geometry_for_mask() {
         const size_t n_new = n_geo + ((size_t)cfg.B * cfg.NV + 3) / 4;
-        void* g = nullptr; float* ring[GEO_RING] = {nullptr, nullptr, nullptr, nullptr};
+        void* g = nullptr; StagingRing ring;          // frees what it got on a failure, the old ring after the swap
         auto acquire = [&]() -> int {
             PL_HIP(hipMalloc(&g, n_new * 4));
             PL_HIP(hipMemset(g, 0, n_new * 4));
-            for (int i = 0; i < GEO_RING; ++i) { PL_HIP(hipHostMalloc((void**)&ring[i], n_new * 4, hipHostMallocDefault)); memset(ring[i], 0, n_new * 4); }
-            return LT_OK;
+            return ring.alloc(n_new * 4);
         };
         const int rc = acquire();
         if (rc != LT_OK) {
             if (g) (void)hipFree(g);
-            for (int i = 0; i < GEO_RING; ++i) if (ring[i]) (void)hipHostFree(ring[i]);
             return rc;
         }
         for (size_t i = 0; i < allocs.size(); ++i)
@@ -1112,7 +1138,7 @@ struct lt_plan {
         (void)hipFree(geo_dev);
         bytes_alloc += (n_new - n_geo) * 4;
         allocs.push_back(g);
-        for (int i = 0; i < GEO_RING; ++i) { if (geo_host[i]) (void)hipHostFree(geo_host[i]); geo_host[i] = ring[i]; }
+        geo.swap(ring);
         geo_dev = (float*)g; o_mask = n_geo; n_geo = n_new;
         mask_dev = (const uint8_t*)(geo_dev + o_mask);
         return LT_OK;
@@ -1120,19 +1146,17 @@ struct lt_plan {
     // algebraic plans, first lt_plan_set_view_mask: the mask's device block and its pinned ring
     int alloc_alg_mask() {
         const size_t n = (size_t)cfg.B * cfg.NV;
-        for (int i = 0; i < GEO_RING; ++i) if (!amask_host[i]) PL_HIP(hipHostMalloc((void**)&amask_host[i], n, hipHostMallocDefault));          // a retry after a failure keeps what it has
+        PL_TRY(amask.alloc(n));
         void* q; PL_TRY(dev_alloc(n, &q)); amask_dev = (uint8_t*)q; mask_dev = amask_dev;
         return LT_OK;
     }
-    // algebraic plans, per forward: a changed mask to the device through the ring (a slot is rewritten only after its last copy has completed)
+    // algebraic plans, per forward: a changed mask to the device through the ring
     int stage_alg_mask(hipStream_t st) {
         if (!masked || !amask_dev || !mask_dirty) return LT_OK;
-        const int slot = amask_slot = (amask_slot + 1) % GEO_RING;
-        if (amask_ev[slot]) PL_HIP(hipEventSynchronize(amask_ev[slot]));
-        else PL_HIP(hipEventCreateWithFlags(&amask_ev[slot], hipEventDisableTiming));
-        memcpy(amask_host[slot], mask_cur.data(), mask_cur.size());
-        PL_HIP(hipMemcpyAsync(amask_dev, amask_host[slot], mask_cur.size(), hipMemcpyHostToDevice, st));
-        PL_HIP(hipEventRecord(amask_ev[slot], st));
+        void* blk; PL_TRY(amask.acquire(&blk));
+        memcpy(blk, mask_cur.data(), mask_cur.size());
+        PL_HIP(hipMemcpyAsync(amask_dev, blk, mask_cur.size(), hipMemcpyHostToDevice, st));
+        PL_TRY(amask.commit(st));
         mask_dirty = false;
         return LT_OK;
     }
@@ -1333,8 +1357,7 @@ extern "C" int lt_plan_create_cascade(const lt_cascade_plan_config* cfg, const l
         void* q;
         PL_TRY(p->dev_alloc(nproj, &q)); p->cproj_dev = (float*)q;
         PL_TRY(p->dev_alloc((size_t)a.B * a.num_joints * 3 * 4, &q)); p->ckp_alg = (float*)q;
-        for (int i = 0; i < GEO_RING; ++i) PL_HIP(hipHostMalloc((void**)&p->cproj_host[i], nproj, hipHostMallocDefault));
-        return LT_OK;
+        return p->cproj.alloc(nproj);
     };
     if (rc == LT_OK) rc = finish();
     if (rc != LT_OK) { delete p; return rc; }
@@ -1358,10 +1381,12 @@ extern "C" int lt_plan_forward_cascade(lt_plan* p, const float* images, const do
     const int B = Vp->cfg.B, NV = Vp->cfg.NV, V = Vp->cfg.volume_size;
     p->ran = true;
     // cameras once: the volumetric stage's block (projections at heatmap resolution, rotations; pos / center are the seam kernel's) and the algebraic
-    // stage's projections at image resolution, two H2D copies out of the same ring slot; the slot's event is re-recorded behind the second
-    PL_TRY(Vp->stage_geometry(K_host, R_host, t_host, nullptr, rot_host, st, p->cproj_host));
-    PL_HIP(hipMemcpyAsync(p->cproj_dev, p->cproj_host[Vp->geo_slot], (size_t)B * NV * 12 * 4, hipMemcpyHostToDevice, st));
-    PL_HIP(hipEventRecord(Vp->geo_ev[Vp->geo_slot], st));
+    // stage's projections at image resolution: two H2D copies, the geometry slot's event re-recorded behind the second.  The wait in stage_geometry covers
+    // both blocks: this cproj block was last read one turn of the rings ago, by the copy in front of that event.
+    void* cproj_blk; PL_TRY(p->cproj.acquire(&cproj_blk));
+    PL_TRY(Vp->stage_geometry(K_host, R_host, t_host, nullptr, rot_host, st, (float*)cproj_blk));
+    PL_HIP(hipMemcpyAsync(p->cproj_dev, cproj_blk, (size_t)B * NV * 12 * 4, hipMemcpyHostToDevice, st));
+    PL_TRY(Vp->geo.commit(st));
     // stage 1: lt_plan_forward_alg's launches
     float* kp_alg = alg_keypoints_3d ? alg_keypoints_3d : p->ckp_alg;
     A->cur_images = images; A->cur_proj = p->cproj_dev; A->out_kp = kp_alg; A->out_kp2d = nullptr; A->out_hm = nullptr; A->out_conf = nullptr;

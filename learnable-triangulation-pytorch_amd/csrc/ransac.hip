@@ -9,13 +9,15 @@
 // lt_triangulate_ransac: one lane per (sample, joint) problem, fp64 throughout (the reference's numpy fp64 on fp32 projection
 // matrices and integer points).  Every DLT (multiview.py:113-138) streams the rows of A (2n x 4) through Givens rotations into a
 // 4x4 upper-triangular R (A = QR, same right singular vectors and the same condition number: A^T A would square it), then runs a
-// one-sided Jacobi SVD on R.  Hypotheses are 2-view DLTs; the inlier set is the pair plus every view whose reprojection error
+// one-sided Jacobi SVD on R: the routine of csrc/dlt.h, shared with lt_triangulate_dlt and the algebraic tails.
+// Hypotheses are 2-view DLTs; the inlier set is the pair plus every view whose reprojection error
 // r_v = 1/2 |p_v - pi_v(X)| (multiview.py:186-193) is < eps, kept only when strictly larger than the best so far (:84-97).
 // The final DLT uses the inlier views; with direct_opt, Levenberg-Marquardt minimises scipy's least_squares(loss='huber')
 // objective 0.5 sum_v rho(r_v^2) over them, with IRLS weights rho'(r_v^2) on both 2D components of view v (exact for this
 // objective and smooth at r_v = 0) and analytic Jacobians, started from the inlier DLT point and from one DLT per inlier view with
 // that view pinned (the objective is multimodal when residuals sit in Huber's linear regime); the lowest cost wins.
 #include "lt_common.h"
+#include "dlt.h"
 
 using namespace lt;
 
@@ -105,78 +107,6 @@ struct RansacArgs {
     int n_iters, direct, B, NV, J;
 };
 
-// one view's two rows of A (multiview.py:131-132) in fp64 from the fp32 matrix and the integer point, as numpy computes them
-__device__ __forceinline__ void a_rows(const float* P, double px, double py, double r0[4], double r1[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        r0[k] = px * (double)P[8 + k] - (double)P[k];
-        r1[k] = py * (double)P[8 + k] - (double)P[4 + k];
-    }
-}
-
-// rotate one row into the upper-triangular R (Givens)
-__device__ __forceinline__ void qr_add_row(double R[4][4], double a[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (a[k] != 0.0) {
-            const double r = sqrt(R[k][k] * R[k][k] + a[k] * a[k]);
-            const double c = R[k][k] / r, s = a[k] / r;
-            R[k][k] = r;
-#pragma unroll
-            for (int m = k + 1; m < 4; ++m) {
-                const double rk = R[k][m], am = a[m];
-                R[k][m] = c * rk + s * am;
-                a[m] = c * am - s * rk;
-            }
-        }
-    }
-}
-
-// X = v[:3] / v[3], v = right singular vector of R for its smallest singular value (one-sided Jacobi: orthogonalise R's columns)
-__device__ __forceinline__ void svd_point(double U[4][4], double X[3]) {
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                double al = 0, be = 0, ga = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { al += U[k][p] * U[k][p]; be += U[k][q] * U[k][q]; ga += U[k][p] * U[k][q]; }
-                if (ga != 0.0 && fabs(ga) > 1e-15 * sqrt(al * be)) {
-                    rotated = true;
-                    const double zeta = (be - al) / (2.0 * ga);
-                    const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const double up = U[k][p], uq = U[k][q];
-                        U[k][p] = c * up - s * uq; U[k][q] = s * up + c * uq;
-                        const double vp = V[k][p], vq = V[k][q];
-                        V[k][p] = c * vp - s * vq; V[k][q] = s * vp + c * vq;
-                    }
-                }
-            }
-        if (!rotated) break;
-    }
-    double nrm[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) nrm[p] = U[0][p] * U[0][p] + U[1][p] * U[1][p] + U[2][p] * U[2][p] + U[3][p] * U[3][p];
-    double v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = V[k][0];
-    double best = nrm[0];
-#pragma unroll
-    for (int p = 1; p < 4; ++p)
-        if (nrm[p] < best) {
-            best = nrm[p];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = V[k][p];
-        }
-    X[0] = v[0] / v[3]; X[1] = v[1] / v[3]; X[2] = v[2] / v[3];
-}
-
 struct Problem {
     const float* P;         // this sample's NV matrices
     const int64_t* pts;     // this sample's points, joint j: pts[(v * J + j) * 2]
@@ -185,20 +115,12 @@ struct Problem {
     __device__ __forceinline__ double py(int v) const { return (double)pts[((long long)v * J + j) * 2 + 1]; }
 };
 
-// DLT of the views in mask; view `pin` (or -1) has its rows weighted by RS_PIN: a point close to that view's ray
-__device__ __forceinline__ void dlt(const Problem& pb, unsigned mask, double X[3], int pin = -1) {
+// DLT of the views in mask (the routine of dlt.h on the integer points); view `pin` (or -1) has its rows weighted by RS_PIN: a point close to that view's ray
+__device__ __forceinline__ void dlt(const Problem& pb, unsigned mask, double (&X)[3], int pin = -1) {
     double R[4][4] = {};
-    for (int v = 0; v < pb.NV; ++v) {
-        if (!((mask >> v) & 1u)) continue;
-        double r0[4], r1[4];
-        a_rows(pb.P + v * 12, pb.px(v), pb.py(v), r0, r1);
-        if (v == pin)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { r0[k] *= RS_PIN; r1[k] *= RS_PIN; }
-        qr_add_row(R, r0);
-        qr_add_row(R, r1);
-    }
-    svd_point(R, X);
+    for (int v = 0; v < pb.NV; ++v)
+        if ((mask >> v) & 1u) dlt_add_view(R, pb.P + v * 12, pb.px(v), pb.py(v), v == pin ? RS_PIN : 1.0);
+    dlt_point(R, X);
 }
 
 // projection of X by view v (numpy: homogeneous X @ P.T, then divide), the residual e = p - pi(X) and q = P [X; 1]

@@ -10,6 +10,7 @@
 // voxels, every joint is one 16-byte load per lane (all J of them in flight at once) and the probabilities are written by a
 // plain vectorised elementwise pass.
 #include "lt_common.h"
+#include "dlt.h"
 
 using namespace lt;
 
@@ -379,73 +380,12 @@ __global__ __launch_bounds__(256) void sa2_kernel(const float* __restrict__ hm, 
         }
 }
 
-// ---- DLT: one lane per (sample, joint) ----------------------------------------------------------------------------------------------------
-// The per-lane routine every DLT kernel here shares (forward, algebraic tail, backward), so that they solve the same system with the same
-// instruction sequence.  dlt_accumulate: one view's two rows of A (multiview.py:159-161), c (x P[2,:] - P[r,:]), formed in fp64 from the fp32
-// inputs (the product of two fp32 values is exact in fp64; the reference rounds every step to fp32, which costs up to u32 |x P[2,:]| where
-// the subtraction cancels), and rotated into the upper-triangular R of A = QR (Givens).  The solve works on R, i.e. on A itself as the
-// reference's torch.svd(A) does: the normal matrix A^T A would square A's condition number (pixel-space rows, far points, confidences
-// down to 1e-5 reach kappa(A) ~ 1e8, where u64 kappa^2 exceeds what fp32 inputs can explain).
-// INVARIANT callers rely on: a row of zeros (confidence 0 with a finite point and matrix) leaves R untouched -- every a[k] == 0.0 takes the `continue` --
-// so a view given weight 0 is, bit for bit, a view that is not there (multiview.triangulate_batch_of_points(view_mask=) masks views this way).
-__device__ __forceinline__ void dlt_accumulate(double (&R)[4][4], const float* __restrict__ P, const float x, const float y, const float c) {
-    const double p[2] = {(double)x, (double)y};
-    for (int r = 0; r < 2; ++r) {
-        double a[4];
-        for (int k = 0; k < 4; ++k) a[k] = ((double)P[8 + k] * p[r] - (double)P[4 * r + k]) * (double)c;
-        for (int k = 0; k < 4; ++k) {          // Givens: rotate the row into R
-            if (a[k] == 0.0) continue;
-            const double h = sqrt(R[k][k] * R[k][k] + a[k] * a[k]);
-            const double cs = R[k][k] / h, sn = a[k] / h;
-            R[k][k] = h;
-            for (int m = k + 1; m < 4; ++m) {
-                const double rk = R[k][m], am = a[m];
-                R[k][m] = cs * rk + sn * am;
-                a[m] = cs * am - sn * rk;
-            }
-        }
-    }
-}
-
-// one-sided Jacobi SVD of R (its columns orthogonalised in place): right singular vectors in the columns of V, squared singular values
-// (the eigenvalues of A^T A) in lam; returns the column of the smallest = the last right singular vector of A
-__device__ __forceinline__ int dlt_svd(double (&U)[4][4], double (&V)[4][4], double (&lam)[4]) {
-    for (int i = 0; i < 4; ++i)
-        for (int k = 0; k < 4; ++k) V[i][k] = i == k ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-        for (int p = 0; p < 4; ++p)
-            for (int q = p + 1; q < 4; ++q) {
-                double al = 0, be = 0, ga = 0;
-                for (int k = 0; k < 4; ++k) { al += U[k][p] * U[k][p]; be += U[k][q] * U[k][q]; ga += U[k][p] * U[k][q]; }
-                if (ga == 0.0 || !(fabs(ga) > 1e-15 * sqrt(al * be))) continue;
-                rotated = true;
-                const double zeta = (be - al) / (2.0 * ga);
-                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-                for (int k = 0; k < 4; ++k) {
-                    const double up = U[k][p], uq = U[k][q];
-                    U[k][p] = cs * up - sn * uq; U[k][q] = sn * up + cs * uq;
-                    const double vp = V[k][p], vq = V[k][q];
-                    V[k][p] = cs * vp - sn * vq; V[k][q] = sn * vp + cs * vq;
-                }
-            }
-        if (!rotated) break;
-    }
-    int best = 0;
-    for (int p = 0; p < 4; ++p) {
-        lam[p] = U[0][p] * U[0][p] + U[1][p] * U[1][p] + U[2][p] * U[2][p] + U[3][p] * U[3][p];
-        if (lam[p] < lam[best]) best = p;
-    }
-    return best;
-}
-
-// the DLT point of one (sample, joint) from its R, dehomogenised
+// ---- DLT: one lane per (sample, joint), the routine of dlt.h ------------------------------------------------------------------------------------
+// the DLT point of one (sample, joint) from its R, rounded to fp32
 __device__ __forceinline__ void dlt_solve(double (&R)[4][4], float* __restrict__ o) {
-    double V[4][4], lam[4];
-    const int best = dlt_svd(R, V, lam);
-    const double wv = V[3][best];
-    o[0] = (float)(V[0][best] / wv); o[1] = (float)(V[1][best] / wv); o[2] = (float)(V[2][best] / wv);
+    double X[3];
+    dlt_point(R, X);
+    o[0] = (float)X[0]; o[1] = (float)X[1]; o[2] = (float)X[2];
 }
 
 __global__ void dlt_kernel(const float* __restrict__ proj, const float* __restrict__ pts, const float* __restrict__ conf,
@@ -457,7 +397,7 @@ __global__ void dlt_kernel(const float* __restrict__ proj, const float* __restri
     for (int v = 0; v < NV; ++v) {
         const float* p = pts + (((long long)b * NV + v) * J + j) * 2;
         const float c = conf ? conf[((long long)b * NV + v) * J + j] : 1.f;
-        dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, p[0], p[1], c);
+        dlt_add_view(R, proj + ((long long)b * NV + v) * 12, (double)p[0], (double)p[1], (double)c);
     }
     dlt_solve(R, out + (long long)g * 3);
 }
@@ -468,64 +408,42 @@ __global__ void dlt_kernel(const float* __restrict__ proj, const float* __restri
 // kp2d * scale, lt_triangulate_dlt), with the explicit _rn intrinsics so that no contraction can merge two of them.  The sum over views
 // is torch's GPU reduction order: four interleaved partial sums (view v into sum v % 4), combined ((s0 + s1) + s2) + s3 -- plain view
 // order for up to four views.
+// MASKED: the same over the valid views of each sample (mask: (B, NV), non-zero = valid; never read otherwise), i.e. the unmasked tail on
+// the compacted views, step for step -- the k-th VALID view goes into partial k % 4, the rows of the valid views enter R in view order.  A
+// masked view gets confidence 0 and its 2D keypoint is passed through to kp2d only (never into the system, so NaN there stays there);
+// fewer than two valid views: NaN joints.
+template <bool MASKED>
 __global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
-                                float sx, float sy, float* __restrict__ kp2d, float* __restrict__ conf_out, float* __restrict__ kp3d, int B, int NV, int J) {
+                                float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
+                                float* __restrict__ kp3d, int B, int NV, int J) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= B * J) return;
     const int b = g / J, j = g - b * J;
-    float part[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int v = 0; v < NV; ++v) {
-        const float c = conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f;
-        part[v & 3] = __fadd_rn(part[v & 3], c);
-    }
-    const float sum = __fadd_rn(__fadd_rn(__fadd_rn(part[0], part[1]), part[2]), part[3]);
-    double R[4][4] = {};  // R of A = QR, grown one view at a time
-    for (int v = 0; v < NV; ++v) {
-        const long long i = ((long long)b * NV + v) * J + j;
-        const float c = __fadd_rn(__fdiv_rn(conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f, sum), 1e-5f);
-        const float x = __fmul_rn(kp_hm[i * 2], sx), y = __fmul_rn(kp_hm[i * 2 + 1], sy);
-        if (conf_out) conf_out[i] = c;
-        if (kp2d) { kp2d[i * 2] = x; kp2d[i * 2 + 1] = y; }
-        dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, x, y, c);
-    }
-    dlt_solve(R, kp3d + (long long)g * 3);
-}
-
-// The same over the valid views of each sample (mask: (B, NV), non-zero = valid): alg_tail_kernel on the compacted views, step for step -- the
-// k-th VALID view goes into partial k % 4, the rows of the valid views enter R in view order.  A masked view gets confidence 0 and its 2D
-// keypoint is passed through to kp2d only (never into the system, so NaN there stays there); fewer than two valid views: NaN joints.
-__global__ void alg_tail_masked_kernel(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
-                                       float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
-                                       float* __restrict__ kp3d, int B, int NV, int J) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= B * J) return;
-    const int b = g / J, j = g - b * J;
-    const uint8_t* mk = mask + (long long)b * NV;
+    const uint8_t* mk = MASKED ? mask + (long long)b * NV : nullptr;
     float part[4] = {0.f, 0.f, 0.f, 0.f};
     int nvalid = 0;
     for (int v = 0; v < NV; ++v) {
-        if (!mk[v]) continue;
+        if (MASKED && !mk[v]) continue;
         const float c = conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f;
         part[nvalid & 3] = __fadd_rn(part[nvalid & 3], c);
         ++nvalid;
     }
     const float sum = __fadd_rn(__fadd_rn(__fadd_rn(part[0], part[1]), part[2]), part[3]);
-    double R[4][4] = {};  // R of A = QR, grown one valid view at a time
+    double R[4][4] = {};  // R of A = QR, grown one (valid) view at a time
     for (int v = 0; v < NV; ++v) {
         const long long i = ((long long)b * NV + v) * J + j;
-        if (!mk[v]) {
+        const float x = __fmul_rn(kp_hm[i * 2], sx), y = __fmul_rn(kp_hm[i * 2 + 1], sy);
+        if (kp2d) { kp2d[i * 2] = x; kp2d[i * 2 + 1] = y; }
+        if (MASKED && !mk[v]) {
             if (conf_out) conf_out[i] = 0.f;
-            if (kp2d) { kp2d[i * 2] = __fmul_rn(kp_hm[i * 2], sx); kp2d[i * 2 + 1] = __fmul_rn(kp_hm[i * 2 + 1], sy); }
             continue;
         }
         const float c = __fadd_rn(__fdiv_rn(conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f, sum), 1e-5f);
-        const float x = __fmul_rn(kp_hm[i * 2], sx), y = __fmul_rn(kp_hm[i * 2 + 1], sy);
         if (conf_out) conf_out[i] = c;
-        if (kp2d) { kp2d[i * 2] = x; kp2d[i * 2 + 1] = y; }
-        dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, x, y, c);
+        dlt_add_view(R, proj + ((long long)b * NV + v) * 12, (double)x, (double)y, (double)c);
     }
     float* o = kp3d + (long long)g * 3;
-    if (nvalid < 2) { o[0] = o[1] = o[2] = __int_as_float(0x7fc00000); return; }
+    if (MASKED && nvalid < 2) { o[0] = o[1] = o[2] = __int_as_float(0x7fc00000); return; }
     dlt_solve(R, o);
 }
 
@@ -569,7 +487,7 @@ __global__ void dlt_bwd_kernel(const float* __restrict__ proj, const float* __re
     for (int v = 0; v < NV; ++v) {
         const float* p = pts + (((long long)b * NV + v) * J + j) * 2;
         const float c = conf ? conf[((long long)b * NV + v) * J + j] : 1.f;
-        dlt_accumulate(R, proj + ((long long)b * NV + v) * 12, p[0], p[1], c);
+        dlt_add_view(R, proj + ((long long)b * NV + v) * 12, (double)p[0], (double)p[1], (double)c);
     }
     double V[4][4], ev[4];
     const int best = dlt_svd(R, V, ev);         // the forward's solve: eigenvectors of A^T A = right singular vectors, eigenvalues = sigma^2
@@ -684,26 +602,29 @@ extern "C" int lt_triangulate_dlt(const float* proj, const float* points, const 
     return LT_OK;
 }
 
+// the one checked launch behind lt_alg_tail_fwd and lt_alg_tail_masked_fwd
+template <bool MASKED>
+static int alg_tail_launch(const char* name, const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                           const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV, int32_t J, void* stream) {
+    LT_REQUIRE(keypoints_hm && proj && keypoints_3d, LT_ERR_INVALID, "%s: null argument", name);
+    LT_REQUIRE(!MASKED || view_mask, LT_ERR_INVALID, "%s: null view_mask", name);
+    LT_REQUIRE(B >= 1 && NV >= 2 && J >= 1, LT_ERR_INVALID, "%s: bad shape (B %d, NV %d, J %d)", name, B, NV, J);
+    LT_REQUIRE(!conf_raw || ld_conf >= J, LT_ERR_INVALID, "%s: ld_conf %d < J %d", name, ld_conf, J);
+    hipLaunchKernelGGL(alg_tail_kernel<MASKED>, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x,
+                       scale_y, view_mask, keypoints_2d, confidences, keypoints_3d, B, NV, J);
+    LT_CHECK_LAUNCH(name);
+    return LT_OK;
+}
+
 extern "C" int lt_alg_tail_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
                                float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV, int32_t J, void* stream) {
-    LT_REQUIRE(keypoints_hm && proj && keypoints_3d, LT_ERR_INVALID, "lt_alg_tail_fwd: null argument");
-    LT_REQUIRE(B >= 1 && NV >= 2 && J >= 1, LT_ERR_INVALID, "lt_alg_tail_fwd: bad shape (B %d, NV %d, J %d)", B, NV, J);
-    LT_REQUIRE(!conf_raw || ld_conf >= J, LT_ERR_INVALID, "lt_alg_tail_fwd: ld_conf %d < J %d", ld_conf, J);
-    hipLaunchKernelGGL(alg_tail_kernel, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y,
-                       keypoints_2d, confidences, keypoints_3d, B, NV, J);
-    LT_CHECK_LAUNCH("lt_alg_tail_fwd");
-    return LT_OK;
+    return alg_tail_launch<false>("lt_alg_tail_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, nullptr, keypoints_2d, confidences, keypoints_3d,
+                                  B, NV, J, stream);
 }
 
 extern "C" int lt_alg_tail_masked_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
                                       const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV,
                                       int32_t J, void* stream) {
-    LT_REQUIRE(keypoints_hm && proj && keypoints_3d, LT_ERR_INVALID, "lt_alg_tail_masked_fwd: null argument");
-    LT_REQUIRE(view_mask, LT_ERR_INVALID, "lt_alg_tail_masked_fwd: null view_mask");
-    LT_REQUIRE(B >= 1 && NV >= 2 && J >= 1, LT_ERR_INVALID, "lt_alg_tail_masked_fwd: bad shape (B %d, NV %d, J %d)", B, NV, J);
-    LT_REQUIRE(!conf_raw || ld_conf >= J, LT_ERR_INVALID, "lt_alg_tail_masked_fwd: ld_conf %d < J %d", ld_conf, J);
-    hipLaunchKernelGGL(alg_tail_masked_kernel, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x,
-                       scale_y, view_mask, keypoints_2d, confidences, keypoints_3d, B, NV, J);
-    LT_CHECK_LAUNCH("lt_alg_tail_masked_fwd");
-    return LT_OK;
+    return alg_tail_launch<true>("lt_alg_tail_masked_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, view_mask, keypoints_2d, confidences,
+                                 keypoints_3d, B, NV, J, stream);
 }

@@ -28,6 +28,7 @@ import torch
 
 import lt_engine as E
 import lt_hip as H
+from lt_staging import PinnedRing
 
 BN_EPS = 1e-5
 
@@ -839,14 +840,13 @@ class Adam:
             self._tables_used.append(tkey)
             slot = self._tables.get(tkey)
             if slot is None:
-                slot = self._tables[tkey] = (torch.empty(tab.nbytes, dtype=torch.uint8).pin_memory(), torch.empty(tab.nbytes, dtype=torch.uint8, device=dev),
-                                                          torch.cuda.Event())
-            host, devt, ev = slot
-            ev.synchronize()                       # the previous step's upload of this table has been consumed
+                slot = self._tables[tkey] = (PinnedRing(tab.nbytes, torch.uint8, 1), torch.empty(tab.nbytes, dtype=torch.uint8, device=dev))
+            ring, devt = slot
+            host = ring.acquire()                  # the previous step's upload of this table has been consumed
             host.numpy()[:] = tab.view(np.uint8)
             with torch.cuda.device(dev):
                 devt.copy_(host, non_blocking=True)
-                ev.record()
+                ring.commit(torch.cuda.current_stream(dev))
                 H.check(lib.lt_adam_step_multi(devt.data_ptr(), len(items), fb, b1, b2, eps, wd, pstep, torch.cuda.current_stream(dev).cuda_stream),
                         "lt_adam_step_multi")
         for p in touched:          # version counters: cached inference plans see that the weights have changed

@@ -8,6 +8,8 @@ copy, and the HWC -> CHW permutation happens on the device."""
 import numpy as np
 import torch
 
+from lt_staging import PinnedRing
+
 
 def make_collate_fn(randomize_n_views=True, min_n_views=10, max_n_views=31):
     """Reference datasets/utils.py:6-39: drops ``None`` items, optionally sub-samples the views (np.random, like the
@@ -53,22 +55,15 @@ STAGE_RING = 3          # pinned staging blocks per shape: prepare_batch of batc
 _staging = {}
 
 
-def _pinned(shape, dtype):
-    """Next slot of the pinned staging ring for this shape: [tensor, event of the last H2D copy that read it].  The caller waits for that
-    event before overwriting the block (a loop that never synchronises -- inference without a loss.item() -- would otherwise hand batch
-    i+1's pixels to batch i's queued copy) and records a new one behind its own copy.  Same hazard handling as the geometry ring of
-    VolumetricTriangulationNet (GEO_RING) and the job table of lt_train.Adam."""
+def _ring(shape, dtype):
+    """The staging ring (lt_staging.PinnedRing) for blocks of this shape."""
     key = (tuple(shape), dtype)
     ring = _staging.get(key)
     if ring is None:
         if len(_staging) > 4:
             _staging.clear()
-        pin = torch.cuda.is_available()
-        ring = _staging[key] = {"slots": [[torch.empty(shape, dtype=dtype).pin_memory() if pin else torch.empty(shape, dtype=dtype), None]
-                                          for _ in range(STAGE_RING)], "next": 0}
-    slot = ring["slots"][ring["next"]]
-    ring["next"] = (ring["next"] + 1) % STAGE_RING
-    return slot
+        ring = _staging[key] = PinnedRing(shape, dtype, STAGE_RING, pin=torch.cuda.is_available())
+    return ring
 
 
 def prepare_batch(batch, device, config=None, is_train=True):
@@ -77,14 +72,11 @@ def prepare_batch(batch, device, config=None, is_train=True):
     device = torch.device(device)
     images = np.asarray(batch["images"])                     # (B, NV, H, W, 3), any real dtype
     if device.type == "cuda":
-        slot = _pinned(images.shape, torch.float32)
-        stage, ev = slot
-        if ev is not None:
-            ev.synchronize()                                          # the H2D copy that last read this block (STAGE_RING batches ago) has completed
+        ring = _ring(images.shape, torch.float32)
+        stage = ring.acquire()
         stage.copy_(torch.from_numpy(np.ascontiguousarray(images)))   # dtype conversion on the way into the pinned block
         dev = stage.to(device, non_blocking=True)
-        slot[1] = torch.cuda.Event()
-        slot[1].record(torch.cuda.current_stream(device))
+        ring.commit(torch.cuda.current_stream(device))
     else:
         dev = torch.from_numpy(np.ascontiguousarray(images)).float()
     images_batch = dev.permute(0, 1, 4, 2, 3).contiguous()   # BxNVxHxWxC -> BxNVxCxHxW (reference img.py:95-98 per view)
@@ -104,7 +96,7 @@ def prepare_batch_frames(batch, device, image_shape, norm_image=True):
     """prepare_batch for a batch of deferred items (Human36MMultiViewDataset(defer_image_ops=True) collated by make_collate_fn):
     batch["frames"] list[NV] of list[B] uint8 (h, w, 3) frames of any sizes, batch["bboxes"] (B, NV, 4) crop boxes in frame
     coordinates.  Only the bytes of bbox & frame travel: the host packs them, with the view descriptors in front, into one pinned
-    block (same ring discipline as prepare_batch), one asynchronous H2D copy moves it, and one lt_crop_resize_u8 launch crops,
+    block of the staging ring, one asynchronous H2D copy moves it, and one lt_crop_resize_u8 launch crops,
     resizes (INTER_AREA) and normalises every view.  Returns the same 4-tuple as prepare_batch; the images are bitwise what
     prepare_batch gives for the CPU-prepared items (normalize_image(resize_image(crop_image(...))) cast to fp32).
 
@@ -160,10 +152,8 @@ def _upload(desc, regions, off, device):
     head = desc.nbytes
     total = head + off
     cap = 1 << max(20, (total - 1).bit_length())          # power-of-two blocks: one ring serves batches of similar byte counts
-    slot = _pinned((cap,), torch.uint8)
-    stage, ev = slot
-    if ev is not None:
-        ev.synchronize()
+    ring = _ring((cap,), torch.uint8)
+    stage = ring.acquire()
     host = stage.numpy()
     host[:head] = desc.view(np.uint8).reshape(-1)
     for i, reg in enumerate(regions):
@@ -171,8 +161,7 @@ def _upload(desc, regions, off, device):
             o = head + int(desc[i, 0])
             host[o:o + reg.size].reshape(reg.shape)[...] = reg
     dev = stage[:total].to(device, non_blocking=True)
-    slot[1] = torch.cuda.Event()
-    slot[1].record(torch.cuda.current_stream(device))
+    ring.commit(torch.cuda.current_stream(device))
     return dev, head
 
 

@@ -30,6 +30,7 @@ import torch.nn as nn
 
 import lt_engine as E
 import lt_hip as H
+from lt_staging import PinnedRing
 from mvn.models import pose_resnet
 from mvn.models.v2v import V2VModel
 from mvn.utils import multiview, op, volumetric
@@ -109,9 +110,7 @@ class _VolTrainPlan:
             self.feats = feats = tape.conv(feats256, pf.weight, pf.bias, None)
             h, w = feats.shape[2], feats.shape[3]
             n_geo = B * NV * 12 + B * 15
-            self.G = {"hw": (h, w), "offs": (B * NV * 12, B * NV * 12 + 3 * B, B * NV * 12 + 6 * B),
-                      "geo_ring": [torch.zeros(n_geo, dtype=torch.float32).pin_memory() for _ in range(GEO_RING)],
-                      "geo_events": [None] * GEO_RING, "geo_slot": 0}
+            self.G = {"hw": (h, w), "offs": (B * NV * 12, B * NV * 12 + 3 * B, B * NV * 12 + 6 * B), "geo_ring": PinnedRing(n_geo, torch.float32, GEO_RING)}
             self.geo = torch.zeros(n_geo, dtype=torch.float32, device=device)
             self.n_front = len(tape.fwd_ops)
         else:
@@ -124,8 +123,7 @@ class _VolTrainPlan:
         # host geometry exactly as in inference (numpy fp64; theta ~ U(0, 2 pi) because self.training), one pinned H2D copy
         position, base, sides = model._host_geometry(batch, B, (Hh, W), G)
         self.geo.copy_(G["geo_host"], non_blocking=True)
-        ev = G["geo_events"][G["geo_slot"]] = G["geo_events"][G["geo_slot"]] or torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(device))
+        G["geo_ring"].commit(torch.cuda.current_stream(device))
         if first:
             feats, gp = self.feats, self.geo.data_ptr()
             self.coords = coords = torch.empty(B, V, V, V, 3, dtype=torch.float32, device=device)
@@ -425,12 +423,8 @@ class VolumetricTriangulationNet(_PlannedNet):
         o_mask = B * NV * 12 + B * 15          # masked plans: B*NV mask bytes behind the floats (whole words)
         n_geo = o_mask + ((B * NV + 3) // 4 if masked else 0)
         geo = torch.zeros(n_geo, dtype=torch.float32, device=device)
-        # pinned staging RING: forward N+1 fills the next slot while forward N's copy may still be queued; a slot is rewritten only
-        # after the event recorded behind its last copy has completed (forward never blocks on the GPU otherwise)
-        geo_ring = [torch.zeros(n_geo, dtype=torch.float32) for _ in range(1 if dry_run else GEO_RING)]
-        if not dry_run:
-            geo_ring = [g.pin_memory() for g in geo_ring]
-        geo_host = geo_ring[0]
+        # pinned staging ring: forward N+1 fills the next slot while forward N's copy may still be queued (forward never blocks on the GPU otherwise)
+        geo_ring = PinnedRing(n_geo, torch.float32, 1 if dry_run else GEO_RING, pin=not dry_run)
         o_pos, o_cen, o_rot = B * NV * 12, B * NV * 12 + 3 * B, B * NV * 12 + 6 * B
         coords = torch.empty(B, V, V, V, 3, dtype=torch.float32, device=device)
         step = float(np.float32(self.cuboid_side / (V - 1)))
@@ -481,9 +475,8 @@ class VolumetricTriangulationNet(_PlannedNet):
         plan.keep += [geo, geo_ring, coords, kp, probs, ws]
         if image_cell is not None and not dry_run:
             x_in.t.untyped_storage().resize_(0)   # the fused stem reads the caller's images: x_in is only a shape (150 MB at B = 32)
-        return {"plan": plan, "x_in": x_in, "image_cell": image_cell, "feats": feats, "geo": geo, "geo_host": geo_host, "geo_ring": geo_ring,
-                "geo_events": [None] * len(geo_ring), "geo_slot": 0, "coords": coords, "kp": kp,
-                "probs": probs, "conf": conf, "logits": logits, "vol": vol, "hw": (h, w), "offs": (o_pos, o_cen, o_rot),
+        return {"plan": plan, "x_in": x_in, "image_cell": image_cell, "feats": feats, "geo": geo, "geo_host": geo_ring.blocks[0], "geo_ring": geo_ring,
+                "coords": coords, "kp": kp, "probs": probs, "conf": conf, "logits": logits, "vol": vol, "hw": (h, w), "offs": (o_pos, o_cen, o_rot),
                 "captured": False, "masked": masked, "o_mask": o_mask}
 
     def _host_cameras(self, batch, B, image_shape, P):
@@ -499,11 +492,7 @@ class VolumetricTriangulationNet(_PlannedNet):
             theta = np.random.uniform(0.0, 2 * np.pi) if self.training else 0.0
             rot[i] = volumetric.get_rotation_matrix(axis, theta).reshape(-1)
         o_pos, o_cen, o_rot = P["offs"]
-        slot = P["geo_slot"] = (P["geo_slot"] + 1) % len(P["geo_ring"])
-        ev = P["geo_events"][slot]
-        if ev is not None:
-            ev.synchronize()         # the copy that last read this slot (GEO_RING forwards ago) has completed
-        gh = P["geo_host"] = P["geo_ring"][slot]
+        gh = P["geo_host"] = P["geo_ring"].acquire()
         gh[:o_pos] = torch.from_numpy(proj.astype(np.float32).reshape(-1))
         gh[o_rot:o_rot + 9 * B] = torch.from_numpy(rot.astype(np.float32).reshape(-1))
         if P.get("masked"):
@@ -662,8 +651,7 @@ class VolumetricTriangulationNet(_PlannedNet):
     def _copy_geometry(P, side):
         """On the side stream: the filled ring slot to the plan's device block, and the event that frees the slot."""
         P["geo"].copy_(P["geo_host"], non_blocking=True)
-        ev = P["geo_events"][P["geo_slot"]] = P["geo_events"][P["geo_slot"]] or torch.cuda.Event()
-        ev.record(side)
+        P["geo_ring"].commit(side)
 
     def _replay(self, P, x, B, NV, side, cur, view_mask=None):
         """On the side stream, behind the geometry: the plan's launches.  Returns (kp, feats, probs, conf, coords, base_points).  view_mask (masked
@@ -756,9 +744,8 @@ class AlgebraicTriangulationNet(_PlannedNet):
         plan.keep += [hm_nchw, kp2d, probs]
         P = {"plan": plan, "x_in": x_in, "kp2d": kp2d, "probs": probs, "algc": algc, "hw": (h, w), "J": J, "masked": masked}
         if masked:
-            ring = [torch.zeros(N, dtype=torch.uint8) for _ in range(1 if dry_run else GEO_RING)]
-            P.update({"mask": torch.zeros(N, dtype=torch.uint8, device=device), "mask_ring": ring if dry_run else [r.pin_memory() for r in ring],
-                      "mask_events": [None] * len(ring), "mask_slot": 0})
+            P.update({"mask": torch.zeros(N, dtype=torch.uint8, device=device),
+                      "mask_ring": PinnedRing(N, torch.uint8, 1 if dry_run else GEO_RING, pin=not dry_run)})
         return P
 
     def forward(self, images, proj_matricies, batch):
@@ -837,15 +824,11 @@ class AlgebraicTriangulationNet(_PlannedNet):
     def _run(self, P, images, proj_matricies, B, NV, Hh, W, device, view_mask=None):
         h, w = P["hw"]; J = P["J"]
         st = torch.cuda.current_stream(device).cuda_stream
-        if view_mask is not None:          # the mask to its device block through the plan's pinned ring (a slot is rewritten only after its last copy has completed)
-            slot = P["mask_slot"] = (P["mask_slot"] + 1) % len(P["mask_ring"])
-            ev = P["mask_events"][slot]
-            if ev is not None:
-                ev.synchronize()
-            P["mask_ring"][slot].copy_(torch.from_numpy(view_mask.reshape(-1)))
-            P["mask"].copy_(P["mask_ring"][slot], non_blocking=True)
-            ev = P["mask_events"][slot] = ev or torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(device))
+        if view_mask is not None:          # the mask to its device block through the plan's pinned ring
+            host = P["mask_ring"].acquire()
+            host.copy_(torch.from_numpy(view_mask.reshape(-1)))
+            P["mask"].copy_(host, non_blocking=True)
+            P["mask_ring"].commit(torch.cuda.current_stream(device))
         E.stage_images(images.reshape(B * NV, 3, Hh, W).float().contiguous(), P["x_in"], st)
         P["plan"].run_eager(st)
         heatmaps = P["probs"].reshape(B, NV, J, h, w).clone()

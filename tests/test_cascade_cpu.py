@@ -56,6 +56,7 @@ def _random_joints(nb, seed):
 @pytest.mark.parametrize("kind", ["mpii", "coco"])
 @pytest.mark.parametrize("nb,side", [(1, 2500.0), (5, 2500.0), (3, 1234.567)])
 def test_cuboid_from_keypoints_equals_host_geometry_bit_for_bit(kind, nb, side):
+    from lt_staging import PinnedRing
     from mvn.models.triangulation import VolumetricTriangulationNet
     from mvn.utils import volumetric
     cfg = synth.vol_config(18, 32, "softmax", kind=kind, cuboid_side=side)
@@ -66,7 +67,12 @@ def test_cuboid_from_keypoints_equals_host_geometry_bit_for_bit(kind, nb, side):
     kp = _random_joints(nb, 17 * nb + (kind == "coco"))
     n_geo = nb * nv * 12 + nb * 15
     o_pos, o_cen, o_rot = nb * nv * 12, nb * nv * 12 + 3 * nb, nb * nv * 12 + 6 * nb
-    P = {"hw": (h, h), "offs": (o_pos, o_cen, o_rot), "geo_ring": [torch.full((n_geo,), float("nan")) for _ in range(2)], "geo_events": [None, None], "geo_slot": 0}
+    def nan_ring():
+        ring = PinnedRing(n_geo, torch.float32, 2, pin=False)
+        for blk in ring.blocks:
+            blk.fill_(float("nan"))
+        return ring
+    P = {"hw": (h, h), "offs": (o_pos, o_cen, o_rot), "geo_ring": nan_ring()}
     position, base, sides = m._host_geometry({"cameras": cameras(inp, nb), "pred_keypoints_3d": kp}, nb, (64, 64), P)
     gh = P["geo_host"].numpy()
     pos, center = volumetric.cuboid_from_keypoints(kp, kind, side)
@@ -74,7 +80,7 @@ def test_cuboid_from_keypoints_equals_host_geometry_bit_for_bit(kind, nb, side):
     assert pos.tobytes() == gh[o_pos:o_cen].tobytes()
     assert center.tobytes() == gh[o_cen:o_rot].tobytes()
     # and the camera half alone fills what the cuboid half does not
-    P2 = dict(P, geo_ring=[torch.full((n_geo,), float("nan")) for _ in range(2)], geo_slot=0)
+    P2 = dict(P, geo_ring=nan_ring())
     g2 = m._host_cameras({"cameras": cameras(inp, nb)}, nb, (64, 64), P2).numpy()
     assert np.isnan(g2[o_pos:o_rot]).all()
     assert g2[:o_pos].tobytes() == gh[:o_pos].tobytes() and g2[o_rot:].tobytes() == gh[o_rot:].tobytes()

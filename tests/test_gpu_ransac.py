@@ -117,6 +117,23 @@ def test_ransac_kernel_vs_reference(golden_dir, nv, direct, mode):
                   r("cost"), r("well"), direct)
 
 
+@pytest.mark.parametrize("nv", [2, 3, 8])
+def test_ransac_with_every_view_an_inlier_equals_the_dlt_kernel_bit_for_bit(nv):
+    """Both kernels solve through the one routine of csrc/dlt.h: with eps = 1e30 every view is an inlier of every hypothesis, the final
+    DLT of lt_triangulate_ransac (no refinement) is over all views with weight 1, and lt_triangulate_dlt on the same points as fp32
+    without confidences is the same system -- the same bits."""
+    from mvn.utils import multiview
+    B, J = 3, 5
+    K, R, t = synth.ring_cameras(nv, 384)
+    P = torch.from_numpy((K @ np.concatenate([R, t], -1)).astype(np.float32))[None].repeat(B, 1, 1, 1).to(DEV)
+    pts = torch.from_numpy(np.random.RandomState(29).randint(0, 384, (B, nv, J, 2)).astype(np.int64)).to(DEV)
+    kp, inl = multiview.triangulate_ransac_batch(P, pts, None, 1e30, False, return_inliers=True)
+    assert inl.all()
+    ref = multiview.triangulate_batch_of_points(P, pts.float())
+    assert torch.isfinite(ref).all()
+    assert torch.equal(kp, ref)
+
+
 def _net(direct=True):
     from mvn.models.triangulation import RANSACTriangulationNet
     import json
