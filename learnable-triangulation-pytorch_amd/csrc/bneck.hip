@@ -23,7 +23,7 @@
 
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wave_prims.h"
 
 using namespace lt;
 
@@ -44,8 +44,6 @@ __device__ unsigned long long g_bneck_trace[LT_BNECK_TRACE_WG * 4 * 8];
 #define BN_STAMP(k)
 #endif
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 struct BneckArgs {
     const bf16_t* x;
     bf16_t* y;
@@ -57,31 +55,6 @@ struct BneckArgs {
     const float* shift[3];
     int N, H, W, tiles_x, tiles_y;
 };
-
-__device__ __forceinline__ void dma16b(const void* src, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(lds_base)
-        : "memory");
-}
-
-__device__ __forceinline__ void wait_vm(int n) {
-    switch (n) {
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-        case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
 
 // Phase 1 issue order of a wave (all of it inline asm, so the waits are counted by hand; loads return in order): prologue W1 fragments A(0 .. D-1)
 // [2 loads each], ring stages DMA(0 .. AHEAD-1) [3 pieces each]; K step s issues A(s + D) and then DMA(s + AHEAD) while they exist.  Returns
@@ -97,37 +70,6 @@ constexpr int bneck_after(int ks) {
     }
     return total - last;
 }
-template <int N>
-__device__ __forceinline__ void wait_vm_c() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void frag_ready_b(V16& f) {
-    f32x4 t = f.f;
-    asm volatile("" : "+v"(t));
-    f.f = t;
-}
-
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void static_for_b(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        static_for_b<I0 + 1, I1>(f);
-    }
-}
-
-// wave-uniform base in SGPRs + 32-bit lane offset (conv_igemm7's gload16: s_nop for the readfirstlane -> vector-memory hazard)
-__device__ __forceinline__ void gload16b(V16& d, const void* sbase, unsigned voff) {
-    f32x4 t;
-    const unsigned long long b = (unsigned long long)(size_t)sbase;
-    const unsigned long long ub = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                                  (unsigned)__builtin_amdgcn_readfirstlane((int)b);
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=v"(t) : "v"(voff), "s"(ub) : "memory");
-    d.f = t;
-}
-
-__device__ __forceinline__ int swz64_b(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
 
 template <int C, int P, int NSTR, int NHELD>
 __global__ __launch_bounds__(256, 2) void bneck_kernel(const BneckArgs a) {
@@ -217,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(const BneckArgs a) {
 #elif defined(LT_BNECK_ABL_NOSWZ)   /* timing only: is the permuted 16-byte order inside a row's 64 bytes what the address path pays for? */
         const int kvlog = lane & 3;
 #else
-        const int kvlog = (lane & 3) ^ swz64_b(prow);
+        const int kvlog = (lane & 3) ^ swz64(prow);
 #endif
         int dbase[3];
         bool dact[3];
@@ -242,7 +184,7 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(const BneckArgs a) {
                 const void* src = dbase[I] >= 0 ? (const void*)(x + (dbase[I] + ks * 32)) : zero_page;
 #endif
 #endif
-                dma16b(src, lds0 + stage_base + (wave + 4 * I) * 1024);
+                dma16(src, lds0 + stage_base + (wave + 4 * I) * 1024);
             }
         };
         const int hb0 = NCB == 4 ? 0 : 3 * whalf;          // first halo pixel block of this wave
@@ -255,18 +197,18 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(const BneckArgs a) {
         V16 fa[NFA][2];
         auto loadA = [&](int ks, V16 (&dst)[2]) {
             const T* p = w1l + (size_t)(2 * ks) * NCB * 512;
-            gload16b(dst[0], p, wlane);
-            gload16b(dst[1], p + NCB * 512, wlane);
+            gload16(dst[0], p, wlane);
+            gload16(dst[1], p + NCB * 512, wlane);
         };
-        const unsigned fo0 = n31 * 64 + (((0 + hk) ^ swz64_b(n31)) << 4);
-        const unsigned fo1 = n31 * 64 + (((2 + hk) ^ swz64_b(n31)) << 4);
+        const unsigned fo0 = n31 * 64 + (((0 + hk) ^ swz64(n31)) << 4);
+        const unsigned fo1 = n31 * 64 + (((2 + hk) ^ swz64(n31)) << 4);
         auto capture = [&](unsigned stage_base, uint4 (&dst)[NPB][2]) {
 #pragma unroll
             for (int pb = 0; pb < NPB; ++pb) {
                 const int hpc = (2 * pb + prr + 1) * HPI + pcc + 1;
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    dst[pb][j] = *(const uint4*)((lptr_t)(size_t)(lds0 + stage_base + hpc * 64 + (((2 * j + hk) ^ swz64_b(hpc)) << 4)));
+                    dst[pb][j] = *(const uint4*)((lptr_t)(size_t)(lds0 + stage_base + hpc * 64 + (((2 * j + hk) ^ swz64(hpc)) << 4)));
             }
         };
 
@@ -276,22 +218,22 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(const BneckArgs a) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
 
-        static_for_b<0, DA>([&](auto kc) { loadA(decltype(kc)::value, fa[decltype(kc)::value]); });
+        static_for<0, DA>([&](auto kc) { loadA(decltype(kc)::value, fa[decltype(kc)::value]); });
 #pragma unroll
         for (int s = 0; s < AHEAD; ++s)
-            static_for_b<0, 3>([&](auto ic) { issue_piece(s, s * STAGE, ic); });
+            static_for<0, 3>([&](auto ic) { issue_piece(s, s * STAGE, ic); });
 
         // fully unrolled: every K step's wait count, ring stage and fragment register set are compile-time (and every asm load's result is used:
         // hipcc may give the registers of a dead one to something live, and the data landing later overwrites it)
-        static_for_b<0, NK1>([&](auto kc) {
+        static_for<0, NK1>([&](auto kc) {
             constexpr int ks = decltype(kc)::value, R = ks % NFA;
             constexpr unsigned rbuf = (ks % NST) * STAGE, wbuf = ((ks + AHEAD) % NST) * STAGE;
-            wait_vm_c<bneck_after<NK1, AHEAD, DA>(ks)>();    // A(ks) and this wave's pieces of stage ks
+            wait_vmcnt<bneck_after<NK1, AHEAD, DA>(ks)>();    // A(ks) and this wave's pieces of stage ks
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            frag_ready_b(fa[R][0]);
-            frag_ready_b(fa[R][1]);
+            frag_ready(fa[R][0]);
+            frag_ready(fa[R][1]);
             if constexpr (ks + DA < NK1) loadA(ks + DA, fa[(ks + DA) % NFA]);
-            if constexpr (ks + AHEAD < NK1) static_for_b<0, 3>([&](auto ic) { issue_piece(ks + AHEAD, wbuf, ic); });
+            if constexpr (ks + AHEAD < NK1) static_for<0, 3>([&](auto ic) { issue_piece(ks + AHEAD, wbuf, ic); });
             if constexpr (NHELD > 0 && ks < 4) { if (ks == wave) capture(rbuf, held[0]); }
             if constexpr (NHELD > 1 && ks >= 4 && ks < 8) { if (ks == wave + 4) capture(rbuf, held[NHELD > 1 ? 1 : 0]); }
             const unsigned rb = lds0 + rbuf + hb0 * 2048;
@@ -405,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(const BneckArgs a) {
         auto load_x = [&](auto uc, V16 (&dst)[NPB2]) {
             constexpr int u = decltype(uc)::value;
             constexpr int tap = u / G2, g = u % G2, dy = tap / 3, dx = tap % 3;
-            static_for_b<0, NPB2>([&](auto ic) {
+            static_for<0, NPB2>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 constexpr int TT = dy * HPI + dx + 2 * HPI * i;
                 const unsigned ad = am[TT & 15] ^ (g << 5);
@@ -413,7 +355,7 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(const BneckArgs a) {
             });
         };
         load_x(std::integral_constant<int, 0>{}, xa[0]);
-        static_for_b<0, NU>([&](auto uc) {
+        static_for<0, NU>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             if constexpr (u + WD < NU) wf[(u + WD) % (WD + 1)] = load_w(u + WD);
             if constexpr (u + 1 < NU) load_x(std::integral_constant<int, u + 1>{}, xa[(u + 1) & 1]);
@@ -462,7 +404,7 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(const BneckArgs a) {
     {
         const unsigned a2 = lds0 + T2_OFF + n31 * RB + ((hk ^ fsw(n31)) << 4);   // K block g: ^ (g << 5), pixel block pb: + pb * 32 * RB
         f32x16 acc[NPB];
-        static_for_b<0, NU3>([&](auto uc) {
+        static_for<0, NU3>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             constexpr int q = u / G2, g = u % G2;
             const int ob = wave + 4 * q;
@@ -614,15 +556,15 @@ __global__ __launch_bounds__(256, 2) void bneck_ds_kernel(const BneckDsArgs a) {
     // ================================================ phase 1: t1 = relu(bn1(W1 x)) on the halo =======================================
     {
         const int prow = lane >> 2;
-        const int kvlog = (lane & 3) ^ swz64_b(prow);
+        const int kvlog = (lane & 3) ^ swz64(prow);
         const T* w1l = a.w1 + (size_t)cb * 512;
         const unsigned wlane = lane * 16;
         V16 fa[NK1][2];
 #pragma unroll
         for (int ks = 0; ks < NK1; ++ks) {
             const T* p = w1l + (size_t)(2 * ks) * NCB * 512;
-            gload16b(fa[ks][0], p, wlane);
-            gload16b(fa[ks][1], p + NCB * 512, wlane);
+            gload16(fa[ks][0], p, wlane);
+            gload16(fa[ks][1], p + NCB * 512, wlane);
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -635,13 +577,13 @@ __global__ __launch_bounds__(256, 2) void bneck_ds_kernel(const BneckDsArgs a) {
 #pragma unroll
                 for (int ks = 0; ks < NK1; ++ks) {
                     const void* src = dbase >= 0 ? (const void*)(x + (dbase + ks * 32)) : zero_page;
-                    dma16b(src, lds0 + XS_OFF + ks * STAGE + (wave + 4 * i) * 1024);
+                    dma16(src, lds0 + XS_OFF + ks * STAGE + (wave + 4 * i) * 1024);
                 }
             }
         }
         const int hb0 = 3 * whalf;
-        const unsigned fo0 = n31 * 64 + (((0 + hk) ^ swz64_b(n31)) << 4);
-        const unsigned fo1 = n31 * 64 + (((2 + hk) ^ swz64_b(n31)) << 4);
+        const unsigned fo0 = n31 * 64 + (((0 + hk) ^ swz64(n31)) << 4);
+        const unsigned fo1 = n31 * 64 + (((2 + hk) ^ swz64(n31)) << 4);
         f32x16 acc[NPB1];
 #pragma unroll
         for (int i = 0; i < NPB1; ++i)
@@ -650,8 +592,8 @@ __global__ __launch_bounds__(256, 2) void bneck_ds_kernel(const BneckDsArgs a) {
         asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // both stages of x (all four waves' pieces), W1, the constants
 #pragma unroll
         for (int ks = 0; ks < NK1; ++ks) {
-            frag_ready_b(fa[ks][0]);
-            frag_ready_b(fa[ks][1]);
+            frag_ready(fa[ks][0]);
+            frag_ready(fa[ks][1]);
             const unsigned rb = lds0 + XS_OFF + ks * STAGE + hb0 * 2048;
             V16 b0[NPB1], b1[NPB1];
 #pragma unroll
@@ -736,7 +678,7 @@ __global__ __launch_bounds__(256, 2) void bneck_ds_kernel(const BneckDsArgs a) {
         auto load_x = [&](auto uc, V16 (&dst)[NPB2]) {
             constexpr int u = decltype(uc)::value;
             constexpr int tap = u / G2, g = u % G2, dy = tap / 3, dx = tap % 3;
-            static_for_b<0, NPB2>([&](auto ic) {
+            static_for<0, NPB2>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 constexpr int TT = dy * HPI + dx + 2 * HPI * i;
                 const unsigned ad = am[TT & 15] ^ (g << 5);
@@ -744,7 +686,7 @@ __global__ __launch_bounds__(256, 2) void bneck_ds_kernel(const BneckDsArgs a) {
             });
         };
         load_x(std::integral_constant<int, 0>{}, xa[0]);
-        static_for_b<0, NU>([&](auto uc) {
+        static_for<0, NU>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             if constexpr (u + WD < NU) wf[(u + WD) % (WD + 1)] = load_w(u + WD);
             if constexpr (u + 1 < NU) load_x(std::integral_constant<int, u + 1>{}, xa[(u + 1) & 1]);
@@ -789,10 +731,10 @@ __global__ __launch_bounds__(256, 2) void bneck_ds_kernel(const BneckDsArgs a) {
         for (int pb = 0; pb < NPB; ++pb) {
             const int hpc = (2 * pb + prr + 1) * HPI + pcc + 1;
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) xd[pb][s2] = lds0 + XS_OFF + hpc * 64 + (((2 * s2 + hk) ^ swz64_b(hpc)) << 4);
+            for (int s2 = 0; s2 < 2; ++s2) xd[pb][s2] = lds0 + XS_OFF + hpc * 64 + (((2 * s2 + hk) ^ swz64(hpc)) << 4);
         }
         f32x16 acc[NPB], accd[NPB];
-        static_for_b<0, NU3>([&](auto uc) {
+        static_for<0, NU3>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             constexpr int q = u / NUQ, k = u % NUQ;
             const int ob = wave + 4 * q;

@@ -18,37 +18,13 @@
 
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wave_prims.h"
 
 using namespace lt;
 
 namespace {
 
 __device__ uint4 g_zero_page_2d[4];
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void dma16p(const void* src, unsigned lds_base) {
-    unsigned keep;
-    lds_base = __builtin_amdgcn_readfirstlane(lds_base);
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(lds_base)
-        : "memory");
-}
-
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void static_for_p(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        static_for_p<I0 + 1, I1>(f);
-    }
-}
 
 struct Halo2dPhase {
     const bf16_t* wfrag;     // lt_conv_pack_weights_t32 of this phase's [256][k_pad] weights (k = tap * 256 + ci)
@@ -105,7 +81,7 @@ __global__ __launch_bounds__(512, (TH == 8 ? 1 : 2)) void conv2d_halo_kernel(con
         const int ih = h0 - 1 + hh_, iw = w0 - 1 + hw_;
         const bool ok = ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
         const void* src = ok ? (const void*)(x + ((size_t)ih * a.W + iw) * CIN + (ps ^ swz(hh_, hw_)) * 8) : zero_page;
-        dma16p(src, lds0 + i * 1024);
+        dma16_uniform(src, lds0 + i * 1024);
     }
 
     // ---- roles: wave = output-channel block; fragment f = (row group i = f / CG, column group j = f % CG): pixel (4 i + vl / 8, 8 j + vl % 8) ----
@@ -163,7 +139,7 @@ __global__ __launch_bounds__(512, (TH == 8 ? 1 : 2)) void conv2d_halo_kernel(con
     // the halo pieces are the oldest vector-memory operations of this wave: wait for everything once, the barrier publishes the image
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
 
-    static_for_p<0, NPH>([&](auto pc) {
+    static_for<0, NPH>([&](auto pc) {
         constexpr int p = decltype(pc)::value;
         unsigned lp[NT][RG];                              // tap t, row group i: + j * 8 pixels as an immediate, K block g as XOR (g << 5)
 #pragma unroll
@@ -188,13 +164,13 @@ __global__ __launch_bounds__(512, (TH == 8 ? 1 : 2)) void conv2d_halo_kernel(con
         auto load_x = [&](auto uc, V16 (&dst)[FR]) {
             constexpr int u = decltype(uc)::value;
             constexpr int tap = u / G, g = u % G;
-            static_for_p<0, FR>([&](auto fc) {
+            static_for<0, FR>([&](auto fc) {
                 constexpr int f = decltype(fc)::value, i = f / CG, j = f % CG;
                 dst[f].u = *(const uint4*)((lptr_t)(size_t)((lp[tap][i] ^ (g << 5)) + j * 8 * PXB));
             });
         };
-        static_for_p<0, XL>([&](auto uc) { load_x(uc, xa[decltype(uc)::value % XS]); });
-        static_for_p<0, NU>([&](auto uc) {
+        static_for<0, XL>([&](auto uc) { load_x(uc, xa[decltype(uc)::value % XS]); });
+        static_for<0, NU>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             if constexpr (u + WD < NU) wf[(u + WD) % NS] = load_w(p, u + WD);
             else if constexpr (p + 1 < NPH) wf[(u + WD) % NS] = load_w(p + 1, u + WD - NU);    // the next phase's first fragments, under this phase's tail

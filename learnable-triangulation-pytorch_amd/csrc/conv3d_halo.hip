@@ -28,7 +28,7 @@
 
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wave_prims.h"
 
 #ifndef LT_ACC64_MASK
 #define LT_ACC64_MASK 3          // fp32 (parity) kernels: fp64 flush of the MFMA accumulators every LT_ACC64_MASK + 1 taps / K steps
@@ -44,54 +44,7 @@ __device__ uint4 g_zero_page_h[4];   // 64 zero bytes: DMA source of padding vox
 // profiling build: shader-clock accounting of the persistent kernel's per-tile phases, written by wave 0 of every 8th workgroup:
 // [total, top wait+barrier, halo issue, residual issue, tap loop, barrier, epilogue, tiles]
 __device__ long long g_trace_h[8 * 64];
-#define LT_CLKH() ((long long)__builtin_amdgcn_s_memtime())
 #endif
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void dma16h(const void* src, unsigned lds_base) {
-    unsigned keep;
-    lds_base = __builtin_amdgcn_readfirstlane(lds_base);   // wave-uniform by construction; make it provable
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(lds_base)
-        : "memory");
-}
-
-// ---- hand-scheduled LDS fragment reads -------------------------------------------------------------------------------------
-// hipcc's own s_waitcnt insertion degrades to lgkmcnt(0) as soon as more than one tap of fragment reads is in flight (seen
-// in the ISA: every third tap drained the whole queue).  The deep-lookahead paths therefore issue ds_read_b128 themselves
-// and wait with an explicit count; frag_ready() ties the wait to the registers so that no MFMA can be scheduled above it.
-template <int IMM>
-__device__ __forceinline__ void lds_read16(V16& d, unsigned addr) {
-    static_assert(IMM >= 0 && IMM < 65536, "ds_read offset field");
-    f32x4 t;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(t) : "v"(addr), "n"(IMM));
-    d.f = t;
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {
-    static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
-}
-__device__ __forceinline__ void frag_ready(V16& f) {
-    f32x4 t = f.f;   // a native vector: HIP's uint4 is a struct, which inline asm can only take indirectly
-    asm volatile("" : "+v"(t));
-    f.f = t;
-}
-
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        static_for<I0 + 1, I1>(f);
-    }
-}
 
 // swizzle constants {FA, FB, FC, FSH, pitch multiple}
 template <int KS, int CINB, int MF> struct HaloSwz { static constexpr int FA = 0, FB = 0, FC = 0, FSH = 1, PAD = 1; };   // (3, 64 B, 32x32)
@@ -137,28 +90,6 @@ struct HaloCfg {
         return (SW::FA * hh + SW::FB * hd + ((hw + SW::FC * hh) >> SW::FSH)) & (NVV - 1);
     }
 };
-
-// s_waitcnt vmcnt(n), n wave-uniform
-__device__ __forceinline__ void wait_vmcnt_h(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-        case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;   // conservative
-    }
-}
 
 #ifdef LT_ABL_NO_MMA
 #define LT_HMMA(c_, a_, b_) (void)0
@@ -410,7 +341,7 @@ __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const Halo
             const int id = d0 - P + hd_, ih = h0 - P + hh_, iw = w0 - P + hw_;
             const bool ok = hv < C::HV && hw_ < C::HW && ((unsigned)id < (unsigned)a.D) & ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
             const void* src = ok ? (const void*)(x + (((size_t)id * a.H + ih) * a.W + iw) * XLD + cph * CIN + lv * C::VEC) : zero_page;
-            dma16h(src, lds0 + i * 1024);
+            dma16_uniform(src, lds0 + i * 1024);
         }
 #endif
     };
@@ -428,7 +359,7 @@ __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const Halo
             const int lv = pv ^ ((-(col / VPR)) & (NVV - 1));
             const bool ok = tj < TPC && tap < C::NTAPS;
             const void* src = ok ? (const void*)(w + (size_t)col * a.k_pad + tap * XLD + cph * CIN + lv * C::VEC) : zero_page;
-            dma16h(src, lds0 + C::HALO_BYTES + buf * C::WCH + i * 1024);
+            dma16_uniform(src, lds0 + C::HALO_BYTES + buf * C::WCH + i * 1024);
         }
     };
 #ifdef LT_ABL_NO_B
@@ -446,7 +377,7 @@ __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const Halo
         for (int ch = 0; ch < C::NCH; ++ch) {
             int younger = C::NCH - 1 - ch;
             if (younger > NBUF - 2) younger = NBUF - 2;
-            wait_vmcnt_h(younger * dpc);
+            wait_vmcnt(younger * dpc);
             asm volatile("s_barrier" ::: "memory");
             if (ch + NBUF - 1 < C::NCH) stage_w(ch + NBUF - 1, (ch + NBUF - 1) % NBUF);
         }
@@ -577,7 +508,7 @@ __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const Halo
         int younger = C::NCH - 2 - ch;                                                                                  \
         if (younger > NBUF - 3) younger = NBUF - 3;                                                                     \
         if (younger < 0) younger = 0;                                                                                   \
-        wait_vmcnt_h(younger * dpc);                                                                                    \
+        wait_vmcnt(younger * dpc);                                                                                      \
         asm volatile("s_barrier" ::: "memory"); /* all waves: chunks <= ch+1 landed, chunk ch-1 fully consumed */       \
         if (ch + NBUF - 1 < C::NCH) stage_w(ch + NBUF - 1, (ch + NBUF - 1) % NBUF);                                     \
         const int coff = (((ch / KS) * C::HH + (ch % KS)) * C::PW) * CINB; /* bytes, wave-uniform */                    \
@@ -615,7 +546,7 @@ __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const Halo
             int younger = C::NCH - 2;
             if (younger > NBUF - 3) younger = NBUF - 3;
             if (younger < 0) younger = 0;
-            wait_vmcnt_h(younger * dpc);
+            wait_vmcnt(younger * dpc);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             static_for<0, PD>([&](auto tjc) { load_ring(0, lds_w, tjc); });
         }
@@ -638,7 +569,7 @@ __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const Halo
             // chunk ch (and, the first time, the halo issued before it) must have landed; up to NBUF-2 younger chunks stay in flight
             int younger = C::NCH - 1 - ch;
             if (younger > NBUF - 2) younger = NBUF - 2;
-            if (!LDR) wait_vmcnt_h(younger * dpc);
+            if (!LDR) wait_vmcnt(younger * dpc);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // all waves: chunk ch landed, chunk ch-1 fully consumed
             if (!LDR && ch + NBUF - 1 < C::NCH) stage_w(ch + NBUF - 1, (ch + NBUF - 1) % NBUF);
             // per-chunk scalar parts
@@ -799,7 +730,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_persist_kernel(const HaloArgs
             const int id = d0 - P + hd_, ih = h0 - P + hh_, iw = w0 - P + hw_;
             const bool ok = hv < C::HV && hw_ < C::HW && ((unsigned)id < (unsigned)a.D) & ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
             const void* src = ok ? (const void*)(x + (((size_t)id * a.H + ih) * a.W + iw) * CIN + lv * C::VEC) : zero_page;
-            dma16h(src, lds_halo + buf * C::HALO_BYTES + i * 1024);
+            dma16_uniform(src, lds_halo + buf * C::HALO_BYTES + i * 1024);
         }
     };
 
@@ -810,7 +741,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_persist_kernel(const HaloArgs
         const int pv = q % NVV, col = (q / NVV) % CP, tap = q / (NVV * CP);
         const int lv = pv ^ ((-(col / VPR)) & (NVV - 1));
         const void* src = tap < C::NTAPS ? (const void*)(w + (size_t)col * a.k_pad + tap * CIN + lv * C::VEC) : zero_page;
-        dma16h(src, lds0 + i * 1024);
+        dma16_uniform(src, lds0 + i * 1024);
     }
 
     int v = blockIdx.x;
@@ -819,8 +750,8 @@ __global__ __launch_bounds__(512) void conv3d_halo_persist_kernel(const HaloArgs
 
 #ifdef LT_TRACE
     long long tr[7] = {0, 0, 0, 0, 0, 0, 0};
-    const long long tr_begin = LT_CLKH();
-#define LT_TRH(k_) { const long long c_ = LT_CLKH(); tr[k_] += c_ - tr_last; tr_last = c_; }
+    const long long tr_begin = LT_CLK();
+#define LT_TRH(k_) { const long long c_ = LT_CLK(); tr[k_] += c_ - tr_last; tr_last = c_; }
     long long tr_last = tr_begin;
 #else
 #define LT_TRH(k_)
@@ -1002,7 +933,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_persist_kernel(const HaloArgs
 #ifdef LT_TRACE
     if (wave == 0 && lane == 0 && (blockIdx.x & 7) == 0 && (blockIdx.x >> 3) < 64) {
         long long* o = g_trace_h + (blockIdx.x >> 3) * 8;
-        o[0] = LT_CLKH() - tr_begin;
+        o[0] = LT_CLK() - tr_begin;
         for (int k = 1; k < 7; ++k) o[k] = tr[k];
         o[7] = tr[0];
     }
@@ -1082,7 +1013,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, 
         const int pv = q % NVV, col = (q / NVV) % CP, tap = q / (NVV * CP);
         const int lv = pv ^ ((-(col / VPR)) & (NVV - 1));
         const void* src = tap < C::NTAPS ? (const void*)(w + (size_t)col * a.k_pad + tap * CIN + lv * C::VEC) : zero_page;
-        dma16h(src, lds0 + i * 1024);
+        dma16_uniform(src, lds0 + i * 1024);
     }
 
     if (loader) {
@@ -1131,7 +1062,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, 
 #ifdef LT_ABL_NO_A
                     if (a.N < 0)
 #endif
-                    dma16h(src, dst + (wl + 4 * m) * 1024);
+                    dma16_uniform(src, dst + (wl + 4 * m) * 1024);
                 }
             }
             ++issued;
@@ -1146,7 +1077,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, 
         const int ntile = ncol * tpc;
         for (int ti = 0; ti < ntile; ++ti) {
             const int ahead = issued - sidx - 2;          // groups requested beyond the two this tile reads: 0, 1 or 2
-            wait_vmcnt_h(ahead > 0 ? ahead * mine : 0);
+            wait_vmcnt(ahead > 0 ? ahead * mine : 0);
             asm volatile("s_barrier" ::: "memory");       // A: groups sidx, sidx + 1 landed; the consumers are done with tile ti - 1
             while (issued <= sidx + 3 && issued < total_groups) issue_next();
             ++sidx;
@@ -1338,9 +1269,9 @@ __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, 
     }
 #ifdef LT_TRACE
     long long tr[7] = {0, 0, 0, 0, 0, 0, 0};
-    const long long tr_begin = LT_CLKH();
+    const long long tr_begin = LT_CLK();
     long long tr_last = tr_begin;
-#define LT_TRC(k_) { const long long c_ = LT_CLKH(); tr[k_] += c_ - tr_last; tr_last = c_; }
+#define LT_TRC(k_) { const long long c_ = LT_CLK(); tr[k_] += c_ - tr_last; tr_last = c_; }
 #else
 #define LT_TRC(k_)
 #endif
@@ -1395,7 +1326,7 @@ __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, 
 #ifdef LT_TRACE
     if (wave == 0 && lane == 0 && (blockIdx.x & 7) == 0 && (blockIdx.x >> 3) < 64) {   // same record as the persistent kernel
         long long* o = g_trace_h + (blockIdx.x >> 3) * 8;
-        o[0] = LT_CLKH() - tr_begin;
+        o[0] = LT_CLK() - tr_begin;
         for (int q = 1; q < 7; ++q) o[q] = tr[q];
         o[7] = ntile;
     }
@@ -1468,7 +1399,7 @@ __global__ __launch_bounds__(256, (CIN == 128 ? 1 : CIN == 16 ? 4 : 2)) void con
         const int id = d0 - 1 + hd_, ih = h0 - 1 + hh_, iw = w0 - 1 + hw_;
         const bool ok = hv < C::HV && ((unsigned)id < (unsigned)a.D) & ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
         const void* src = ok ? (const void*)(x + (((size_t)id * a.H + ih) * a.W + iw) * CIN + lv * C::VEC) : zero_page;
-        dma16h(src, lds0 + i * 1024);
+        dma16_uniform(src, lds0 + i * 1024);
     }
 
     // ---- roles ----
@@ -1688,7 +1619,7 @@ __global__ __launch_bounds__(512) void conv3d_halo7b_kernel(const HaloArgs a) {
             const int id = d0 - P + hd_, ih = h0 - P + hh_, iw = w0 - P + hw_;
             const bool ok = hv < C::HV && hw_ < C::HW && ((unsigned)id < (unsigned)a.D) & ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
             const void* src = ok ? (const void*)(x + (((size_t)id * a.H + ih) * a.W + iw) * CIN + lv * C::VEC) : zero_page;
-            dma16h(src, lds0 + i * 1024);
+            dma16_uniform(src, lds0 + i * 1024);
         }
         // chunk c = (kh, kw): slab kd is tap kd*49 + c; this loader carries kd = wl (and wl + 4 when < 7)
         const int pv = lane % NVV, col = lane / NVV;
@@ -1699,8 +1630,8 @@ __global__ __launch_bounds__(512) void conv3d_halo7b_kernel(const HaloArgs a) {
         const int dpc = two ? 2 : 1;
         auto stage_w = [&](int c) {
             const unsigned dst = lds_w + (c % NBUF) * C::WCH;
-            dma16h(wsrc0 + (size_t)c * CIN, dst + wl * 1024);
-            if (two) dma16h(wsrc1 + (size_t)c * CIN, dst + (wl + 4) * 1024);
+            dma16_uniform(wsrc0 + (size_t)c * CIN, dst + wl * 1024);
+            if (two) dma16_uniform(wsrc1 + (size_t)c * CIN, dst + (wl + 4) * 1024);
         };
 #pragma unroll
         for (int c = 0; c < NBUF - 1; ++c) stage_w(c);
@@ -1709,7 +1640,7 @@ __global__ __launch_bounds__(512) void conv3d_halo7b_kernel(const HaloArgs a) {
             int younger = NCH - 2 - c;
             if (younger > NBUF - 3) younger = NBUF - 3;
             if (younger < 0) younger = 0;
-            wait_vmcnt_h(younger * dpc);
+            wait_vmcnt(younger * dpc);
             asm volatile("s_barrier" ::: "memory");
             if (c + NBUF - 1 < NCH) stage_w(c + NBUF - 1);
         }

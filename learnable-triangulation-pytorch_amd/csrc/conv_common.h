@@ -1,5 +1,8 @@
-// Shared pieces of the implicit-GEMM convolution kernels (conv_igemm.hip = register-staged v1,
-// conv_igemm2.hip = LDS-DMA staged v2 with the LDS-transposed vector epilogue).
+// Shared pieces of the implicit-GEMM and halo convolution kernels: the kernel-side argument block (ConvArgs), the host predicates that say which
+// layers a kernel family covers, the MFMA wrappers per operand type and tile shape, and the entry points of every family for the dispatcher in
+// conv_igemm.hip (register-staged v1): conv_igemm2 (LDS-DMA staged, LDS-transposed vector epilogue), conv_igemm3 (288-row tiles: v3 / v5 / v6),
+// conv_igemm7 (288 x 256 on 32x32x16 MFMAs), conv_pw (single-tap streaming), conv2d_halo and conv3d_halo (input halo resident in LDS).
+// The wave-level asm primitives these kernels share live in wave_prims.h, which includes this header.
 #pragma once
 #include "lt_common.h"
 
@@ -72,6 +75,15 @@ inline bool halo_col_fits(long long N, int D, int H, int W) {
     if (D % 4 || H % 8 || W % 8) return false;
     const long long nblk = N * (D / 4) * (H / 8) * (W / 8), cols = N * (H / 8) * (W / 8);
     return nblk >= 1024 && nblk % 8 == 0 && D / 4 >= 2 && cols % 8 == 0 && cols >= 256;
+}
+
+// The "plain pointwise" layer: its one phase has one tap at offset 0, unit strides, no padding, an output grid equal to the input grid, and dense K
+// (k_pad == Cin) -- GEMM row m is input pixel m, so the kernels' pointwise modes need no tap table.  (A caller with several phases asks per phase.)
+inline bool plain_pointwise(const ConvArgs& a) {
+    const PhaseArg& p0 = a.phase[0];
+    return p0.ntaps == 1 && a.sd == 1 && a.sh == 1 && a.sw == 1 && a.pd == 0 && a.ph == 0 && a.pw == 0 && a.osd == 1 && a.osh == 1 && a.osw == 1 &&
+           p0.ood == 0 && p0.ooh == 0 && p0.oow == 0 && a.OD == a.Do && a.OH == a.Ho && a.OW == a.Wo && a.D == a.Do && a.H == a.Ho && a.W == a.Wo &&
+           a.k_pad == a.Cin;
 }
 
 // The layers conv2d_halo_kernel covers, whatever the weights and extra sources: 256 -> 256 dense channels, maps whose width is a multiple of 24 and

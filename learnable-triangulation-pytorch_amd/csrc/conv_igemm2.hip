@@ -20,7 +20,7 @@
 
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wave_prims.h"
 
 // fp32 (parity) kernels: the MFMA accumulators are added into fp64 registers every LT_ACC64_MASK + 1 K steps of 32 products
 #ifndef LT_ACC64_MASK
@@ -37,43 +37,7 @@ __device__ uint4 g_zero_page[2];  // source of out-of-image taps
 // -DLT_TRACE (profiling build, lt_build.build_variant): shader-clock accounting of the K loop phases, summed per wave and
 // written by wave 0 of every 32nd workgroup: [total, wait_vmcnt, barrier, dma_issue, compute, nk, realtime_100MHz, blockIdx]
 __device__ long long g_trace[8 * 1024];
-#define LT_CLK() ((long long)__builtin_amdgcn_s_memtime())
 #endif
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// one LDS-DMA wave-instruction: 64 lanes x 16 B -> lds_base .. lds_base + 1 KiB (wave-uniform base)
-__device__ __forceinline__ void dma16(const void* src, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(lds_base)
-        : "memory");
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform n (the immediate must be a literal)
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;  // conservative
-    }
-}
 
 __device__ __forceinline__ void block_barrier() {
     // LDS reads of this wave are consumed (lgkmcnt(0)) before it releases the buffer to the next DMA
@@ -650,10 +614,7 @@ int dispatch2(const ConvArgs& a, int cout_pad, int nphase, int max_taps, int til
     // M=18432, N=256 layer ran 1.6x slower than 576 of 128x64)
     auto blocks = [&](int bm, int bn) { return cdiv(a.M, bm) * (long long)(cout_pad / bn) * nphase; };
     // pointwise fast path: one tap at offset 0, unit strides, dense output rows
-    const PhaseArg& p0 = a.phase[0];
-    const bool pw = nphase == 1 && p0.ntaps == 1 && a.sd == 1 && a.sh == 1 && a.sw == 1 && a.pd == 0 && a.ph == 0 && a.pw == 0 &&
-                    a.osd == 1 && a.osh == 1 && a.osw == 1 && p0.ood == 0 && p0.ooh == 0 && p0.oow == 0 && a.OD == a.Do && a.OH == a.Ho &&
-                    a.OW == a.Wo && a.D == a.Do && a.H == a.Ho && a.W == a.Wo && a.k_pad == a.Cin;
+    const bool pw = nphase == 1 && plain_pointwise(a);
     if (tile == LT_TILE_AUTO) {
         static const int minblk = getenv("LT_CONV2_MINBLK") ? atoi(getenv("LT_CONV2_MINBLK")) : 480;          // tuning knob
         if (cout_pad <= 16) tile = LT_TILE2_256x16;

@@ -23,7 +23,7 @@
 
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wave_prims.h"
 
 using namespace lt;
 
@@ -33,65 +33,7 @@ __device__ uint4 g_zero_page3[2];
 
 #ifdef LT_TRACE
 __device__ long long g_trace3[8 * 1024];
-#define LT_CLK3() ((long long)__builtin_amdgcn_s_memtime())
 #endif
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void dma16(const void* src, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(lds_base)
-        : "memory");
-}
-
-__device__ __forceinline__ void wait_vmcnt3(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;  // conservative
-    }
-}
-
-template <int IMM>
-__device__ __forceinline__ void lds_read16(V16& d, unsigned addr) {
-    static_assert(IMM >= 0 && IMM < 65536, "ds_read offset field");
-    f32x4 t;   // a native vector (HIP's uint4 is a struct, which inline asm can only take indirectly)
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(t) : "v"(addr), "n"(IMM));
-    d.f = t;
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {
-    static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
-}
-__device__ __forceinline__ void frag_ready(V16& f) {
-    f32x4 t = f.f;
-    asm volatile("" : "+v"(t));
-    f.f = t;
-}
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        static_for<I0 + 1, I1>(f);
-    }
-}
 
 constexpr int BM3 = 288;
 
@@ -308,30 +250,30 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
 
 #ifdef LT_TRACE
     long long tr_vm = 0, tr_bar = 0, tr_iss = 0, tr_cmp = 0, tr_prev = 0;
-    const long long tr_begin = LT_CLK3();
+    const long long tr_begin = LT_CLK();
     const long long tr_rt0 = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
     for (int ks = 0; ks < nk; ++ks) {
 #ifdef LT_TRACE
-        const long long tr0 = LT_CLK3();
+        const long long tr0 = LT_CLK();
         if (ks > 0) tr_cmp += tr0 - tr_prev;
 #endif
         // stage ks must have landed; stage ks+1 (this wave's dps pieces, if it exists) may stay in flight
-        wait_vmcnt3(ks + 1 < nk ? dps : 0);
+        wait_vmcnt(ks + 1 < nk ? dps : 0);
 #ifdef LT_TRACE
-        const long long tr1 = LT_CLK3();
+        const long long tr1 = LT_CLK();
         tr_vm += tr1 - tr0;
 #endif
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // all DMAs of stage ks landed; stage ks-1 fully consumed
 #ifdef LT_TRACE
-        const long long tr2 = LT_CLK3();
+        const long long tr2 = LT_CLK();
         tr_bar += tr2 - tr1;
 #endif
         const bool more = ks + 2 < nk;
         const int nbuf = (ks + 2) % NST;
         if (more) stage_prep(ks + 2);                    // tap table read here, while no fragment read is in flight
 #ifdef LT_TRACE
-        const long long tr3 = LT_CLK3();
+        const long long tr3 = LT_CLK();
         tr_iss += tr3 - tr2;
         tr_prev = tr3;
 #endif
@@ -373,7 +315,7 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
     }
 #ifdef LT_TRACE
     {
-        const long long tr_end = LT_CLK3();
+        const long long tr_end = LT_CLK();
         tr_cmp += tr_end - tr_prev;
         const long long tr_rt1 = (long long)__builtin_amdgcn_s_memrealtime();
         if (wave == 0 && (blockIdx.x & 7) == 0 && (blockIdx.x >> 3) < 1024 && lane == 0) {
@@ -444,8 +386,6 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
 // 64-byte rows: a 16-byte slot holds K vector (slot ^ g(row)), g = [0,2,3,1][(row >> 2) & 3] -- with that the four 16-lane groups
 // of a ds_read_b128 fragment read (rows r, K vector lane >> 4) each touch all 64 banks once (checked by enumeration, comment in
 // DESIGN.md); the DMA writes lane-linearly, so the swizzle is applied to the source address as everywhere else.
-__device__ __forceinline__ int swz64(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
-
 template <int MODE>
 __global__ __launch_bounds__(512) void conv_igemm5_kernel(const ConvArgs a) {
     typedef bf16_t T;
@@ -577,7 +517,7 @@ __global__ __launch_bounds__(512) void conv_igemm5_kernel(const ConvArgs a) {
         // stage ks must have landed; up to NST-2 younger stages of this wave's pieces stay in flight
         int younger = nk - 1 - ks;
         if (younger > NST - 2) younger = NST - 2;
-        wait_vmcnt3(younger * dps);
+        wait_vmcnt(younger * dps);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // all DMAs of stage ks landed; stage ks-1 fully consumed
         const bool more = ks + NST - 1 < nk;
         const int nbuf = (ks + NST - 1) % NST;
@@ -681,27 +621,6 @@ __global__ __launch_bounds__(512) void conv_igemm5_kernel(const ConvArgs a) {
 // per stage, six stages in 108 KB, and half the LDS fragment reads.  Everything else (tile, waves, sliced DMA issue, read
 // stream with counted lgkmcnt, epilogue) is conv_igemm5's.  The K loop is unrolled by two because the two B register sets
 // alternate (k_pad is a multiple of 64, so the number of 32-element steps is even).
-// wave-uniform base in SGPRs + 32-bit lane offset + immediate: no 64-bit address arithmetic in VGPRs
-template <int IMM>
-__device__ __forceinline__ void gload16(V16& d, const void* sbase, unsigned voff) {
-    static_assert(IMM >= 0 && IMM < 4096, "global_load immediate offset");
-    f32x4 t;
-    const unsigned long long b = (unsigned long long)(size_t)sbase;
-    const unsigned long long ub = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                                  (unsigned)__builtin_amdgcn_readfirstlane((int)b);   // uniform by construction; make it provable
-    // s_nop: the base may have just been written by v_readfirstlane, and a VALU write of an SGPR needs 5 wait states before a
-    // vector-memory instruction reads it -- the hazard recognizer does not look inside inline asm (seen: the load took the
-    // stale low dword and faulted)
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(t) : "v"(voff), "s"(ub), "n"(IMM) : "memory");
-    d.f = t;
-}
-__device__ __forceinline__ void wait_vmcnt6(int n) {
-    switch (n) {
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        default: wait_vmcnt3(n); break;
-    }
-}
 
 // NWM = 2: 288-row tile, eight waves, one workgroup per CU; NWM = 1: 144-row tile, four waves, TWO workgroups per CU (55 KB ring each):
 // the short-K pointwise layers are mostly epilogue traffic, and a second workgroup's K loop overlaps it.
@@ -909,14 +828,14 @@ __global__ __launch_bounds__(256 * NWM, 2) void conv_igemm6_kernel(const ConvArg
     unsigned rbuf = 0, wbuf = AHEAD * STAGE;              // ring offsets of the stage being read / being requested
 #ifdef LT_TRACE
     long long tr_vm = 0, tr_bar = 0, tr_iss = 0, tr_cmp = 0, tr_prev = 0;
-    const long long tr_begin = LT_CLK3();
+    const long long tr_begin = LT_CLK();
     const long long tr_rt0 = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
     const bool YW = PP && wm == 1;                        // a "Y" wave of the ping-pong (wave-uniform: scalar branches around the barriers)
     auto step = [&](int ks, auto rc) {
         constexpr int R = decltype(rc)::value;           // ks % NBS: which B register set this step multiplies with
 #ifdef LT_TRACE
-        const long long tr0 = LT_CLK3();
+        const long long tr0 = LT_CLK();
         if (ks > 0) tr_cmp += tr0 - tr_prev;
 #endif
         // needed now: B(ks) and, older, stage ks.  The queue, oldest first: prologue [B(0 .. BPF-1) | stages 0 .. P-1], then per step j
@@ -933,16 +852,16 @@ __global__ __launch_bounds__(256 * NWM, 2) void conv_igemm6_kernel(const ConvArg
             if (after < 0) after = 0;
             for (int j = 0; j < ks; ++j) after += lb + pieces_of(j);
         }
-        wait_vmcnt6(after);                                // (> 12: waits for everything; only possible in the first steps)
+        wait_vmcnt(after);                                // (> 12: waits for everything; only possible in the first steps)
 #ifdef LT_TRACE
-        const long long tr1 = LT_CLK3();
+        const long long tr1 = LT_CLK();
         tr_vm += tr1 - tr0;
 #endif
         // X (and every wave without ping-pong): stage ks landed for every wave (each waited for its own pieces above; a wave's wait
         // at the top of step j covers its pieces up to stage j + AHEAD - BPF, so Y's wait at the top of ITS step ks-1 covered stage ks)
         if (!YW) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #ifdef LT_TRACE
-        const long long tr2 = LT_CLK3();
+        const long long tr2 = LT_CLK();
         tr_bar += tr2 - tr1;
 #endif
 #pragma unroll
@@ -954,7 +873,7 @@ __global__ __launch_bounds__(256 * NWM, 2) void conv_igemm6_kernel(const ConvArg
         const bool more = !ABL_A && ks + AHEAD < nk;
         if (more) stage_prep(ks + AHEAD);
 #ifdef LT_TRACE
-        const long long tr3 = LT_CLK3();                  // B loads + tap bookkeeping
+        const long long tr3 = LT_CLK();                  // B loads + tap bookkeeping
         tr_iss += tr3 - tr2;
         tr_prev = tr3;
 #endif
@@ -987,7 +906,7 @@ __global__ __launch_bounds__(256 * NWM, 2) void conv_igemm6_kernel(const ConvArg
         wbuf = wbuf + STAGE == REGION ? 0 : wbuf + STAGE;
     };
     if (YW) {   // Y's barrier 0 (X: top of step 0): vouch for the own pieces of stage 0 first, like X does at the top of its step 0
-        wait_vmcnt6(((nk < AHEAD ? nk : AHEAD) - 1) * dps);
+        wait_vmcnt(((nk < AHEAD ? nk : AHEAD) - 1) * dps);
         asm volatile("s_barrier" ::: "memory");
     }
     if constexpr (NBS == 2) {
@@ -1011,7 +930,7 @@ __global__ __launch_bounds__(256 * NWM, 2) void conv_igemm6_kernel(const ConvArg
     }
 #ifdef LT_TRACE
     {   // same record as conv_igemm3_kernel: total, vmcnt wait, barrier, issue (B loads), fragment reads + MFMAs + DMA issue, steps, 100 MHz ticks
-        const long long tr_end = LT_CLK3();
+        const long long tr_end = LT_CLK();
         tr_cmp += tr_end - tr_prev;
         const long long tr_rt1 = (long long)__builtin_amdgcn_s_memrealtime();
         if (wave == 0 && (blockIdx.x & 7) == 0 && (blockIdx.x >> 3) < 1024 && lane == 0) {
@@ -1175,44 +1094,38 @@ int conv3_try(int dtype, const ConvArgs& a, int cout_pad, int nphase, int max_ta
     // 1.5x slower than the 128x64 tile of conv_igemm2 on the 64-channel level
     const int BN = cout_pad % 128 == 0 ? 128 : ((cout_pad == 64 && forced) ? 64 : 0);
     if (!BN) return 0;
+    const bool pw = plain_pointwise(a);
     // 288 x 256 tile (v5): Cout a multiple of 256 and enough 288-row tiles to give every CU one (LT_CONV_V5=0/1 forces it off/on)
     {
         const char* v5e = getenv("LT_CONV_V5");
         const long long tiles_m5 = cdiv(a.M, BM3), nblk5 = tiles_m5 * (cout_pad / 256);
         const bool fits5 = cout_pad % 256 == 0 && a.k_pad % 32 == 0 && max_taps <= 64;
         const PhaseArg& q0 = a.phase[0];
-        const bool pw5 = q0.ntaps == 1 && a.sd == 1 && a.sh == 1 && a.sw == 1 && a.pd == 0 && a.ph == 0 && a.pw == 0 && a.osd == 1 &&
-                         a.osh == 1 && a.osw == 1 && q0.ood == 0 && q0.ooh == 0 && q0.oow == 0 && a.OD == a.Do && a.OH == a.Ho &&
-                         a.OW == a.Wo && a.D == a.Do && a.H == a.Ho && a.W == a.Wo && a.k_pad == a.Cin;
         const bool no6 = env_on("LT_CONV_NO_V6");   // A/B, read per call
         // small batches (the reference trains at 5 samples = 20 images): the short-K expand layers still fill the chip with the 144-row variant of
         // conv_igemm6 (two workgroups per CU) when the 288-row count says no -- 256 -> 1024 at 20 images: 320 tiles of 144 x 256 instead of
         // 1440 L2-stream-bound 128 x 64 tiles of the generic kernel (LT_CONV_NO_SMALL144=1: off)
-        const bool small144 = pw5 && q0.wfrag && !no6 && a.k_pad % 64 == 0 && a.k_pad <= 256 && a.M % 144 == 0 && (a.M / 144) * (cout_pad / 256) >= 200 &&
+        const bool small144 = pw && q0.wfrag && !no6 && a.k_pad % 64 == 0 && a.k_pad <= 256 && a.M % 144 == 0 && (a.M / 144) * (cout_pad / 256) >= 200 &&
                               !env_on("LT_CONV_NO_SMALL144");
         const bool want5 = v5e ? v5e[0] == '1' : ((nblk5 >= 200 && tiles_m5 * BM3 - a.M <= a.M / 16 && a.k_pad >= 64) || small144);
         if (fits5 && want5) {
             if (q0.wfrag32 && a.k_pad % 64 == 0) {       // weights packed for the 32x32x16 MFMA (plan built with LT_CONV_V7=1): conv_igemm7
-                const int rc7 = conv7_try(a, cout_pad, max_taps, pw5, s);
+                const int rc7 = conv7_try(a, cout_pad, max_taps, pw, s);
                 if (rc7 != 0) return rc7;
             }
             if (q0.wfrag && !no6 && a.k_pad % 64 == 0) {  // weights also available in fragment order: B operand from registers
                 // short-K pointwise layers (the 1x1 expands): 144-row tiles, two workgroups per CU (LT_CONV_V6_BM144=0/1 forces it off/on)
                 const char* e144 = getenv("LT_CONV_V6_BM144");
-                const bool bm144 = e144 ? e144[0] == '1' : (pw5 && a.k_pad <= 256 && a.M % 144 == 0);
+                const bool bm144 = e144 ? e144[0] == '1' : (pw && a.k_pad <= 256 && a.M % 144 == 0);
                 int rc6;
-                if (bm144) rc6 = pw5 ? launch6<1, 1>(a, cout_pad, max_taps, s) : launch6<2, 1>(a, cout_pad, max_taps, s);
-                else rc6 = pw5 ? launch6<1, 2>(a, cout_pad, max_taps, s) : launch6<2, 2>(a, cout_pad, max_taps, s);
+                if (bm144) rc6 = pw ? launch6<1, 1>(a, cout_pad, max_taps, s) : launch6<2, 1>(a, cout_pad, max_taps, s);
+                else rc6 = pw ? launch6<1, 2>(a, cout_pad, max_taps, s) : launch6<2, 2>(a, cout_pad, max_taps, s);
                 return rc6 == LT_OK ? 1 : rc6;
             }
-            const int rc5 = pw5 ? launch5<1>(a, cout_pad, max_taps, s) : launch5<2>(a, cout_pad, max_taps, s);
+            const int rc5 = pw ? launch5<1>(a, cout_pad, max_taps, s) : launch5<2>(a, cout_pad, max_taps, s);
             return rc5 == LT_OK ? 1 : rc5;
         }
     }
-    const PhaseArg& p0 = a.phase[0];
-    const bool pw = p0.ntaps == 1 && a.sd == 1 && a.sh == 1 && a.sw == 1 && a.pd == 0 && a.ph == 0 && a.pw == 0 && a.osd == 1 &&
-                    a.osh == 1 && a.osw == 1 && p0.ood == 0 && p0.ooh == 0 && p0.oow == 0 && a.OD == a.Do && a.OH == a.Ho && a.OW == a.Wo &&
-                    a.D == a.Do && a.H == a.Ho && a.W == a.Wo && a.k_pad == a.Cin;
     if (!forced) {
         // one workgroup per CU: worth it from about one round of the chip (below that the 64x64 / 128x64 tiles spread better),
         // and only when the 288-row tiles leave little of the last one empty

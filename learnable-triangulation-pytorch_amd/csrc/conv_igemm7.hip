@@ -18,85 +18,13 @@
 
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wave_prims.h"
 
 using namespace lt;
 
 namespace {
 
 __device__ uint4 g_zero_page7[2];
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void dma16(const void* src, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(lds_base)
-        : "memory");
-}
-
-__device__ __forceinline__ void wait_vmcnt7(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;  // conservative
-    }
-}
-
-template <int IMM>
-__device__ __forceinline__ void lds_read16(V16& d, unsigned addr) {
-    static_assert(IMM >= 0 && IMM < 65536, "ds_read offset field");
-    f32x4 t;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(t) : "v"(addr), "n"(IMM));
-    d.f = t;
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {
-    static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
-}
-__device__ __forceinline__ void frag_ready(V16& f) {
-    f32x4 t = f.f;
-    asm volatile("" : "+v"(t));
-    f.f = t;
-}
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        static_for<I0 + 1, I1>(f);
-    }
-}
-// wave-uniform base in SGPRs + 32-bit lane offset + immediate (see conv_igemm3.hip gload16: s_nop for the readfirstlane hazard)
-template <int IMM>
-__device__ __forceinline__ void gload16(V16& d, const void* sbase, unsigned voff) {
-    static_assert(IMM >= 0 && IMM < 4096, "global_load immediate offset");
-    f32x4 t;
-    const unsigned long long b = (unsigned long long)(size_t)sbase;
-    const unsigned long long ub = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                                  (unsigned)__builtin_amdgcn_readfirstlane((int)b);
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(t) : "v"(voff), "s"(ub), "n"(IMM) : "memory");
-    d.f = t;
-}
-
-__device__ __forceinline__ int swz64_7(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
 
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void conv_igemm7_kernel(const ConvArgs a) {
@@ -136,7 +64,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm7_kernel(const ConvArgs a) {
     const T* __restrict__ x = (const T*)a.x;
 
     const int prow = lane >> 2;
-    const int kv = (lane & 3) ^ swz64_7(prow);
+    const int kv = (lane & 3) ^ swz64(prow);
     const bool a_tail = wave < NPA % NW;                 // waves 0, 1 own a third piece
     const int dps = (A_IT - 1) + (a_tail ? 1 : 0);       // 3 or 2 DMA pieces per wave and stage
     int id0[PW ? 1 : A_IT], ih0[PW ? 1 : A_IT], iw0[PW ? 1 : A_IT], baseC[A_IT], cur[PW ? 1 : A_IT], base2[PW2 ? A_IT : 1];
@@ -207,8 +135,8 @@ __global__ __launch_bounds__(512, 2) void conv_igemm7_kernel(const ConvArgs a) {
 
     // A fragment of row block i, K half kk: lane (r = lane & 31, h = lane >> 5) reads row 32 i + r, K vector 2 kk + h
     const int r31 = lane & 31, hk = lane >> 5;
-    const unsigned fo0 = r31 * ROWB + (((0 + hk) ^ swz64_7(r31)) << 4);   // kk = 0
-    const unsigned fo1 = r31 * ROWB + (((2 + hk) ^ swz64_7(r31)) << 4);   // kk = 1
+    const unsigned fo0 = r31 * ROWB + (((0 + hk) ^ swz64(r31)) << 4);   // kk = 0
+    const unsigned fo1 = r31 * ROWB + (((2 + hk) ^ swz64(r31)) << 4);   // kk = 1
 
     acc_t acc[SM];
 #pragma unroll
@@ -232,7 +160,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm7_kernel(const ConvArgs a) {
     auto step = [&](int ks, auto rc) {
         constexpr int R = decltype(rc)::value;
         const int after = ks == 0 ? ((nk < AHEAD ? nk : AHEAD) - 1) * dps : (ks + AHEAD - 1 < nk ? dps : 0);
-        wait_vmcnt7(after);                               // B(ks) and, older, this wave's pieces of stage ks
+        wait_vmcnt(after);                               // B(ks) and, older, this wave's pieces of stage ks
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         frag_ready(fb[R][0]); frag_ready(fb[R][1]);
         {

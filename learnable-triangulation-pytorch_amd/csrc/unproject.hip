@@ -15,7 +15,7 @@
 
 #include <type_traits>
 
-#include "lt_common.h"
+#include "wave_prims.h"
 
 using namespace lt;
 
@@ -85,14 +85,6 @@ template <> struct ChVec<bf16_t, 1> {
     static __device__ __forceinline__ void ld(const bf16_t* p, float (&f)[1]) { f[0] = bf16_to_f32(*p); }
     static __device__ __forceinline__ void st(bf16_t* p, const float (&f)[1]) { *p = f32_to_bf16(f[0]); }
 };
-
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void static_for_views(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        static_for_views<I0 + 1, I1>(f);
-    }
-}
 
 struct UnprojArgs {
     const void* feats;
@@ -474,7 +466,7 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
                 val[V][d] = pk_fma(f11, W11, pk_fma(f10, W10, pk_fma(f01, W01, f00 * W00)));
             }
         };
-        static_for_views<0, NV>(view);
+        static_for<0, NV>(view);
 
         // ---- softmax over the views per channel: sum_v x_v softmax_v(x) = (sum_v x_v e_v) / (sum_v e_v) ----
         unsigned o[4];
@@ -487,13 +479,13 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
             f32x2_t m[4], s[4], tt[4];
 #pragma unroll
             for (int d = 0; d < 4; ++d) { m[d] = f32x2_t{-INFINITY, -INFINITY}; s[d] = f32x2_t{0.f, 0.f}; tt[d] = f32x2_t{0.f, 0.f}; }
-            static_for_views<0, NV>([&](auto vc) {       // fmaxf(-inf, x) = x: the first valid view starts the max, as view 0 does below
+            static_for<0, NV>([&](auto vc) {       // fmaxf(-inf, x) = x: the first valid view starts the max, as view 0 does below
                 constexpr int V = decltype(vc)::value;
                 if (!((mbits >> V) & 1u)) return;
 #pragma unroll
                 for (int d = 0; d < 4; ++d) { m[d][0] = fmaxf(m[d][0], val[V][d][0]); m[d][1] = fmaxf(m[d][1], val[V][d][1]); }
             });
-            static_for_views<0, NV>([&](auto vc) {
+            static_for<0, NV>([&](auto vc) {
                 constexpr int V = decltype(vc)::value;
                 if (!((mbits >> V) & 1u)) return;
 #pragma unroll

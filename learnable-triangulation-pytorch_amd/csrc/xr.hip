@@ -35,15 +35,13 @@
 
 #include <type_traits>
 
-#include "conv_common.h"
+#include "wave_prims.h"
 
 using namespace lt;
 
 namespace {
 
 __device__ uint4 g_zero_page_x[2];
-
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // -DLT_XR_TRACE: shader-clock stamps of every wave of the first LT_XR_TRACE_WG workgroups (profiling builds only: lt_build.build_variant; read back with
 // lt_xr_trace_read, tools/xr_bench.py --trace).  Slot 0: entry, 1: t2 tile + constants in LDS; chunk c: 2 + 3 c, 3 + 3 c, 4 + 3 c (see the two roles).
@@ -70,27 +68,6 @@ struct XrArgs {
     const float* consts;                     // optional: [sc3 | sh3 | sc1 | sh1] back to back (16-byte aligned)
     int M, tile0;                            // rows; first tile of this launch
 };
-
-__device__ __forceinline__ void dma16x(const void* src, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(src), "s"(lds_base)
-        : "memory");
-}
-
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void static_for_x(F&& f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        static_for_x<I0 + 1, I1>(f);
-    }
-}
 
 // FULL: every tile of the launch is complete (no row checks anywhere: a wave-uniform run-time switch made hipcc merge its counter state at the join and wait
 // vmcnt(0), a per-store condition made it park the rows in scratch); the ragged last tile of a tensor runs as a second one-tile launch with FULL = false.
@@ -131,7 +108,7 @@ __global__ __launch_bounds__(512, 2) void xr_kernel(const XrArgs a) {
         // lgkmcnt(0) there -- a piece issued by a reducer could still be in flight when an expander reads sh3 in the chunk-0 epilogue: ADVICE r5)
         constexpr int NPC = (2 * C + 2 * P) * 4 / 1024;
         if (wave < 4)
-            for (int p = wave; p < NPC; p += 4) dma16x((const void*)((const char*)a.consts + p * 1024 + lane * 16), lds0 + CST_OFF + p * 1024);
+            for (int p = wave; p < NPC; p += 4) dma16((const void*)((const char*)a.consts + p * 1024 + lane * 16), lds0 + CST_OFF + p * 1024);
     } else {
         for (int i = t; i < 2 * C + 2 * P; i += 512)
             cst[i] = i < C ? a.sc3[i] : i < 2 * C ? a.sh3[i - C] : i < 2 * C + P ? a.sc1[i - 2 * C] : a.sh1[i - 2 * C - P];
@@ -175,7 +152,7 @@ __global__ __launch_bounds__(512, 2) void xr_kernel(const XrArgs a) {
                 const int row = RPP * p + lane / LPR, phys = lane % LPR;
                 const int m = m0 + row;
                 const void* src = m < a.M ? (const void*)(t2p + (size_t)m * P + (phys ^ (row & 15)) * 8) : zero_page;
-                dma16x(src, lds0 + p * 1024);
+                dma16(src, lds0 + p * 1024);
             }
 #pragma unroll
             for (int pb = 0; pb < NPB; ++pb) { prow[pb] = (long long)m0 + 32 * pb + n31; pok[pb] = prow[pb] < a.M; }
@@ -188,14 +165,14 @@ __global__ __launch_bounds__(512, 2) void xr_kernel(const XrArgs a) {
         {
             asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // this tile's t2 rows and the constants are in LDS
             if (first) XR_STAMP(1);
-            static_for_x<0, NCH>([&](auto cc) {
+            static_for<0, NCH>([&](auto cc) {
                 constexpr int c = decltype(cc)::value;
                 f32x16 acc[NPB];
 #pragma unroll
                 for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) acc[pb][e] = 0.f;
-                static_for_x<0, G3>([&](auto gc) {
+                static_for<0, G3>([&](auto gc) {
                     constexpr int g = decltype(gc)::value, u = G3 * c + g;
                     if constexpr (u + WD3 < NU) wf[(u + WD3) % (WD3 + 1)] = load_w(u + WD3);
                     V16 xb[NPB];
@@ -271,7 +248,7 @@ __global__ __launch_bounds__(512, 2) void xr_kernel(const XrArgs a) {
         for (int u = 0; u < WD1; ++u) load_w1(u, wf1[u]);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // the expanders' "t2 tile is in LDS" barrier
         if (first) XR_STAMP(1);
-        static_for_x<0, NCH>([&](auto kc) {
+        static_for<0, NCH>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // chunk k is complete in LDS
             if (first) XR_STAMP(2 + 3 * k);                      // through the barrier
@@ -297,7 +274,7 @@ __global__ __launch_bounds__(512, 2) void xr_kernel(const XrArgs a) {
             }
             if (first) XR_STAMP(3 + 3 * k);                      // copy-out issued
             const unsigned ay = ayb + (k & 1) * Y_BYTES;
-            static_for_x<0, G1>([&](auto gc) {
+            static_for<0, G1>([&](auto gc) {
                 constexpr int g = decltype(gc)::value, u = G1 * k + g;
                 if constexpr (u + WD1 < NU1) load_w1(u + WD1, wf1[(u + WD1) % (WD1 + 1)]);
                 V16 xb[NPB];
