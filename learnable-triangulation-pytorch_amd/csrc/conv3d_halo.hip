@@ -18,12 +18,21 @@
 //   weights: per tap a [cout_pad][CINB] slab, slot lv ^ ((-(col/VPR)) % NVV) (conflict free for both MFMA shapes).
 // Weight ring: NBUF chunk buffers, NBUF-1 chunks of DMA in flight (counted vmcnt), one barrier per chunk.
 //
-// Kernels in this file (dispatch: conv3d_halo_try at the end):
-//   conv3d_halo_kernel          one tile per workgroup, weight ring in LDS, optional loader waves: fp32, and the bf16 shapes below miss
-//   conv3d_halo_persist_kernel  3^3 32->32: persistent, weights resident, double-buffered halo (small grids)
-//   conv3d_halo_col_kernel      3^3 32->32: column walk, ring of 4-plane halo groups, epilogue under the next tile's MFMAs
-//   conv3d_halo7b_kernel        7^3 32->16: loader waves, kd-register-blocked
-//   conv3d_halo_wreg_kernel     3^3 64->64, 32->64, 128->128: halo-only LDS, weights as fragments from global memory
+// Dispatch (conv3d_halo_try at the end; the first row that matches launches, and an A/B switch in brackets sends its row's layers on to the rows below):
+//   bf16 3^3 32->32, >= 1024 tiles, count % 8 == 0    [LT_HALO_NO_PERSIST]
+//     every workgroup gets whole columns of >= 2 tiles  conv3d_halo_col_kernel       column walk, ring of 4-plane halo groups, epilogue under the next
+//                                                       [LT_HALO_NO_COL]             tile's MFMAs (also: fp32 store, computed skip residual)
+//     else                                              conv3d_halo_persist_kernel   persistent, weights resident, double-buffered halo
+//   bf16 3^3 64->64, 16->32, 32->64, 128->128          conv3d_halo_wreg_kernel      halo-only LDS, weights as fragments from global memory
+//     with fragment-order weights  [LT_HALO_NO_WREG]
+//   fp8  3^3 64->64, 32->32, 32->64                    conv3d_halo_kernel, LDR      one tile per workgroup, weight ring in LDS, waves 4-7 are loaders
+//   bf16 3^3 64->64, 32->32, 16->32, 32->64            conv3d_halo_kernel, LDR
+//   bf16 7^3 32->16                                    conv3d_halo7b_kernel         loader waves, kd-register-blocked
+//   bf16 7^3 16->32  [LT_HALO_NO_D7]                   conv3d_halo_kernel, PD 2     fragment ring two taps deep
+//   fp32 3^3 32->32  [LT_HALO_F3=1]                    conv3d_halo_kernel, NPH 2    two channel phases of 16, row chunks
+//   fp32 3^3 32->32, 16->32                            conv3d_halo_kernel           row chunks / plane chunks
+//   fp32 7^3 32->16, 16->32  [LT_HALO_NO_F7]           conv3d_halo_kernel           NPH 2 with the fragment ring / one phase, one-tap lookahead
+//   anything else: 0, the caller takes the implicit-GEMM path
 #include <stdlib.h>
 
 #include <type_traits>
@@ -54,8 +63,11 @@ template <> struct HaloSwz<3, 32, 32> { static constexpr int FA = 0, FB = 0, FC 
 // (7, 32 B, 32x32) -- round 6: the input gradient of V2V's 7^3 front layer, 16 -> 32 -- takes the default: the 7^3 tap loop needs a swizzle that depends on kw only,
 // and the best of those is 2-way conflicted (tools/halo_bank_search.py: 2.0 for every kw-only candidate; the conflict-free ones mix in kh)
 
-template <typename T, int KS, int CIN, int CP, int TD, int TH, int TW, int TPC, int NBUF>
-struct HaloCfg {
+// every kernel of this file computes a 4 x 8 x 8 block of output voxels per workgroup tile (256 GEMM rows, one d-plane per compute wave)
+struct HaloTile { static constexpr int TD = 4, TH = 8, TW = 8; };
+
+template <typename T, int KS, int CIN, int CP, int TPC, int NBUF>
+struct HaloCfg : HaloTile {
     static constexpr int ES = sizeof(T);
     static constexpr int VEC = 16 / ES;
     // outputs / residuals are the operand type, except that fp8 (an operand type only: the 'fp8v2v' training step) stores bf16
@@ -82,7 +94,6 @@ struct HaloCfg {
     static constexpr int EP_BYTES = 4 * 64 * EP_LD * 4;
     static constexpr int MAIN_BYTES = HALO_BYTES + NBUF * WCH;
     static constexpr int LDS_BYTES = MAIN_BYTES > EP_BYTES ? MAIN_BYTES : EP_BYTES;
-    static_assert(TD * TH * TW == 256, "256 rows per workgroup");
     static_assert(NVV >= 1 && (MF == 32 ? NVV >= 2 : NVV >= 4), "Cin too small for the MFMA K");
     static_assert((NVV & (NVV - 1)) == 0 && NVV <= 16, "NVV must be a power of two <= 16");
     static_assert(NBUF >= 2 && NBUF <= 4, "2..4 weight chunk buffers");
@@ -100,11 +111,10 @@ struct HaloCfg {
 // All MFMAs of one tap for a wave's SM x SN accumulator blocks over G fragment groups.  bf16: one MFMA per (group, block).  fp32 (round 6): a 16-byte
 // fragment is FOUR exact-fp32 MFMAs (K pairs e = 0 .. 3); issued back to back on one accumulator they wait for each other (~10 % below the issue rate,
 // measured in conv_igemm2's K loop: 4740 cycles for 64 MFMAs of 64) -- the K pair goes outermost, so that consecutive MFMAs write different blocks.  The
-// summation order of every accumulator is unchanged (results are bit-identical).  -DLT_FP32_NO_PIPE: the old order (A/B builds).
+// summation order of every accumulator is unchanged (results are bit-identical).
 template <typename T, int MF, int SM, int SN, int G, typename ACC, typename FA, typename FB>
 __device__ __forceinline__ void mma_tap_blocks(ACC (&acc)[SM][SN], const FA& fa, const FB& fb) {
 #if !defined(LT_ABL_NO_MMA)
-#if !defined(LT_FP32_NO_PIPE)
     if constexpr (sizeof(T) == 4 && SM * SN > 1) {
 #pragma unroll
         for (int g = 0; g < G; ++g)
@@ -119,7 +129,6 @@ __device__ __forceinline__ void mma_tap_blocks(ACC (&acc)[SM][SN], const FA& fa,
                     }
         return;
     }
-#endif
 #pragma unroll
     for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -163,11 +172,11 @@ struct HaloCst {
 // Epilogue shared by the halo kernels (same scheme as conv_igemm2): (acc + bias)*scale + shift into this wave's fp32 LDS tile
 // (64 rows, padded), then 16-byte vectors: optional pre-activation ReLU, residual, ReLU, store.  rp0..rp7: the lane's residual
 // vectors when they were prefetched (pre_res), in named registers (an array was kept in scratch memory by hipcc).
-template <typename T, int CP, int MF, int SM, int SN, int NACC, int TH, int TW, bool ACC64, typename ACC, typename DACC>
+template <typename T, int CP, int MF, int SM, int SN, int NACC, bool ACC64, typename ACC, typename DACC>
 __device__ __forceinline__ void halo_epilogue(unsigned char* smem, const HaloArgs& a, int wave, int lane, int n, int d0, int h0, int w0,
                                               ACC& acc, DACC& dacc, bool pre_res, uint4 rp0, uint4 rp1, uint4 rp2, uint4 rp3, uint4 rp4,
                                               uint4 rp5, uint4 rp6, uint4 rp7, const HaloCst<SN>& cst) {
-    constexpr int EP_LD = CP + 4;
+    constexpr int EP_LD = CP + 4, TH = HaloTile::TH, TW = HaloTile::TW;
     typedef typename std::conditional<sizeof(T) == 1, bf16_t, T>::type OT;          // fp8 operands: bf16 outputs and residuals
     constexpr int VEC_ = 16 / (int)sizeof(OT);
     // ---- epilogue (same scheme as conv_igemm2: per-wave fp32 LDS tile -> 16-byte vectors) ----
@@ -277,9 +286,10 @@ __device__ __forceinline__ void halo_epilogue(unsigned char* smem, const HaloArg
 // channels [0, CIN), reloads the halo image with channels [CIN, 2 CIN) and walks the taps again; the accumulators live across the phases.  Every input
 // voxel enters LDS once per tile and phase -- on the generic 256 x 16 tile it crossed L2 -> LDS once per TAP (343 times), and the eight-piece DMA issue
 // per K step cost as much as its 32 MFMAs (51 % of the fp32 MFMA peak).
-template <typename T, int KS, int CIN, int CP, int TD, int TH, int TW, int TPC, int NBUF, int PD, bool LDR, int NPH = 1>
+template <typename T, int KS, int CIN, int CP, int TPC, int NBUF, int PD, bool LDR, int NPH = 1>
 __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const HaloArgs a) {
-    typedef HaloCfg<T, KS, CIN, CP, TD, TH, TW, TPC, NBUF> C;
+    typedef HaloCfg<T, KS, CIN, CP, TPC, NBUF> C;
+    constexpr int TD = C::TD, TH = C::TH, TW = C::TW;
     static_assert(!LDR || PD == 1, "loader waves: non-ring path");
     static_assert(NPH == 1 || !LDR, "channel phases: no loader waves");
     constexpr int XLD = CIN * NPH;                       // channels per voxel of the tensor (and per tap of a weight row)
@@ -657,7 +667,7 @@ __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const Halo
 #ifdef LT_ABL_NO_EPI
     if (a.N < 0)
 #endif
-    halo_epilogue<T, CP, MF, SM, SN, NACC, TH, TW, ACC64>(smem, a, wave, lane, n, d0, h0, w0, acc, dacc, pre_res, rp0, rp1, rp2, rp3, rp4, rp5,
+    halo_epilogue<T, CP, MF, SM, SN, NACC, ACC64>(smem, a, wave, lane, n, d0, h0, w0, acc, dacc, pre_res, rp0, rp1, rp2, rp3, rp4, rp5,
                                                          rp6, rp7, cst);
 }
 
@@ -678,8 +688,9 @@ __global__ __launch_bounds__(LDR ? 512 : 256) void conv3d_halo_kernel(const Halo
 // workgroup b (XCD b % 8) keeps to the samples / raster run of that XCD, as above.
 template <typename T, int CIN, int CP>
 __global__ __launch_bounds__(512) void conv3d_halo_persist_kernel(const HaloArgs a, const int total_tiles) {
-    constexpr int KS = 3, TD = 4, TH = 8, TW = 8;
-    typedef HaloCfg<T, KS, CIN, CP, TD, TH, TW, 9, 2> C;
+    constexpr int KS = 3;
+    typedef HaloCfg<T, KS, CIN, CP, 9, 2> C;
+    constexpr int TD = C::TD, TH = C::TH, TW = C::TW;
     static_assert(sizeof(T) == 2, "bf16 only: fp32 slabs do not fit beside two halo buffers");
     constexpr int MF = C::MF, SM = C::SM, SN = C::SN, G = C::G, NACC = C::NACC, NVV = C::NVV, VPR = C::VPR, CINB = C::CINB;
     constexpr int W_BYTES = ((C::NTAPS * C::SLAB + 1023) / 1024) * 1024;
@@ -959,8 +970,9 @@ __global__ __launch_bounds__(512) void conv3d_halo_persist_kernel(const HaloArgs
 // tensor's read here all disappear (lt_conv_skip_fwd).
 template <typename T, bool F32OUT, bool SKIP>
 __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, const int total_cols) {
-    constexpr int KS = 3, CIN = 32, CP = 32, TD = 4, TH = 8, TW = 8;
-    typedef HaloCfg<T, KS, CIN, CP, TD, TH, TW, 9, 2> C;
+    constexpr int KS = 3, CIN = 32, CP = 32;
+    typedef HaloCfg<T, KS, CIN, CP, 9, 2> C;
+    constexpr int TD = C::TD, TH = C::TH, TW = C::TW;
     static_assert(sizeof(T) == 2, "bf16 only");
     constexpr int MF = C::MF, SM = C::SM, SN = C::SN, G = C::G, NACC = C::NACC, NVV = C::NVV, VPR = C::VPR, CINB = C::CINB;
     static_assert(MF == 32 && SM == 2 && SN == 1 && G == 2 && NACC == 16 && NVV == 4, "3^3 32->32 bf16 layout");
@@ -1352,8 +1364,9 @@ __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, 
 // 110 registers let four workgroups share a CU -- the one-tile loader-wave kernel it replaces there was latency-bound at 0.25 MFMA-busy).
 template <typename T, int CIN, int CP>
 __global__ __launch_bounds__(256, (CIN == 128 ? 1 : CIN == 16 ? 4 : 2)) void conv3d_halo_wreg_kernel(const HaloArgs a) {
-    constexpr int KS = 3, TD = 4, TH = 8, TW = 8, G = CIN / 16, NB = CP / 32;
-    typedef HaloCfg<T, KS, CIN, CP, TD, TH, TW, 3, 3> C;
+    constexpr int KS = 3, G = CIN / 16, NB = CP / 32;
+    typedef HaloCfg<T, KS, CIN, CP, 3, 3> C;
+    constexpr int TD = C::TD, TH = C::TH, TW = C::TW;
     static_assert(sizeof(T) == 2 && (NB == 1 || NB == 2 || NB == 4) && (C::CINB == 32 || C::CINB == 64 || C::CINB == 128 || C::CINB == 256),
                   "bf16; 16/32/64/128 -> 32/64/128");
     static_assert(C::SW::FB == 0, "plane-independent swizzle");
@@ -1564,8 +1577,9 @@ constexpr int h7_gpos(int c, int hd) { return 7 + 17 * c + (c == 48 ? hd : h7_lp
 constexpr int h7_target(int c, int hd, int look, int gend) { return h7_gpos(c, hd) + 1 + look < gend ? h7_gpos(c, hd) + 1 + look : gend; }
 template <typename T>
 __global__ __launch_bounds__(512) void conv3d_halo7b_kernel(const HaloArgs a) {
-    constexpr int KS = 7, CIN = 32, CP = 16, TD = 4, TH = 8, TW = 8, TPC = 7, NBUF = 5;
-    typedef HaloCfg<T, KS, CIN, CP, TD, TH, TW, TPC, 4> C;
+    constexpr int KS = 7, CIN = 32, CP = 16, TPC = 7, NBUF = 5;
+    typedef HaloCfg<T, KS, CIN, CP, TPC, 4> C;
+    constexpr int TD = C::TD, TH = C::TH, TW = C::TW;
     static_assert(sizeof(T) == 2, "bf16 only");
     constexpr int MF = C::MF, NVV = C::NVV, VPR = C::VPR, CINB = C::CINB;
     static_assert(MF == 16 && NVV == 4 && C::SW::FSH == 0 && C::SW::FA == 0 && C::SW::FC == 0 && C::SLAB == 1024 && C::WCH == TPC * 1024, "7^3 32->16 layout");
@@ -1772,7 +1786,7 @@ __global__ __launch_bounds__(512) void conv3d_halo7b_kernel(const HaloArgs a) {
 }
 
 int launch_halo7(const HaloArgs& a, hipStream_t s) {
-    typedef HaloCfg<bf16_t, 7, 32, 16, 4, 8, 8, 7, 4> C;
+    typedef HaloCfg<bf16_t, 7, 32, 16, 7, 4> C;
     constexpr int LDS = C::HALO_BYTES + 5 * C::WCH;
     const long long nblk = (long long)a.N * a.tiles_d * a.tiles_h * a.tiles_w;
     auto kern_b = conv3d_halo7b_kernel<bf16_t>;
@@ -1784,7 +1798,7 @@ int launch_halo7(const HaloArgs& a, hipStream_t s) {
 
 template <typename T, int CIN, int CP>
 int launch_halo_persist(const HaloArgs& a, hipStream_t s) {
-    typedef HaloCfg<T, 3, CIN, CP, 4, 8, 8, 9, 2> C;
+    typedef HaloCfg<T, 3, CIN, CP, 9, 2> C;
     constexpr int W_BYTES = ((C::NTAPS * C::SLAB + 1023) / 1024) * 1024;
     constexpr int LDS = W_BYTES + 2 * C::HALO_BYTES;
     static_assert(LDS <= 160 * 1024, "weights + two halo buffers do not fit LDS");
@@ -1800,7 +1814,7 @@ int launch_halo_persist(const HaloArgs& a, hipStream_t s) {
 
 template <typename T, int CIN, int CP>
 int launch_halo_wreg(const HaloArgs& a, hipStream_t s) {
-    typedef HaloCfg<T, 3, CIN, CP, 4, 8, 8, 3, 3> C;
+    typedef HaloCfg<T, 3, CIN, CP, 3, 3> C;
     static_assert(C::HALO_BYTES <= 160 * 1024, "the halo must fit LDS");
     auto kern = conv3d_halo_wreg_kernel<T, CIN, CP>;
     LT_OPT_IN_LDS(kern, 160 * 1024);
@@ -1812,7 +1826,7 @@ int launch_halo_wreg(const HaloArgs& a, hipStream_t s) {
 
 template <typename T>
 int launch_halo_col(const HaloArgs& a, hipStream_t s) {
-    typedef HaloCfg<T, 3, 32, 32, 4, 8, 8, 9, 2> C;
+    typedef HaloCfg<T, 3, 32, 32, 9, 2> C;
     constexpr int W_BYTES = ((C::NTAPS * C::SLAB + 1023) / 1024) * 1024;
     constexpr int LDS = W_BYTES + 4 * 4 * C::HH * C::PW * C::CINB;
     const int n_cu = lt::device_cu_count8();
@@ -1835,11 +1849,11 @@ int launch_halo_col(const HaloArgs& a, hipStream_t s) {
     return LT_OK;
 }
 
-template <typename T, int KS, int CIN, int CP, int TD, int TH, int TW, int TPC, int NBUF, int PD, bool LDR, int NPH = 1>
+template <typename T, int KS, int CIN, int CP, int TPC, int NBUF, int PD, bool LDR, int NPH = 1>
 int launch_halo(const HaloArgs& a, hipStream_t s) {
-    typedef HaloCfg<T, KS, CIN, CP, TD, TH, TW, TPC, NBUF> C;
+    typedef HaloCfg<T, KS, CIN, CP, TPC, NBUF> C;
     static_assert(C::LDS_BYTES <= 160 * 1024, "halo tile does not fit LDS");
-    auto kern = conv3d_halo_kernel<T, KS, CIN, CP, TD, TH, TW, TPC, NBUF, PD, LDR, NPH>;
+    auto kern = conv3d_halo_kernel<T, KS, CIN, CP, TPC, NBUF, PD, LDR, NPH>;
     LT_OPT_IN_LDS(kern, 160 * 1024);
     const long long nblk = (long long)a.N * a.tiles_d * a.tiles_h * a.tiles_w;
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(LDR ? 512 : 256), C::LDS_BYTES, s, a);
@@ -1866,25 +1880,22 @@ int conv3d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, bool
     if (p0.ntaps == 27 && c.pd == 1 && c.ph == 1 && c.pw == 1) ks = 3;
     else if (p0.ntaps == 343 && c.pd == 3 && c.ph == 3 && c.pw == 3) ks = 7;
     else return 0;
-    if (c.D % 4 || c.H % 8 || c.W % 8) return 0;
-    const long long nblk = (long long)c.N * (c.D / 4) * (c.H / 8) * (c.W / 8);
+    constexpr int TD = HaloTile::TD, TH = HaloTile::TH, TW = HaloTile::TW;
+    if (c.D % TD || c.H % TH || c.W % TW) return 0;
+    const long long nblk = (long long)c.N * (c.D / TD) * (c.H / TH) * (c.W / TW);
     if (nblk < 256 && !forced) return 0;   // too few workgroups: the 64x64 implicit-GEMM tile fills the chip better
     HaloArgs a;
     a.x = c.x; a.w = p0.w; a.wfrag = p0.wfrag_t; a.y = c.y; a.res = c.res; a.bias = c.bias; a.scale = c.scale; a.shift = c.shift;
     a.N = c.N; a.D = c.D; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.ldc = c.ldc; a.k_pad = c.k_pad; a.flags = c.flags;
-    a.tiles_d = c.D / 4; a.tiles_h = c.H / 8; a.tiles_w = c.W / 8;
+    a.tiles_d = c.D / TD; a.tiles_h = c.H / TH; a.tiles_w = c.W / TW;
     a.xcd_pin = (c.N % 8 == 0) ? 1 : 0;
     a.skip_x = c.skip_x; a.skip_w = c.skip_w;
     const bool bf = dtype == LT_BF16, f8 = dtype == LT_FP8;
     if (c.skip_x && (f32_out || c.res || (c.flags & LT_EPI_RELU_PRE) || !bf)) return LT_ERR_UNSUPPORTED;
-#define HALO_CASE_L(T_, KS_, CIN_, CP_, TPC_, NBUF_, PD_, LDR_)                                  \
+    // conv3d_halo_kernel<T, KS, CIN, CP, TPC, NBUF, PD, LDR> for a KS^3 layer of CIN -> CP channels
+#define HALO_CASE(T_, KS_, CIN_, CP_, ...)                                                       \
     if (ks == KS_ && c.Cin == CIN_ && cout_pad == CP_) {                                        \
-        int rc = launch_halo<T_, KS_, CIN_, CP_, 4, 8, 8, TPC_, NBUF_, PD_, LDR_>(a, s);        \
-        return rc == LT_OK ? 1 : rc;                                                            \
-    }
-#define HALO_CASE(T_, KS_, CIN_, CP_, TPC_, NBUF_, PD_)                                          \
-    if (ks == KS_ && c.Cin == CIN_ && cout_pad == CP_) {                                        \
-        int rc = launch_halo<T_, KS_, CIN_, CP_, 4, 8, 8, TPC_, NBUF_, PD_, false>(a, s);       \
+        int rc = launch_halo<T_, KS_, CIN_, CP_, __VA_ARGS__>(a, s);                            \
         return rc == LT_OK ? 1 : rc;                                                            \
     }
     // persistent variant: needs a few tiles per workgroup to amortise the weight load, and total % 8 == 0 for the XCD dealing
@@ -1906,72 +1917,57 @@ int conv3d_halo_try(int dtype, const ConvArgs& c, int cout_pad, int nphase, bool
     if (bf && ks == 3 && c.Cout == cout_pad && c.ldc % 8 == 0 && a.wfrag && !env_on("LT_HALO_NO_WREG")) {
         int rc = 1;
         if (c.Cin == 64 && cout_pad == 64) rc = launch_halo_wreg<bf16_t, 64, 64>(a, s);
-        else if (c.Cin == 16 && cout_pad == 32 && !env_on("LT_HALO_NO_WREG16")) rc = launch_halo_wreg<bf16_t, 16, 32>(a, s);
+        else if (c.Cin == 16 && cout_pad == 32) rc = launch_halo_wreg<bf16_t, 16, 32>(a, s);
         else if (c.Cin == 32 && cout_pad == 64) rc = launch_halo_wreg<bf16_t, 32, 64>(a, s);
         else if (c.Cin == 128 && cout_pad == 128) rc = launch_halo_wreg<bf16_t, 128, 128>(a, s);
         if (rc != 1) return rc == LT_OK ? 1 : rc;
     }
-    static const bool row_chunks = env_on("LT_HALO_ROW");   // A/B: 3-tap weight chunks -> 51 KB of LDS -> 3 workgroups per CU
     if (f8) {
         // e4m3 operands (train_precision 'fp8v2v'): the one-tile loader-wave kernel at half the bytes per voxel / per weight slab; bf16 stores.  The byte
         // geometries are the bf16 ones of half the channel count: (64, 64) = bf16 (32 -> 64), (32, 32) = bf16 (16 -> 32)
-        if (c.Cout % 8 || c.ldc % 8 || env_on("LT_HALO_NO_FP8")) return 0;
-        HALO_CASE_L(fp8_t, 3, 64, 64, 9, 2, 1, true)
-        HALO_CASE_L(fp8_t, 3, 32, 32, 9, 2, 1, true)
-        HALO_CASE_L(fp8_t, 3, 32, 64, 9, 2, 1, true)
+        if (c.Cout % 8 || c.ldc % 8) return 0;
+        HALO_CASE(fp8_t, 3, 64, 64, 9, 2, 1, true)
+        HALO_CASE(fp8_t, 3, 32, 32, 9, 2, 1, true)
+        HALO_CASE(fp8_t, 3, 32, 64, 9, 2, 1, true)
         return 0;
     }
     if (bf) {
-        static const bool no_ldr = env_on("LT_HALO_NO_LDR");   // A/B: no loader waves in the one-tile kernel
-        if (!no_ldr) {
-            HALO_CASE_L(bf16_t, 3, 64, 64, 3, 3, 1, true)
-            HALO_CASE_L(bf16_t, 3, 32, 32, 9, 2, 1, true)
-            HALO_CASE_L(bf16_t, 3, 16, 32, 9, 2, 1, true)
-            HALO_CASE_L(bf16_t, 3, 32, 64, 9, 2, 1, true)
-        }
-        if (row_chunks) { HALO_CASE(bf16_t, 3, 32, 32, 3, 2, 1) }
-        HALO_CASE(bf16_t, 3, 32, 32, 9, 2, 1)
-        HALO_CASE(bf16_t, 3, 16, 32, 9, 2, 1)
-        HALO_CASE(bf16_t, 3, 64, 64, 3, 2, 1)
-        HALO_CASE(bf16_t, 3, 32, 64, 9, 2, 1)
-        static const bool no_ring = env_on("LT_HALO_NO_RING");   // A/B: 1-tap fragment lookahead for 7^3
-        static const bool no_h7 = env_on("LT_HALO_NO_H7");       // A/B: no loader-wave 7^3 kernel
-        if (no_ring) { HALO_CASE(bf16_t, 7, 32, 16, 7, 4, 1) }
-        if (ks == 7 && c.Cin == 32 && cout_pad == 16 && !no_h7) {
+        HALO_CASE(bf16_t, 3, 64, 64, 3, 3, 1, true)
+        HALO_CASE(bf16_t, 3, 32, 32, 9, 2, 1, true)
+        HALO_CASE(bf16_t, 3, 16, 32, 9, 2, 1, true)
+        HALO_CASE(bf16_t, 3, 32, 64, 9, 2, 1, true)
+        if (ks == 7 && c.Cin == 32 && cout_pad == 16) {
             int rc = launch_halo7(a, s);
             return rc == LT_OK ? 1 : rc;
         }
-        HALO_CASE(bf16_t, 7, 32, 16, 7, 4, 2)
         // round 6: 7^3 16 -> 32 = the INPUT GRADIENT of the front layer in the 16-bit training step (the flipped / transposed filter): it ran on the generic
         // 256 x 32 implicit-GEMM tile with four taps per 128-byte K step (1.78 ms at 8 samples, 4.2 % of the step's kernel time); LT_HALO_NO_D7=1: that tile again (A/B)
-        if (!env_on("LT_HALO_NO_D7")) { HALO_CASE(bf16_t, 7, 16, 32, 7, 4, 2) }
+        if (!env_on("LT_HALO_NO_D7")) { HALO_CASE(bf16_t, 7, 16, 32, 7, 4, 2, false) }
     } else {
         // round 6: 3^3 32 -> 32 (nine layers at 64^3, 23 % of the exact-fp32 forward) in two channel phases of 16: 38 KB of halo + 18 KB of weight ring instead of
         // 77 + 36 KB -> TWO workgroups per CU = two waves per SIMD, so that one tile's halo load, chunk barriers, fp64 flushes and epilogue run under the other
-        // tile's MFMAs (with one workgroup per CU all of that was exposed: 59 % of the fp32 MFMA peak).  LT_HALO_F3=1: the one-phase kernel; =9: plane chunks
+        // tile's MFMAs (with one workgroup per CU all of that was exposed: 59 % of the fp32 MFMA peak).  LT_HALO_F3=1: the one-phase kernel
         {
             const char* f3 = getenv("LT_HALO_F3");
             if (ks == 3 && c.Cin == 32 && cout_pad == 32 && !(f3 && f3[0] == '1')) {
-                int rc = (f3 && f3[0] == '9') ? launch_halo<float, 3, 16, 32, 4, 8, 8, 9, 2, 1, false, 2>(a, s)
-                                              : launch_halo<float, 3, 16, 32, 4, 8, 8, 3, 3, 1, false, 2>(a, s);
+                int rc = launch_halo<float, 3, 16, 32, 3, 3, 1, false, 2>(a, s);
                 return rc == LT_OK ? 1 : rc;
             }
         }
-        HALO_CASE(float, 3, 32, 32, 3, 3, 1)
-        HALO_CASE(float, 3, 16, 32, 9, 2, 1)
+        HALO_CASE(float, 3, 32, 32, 3, 3, 1, false)
+        HALO_CASE(float, 3, 16, 32, 9, 2, 1, false)
         // round 6: the 7^3 layers of the exact-fp32 kernel set.  32 -> 16 (V2V's front layer, 18 % of the fp32 forward on the generic 256 x 16 tile at 51 % of
         // the fp32 MFMA peak): two channel phases of 16 over a 123 KB halo image (NPH = 2, see the kernel).  16 -> 32 (its input gradient in the fp32
         // training step): one phase, one-tap lookahead, two weight buffers (151 KB).  LT_HALO_NO_F7=1: the generic tiles again (A/B).
         if (ks == 7 && !env_on("LT_HALO_NO_F7")) {
             if (c.Cin == 32 && cout_pad == 16) {
-                int rc = launch_halo<float, 7, 16, 16, 4, 8, 8, 7, 4, 2, false, 2>(a, s);
+                int rc = launch_halo<float, 7, 16, 16, 7, 4, 2, false, 2>(a, s);
                 return rc == LT_OK ? 1 : rc;
             }
-            HALO_CASE(float, 7, 16, 32, 7, 2, 1)
+            HALO_CASE(float, 7, 16, 32, 7, 2, 1, false)
         }
     }
 #undef HALO_CASE
-#undef HALO_CASE_L
     return 0;
 }
 

@@ -313,19 +313,10 @@ __global__ __launch_bounds__(256) void conv_igemm2_kernel(const ConvArgs a) {
         if (s < nk) stage(s, s, 0, NPIECE);
 
     // One K step. MORE_ (compile time): stage ks+NST-1 is still to be requested, right after the barrier, so that it has the
-    // whole K step to land.  (-DLT_DMA_SLICED issues the pieces in slices behind the MFMAs of each fragment group instead:
-    // measured 5 % SLOWER end to end with the 2-stage ring -- the last slice then has only a quarter of a K step to land.)
+    // whole K step to land.  (Issuing the pieces in slices behind the MFMAs of each fragment group instead measured 5 % SLOWER
+    // end to end with the 2-stage ring -- the last slice then has only a quarter of a K step to land: removed, see DESIGN.md.)
     // The main loop and the NST-1 drain steps are separate loops so that the K step has no control flow.
-#ifdef LT_DMA_SLICED
-    constexpr bool UPFRONT = false;
-#else
-    constexpr bool UPFRONT = true;
-#endif
-#ifdef LT_FP32_NO_PIPE
-    constexpr bool PIPE32 = false;
-#else
-    constexpr bool PIPE32 = ACC64 && UPFRONT;
-#endif
+    constexpr bool PIPE32 = ACC64;   // the exact-fp32 K step (see LT_KSTEP): DMA pieces and fp64 flushes go out between its MFMA blocks
 #ifdef LT_TRACE
 #define LT_TR0 const long long tr0 = LT_CLK(); if (ks > 0) tr_cmp += tr0 - tr_prev;
 #define LT_TR1 const long long tr1 = LT_CLK(); tr_vm += tr1 - tr0;
@@ -346,7 +337,7 @@ __global__ __launch_bounds__(256) void conv_igemm2_kernel(const ConvArgs a) {
        occupies the matrix pipe for 64 cycles: everything the wave issues BETWEEN two MFMAs is free, everything it issues before the first or after the    \
        last one of a K step is exposed (shader-clock trace, 256 images, 3x3 256 -> 256: 5490 cycles per K step for 4096 of MFMA -- 620 DMA issue, ~700      \
        around the fragment groups and the fp64 flush, 130 wait + barrier).  PIPE32: the next stage's DMA pieces go out one by one behind the MFMA blocks   \
-       of the first half of the step, and a flush step folds block b - 1 into its fp64 sums behind the MFMAs of block b.  -DLT_FP32_NO_PIPE: the old order. */ \
+       of the first half of the step, and a flush step folds block b - 1 into its fp64 sums behind the MFMAs of block b. */                                   \
 #define LT_KSTEP(MORE_)                                                                                              \
     {                                                                                                                \
         LT_TR0                                                                                                       \
@@ -354,7 +345,7 @@ __global__ __launch_bounds__(256) void conv_igemm2_kernel(const ConvArgs a) {
         LT_TR1                                                                                                       \
         block_barrier(); /* everybody's stage-ks DMAs landed, everybody is done reading stage ks-1 */                \
         LT_TR2                                                                                                       \
-        if (MORE_ && UPFRONT && !PIPE32) stage(ks + NST - 1, (ks + NST - 1) % NST, 0, NPIECE);                       \
+        if (MORE_ && !PIPE32) stage(ks + NST - 1, (ks + NST - 1) % NST, 0, NPIECE);                                  \
         LT_TR3                                                                                                       \
         const int buf = ks % NST;                                                                                    \
         const unsigned char* pa = smem + buf * STAGE + a_base;                                                       \
@@ -396,10 +387,6 @@ __global__ __launch_bounds__(256) void conv_igemm2_kernel(const ConvArgs a) {
             _Pragma("unroll") for (int i = 0; i < SM; ++i)                                                           \
                 _Pragma("unroll") for (int j = 0; j < SN; ++j) LT_MMA_RUN(acc[i][j], fa[g & 1][i], fb[g & 1][j]);      \
             __builtin_amdgcn_sched_barrier(0);                                                                       \
-            if (MORE_ && !UPFRONT) {                                                                                 \
-                stage(ks + NST - 1, (ks + NST - 1) % NST, g * NPIECE / G, (g + 1) * NPIECE / G);                     \
-                __builtin_amdgcn_sched_barrier(0);                                                                   \
-            }                                                                                                        \
         }                                                                                                            \
         if (ACC64 && ((ks & LT_ACC64_MASK) == LT_ACC64_MASK || ks + 1 == nk)) {                                                              \
             _Pragma("unroll") for (int i = 0; i < SM; ++i)                                                           \
@@ -616,7 +603,7 @@ int dispatch2(const ConvArgs& a, int cout_pad, int nphase, int max_taps, int til
     // pointwise fast path: one tap at offset 0, unit strides, dense output rows
     const bool pw = nphase == 1 && plain_pointwise(a);
     if (tile == LT_TILE_AUTO) {
-        static const int minblk = getenv("LT_CONV2_MINBLK") ? atoi(getenv("LT_CONV2_MINBLK")) : 480;          // tuning knob
+        constexpr int minblk = 480;
         if (cout_pad <= 16) tile = LT_TILE2_256x16;
         else if (cout_pad <= 32) tile = LT_TILE2_256x32;
         else if (cout_pad <= 64) tile = blocks(128, 64) >= minblk ? LT_TILE2_128x64 : LT_TILE2_64x64;
@@ -628,8 +615,7 @@ int dispatch2(const ConvArgs& a, int cout_pad, int nphase, int max_taps, int til
         else tile = blocks(128, 128) >= minblk ? LT_TILE2_128x128 : (blocks(128, 64) >= minblk ? LT_TILE2_128x64 : LT_TILE2_64x64);
     }
     // uniform-tap path: every 128-byte K step lies inside one tap
-    static const bool no_ut = env_on("LT_CONV_NO_UT");   // A/B switch
-    const int mode = pw ? 1 : (((a.Cin * (int)sizeof(T)) % ROW_BYTES == 0 && !no_ut) ? 2 : 0);
+    const int mode = pw ? 1 : ((a.Cin * (int)sizeof(T)) % ROW_BYTES == 0 ? 2 : 0);
     // ring depth: 3 stages cost a resident workgroup per CU on the big tiles, so they only pay when the grid leaves at most
     // one workgroup per CU anyway (tiny layers: pure latency chains)
     int nst = a.stages;

@@ -1,4 +1,4 @@
-// Implicit-GEMM convolution, third generation: 288 x BN tile, eight waves, three-stage LDS-DMA ring, skewed DMA issue.
+// Implicit-GEMM convolution, third generation: 288 x BN tile, twelve waves, three-stage LDS-DMA ring, skewed DMA issue.
 //
 // Why (measured on MI355X with the shader-clock build of conv_igemm2, tools/trace_kstep.py, ResNet-152 layer3 at 64 images):
 //   * a 128x128 tile needs 64 bytes of A/B per CU clock at the MFMA peak = exactly what the vector-memory path can deliver;
@@ -8,7 +8,7 @@
 // Here:
 //   * BM = 288 = 2 x 144 rows: every ResNet level of the 384x384 input is a multiple of 144 pixels per image (24^2 = 4 x 144,
 //     48^2, 96^2, 12^2 = 144), so layer3 at 64 images is 128 x (Cout/128) tiles = one workgroup per CU, rounds are exact;
-//   * one workgroup per CU, eight waves = 2 (M) x 4 (N), wave tile 144 x BN/4 on the 16x16x32 MFMA (9 x 2 accumulator tiles);
+//   * one workgroup per CU, twelve waves = 3 (M) x 4 (N), wave tile 96 x BN/4 on the 16x16x32 MFMA (6 x 2 accumulator tiles);
 //     288x128 needs 46 B/clk at the MFMA peak (below the 64 B/clk of the load path);
 //   * three stages: a stage is requested two K steps before it is needed, so WHEN inside the step it is requested is free:
 //     every wave issues one DMA piece behind every second A fragment (a piece holds the wave in the issue stage for ~100
@@ -16,7 +16,7 @@
 //   * fragments: hand-issued ds_read_b128 with counted lgkmcnt (hipcc falls back to lgkmcnt(0) beyond one group in flight).
 // bf16 only (the fp32 parity mode stays on conv_igemm2), one phase, pointwise or uniform-tap addressing, vector epilogue.
 //
-// Kernels in this file (dispatch: conv3_try at the end): conv_igemm3_kernel (288 x 128 / 64, 8 or 12 waves),
+// Kernels in this file (dispatch: conv3_try at the end): conv_igemm3_kernel (288 x 128 / 64, twelve waves),
 // conv_igemm5_kernel (288 x 256, 32-element K steps, both operands staged),
 // conv_igemm6_kernel (288 x 256 or 144 x 256, weights from global memory in fragment order: the default for Cout % 256 == 0).
 #include <stdlib.h>
@@ -50,20 +50,22 @@ constexpr int s3_target(int u, int SM, int SN, int LOOK, int TOTAL) {
     return u < 0 ? 0 : (s3_pos(u, SM, SN) + 1 + LOOK < TOTAL ? s3_pos(u, SM, SN) + 1 + LOOK : TOTAL);
 }
 
-template <int BN, int MODE, int NWM>
-__global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a) {
+constexpr int NWM3 = 3;   // waves along M of conv_igemm3_kernel
+
+template <int BN, int MODE>
+__global__ __launch_bounds__(256 * NWM3) void conv_igemm3_kernel(const ConvArgs a) {
     typedef bf16_t T;
     constexpr bool PW = MODE == 1;   // pointwise: rows contiguous, no taps; else uniform tap (Cin*2 % 128 == 0)
-    // NWM waves along M x 4 along N: 2 -> eight waves of 144 x BN/4, 3 -> twelve waves of 96 x BN/4 (three per SIMD)
-    constexpr int BM = BM3, NW = 4 * NWM, WM = BM / NWM, WN = BN / 4, MF = 16, SM = WM / MF, SN = WN / MF, G = 2, NST = 3, VEC = 8, BK = 64;
+    // 3 waves along M x 4 along N: twelve waves of 96 x BN/4 (three per SIMD)
+    constexpr int NWM = NWM3, BM = BM3, NW = 4 * NWM, WM = BM / NWM, WN = BN / 4, MF = 16, SM = WM / MF, SN = WN / MF, G = 2, NST = 3, VEC = 8, BK = 64;
     constexpr int NPA = BM / 8, NPB = BN / 8;            // 1 KiB DMA pieces per stage (8 rows of 128 B each)
     constexpr int A_IT = (NPA + NW - 1) / NW;            // piece wave + NW i, valid while < NPA (wave-uniform)
     constexpr int B_IT = (NPB + NW - 1) / NW;
     constexpr int NPASS = WM / 48;                       // epilogue passes of 48 rows
     constexpr int STAGE = (BM + BN) * ROW_BYTES;
     constexpr int REGION = NST * STAGE;
-    constexpr int EP_ROWS = 48, EP_LD = WN + 4, EP_WAVE = EP_ROWS * EP_LD * 4;   // per-wave fp32 staging, three passes of 48 rows
-    static_assert(SN >= 1 && NW * EP_WAVE <= REGION && WM == NPASS * EP_ROWS && (NPASS == 2 || NPASS == 3), "tile shape");
+    constexpr int EP_ROWS = 48, EP_LD = WN + 4, EP_WAVE = EP_ROWS * EP_LD * 4;   // per-wave fp32 staging, two passes of 48 rows
+    static_assert(SN >= 1 && NW * EP_WAVE <= REGION && WM == NPASS * EP_ROWS && NPASS == 2, "tile shape");
     typedef typename Mma<T, MF>::acc_t acc_t;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
     const T* __restrict__ w = (const T*)ph.w;
 
     // DMA ownership: thread t fills physical slot t&7 of rows (t>>3) + 8 NW i; the logical K vector it must fetch is
-    // v = (t&7) ^ ((row>>1)&7), the same for all its rows (8 NW i = 64 i or 96 i does not change (row>>1)&7)
+    // v = (t&7) ^ ((row>>1)&7), the same for all its rows (8 NW i = 96 i does not change (row>>1)&7)
     const int v = (t & 7) ^ ((t >> 4) & 7);
     // the last round of A / B pieces may be partial: only waves < NP % NW own a piece in it (wave-uniform)
     const bool a_tail = (NPA % NW == 0) || wave < NPA % NW;
@@ -144,8 +146,8 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
     const int nk = a.k_pad / BK;
 
     // ---- output rows of this lane in the epilogue: pass p (48 rows of the wave tile), iteration k ----
-    constexpr int LPR = WN / 8, RPP = 64 / LPR, ITP = (EP_ROWS + RPP - 1) / RPP, NRES = NPASS * ITP;   // <= 9
-    static_assert(NRES <= 9, "named residual registers");
+    constexpr int LPR = WN / 8, RPP = 64 / LPR, ITP = (EP_ROWS + RPP - 1) / RPP, NRES = NPASS * ITP;   // <= 6
+    static_assert(NRES <= 6, "named residual registers");
     const int colv = n0 + wn * WN + (lane % LPR) * 8;
     auto out_off = [&](int p, int k) -> long long {   // element offset of the lane's 8-channel vector, or -1
         const int rr = k * RPP + lane / LPR;
@@ -160,8 +162,8 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
         return pix * a.ldc + colv;
     };
     // residual vectors requested before the K loop, in named registers (an array stayed in scratch memory, see conv_igemm2.hip)
-    uint4 rp0, rp1, rp2, rp3, rp4, rp5, rp6, rp7, rp8;
-    rp0 = rp1 = rp2 = rp3 = rp4 = rp5 = rp6 = rp7 = rp8 = make_uint4(0, 0, 0, 0);
+    uint4 rp0, rp1, rp2, rp3, rp4, rp5;
+    rp0 = rp1 = rp2 = rp3 = rp4 = rp5 = make_uint4(0, 0, 0, 0);
     const bool has_res = a.res != nullptr;
     if (has_res) {
         auto pf = [&](int idx) -> uint4 {
@@ -175,9 +177,6 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
         if (NRES > 3) rp3 = pf(3);
         if (NRES > 4) rp4 = pf(4);
         if (NRES > 5) rp5 = pf(5);
-        if (NRES > 6) rp6 = pf(6);
-        if (NRES > 7) rp7 = pf(7);
-        if (NRES > 8) rp8 = pf(8);
     }
 
     // ---- DMA of this wave's pieces of one stage: stage_prep (tap bookkeeping), then pieces 0..NPIECE-1 (A rounds, then B) ----
@@ -221,7 +220,7 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
     };
 
     // ---- fragment addresses: row r15 = lane & 15 of a 16-row MFMA tile, K vector (lane >> 4) + 4 g, slot = vector ^ ((row>>1)&7)
-    // ((row>>1)&7 depends on r15 only: 144 wm, 16 i, WN wn and 16 j are all multiples of 16) ----
+    // ((row>>1)&7 depends on r15 only: 96 wm, 16 i, WN wn and 16 j are all multiples of 16) ----
     const int r15 = lane & 15;
     const int fsw = (r15 >> 1) & 7;
     unsigned aoff[G], boff[G];
@@ -329,7 +328,7 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
     if (a.M >= 0) return;
 #endif
 
-    // ---- epilogue: three passes of 48 rows through this wave's private fp32 LDS tile -> 16-byte vectors ----
+    // ---- epilogue: two passes of 48 rows through this wave's private fp32 LDS tile -> 16-byte vectors ----
     const EpiFloors fl = epi_floors(a.flags);
     const unsigned no_res = has_res ? 0u : 0x80008000u;   // residual registers are zero without a residual: make them -0.0 (v + -0.0 == v)
     float* ep = (float*)(smem + wave * EP_WAVE);
@@ -368,11 +367,9 @@ __global__ __launch_bounds__(256 * NWM) void conv_igemm3_kernel(const ConvArgs a
     if (ITP == 3) {
         LT3_PASS(0, rp0, rp1, rp2)
         LT3_PASS(1, rp3, rp4, rp5)
-        if (NPASS > 2) LT3_PASS(2, rp6, rp7, rp8)
     } else {
         LT3_PASS(0, rp0, rp1, rp1)
         LT3_PASS(1, rp2, rp3, rp3)
-        if (NPASS > 2) LT3_PASS(2, rp4, rp5, rp5)
     }
 #undef LT3_PASS
 }
@@ -1049,16 +1046,16 @@ int launch5(ConvArgs a, int cout_pad, int max_taps, hipStream_t s) {
     return LT_OK;
 }
 
-template <int BN, int MODE, int NWM>
+template <int BN, int MODE>
 int launch3(ConvArgs a, int cout_pad, int max_taps, hipStream_t s) {
     a.tiles_n = cout_pad / BN;
     const long long nblk = cdiv(a.M, BM3) * a.tiles_n;
     LT_REQUIRE(nblk < (1ll << 31), LT_ERR_INVALID, "lt_conv_fwd: grid too large");
     const size_t lds = 3 * (size_t)(BM3 + BN) * ROW_BYTES + (size_t)max_taps * sizeof(int4);
     LT_REQUIRE(lds <= 160 * 1024, LT_ERR_UNSUPPORTED, "lt_conv_fwd: 288-row tile needs %zu B of LDS", lds);
-    auto kern = conv_igemm3_kernel<BN, MODE, NWM>;
+    auto kern = conv_igemm3_kernel<BN, MODE>;
     LT_OPT_IN_LDS(kern, 160 * 1024);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256 * NWM), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256 * NWM3), lds, s, a);
     LT_CHECK_LAUNCH("lt_conv_fwd(v3)");
     return LT_OK;
 }
@@ -1104,9 +1101,8 @@ int conv3_try(int dtype, const ConvArgs& a, int cout_pad, int nphase, int max_ta
         const bool no6 = env_on("LT_CONV_NO_V6");   // A/B, read per call
         // small batches (the reference trains at 5 samples = 20 images): the short-K expand layers still fill the chip with the 144-row variant of
         // conv_igemm6 (two workgroups per CU) when the 288-row count says no -- 256 -> 1024 at 20 images: 320 tiles of 144 x 256 instead of
-        // 1440 L2-stream-bound 128 x 64 tiles of the generic kernel (LT_CONV_NO_SMALL144=1: off)
-        const bool small144 = pw && q0.wfrag && !no6 && a.k_pad % 64 == 0 && a.k_pad <= 256 && a.M % 144 == 0 && (a.M / 144) * (cout_pad / 256) >= 200 &&
-                              !env_on("LT_CONV_NO_SMALL144");
+        // 1440 L2-stream-bound 128 x 64 tiles of the generic kernel
+        const bool small144 = pw && q0.wfrag && !no6 && a.k_pad % 64 == 0 && a.k_pad <= 256 && a.M % 144 == 0 && (a.M / 144) * (cout_pad / 256) >= 200;
         const bool want5 = v5e ? v5e[0] == '1' : ((nblk5 >= 200 && tiles_m5 * BM3 - a.M <= a.M / 16 && a.k_pad >= 64) || small144);
         if (fits5 && want5) {
             if (q0.wfrag32 && a.k_pad % 64 == 0) {       // weights packed for the 32x32x16 MFMA (plan built with LT_CONV_V7=1): conv_igemm7
@@ -1136,17 +1132,11 @@ int conv3_try(int dtype, const ConvArgs& a, int cout_pad, int nphase, int max_ta
         // stores with the next one's loads better than one big tile per CU (measured: 128x64 beats this kernel below K = 512)
         if (a.k_pad < 512) return 0;
     }
-    static const bool w8 = env_on("LT_CONV_V3_W8");   // A/B: eight waves (2 per SIMD) instead of twelve
     // (a role-specialised variant -- four compute waves + four loader waves, conv_igemm4 -- was 10-15 % faster per layer on dense data
     // and a wash inside the forward: removed in round 2)
     int rc;
-    if (w8) {
-        if (BN == 128) rc = pw ? launch3<128, 1, 2>(a, cout_pad, max_taps, s) : launch3<128, 2, 2>(a, cout_pad, max_taps, s);
-        else rc = pw ? launch3<64, 1, 2>(a, cout_pad, max_taps, s) : launch3<64, 2, 2>(a, cout_pad, max_taps, s);
-    } else {
-        if (BN == 128) rc = pw ? launch3<128, 1, 3>(a, cout_pad, max_taps, s) : launch3<128, 2, 3>(a, cout_pad, max_taps, s);
-        else rc = pw ? launch3<64, 1, 3>(a, cout_pad, max_taps, s) : launch3<64, 2, 3>(a, cout_pad, max_taps, s);
-    }
+    if (BN == 128) rc = pw ? launch3<128, 1>(a, cout_pad, max_taps, s) : launch3<128, 2>(a, cout_pad, max_taps, s);
+    else rc = pw ? launch3<64, 1>(a, cout_pad, max_taps, s) : launch3<64, 2>(a, cout_pad, max_taps, s);
     return rc == LT_OK ? 1 : rc;
 }
 

@@ -94,9 +94,9 @@ pmcconv)
   cd $R
   ;;
 abenv)
-  # in-session A/B of env switches (two interleaved rounds each): baseline, no residual prefetch, no uniform-tap path, no halo kernel
+  # in-session A/B of env switches (two interleaved rounds each): baseline, no 288-row kernels, no XCD tile remap, no persistent halo kernel
   for round in 1 2; do
-    for v in ${ABVARS:-base LT_CONV_NO_V3 LT_CONV_NO_XCD LT_HALO_NO_PERSIST LT_HALO_NO_H7 LT_HALO_NO_LDR}; do
+    for v in ${ABVARS:-base LT_CONV_NO_V3 LT_CONV_NO_XCD LT_HALO_NO_PERSIST}; do
       # LIB_<name>: an A/B build of the library (lt_build.build_variant), else an env switch read by the kernels' dispatchers
       case $v in
         base) E="LT_AB=base" ;;
@@ -121,7 +121,7 @@ PYEOF
   for lib in base nomma noepi noa nob; do
     for pers in persist onetile; do
       E="LT_AB=1"; [ $lib != base ] && E="LT_HIP_LIB=$L/liblt_hip_abl_$lib.so"
-      P="LT_AB2=1"; [ $pers = onetile ] && P="LT_HALO_NO_PERSIST=1 LT_HALO_NO_RING=1"
+      P="LT_AB2=1"; [ $pers = onetile ] && P="LT_HALO_NO_PERSIST=1"
       [ $pers = onetile ] && ONLY="v2v 3^3 32->32,v2v 7^3" || ONLY="${ABL_LAYERS:-v2v 3^3 32->32,v2v 7^3,rn l3,rn l2 1x1 128,rn l1 1x1}"
       echo "== ablate lib=$lib halo=$pers" | tee -a $OUT/ablate.log
       env $E $P timeout 300 python tools/conv_bench.py --batch 16 --only "$ONLY" --variants auto --residual --rounds 3 2>&1 | grep -v amdgpu.ids | tee -a $OUT/ablate.log
