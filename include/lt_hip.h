@@ -341,8 +341,16 @@ int lt_triangulate_dlt_bwd(const float* proj, const float* points, const float* 
  *   completely, no pre-zeroing), grad_conf B,NV,C or NULL.  Autograd semantics of op.py:113-162: nothing flows to the grid / projections;
  *   depth <= 0 samples pass no gradient but their zero takes part in the view softmax, d out/d x_v = w_v (1 + x_v - out); 'max': the first
  *   maximal view; LT_AGG_CONF: g * conf_v and grad_conf_v = sum over voxels of g * x_v; LT_AGG_CONF_NORM: conf is the RAW head output,
- *   normalised over the views as in the forward (triangulation.py:268-269), grad_conf is the gradient of the raw values.  NV <= 8,
- *   C % 4 == 0.  A deterministic GATHER (bitwise repeatable; no global atomics): workspace from lt_unproject_bwd_workspace (bytes for the
+ *   normalised over the views as in the forward (triangulation.py:268-269), grad_conf is the gradient of the raw values.  1 <= NV <= 32
+ *   (more is LT_ERR_UNSUPPORTED: the many-view kernels' LDS copies and the finalizer's workgroup are sized by it), C % 4 == 0.  Three
+ *   launches over a workspace, K0 taps, K1 per-view gradient of the sampled values, K2 gather; K0 and K2 take any NV.  NV <= 8: K1 keeps
+ *   every view's sample in registers (a 4- and an 8-view form), as do the confidence finalizer and the scatter.  9 <= NV <= 32: K1 walks
+ *   the views without per-view registers -- sum / conf / conf_norm in groups of 8 views (one group per workgroup, the 8-view kernel's
+ *   arithmetic and partial sums: a view's gradients are the bits the 8-view kernel gives for it), softmax / max in three passes over the
+ *   views (max, sums, gradients) that sample again in each -- and the finalizer and the scatter have many-view forms of their own.
+ *   Workspace per sample and view, each block rounded up to 256 bytes per sample: nvox * C * 4 (dxs, K1's output: 1.04 GB per sample at
+ *   31 views, 64^3 voxels, C = 32) + nvox * 20 (tap records) + nbricks * 16 (bounding boxes, nbricks = product of ceil(v / 4)) +
+ *   min(2048, ceil(nvox * C / 1024)) * C * 8 (confidence partials).  A deterministic GATHER (bitwise repeatable; no global atomics): workspace from lt_unproject_bwd_workspace (bytes for the
  *   whole batch; with less -- at least one sample's share -- the batch is walked in chunks).  C > 64 or not a power of two (and
  *   LT_UNPROJ_BWD_ATOMICS=1): the round-2 scatter by float atomics (no workspace, not repeatable, no conf_norm).
  * lt_softargmax3d_bwd: probs B,J,nvox and kp B,J,3 are the forward's outputs; grad_kp B,J,3; an optional SPARSE gradient on the

@@ -25,6 +25,8 @@
 // (LDS float atomics) took 9.0 ms, 3.1 ms with the atomic replaced by a plain store -- LDS float atomics run at a small fraction of the
 // LDS rate -- and 0.8 ms without the hit loop.  The round-2 scatter kernel stays reachable (LT_UNPROJ_BWD_ATOMICS=1) as the A/B
 // reference and for configurations the gather does not take (C > 64 or not a power of two).
+// More than 8 views (up to UB_MANYV = 32): K0 and K2 as they are; K1, the confidence finalizer and the scatter have many-view forms below that
+// hold no per-view register array (the host entry dispatches on NV > UB_MAXV; nothing changes for NV <= 8).
 #include <stdlib.h>
 
 #include "lt_common.h"
@@ -338,6 +340,290 @@ __global__ void unproj_gconf_finalize_kernel(const UnprojBwdArgs a, int nblk1) {
     for (int v = 0; v < a.NV; ++v) a.gconf[((long long)b * a.NV + v) * a.C + c] = (float)s[v];
 }
 
+// ---- more than UB_MAXV views ----------------------------------------------------------------------------------------------------------------
+// Nothing below keeps a per-view register array sized by NV.  The three aggregations that are separable over the views once the confidence
+// sum is known (sum, conf, conf_norm) run in GROUPS of up to UB_MAXV views, one group per workgroup (grid z), with the 8-view kernel's
+// confidence-gradient accumulators and partial sums; softmax and max, which need statistics over all views (and have no confidence
+// gradient), walk the views in passes and sample again in each, as the forward's any-NV branch does.  The gather-path kernels read K0's tap
+// records (project_taps' own output) instead of projecting again, so they never touch the projection rows; the confidences are read once
+// per workgroup into LDS.  The arithmetic is that of sample_views / view_gradients, expression for expression.
+constexpr int UB_MANYV = 32;     // view limit of the many-view kernels: their LDS copies and the finalizer's workgroup shape are sized by it
+
+// one view's sample of one voxel / channel vector: the bilinear sum of sample_views
+template <typename T>
+__device__ __forceinline__ void sample_one_view(const T* fm, const Tap& t, int w, int C, float (&x)[4]) {
+    float t0[4], t1[4], t2[4], t3[4];
+    ld4<T>(fm + (long long)(t.y[0] * w + t.x[0]) * C, t0); ld4<T>(fm + (long long)(t.y[1] * w + t.x[1]) * C, t1);
+    ld4<T>(fm + (long long)(t.y[2] * w + t.x[2]) * C, t2); ld4<T>(fm + (long long)(t.y[3] * w + t.x[3]) * C, t3);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = t0[e] * t.k[0] + t1[e] * t.k[1] + t2[e] * t.k[2] + t3[e] * t.k[3];
+}
+
+// K0's tap record (txy, tw) back as the Tap that project_taps returned for it
+__device__ __forceinline__ Tap tap_of_record(int xy, const float4 k, int h, int w) {
+    Tap t;
+    t.x0 = (xy & 0xffff) - 1; t.y0 = (xy >> 16) - 1;
+    const int xwc = min(max(t.x0, 0), w - 1), xec = min(max(t.x0 + 1, 0), w - 1);
+    const int ync = min(max(t.y0, 0), h - 1), ysc = min(max(t.y0 + 1, 0), h - 1);
+    t.x[0] = xwc; t.x[1] = xec; t.x[2] = xwc; t.x[3] = xec;
+    t.y[0] = ync; t.y[1] = ync; t.y[2] = ysc; t.y[3] = ysc;
+    t.k[0] = k.x; t.k[1] = k.y; t.k[2] = k.z; t.k[3] = k.w;
+    return t;
+}
+
+// softmax / max over any number of views: view_gradients' arithmetic with the samples recomputed per pass.  sample(v, x) gives view v's
+// sampled vector, emit(v, dx, sampled) takes d out / d x_v times the upstream gradient in view order (sampled: sample(v) was the last
+// call of sample).  Pass 1: the max as an fmaxf chain / the first maximal view; pass 2: s and tt in view order; pass 3: dx_v.
+template <class Sample, class Emit>
+__device__ __forceinline__ void cross_view_gradients(int agg, int NV, const float (&g)[4], Sample sample, Emit emit) {
+    float x[4], dx[4];
+    if (agg == LT_AGG_SOFTMAX) {
+        float m[4], s[4] = {0.f, 0.f, 0.f, 0.f}, tt[4] = {0.f, 0.f, 0.f, 0.f}, out[4];
+        sample(0, m);
+        for (int v = 1; v < NV; ++v) {
+            sample(v, x);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], x[e]);
+        }
+        for (int v = 0; v < NV; ++v) {
+            sample(v, x);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float ex = expf(x[e] - m[e]); s[e] += ex; tt[e] += x[e] * ex; }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[e] = __fdiv_rn(tt[e], s[e]);
+        for (int v = 0; v < NV; ++v) {
+            sample(v, x);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float ex = expf(x[e] - m[e]); dx[e] = g[e] * __fdiv_rn(ex, s[e]) * (1.0f + x[e] - out[e]); }
+            emit(v, dx, true);
+        }
+    } else {                                            // LT_AGG_MAX: torch.max(dim), gradient to the FIRST maximal view
+        float best[4];
+        int am[4] = {0, 0, 0, 0};
+        sample(0, best);
+        for (int v = 1; v < NV; ++v) {
+            sample(v, x);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (x[e] > best[e]) { best[e] = x[e]; am[e] = v; }
+        }
+        for (int v = 0; v < NV; ++v) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dx[e] = v == am[e] ? g[e] : 0.f;
+            emit(v, dx, false);
+        }
+    }
+}
+
+// K1 for NV > UB_MAXV, softmax / max: grid (nblk1, B), one lane per (voxel, 4-channel vector) as in unproj_dx_kernel; per view and pass one
+// tap record (20 bytes, the same for the C / 4 lanes of a voxel) and four 16-byte taps.
+// gfx950 resource usage: fp32 maps 64 VGPRs and 8 waves per SIMD, bf16 maps 68 VGPRs and 7 waves; no LDS, no scratch
+template <typename T>
+__global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdArgs a) {
+    const int tpv = a.C >> 2;
+    const long long items = a.nvox * tpv;
+    const int b = blockIdx.y;
+    const long long hw = (long long)a.h * a.w;
+    const T* feats = (const T*)a.feats + (long long)b * a.NV * hw * a.C;
+    const float* gout = a.gout + (long long)b * a.nvox * a.C;
+    float* dxs = a.dxs + (long long)b * a.NV * a.nvox * a.C;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < items; q += (long long)gridDim.x * 256) {
+        const long long vox = q / tpv;
+        const int c0 = (int)(q - vox * tpv) * 4;
+        float g[4];
+        ld4<float>(gout + vox * a.C + c0, g);
+        const int* txy = a.txy + (long long)b * a.NV * a.nvox + vox;
+        const float4* tw = a.tw + (long long)b * a.NV * a.nvox + vox;
+        auto sample = [&](int v, float (&x)[4]) {
+            const Tap t = tap_of_record(txy[(long long)v * a.nvox], tw[(long long)v * a.nvox], a.h, a.w);
+            sample_one_view<T>(feats + v * hw * a.C + c0, t, a.w, a.C, x);
+        };
+        auto emit = [&](int v, const float (&dx)[4], bool) {
+            *(float4*)(dxs + ((long long)v * a.nvox + vox) * a.C + c0) = make_float4(dx[0], dx[1], dx[2], dx[3]);
+        };
+        cross_view_gradients(a.agg, a.NV, g, sample, emit);
+    }
+}
+
+// K1 for NV > UB_MAXV, sum / conf / conf_norm: grid (nblk1, B, ceil(NV / UB_MAXV)), workgroup z works on views [z * UB_MAXV, ...) with
+// unproj_dx_kernel's lane mapping, accumulators and fp64 workgroup partials (same nblk1, same order: the partials of a view are the bits
+// the 8-view kernel gives for it).  d out / d x_v per channel (c_v, or c_v / sum over ALL views for conf_norm) is computed once per
+// workgroup into LDS; the maps are sampled only where a confidence gradient is asked for.
+// gfx950 resource usage: fp32 maps 79 VGPRs and 6 waves per SIMD, bf16 maps 81 VGPRs and 5 waves; 6 KB LDS, no scratch
+template <typename T>
+__global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdArgs a) {
+    __shared__ float red[256][4];
+    __shared__ float coef[UB_MAXV][64];
+    const int tpv = a.C >> 2;
+    const long long items = a.nvox * tpv;
+    const int b = blockIdx.y;
+    const int vg = blockIdx.z * UB_MAXV, nv = min(UB_MAXV, a.NV - vg);
+    const long long hw = (long long)a.h * a.w;
+    const T* feats = (const T*)a.feats + ((long long)b * a.NV + vg) * hw * a.C;
+    const float* gout = a.gout + (long long)b * a.nvox * a.C;
+    float* dxs = a.dxs + ((long long)b * a.NV + vg) * a.nvox * a.C;
+    const bool is_conf = a.agg == LT_AGG_CONF || a.agg == LT_AGG_CONF_NORM;
+    const bool want_gc = a.gconf != nullptr;
+    if (is_conf) {
+        for (int i = threadIdx.x; i < nv * a.C; i += 256) {
+            const int v = i / a.C, c = i - v * a.C;
+            const float* cf = a.conf + (long long)b * a.NV * a.C + c;
+            float cv = cf[(vg + v) * a.C];
+            if (a.agg == LT_AGG_CONF_NORM) {
+                float cs = 0.f;
+                for (int u = 0; u < a.NV; ++u) cs += cf[u * a.C];
+                cv = __fdiv_rn(cv, cs);
+            }
+            coef[v][c] = cv;
+        }
+        __syncthreads();
+    }
+    float gc[UB_MAXV][4];
+#pragma unroll
+    for (int v = 0; v < UB_MAXV; ++v)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gc[v][e] = 0.f;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < items; q += (long long)gridDim.x * 256) {
+        const long long vox = q / tpv;
+        const int c0 = (int)(q - vox * tpv) * 4;
+        float g[4];
+        ld4<float>(gout + vox * a.C + c0, g);
+        const int* txy = a.txy + ((long long)b * a.NV + vg) * a.nvox + vox;
+        const float4* tw = a.tw + ((long long)b * a.NV + vg) * a.nvox + vox;
+#pragma unroll
+        for (int v = 0; v < UB_MAXV; ++v)
+            if (v < nv) {
+                float4 d = make_float4(g[0], g[1], g[2], g[3]);
+                if (is_conf) {
+                    const float4 k = *(const float4*)&coef[v][c0];
+                    d = make_float4(g[0] * k.x, g[1] * k.y, g[2] * k.z, g[3] * k.w);
+                }
+                *(float4*)(dxs + ((long long)v * a.nvox + vox) * a.C + c0) = d;
+                if (want_gc) {
+                    float x[4];
+                    const Tap t = tap_of_record(txy[(long long)v * a.nvox], tw[(long long)v * a.nvox], a.h, a.w);
+                    sample_one_view<T>(feats + v * hw * a.C + c0, t, a.w, a.C, x);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) gc[v][e] += g[e] * x[e];
+                }
+            }
+    }
+    if (!want_gc) return;
+    const int cl = threadIdx.x % tpv;
+    for (int v = 0; v < nv; ++v) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[threadIdx.x][e] = gc[v][e];
+        __syncthreads();
+        if (threadIdx.x < tpv) {
+            double s[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int t = threadIdx.x; t < 256; t += tpv)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s[e] += (double)red[t][e];
+            double* dst = a.gcpart + (((long long)b * gridDim.x + blockIdx.x) * a.NV + vg + v) * a.C + cl * 4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dst[e] = s[e];
+        }
+    }
+}
+
+// unproj_gconf_finalize_kernel for NV > UB_MAXV: one workgroup per (sample, 8 channels) of 32 x 8 threads, thread (v, c) adds view v's
+// partials in workgroup order; the conf_norm chain rule then reads every view's sum from LDS, in view order and in fp64 as the 8-view
+// finalizer does (each thread for itself: the same S and dot in every thread of a channel).
+// gfx950 resource usage: 54 VGPRs, 2 KB LDS, no scratch; 8 waves per SIMD
+constexpr int UB_FIN_C = 8;
+__global__ __launch_bounds__(UB_MANYV * UB_FIN_C) void unproj_gconf_finalize_many_kernel(const UnprojBwdArgs a, int nblk1) {
+    __shared__ double sv[UB_MANYV][UB_FIN_C];
+    const int cc = a.C < UB_FIN_C ? a.C : UB_FIN_C;                       // channels per workgroup (C = 4: half of the threads idle)
+    const int chunks = a.C / cc;
+    const int b = blockIdx.x / chunks, ci = threadIdx.x % UB_FIN_C, v = threadIdx.x / UB_FIN_C;
+    const int c = (blockIdx.x - b * chunks) * cc + ci;
+    const bool mine = ci < cc && v < a.NV;
+    double t = 0.0;
+    if (mine)
+        for (int k = 0; k < nblk1; ++k) t += a.gcpart[(((long long)b * nblk1 + k) * a.NV + v) * a.C + c];
+    sv[v][ci] = t;
+    __syncthreads();
+    if (!mine) return;
+    if (a.agg == LT_AGG_CONF_NORM) {
+        const float* cf = a.conf + (long long)b * a.NV * a.C + c;
+        double S = 0.0, dot = 0.0;
+        for (int u = 0; u < a.NV; ++u) S += (double)cf[u * a.C];
+        for (int u = 0; u < a.NV; ++u) dot += sv[u][ci] * (double)cf[u * a.C] / S;
+        t = (t - dot) / S;
+    }
+    a.gconf[((long long)b * a.NV + v) * a.C + c] = (float)t;
+}
+
+// round-2 scatter for NV > UB_MAXV (same semantics as unproject_bwd_kernel: zeroed outputs, float atomics): one view at a time, softmax /
+// max in the passes of cross_view_gradients with the projection redone in each; the sample's projection rows in LDS.
+// gfx950 resource usage: fp32 maps 90 VGPRs, bf16 maps 85 VGPRs; 1.5 KB LDS, no scratch; 5 waves per SIMD
+template <typename T>
+__global__ __launch_bounds__(256) void unproject_bwd_many_kernel(const UnprojBwdArgs a) {
+    __shared__ float Ps[UB_MANYV * 12];
+    const int tpv = a.C >> 2;
+    const long long items = a.nvox * tpv;
+    const int b = blockIdx.y;
+    const long long hw = (long long)a.h * a.w;
+    const T* feats = (const T*)a.feats + (long long)b * a.NV * hw * a.C;
+    float* gfeats = a.gfeats + (long long)b * a.NV * hw * a.C;
+    const float* coords = a.coords + (long long)b * a.nvox * 3;
+    const float* gout = a.gout + (long long)b * a.nvox * a.C;
+    for (int i = threadIdx.x; i < a.NV * 12; i += 256) Ps[i] = a.proj[(long long)b * a.NV * 12 + i];
+    __syncthreads();
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < items; q += (long long)gridDim.x * 256) {
+        const long long vox = q / tpv;
+        const int c0 = (int)(q - vox * tpv) * 4;
+        const float X0 = coords[vox * 3], X1 = coords[vox * 3 + 1], X2 = coords[vox * 3 + 2];
+        float g[4];
+        ld4<float>(gout + vox * a.C + c0, g);
+        Tap cur;
+        auto scatter = [&](int v, const float (&dx)[4]) {
+            float* gm = gfeats + v * hw * a.C + c0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float wk = cur.k[k];
+                if (wk != 0.f) {
+                    float* dst = gm + (long long)(cur.y[k] * a.w + cur.x[k]) * a.C;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) atomicAdd(dst + e, wk * dx[e]);
+                }
+            }
+        };
+        if (a.agg == LT_AGG_SOFTMAX || a.agg == LT_AGG_MAX) {
+            auto sample = [&](int v, float (&x)[4]) {
+                cur = project_taps(Ps + v * 12, X0, X1, X2, a.h, a.w);
+                sample_one_view<T>(feats + v * hw * a.C + c0, cur, a.w, a.C, x);
+            };
+            auto emit = [&](int v, const float (&dx)[4], bool sampled) {
+                if (!sampled) {
+                    if (dx[0] == 0.f && dx[1] == 0.f && dx[2] == 0.f && dx[3] == 0.f) return;      // max: a view that wins no channel
+                    cur = project_taps(Ps + v * 12, X0, X1, X2, a.h, a.w);
+                }
+                scatter(v, dx);
+            };
+            cross_view_gradients(a.agg, a.NV, g, sample, emit);
+        } else {
+            for (int v = 0; v < a.NV; ++v) {
+                cur = project_taps(Ps + v * 12, X0, X1, X2, a.h, a.w);
+                float dx[4] = {g[0], g[1], g[2], g[3]};
+                if (a.agg == LT_AGG_CONF) {
+                    const float* cf = a.conf + ((long long)b * a.NV + v) * a.C + c0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dx[e] = g[e] * cf[e];
+                    if (a.gconf) {
+                        float x[4];
+                        sample_one_view<T>(feats + v * hw * a.C + c0, cur, a.w, a.C, x);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) atomicAdd(a.gconf + ((long long)b * a.NV + v) * a.C + c0 + e, g[e] * x[e]);
+                    }
+                }
+                scatter(v, dx);
+            }
+        }
+    }
+}
+
 // K2: grid (tiles_x * tiles_y, NV, B), 4 waves; wave wv owns channels [wv * CW, (wv + 1) * CW) of the tile, CW = C / 4.
 // LDS tile: HALVES half tiles of G_TW / HALVES pixel columns, [half][row][column][C + 8 floats] (+16 per row, +32 per half: the four taps
 // of a voxel land in different banks).  With 4 * CW <= 32 lanes per hit (C <= 32) the two half-waves work on DIFFERENT hits at the same
@@ -574,8 +860,8 @@ extern "C" int lt_unproject_bwd(int32_t dtype, const void* feats, const float* p
                "lt_unproject_bwd: unknown aggregation %d", agg);
     const bool is_conf = agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM;
     LT_REQUIRE(!is_conf || conf, LT_ERR_INVALID, "lt_unproject_bwd: the conf aggregations need confidences");
-    LT_REQUIRE(B >= 1 && NV >= 1 && NV <= UB_MAXV && C >= 4 && C % 4 == 0 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_UNSUPPORTED,
-               "lt_unproject_bwd: needs 1 <= NV <= %d and C %% 4 == 0 (got NV=%d C=%d)", UB_MAXV, NV, C);
+    LT_REQUIRE(B >= 1 && NV >= 1 && NV <= UB_MANYV && C >= 4 && C % 4 == 0 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_UNSUPPORTED,
+               "lt_unproject_bwd: needs 1 <= NV <= %d and C %% 4 == 0 (got NV=%d C=%d)", UB_MANYV, NV, C);
     LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_bwd: feature maps too large");
     hipStream_t st = (hipStream_t)stream;
     UnprojBwdArgs a;
@@ -592,7 +878,10 @@ extern "C" int lt_unproject_bwd(int32_t dtype, const void* feats, const float* p
         if (a.gconf) LT_REQUIRE(hipMemsetAsync(a.gconf, 0, (size_t)B * NV * C * 4, st) == hipSuccess, LT_ERR_LAUNCH, "lt_unproject_bwd: hipMemsetAsync failed");
         const long long blocks = cdiv(a.nvox * (C / 4), 256);
         dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)B);
-        if (dtype == LT_F32) hipLaunchKernelGGL(unproject_bwd_kernel<float>, grid, dim3(256), 0, st, a);
+        if (NV > UB_MAXV) {
+            if (dtype == LT_F32) hipLaunchKernelGGL(unproject_bwd_many_kernel<float>, grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(unproject_bwd_many_kernel<bf16_t>, grid, dim3(256), 0, st, a);
+        } else if (dtype == LT_F32) hipLaunchKernelGGL(unproject_bwd_kernel<float>, grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(unproject_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, a);
         LT_CHECK_LAUNCH("lt_unproject_bwd(scatter)");
         return LT_OK;
@@ -627,7 +916,14 @@ extern "C" int lt_unproject_bwd(int32_t dtype, const void* feats, const float* p
         hipLaunchKernelGGL(unproj_taps_kernel, dim3((unsigned)cdiv(nbricks, 4), (unsigned)nb), dim3(256), 0, st, c);
         LT_CHECK_LAUNCH("lt_unproject_bwd(taps)");
         const dim3 g1((unsigned)nblk1, (unsigned)nb);
-        if (dtype == LT_F32) {
+        if (NV > UB_MAXV) {                                       // views in passes (softmax, max) or in groups of UB_MAXV (grid z)
+            const dim3 gz((unsigned)nblk1, (unsigned)nb, (unsigned)cdiv(NV, UB_MAXV));
+            if (agg == LT_AGG_SOFTMAX || agg == LT_AGG_MAX) {
+                if (dtype == LT_F32) hipLaunchKernelGGL(unproj_dx_passes_kernel<float>, g1, dim3(256), 0, st, c);
+                else hipLaunchKernelGGL(unproj_dx_passes_kernel<bf16_t>, g1, dim3(256), 0, st, c);
+            } else if (dtype == LT_F32) hipLaunchKernelGGL(unproj_dx_groups_kernel<float>, gz, dim3(256), 0, st, c);
+            else hipLaunchKernelGGL(unproj_dx_groups_kernel<bf16_t>, gz, dim3(256), 0, st, c);
+        } else if (dtype == LT_F32) {
             if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<float, 4>), g1, dim3(256), 0, st, c);
             else hipLaunchKernelGGL((unproj_dx_kernel<float, UB_MAXV>), g1, dim3(256), 0, st, c);
         } else {
@@ -635,7 +931,10 @@ extern "C" int lt_unproject_bwd(int32_t dtype, const void* feats, const float* p
             else hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, UB_MAXV>), g1, dim3(256), 0, st, c);
         }
         LT_CHECK_LAUNCH("lt_unproject_bwd(dx)");
-        if (c.gconf) {
+        if (c.gconf && NV > UB_MAXV) {
+            hipLaunchKernelGGL(unproj_gconf_finalize_many_kernel, dim3((unsigned)(nb * (C / (C < UB_FIN_C ? C : UB_FIN_C)))), dim3(UB_MANYV * UB_FIN_C), 0, st, c, nblk1);
+            LT_CHECK_LAUNCH("lt_unproject_bwd(gconf)");
+        } else if (c.gconf) {
             hipLaunchKernelGGL(unproj_gconf_finalize_kernel, dim3((unsigned)cdiv((long long)nb * C, 64)), dim3(64), 0, st, c, nblk1);
             LT_CHECK_LAUNCH("lt_unproject_bwd(gconf)");
         }
