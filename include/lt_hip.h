@@ -397,7 +397,8 @@ int lt_bn_stats_fwd(int32_t dtype, const void* x, int64_t rows, int32_t C, float
  *   slabs whose partial sums are added in a fixed order: workspace of lt_conv_wgrad_workspace(rows = N*Do*Ho*Wo, cout_pad, k_pad) bytes,
  *   may be 0).  For a transposed convolution swap the roles (dy := the layer's INPUT at its own resolution, x := the output gradient,
  *   stride 2): dw[ci][tap * Cout + co].
- * lt_adam_step  : torch.optim.Adam's single-tensor update (bias-corrected, eps outside the sqrt).
+ * lt_adam_step  : torch.optim.Adam's single-tensor update (bias-corrected, eps outside the sqrt).  beta1 / beta2 are doubles: 1 - beta and
+ *   1 - beta^step are formed in fp64 and then rounded to fp32, as torch does from its Python floats (1 - 0.999f is 1.3e-5 off 0.001).
  * -------------------------------------------------------------------------------------------*/
 int lt_bn_act_fwd(const void* y /* fp32, or bf16 with LT_BN_Y_BF16 */, const float* mean, const float* var, const float* gamma, const float* beta, const void* residual, void* z,
                   void* z_bf16 /* optional: a bf16 copy of z on the way (mixed-precision training), or NULL */, int64_t rows, int32_t C, float eps,
@@ -492,9 +493,9 @@ int lt_gather_f32_multi(const void* jobs, int32_t njobs, int32_t total_blocks, v
 /* the same update for MANY tensors in one launch.  jobs (device memory): njobs records of
  *   { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; int64_t n; float lr; int32_t first_block; }   (48 bytes)
  * with first_block = running sum of ceil(n / 1024) over the preceding jobs; total_blocks = that sum over all jobs. */
-int lt_adam_step_multi(const void* jobs, int32_t njobs, int32_t total_blocks, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+int lt_adam_step_multi(const void* jobs, int32_t njobs, int32_t total_blocks, double beta1, double beta2, float eps, float weight_decay, int32_t step,
                        void* stream);
-int lt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
+int lt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1, double beta2, float eps,
                  float weight_decay, int32_t step, void* stream);
 
 /* multiview.triangulate_batch_of_points (mvn/utils/multiview.py:141-183): confidence-weighted DLT.

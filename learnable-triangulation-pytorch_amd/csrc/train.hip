@@ -926,12 +926,12 @@ WgradPlan wgrad_plan(long long M, int cout_pad, int k_pad) {
 }
 
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float lr,
-                            float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2) {
+                            float beta1, float beta2, float omb1, float omb2, float eps, float weight_decay, float bc1, float bc2) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         float grad = g[i];
         if (weight_decay != 0.f) grad += weight_decay * p[i];
-        const float mi = beta1 * m[i] + (1.f - beta1) * grad;
-        const float vi = beta2 * v[i] + (1.f - beta2) * grad * grad;
+        const float mi = beta1 * m[i] + omb1 * grad;
+        const float vi = beta2 * v[i] + omb2 * grad * grad;
         m[i] = mi; v[i] = vi;
         // torch.optim.Adam (single tensor): denom = sqrt(v) / sqrt(bias_correction2) + eps; p -= lr / bias_correction1 * m / denom
         const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
@@ -942,8 +942,8 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 struct AdamJob { float* p; const float* g; float* m; float* v; long long n; float lr; int first_block; };
 
 // every parameter tensor of the model in ONE launch: a workgroup updates 1024 consecutive elements of the job its index falls into
-__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamJob* __restrict__ jobs, int njobs, float beta1, float beta2, float eps, float weight_decay,
-                                                         float bc1, float bc2) {
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamJob* __restrict__ jobs, int njobs, float beta1, float beta2, float omb1, float omb2, float eps,
+                                                         float weight_decay, float bc1, float bc2) {
     int lo = 0, hi = njobs - 1;
     while (lo < hi) {          // last job whose first_block <= blockIdx.x
         const int mid = (lo + hi + 1) >> 1;
@@ -958,8 +958,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamJob* __restri
         if (i >= j.n) break;
         float grad = j.g[i];
         if (weight_decay != 0.f) grad += weight_decay * j.p[i];
-        const float mi = beta1 * j.m[i] + (1.f - beta1) * grad;
-        const float vi = beta2 * j.v[i] + (1.f - beta2) * grad * grad;
+        const float mi = beta1 * j.m[i] + omb1 * grad;
+        const float vi = beta2 * j.v[i] + omb2 * grad * grad;
         j.m[i] = mi; j.v[i] = vi;
         const float denom = sqrtf(vi) / sq2 + eps;
         j.p[i] -= (j.lr / bc1) * (mi / denom);
@@ -1267,12 +1267,14 @@ extern "C" int lt_conv_wgrad(const float* dy, const float* x, const int32_t* tap
     return LT_OK;
 }
 
-extern "C" int lt_adam_step_multi(const void* jobs, int32_t njobs, int32_t total_blocks, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+// beta1 / beta2 are doubles: torch.optim.Adam forms 1 - beta and 1 - beta^step from the Python doubles and rounds the RESULTS to fp32.  From an fp32 beta2
+// (0.999f = 0.99900001287) 1 - beta2 is 0.00099998713: exp_avg_sq came out 1.3e-5 below torch's, relative, at every element
+extern "C" int lt_adam_step_multi(const void* jobs, int32_t njobs, int32_t total_blocks, double beta1, double beta2, float eps, float weight_decay, int32_t step,
                                   void* stream) {
     LT_REQUIRE(jobs && njobs >= 1 && total_blocks >= 1 && step >= 1, LT_ERR_INVALID, "lt_adam_step_multi: bad argument");
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const AdamJob*)jobs, njobs, beta1, beta2, eps, weight_decay,
-                       bc1, bc2);
+    const float bc1 = (float)(1.0 - pow(beta1, (double)step)), bc2 = (float)(1.0 - pow(beta2, (double)step));
+    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const AdamJob*)jobs, njobs, (float)beta1, (float)beta2,
+                       (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, bc1, bc2);
     LT_CHECK_LAUNCH("lt_adam_step_multi");
     return LT_OK;
 }
@@ -1398,13 +1400,13 @@ extern "C" int lt_gather_f32(const float* src, const int32_t* idx, float* dst, i
     return LT_OK;
 }
 
-extern "C" int lt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
+extern "C" int lt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1, double beta2, float eps,
                             float weight_decay, int32_t step, void* stream) {
     LT_REQUIRE(param && grad && exp_avg && exp_avg_sq && n >= 1 && step >= 1, LT_ERR_INVALID, "lt_adam_step: bad argument");
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+    const float bc1 = (float)(1.0 - pow(beta1, (double)step)), bc2 = (float)(1.0 - pow(beta2, (double)step));
     const long long blocks = cdiv(n, 256);
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
-                       (long long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2);
+                       (long long)n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, bc1, bc2);
     LT_CHECK_LAUNCH("lt_adam_step");
     return LT_OK;
 }

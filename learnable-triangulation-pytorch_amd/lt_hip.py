@@ -28,7 +28,7 @@ TILE_HALO = 20
 TILE3_288 = 30
 MAX_PHASES = 8
 
-vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 
 class ConvPhase(C.Structure):
@@ -190,7 +190,7 @@ SIGNATURES = {
     "lt_maxpool_bwd_dt": (C.c_int, [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32 * 3, vp]),
     "lt_convert_pad": (C.c_int, [i32, vp, i32, vp, i64, i32, i32, vp]),
     "lt_maxpool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32 * 3, vp]),
-    "lt_adam_step_multi": (C.c_int, [vp, i32, i32, f32, f32, f32, f32, i32, vp]),
+    "lt_adam_step_multi": (C.c_int, [vp, i32, i32, f64, f64, f32, f32, i32, vp]),
     "lt_add_f32": (C.c_int, [vp, vp, i64, vp]),
     "lt_pad_channels_f32": (C.c_int, [vp, vp, i64, i32, i32, vp]),
     "lt_zero": (C.c_int, [vp, i64, vp]),
@@ -217,7 +217,7 @@ SIGNATURES = {
     "lt_conv_wgrad_bf16_nhwc_ok": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32, i32, i32, i32, i32]),
     "lt_conv_wgrad_bf16_nhwc": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32, i32, i32, i32, i32, i32, vp, vp]),
     "lt_conv_wgrad": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32, i32, i32, i32, i32, i32, vp, vp]),
-    "lt_adam_step": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp]),
+    "lt_adam_step": (C.c_int, [vp, vp, vp, vp, i64, f32, f64, f64, f32, f32, i32, vp]),
     "lt_unproject_bwd_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
     "lt_unproject_bwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]),
     "lt_global_avgpool_bwd": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
