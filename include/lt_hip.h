@@ -387,6 +387,12 @@ int lt_bn_stats_fwd(int32_t dtype, const void* x, int64_t rows, int32_t C, float
  * lt_bn_act_bwd : its autograd: g = dz * relu mask; dbeta = sum g; dgamma = sum g x^; dy = gamma invstd (g - dbeta/n - x^ dgamma/n)
  *   (LT_BN_FROZEN in flags: mean / var are running statistics that do not depend on the batch: dy = gamma invstd g);
  *   dres (may be NULL) = the residual input's gradient, added to the buffer when accumulate_res.  workspace: lt_bn_act_bwd_workspace.
+ *   Optional outputs (fine-tuning with frozen parameters; the shape and flag checks come first, so a refusal names what is wrong):
+ *     dgamma = dbeta = NULL, dy given : frozen gamma / beta under a layer that still owes dy.  Batch statistics: the same three launches, the two
+ *       column sums are finalized into the workspace (its last 2 C floats) instead of caller memory; dy / dres / dy_bf16 bit for bit as with them.
+ *       LT_BN_FROZEN: dy = gamma invstd g is elementwise -- ONE launch, no reduce / finalize, workspace may be NULL.
+ *     dy = NULL, dgamma and dbeta given : only the parameter gradients (reduce + finalize, no apply pass); dy_bf16 and dres must be NULL too.
+ *     exactly one of dgamma / dbeta NULL, or dy, dgamma and dbeta all NULL : LT_ERR_INVALID.
  * lt_act_bwd    : layers without BatchNorm: dy = dz * mask(z, flags) (+ dres); LT_EPI_SIGMOID: dy = dz * z * (1 - z).  LT_EPI_RELU_PRE together
  *   with a residual is refused (LT_ERR_UNSUPPORTED): the sign of v cannot be rebuilt from z = relu(v) + res.
  * lt_channel_sum: out[c] (+)= sum over rows of x[row][c] (bias gradients), fp64 accumulation.

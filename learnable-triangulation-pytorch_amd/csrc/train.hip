@@ -133,6 +133,9 @@ __global__ void bn_bwd_finalize_kernel(const BnBwdArgs a) {
     a.dgamma[c] = (float)q;
 }
 
+// ELEM: frozen statistics and frozen gamma / beta (LT_BN_FROZEN without dgamma / dbeta): dy = gamma invstd g needs no column sum, so no reduce /
+// finalize launch runs in front of it and a.dgamma / a.dbeta / a.part are never read
+template <bool ELEM>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a) {
     const long long total = a.rows * a.C;
     const float inv_n = (a.flags & LT_BN_FROZEN) ? 0.f : 1.0f / (float)a.rows;       // frozen statistics: no batch-statistics terms
@@ -143,7 +146,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a) {
         const float dzv = ld1_f32_or_bf16(a.dz, (size_t)i, a.a16);
         const float g = bn_g(a, dzv, ld1_f32_or_bf16(a.y, (size_t)i, a.y16), r, c, xh);
         const float invstd = 1.0f / sqrtf(a.var[c] + a.eps);
-        st1_f32_or_bf16(a.dy, (size_t)i, a.a16, a.gamma[c] * invstd * (g - a.dbeta[c] * inv_n - xh * a.dgamma[c] * inv_n));
+        if constexpr (ELEM) st1_f32_or_bf16(a.dy, (size_t)i, a.a16, a.gamma[c] * invstd * g);
+        else st1_f32_or_bf16(a.dy, (size_t)i, a.a16, a.gamma[c] * invstd * (g - a.dbeta[c] * inv_n - xh * a.dgamma[c] * inv_n));
         if (a.dres) {
             const float dr = (a.flags & LT_EPI_RELU_POST) ? g : dzv;     // RELU_PRE / none: the residual is added after the activation
             st1_f32_or_bf16(a.dres, (size_t)i, a.a16, a.accumulate_res ? ld1_f32_or_bf16(a.dres, (size_t)i, a.a16) + dr : dr);
@@ -227,6 +231,8 @@ struct BnBwdFin {
 __global__ __launch_bounds__(256) void bn_bwd_finalize_vec_kernel(const BnBwdArgs a) { colsum_finalize<2>(a.part, a.C, a.nslab, BnBwdFin{a.dgamma, a.dbeta}); }
 
 // dy (and the residual's gradient): a thread keeps ONE float4 of channels -- its per-channel constants live in registers -- and walks rows
+// (ELEM as in bn_bwd_apply_kernel: the elementwise pass of a layer with frozen statistics and frozen gamma / beta)
+template <bool ELEM>
 __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const BnBwdArgs a, int nslab, int cw4, int rl_n) {
     const long long r0 = a.rows * blockIdx.x / nslab, r1 = a.rows * (blockIdx.x + 1) / nslab;
     const int rl = threadIdx.x / cw4, cv = threadIdx.x - rl * cw4;
@@ -238,7 +244,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const BnBwdArgs a
     for (int e = 0; e < 4; ++e) {
         invstd[e] = 1.0f / sqrtf(a.var[c + e] + a.eps);
         mean[e] = a.mean[c + e]; gam[e] = a.gamma[c + e]; bet[e] = a.beta[c + e];
-        k1[e] = gam[e] * invstd[e]; kb[e] = a.dbeta[c + e] * inv_n; kg[e] = a.dgamma[c + e] * inv_n;
+        k1[e] = gam[e] * invstd[e];
+        if constexpr (ELEM) kb[e] = kg[e] = 0.f;
+        else { kb[e] = a.dbeta[c + e] * inv_n; kg[e] = a.dgamma[c + e] * inv_n; }
     }
     const bool post = a.flags & LT_EPI_RELU_POST, pre = a.flags & LT_EPI_RELU_PRE;
     for (long long r = r0 + rl; r < r1; r += rl_n) {
@@ -256,7 +264,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const BnBwdArgs a
             if (post) mk = (v + rv[e]) > 0.f ? 1.f : 0.f;
             else if (pre) mk = v > 0.f ? 1.f : 0.f;
             const float g = dzv[e] * mk;
-            o[e] = k1[e] * (g - kb[e] - xh * kg[e]);
+            o[e] = ELEM ? k1[e] * g : k1[e] * (g - kb[e] - xh * kg[e]);
             dr[e] = post ? g : dzv[e];     // RELU_PRE / none: the residual is added after the activation
         }
         st4_f32_or_bf16(a.dy, off, a.a16, o[0], o[1], o[2], o[3]);
@@ -994,15 +1002,15 @@ extern "C" int lt_bn_act_fwd(const void* y, const float* mean, const float* var,
 
 extern "C" size_t lt_bn_act_bwd_workspace(int64_t rows, int32_t C) {
     const size_t generic = (size_t)slabs_for(rows) * C * 2 * sizeof(double), fast = colsum_workspace(rows, C, 2);
-    return generic > fast ? generic : fast;
+    // behind the partial sums: 2 C floats for the finalized column sums of a call without dgamma / dbeta (batch statistics still need them for dy)
+    return (generic > fast ? generic : fast) + (size_t)2 * C * sizeof(float);
 }
 
 extern "C" int lt_bn_act_bwd(const void* dz, const void* y, const void* residual, const float* mean, const float* var, const float* gamma,
                              const float* beta, void* dy, void* dy_bf16, float* dgamma, float* dbeta, void* dres, int32_t accumulate_res, int64_t rows,
                              int32_t C, float eps, int32_t flags, void* workspace, void* stream) {
-    LT_REQUIRE(dz && y && mean && var && gamma && beta && dy && dgamma && dbeta && workspace, LT_ERR_INVALID, "lt_bn_act_bwd: null argument");
-    LT_REQUIRE(rows >= 1 && C >= 1 && C <= 4096, LT_ERR_INVALID, "lt_bn_act_bwd: bad shape");
-    LT_REQUIRE(!dres || residual, LT_ERR_INVALID, "lt_bn_act_bwd: a residual gradient needs the residual");
+    LT_REQUIRE(dz && y && mean && var && gamma && beta, LT_ERR_INVALID, "lt_bn_act_bwd: null argument");
+    LT_REQUIRE(rows >= 1 && C >= 1 && C <= 4096, LT_ERR_INVALID, "lt_bn_act_bwd: bad shape (rows=%lld, C=%d)", (long long)rows, C);
     BnBwdArgs a;
     a.dz = dz; a.y = y; a.res = residual; a.mean = mean; a.var = var; a.gamma = gamma; a.beta = beta; a.part = (double*)workspace;
     a.dgamma = dgamma; a.dbeta = dbeta; a.dy = dy; a.dy16 = (bf16_t*)dy_bf16; a.dres = dres; a.eps = eps; a.flags = flags; a.C = C; a.nslab = slabs_for(rows);
@@ -1011,34 +1019,57 @@ extern "C" int lt_bn_act_bwd(const void* dz, const void* y, const void* residual
     a.a16 = (flags & LT_ACT_BF16) ? 1 : 0;
     LT_REQUIRE(!a.y16 || C % 4 == 0, LT_ERR_UNSUPPORTED, "lt_bn_act_bwd: a bf16 y needs C %% 4 == 0 (C=%d)", C);
     LT_REQUIRE(!a.a16 || (C % 4 == 0 && !dy_bf16), LT_ERR_UNSUPPORTED, "lt_bn_act_bwd: LT_ACT_BF16 needs C %% 4 == 0 and no separate bf16 copy of dy (C=%d)", C);
+    // the optional outputs: dgamma / dbeta come as a pair (frozen affine parameters: neither), dy with its companions dy_bf16 / dres (only the parameter
+    // gradients: none of the three)
+    LT_REQUIRE(!dgamma == !dbeta, LT_ERR_INVALID, "lt_bn_act_bwd: dgamma / dbeta are given together or not at all (dgamma %s, dbeta %s)", dgamma ? "given" : "NULL",
+               dbeta ? "given" : "NULL");
+    const bool want_pg = dgamma != nullptr;
+    LT_REQUIRE(want_pg || dy, LT_ERR_INVALID, "lt_bn_act_bwd: no output (dy, dgamma and dbeta are all NULL)");
+    LT_REQUIRE(dy || (!dy_bf16 && !dres), LT_ERR_INVALID, "lt_bn_act_bwd: without dy there is no apply pass: dy_bf16 and dres must be NULL too");
+    LT_REQUIRE(!dres || residual, LT_ERR_INVALID, "lt_bn_act_bwd: a residual gradient needs the residual");
+    const bool elem = !want_pg && (flags & LT_BN_FROZEN);          // frozen statistics, frozen gamma / beta: dy = gamma invstd g, one pass, no workspace
+    LT_REQUIRE(elem || workspace, LT_ERR_INVALID, "lt_bn_act_bwd: null workspace (only LT_BN_FROZEN without dgamma / dbeta runs without one)");
     hipStream_t st = (hipStream_t)stream;
     if (colsum_fast(C)) {
         const ColsumPlan p = colsum_plan(rows, C);
         a.nslab = p.nslab;
-        // rows in flight per thread: 4 / 8 / 2 measured 130.9 / 128.9 / 129.5 samples/s on the act16 step at 8 samples (one session); LT_BNBWD_ROWS=8 keeps the wider one
-        static const int nrows = [] { const char* e = getenv("LT_BNBWD_ROWS"); return e ? atoi(e) : 4; }();
-        if (a.a16 && a.y16) {
-            if (nrows == 8) hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<true, 8>), dim3(p.nslab, p.ncb), dim3(256), 0, st, a, p.cw4, p.rl);
-            else if (nrows == 2) hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<true, 2>), dim3(p.nslab, p.ncb), dim3(256), 0, st, a, p.cw4, p.rl);
-            else hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<true, 4>), dim3(p.nslab, p.ncb), dim3(256), 0, st, a, p.cw4, p.rl);
-        } else
-            hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<false, 4>), dim3(p.nslab, p.ncb), dim3(256), 0, st, a, p.cw4, p.rl);
-        LT_CHECK_LAUNCH("lt_bn_act_bwd(reduce)");
-        hipLaunchKernelGGL(bn_bwd_finalize_vec_kernel, dim3((unsigned)cdiv(C, COLSUM_FIN_C)), dim3(256), 0, st, a);
-        LT_CHECK_LAUNCH("lt_bn_act_bwd(finalize)");
+        if (!want_pg && !elem) {          // batch statistics: the two column sums are finalized into the workspace, behind the partials
+            a.dgamma = (float*)(a.part + (size_t)a.nslab * C * 2); a.dbeta = a.dgamma + C;
+        }
+        if (!elem) {
+            // rows in flight per thread: 4 / 8 / 2 measured 130.9 / 128.9 / 129.5 samples/s on the act16 step at 8 samples (one session); LT_BNBWD_ROWS=8 keeps the wider one
+            static const int nrows = [] { const char* e = getenv("LT_BNBWD_ROWS"); return e ? atoi(e) : 4; }();
+            if (a.a16 && a.y16) {
+                if (nrows == 8) hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<true, 8>), dim3(p.nslab, p.ncb), dim3(256), 0, st, a, p.cw4, p.rl);
+                else if (nrows == 2) hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<true, 2>), dim3(p.nslab, p.ncb), dim3(256), 0, st, a, p.cw4, p.rl);
+                else hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<true, 4>), dim3(p.nslab, p.ncb), dim3(256), 0, st, a, p.cw4, p.rl);
+            } else
+                hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<false, 4>), dim3(p.nslab, p.ncb), dim3(256), 0, st, a, p.cw4, p.rl);
+            LT_CHECK_LAUNCH("lt_bn_act_bwd(reduce)");
+            hipLaunchKernelGGL(bn_bwd_finalize_vec_kernel, dim3((unsigned)cdiv(C, COLSUM_FIN_C)), dim3(256), 0, st, a);
+            LT_CHECK_LAUNCH("lt_bn_act_bwd(finalize)");
+        }
+        if (!dy) return LT_OK;
         long long ns = rows / ((long long)p.rl * 2);          // >= 2 rows per thread, <= 4096 workgroups
         ns = ns < 1 ? 1 : ns > 4096 / p.ncb ? 4096 / p.ncb : ns;
-        hipLaunchKernelGGL(bn_bwd_apply_vec_kernel, dim3((unsigned)ns, p.ncb), dim3(256), 0, st, a, (int)ns, p.cw4, p.rl);
+        if (elem) hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<true>, dim3((unsigned)ns, p.ncb), dim3(256), 0, st, a, (int)ns, p.cw4, p.rl);
+        else hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<false>, dim3((unsigned)ns, p.ncb), dim3(256), 0, st, a, (int)ns, p.cw4, p.rl);
         LT_CHECK_LAUNCH("lt_bn_act_bwd(apply)");
         return LT_OK;
     }
     LT_REQUIRE(!dy_bf16, LT_ERR_UNSUPPORTED, "lt_bn_act_bwd: the bf16 copy of dy needs a channel count of the vector path (C=%d)", C);
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(a.nslab), dim3(256), 0, st, a);
-    LT_CHECK_LAUNCH("lt_bn_act_bwd(reduce)");
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0, st, a);
-    LT_CHECK_LAUNCH("lt_bn_act_bwd(finalize)");
+    if (!want_pg && !elem) { a.dgamma = (float*)(a.part + (size_t)a.nslab * C * 2); a.dbeta = a.dgamma + C; }
+    if (!elem) {
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(a.nslab), dim3(256), 0, st, a);
+        LT_CHECK_LAUNCH("lt_bn_act_bwd(reduce)");
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0, st, a);
+        LT_CHECK_LAUNCH("lt_bn_act_bwd(finalize)");
+    }
+    if (!dy) return LT_OK;
     const long long blocks = cdiv(rows * C, 256);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, a);
+    const unsigned nb = (unsigned)(blocks < 8192 ? blocks : 8192);
+    if (elem) hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(nb), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(nb), dim3(256), 0, st, a);
     LT_CHECK_LAUNCH("lt_bn_act_bwd(apply)");
     return LT_OK;
 }

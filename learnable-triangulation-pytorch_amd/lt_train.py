@@ -16,7 +16,10 @@ REPLAY the two launch lists (DESIGN.md "Training step").  The backward of a laye
 The weights are live (lt_gather_f32 from the Parameters into each layer's GEMM layout, index maps built at record time), the
 parameter gradients land in one flat arena (contiguous buckets for lt_dist.GradReducer).  fp32 throughout by default (the reference
 trains in fp32); ``mixed=True`` takes the convolutions and their input gradients to the bf16 MFMA (bf16 operand copies, fp32
-accumulation and storage).  All arithmetic is liblt_hip's, torch only owns the memory.  What the reference does with
+accumulation and storage).  All arithmetic is liblt_hip's, torch only owns the memory.
+``requires_grad == False`` means what it means to autograd: a frozen parameter gets no gradient slot and no gradient kernel, an activation carries a
+gradient only if something trainable produced it or lies in front of it, and a layer records only the parts of its backward that someone reads (its input
+gradient only into an input that carries one) -- none at all in front of the first trainable layer.  What the reference does with
 ``total_loss.backward()`` (train.py:233-236) arrives here through the autograd Function that wraps a network's training forward
 (mvn/models/triangulation.py), so ``torch.optim`` and hooks see ordinary ``.grad`` tensors.
 """
@@ -79,7 +82,9 @@ class TrainTape(E.Recorder):
         self.layer_outputs = []                                 # (label, output Act) of every convolution layer, in forward order
         self.grads = {}                                         # id(Act) -> (Act, gradient tensor of act.t's shape)
         self.momentum = momentum
-        self.no_grad_ids = set()                                # id(Act) of inputs that need no gradient (the images)
+        # id(Act) of the activations that carry NO gradient: the inputs declared so (no_grad(): the images, the outputs of a frozen inference plan) and
+        # every output of an op without a trainable parameter whose inputs all carry none (_derive).  An Act the tape has never seen carries one.
+        self.no_grad_ids = set()
         self.npre = 0
         self.stream = torch.cuda.current_stream(self.device).cuda_stream
         self._ws = torch.empty(1 << 16, dtype=torch.uint8, device=self.device)
@@ -175,8 +180,25 @@ class TrainTape(E.Recorder):
     def alloc(self, shape, dtype=None):
         return E.Act(torch.empty(shape, dtype=dtype or self.adt, device=self.device))
 
-    def release(self, act):            # activations are needed again by the backward: nothing is recycled
+    def release(self, act):            # every replay writes the same buffers, and the backward reads most of them again: nothing is recycled
         pass
+
+    # ---- where gradients are needed ----------------------------------------------------------------------------------------------
+    def no_grad(self, act):
+        """Declares ``act`` gradient-free (an input of the step that nothing trainable has produced)."""
+        self.no_grad_ids.add(id(act))
+        self.keep.append(act)          # (the id stays this Act's)
+        return act
+
+    def carries(self, act):
+        return act is not None and id(act) not in self.no_grad_ids
+
+    def _derive(self, out, inputs, trainable=False):
+        """``out`` carries a gradient iff the op that produced it has a trainable parameter or one of its inputs carries one; True if it does."""
+        if trainable or any(self.carries(i) for i in inputs):
+            return True
+        self.no_grad(out)
+        return False
 
     def const(self, t, dtype=None):
         return t.to(device=self.device, dtype=dtype or t.dtype).contiguous()
@@ -189,6 +211,8 @@ class TrainTape(E.Recorder):
         y = self.alloc((1, 1, 1, N, Cc))
         ac = self.acode
         self.do(lambda st: H.check(H.lib().lt_global_avgpool(ac, x.t.data_ptr(), y.t.data_ptr(), N, HW, Cc, st), "lt_global_avgpool"), "avgpool")
+        if not self._derive(y, (x,)):
+            return y
 
         def bwd():
             dy = self.grad_of(y)
@@ -199,7 +223,7 @@ class TrainTape(E.Recorder):
             if dx is None:
                 dx = torch.empty_like(x.t)
                 self._add_grad(x, dx)
-            self.do(lambda st: H.check(H.lib().lt_global_avgpool_bwd_dt(ac, dy.data_ptr(), dx.data_ptr(), N, HW, Cc, acc, st), "lt_global_avgpool_bwd"), "avgpool_bwd")
+            self.do(lambda st: H.check(H.lib().lt_global_avgpool_bwd_dt(ac, dy.data_ptr(), dx.data_ptr(), N, HW, Cc, acc, st), "lt_global_avgpool_bwd"), "avgpool_bwd @" + "x".join(map(str, x.shape[:4])))
         self.recorders.append(bwd)
         return y
 
@@ -410,7 +434,9 @@ class TrainTape(E.Recorder):
             self.do(lambda st: H.check(lib.lt_bn_act_fwd(y_raw.t.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(), H.ptr(rp),
                                                          z.t.data_ptr(), H.ptr(z16), rows, Cc, BN_EPS, flags, st), "lt_bn_act_fwd"), "bn_act %dx%d" % (rows, Cc))
             stats = (mean, var)
-        self.recorders.append(lambda: self._conv_bwd(x, weight, bias, bn, stride, pad, transposed, flags, residual, y_raw, stats, z))
+        trainable = any(q is not None and q.requires_grad for q in (weight, bias) + (tuple(bn[:2]) if bn is not None else ()))
+        if self._derive(z, (x, residual), trainable):          # (else: nothing trainable in this layer or in front of it -- no backward at all)
+            self.recorders.append(lambda: self._conv_bwd(x, weight, bias, bn, stride, pad, transposed, flags, residual, y_raw, stats, z))
         self.layer_outputs.append(("%s %s" % ("deconv" if transposed else "conv", "x".join(map(str, weight.shape))), z))      # diagnostics (tools/mixed_trace.py)
         return z
 
@@ -421,6 +447,8 @@ class TrainTape(E.Recorder):
         kk = (1, k, k) if nd == 2 else (k, k, k)
         ss = (1, s, s) if nd == 2 else (s, s, s)
         pp = (0, p, p) if nd == 2 else (p, p, p)
+        if not self._derive(y, (x,)):
+            return y
 
         def bwd():
             dy = self.grad_of(y)
@@ -435,7 +463,7 @@ class TrainTape(E.Recorder):
             N, D, Hh, W, Cc = x.shape
             ac = self.acode
             self.do(lambda st: H.check(H.lib().lt_maxpool_bwd_dt(ac, x.t.data_ptr(), dy.data_ptr(), dx.data_ptr(), N, D, Hh, W, Cc, H.i3(kk), H.i3(ss), H.i3(pp), st),
-                                       "lt_maxpool_bwd"))
+                                       "lt_maxpool_bwd"), "maxpool_bwd @" + "x".join(map(str, x.shape[:4])))
         self.recorders.append(bwd)
         return y
 
@@ -484,10 +512,16 @@ class TrainTape(E.Recorder):
             return
         Cout = z.shape[-1]
         rows = z.t.numel() // Cout
-        dy = torch.empty(z.t.shape, dtype=self.adt, device=self.device)
+        # what this layer owes: the input's gradient only if the input carries one, the residual's likewise, a parameter's only if it is trainable
+        need_dx = self.carries(x)
+        w_rg, b_rg = weight.requires_grad, bias is not None and bias.requires_grad
+        bn_rg = bn is not None and (bn[0].requires_grad or bn[1].requires_grad)
+        # dy feeds the input gradient, the weight gradient and the bias gradient; lt_bn_act_bwd writes dres in its apply pass only, lt_act_bwd always writes dy
+        need_dy = need_dx or w_rg or b_rg or bn is None or self.carries(residual) or not bn_rg
+        dy = torch.empty(z.t.shape, dtype=self.adt, device=self.device) if need_dy else None
         dres, acc_res = None, 0
         rp = residual.t if residual is not None else None
-        if residual is not None:
+        if self.carries(residual):
             dres = self.grad_of(residual)
             acc_res = 1 if dres is not None else 0
             if dres is None:
@@ -496,13 +530,16 @@ class TrainTape(E.Recorder):
         if bn is not None:
             gamma, beta, _, _ = bn
             mean, var = stats
-            dgamma, dbeta = self._grad_view(gamma), self._grad_view(beta)
+            dgamma = dbeta = None
+            if bn_rg:          # frozen gamma AND beta: the kernel computes neither sum (none at all with frozen statistics); one of the two: its twin goes to scratch
+                dgamma = self._grad_view(gamma) if gamma.requires_grad else torch.empty(Cout, dtype=torch.float32, device=self.device)
+                dbeta = self._grad_view(beta) if beta.requires_grad else torch.empty(Cout, dtype=torch.float32, device=self.device)
             self._ws_need(lib.lt_bn_act_bwd_workspace(rows, Cout))
             dy16 = None
-            if self.mixed and not self.act16 and id(x) not in self.no_grad_ids and Cout >= 4 and Cout & (Cout - 1) == 0:      # the input gradient's bf16 operand on the way
+            if self.mixed and not self.act16 and need_dx and Cout >= 4 and Cout & (Cout - 1) == 0:      # the input gradient's bf16 operand on the way
                 dy16 = torch.empty(dy.shape, dtype=torch.bfloat16, device=self.device)
             self.do(lambda st: H.check(lib.lt_bn_act_bwd(dz.data_ptr(), y_raw.t.data_ptr(), H.ptr(rp), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(),
-                                                         beta.data_ptr(), dy.data_ptr(), H.ptr(dy16), dgamma.data_ptr(), dbeta.data_ptr(), H.ptr(dres), acc_res, rows,
+                                                         beta.data_ptr(), H.ptr(dy), H.ptr(dy16), H.ptr(dgamma), H.ptr(dbeta), H.ptr(dres), acc_res, rows,
                                                          Cout, BN_EPS, flags, self._ws.data_ptr(), st), "lt_bn_act_bwd"), "bn_bwd %dx%d" % (rows, Cout))
         else:
             total = z.t.numel()
@@ -537,7 +574,7 @@ class TrainTape(E.Recorder):
         # lt_conv_fwd wants a power-of-two channel count on its input: dY widened with zero channels (17 joints -> 32) for the input gradient
         # (and, in the 16-bit step, for the octet pack of the weight gradient)
         dy_in, cpad = dy, Cout
-        if (Cout & (Cout - 1) or Cout < 4) and (self.act16 or id(x) not in self.no_grad_ids):
+        if (Cout & (Cout - 1) or Cout < 4) and ((self.act16 and w_rg) or need_dx):
             cpad = max(4, 1 << (Cout - 1).bit_length())
             if self.act16:
                 cpad = max(8, cpad)
@@ -650,8 +687,8 @@ class TrainTape(E.Recorder):
                 H.check(lib.lt_gather_f32(dw.data_ptr(), imap.data_ptr(), gview.data_ptr(), ng, st), "lt_gather_f32")      # into the Parameter's layout
             self.do(wgrad, label)
         self._grads_ready()
-        # ---- input gradient (skipped for the network input)
-        if id(x) in self.no_grad_ids:
+        # ---- input gradient (skipped where the input carries none: the network input, the output of a frozen part)
+        if not need_dx:
             return
         prev = self.grad_of(x)
         dya = E.Act(dy_in)

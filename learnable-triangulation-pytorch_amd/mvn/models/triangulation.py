@@ -97,14 +97,40 @@ class _VolTrainPlan:
             mixed, act16 = prec != "fp32", prec in ("act16", "fp8v2v")
             self.tape = tape = lt_train.TrainTape(device, params=list(model.parameters()), reducer=getattr(model, "grad_reducer", None), mixed=mixed, act16=act16,
                                                   fp8_3d=prec == "fp8v2v")
-            self.x_in = tape.alloc((B * NV, 1, Hh, W, E.min_cin_of(torch.bfloat16 if mixed else torch.float32)))
-            tape.no_grad_ids.add(id(self.x_in))
+            # a FULLY FROZEN backbone in eval() (no trainable parameter, no BatchNorm module in train()) is exactly the inference backbone: its feature map
+            # (and the vol_confidences head's output) come from an inference plan -- fused launches, folded BatchNorm, no activation kept -- and the tape
+            # starts at process_features.  LT_TRAIN_NO_FROZEN_PLAN=1 (read here, when the training plan is built) keeps it on the tape, backward pruned.
+            bb = model.backbone
+            self.frozen_plan = (os.environ.get("LT_TRAIN_NO_FROZEN_PLAN") != "1" and not any(p.requires_grad for p in bb.parameters()) and
+                                not any(c.training for c in bb.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm)))
+            # the plan's element type is the tape's activation type (bf16 for act16 / fp8v2v, fp32 for fp32); 'bf16' stores fp32, so the fp32 plan it is:
+            # the one conversion left is the tape's own cast of process_features' input to the bf16 MFMA operand
+            self.bb_dtype = torch.bfloat16 if act16 else torch.float32
+            if not self.frozen_plan:
+                self.x_in = tape.alloc((B * NV, 1, Hh, W, E.min_cin_of(torch.bfloat16 if mixed else torch.float32)))
+                tape.no_grad(self.x_in)
         tape = self.tape
         ac = tape.acode          # element type of the activations: fp32, or bf16 in the 16-bit-activation step
-        E.stage_images(x, self.x_in, st)
+        if self.frozen_plan:
+            bb_feats, bb_volc = self._frozen_backbone(x, st)
+            if first:          # the tape's gradient-free inputs: buffers of its own, so that a rebuilt plan (changed backbone weights) leaves the recorded pointers valid
+                self.f_in = tape.no_grad(tape.alloc(bb_feats.shape))
+                self.c_in = None if bb_volc is None else tape.no_grad(tape.alloc(bb_volc.shape, torch.float32))
+            f_in, c_in = self.f_in, self.c_in
+            assert f_in.t.dtype == bb_feats.t.dtype and f_in.shape == bb_feats.shape
+            cf = f_in.shape[-1]
+            H.check(lib.lt_convert_pad(ac, bb_feats.t.data_ptr(), ac, f_in.t.data_ptr(), f_in.t.numel() // cf, cf, cf, st), "lt_convert_pad")
+            if c_in is not None:
+                cc = c_in.shape[-1]
+                H.check(lib.lt_convert_pad(H.LT_F32, bb_volc.t.data_ptr(), H.LT_F32, c_in.t.data_ptr(), c_in.t.numel() // cc, cc, cc, st), "lt_convert_pad")
+        else:
+            E.stage_images(x, self.x_in, st)
         if first:
             # layers in front of the unprojection (its launch needs the map size, the geometry block the launch reads needs the maps' size too)
-            _, feats256, _, volc = model.backbone.record(tape, self.x_in, want_heatmaps=False)
+            if self.frozen_plan:
+                feats256, volc = self.f_in, self.c_in
+            else:
+                _, feats256, _, volc = model.backbone.record(tape, self.x_in, want_heatmaps=False)
             self.volc = volc          # conf / conf_norm: the vol_confidences head's sigmoid output, Act [1,1,1,B*NV,32] (pose_resnet.py:140-174)
             pf = model.process_features[0]
             self.feats = feats = tape.conv(feats256, pf.weight, pf.bias, None)
@@ -136,10 +162,12 @@ class _VolTrainPlan:
             tape.do(lambda s_: H.check(lib.lt_unproject_grid_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
                                                                  coords.data_ptr(), conf_p, vol.t.data_ptr(), B, NV, 32, h, w, V, agg, s_), "lt_unproject_grid_fwd"),
                     "unproject")
+            tape._derive(vol, (feats, volc))
+            need_f, need_c = tape.carries(feats), tape.carries(volc)
 
             def unproject_bwd():
                 dvol = tape.grad_of(vol)
-                if dvol is None:
+                if dvol is None or not (need_f or need_c):          # nothing trainable in front of the volume: no unprojection backward
                     return
                 gfe32 = torch.empty(feats.t.shape, dtype=torch.float32, device=device)                    # written completely by the gather (no zero fill)
                 gconf = None if volc is None else torch.empty_like(volc.t)
@@ -165,8 +193,9 @@ class _VolTrainPlan:
                     gfe = torch.empty(feats.t.shape, dtype=torch.bfloat16, device=device)
                     nfe = gfe.numel()
                     tape.do(lambda s_: H.check(lib.lt_convert_pad(H.LT_F32, gfe32.data_ptr(), H.LT_BF16, gfe.data_ptr(), nfe // 32, 32, 32, s_), "lt_convert_pad"), "cast")
-                tape.seed(feats, gfe)
-                if volc is not None:
+                if need_f:          # (the kernel computes both gradients; one that nothing in front needs is dropped here)
+                    tape.seed(feats, gfe)
+                if need_c:
                     tape.seed(volc, gconf)            # the head's backward (recorded earlier, so replayed later) starts from here
             tape.add_backward(unproject_bwd)
             self.logits = logits = model.volume_net.record(tape, vol)          # channels-last (B,V,V,V,J) fp32
@@ -192,6 +221,23 @@ class _VolTrainPlan:
         H.check(lib.lt_nhwc_to_nchw_f32(ac, self.feats.t.data_ptr(), feats_out.data_ptr(), B * NV, 32, h * w, 32, st), "lt_nhwc_to_nchw_f32")
         base_points = self.geo[o_cen:o_rot].reshape(B, 3).clone()
         return self.kp.clone(), self.probs.clone(), feats_out, self.coords.clone(), base_points, position, sides
+
+    def _frozen_backbone(self, x, st):
+        """The frozen, eval-mode backbone of this step on the inference kernel set, on the step's stream: (features Act, vol_confidences Act | None) of an
+        inference plan recorded by PoseResNet.record on a PlanBuilder, kept in the backbone's own plan cache -- whose weights fingerprint (data_ptr and
+        version counter of every parameter and buffer of the backbone) rebuilds it after an in-place change or a load_state_dict."""
+        bb, N, dt = self.model.backbone, self.B * self.NV, self.bb_dtype
+
+        def build():
+            b = E.PlanBuilder(self.device, dt)
+            inp = b.alloc((N, 1, self.Hh, self.W, E.min_cin_of(dt)))
+            _, feats, _, volc = bb.record(b, inp, want_heatmaps=False)
+            return {"plan": b.finish(), "inp": inp, "outs": (feats, volc)}
+
+        P = bb._plan_for(("train-frozen", N, self.Hh, self.W, dt, self.device), build)
+        E.stage_images(x, P["inp"], st)
+        P["plan"].run_eager(st)
+        return P["outs"]
 
     def backward(self, g_kp, idx, val, g_dense=None):
         B, J = self.probs.shape[:2]
@@ -271,7 +317,7 @@ class _AlgTrainPlan:
             mixed = prec != "fp32"
             self.tape = tape = lt_train.TrainTape(device, params=list(model.parameters()), reducer=getattr(model, "grad_reducer", None), mixed=mixed, act16=prec == "act16")
             self.x_in = tape.alloc((N, 1, Hh, W, E.min_cin_of(torch.bfloat16 if mixed else torch.float32)))
-            tape.no_grad_ids.add(id(self.x_in))
+            tape.no_grad(self.x_in)
         tape = self.tape
         E.stage_images(x, self.x_in, st)
         if first:
@@ -568,8 +614,9 @@ class VolumetricTriangulationNet(_PlannedNet):
         result carries the autograd node whose backward is liblt_hip's (lt_train.py).  Same 7-tuple as the inference forward.  Every
         ``volume_aggregation_method`` trains: for conf / conf_norm the gradient reaches the backbone through the vol_confidences head as
         well (GlobalAveragePoolingHead, pose_resnet.py:140-174)."""
-        # BatchNorm modules in train() use batch statistics (and update the running ones); modules left in eval() -- a frozen backbone while V2V
-        # is fine-tuned, say -- normalise with their frozen running statistics (round 3; lt_train.TrainTape.conv)
+        # BatchNorm modules in train() use batch statistics (and update the running ones); modules left in eval() normalise with their frozen
+        # RUNNING STATISTICS (round 3; lt_train.TrainTape.conv) -- that alone freezes no parameter.  Frozen PARAMETERS are requires_grad_(False): the tape
+        # records no gradient for them and no backward in front of the first trainable layer (both are in the plan key below)
         bns = [c for c in self.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm) and c.training]
         if any(c.momentum is None or abs(c.momentum - 0.1) > 1e-12 or not c.track_running_stats or not c.affine for c in bns):
             raise NotImplementedError("BatchNorm with a momentum other than 0.1, without running statistics or without affine parameters")
@@ -773,8 +820,9 @@ class AlgebraicTriangulationNet(_PlannedNet):
         ``use_confidences``, the alg_confidences head included -- runs its recorded training step (lt_train.TrainTape: batch-statistics
         BatchNorm, liblt_hip backward); 2D soft-argmax, confidence normalisation and the DLT are autograd nodes over liblt_hip kernels
         (lt_softargmax2d_bwd, lt_triangulate_dlt_bwd: what autograd derives through torch.svd in the reference).  Same 4-tuple as inference."""
-        # BatchNorm modules in train() use batch statistics (and update the running ones); modules left in eval() -- a frozen backbone while V2V
-        # is fine-tuned, say -- normalise with their frozen running statistics (round 3; lt_train.TrainTape.conv)
+        # BatchNorm modules in train() use batch statistics (and update the running ones); modules left in eval() normalise with their frozen
+        # RUNNING STATISTICS (round 3; lt_train.TrainTape.conv) -- that alone freezes no parameter.  Frozen PARAMETERS are requires_grad_(False): the tape
+        # records no gradient for them and no backward in front of the first trainable layer (both are in the plan key below)
         bns = [c for c in self.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm) and c.training]
         if any(c.momentum is None or abs(c.momentum - 0.1) > 1e-12 or not c.track_running_stats or not c.affine for c in bns):
             raise NotImplementedError("BatchNorm with a momentum other than 0.1, without running statistics or without affine parameters")
