@@ -309,9 +309,14 @@ int lt_cuboid_from_keypoints(const float* keypoints_3d, int32_t B, int32_t J, in
  * op.integrate_tensor_3d_with_coordinates (mvn/utils/op.py:84-96):
  *   p = softmax_over_voxels(mult * logits[b,j,:])  (or relu(mult*logits) when softmax == 0)
  *   kp[b,j,:] = sum_vox p * coords[b,vox,:]
- * logits: fp32, element (b,j,vox) at b*J*nvox + vox*ld + j when channels_last (ld >= J) else
- * b*J*nvox.. (b*J + j)*nvox + vox.  probs: B,J,nvox fp32 (always joint-major, the API layout) or
- * NULL.  workspace: lt_softargmax3d_workspace() bytes.
+ * logits: fp32, element (b,j,vox) at b*J*nvox + vox*ld + j when channels_last (dense rows: ld == J;
+ * ld > J is LT_ERR_UNSUPPORTED, ld < J LT_ERR_INVALID) else b*J*nvox.. (b*J + j)*nvox + vox.
+ * J <= 32 (more: LT_ERR_UNSUPPORTED).  probs: B,J,nvox fp32 (always joint-major, the API layout) or
+ * NULL: the joints are bitwise the same with and without it.  workspace: lt_softargmax3d_workspace() bytes.
+ * PRECONDITION: every logit is FINITE.  The online softmax rescales its running sums by
+ * exp(m_old - m_new); a lane whose first logit is -inf computes exp(-inf - -inf) = NaN there, where
+ * torch.softmax gives that voxel probability 0 (+inf and NaN are NaN in torch too).  No layer of
+ * these networks produces an infinity in front of the soft-argmax, and nothing is checked on the device.
  * -------------------------------------------------------------------------------------------*/
 size_t lt_softargmax3d_workspace(int32_t B, int32_t J, int64_t nvox);
 int lt_softargmax3d_fwd(const float* logits, const float* coords, float mult, int32_t softmax, int32_t channels_last,
