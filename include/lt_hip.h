@@ -271,6 +271,10 @@ int lt_rotate_points(const float* x, const float* rot, float* y, int64_t n, void
  * One 16-byte channel vector per lane (a voxel's C channels = consecutive lanes -> every bilinear tap
  * and every output voxel is one contiguous run); 4x4x16 voxel bricks per workgroup keep the projected
  * footprint compact in L1/L2; with B % 8 == 0 sample b is pinned to XCD b % 8 (private L2).
+ * Precondition of all four entries below, documented and not guarded: proj and coords (or pos, center, rot, step
+ * of the grid entries) are FINITE.  A NaN or infinite pixel coordinate gives a NaN sample in the reference's CPU
+ * grid_sample and a zero sample in both kernels here (their in-range tests are float comparisons, which a NaN
+ * fails); nobody should rely on either.  Feature maps may hold anything; only a masked view's map is never read.
  * -------------------------------------------------------------------------------------------*/
 int lt_unproject_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf,
                      void* out, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1,
