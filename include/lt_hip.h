@@ -326,6 +326,30 @@ size_t lt_softargmax3d_workspace(int32_t B, int32_t J, int64_t nvox);
 int lt_softargmax3d_fwd(const float* logits, const float* coords, float mult, int32_t softmax, int32_t channels_last,
                         int32_t ld, float* kp, float* probs, int32_t B, int32_t J, int64_t nvox, void* workspace,
                         void* stream);
+/* lt_softargmax3d_fwd plus per-joint statistics of the 3D heatmap, out of the same pass that writes the probabilities (mvn.utils.volumetric.keypoint_stats
+ * states them in numpy fp64).  Arguments, layouts, limits and refusals are lt_softargmax3d_fwd's (stats or peak_index NULL: LT_ERR_INVALID); kp and
+ * probs are bit for bit what it writes for the same arguments; probs may be NULL (the same pass without the stores).  workspace:
+ * lt_softargmax3d_stats_workspace() bytes.  stats: B,J,8 fp32 records {peak, mass, cxx, cxy, cxz, cyy, cyz, czz}; peak_index: B,J int32.
+ * Per (b, j), with x_i = fp32(mult * logit_i) over the nvox voxels (the one rounding the kernels make):
+ *   softmax != 0, p = softmax(x):
+ *     peak_index  the smallest flat voxel index i at which x_i is maximal (the index order of probs[b, j])
+ *     peak        p at peak_index; equal to probs[b, j, peak_index] bit for bit (that value is 1 / S)
+ *     mass        1.0f
+ *     centre      the returned fp32 joint kp[b, j]
+ *     cov         sum_i p_i (c_i - centre)(c_i - centre)^T, mm^2, in the frame of coords (rotated cuboids need no special handling)
+ *   softmax == 0, w = relu(x), joints unnormalised as in lt_softargmax3d_fwd:
+ *     mass        sum_i w_i
+ *     peak_index  as above, on x (not on w)
+ *     peak        relu(x_peak) / mass, one fp32 division
+ *     centre      kp[b, j] / mass, one fp32 division per coordinate of the two returned numbers
+ *     cov         sum_i (w_i / mass)(c_i - centre)(c_i - centre)^T
+ *     mass == 0 gives peak = 0 and cov = 0
+ * The moments are taken about the centre, never as a difference of raw second moments.  Lanes accumulate in fp32, the chunk partials are combined
+ * in fp64 in a fixed order, there are no float atomics: two calls give equal bits.  nvox must fit an int32. */
+size_t lt_softargmax3d_stats_workspace(int32_t B, int32_t J, int64_t nvox);
+int lt_softargmax3d_stats_fwd(const float* logits, const float* coords, float mult, int32_t softmax, int32_t channels_last, int32_t ld,
+                              float* kp, float* probs, float* stats, int32_t* peak_index, int32_t B, int32_t J, int64_t nvox, void* workspace,
+                              void* stream);
 
 /* op.integrate_tensor_2d (mvn/utils/op.py:11-47) on N,J,h,w fp32 heatmaps (joint-major): 2D
  * soft-argmax; writes coords N,J,2 (x,y) and the normalised heatmaps (or NULL). */
@@ -863,6 +887,12 @@ int lt_plan_forward_cascade(lt_plan* plan, const float* images, const double* K_
  *   LT_ERR_INVALID (the message names the sample): a sample without a valid view (volumetric plans) or with fewer than two (algebraic, cascade).
  *   LT_ERR_UNSUPPORTED: an LT_MODEL_RANSAC plan.  Results are bit-identical to the Python host's forward with batch["view_mask"]. */
 int lt_plan_set_view_mask(lt_plan* plan, const uint8_t* mask_host);
+/* Per-joint statistics of the volumetric joints (the definitions of lt_softargmax3d_stats_fwd, with the plan's volume_multiplier and volume_softmax):
+ * with both pointers non-NULL every later forward of a volumetric or cascade plan also writes stats_dev (DEVICE, B,J,8 fp32 records {peak, mass, cxx,
+ * cxy, cxz, cyy, cyz, czz}) and peak_index_dev (DEVICE, B,J int32) on the forward's stream; every other output keeps its bits.  Both NULL: back to the
+ * plain tail.  One NULL: LT_ERR_INVALID.  LT_MODEL_ALG / LT_MODEL_RANSAC plans: LT_ERR_UNSUPPORTED.  The tail op is eager and reads these fields when it
+ * runs, so the call may come before or after the plan's first forward and nothing is captured again. */
+int lt_plan_set_keypoint_stats(lt_plan* plan, float* stats_dev, int32_t* peak_index_dev);
 int lt_plan_info(const lt_plan* plan, lt_plan_info_t* info);
 void lt_plan_destroy(lt_plan* plan);
 

@@ -293,6 +293,9 @@ struct lt_plan {
     // results
     Act feats, vol, logits, volc;
     float* coords = nullptr; float* kp = nullptr; float* probs = nullptr; void* sa_ws = nullptr;
+    // per-joint statistics (lt_plan_set_keypoint_stats): the caller's device buffers, read by the eager tail op when it runs, and the larger workspace of
+    // lt_softargmax3d_stats_fwd, allocated by the first call that asks for them
+    float* ks_stats = nullptr; int32_t* ks_index = nullptr; void* ks_ws = nullptr;
     Act algc;                                   // alg_confidences head output [1,1,1,N,J] fp32 (algebraic plans with use_confidences)
     float* hm_nchw = nullptr; float* kp_hm = nullptr; int64_t* kp_i64 = nullptr;          // heatmaps N,J,h,w; soft-argmax N,J,2 (heatmap px); argmax N,J,2
     int hm_h = 0, hm_w = 0;
@@ -1002,6 +1005,9 @@ struct lt_plan {
             const float* lp = (const float*)logits.p; const float* cp = coords; void* ws = sa_ws; lt_plan* self = this;
             float* kpd = kp; float* prd = probs;
             ops.push_back([=](hipStream_t s) {
+                if (self->ks_stats)
+                    return lt_softargmax3d_stats_fwd(lp, cp, mult, sm, cl, J, self->out_kp ? self->out_kp : kpd, self->out_probs ? self->out_probs : prd, self->ks_stats,
+                                                     self->ks_index, B, J, nvox, self->ks_ws, s);
                 return lt_softargmax3d_fwd(lp, cp, mult, sm, cl, J, self->out_kp ? self->out_kp : kpd, self->out_probs ? self->out_probs : prd, B, J, nvox, ws, s);
             });
         }
@@ -1434,6 +1440,21 @@ extern "C" int lt_plan_set_view_mask(lt_plan* p, const uint8_t* mask_host) {
     lt_plan* holder = p->model == MODEL_CASCADE ? p->sub_vol : p;
     holder->mask_cur = m;
     holder->mask_dirty = true;
+    return LT_OK;
+}
+
+extern "C" int lt_plan_set_keypoint_stats(lt_plan* p, float* stats_dev, int32_t* peak_index_dev) {
+    const char* who = "lt_plan_set_keypoint_stats";
+    LT_REQUIRE(p, LT_ERR_INVALID, "%s: null plan", who);
+    LT_REQUIRE(p->model == 0 || p->model == MODEL_CASCADE, LT_ERR_UNSUPPORTED, "%s: the plan is %s; the statistics are those of the volumetric joints' 3D heatmaps", who,
+               plan_kind_name(p));
+    LT_REQUIRE((stats_dev == nullptr) == (peak_index_dev == nullptr), LT_ERR_INVALID, "%s: stats_dev and peak_index_dev come together (both NULL: the plain tail)", who);
+    lt_plan* v = p->model == MODEL_CASCADE ? p->sub_vol : p;
+    if (stats_dev && !v->ks_ws) {
+        const int V = v->cfg.volume_size;
+        PL_TRY(v->dev_alloc(lt_softargmax3d_stats_workspace(v->cfg.B, v->cfg.num_joints, (int64_t)V * V * V), &v->ks_ws));
+    }
+    v->ks_stats = stats_dev; v->ks_index = peak_index_dev;
     return LT_OK;
 }
 

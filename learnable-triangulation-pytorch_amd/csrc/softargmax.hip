@@ -307,6 +307,237 @@ __global__ __launch_bounds__(256) void sa3_probs_kernel(const SA3Args a) {
     }
 }
 
+// ---- per-joint statistics of the 3D heatmap (lt_softargmax3d_stats_fwd): the probabilities pass, which knows M, S and the joint, also reduces the six
+// second moments of the heatmap ABOUT the returned joint (never E[xx^T] - mu mu^T: at world coordinates of 1e5 mm that difference has no digits left
+// in fp32) and the lexicographic (largest x, smallest voxel index) pair.  Lanes and workgroups add in fp32 in a fixed order, the chunk records are
+// combined in fp64 by one wave per (b, joint) as in sa3_finalize_kernel: no atomics, the same bits on every call.
+constexpr int SS_REC = 8;                    // chunk record: cxx cxy cxz cyy cyz czz, x at the peak, the peak's voxel index (int bits)
+
+struct SA3StatArgs {
+    SA3Args a;
+    float* spart;      // [B][J][snchunks][8]
+    float* out;        // [B][J][8] = peak, mass, cxx, cxy, cxz, cyy, cyz, czz
+    int* peak_index;   // [B][J]
+    int snchunks;
+};
+
+struct SSAcc { float xx, xy, xz, yy, yz, zz, px; int pi; };
+struct SSNorm { float M, S, cx, cy, cz; };
+
+__device__ __forceinline__ void ss_init(SSAcc& s) {
+    s.xx = s.xy = s.xz = s.yy = s.yz = s.zz = 0.f;
+    s.px = -INFINITY; s.pi = 0x7fffffff;
+}
+
+// M, S and the centre of one (b, joint): the returned joint, divided by the mass in ReLU mode (whose joints are not normalised); no mass: no weights
+__device__ __forceinline__ SSNorm ss_norm(const SA3Args& a, long long bj) {
+    SSNorm n;
+    n.M = a.stats[bj * 2]; n.S = a.stats[bj * 2 + 1];
+    const float kx = a.kp[bj * 3], ky = a.kp[bj * 3 + 1], kz = a.kp[bj * 3 + 2];
+    if (a.softmax) { n.cx = kx; n.cy = ky; n.cz = kz; }
+    else if (n.S > 0.f) { n.cx = __fdiv_rn(kx, n.S); n.cy = __fdiv_rn(ky, n.S); n.cz = __fdiv_rn(kz, n.S); }
+    else n.cx = n.cy = n.cz = 0.f;
+    return n;
+}
+
+// the value the probabilities pass writes for x = mult * logit (the expressions of sa3_probs_kernel / sa3_probs_planar_kernel) ...
+__device__ __forceinline__ float ss_prob(const SA3Args& a, const SSNorm& n, float x) {
+    return a.softmax ? __fdiv_rn(expf(x - n.M), n.S) : fmaxf(x, 0.f);
+}
+
+// ... and the normalised weight of that voxel in the moments
+__device__ __forceinline__ float ss_weight(const SA3Args& a, const SSNorm& n, float p) {
+    return a.softmax ? p : (n.S > 0.f ? __fdiv_rn(p, n.S) : 0.f);
+}
+
+__device__ __forceinline__ void ss_peak(float& px, int& pi, float x2, int i2) {
+    if (x2 > px || (x2 == px && i2 < pi)) { px = x2; pi = i2; }
+}
+
+// one voxel of a lane's run; a lane visits its voxels in increasing index order, so the strict comparison keeps the first of equal maxima
+__device__ __forceinline__ void ss_add(SSAcc& s, float x, float w, float dx, float dy, float dz, int idx) {
+    const float wx = w * dx, wy = w * dy, wz = w * dz;
+    s.xx += wx * dx; s.xy += wx * dy; s.xz += wx * dz; s.yy += wy * dy; s.yz += wy * dz; s.zz += wz * dz;
+    if (x > s.px) { s.px = x; s.pi = idx; }
+}
+
+__device__ __forceinline__ void ss_wave_reduce(SSAcc& s) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        s.xx += __shfl_xor(s.xx, off); s.xy += __shfl_xor(s.xy, off); s.xz += __shfl_xor(s.xz, off);
+        s.yy += __shfl_xor(s.yy, off); s.yz += __shfl_xor(s.yz, off); s.zz += __shfl_xor(s.zz, off);
+        const float x2 = __shfl_xor(s.px, off);
+        const int i2 = __shfl_xor(s.pi, off);
+        ss_peak(s.px, s.pi, x2, i2);
+    }
+}
+
+__device__ __forceinline__ void ss_store(float* o, const SSAcc& s) {
+    o[0] = s.xx; o[1] = s.xy; o[2] = s.xz; o[3] = s.yy; o[4] = s.yz; o[5] = s.zz; o[6] = s.px; o[7] = __int_as_float(s.pi);
+}
+
+// Generic planar and channels-last logits, the chunks of sa3_probs_kernel.  Here a WAVE owns joints (wave, wave + 4, ... : at most SS_JW of the 32) and its
+// lanes walk the 256 voxels of an iteration 64 at a time, so the state is SS_JW accumulators however many joints there are, a joint's record needs one
+// wave reduction per chunk and no LDS, and the probabilities leave as 256-byte rows.  Channels-last logits come through the staged tile of the other
+// kernels (row stride odd: lanes on consecutive voxels read distinct banks).
+constexpr int SS_JW = 8;
+
+template <bool CL>
+__global__ __launch_bounds__(256) void sa3_probs_stats_kernel(const SA3StatArgs sa) {
+    extern __shared__ float smem[];
+    const SA3Args& a = sa.a;
+    const int ts = a.J | 1;
+    float* tile = smem;                       // CL only: [256][ts]
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* lg = a.logits + (long long)b * a.J * a.nvox;
+    const float* cd = a.coords + (long long)b * a.nvox * 3;
+    float* pr = a.probs ? a.probs + (long long)b * a.J * a.nvox : nullptr;
+    SSAcc acc[SS_JW];
+    SSNorm nm[SS_JW];
+#pragma unroll
+    for (int q = 0; q < SS_JW; ++q) {
+        ss_init(acc[q]);
+        nm[q] = ss_norm(a, (long long)b * a.J + min(wave + 4 * q, a.J - 1));
+    }
+    for (int it = 0; it < SA_ITERS; ++it) {
+        const long long vox0 = (long long)chunk * SA_CHUNK + it * 256;
+        if (vox0 >= a.nvox) break;
+        const int nv = (int)min((long long)256, a.nvox - vox0);
+        if (CL) {
+            __syncthreads();
+            stage_cl(a, lg, vox0, nv, tile, ts);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int v = k * 64 + lane;
+            if (v < nv) {
+                const long long vox = vox0 + v;
+                const float cx = cd[vox * 3], cy = cd[vox * 3 + 1], cz = cd[vox * 3 + 2];
+#pragma unroll
+                for (int q = 0; q < SS_JW; ++q) {
+                    const int j = wave + 4 * q;
+                    if (j < a.J) {
+                        const float x = a.mult * (CL ? tile[v * ts + j] : lg[(long long)j * a.nvox + vox]);
+                        const float p = ss_prob(a, nm[q], x);
+                        if (pr) pr[(long long)j * a.nvox + vox] = p;
+                        ss_add(acc[q], x, ss_weight(a, nm[q], p), cx - nm[q].cx, cy - nm[q].cy, cz - nm[q].cz, (int)vox);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < SS_JW; ++q) {
+        const int j = wave + 4 * q;
+        if (j < a.J) {
+            ss_wave_reduce(acc[q]);
+            if (lane == 0) ss_store(sa.spart + (((long long)b * a.J + j) * sa.snchunks + chunk) * SS_REC, acc[q]);
+        }
+    }
+}
+
+// Vectorised planar logits: the chunks and the lane-to-voxel map of sa3_partial_planar_kernel (a lane keeps the coordinates of its SAP_V groups of four
+// voxels in registers and the workgroup walks the joints, the next joint's loads in flight), so the coordinates are read once per sample, not once per
+// joint as a per-plane grid like sa3_probs_planar_kernel's would.  Per joint one wave reduction, the four waves through LDS.
+__global__ __launch_bounds__(256) void sa3_probs_stats_planar_kernel(const SA3StatArgs sa) {
+    __shared__ float red[32 * 4 * SS_REC];    // [J][wave][8]
+    const SA3Args& a = sa.a;
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const float* lg = a.logits + (long long)b * a.J * a.nvox;
+    const float* cd = a.coords + (long long)b * a.nvox * 3;
+    float* pr = a.probs ? a.probs + (long long)b * a.J * a.nvox : nullptr;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long vox[SAP_V];
+    bool ok[SAP_V];
+    sa_f32x4 ca[SAP_V], cb[SAP_V], cc[SAP_V];   // x0 y0 z0 x1 | y1 z1 x2 y2 | z2 x3 y3 z3
+#pragma unroll
+    for (int k = 0; k < SAP_V; ++k) {
+        const long long v = (long long)chunk * SAP_CHUNK + k * 1024 + threadIdx.x * 4;
+        ok[k] = v < a.nvox;                  // nvox % 4 == 0: a group is inside or outside as a whole
+        vox[k] = ok[k] ? v : 0;              // outside: group 0 is loaded in its place and never used
+        const sa_f32x4* c4 = (const sa_f32x4*)(cd + vox[k] * 3);
+        ca[k] = c4[0]; cb[k] = c4[1]; cc[k] = c4[2];
+    }
+    sa_f32x4 cur[SAP_V], nxt[SAP_V];
+#pragma unroll
+    for (int k = 0; k < SAP_V; ++k) cur[k] = *(const sa_f32x4*)(lg + vox[k]);
+#pragma unroll 1
+    for (int j = 0; j < a.J; ++j) {
+        const float* nl = lg + (long long)min(j + 1, a.J - 1) * a.nvox;
+#pragma unroll
+        for (int k = 0; k < SAP_V; ++k) nxt[k] = *(const sa_f32x4*)(nl + vox[k]);
+        const SSNorm n = ss_norm(a, (long long)b * a.J + j);
+        SSAcc s;
+        ss_init(s);
+#pragma unroll
+        for (int k = 0; k < SAP_V; ++k) {
+            if (ok[k]) {
+                const float x0 = a.mult * cur[k][0], x1 = a.mult * cur[k][1], x2 = a.mult * cur[k][2], x3 = a.mult * cur[k][3];
+                sa_f32x4 p;
+                p[0] = ss_prob(a, n, x0); p[1] = ss_prob(a, n, x1); p[2] = ss_prob(a, n, x2); p[3] = ss_prob(a, n, x3);
+                if (pr) *(sa_f32x4*)(pr + (long long)j * a.nvox + vox[k]) = p;
+                const int i0 = (int)vox[k];
+                ss_add(s, x0, ss_weight(a, n, p[0]), ca[k][0] - n.cx, ca[k][1] - n.cy, ca[k][2] - n.cz, i0);
+                ss_add(s, x1, ss_weight(a, n, p[1]), ca[k][3] - n.cx, cb[k][0] - n.cy, cb[k][1] - n.cz, i0 + 1);
+                ss_add(s, x2, ss_weight(a, n, p[2]), cb[k][2] - n.cx, cb[k][3] - n.cy, cc[k][0] - n.cz, i0 + 2);
+                ss_add(s, x3, ss_weight(a, n, p[3]), cc[k][1] - n.cx, cc[k][2] - n.cy, cc[k][3] - n.cz, i0 + 3);
+            }
+        }
+        ss_wave_reduce(s);
+        if (lane == 0) ss_store(red + (j * 4 + wave) * SS_REC, s);
+#pragma unroll
+        for (int k = 0; k < SAP_V; ++k) cur[k] = nxt[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < a.J) {
+        const int j = threadIdx.x;
+        SSAcc s;
+        ss_init(s);
+        for (int w = 0; w < 4; ++w) {
+            const float* r = red + (j * 4 + w) * SS_REC;
+            s.xx += r[0]; s.xy += r[1]; s.xz += r[2]; s.yy += r[3]; s.yz += r[4]; s.zz += r[5];
+            ss_peak(s.px, s.pi, r[6], __float_as_int(r[7]));
+        }
+        ss_store(sa.spart + (((long long)b * a.J + j) * sa.snchunks + chunk) * SS_REC, s);
+    }
+}
+
+// one wave per (b, joint): the chunk records in fp64, then the record the caller reads
+__global__ void sa3_stats_finalize_kernel(const SA3StatArgs sa) {
+    const SA3Args& a = sa.a;
+    const int bj = blockIdx.x, lane = threadIdx.x;
+    const float* p = sa.spart + (long long)bj * sa.snchunks * SS_REC;
+    double m[6] = {0, 0, 0, 0, 0, 0};
+    float px = -INFINITY;
+    int pi = 0x7fffffff;
+    for (int c = lane; c < sa.snchunks; c += 64) {
+        const float* r = p + c * SS_REC;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) m[i] += (double)r[i];
+        ss_peak(px, pi, r[6], __float_as_int(r[7]));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) m[i] += __shfl_xor(m[i], off);
+        const float x2 = __shfl_xor(px, off);
+        const int i2 = __shfl_xor(pi, off);
+        ss_peak(px, pi, x2, i2);
+    }
+    if (lane == 0) {
+        const float M = a.stats[bj * 2], S = a.stats[bj * 2 + 1];
+        float* o = sa.out + (long long)bj * 8;
+        // softmax: the expression of the probabilities pass at the peak voxel (x == M there, so 1 / S); ReLU: relu(x) / mass, nothing over no mass
+        o[0] = a.softmax ? __fdiv_rn(expf(px - M), S) : (S > 0.f ? __fdiv_rn(fmaxf(px, 0.f), S) : 0.f);
+        o[1] = a.softmax ? 1.f : S;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) o[2 + i] = (float)m[i];
+        sa.peak_index[bj] = pi;
+    }
+}
+
 // planar logits whose volumes are float4-addressable take the vectorised kernels
 bool sa3_planar_vec(const SA3Args& a) {
     static const bool off = env_on("LT_SA3_NO_VEC");
@@ -549,14 +780,17 @@ extern "C" size_t lt_softargmax3d_workspace(int32_t B, int32_t J, int64_t nvox) 
     return (size_t)((int64_t)B * J * nchunks * SA_REC + (int64_t)B * J * 2) * sizeof(float);
 }
 
-extern "C" int lt_softargmax3d_fwd(const float* logits, const float* coords, float mult, int32_t softmax, int32_t channels_last,
-                                   int32_t ld, float* kp, float* probs, int32_t B, int32_t J, int64_t nvox, void* workspace,
-                                   void* stream) {
-    LT_REQUIRE(logits && coords && kp && workspace, LT_ERR_INVALID, "lt_softargmax3d_fwd: null argument");
-    LT_REQUIRE(B >= 1 && J >= 1 && nvox >= 1, LT_ERR_INVALID, "lt_softargmax3d_fwd: bad shape");
-    LT_REQUIRE(J <= 32, LT_ERR_UNSUPPORTED, "lt_softargmax3d_fwd: J=%d > 32 (split the joints into groups of <= 32)", J);
-    LT_REQUIRE(!channels_last || ld >= J, LT_ERR_INVALID, "lt_softargmax3d_fwd: ld < J");
-    LT_REQUIRE(!channels_last || ld == J, LT_ERR_UNSUPPORTED, "lt_softargmax3d_fwd: channels-last logits must be dense (ld == J)");
+// the one body of lt_softargmax3d_fwd and lt_softargmax3d_stats_fwd: partial and finalize kernels, then the probabilities pass -- the plain one, or
+// (stats != NULL) the one that also reduces the statistics, followed by their finalize
+static int sa3_forward(const char* who, const float* logits, const float* coords, float mult, int32_t softmax, int32_t channels_last, int32_t ld, float* kp,
+                       float* probs, float* stats, int32_t* peak_index, bool with_stats, int32_t B, int32_t J, int64_t nvox, void* workspace, void* stream) {
+    LT_REQUIRE(logits && coords && kp && workspace, LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(!with_stats || (stats && peak_index), LT_ERR_INVALID, "%s: null stats or peak_index", who);
+    LT_REQUIRE(B >= 1 && J >= 1 && nvox >= 1, LT_ERR_INVALID, "%s: bad shape", who);
+    LT_REQUIRE(!with_stats || nvox <= 0x7fffffff, LT_ERR_UNSUPPORTED, "%s: nvox %lld does not fit the int32 peak index", who, (long long)nvox);
+    LT_REQUIRE(J <= 32, LT_ERR_UNSUPPORTED, "%s: J=%d > 32 (split the joints into groups of <= 32)", who, J);
+    LT_REQUIRE(!channels_last || ld >= J, LT_ERR_INVALID, "%s: ld < J", who);
+    LT_REQUIRE(!channels_last || ld == J, LT_ERR_UNSUPPORTED, "%s: channels-last logits must be dense (ld == J)", who);
     SA3Args a;
     a.logits = logits; a.coords = coords; a.kp = kp; a.probs = probs; a.mult = mult; a.softmax = softmax; a.J = J; a.ld = ld; a.nvox = nvox;
     a.nchunks = (int)((nvox + SA_CHUNK - 1) / SA_CHUNK);
@@ -575,7 +809,18 @@ extern "C" int lt_softargmax3d_fwd(const float* logits, const float* coords, flo
     if (rc != LT_OK) return rc;
     hipLaunchKernelGGL(sa3_finalize_kernel, dim3(B * J), dim3(64), 0, st, a, B);
     LT_CHECK_LAUNCH("lt_softargmax3d_fwd(finalize)");
-    if (probs) {
+    if (with_stats) {
+        SA3StatArgs sa;
+        sa.a = a; sa.out = stats; sa.peak_index = peak_index; sa.snchunks = a.nchunks;
+        sa.spart = (float*)((char*)workspace + lt_softargmax3d_workspace(B, J, nvox));   // behind the plain call's workspace, sized for SA_CHUNK chunks as well
+        const dim3 grid(sa.snchunks, B);
+        if (channels_last) hipLaunchKernelGGL(sa3_probs_stats_kernel<true>, grid, dim3(256), 256 * (J | 1) * sizeof(float), st, sa);
+        else if (vec) hipLaunchKernelGGL(sa3_probs_stats_planar_kernel, grid, dim3(256), 0, st, sa);
+        else hipLaunchKernelGGL(sa3_probs_stats_kernel<false>, grid, dim3(256), 0, st, sa);
+        LT_CHECK_LAUNCH("lt_softargmax3d_stats_fwd(probs + statistics)");
+        hipLaunchKernelGGL(sa3_stats_finalize_kernel, dim3(B * J), dim3(64), 0, st, sa);
+        LT_CHECK_LAUNCH("lt_softargmax3d_stats_fwd(finalize)");
+    } else if (probs) {
         const dim3 grid(a.nchunks, B);
         if (channels_last) hipLaunchKernelGGL(sa3_probs_kernel<true>, grid, dim3(256), 256 * (J | 1) * sizeof(float), st, a);
         else if (vec)
@@ -584,6 +829,23 @@ extern "C" int lt_softargmax3d_fwd(const float* logits, const float* coords, flo
         LT_CHECK_LAUNCH("lt_softargmax3d_fwd(probs)");
     }
     return LT_OK;
+}
+
+extern "C" int lt_softargmax3d_fwd(const float* logits, const float* coords, float mult, int32_t softmax, int32_t channels_last,
+                                   int32_t ld, float* kp, float* probs, int32_t B, int32_t J, int64_t nvox, void* workspace,
+                                   void* stream) {
+    return sa3_forward("lt_softargmax3d_fwd", logits, coords, mult, softmax, channels_last, ld, kp, probs, nullptr, nullptr, false, B, J, nvox, workspace, stream);
+}
+
+extern "C" size_t lt_softargmax3d_stats_workspace(int32_t B, int32_t J, int64_t nvox) {
+    const int64_t nchunks = (nvox + SA_CHUNK - 1) / SA_CHUNK;
+    return lt_softargmax3d_workspace(B, J, nvox) + (size_t)((int64_t)B * J * nchunks * SS_REC) * sizeof(float);
+}
+
+extern "C" int lt_softargmax3d_stats_fwd(const float* logits, const float* coords, float mult, int32_t softmax, int32_t channels_last, int32_t ld, float* kp,
+                                         float* probs, float* stats, int32_t* peak_index, int32_t B, int32_t J, int64_t nvox, void* workspace, void* stream) {
+    return sa3_forward("lt_softargmax3d_stats_fwd", logits, coords, mult, softmax, channels_last, ld, kp, probs, stats, peak_index, true, B, J, nvox, workspace,
+                       stream);
 }
 
 extern "C" int lt_softargmax2d_fwd(const float* heatmaps, float mult, int32_t softmax, float* coords, float* probs, int32_t NJ,

@@ -130,6 +130,7 @@ SIGNATURES = {
     "lt_plan_create_cascade": (C.c_int, [C.POINTER(CascadePlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
     "lt_plan_forward_cascade": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_set_view_mask": (C.c_int, [vp, vp]),
+    "lt_plan_set_keypoint_stats": (C.c_int, [vp, vp, vp]),
     "lt_plan_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),
     "lt_plan_destroy": (None, [vp]),
     "lt_last_error": (C.c_char_p, []),
@@ -172,6 +173,8 @@ SIGNATURES = {
     "lt_cuboid_from_keypoints": (C.c_int, [vp, i32, i32, i32, C.c_double, vp, vp, vp]),
     "lt_softargmax3d_workspace": (C.c_size_t, [i32, i32, i64]),
     "lt_softargmax3d_fwd": (C.c_int, [vp, vp, f32, i32, i32, i32, vp, vp, i32, i32, i64, vp, vp]),
+    "lt_softargmax3d_stats_workspace": (C.c_size_t, [i32, i32, i64]),
+    "lt_softargmax3d_stats_fwd": (C.c_int, [vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp]),
     "lt_softargmax2d_fwd": (C.c_int, [vp, f32, i32, vp, vp, i32, i32, i32, vp]),
     "lt_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_alg_tail_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, vp]),

@@ -432,6 +432,10 @@ class VolumetricTriangulationNet(_PlannedNet):
         self.heatmap_softmax = m.heatmap_softmax
         self.heatmap_multiplier = m.heatmap_multiplier
         self.transfer_cmu_to_human36m = m.transfer_cmu_to_human36m if hasattr(m, "transfer_cmu_to_human36m") else False
+        # True: an eval forward also leaves the per-joint statistics of its 3D heatmaps (op.KeypointStats: peak, peak voxel, mass, covariance about the
+        # returned joint) in last_keypoint_stats; the 7-tuple keeps its bits.  Ignored in train(), where last_keypoint_stats is None.
+        self.keypoint_stats = False
+        self.last_keypoint_stats = None
         if self.volume_aggregation_method not in H.AGG:
             raise ValueError("Unknown volume_aggregation_method: {}".format(self.volume_aggregation_method))
         # same config mutation as the reference (:228-231)
@@ -447,10 +451,11 @@ class VolumetricTriangulationNet(_PlannedNet):
                                   "bfloat16": torch.bfloat16}[str(m.compute_dtype)]
 
     # ---------------------------------------------------------------------------------------
-    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False):
+    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False):
         """masked: the plan of forwards with ``batch["view_mask"]`` -- the same launch list with lt_unproject_grid_masked_fwd in the gather's place; the
         (B, NV) uint8 mask rides at the end of the geometry block (same pinned ring, same copy), outside the captured graph's baked pointers like the
-        rest of the block, so a new mask on a captured plan is just another forward."""
+        rest of the block, so a new mask on a captured plan is just another forward.
+        stats: the plan of forwards with ``keypoint_stats`` -- the same launch list with lt_softargmax3d_stats_fwd in the tail op's place (same op kind)."""
         V, J = self.volume_size, self.num_joints
         b, x_in = self._open_plan(B * NV, Hh, W, device, dry_run)
         lib = b.lib
@@ -512,18 +517,31 @@ class VolumetricTriangulationNet(_PlannedNet):
                  "features_out", nbytes=B * NV * h * w * 32 * (esz + 4), info={"feats": feats}, tail=True)
         # tail op (outside the captured graph): forward() points it at the tensors it returns, so the 17 x 64^3 probabilities
         # are written once, where the caller gets them, instead of being cloned out of a plan buffer (0.45 ms of copies per step)
-        b.custom(lambda st, outs=None: H.check(lib.lt_softargmax3d_fwd(
-                     logits.t.data_ptr(), coords.data_ptr(), mult, sm, cl, J, (outs[0] if outs else kp).data_ptr(),
-                     (outs[1] if outs else probs).data_ptr(), B, J, V ** 3, ws.data_ptr(), st), "lt_softargmax3d_fwd"),
-                 "softargmax3d", nbytes=2 * B * J * V ** 3 * 4,  # read logits + write probabilities
-                 info={"logits": logits, "coords": coords, "mult": mult, "softmax": sm, "kp": kp, "probs": probs}, tail=True)
+        kstats = kindex = None
+        if stats:          # the same tail with the per-joint statistics out of its probabilities pass: records (B, J, 8) and peak voxels (B, J)
+            kstats = torch.empty(B, J, 8, dtype=torch.float32, device=device)
+            kindex = torch.empty(B, J, dtype=torch.int32, device=device)
+            ws = torch.empty(1 if dry_run else max(1, lib.lt_softargmax3d_stats_workspace(B, J, V ** 3)), dtype=torch.uint8, device=device)
+            b.custom(lambda st, outs=None: H.check(lib.lt_softargmax3d_stats_fwd(
+                         logits.t.data_ptr(), coords.data_ptr(), mult, sm, cl, J, (outs[0] if outs else kp).data_ptr(),
+                         (outs[1] if outs else probs).data_ptr(), (outs[3] if outs else kstats).data_ptr(), (outs[4] if outs else kindex).data_ptr(),
+                         B, J, V ** 3, ws.data_ptr(), st), "lt_softargmax3d_stats_fwd"),
+                     "softargmax3d", nbytes=2 * B * J * V ** 3 * 4 + B * V ** 3 * 12,  # ... + the coordinates once more
+                     info={"logits": logits, "coords": coords, "mult": mult, "softmax": sm, "kp": kp, "probs": probs, "entry": "lt_softargmax3d_stats_fwd",
+                           "stats": kstats, "peak_index": kindex}, tail=True)
+        else:
+            b.custom(lambda st, outs=None: H.check(lib.lt_softargmax3d_fwd(
+                         logits.t.data_ptr(), coords.data_ptr(), mult, sm, cl, J, (outs[0] if outs else kp).data_ptr(),
+                         (outs[1] if outs else probs).data_ptr(), B, J, V ** 3, ws.data_ptr(), st), "lt_softargmax3d_fwd"),
+                     "softargmax3d", nbytes=2 * B * J * V ** 3 * 4,  # read logits + write probabilities
+                     info={"logits": logits, "coords": coords, "mult": mult, "softmax": sm, "kp": kp, "probs": probs}, tail=True)
         plan = b.finish()
-        plan.keep += [geo, geo_ring, coords, kp, probs, ws]
+        plan.keep += [geo, geo_ring, coords, kp, probs, ws] + ([kstats, kindex] if stats else [])
         if image_cell is not None and not dry_run:
             x_in.t.untyped_storage().resize_(0)   # the fused stem reads the caller's images: x_in is only a shape (150 MB at B = 32)
         return {"plan": plan, "x_in": x_in, "image_cell": image_cell, "feats": feats, "geo": geo, "geo_host": geo_ring.blocks[0], "geo_ring": geo_ring,
                 "coords": coords, "kp": kp, "probs": probs, "conf": conf, "logits": logits, "vol": vol, "hw": (h, w), "offs": (o_pos, o_cen, o_rot),
-                "captured": False, "masked": masked, "o_mask": o_mask}
+                "captured": False, "masked": masked, "o_mask": o_mask, "kstats": kstats, "kindex": kindex}
 
     def _host_cameras(self, batch, B, image_shape, P):
         """The camera half of the host geometry (reference :272-279, :318-328): fills the projections and rotations of the next slot of the plan's
@@ -586,13 +604,17 @@ class VolumetricTriangulationNet(_PlannedNet):
                 raise NotImplementedError("VolumetricTriangulationNet: batch['view_mask'] is inference only (there is no masked backward); call eval() first")
             batch = dict(batch, view_mask=vm)
         H.require_gpu(images, "images")
+        self.last_keypoint_stats = None
+        self.__dict__.pop("_chunk_stats", None)
         if _bn_in_train_mode(self):          # any BatchNorm module in train(): the training step (modules left in eval() keep frozen statistics)
-            return self._forward_train(images, batch)
+            return self._forward_train(images, batch)          # keypoint_stats is ignored there: the training tape is not touched
         _sync_buffers_before_eval(self)
         cap = self.max_samples_per_launch(NV, images.shape[3], images.shape[4])
         if B <= cap:
             with torch.cuda.device(images.device):
-                return self._forward_chunk(images, batch, 0, B)
+                out = self._forward_chunk(images, batch, 0, B)
+            self.last_keypoint_stats = self._take_keypoint_stats()
+            return out
         n = -(-B // cap)
         size = -(-B // n)            # equal-sized chunks (one plan), a shorter last one only if B does not divide
         if not self.__dict__.get("_warned_sub_batches"):
@@ -606,8 +628,18 @@ class VolumetricTriangulationNet(_PlannedNet):
             for lo in range(0, B, size):
                 parts.append(self._forward_chunk(images, batch, lo, min(B, lo + size)))
         cat = lambda i: torch.cat([p[i] for p in parts], dim=0)
+        self.last_keypoint_stats = self._take_keypoint_stats()
         conf = None if parts[0][3] is None else cat(3)
         return cat(0), cat(1), cat(2), conf, [c for p in parts for c in p[4]], cat(5), cat(6)
+
+    def _take_keypoint_stats(self):
+        """The op.KeypointStats of the forward whose chunks just ran (``_replay`` left each chunk's records behind), chunks concatenated; None for a
+        forward without ``keypoint_stats``."""
+        recs = self.__dict__.pop("_chunk_stats", None)
+        if not recs:
+            return None
+        one = len(recs) == 2
+        return op.keypoint_stats_from_records(recs[0] if one else torch.cat(recs[0::2], dim=0), recs[1] if one else torch.cat(recs[1::2], dim=0))
 
     def _forward_train(self, images, batch):
         """Training mode (any BatchNorm in train()): fp32, batch statistics, running statistics updated, random cuboid rotation; the
@@ -677,15 +709,17 @@ class VolumetricTriangulationNet(_PlannedNet):
                 batch["view_mask"] = np.ascontiguousarray(batch["view_mask"][lo:hi])
         B = hi - lo
         masked = batch.get("view_mask") is not None
+        stats = bool(self.keypoint_stats)
         # the key: everything a plan bakes in besides the weights (those: the fingerprint inside _plan_for)
-        P = self._plan_for(self._plan_key(B, NV, Hh, W, device, masked), lambda: self._build_plan(B, NV, Hh, W, device, masked=masked))
+        P = self._plan_for(self._plan_key(B, NV, Hh, W, device, masked, stats), lambda: self._build_plan(B, NV, Hh, W, device, masked=masked, stats=stats))
         return images, batch, B, P
 
-    def _plan_key(self, B, NV, Hh, W, device, masked=False):
-        """Everything a plan bakes in besides the weights; ``masked``: the plan records the masked gather (forwards without a mask keep their plan)."""
+    def _plan_key(self, B, NV, Hh, W, device, masked=False, stats=False):
+        """Everything a plan bakes in besides the weights; ``masked``: the plan records the masked gather (forwards without a mask keep their plan);
+        ``stats``: its tail is lt_softargmax3d_stats_fwd (``keypoint_stats``; forwards without the flag keep their plan)."""
         return (B, NV, Hh, W, self.compute_dtype, device, self.use_graph, self.volume_size, float(self.cuboid_side),
                 float(self.volume_multiplier), bool(self.volume_softmax), self.volume_aggregation_method,
-                bool(self.transfer_cmu_to_human36m), self.tile_override, self.num_joints, masked)
+                bool(self.transfer_cmu_to_human36m), self.tile_override, self.num_joints, masked, stats)
 
     @staticmethod
     def _plan_images(images, B, NV):
@@ -717,13 +751,19 @@ class VolumetricTriangulationNet(_PlannedNet):
             plan.capture(st)
             P["captured"] = True
         kp, probs, coords = P["kp"], P["probs"], P["coords"]
+        kstats, kindex = P.get("kstats"), P.get("kindex")          # plans with keypoint_stats: the records of lt_softargmax3d_stats_fwd
         if self.copy_outputs:       # fresh result tensors like the reference's: the tail ops write them directly
             kp, probs = torch.empty_like(kp), torch.empty_like(probs)
             feats = torch.empty(B, NV, 32, h, w, dtype=torch.float32, device=device)
-            plan.run(st, (kp, probs, feats))
+            if kstats is not None:
+                kstats, kindex = torch.empty_like(kstats), torch.empty_like(kindex)
+            plan.run(st, (kp, probs, feats, kstats, kindex))
         else:
             plan.run(st)
             feats = P["feats"].t.reshape(B, NV, h, w, 32).permute(0, 1, 4, 2, 3)
+        if kstats is not None:          # left for forward(), which hands them out as last_keypoint_stats (one pair per chunk of the call)
+            kstats.record_stream(cur); kindex.record_stream(cur)
+            self.__dict__.setdefault("_chunk_stats", []).extend([kstats, kindex])
         conf = P["conf"]
         o_pos, o_cen, o_rot = P["offs"]
         base_points = P["geo"][o_cen:o_rot].reshape(B, 3).clone()    # fp32(base), from the block that was just copied in
@@ -1022,6 +1062,7 @@ class CascadeTriangulationNet(nn.Module):
         if J < need:
             raise ValueError("CascadeTriangulationNet: the algebraic model has %d joints, kind '%s' reads joint %d" % (J, vol_net.kind, need - 1))
         self.alg, self.vol = alg_net, vol_net
+        self.last_keypoint_stats = None          # with vol.keypoint_stats: the op.KeypointStats of the last forward's volumetric stage
 
     def forward(self, images, proj_matricies, batch):
         """images (B,NV,3,H,W) fp32 on the GPU; ``proj_matricies`` (B,NV,3,4) at image resolution for the algebraic stage; ``batch`` needs only
@@ -1039,6 +1080,8 @@ class CascadeTriangulationNet(nn.Module):
             raise NotImplementedError("CascadeTriangulationNet runs in eval() only: train the two stages on their own (the reference trains the "
                                       "volumetric model on pelvises read from a results file)")
         vol = self.vol
+        self.last_keypoint_stats = vol.last_keypoint_stats = None
+        vol.__dict__.pop("_chunk_stats", None)
         alg_out = self.alg(images, proj_matricies, batch)
         kp_alg = alg_out[0]
         _sync_buffers_before_eval(vol)
@@ -1049,6 +1092,7 @@ class CascadeTriangulationNet(nn.Module):
         with torch.cuda.device(images.device):
             for lo in range(0, B, size):
                 parts.append(self._vol_chunk(images, batch, kp_alg, lo, min(B, lo + size)))
+        self.last_keypoint_stats = vol.last_keypoint_stats = vol._take_keypoint_stats()
         if len(parts) == 1:
             kp, feats, probs, conf, coords, base_points = parts[0]
         else:

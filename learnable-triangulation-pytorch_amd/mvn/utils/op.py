@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 import lt_hip as H
+from mvn.utils.volumetric import KeypointStats
 
 # workspace of lt_unproject_bwd's deterministic gather: at most this much (or one sample's share, if that is more); with less than the whole
 # batch's worth the entry point walks the batch in chunks.  One constant for the autograd path here and the recorded training step.
@@ -149,7 +150,13 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
     return _unproject_launch(_as_channels_last(heatmaps, 2), P, cv, conf, volume_aggregation_method).permute(0, 4, 1, 2, 3)
 
 
-def _softargmax3d_launch(volumes, cv, softmax):
+def keypoint_stats_from_records(records, peak_index):
+    """The (B,J,8) records {peak, mass, cxx, cxy, cxz, cyy, cyz, czz} and (B,J) peak voxels of lt_softargmax3d_stats_fwd as a KeypointStats."""
+    cov = records[..., [2, 3, 4, 3, 5, 6, 4, 6, 7]].reshape(records.shape[:-1] + (3, 3))
+    return KeypointStats(records[..., 0], peak_index, records[..., 1], cov)
+
+
+def _softargmax3d_launch(volumes, cv, softmax, with_stats=False):
     B, J = volumes.shape[:2]
     nvox = int(np.prod(volumes.shape[2:]))
     cl = volumes.permute(0, 2, 3, 4, 1).is_contiguous() and not volumes.is_contiguous()
@@ -157,6 +164,13 @@ def _softargmax3d_launch(volumes, cv, softmax):
     kp = torch.empty(B, J, 3, dtype=torch.float32, device=volumes.device)
     probs = torch.empty((B, J) + tuple(volumes.shape[2:]), dtype=torch.float32, device=volumes.device)
     lib = H.lib()
+    if with_stats:          # the same launches with the statistics out of the probabilities pass: kp and probs keep their bits
+        rec = torch.empty(B, J, 8, dtype=torch.float32, device=volumes.device)
+        idx = torch.empty(B, J, dtype=torch.int32, device=volumes.device)
+        ws = torch.empty(max(1, lib.lt_softargmax3d_stats_workspace(B, J, nvox)), dtype=torch.uint8, device=volumes.device)
+        H.check(lib.lt_softargmax3d_stats_fwd(lg.data_ptr(), cv.data_ptr(), 1.0, int(bool(softmax)), int(cl), J, kp.data_ptr(), probs.data_ptr(), rec.data_ptr(),
+                                              idx.data_ptr(), B, J, nvox, ws.data_ptr(), H.cur_stream()), "lt_softargmax3d_stats_fwd")
+        return kp, probs, keypoint_stats_from_records(rec, idx)
     ws = torch.empty(max(1, lib.lt_softargmax3d_workspace(B, J, nvox)), dtype=torch.uint8, device=volumes.device)
     H.check(lib.lt_softargmax3d_fwd(lg.data_ptr(), cv.data_ptr(), 1.0, int(bool(softmax)), int(cl), J, kp.data_ptr(), probs.data_ptr(),
                                     B, J, nvox, ws.data_ptr(), H.cur_stream()), "lt_softargmax3d_fwd")
@@ -169,8 +183,13 @@ class _SoftArgmax3dFn(torch.autograd.Function):
     one-voxel-per-joint gradient in sparse form (``sparse_prob_grad``), so no (B,J,V^3) gradient tensor is ever materialised."""
 
     @staticmethod
-    def forward(ctx, volumes, cv, softmax):
-        kp, probs = _softargmax3d_launch(volumes, cv, softmax)
+    def forward(ctx, volumes, cv, softmax, stats_out=None):
+        # stats_out (integrate_tensor_3d_with_stats): a list that receives the KeypointStats of this forward; they are no outputs of the node (no gradient)
+        if stats_out is None:
+            kp, probs = _softargmax3d_launch(volumes, cv, softmax)
+        else:
+            kp, probs, st = _softargmax3d_launch(volumes, cv, softmax, with_stats=True)
+            stats_out.append(st)
         ctx.save_for_backward(probs, cv, kp)
         ctx.softmax, ctx.in_dtype = bool(softmax), volumes.dtype
         return kp, probs
@@ -201,7 +220,7 @@ class _SoftArgmax3dFn(torch.autograd.Function):
         gl = torch.empty_like(probs)
         H.check(H.lib().lt_softargmax3d_bwd_dense(probs.data_ptr(), cv.data_ptr(), kp.data_ptr(), g_kp.data_ptr(), H.ptr(idx), H.ptr(val), H.ptr(dense), H.ptr(ws), 1.0,
                                                   int(ctx.softmax), 0, gl.data_ptr(), B, J, nvox, H.cur_stream()), "lt_softargmax3d_bwd")
-        return gl.to(ctx.in_dtype), None, None
+        return gl.to(ctx.in_dtype), None, None, None
 
 
 def is_sparse_placeholder(node, g):
@@ -242,6 +261,20 @@ def integrate_tensor_3d_with_coordinates(volumes, coord_volumes, softmax=True):
     if torch.is_grad_enabled() and volumes.requires_grad:
         return _SoftArgmax3dFn.apply(volumes, cv, softmax)
     return _softargmax3d_launch(volumes, cv, softmax)
+
+
+def integrate_tensor_3d_with_stats(volumes, coord_volumes, softmax=True):
+    """integrate_tensor_3d_with_coordinates plus the per-joint statistics of the 3D heatmaps, out of the same pass that writes the probabilities
+    (lt_softargmax3d_stats_fwd).  Returns (coordinates, volumes, stats): the first two are bit for bit what integrate_tensor_3d_with_coordinates returns
+    and differentiable in the same way; ``stats`` is a KeypointStats (peak, peak_index, mass, covariance about the returned joint) without a gradient.
+    The definitions in numpy fp64: mvn.utils.volumetric.keypoint_stats."""
+    H.require_gpu(volumes, "volumes")
+    cv = coord_volumes.to(volumes.device, torch.float32).contiguous()
+    if torch.is_grad_enabled() and volumes.requires_grad:
+        out = []
+        kp, probs = _SoftArgmax3dFn.apply(volumes, cv, softmax, out)
+        return kp, probs, out[0]
+    return _softargmax3d_launch(volumes, cv, softmax, with_stats=True)
 
 
 def batchnorm_batch_stats(x, running_mean=None, running_var=None, momentum=0.1):
