@@ -355,6 +355,28 @@ int lt_softargmax3d_stats_fwd(const float* logits, const float* coords, float mu
  * soft-argmax; writes coords N,J,2 (x,y) and the normalised heatmaps (or NULL). */
 int lt_softargmax2d_fwd(const float* heatmaps, float mult, int32_t softmax, float* coords, float* probs, int32_t NJ,
                         int32_t h, int32_t w, void* stream);
+/* lt_softargmax2d_fwd plus per-heatmap statistics out of its third pass, the one that writes the probabilities (mvn.utils.multiview.heatmap_stats_2d
+ * states them in numpy fp64).  Arguments and layout are lt_softargmax2d_fwd's; coords and probs are bit for bit what it writes; probs may be NULL (the
+ * same pass without its store).  stats: NJ,5 fp32 records {peak, mass, cxx, cxy, cyy}; peak_index: NJ int32.
+ * Per heatmap, with x_i = fp32(mult * hm_i) (the one rounding the kernel makes) and the flat index i = y * w + x, pixel centres c_i = (x, y):
+ *   softmax != 0, p = softmax(x):
+ *     peak_index  the smallest i at which x_i is maximal
+ *     peak        p at peak_index; equal to probs[peak_index] bit for bit
+ *     mass        1.0f
+ *     centre      the returned fp32 (coords_x, coords_y)
+ *     cov         sum_i p_i (c_i - centre)(c_i - centre)^T, heatmap pixels^2
+ *   softmax == 0, w = relu(x) (the returned heatmaps stay unnormalised):
+ *     mass        sum_i w_i
+ *     peak_index  as above, on x (not on w)
+ *     peak        relu(x_peak) / mass, one fp32 division
+ *     centre      the returned coordinates
+ *     cov         sum_i (w_i / mass)(c_i - centre)(c_i - centre)^T
+ *     mass == 0 gives peak = 0 and cov = 0 (the coordinates are NaN, as lt_softargmax2d_fwd's)
+ * The moments are taken about the centre, never as a difference of raw second moments.  Lanes accumulate in fp32, the waves' partials are combined in
+ * fp64 in a fixed order, the (largest x, smallest index) pair by compare-and-select; there are no atomics: two calls give equal bits.
+ * LT_ERR_INVALID: stats, peak_index, heatmaps or coords NULL, a size < 1.  LT_ERR_UNSUPPORTED: h * w does not fit an int32. */
+int lt_softargmax2d_stats_fwd(const float* heatmaps, float mult, int32_t softmax, float* coords, float* probs, float* stats, int32_t* peak_index,
+                              int32_t NJ, int32_t h, int32_t w, void* stream);
 /* Backward of the two ops above and of lt_triangulate_dlt (training of AlgebraicTriangulationNet, train.py:189-236): what autograd derives in the
  * reference through softmax / sums (op.py:23-45) and through torch.svd (multiview.py:163).  lt_softargmax2d_bwd: probs / coords are the forward's
  * outputs, grad_coords N*J,2 -> grad_heatmaps (both modes; a gradient on the returned heatmaps is not supported).  lt_triangulate_dlt_bwd:
@@ -563,6 +585,29 @@ int lt_alg_tail_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld
 int lt_alg_tail_masked_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
                            const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV,
                            int32_t J, void* stream);
+/* The algebraic tail with the statistics of its joints (mvn.utils.multiview.triangulation_stats states them in numpy fp64).  view_mask NULL:
+ * keypoints_2d, confidences and keypoints_3d are bit for bit lt_alg_tail_fwd's; view_mask DEVICE (B, NV): lt_alg_tail_masked_fwd's (same loops, same
+ * dlt_add_view / SVD sequence).  stats2d: the B*NV*J,5 records of lt_softargmax2d_stats_fwd for keypoints_hm.  Additional outputs:
+ *   cov2d_img  B,NV,J,3 {xx, xy, yy}, image px^2: S Sigma_hm S, S = diag(scale_x, scale_y), Sigma_hm the record's {cxx, cxy, cyy}; formed in fp64,
+ *              rounded once.  It is the spread of the network's heatmap, not a calibrated error bar.
+ *   reproj_err B,NV,J, image px: || pi(P_v, X) - keypoints_2d[b, v, j] ||_2, pi the perspective division of P_v [X; 1], X the RETURNED fp32 joint read
+ *              back as fp64; fp64, rounded once.
+ *   cov3d      B,J,6 {xx, xy, xz, yy, yz, zz}, squared world units of proj (mm^2 for Human3.6M): sum over the valid views of J_v Sigma_v J_v^T, the
+ *              first-order propagation with the confidences held fixed; Sigma_v = the RETURNED cov2d_img[b, v, j] read back as fp64 (so a caller can
+ *              reproduce cov3d from the outputs alone), J_v = dX / d keypoints_2d[b, v, j] (3 x 2) at the solution, by the formulas of
+ *              lt_triangulate_dlt_bwd: w = (lambda I - A^T A)^+ g_v, dL/dA = A (w v^T + v w^T), for g_X = e_0, e_1, e_2 off the forward's one SVD.
+ * A masked view adds nothing to cov3d, its reproj_err is a quiet NaN, its cov2d_img is unspecified, and its keypoint, matrix and record never enter
+ * the system.  Fewer than two valid views: NaN joints, NaN cov3d.  LT_ERR_INVALID: stats2d, cov2d_img, reproj_err or cov3d NULL; otherwise the
+ * refusals of lt_alg_tail_fwd (NV >= 2). */
+int lt_alg_tail_stats_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                          const uint8_t* view_mask, const float* stats2d, float* keypoints_2d, float* confidences, float* keypoints_3d,
+                          float* cov2d_img, float* reproj_err, float* cov3d, int32_t B, int32_t NV, int32_t J, void* stream);
+/* lt_triangulate_dlt over the valid views (view_mask DEVICE (B, NV) or NULL = all valid) with the two statistics of lt_alg_tail_stats_fwd, for
+ * callers that hold the 2D points, the confidences (as they enter the system; NULL = 1) and the 2D covariances cov2d (B,NV,J,3 {xx, xy, yy}) already:
+ * out B,J,3; reproj_err B,NV,J; cov3d B,J,6.  Given lt_alg_tail_stats_fwd's keypoints_2d, confidences and cov2d_img it returns that call's joints,
+ * reproj_err and cov3d bit for bit.  LT_ERR_INVALID: a NULL pointer other than conf and view_mask, NV < 2. */
+int lt_triangulate_dlt_stats(const float* proj, const float* points, const float* conf, const float* cov2d, const uint8_t* view_mask, float* out,
+                             float* reproj_err, float* cov3d, int32_t B, int32_t NV, int32_t J, void* stream);
 
 /* RANSACTriangulationNet (reference mvn/models/triangulation.py:17-128), 2D part: the backbone's N,h,w,(ld) fp32 heatmaps ->
  * heatmaps_nchw N,J,h,w (the raw heatmaps the model returns, bit-identical to lt_nhwc_to_nchw_f32) and, in the same pass, the argmax
@@ -893,6 +938,15 @@ int lt_plan_set_view_mask(lt_plan* plan, const uint8_t* mask_host);
  * plain tail.  One NULL: LT_ERR_INVALID.  LT_MODEL_ALG / LT_MODEL_RANSAC plans: LT_ERR_UNSUPPORTED.  The tail op is eager and reads these fields when it
  * runs, so the call may come before or after the plan's first forward and nothing is captured again. */
 int lt_plan_set_keypoint_stats(lt_plan* plan, float* stats_dev, int32_t* peak_index_dev);
+/* Per-joint statistics of the algebraic joints (the definitions of lt_softargmax2d_stats_fwd and lt_alg_tail_stats_fwd, with the plan's
+ * heatmap_multiplier and heatmap_softmax): with all five pointers non-NULL every later lt_plan_forward_alg of an LT_MODEL_ALG plan -- and the algebraic
+ * stage of every later lt_plan_forward_cascade -- also writes, on the forward's stream, stats2d_dev (DEVICE, B*NV*J,5 fp32 {peak, mass, cxx, cxy, cyy},
+ * heatmap px^2), peak_index_dev (B*NV*J int32), cov2d_img_dev (B,NV,J,3, image px^2), reproj_err_dev (B,NV,J, px) and cov3d_dev (B,J,6); every other
+ * output keeps its bits, with lt_plan_set_view_mask too.  All five NULL: back to the plain tail.  A mixture: LT_ERR_INVALID.  LT_MODEL_RANSAC and
+ * volumetric plans: LT_ERR_UNSUPPORTED.  The algebraic tail is eager and reads these fields when it runs, so the call may come before or after the plan's
+ * first forward and nothing is captured again.  Results are bit-identical to the Python host's (AlgebraicTriangulationNet.keypoint_stats). */
+int lt_plan_set_alg_keypoint_stats(lt_plan* plan, float* stats2d_dev, int32_t* peak_index_dev, float* cov2d_img_dev, float* reproj_err_dev,
+                                   float* cov3d_dev);
 int lt_plan_info(const lt_plan* plan, lt_plan_info_t* info);
 void lt_plan_destroy(lt_plan* plan);
 

@@ -296,6 +296,9 @@ struct lt_plan {
     // per-joint statistics (lt_plan_set_keypoint_stats): the caller's device buffers, read by the eager tail op when it runs, and the larger workspace of
     // lt_softargmax3d_stats_fwd, allocated by the first call that asks for them
     float* ks_stats = nullptr; int32_t* ks_index = nullptr; void* ks_ws = nullptr;
+    // per-joint statistics of the algebraic joints (lt_plan_set_alg_keypoint_stats): the caller's five device buffers, all set or all NULL, read by the
+    // two eager tail ops when they run
+    float* aks_stats2d = nullptr; int32_t* aks_index = nullptr; float* aks_cov2d = nullptr; float* aks_reproj = nullptr; float* aks_cov3d = nullptr;
     Act algc;                                   // alg_confidences head output [1,1,1,N,J] fp32 (algebraic plans with use_confidences)
     float* hm_nchw = nullptr; float* kp_hm = nullptr; int64_t* kp_i64 = nullptr;          // heatmaps N,J,h,w; soft-argmax N,J,2 (heatmap px); argmax N,J,2
     int hm_h = 0, hm_w = 0;
@@ -1046,12 +1049,19 @@ struct lt_plan {
         PL_TRY(dev_alloc((size_t)N * J * h * w * 4, &q)); probs = (float*)q;
         {   // tail op 1: integrate_tensor_2d, the normalised heatmaps straight into the caller's tensor
             const float mult = (float)c.heatmap_multiplier; const int sm = c.heatmap_softmax ? 1 : 0; float* kh = kp_hm; float* pr = probs;
-            ops.push_back([=](hipStream_t s) { return lt_softargmax2d_fwd(hn, mult, sm, kh, self->out_hm ? self->out_hm : pr, N * J, h, w, s); });
+            ops.push_back([=](hipStream_t s) {
+                if (self->aks_stats2d)
+                    return lt_softargmax2d_stats_fwd(hn, mult, sm, kh, self->out_hm ? self->out_hm : pr, self->aks_stats2d, self->aks_index, N * J, h, w, s);
+                return lt_softargmax2d_fwd(hn, mult, sm, kh, self->out_hm ? self->out_hm : pr, N * J, h, w, s);
+            });
         }
         {   // tail op 2: confidences normalised over the views, keypoints to image pixels, the DLT (triangulation.py:166-193)
             const float sx = (float)((double)W / (double)w), sy = (float)((double)Hh / (double)h);          // torch.tensor([W / w, H / h], float32)
             const float* kh = kp_hm; const float* cp = algc.null() ? nullptr : (const float*)algc.p; const int ldc = algc.null() ? J : algc.c;
             ops.push_back([=](hipStream_t s) {
+                if (self->aks_stats2d)
+                    return lt_alg_tail_stats_fwd(kh, cp, ldc, self->cur_proj, sx, sy, self->masked ? self->mask_dev : nullptr, self->aks_stats2d, (float*)self->out_kp2d,
+                                                 self->out_conf, self->out_kp, self->aks_cov2d, self->aks_reproj, self->aks_cov3d, B, NV, J, s);
                 if (self->masked)
                     return lt_alg_tail_masked_fwd(kh, cp, ldc, self->cur_proj, sx, sy, self->mask_dev, (float*)self->out_kp2d, self->out_conf, self->out_kp, B, NV, J, s);
                 return lt_alg_tail_fwd(kh, cp, ldc, self->cur_proj, sx, sy, (float*)self->out_kp2d, self->out_conf, self->out_kp, B, NV, J, s);
@@ -1455,6 +1465,20 @@ extern "C" int lt_plan_set_keypoint_stats(lt_plan* p, float* stats_dev, int32_t*
         PL_TRY(v->dev_alloc(lt_softargmax3d_stats_workspace(v->cfg.B, v->cfg.num_joints, (int64_t)V * V * V), &v->ks_ws));
     }
     v->ks_stats = stats_dev; v->ks_index = peak_index_dev;
+    return LT_OK;
+}
+
+extern "C" int lt_plan_set_alg_keypoint_stats(lt_plan* p, float* stats2d_dev, int32_t* peak_index_dev, float* cov2d_img_dev, float* reproj_err_dev,
+                                              float* cov3d_dev) {
+    const char* who = "lt_plan_set_alg_keypoint_stats";
+    LT_REQUIRE(p, LT_ERR_INVALID, "%s: null plan", who);
+    LT_REQUIRE(p->model == LT_MODEL_ALG || p->model == MODEL_CASCADE, LT_ERR_UNSUPPORTED, "%s: the plan is %s; the statistics are those of the algebraic joints", who,
+               plan_kind_name(p));
+    const int n = (stats2d_dev != nullptr) + (peak_index_dev != nullptr) + (cov2d_img_dev != nullptr) + (reproj_err_dev != nullptr) + (cov3d_dev != nullptr);
+    LT_REQUIRE(n == 0 || n == 5, LT_ERR_INVALID,
+               "%s: stats2d_dev, peak_index_dev, cov2d_img_dev, reproj_err_dev and cov3d_dev come together (all NULL: the plain tail); %d of 5 given", who, n);
+    lt_plan* a = p->model == MODEL_CASCADE ? p->sub_alg : p;
+    a->aks_stats2d = stats2d_dev; a->aks_index = peak_index_dev; a->aks_cov2d = cov2d_img_dev; a->aks_reproj = reproj_err_dev; a->aks_cov3d = cov3d_dev;
     return LT_OK;
 }
 

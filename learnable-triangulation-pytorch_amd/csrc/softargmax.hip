@@ -578,8 +578,13 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
     return r;
 }
 
-__global__ __launch_bounds__(256) void sa2_kernel(const float* __restrict__ hm, float mult, int softmax, float* __restrict__ coords,
-                                                   float* __restrict__ probs, int h, int w) {
+// STATS (sa2_stats_kernel, lt_softargmax2d_stats_fwd): the third pass, which holds M, S and the returned coordinates, also reduces the heatmap's second
+// moments ABOUT those coordinates and the (largest x, smallest index) pair together with the value it writes there, so that peak is probs[peak_index] by construction.  Lanes
+// add in fp32 in index order, the wave butterfly and the four waves are combined in a fixed order (the waves in fp64): no atomics, equal bits every call.
+// The first two passes and the plain third pass are the same text for both instantiations: coords and probs keep their bits.
+template <bool STATS>
+__device__ __forceinline__ void sa2_body(const float* __restrict__ hm, float mult, int softmax, float* __restrict__ coords, float* __restrict__ probs,
+                                         float* __restrict__ stats, int* __restrict__ peak_index, int h, int w) {
     __shared__ float red[4];
     const long long base = (long long)blockIdx.x * h * w;
     const int n = h * w;
@@ -604,11 +609,67 @@ __global__ __launch_bounds__(256) void sa2_kernel(const float* __restrict__ hm, 
         coords[blockIdx.x * 2] = X / S;
         coords[blockIdx.x * 2 + 1] = Y / S;
     }
-    if (probs)
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const float x = mult * hm[base + i];
-            probs[base + i] = softmax ? __fdiv_rn(expf(x - M), S) : fmaxf(x, 0.f);
+    if (!STATS) {
+        if (probs)
+            for (int i = threadIdx.x; i < n; i += 256) {
+                const float x = mult * hm[base + i];
+                probs[base + i] = softmax ? __fdiv_rn(expf(x - M), S) : fmaxf(x, 0.f);
+            }
+        return;
+    }
+    __shared__ float sred[4][5];     // per wave: cxx, cxy, cyy, x at the peak, the value written at the peak
+    __shared__ int sidx[4];
+    const bool some = softmax || S > 0.f;          // ReLU without mass: no weights, the centre is never used (the coordinates are NaN as in the plain kernel)
+    const float cx = some ? X / S : 0.f, cy = some ? Y / S : 0.f;
+    float cxx = 0.f, cxy = 0.f, cyy = 0.f, px = -INFINITY, pp = 0.f;
+    int pi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float x = mult * hm[base + i];
+        const float p = softmax ? __fdiv_rn(expf(x - M), S) : fmaxf(x, 0.f);
+        if (probs) probs[base + i] = p;
+        const float wgt = softmax ? p : (some ? __fdiv_rn(p, S) : 0.f);
+        const int yy = i / w, xx = i - yy * w;
+        const float dx = (float)xx - cx, dy = (float)yy - cy;
+        const float wx = wgt * dx, wy = wgt * dy;
+        cxx += wx * dx; cxy += wx * dy; cyy += wy * dy;
+        if (x > px) { px = x; pi = i; pp = p; }          // increasing i: the strict comparison keeps the first of equal maxima
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        cxx += __shfl_xor(cxx, off); cxy += __shfl_xor(cxy, off); cyy += __shfl_xor(cyy, off);
+        const float x2 = __shfl_xor(px, off), p2 = __shfl_xor(pp, off);
+        const int i2 = __shfl_xor(pi, off);
+        if (x2 > px || (x2 == px && i2 < pi)) { px = x2; pi = i2; pp = p2; }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        float* r = sred[threadIdx.x >> 6];
+        r[0] = cxx; r[1] = cxy; r[2] = cyy; r[3] = px; r[4] = pp;
+        sidx[threadIdx.x >> 6] = pi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m[3] = {0, 0, 0};
+        for (int wv = 0; wv < 4; ++wv) {
+            m[0] += (double)sred[wv][0]; m[1] += (double)sred[wv][1]; m[2] += (double)sred[wv][2];
+            if (wv && (sred[wv][3] > px || (sred[wv][3] == px && sidx[wv] < pi))) { px = sred[wv][3]; pi = sidx[wv]; pp = sred[wv][4]; }
         }
+        float* o = stats + (long long)blockIdx.x * 5;
+        o[0] = softmax ? pp : (some ? __fdiv_rn(pp, S) : 0.f);          // softmax: the value written at the peak; ReLU: relu(x_peak) / mass
+        o[1] = softmax ? 1.f : S;
+        o[2] = (float)m[0]; o[3] = (float)m[1]; o[4] = (float)m[2];
+        peak_index[blockIdx.x] = pi;
+    }
+}
+
+// the plain kernel keeps its arguments; the statistics are a kernel of their own over the same body
+__global__ __launch_bounds__(256) void sa2_kernel(const float* __restrict__ hm, float mult, int softmax, float* __restrict__ coords,
+                                                   float* __restrict__ probs, int h, int w) {
+    sa2_body<false>(hm, mult, softmax, coords, probs, nullptr, nullptr, h, w);
+}
+
+__global__ __launch_bounds__(256) void sa2_stats_kernel(const float* __restrict__ hm, float mult, int softmax, float* __restrict__ coords,
+                                                         float* __restrict__ probs, float* __restrict__ stats, int* __restrict__ peak_index, int h, int w) {
+    sa2_body<true>(hm, mult, softmax, coords, probs, stats, peak_index, h, w);
 }
 
 // ---- DLT: one lane per (sample, joint), the routine of dlt.h ------------------------------------------------------------------------------------
@@ -633,6 +694,103 @@ __global__ void dlt_kernel(const float* __restrict__ proj, const float* __restri
     dlt_solve(R, out + (long long)g * 3);
 }
 
+// ---- what the DLT's backward and the forward-mode statistics share --------------------------------------------------------------------------------
+// triangulate_point_from_multiple_views_linear_torch (multiview.py:141-168): X = v[:3] / v[3], v = right singular vector of A for its smallest
+// singular value = eigenvector of M = A^T A for its smallest eigenvalue lambda; rows of A: c_v (x_{v,r} P_v[2,:] - P_v[r,:]).  What autograd derives
+// through torch.svd there, written out:  g_v = (g_X / v3, -(g_X . v[:3]) / v3^2) (orthogonal to v: X does not depend on |v|),
+//   w = (lambda I - M)^+ g_v = sum_{i != min} e_i (e_i . g_v) / (lambda - lambda_i),   dL/dM = (w v^T + v w^T) / 2,   dL/dA = A (w v^T + v w^T),
+//   dL/dc_v = sum_r dL/dA[v,r,:] . (x P2 - Pr),   dL/dx_{v,r} = c_v dL/dA[v,r,:] . P_v[2,:].   fp64.
+// dlt_grad_w: v and w for one g_X off the forward's SVD (V: eigenvectors of A^T A in its columns, ev: the eigenvalues, best: the smallest one's column)
+__device__ __forceinline__ void dlt_grad_w(const double (&V)[4][4], const double (&ev)[4], const int best, const double (&gX)[3], double (&vv)[4],
+                                           double (&wv)[4]) {
+    const double lam = ev[best];
+    double gv[4];
+    for (int k = 0; k < 4; ++k) { vv[k] = V[k][best]; wv[k] = 0; }
+    gv[0] = gX[0] / vv[3]; gv[1] = gX[1] / vv[3]; gv[2] = gX[2] / vv[3];
+    gv[3] = -(gX[0] * vv[0] + gX[1] * vv[1] + gX[2] * vv[2]) / (vv[3] * vv[3]);
+    for (int i = 0; i < 4; ++i) {
+        if (i == best) continue;
+        double dot = 0;
+        for (int k = 0; k < 4; ++k) dot += V[k][i] * gv[k];
+        const double f = dot / (lam - ev[i]);
+        for (int k = 0; k < 4; ++k) wv[k] += V[k][i] * f;
+    }
+}
+
+// dlt_grad_row: row r of one view (point coordinate pr, confidence c, matrix P): returns dL/dA[v,r,:] . P[2,:] -- dL/dx_{v,r} is c times that -- and
+// adds the row's share of dL/dc_v to gc
+__device__ __forceinline__ double dlt_grad_row(const float* __restrict__ P, const double pr, const int r, const double c, const double (&vv)[4],
+                                               const double (&wv)[4], double& gc) {
+    double raw[4], arow[4], av = 0, aw = 0;
+    for (int k = 0; k < 4; ++k) { raw[k] = (double)P[8 + k] * pr - (double)P[4 * r + k]; arow[k] = raw[k] * c; av += arow[k] * vv[k]; aw += arow[k] * wv[k]; }
+    double gp = 0;
+    for (int k = 0; k < 4; ++k) {
+        const double ga = aw * vv[k] + av * wv[k];          // dL/dA[v,r,k] = (A (w v^T + v w^T))[row][k]
+        gc += ga * raw[k];
+        gp += ga * (double)P[8 + k];
+    }
+    return gp;
+}
+
+// ---- statistics of a triangulated joint (lt_alg_tail_stats_fwd, lt_triangulate_dlt_stats): after the forward's dlt_svd of R ------------------------
+// The joint as dlt_point gives it (same divisions, so the same bits), then per valid view the reprojection error of the RETURNED fp32 joint and the
+// first-order covariance sum_v J_v Sigma_v J_v^T, J_v = dX / d(2D point of view v) (3 x 2, confidences fixed): dlt_grad_w for g_X = e_0, e_1, e_2 off the
+// one SVD, dlt_grad_row per view and coordinate.  view(v, x, y, c, s) -> bool: is view v valid, and if so its fp32 2D point, its confidence and its 2D
+// covariance {xx, xy, yy} (image px^2), all as fp64.  Masked views get a quiet NaN as their reprojection error and are never read.
+// reproj: element v * J of it belongs to view v.  solvable == false (fewer than two valid views): NaN everywhere.
+template <class View>
+__device__ __forceinline__ void dlt_stats_finish(double (&R)[4][4], const bool solvable, const float* __restrict__ proj_b, const int NV, const int J, View view,
+                                                 float* __restrict__ o, float* __restrict__ reproj, float* __restrict__ cov3d) {
+    const float qnan = __int_as_float(0x7fc00000);
+    if (!solvable) {
+        o[0] = o[1] = o[2] = qnan;
+        for (int k = 0; k < 6; ++k) cov3d[k] = qnan;
+        for (int v = 0; v < NV; ++v) reproj[(long long)v * J] = qnan;
+        return;
+    }
+    double V[4][4], ev[4];
+    const int best = dlt_svd(R, V, ev);
+    const double wh = V[3][best];
+    double X[3];
+    X[0] = V[0][best] / wh; X[1] = V[1][best] / wh; X[2] = V[2][best] / wh;          // dlt_point
+    o[0] = (float)X[0]; o[1] = (float)X[1]; o[2] = (float)X[2];
+    const double X32[3] = {(double)o[0], (double)o[1], (double)o[2]};                  // the reprojection error is that of the joint the caller gets
+    double vv[4], wj[3][4];
+    for (int e = 0; e < 3; ++e) {
+        const double gX[3] = {e == 0 ? 1.0 : 0.0, e == 1 ? 1.0 : 0.0, e == 2 ? 1.0 : 0.0};
+        dlt_grad_w(V, ev, best, gX, vv, wj[e]);
+    }
+    double C[6] = {0, 0, 0, 0, 0, 0};          // xx, xy, xz, yy, yz, zz
+    for (int v = 0; v < NV; ++v) {
+        double x, y, c, s[3];
+        if (!view(v, x, y, c, s)) { reproj[(long long)v * J] = qnan; continue; }
+        const float* P = proj_b + (long long)v * 12;
+        double hh[3];
+        for (int r = 0; r < 3; ++r) hh[r] = (double)P[4 * r] * X32[0] + (double)P[4 * r + 1] * X32[1] + (double)P[4 * r + 2] * X32[2] + (double)P[4 * r + 3];
+        const double du = hh[0] / hh[2] - x, dv = hh[1] / hh[2] - y;
+        reproj[(long long)v * J] = (float)sqrt(du * du + dv * dv);
+        double Jm[3][2], unused = 0;
+        for (int e = 0; e < 3; ++e) {
+            Jm[e][0] = dlt_grad_row(P, x, 0, c, vv, wj[e], unused) * c;
+            Jm[e][1] = dlt_grad_row(P, y, 1, c, vv, wj[e], unused) * c;
+        }
+        int q = 0;
+        for (int e = 0; e < 3; ++e) {
+            const double t0 = Jm[e][0] * s[0] + Jm[e][1] * s[1], t1 = Jm[e][0] * s[1] + Jm[e][1] * s[2];
+            for (int f = e; f < 3; ++f) C[q++] += t0 * Jm[f][0] + t1 * Jm[f][1];
+        }
+    }
+    for (int k = 0; k < 6; ++k) cov3d[k] = (float)C[k];
+}
+
+// what alg_tail_stats_kernel adds to the tail's arguments
+struct AlgTailStats {
+    const float* stats2d;   // B*NV*J,5 of lt_softargmax2d_stats_fwd
+    float* cov2d;           // B,NV,J,3
+    float* reproj;          // B,NV,J
+    float* cov3d;           // B,J,6
+};
+
 // ---- algebraic tail (AlgebraicTriangulationNet, triangulation.py:166-193 after the 2D soft-argmax): one lane per (sample, joint) ------------
 // conf = raw / (sum over views) + 1e-5 (uniform raw = 1 without the confidence head), kp2d = soft-argmax * (W / w, H / h), then the DLT of
 // dlt_kernel on (kp2d, conf).  Every step is one IEEE rounding in the order of the Python host's torch ops (conf / conf.sum(1) + 1e-5,
@@ -643,10 +801,13 @@ __global__ void dlt_kernel(const float* __restrict__ proj, const float* __restri
 // the compacted views, step for step -- the k-th VALID view goes into partial k % 4, the rows of the valid views enter R in view order.  A
 // masked view gets confidence 0 and its 2D keypoint is passed through to kp2d only (never into the system, so NaN there stays there);
 // fewer than two valid views: NaN joints.
-template <bool MASKED>
-__global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
-                                float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
-                                float* __restrict__ kp3d, int B, int NV, int J) {
+// STATS (alg_tail_stats_kernel, lt_alg_tail_stats_fwd): the same loops, which also write every view's 2D covariance in image pixels (S Sigma_hm S in
+// fp64, rounded once), then dlt_stats_finish in dlt_solve's place.  Sigma_v in the propagation is that ROUNDED value read back, like the joint in the
+// reprojection error: both statistics can be reproduced from the outputs alone.
+template <bool MASKED, bool STATS>
+__device__ __forceinline__ void alg_tail_body(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
+                                              float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
+                                              float* __restrict__ kp3d, int B, int NV, int J, const AlgTailStats& so) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= B * J) return;
     const int b = g / J, j = g - b * J;
@@ -665,6 +826,12 @@ __global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __
         const long long i = ((long long)b * NV + v) * J + j;
         const float x = __fmul_rn(kp_hm[i * 2], sx), y = __fmul_rn(kp_hm[i * 2 + 1], sy);
         if (kp2d) { kp2d[i * 2] = x; kp2d[i * 2 + 1] = y; }
+        if (STATS) {
+            const float* s2 = so.stats2d + i * 5;
+            so.cov2d[i * 3] = (float)((double)sx * (double)sx * (double)s2[2]);
+            so.cov2d[i * 3 + 1] = (float)((double)sx * (double)sy * (double)s2[3]);
+            so.cov2d[i * 3 + 2] = (float)((double)sy * (double)sy * (double)s2[4]);
+        }
         if (MASKED && !mk[v]) {
             if (conf_out) conf_out[i] = 0.f;
             continue;
@@ -674,8 +841,68 @@ __global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __
         dlt_add_view(R, proj + ((long long)b * NV + v) * 12, (double)x, (double)y, (double)c);
     }
     float* o = kp3d + (long long)g * 3;
+    if (STATS) {
+        const long long i0 = (long long)b * NV * J + j;
+        // a view's values again, by the expressions of the loop above (each one IEEE rounding, so the same bits)
+        auto view = [&](const int v, double& x, double& y, double& c, double (&s)[3]) -> bool {
+            if (MASKED && !mk[v]) return false;
+            const long long i = i0 + (long long)v * J;
+            x = (double)__fmul_rn(kp_hm[i * 2], sx); y = (double)__fmul_rn(kp_hm[i * 2 + 1], sy);
+            c = (double)__fadd_rn(__fdiv_rn(conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f, sum), 1e-5f);
+            const float* s2 = so.stats2d + i * 5;
+            s[0] = (double)(float)((double)sx * (double)sx * (double)s2[2]);
+            s[1] = (double)(float)((double)sx * (double)sy * (double)s2[3]);
+            s[2] = (double)(float)((double)sy * (double)sy * (double)s2[4]);
+            return true;
+        };
+        dlt_stats_finish(R, !(MASKED && nvalid < 2), proj + (long long)b * NV * 12, NV, J, view, o, so.reproj + i0, so.cov3d + (long long)g * 6);
+        return;
+    }
     if (MASKED && nvalid < 2) { o[0] = o[1] = o[2] = __int_as_float(0x7fc00000); return; }
     dlt_solve(R, o);
+}
+
+// the plain tails keep their arguments; the statistics are kernels of their own over the same body
+template <bool MASKED>
+__global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
+                                float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
+                                float* __restrict__ kp3d, int B, int NV, int J) {
+    alg_tail_body<MASKED, false>(kp_hm, conf_raw, ld_conf, proj, sx, sy, mask, kp2d, conf_out, kp3d, B, NV, J, AlgTailStats());
+}
+
+template <bool MASKED>
+__global__ void alg_tail_stats_kernel(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
+                                      float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
+                                      float* __restrict__ kp3d, int B, int NV, int J, const AlgTailStats so) {
+    alg_tail_body<MASKED, true>(kp_hm, conf_raw, ld_conf, proj, sx, sy, mask, kp2d, conf_out, kp3d, B, NV, J, so);
+}
+
+// lt_triangulate_dlt_stats: dlt_kernel over the valid views (mask NULL: all of them) with the statistics; cov2d B,NV,J,3 {xx, xy, yy}
+__global__ void dlt_stats_kernel(const float* __restrict__ proj, const float* __restrict__ pts, const float* __restrict__ conf, const float* __restrict__ cov2d,
+                                 const uint8_t* __restrict__ mask, float* __restrict__ out, float* __restrict__ reproj, float* __restrict__ cov3d, int B, int NV,
+                                 int J) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= B * J) return;
+    const int b = g / J, j = g - b * J;
+    const uint8_t* mk = mask ? mask + (long long)b * NV : nullptr;
+    const long long i0 = (long long)b * NV * J + j;
+    auto view = [&](const int v, double& x, double& y, double& c, double (&s)[3]) -> bool {
+        if (mk && !mk[v]) return false;
+        const long long i = i0 + (long long)v * J;
+        x = (double)pts[i * 2]; y = (double)pts[i * 2 + 1];
+        c = conf ? (double)conf[i] : 1.0;
+        s[0] = (double)cov2d[i * 3]; s[1] = (double)cov2d[i * 3 + 1]; s[2] = (double)cov2d[i * 3 + 2];
+        return true;
+    };
+    double R[4][4] = {};  // R of A = QR, grown one valid view at a time
+    int nvalid = 0;
+    for (int v = 0; v < NV; ++v) {
+        double x, y, c, s[3];
+        if (!view(v, x, y, c, s)) continue;
+        dlt_add_view(R, proj + ((long long)b * NV + v) * 12, x, y, c);
+        ++nvalid;
+    }
+    dlt_stats_finish(R, nvalid >= 2, proj + (long long)b * NV * 12, NV, J, view, out + (long long)g * 3, reproj + i0, cov3d + (long long)g * 6);
 }
 
 // ---- backward of the 2D soft-argmax and of the DLT (training of the algebraic model, train.py:189-236) ---------------------------------------
@@ -704,11 +931,7 @@ __global__ __launch_bounds__(256) void sa2_bwd_kernel(const float* __restrict__ 
     }
 }
 
-// triangulate_point_from_multiple_views_linear_torch (multiview.py:141-168): X = v[:3] / v[3], v = right singular vector of A for its smallest
-// singular value = eigenvector of M = A^T A for its smallest eigenvalue lambda; rows of A: c_v (x_{v,r} P_v[2,:] - P_v[r,:]).  What autograd derives
-// through torch.svd there, written out:  g_v = (g_X / v3, -(g_X . v[:3]) / v3^2) (orthogonal to v: X does not depend on |v|),
-//   w = (lambda I - M)^+ g_v = sum_{i != min} e_i (e_i . g_v) / (lambda - lambda_i),   dL/dM = (w v^T + v w^T) / 2,   dL/dA = A (w v^T + v w^T),
-//   dL/dc_v = sum_r dL/dA[v,r,:] . (x P2 - Pr),   dL/dx_{v,r} = c_v dL/dA[v,r,:] . P_v[2,:].   fp64, one lane per (sample, joint).
+// the DLT's backward by the formulas above dlt_grad_w / dlt_grad_row: fp64, one lane per (sample, joint)
 __global__ void dlt_bwd_kernel(const float* __restrict__ proj, const float* __restrict__ pts, const float* __restrict__ conf,
                                const float* __restrict__ gout, float* __restrict__ gpts, float* __restrict__ gconf, int B, int NV, int J) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -722,36 +945,16 @@ __global__ void dlt_bwd_kernel(const float* __restrict__ proj, const float* __re
     }
     double V[4][4], ev[4];
     const int best = dlt_svd(R, V, ev);         // the forward's solve: eigenvectors of A^T A = right singular vectors, eigenvalues = sigma^2
-    const double lam = ev[best];
-    double vv[4], gv[4], wv[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 4; ++k) vv[k] = V[k][best];
+    double vv[4], wv[4];
     const double gX[3] = {(double)gout[g * 3], (double)gout[g * 3 + 1], (double)gout[g * 3 + 2]};
-    gv[0] = gX[0] / vv[3]; gv[1] = gX[1] / vv[3]; gv[2] = gX[2] / vv[3];
-    gv[3] = -(gX[0] * vv[0] + gX[1] * vv[1] + gX[2] * vv[2]) / (vv[3] * vv[3]);
-    for (int i = 0; i < 4; ++i) {
-        if (i == best) continue;
-        double dot = 0;
-        for (int k = 0; k < 4; ++k) dot += V[k][i] * gv[k];
-        const double f = dot / (lam - ev[i]);
-        for (int k = 0; k < 4; ++k) wv[k] += V[k][i] * f;
-    }
+    dlt_grad_w(V, ev, best, gX, vv, wv);
     for (int v = 0; v < NV; ++v) {
         const float* P = proj + ((long long)b * NV + v) * 12;
         const long long pi = ((long long)b * NV + v) * J + j;
         const float* p = pts + pi * 2;
         const double c = conf ? (double)conf[pi] : 1.0;
         double gc = 0;
-        for (int r = 0; r < 2; ++r) {
-            double raw[4], arow[4], av = 0, aw = 0;
-            for (int k = 0; k < 4; ++k) { raw[k] = (double)P[8 + k] * (double)p[r] - (double)P[4 * r + k]; arow[k] = raw[k] * c; av += arow[k] * vv[k]; aw += arow[k] * wv[k]; }
-            double gp = 0;
-            for (int k = 0; k < 4; ++k) {
-                const double ga = aw * vv[k] + av * wv[k];          // dL/dA[v,r,k] = (A (w v^T + v w^T))[row][k]
-                gc += ga * raw[k];
-                gp += ga * (double)P[8 + k];
-            }
-            gpts[pi * 2 + r] = (float)(gp * c);
-        }
+        for (int r = 0; r < 2; ++r) gpts[pi * 2 + r] = (float)(dlt_grad_row(P, (double)p[r], r, c, vv, wv, gc) * c);
         if (gconf) gconf[pi] = (float)gc;
     }
 }
@@ -864,29 +1067,77 @@ extern "C" int lt_triangulate_dlt(const float* proj, const float* points, const 
     return LT_OK;
 }
 
-// the one checked launch behind lt_alg_tail_fwd and lt_alg_tail_masked_fwd
-template <bool MASKED>
+extern "C" int lt_softargmax2d_stats_fwd(const float* heatmaps, float mult, int32_t softmax, float* coords, float* probs, float* stats, int32_t* peak_index,
+                                         int32_t NJ, int32_t h, int32_t w, void* stream) {
+    const char* who = "lt_softargmax2d_stats_fwd";
+    LT_REQUIRE(heatmaps && coords, LT_ERR_INVALID, "%s: null heatmaps or coords", who);
+    LT_REQUIRE(stats, LT_ERR_INVALID, "%s: null stats", who);
+    LT_REQUIRE(peak_index, LT_ERR_INVALID, "%s: null peak_index", who);
+    LT_REQUIRE(NJ >= 1 && h >= 1 && w >= 1, LT_ERR_INVALID, "%s: bad shape (NJ %d, h %d, w %d)", who, NJ, h, w);
+    LT_REQUIRE((int64_t)h * w <= 0x7fffffff, LT_ERR_UNSUPPORTED, "%s: h * w = %lld does not fit the int32 index of a heatmap", who, (long long)h * w);
+    hipLaunchKernelGGL(sa2_stats_kernel, dim3(NJ), dim3(256), 0, (hipStream_t)stream, heatmaps, mult, softmax, coords, probs, stats, peak_index, h, w);
+    LT_CHECK_LAUNCH(who);
+    return LT_OK;
+}
+
+extern "C" int lt_triangulate_dlt_stats(const float* proj, const float* points, const float* conf, const float* cov2d, const uint8_t* view_mask, float* out,
+                                        float* reproj_err, float* cov3d, int32_t B, int32_t NV, int32_t J, void* stream) {
+    const char* who = "lt_triangulate_dlt_stats";
+    LT_REQUIRE(proj && points && out, LT_ERR_INVALID, "%s: null proj, points or out", who);
+    LT_REQUIRE(cov2d, LT_ERR_INVALID, "%s: null cov2d", who);
+    LT_REQUIRE(reproj_err, LT_ERR_INVALID, "%s: null reproj_err", who);
+    LT_REQUIRE(cov3d, LT_ERR_INVALID, "%s: null cov3d", who);
+    LT_REQUIRE(B >= 1 && NV >= 2 && J >= 1, LT_ERR_INVALID, "%s: bad shape (B %d, NV %d, J %d)", who, B, NV, J);
+    hipLaunchKernelGGL(dlt_stats_kernel, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, proj, points, conf, cov2d, view_mask, out, reproj_err, cov3d, B,
+                       NV, J);
+    LT_CHECK_LAUNCH(who);
+    return LT_OK;
+}
+
+// the one checked launch behind lt_alg_tail_fwd, lt_alg_tail_masked_fwd and lt_alg_tail_stats_fwd
+template <bool MASKED, bool STATS>
 static int alg_tail_launch(const char* name, const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
-                           const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV, int32_t J, void* stream) {
+                           const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV, int32_t J, void* stream,
+                           const AlgTailStats so = AlgTailStats()) {
     LT_REQUIRE(keypoints_hm && proj && keypoints_3d, LT_ERR_INVALID, "%s: null argument", name);
     LT_REQUIRE(!MASKED || view_mask, LT_ERR_INVALID, "%s: null view_mask", name);
+    LT_REQUIRE(!STATS || so.stats2d, LT_ERR_INVALID, "%s: null stats2d", name);
+    LT_REQUIRE(!STATS || so.cov2d, LT_ERR_INVALID, "%s: null cov2d_img", name);
+    LT_REQUIRE(!STATS || so.reproj, LT_ERR_INVALID, "%s: null reproj_err", name);
+    LT_REQUIRE(!STATS || so.cov3d, LT_ERR_INVALID, "%s: null cov3d", name);
     LT_REQUIRE(B >= 1 && NV >= 2 && J >= 1, LT_ERR_INVALID, "%s: bad shape (B %d, NV %d, J %d)", name, B, NV, J);
     LT_REQUIRE(!conf_raw || ld_conf >= J, LT_ERR_INVALID, "%s: ld_conf %d < J %d", name, ld_conf, J);
-    hipLaunchKernelGGL(alg_tail_kernel<MASKED>, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x,
-                       scale_y, view_mask, keypoints_2d, confidences, keypoints_3d, B, NV, J);
+    if (STATS)
+        hipLaunchKernelGGL(alg_tail_stats_kernel<MASKED>, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x,
+                           scale_y, view_mask, keypoints_2d, confidences, keypoints_3d, B, NV, J, so);
+    else
+        hipLaunchKernelGGL(alg_tail_kernel<MASKED>, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x,
+                           scale_y, view_mask, keypoints_2d, confidences, keypoints_3d, B, NV, J);
     LT_CHECK_LAUNCH(name);
     return LT_OK;
 }
 
+extern "C" int lt_alg_tail_stats_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                                     const uint8_t* view_mask, const float* stats2d, float* keypoints_2d, float* confidences, float* keypoints_3d,
+                                     float* cov2d_img, float* reproj_err, float* cov3d, int32_t B, int32_t NV, int32_t J, void* stream) {
+    AlgTailStats so = {};
+    so.stats2d = stats2d; so.cov2d = cov2d_img; so.reproj = reproj_err; so.cov3d = cov3d;
+    if (view_mask)
+        return alg_tail_launch<true, true>("lt_alg_tail_stats_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, view_mask, keypoints_2d, confidences,
+                                           keypoints_3d, B, NV, J, stream, so);
+    return alg_tail_launch<false, true>("lt_alg_tail_stats_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, nullptr, keypoints_2d, confidences,
+                                        keypoints_3d, B, NV, J, stream, so);
+}
+
 extern "C" int lt_alg_tail_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
                                float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV, int32_t J, void* stream) {
-    return alg_tail_launch<false>("lt_alg_tail_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, nullptr, keypoints_2d, confidences, keypoints_3d,
+    return alg_tail_launch<false, false>("lt_alg_tail_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, nullptr, keypoints_2d, confidences, keypoints_3d,
                                   B, NV, J, stream);
 }
 
 extern "C" int lt_alg_tail_masked_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
                                       const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV,
                                       int32_t J, void* stream) {
-    return alg_tail_launch<true>("lt_alg_tail_masked_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, view_mask, keypoints_2d, confidences,
+    return alg_tail_launch<true, false>("lt_alg_tail_masked_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, view_mask, keypoints_2d, confidences,
                                  keypoints_3d, B, NV, J, stream);
 }

@@ -131,6 +131,7 @@ SIGNATURES = {
     "lt_plan_forward_cascade": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_set_view_mask": (C.c_int, [vp, vp]),
     "lt_plan_set_keypoint_stats": (C.c_int, [vp, vp, vp]),
+    "lt_plan_set_alg_keypoint_stats": (C.c_int, [vp, vp, vp, vp, vp, vp]),
     "lt_plan_info": (C.c_int, [vp, C.POINTER(PlanInfo)]),
     "lt_plan_destroy": (None, [vp]),
     "lt_last_error": (C.c_char_p, []),
@@ -176,9 +177,12 @@ SIGNATURES = {
     "lt_softargmax3d_stats_workspace": (C.c_size_t, [i32, i32, i64]),
     "lt_softargmax3d_stats_fwd": (C.c_int, [vp, vp, f32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp]),
     "lt_softargmax2d_fwd": (C.c_int, [vp, f32, i32, vp, vp, i32, i32, i32, vp]),
+    "lt_softargmax2d_stats_fwd": (C.c_int, [vp, f32, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_alg_tail_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
     "lt_alg_tail_masked_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "lt_alg_tail_stats_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "lt_triangulate_dlt_stats": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_heatmap_argmax_nchw_f32": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "lt_triangulate_ransac": (C.c_int, [vp, vp, vp, i32, C.c_double, i32, vp, vp, i32, i32, i32, vp]),
     "lt_crop_resize_u8": (C.c_int, [vp, i64, vp, vp, i32, i32, i32, vp, vp, vp]),

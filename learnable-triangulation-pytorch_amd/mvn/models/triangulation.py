@@ -810,10 +810,17 @@ class AlgebraicTriangulationNet(_PlannedNet):
         self.backbone = pose_resnet.get_pose_net(m.backbone, device=device)
         self.heatmap_softmax = m.heatmap_softmax
         self.heatmap_multiplier = m.heatmap_multiplier
+        # True: an eval forward also leaves the statistics of its joints (op.AlgKeypointStats: per view the 2D heatmap's peak, peak pixel, mass, covariance
+        # in image px^2 and the reprojection error; per joint the 3D covariance, the 2D ones pushed through the DLT) in last_keypoint_stats; the 4-tuple
+        # keeps its bits.  Ignored in train(), where last_keypoint_stats is None.
+        self.keypoint_stats = False
+        self.last_keypoint_stats = None
 
-    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False):
+    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False):
         """masked: the plan of forwards with ``batch["view_mask"]`` -- the same launches, plus the mask's device block and its pinned staging ring (the
-        tail after the plan is then lt_alg_tail_masked_fwd)."""
+        tail after the plan is then lt_alg_tail_masked_fwd).
+        stats: the plan of forwards with ``keypoint_stats`` -- the same launch list with lt_softargmax2d_stats_fwd in the soft-argmax op's place (the tail
+        after the plan is then lt_alg_tail_stats_fwd)."""
         b, x_in = self._open_plan(B * NV, Hh, W, device, dry_run)
         lib = b.lib
         hm, feats, algc, _ = self.backbone.record(b, x_in, want_heatmaps=True)
@@ -825,11 +832,20 @@ class AlgebraicTriangulationNet(_PlannedNet):
         kp2d = torch.empty(N, J, 2, dtype=torch.float32, device=device)
         probs = torch.empty_like(hm_nchw)
         mult, sm = float(self.heatmap_multiplier), int(bool(self.heatmap_softmax))
-        b.custom(lambda st: H.check(lib.lt_softargmax2d_fwd(hm_nchw.data_ptr(), mult, sm, kp2d.data_ptr(), probs.data_ptr(), N * J, h, w, st),
-                                    "lt_softargmax2d_fwd"))
+        kstats = kindex = None
+        if stats:          # the records (N, J, 5) {peak, mass, cxx, cxy, cyy} and peak pixels (N, J) out of the pass that writes the probabilities
+            kstats = torch.empty(N, J, 5, dtype=torch.float32, device=device)
+            kindex = torch.empty(N, J, dtype=torch.int32, device=device)
+            b.custom(lambda st: H.check(lib.lt_softargmax2d_stats_fwd(hm_nchw.data_ptr(), mult, sm, kp2d.data_ptr(), probs.data_ptr(), kstats.data_ptr(),
+                                                                      kindex.data_ptr(), N * J, h, w, st), "lt_softargmax2d_stats_fwd"),
+                     info={"entry": "lt_softargmax2d_stats_fwd", "stats": kstats, "peak_index": kindex})
+        else:
+            b.custom(lambda st: H.check(lib.lt_softargmax2d_fwd(hm_nchw.data_ptr(), mult, sm, kp2d.data_ptr(), probs.data_ptr(), N * J, h, w, st),
+                                        "lt_softargmax2d_fwd"))
         plan = b.finish()
-        plan.keep += [hm_nchw, kp2d, probs]
-        P = {"plan": plan, "x_in": x_in, "kp2d": kp2d, "probs": probs, "algc": algc, "hw": (h, w), "J": J, "masked": masked}
+        plan.keep += [hm_nchw, kp2d, probs] + ([kstats, kindex] if stats else [])
+        P = {"plan": plan, "x_in": x_in, "kp2d": kp2d, "probs": probs, "algc": algc, "hw": (h, w), "J": J, "masked": masked, "hm_nchw": hm_nchw,
+             "kstats": kstats, "kindex": kindex}
         if masked:
             P.update({"mask": torch.zeros(N, dtype=torch.uint8, device=device),
                       "mask_ring": PinnedRing(N, torch.uint8, 1 if dry_run else GEO_RING, pin=not dry_run)})
@@ -845,15 +861,20 @@ class AlgebraicTriangulationNet(_PlannedNet):
         if vm is not None and _bn_in_train_mode(self):
             raise NotImplementedError("AlgebraicTriangulationNet: batch['view_mask'] is inference only (there is no masked backward); call eval() first")
         H.require_gpu(images, "images")
+        self.last_keypoint_stats = None
         if _bn_in_train_mode(self):
-            return self._forward_train(images, proj_matricies)
+            return self._forward_train(images, proj_matricies)          # keypoint_stats is ignored there
         _sync_buffers_before_eval(self)
+        masked, stats = vm is not None, bool(self.keypoint_stats)
         with torch.cuda.device(device):
-            P = self._plan_for(self._plan_key(B, NV, Hh, W, device, vm is not None), lambda: self._build_plan(B, NV, Hh, W, device, masked=vm is not None))
+            P = self._plan_for(self._plan_key(B, NV, Hh, W, device, masked, stats), lambda: self._build_plan(B, NV, Hh, W, device, masked=masked, stats=stats))
             return self._run(P, images, proj_matricies, B, NV, Hh, W, device, vm)
 
-    def _plan_key(self, B, NV, Hh, W, device, masked=False):
-        return (B, NV, Hh, W, self.compute_dtype, device, float(self.heatmap_multiplier), bool(self.heatmap_softmax), self.tile_override, masked)
+    def _plan_key(self, B, NV, Hh, W, device, masked=False, stats=False):
+        """``masked``: the plan carries the mask's block; ``stats``: its soft-argmax op is lt_softargmax2d_stats_fwd (``keypoint_stats``).  Forwards without
+        a mask or without the flag keep their plans: an unflagged key is the tuple it always was."""
+        key = (B, NV, Hh, W, self.compute_dtype, device, float(self.heatmap_multiplier), bool(self.heatmap_softmax), self.tile_override, masked)
+        return key + ("keypoint_stats",) if stats else key
 
     def _forward_train(self, images, proj_matricies):
         """Training mode (round 3; the reference's loop for model_type "alg", train.py:189-236): the backbone -- heatmap head and, with
@@ -927,6 +948,17 @@ class AlgebraicTriangulationNet(_PlannedNet):
         kp2d = torch.empty(B, NV, J, 2, dtype=torch.float32, device=device)
         conf = torch.empty(B, NV, J, dtype=torch.float32, device=device)
         kp3d = torch.empty(B, J, 3, dtype=torch.float32, device=device)
+        if P.get("kstats") is not None:          # keypoint_stats: the same tail (masked or not) with the reprojection errors and the propagated covariance
+            rec, idx = P["kstats"].reshape(B, NV, J, 5).clone(), P["kindex"].reshape(B, NV, J).clone()
+            cov2d = torch.empty(B, NV, J, 3, dtype=torch.float32, device=device)
+            err = torch.empty(B, NV, J, dtype=torch.float32, device=device)
+            cov3d = torch.empty(B, J, 6, dtype=torch.float32, device=device)
+            H.check(H.lib().lt_alg_tail_stats_fwd(P["kp2d"].data_ptr(), None if algc is None else algc.t.data_ptr(), J if algc is None else algc.t.shape[-1],
+                                                  proj.data_ptr(), W / w, Hh / h, None if view_mask is None else P["mask"].data_ptr(), P["kstats"].data_ptr(),
+                                                  kp2d.data_ptr(), conf.data_ptr(), kp3d.data_ptr(), cov2d.data_ptr(), err.data_ptr(), cov3d.data_ptr(),
+                                                  B, NV, J, st), "lt_alg_tail_stats_fwd")
+            self.last_keypoint_stats = op.alg_keypoint_stats_from_records(rec, idx, cov2d, err, cov3d)
+            return kp3d, kp2d, heatmaps, conf
         if view_mask is not None:          # the same tail over the valid views of each sample; masked confidences are 0
             H.check(H.lib().lt_alg_tail_masked_fwd(P["kp2d"].data_ptr(), None if algc is None else algc.t.data_ptr(), J if algc is None else algc.t.shape[-1],
                                                    proj.data_ptr(), W / w, Hh / h, P["mask"].data_ptr(), kp2d.data_ptr(), conf.data_ptr(), kp3d.data_ptr(),
@@ -1063,6 +1095,7 @@ class CascadeTriangulationNet(nn.Module):
             raise ValueError("CascadeTriangulationNet: the algebraic model has %d joints, kind '%s' reads joint %d" % (J, vol_net.kind, need - 1))
         self.alg, self.vol = alg_net, vol_net
         self.last_keypoint_stats = None          # with vol.keypoint_stats: the op.KeypointStats of the last forward's volumetric stage
+        self.last_alg_keypoint_stats = None      # with alg.keypoint_stats: the op.AlgKeypointStats of the last forward's algebraic stage
 
     def forward(self, images, proj_matricies, batch):
         """images (B,NV,3,H,W) fp32 on the GPU; ``proj_matricies`` (B,NV,3,4) at image resolution for the algebraic stage; ``batch`` needs only
@@ -1082,7 +1115,9 @@ class CascadeTriangulationNet(nn.Module):
         vol = self.vol
         self.last_keypoint_stats = vol.last_keypoint_stats = None
         vol.__dict__.pop("_chunk_stats", None)
+        self.last_alg_keypoint_stats = None
         alg_out = self.alg(images, proj_matricies, batch)
+        self.last_alg_keypoint_stats = self.alg.last_keypoint_stats
         kp_alg = alg_out[0]
         _sync_buffers_before_eval(vol)
         cap = vol.max_samples_per_launch(NV, images.shape[3], images.shape[4])

@@ -151,6 +151,156 @@ def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_
     return out
 
 
+def triangulate_batch_of_points_with_stats(proj_matricies_batch, points_batch, confidences_batch=None, covariances_2d=None, view_mask=None):
+    """triangulate_batch_of_points plus the two quality measures of a triangulated joint (lt_triangulate_dlt_stats; ``triangulation_stats`` states them
+    in numpy fp64).  covariances_2d: (B,NV,J,2,2) -- or (B,NV,J,3) as {xx, xy, yy} -- the 2D covariance of every point in image px^2, e.g. the
+    ``covariance_2d`` of an AlgKeypointStats or of ``op.integrate_tensor_2d_with_stats`` scaled to image pixels.  Returns (keypoints_3d (B,J,3),
+    reprojection_error (B,NV,J) px, covariance (B,J,3,3)): the joints are bit for bit triangulate_batch_of_points' and differentiable in the same way; the
+    statistics carry no gradient.  view_mask as there (inference only; here the kernel skips masked views, whose reprojection_error is NaN)."""
+    H.require_gpu(points_batch, "points_batch")
+    if covariances_2d is None:
+        raise ValueError("triangulate_batch_of_points_with_stats: covariances_2d is required ((B, NV, J, 2, 2) or (B, NV, J, 3))")
+    dev = points_batch.device
+    P = proj_matricies_batch.to(dev, torch.float32).contiguous()
+    pts = points_batch.detach().float().contiguous()
+    conf = None if confidences_batch is None else confidences_batch.detach().float().contiguous()
+    B, NV, J = pts.shape[:3]
+    cov = covariances_2d.detach().to(dev, torch.float32)
+    if tuple(cov.shape) == (B, NV, J, 2, 2):
+        cov = cov.reshape(B, NV, J, 4)[..., [0, 1, 3]]
+    if tuple(cov.shape) != (B, NV, J, 3):
+        raise ValueError("covariances_2d must be (B, NV, J, 2, 2) or (B, NV, J, 3) = (%d, %d, %d, ...), got %s" % (B, NV, J, tuple(covariances_2d.shape)))
+    cov = cov.contiguous()
+    mask = None
+    needs_grad = torch.is_grad_enabled() and (points_batch.requires_grad or (confidences_batch is not None and confidences_batch.requires_grad))
+    if view_mask is not None:
+        from mvn.utils import op
+        if needs_grad:
+            raise NotImplementedError("triangulate_batch_of_points_with_stats: view_mask is inference only (no masked backward); call it under torch.no_grad()")
+        mask = torch.from_numpy(op.view_mask_host(view_mask, B, NV, min_valid=2)).to(dev)
+    out = torch.empty(B, J, 3, dtype=torch.float32, device=dev)
+    err = torch.empty(B, NV, J, dtype=torch.float32, device=dev)
+    c3 = torch.empty(B, J, 6, dtype=torch.float32, device=dev)
+    H.check(H.lib().lt_triangulate_dlt_stats(P.data_ptr(), pts.data_ptr(), H.ptr(conf), cov.data_ptr(), H.ptr(mask), out.data_ptr(), err.data_ptr(), c3.data_ptr(),
+                                             B, NV, J, H.cur_stream()), "lt_triangulate_dlt_stats")
+    if needs_grad:          # the same joints as an autograd node
+        out = triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_batch)
+    return out, err, c3[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(B, J, 3, 3)
+
+
+# ---- the numpy fp64 statement of the algebraic joints' statistics (CPU only) ------------------------------------------------------------------------
+def heatmap_stats_2d(heatmaps, mult=1.0, softmax=True, coords=None):
+    """The numpy fp64 statement of liblt_hip's ``lt_softargmax2d_stats_fwd`` (op.integrate_tensor_2d_with_stats).
+
+    heatmaps (..., h, w): the raw fp32 heatmaps; x = fp32(mult * heatmaps), the one rounding the kernel makes.  coords (..., 2): the (x, y) the soft-argmax
+    RETURNED (fp32) -- the moments are taken about them, never as E[c c^T] - mu mu^T; None: the fp64 soft-argmax of x, rounded to fp32.  Per heatmap, over
+    the flat index i = y * w + x with pixel centres c_i = (x, y):
+      softmax:  p = softmax(x);  peak_index = the smallest i with x_i maximal;  peak = p[peak_index];  mass = 1
+      ReLU:     w = relu(x);  mass = sum w;  peak_index as above, on x;  peak = w[peak_index] / mass;  p = w / mass;  mass == 0: peak = 0, covariance = 0
+      covariance = sum_i p_i (c_i - coords)(c_i - coords)^T, heatmap pixels^2
+    Returns (peak, peak_index (int64), mass, covariance (..., 2, 2)) as fp64 arrays."""
+    hm = np.asarray(heatmaps, dtype=np.float32)
+    lead, (h, w) = hm.shape[:-2], hm.shape[-2:]
+    x = (np.float32(mult) * hm).astype(np.float32).reshape(-1, h * w).astype(np.float64)
+    idx = x.argmax(axis=1)                                  # numpy: the first of equal maxima
+    if softmax:
+        p = np.exp(x - x.max(axis=1, keepdims=True))
+        p /= p.sum(axis=1, keepdims=True)
+        mass = np.ones(len(x))
+    else:
+        wgt = np.maximum(x, 0.0)
+        mass = wgt.sum(axis=1)
+        some = mass > 0
+        p = np.where(some[:, None], wgt / np.where(some, mass, 1.0)[:, None], 0.0)
+    c = np.stack([np.tile(np.arange(w, dtype=np.float64), h), np.repeat(np.arange(h, dtype=np.float64), w)], axis=1)          # (h * w, 2) as (x, y)
+    centre = (p @ c).astype(np.float32) if coords is None else np.asarray(coords, dtype=np.float32).reshape(-1, 2)
+    centre = np.where((mass > 0)[:, None], centre.astype(np.float64), 0.0)
+    d = c[None] - centre[:, None, :]
+    cov = np.einsum("ni,nir,nis->nrs", p, d, d)
+    cov[:, 1, 0] = cov[:, 0, 1]
+    peak = p[np.arange(len(x)), idx]
+    return peak.reshape(lead), idx.reshape(lead), mass.reshape(lead), cov.reshape(lead + (2, 2))
+
+
+def _dlt_rows(P, pts, conf):
+    """A (2 n, 4) of one joint: rows c_v (x_{v,r} P_v[2, :] - P_v[r, :])."""
+    A = np.empty((2 * len(P), 4))
+    for v in range(len(P)):
+        for r in range(2):
+            A[2 * v + r] = conf[v] * (pts[v, r] * P[v, 2] - P[v, r])
+    return A
+
+
+def triangulation_jacobian(proj, keypoints_2d, confidences=None, view_mask=None):
+    """The DLT joint and its Jacobian with respect to the 2D points, confidences held fixed, in numpy fp64: proj (B,NV,3,4), keypoints_2d (B,NV,J,2),
+    confidences (B,NV,J) as they enter the system (None = 1), view_mask (B,NV) (None = all valid; masked views are never read) ->
+    (X (B,J,3), jac (B,NV,J,3,2) with jac[b, v, j] = dX[b, j] / d keypoints_2d[b, v, j], zero for masked views).
+
+    X = v[:3] / v[3], v the right singular vector of A for its smallest singular value, i.e. the eigenvector of M = A^T A for its smallest eigenvalue
+    lambda.  The perturbation formula of a simple eigenvector, d v = (lambda I - M)^+ dM v, gives for a direction g_X in joint space
+      g_v = (g_X / v3, -(g_X . v[:3]) / v3^2),   w = (lambda I - M)^+ g_v,   dL/dA = A (w v^T + v w^T),   dL/dx_{v,r} = c_v dL/dA[v,r,:] . P_v[2,:]
+    (the formulas of lt_triangulate_dlt_bwd), evaluated for g_X = e_0, e_1, e_2.  Fewer than two valid views: NaN."""
+    P = np.asarray(proj, dtype=np.float64)
+    pts = np.asarray(keypoints_2d, dtype=np.float64)
+    B, NV, J = pts.shape[:3]
+    conf = np.ones((B, NV, J)) if confidences is None else np.asarray(confidences, dtype=np.float64)
+    mask = np.ones((B, NV), dtype=bool) if view_mask is None else np.asarray(view_mask) != 0
+    X = np.full((B, J, 3), np.nan)
+    jac = np.zeros((B, NV, J, 3, 2))
+    for b in range(B):
+        views = np.flatnonzero(mask[b])
+        if len(views) < 2:
+            jac[b] = np.nan
+            continue
+        for j in range(J):
+            A = _dlt_rows(P[b, views], pts[b, views, j], conf[b, views, j])
+            _, sv, vh = np.linalg.svd(A, full_matrices=False)          # at least four rows: four singular values, descending
+            lam = sv ** 2
+            v = vh[3]
+            X[b, j] = v[:3] / v[3]
+            for e in range(3):
+                gX = np.eye(3)[e]
+                gv = np.concatenate([gX / v[3], [-(gX @ v[:3]) / v[3] ** 2]])
+                wv = sum(vh[i] * (vh[i] @ gv) / (lam[3] - lam[i]) for i in range(3))
+                gA = A @ (np.outer(wv, v) + np.outer(v, wv))
+                for k, vw in enumerate(views):
+                    for r in range(2):
+                        jac[b, vw, j, e, r] = conf[b, vw, j] * (gA[2 * k + r] @ P[b, vw, 2])
+    return X, jac
+
+
+def triangulation_stats(proj, keypoints_2d, confidences, cov2d_img, keypoints_3d, view_mask=None):
+    """The numpy fp64 statement of the two statistics of liblt_hip's ``lt_alg_tail_stats_fwd`` / ``lt_triangulate_dlt_stats``.
+
+    proj (B,NV,3,4); keypoints_2d (B,NV,J,2) image px; confidences (B,NV,J) as they enter the system (None = 1); cov2d_img (B,NV,J,2,2) or (B,NV,J,3)
+    as {xx, xy, yy}, image px^2; keypoints_3d (B,J,3): the joints the triangulation RETURNED (fp32); view_mask (B,NV), None = all valid.  Returns
+      reprojection_error (B,NV,J): || pi(P_v, X) - keypoints_2d[b, v, j] ||_2 with X = keypoints_3d[b, j] and pi the perspective division of P_v [X; 1];
+                                   NaN for a masked view;
+      covariance (B,J,3,3): sum over the valid views of J_v Sigma_v J_v^T, J_v of ``triangulation_jacobian`` (first order, confidences fixed), in the
+                            squared world units of proj; NaN with fewer than two valid views.
+    Masked views' keypoints, matrices and covariances are never read."""
+    P = np.asarray(proj, dtype=np.float64)
+    pts = np.asarray(keypoints_2d, dtype=np.float64)
+    B, NV, J = pts.shape[:3]
+    S = np.asarray(cov2d_img, dtype=np.float64)
+    if S.shape == (B, NV, J, 3):
+        S = S[..., [0, 1, 1, 2]].reshape(B, NV, J, 2, 2)
+    X = np.asarray(keypoints_3d, dtype=np.float32).astype(np.float64)
+    mask = np.ones((B, NV), dtype=bool) if view_mask is None else np.asarray(view_mask) != 0
+    _, jac = triangulation_jacobian(P, pts, confidences, mask)
+    err = np.full((B, NV, J), np.nan)
+    cov = np.zeros((B, J, 3, 3))
+    for b in range(B):
+        if mask[b].sum() < 2:
+            cov[b] = np.nan
+            continue
+        for v in np.flatnonzero(mask[b]):
+            hh = X[b] @ P[b, v, :, :3].T + P[b, v, :, 3]          # (J, 3)
+            err[b, v] = np.sqrt(((hh[:, :2] / hh[:, 2:] - pts[b, v]) ** 2).sum(axis=1))
+            cov[b] += np.einsum("jer,jrs,jfs->jef", jac[b, v], S[b, v], jac[b, v])
+    return err, cov
+
+
 def triangulate_point_from_multiple_views_linear_torch(proj_matricies, points, confidences=None):
     """Single-point form of the above (reference :141-168)."""
     conf = None if confidences is None else confidences[None, :, None]

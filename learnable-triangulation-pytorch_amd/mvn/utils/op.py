@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 import lt_hip as H
-from mvn.utils.volumetric import KeypointStats
+from mvn.utils.volumetric import AlgKeypointStats, KeypointStats
 
 # workspace of lt_unproject_bwd's deterministic gather: at most this much (or one sample's share, if that is more); with less than the whole
 # batch's worth the entry point walks the batch in chunks.  One constant for the autograd path here and the recorded training step.
@@ -297,11 +297,31 @@ def batchnorm_batch_stats(x, running_mean=None, running_var=None, momentum=0.1):
     return mean, var
 
 
-def _softargmax2d_launch(heatmaps, softmax):
+def heatmap_stats_from_records(records, peak_index):
+    """The (..., 5) records {peak, mass, cxx, cxy, cyy} and (...) peak indices of lt_softargmax2d_stats_fwd as (peak, peak_index, mass, covariance (..., 2, 2))."""
+    cov = records[..., [2, 3, 3, 4]].reshape(records.shape[:-1] + (2, 2))
+    return records[..., 0], peak_index, records[..., 1], cov
+
+
+def alg_keypoint_stats_from_records(records, peak_index, cov2d_img, reproj_err, cov3d):
+    """The buffers of lt_softargmax2d_stats_fwd (records (B,NV,J,5), peak_index (B,NV,J)) and lt_alg_tail_stats_fwd (cov2d_img (B,NV,J,3), reproj_err
+    (B,NV,J), cov3d (B,J,6)) as an AlgKeypointStats."""
+    c2 = cov2d_img[..., [0, 1, 1, 2]].reshape(cov2d_img.shape[:-1] + (2, 2))
+    c3 = cov3d[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(cov3d.shape[:-1] + (3, 3))
+    return AlgKeypointStats(records[..., 0], peak_index, records[..., 1], c2, reproj_err, c3)
+
+
+def _softargmax2d_launch(heatmaps, softmax, with_stats=False):
     N, J, h, w = heatmaps.shape
     hm = heatmaps.float().contiguous()
     coords = torch.empty(N, J, 2, dtype=torch.float32, device=hm.device)
     probs = torch.empty_like(hm)
+    if with_stats:          # the same kernel with the statistics out of its third pass: coords and probs keep their bits
+        rec = torch.empty(N, J, 5, dtype=torch.float32, device=hm.device)
+        idx = torch.empty(N, J, dtype=torch.int32, device=hm.device)
+        H.check(H.lib().lt_softargmax2d_stats_fwd(hm.data_ptr(), 1.0, int(bool(softmax)), coords.data_ptr(), probs.data_ptr(), rec.data_ptr(), idx.data_ptr(), N * J,
+                                                  h, w, H.cur_stream()), "lt_softargmax2d_stats_fwd")
+        return coords, probs, heatmap_stats_from_records(rec, idx)
     H.check(H.lib().lt_softargmax2d_fwd(hm.data_ptr(), 1.0, int(bool(softmax)), coords.data_ptr(), probs.data_ptr(), N * J, h, w, H.cur_stream()),
             "lt_softargmax2d_fwd")
     return coords, probs
@@ -312,8 +332,13 @@ class _SoftArgmax2dFn(torch.autograd.Function):
     heatmaps; a gradient on the returned (softmaxed) heatmaps is refused -- no loss of the reference uses them."""
 
     @staticmethod
-    def forward(ctx, heatmaps, softmax):
-        coords, probs = _softargmax2d_launch(heatmaps, softmax)
+    def forward(ctx, heatmaps, softmax, stats_out=None):
+        # stats_out (integrate_tensor_2d_with_stats): a list that receives the statistics of this forward; they are no outputs of the node (no gradient)
+        if stats_out is None:
+            coords, probs = _softargmax2d_launch(heatmaps, softmax)
+        else:
+            coords, probs, st = _softargmax2d_launch(heatmaps, softmax, with_stats=True)
+            stats_out.append(st)
         ctx.save_for_backward(coords, probs)
         ctx.softmax, ctx.in_dtype = bool(softmax), heatmaps.dtype
         ctx.mark_non_differentiable(probs)
@@ -327,7 +352,7 @@ class _SoftArgmax2dFn(torch.autograd.Function):
         ghm = torch.empty_like(probs)
         H.check(H.lib().lt_softargmax2d_bwd(probs.data_ptr(), coords.data_ptr(), g.data_ptr(), 1.0, int(ctx.softmax), ghm.data_ptr(), N * J, h, w,
                                             H.cur_stream()), "lt_softargmax2d_bwd")
-        return ghm.to(ctx.in_dtype), None
+        return ghm.to(ctx.in_dtype), None, None
 
 
 def integrate_tensor_2d(heatmaps, softmax=True):
@@ -337,3 +362,15 @@ def integrate_tensor_2d(heatmaps, softmax=True):
     if torch.is_grad_enabled() and heatmaps.requires_grad:
         return _SoftArgmax2dFn.apply(heatmaps, softmax)
     return _softargmax2d_launch(heatmaps, softmax)
+
+def integrate_tensor_2d_with_stats(heatmaps, softmax=True):
+    """integrate_tensor_2d plus the per-heatmap statistics, out of the same pass that writes the normalised heatmaps (lt_softargmax2d_stats_fwd).  Returns
+    (coordinates, heatmaps, (peak (N,J), peak_index (N,J) int32, mass (N,J), covariance (N,J,2,2) in heatmap px^2 about the returned coordinates)): the first
+    two are bit for bit what integrate_tensor_2d returns and differentiable in the same way; the statistics carry no gradient.  The definitions in numpy
+    fp64: mvn.utils.multiview.heatmap_stats_2d."""
+    H.require_gpu(heatmaps, "heatmaps")
+    if torch.is_grad_enabled() and heatmaps.requires_grad:
+        out = []
+        coords, probs = _SoftArgmax2dFn.apply(heatmaps, softmax, out)
+        return coords, probs, out[0]
+    return _softargmax2d_launch(heatmaps, softmax, with_stats=True)

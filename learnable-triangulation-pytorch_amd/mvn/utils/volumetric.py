@@ -38,6 +38,16 @@ volumes[b, j]; mass (B,J) fp32, 1 in softmax mode and sum relu(logits) in ReLU m
 moments about the returned joint, in the frame of coord_volumes.  No gradient."""
 
 
+AlgKeypointStats = collections.namedtuple("AlgKeypointStats", ["peak", "peak_index", "mass", "covariance_2d", "reprojection_error", "covariance"])
+AlgKeypointStats.__doc__ = """Per-joint statistics of algebraic (triangulated) joints (``multiview.heatmap_stats_2d`` and ``multiview.triangulation_stats``
+state them in numpy fp64).  Per view: peak (B,NV,J) fp32, the 2D heatmap's largest normalised value; peak_index (B,NV,J) int32, the smallest flat index
+y * w + x of the largest value; mass (B,NV,J) fp32, 1 in softmax mode and sum relu(heatmap) in ReLU mode; covariance_2d (B,NV,J,2,2) fp32, image px^2:
+the heatmap's second moments about the returned 2D keypoint, scaled to image pixels -- the spread of the network's heatmap, not a calibrated error bar;
+reprojection_error (B,NV,J) fp32, px: distance between the view's 2D keypoint and the projection of the returned joint (NaN for a masked view).  Per
+joint: covariance (B,J,3,3) fp32, squared world units (mm^2 for Human3.6M): covariance_2d pushed through the triangulation to first order, confidences
+held fixed.  Values of masked views other than reprojection_error are unspecified.  No gradient."""
+
+
 def keypoint_stats(values, coords, keypoints, softmax=True, from_probs=False, mass=None):
     """The numpy fp64 statement of liblt_hip's ``lt_softargmax3d_stats_fwd`` (op.integrate_tensor_3d_with_stats, ``keypoint_stats`` of the models).
 
