@@ -395,7 +395,10 @@ int lt_triangulate_dlt_bwd(const float* proj, const float* points, const float* 
  * lt_unproject_bwd: grad_out B,v0,v1,v2,C (channels-last, fp32; the coordinate volume's grid shape) -> grad_feats B,NV,h,w,C fp32 (written
  *   completely, no pre-zeroing), grad_conf B,NV,C or NULL.  Autograd semantics of op.py:113-162: nothing flows to the grid / projections;
  *   depth <= 0 samples pass no gradient but their zero takes part in the view softmax, d out/d x_v = w_v (1 + x_v - out); 'max': the first
- *   maximal view; LT_AGG_CONF: g * conf_v and grad_conf_v = sum over voxels of g * x_v; LT_AGG_CONF_NORM: conf is the RAW head output,
+ *   maximal view.  Tie rule of 'max': the whole gradient of a voxel and channel goes to the LOWEST view index among the views whose sample equals
+ *   the maximum (a later view wins only where it is strictly greater), for every NV.  A view at depth <= 0 takes part in max and softmax with the
+ *   value 0 -- ties at 0 are the normal case -- and where such a view is that first maximum the gradient is dropped: its four weights are 0.
+ *   LT_AGG_CONF: g * conf_v and grad_conf_v = sum over voxels of g * x_v; LT_AGG_CONF_NORM: conf is the RAW head output,
  *   normalised over the views as in the forward (triangulation.py:268-269), grad_conf is the gradient of the raw values.  1 <= NV <= 32
  *   (more is LT_ERR_UNSUPPORTED: the many-view kernels' LDS copies and the finalizer's workgroup are sized by it), C % 4 == 0.  Three
  *   launches over a workspace, K0 taps, K1 per-view gradient of the sampled values, K2 gather; K0 and K2 take any NV.  NV <= 8: K1 keeps

@@ -203,9 +203,10 @@ def test_unproject_backward_is_bitwise_repeatable_and_matches_the_scatter(golden
     assert float(g1.abs().max()) > 0
 
 
-@pytest.mark.parametrize("C,hw,vshape", [(4, (20, 37), (5, 6, 7)), (16, (33, 16), (8, 8, 8)), (64, (17, 40), (9, 4, 6)), (32, (96, 96), (12, 16, 20))])
+@pytest.mark.parametrize("C,hw,vshape", [(4, (20, 37), (5, 6, 7)), (16, (33, 16), (8, 8, 8)), (64, (17, 40), (9, 4, 6)), (32, (96, 96), (12, 16, 20)), (8, (20, 37), (5, 6, 7))])
 def test_unproject_backward_gather_every_channel_width_and_ragged_shapes(C, hw, vshape):
-    """Every instantiation of the gather (channels per wave 1 / 4 / 16 / 8: C = 64 is the one-hit-at-a-time form without half-waves), maps
+    """Every instantiation of the gather (channels per wave 1 / 2 / 4 / 16 / 8 -- C = 8 is the only user of the record path with fewer than four channels
+    per wave, C = 64 is the one-hit-at-a-time form without half-waves), maps
     that are not multiples of the 16 x 16 tile, coordinate grids that are not multiples of the 4 x 4 x 4 brick, a camera inside the grid
     (depth <= 0 voxels): against the round-2 scatter (itself gated against the reference's autograd), all four aggregations with gradients,
     bitwise repeatable."""
