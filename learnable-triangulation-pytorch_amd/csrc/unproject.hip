@@ -15,6 +15,7 @@
 
 #include <type_traits>
 
+#include "unproj_geom.h"
 #include "wave_prims.h"
 
 using namespace lt;
@@ -54,37 +55,6 @@ __global__ void coord_volumes_kernel(const float* __restrict__ pos, const float*
         voxel_coord(pos + 3 * b, center + 3 * b, rot + 9 * b, step, i, j, k, V, cmu, o[0], o[1], o[2]);
     }
 }
-
-template <typename T, int CH> struct ChVec;  // CH channels of one pixel <-> CH floats
-template <> struct ChVec<float, 4> {
-    static __device__ __forceinline__ void ld(const float* p, float (&f)[4]) {
-        const float4 v = *(const float4*)p;
-        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-    }
-    static __device__ __forceinline__ void st(float* p, const float (&f)[4]) { *(float4*)p = make_float4(f[0], f[1], f[2], f[3]); }
-};
-template <> struct ChVec<float, 1> {
-    static __device__ __forceinline__ void ld(const float* p, float (&f)[1]) { f[0] = *p; }
-    static __device__ __forceinline__ void st(float* p, const float (&f)[1]) { *p = f[0]; }
-};
-template <> struct ChVec<bf16_t, 8> {
-    static __device__ __forceinline__ void ld(const bf16_t* p, float (&f)[8]) {
-        const uint4 v = *(const uint4*)p;
-        const unsigned u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            f[2 * i] = __uint_as_float(u[i] << 16);
-            f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ void st(bf16_t* p, const float (&f)[8]) {
-        *(uint4*)p = make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
-    }
-};
-template <> struct ChVec<bf16_t, 1> {
-    static __device__ __forceinline__ void ld(const bf16_t* p, float (&f)[1]) { f[0] = bf16_to_f32(*p); }
-    static __device__ __forceinline__ void st(bf16_t* p, const float (&f)[1]) { *p = f32_to_bf16(f[0]); }
-};
 
 struct UnprojArgs {
     const void* feats;
@@ -132,52 +102,37 @@ __device__ __forceinline__ void brick_of(const UnprojArgs& a, int chunk, int& bi
     }
 }
 
-// fp32 (parity) mode keeps IEEE divisions / expf; bf16 (throughput) mode uses v_rcp_f32 / v_exp_f32: the kernel was
-// issue-bound (PMC: SQ_WAIT_INST_ANY 40 %, ~50 IEEE divisions + 32 expf per lane-item), not memory-bound.
-template <bool FAST> __device__ __forceinline__ float div_(float a, float b) { return FAST ? a * __builtin_amdgcn_rcpf(b) : __fdiv_rn(a, b); }
-template <bool FAST> __device__ __forceinline__ float exp_(float x) { return FAST ? __expf(x) : expf(x); }
+// workgroup -> (sample, chunk); XCD-pinned when B % 8 == 0 (block b runs on XCD b % 8)
+__device__ __forceinline__ void sample_chunk_of(const UnprojArgs& a, int& b, int& chunk) {
+    if (a.xcd_pin) {
+        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+        b = xcd + 8 * (j / a.chunks);
+        chunk = j % a.chunks;
+    } else {
+        b = blockIdx.x / a.chunks;
+        chunk = blockIdx.x % a.chunks;
+    }
+}
 
-// Bilinear sample of CH channels for one voxel in one view; mirrors ATen's CPU grid_sampler_2d
-// (bilinear, zeros padding, align_corners=True) and op.py:116-141.
+// Bilinear sample of CH channels for one voxel in one view (project_taps' geometry): only the corners inside the map are loaded, and
+// blended with the raw weights -- the first of the two load disciplines of unproj_geom.h.
 template <typename T, int CH>
 __device__ __forceinline__ void sample_view(const T* __restrict__ fmap, const float* __restrict__ P, float X0, float X1,
                                             float X2, int h, int w, int C, int c0, float (&val)[CH]) {
-    // multiview.py:105: [X,1] @ P^T, k-ordered
-    const float px = __fadd_rn(fmaf(X2, P[2], fmaf(X1, P[1], __fmul_rn(X0, P[0]))), P[3]);
-    const float py = __fadd_rn(fmaf(X2, P[6], fmaf(X1, P[5], __fmul_rn(X0, P[4]))), P[7]);
-    float pz = __fadd_rn(fmaf(X2, P[10], fmaf(X1, P[9], __fmul_rn(X0, P[8]))), P[11]);
-    const bool invalid = pz <= 0.0f;  // op.py:123
-    if (pz == 0.0f) pz = 1.0f;        // op.py:125
-    constexpr bool FAST = sizeof(T) == 2;
-    const float u = div_<FAST>(px, pz), v = div_<FAST>(py, pz);
-    // op.py:128-129: x normalised by heatmap_shape[0] (= h), y by heatmap_shape[1] (= w)
-    const float gx = __fmul_rn(2.0f, __fsub_rn(div_<FAST>(u, (float)h), 0.5f));
-    const float gy = __fmul_rn(2.0f, __fsub_rn(div_<FAST>(v, (float)w), 0.5f));
-    // grid_sample, align_corners=True: pixel = (g + 1) * (size - 1) / 2
-    const float ix = __fmul_rn(__fadd_rn(gx, 1.0f), 0.5f * (float)(w - 1));
-    const float iy = __fmul_rn(__fadd_rn(gy, 1.0f), 0.5f * (float)(h - 1));
-    const float xw = floorf(ix), yn = floorf(iy);
-    const float we = __fsub_rn(ix, xw), ww = __fsub_rn(1.0f, we);
-    const float ws = __fsub_rn(iy, yn), wn = __fsub_rn(1.0f, ws);
+    const FullTap t = project_taps<sizeof(T) == 2>(P, X0, X1, X2, h, w);
 #pragma unroll
     for (int e = 0; e < CH; ++e) val[e] = 0.f;
-    if (invalid) return;  // op.py:141 (the sample is computed, then zeroed)
-    // in-range tests in float (huge / NaN coordinates never convert to int)
-    const bool xw_ok = xw >= 0.f && xw <= (float)(w - 1), xe_ok = xw >= -1.f && xw <= (float)(w - 2);
-    const bool yn_ok = yn >= 0.f && yn <= (float)(h - 1), ys_ok = yn >= -1.f && yn <= (float)(h - 2);
-    if (!((xw_ok || xe_ok) && (yn_ok || ys_ok))) return;
-    const int x0 = (int)xw, y0 = (int)yn;
+    if (!t.act) return;
     float t00[CH], t01[CH], t10[CH], t11[CH];
 #pragma unroll
     for (int e = 0; e < CH; ++e) t00[e] = t01[e] = t10[e] = t11[e] = 0.f;
-    const T* base = fmap + ((long long)y0 * w + x0) * C + c0;
-    if (yn_ok && xw_ok) ChVec<T, CH>::ld(base, t00);
-    if (yn_ok && xe_ok) ChVec<T, CH>::ld(base + C, t01);
-    if (ys_ok && xw_ok) ChVec<T, CH>::ld(base + (long long)w * C, t10);
-    if (ys_ok && xe_ok) ChVec<T, CH>::ld(base + (long long)w * C + C, t11);
-    const float nw = __fmul_rn(wn, ww), ne = __fmul_rn(wn, we), sw = __fmul_rn(ws, ww), se = __fmul_rn(ws, we);
+    const T* base = fmap + ((long long)t.y0 * w + t.x0) * C + c0;
+    if (t.yn_ok && t.xw_ok) ChVec<T, CH>::ld(base, t00);
+    if (t.yn_ok && t.xe_ok) ChVec<T, CH>::ld(base + C, t01);
+    if (t.ys_ok && t.xw_ok) ChVec<T, CH>::ld(base + (long long)w * C, t10);
+    if (t.ys_ok && t.xe_ok) ChVec<T, CH>::ld(base + (long long)w * C + C, t11);
 #pragma unroll
-    for (int e = 0; e < CH; ++e) val[e] = t00[e] * nw + t01[e] * ne + t10[e] * sw + t11[e] * se;
+    for (int e = 0; e < CH; ++e) val[e] = t00[e] * t.wt[0] + t01[e] * t.wt[1] + t10[e] * t.wt[2] + t11[e] * t.wt[3];
 }
 
 // does view v take part?  Without a mask: constant true, so the unmasked instantiations compile to what they did before the mask existed
@@ -194,16 +149,8 @@ template <typename T, int CH, bool SMALL_NV, bool MASKED = false>
 __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKED> a) {
     constexpr bool FAST = sizeof(T) == 2;
     const int tpv = a.C / CH;  // lanes per voxel
-    // workgroup -> (sample, chunk); XCD-pinned when B % 8 == 0 (block b runs on XCD b % 8)
     int b, chunk;
-    if (a.xcd_pin) {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        b = xcd + 8 * (j / a.chunks);
-        chunk = j % a.chunks;
-    } else {
-        b = blockIdx.x / a.chunks;
-        chunk = blockIdx.x % a.chunks;
-    }
+    sample_chunk_of(a, b, chunk);
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
     const T* feats = (const T*)a.feats + (long long)b * a.NV * a.h * a.w * a.C;
     const float* P = a.proj + (long long)b * a.NV * 12;
@@ -363,14 +310,7 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
     typedef bf16_t T;
     constexpr int C = 32, NV = 4 * NVL;
     int b, chunk;
-    if (a.xcd_pin) {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        b = xcd + 8 * (j / a.chunks);
-        chunk = j % a.chunks;
-    } else {
-        b = blockIdx.x / a.chunks;
-        chunk = blockIdx.x % a.chunks;
-    }
+    sample_chunk_of(a, b, chunk);
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
     const T* feats = (const T*)a.feats + (long long)b * NV * a.h * a.w * C;
     const float* coords = GRID ? nullptr : a.coords + (long long)b * nvox * 3;
@@ -417,33 +357,10 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
         float k00[NVL], k01[NVL], k10[NVL], k11[NVL];
 #pragma unroll
         for (int s = 0; s < NVL; ++s) {
-            // ---- projection of the voxel into view qv + 4 s (the arithmetic of sample_view<bf16>) ----
-            const float* Ps = P[s];
-            const float px = __fadd_rn(fmaf(X2, Ps[2], fmaf(X1, Ps[1], __fmul_rn(X0, Ps[0]))), Ps[3]);
-            const float py = __fadd_rn(fmaf(X2, Ps[6], fmaf(X1, Ps[5], __fmul_rn(X0, Ps[4]))), Ps[7]);
-            float pz = __fadd_rn(fmaf(X2, Ps[10], fmaf(X1, Ps[9], __fmul_rn(X0, Ps[8]))), Ps[11]);
-            const bool invalid = pz <= 0.0f;
-            if (pz == 0.0f) pz = 1.0f;
-            const float rz = __builtin_amdgcn_rcpf(pz);
-            const float u = px * rz, vv = py * rz;
-            const float gx = __fmul_rn(2.0f, __fsub_rn(u * inv_h, 0.5f));      // op.py:128-129: x by h, y by w
-            const float gy = __fmul_rn(2.0f, __fsub_rn(vv * inv_w, 0.5f));
-            const float ix = __fmul_rn(__fadd_rn(gx, 1.0f), 0.5f * (float)(w - 1));
-            const float iy = __fmul_rn(__fadd_rn(gy, 1.0f), 0.5f * (float)(h - 1));
-            const float xw = floorf(ix), yn = floorf(iy);
-            const float we = __fsub_rn(ix, xw), ww = __fsub_rn(1.0f, we);
-            const float ws = __fsub_rn(iy, yn), wn = __fsub_rn(1.0f, ws);
-            const bool xw_ok = xw >= 0.f && xw <= (float)(w - 1), xe_ok = xw >= -1.f && xw <= (float)(w - 2);
-            const bool yn_ok = yn >= 0.f && yn <= (float)(h - 1), ys_ok = yn >= -1.f && yn <= (float)(h - 2);
-            const bool act = !invalid && (xw_ok || xe_ok) && (yn_ok || ys_ok);
-            const int x0 = act ? (int)xw : 0, y0 = act ? (int)yn : 0;
-            const int xwc = min(max(x0, 0), w - 1), xec = min(max(x0 + 1, 0), w - 1);
-            const int rn = min(max(y0, 0), h - 1) * w, rs = min(max(y0 + 1, 0), h - 1) * w;
-            // this view's four corners: element offsets (clamped into the map) and weights (0 where the corner is padding)
-            const int vbase = (qv + 4 * s) * h * w * C;
-            o00[s] = vbase + (rn + xwc) * C; o01[s] = vbase + (rn + xec) * C; o10[s] = vbase + (rs + xwc) * C; o11[s] = vbase + (rs + xec) * C;
-            k00[s] = (act && yn_ok && xw_ok) ? __fmul_rn(wn, ww) : 0.f; k01[s] = (act && yn_ok && xe_ok) ? __fmul_rn(wn, we) : 0.f;
-            k10[s] = (act && ys_ok && xw_ok) ? __fmul_rn(ws, ww) : 0.f; k11[s] = (act && ys_ok && xe_ok) ? __fmul_rn(ws, we) : 0.f;
+            // view qv + 4 s: its four corners as element offsets (clamped into the map) and weights (0 where the corner is padding)
+            const FullTap tp = project_taps<true>(P[s], X0, X1, X2, h, w, inv_h, inv_w, C, (qv + 4 * s) * h * w * C);
+            o00[s] = tp.off[0]; o01[s] = tp.off[1]; o10[s] = tp.off[2]; o11[s] = tp.off[3];
+            k00[s] = tp.k[0]; k01[s] = tp.k[1]; k10[s] = tp.k[2]; k11[s] = tp.k[3];
         }
 
         f32x2_t val[NV][4];                               // [view][channel pair] of this lane's 8 channels
@@ -520,36 +437,38 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
     }
 }
 
+// One workgroup of 256 threads per (sample, chunk).  An unmasked kernel receives a plain UnprojArgs by value (the base of m) and a masked one all of
+// m: that is what keeps the unmasked kernels' argument block, and with it their code, what it was before the mask existed.
+template <bool MASKED>
+void launch_chunks(void (*kern)(UnprojArgsOf<MASKED>), const UnprojMaskedArgs& m, hipStream_t st) {
+    const UnprojArgsOf<MASKED>& a = m;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)m.B * m.chunks)), dim3(256), 0, st, a);
+}
+template <bool MASKED>
+void launch_quad(const UnprojMaskedArgs& m, bool grid, hipStream_t st) {
+    launch_chunks<MASKED>(m.NV == 4 ? (grid ? unproject_qn_kernel<1, true, MASKED> : unproject_qn_kernel<1, false, MASKED>)
+                                    : (grid ? unproject_qn_kernel<2, true, MASKED> : unproject_qn_kernel<2, false, MASKED>), m, st);
+}
+template <typename T, int CH, bool MASKED>
+void launch_generic(const UnprojMaskedArgs& m, hipStream_t st) {
+    launch_chunks<MASKED>(m.NV <= 8 ? unproject_kernel<T, CH, true, MASKED> : unproject_kernel<T, CH, false, MASKED>, m, st);
+}
 template <typename T, int CH>
 int launch_unproject(const UnprojMaskedArgs& m, hipStream_t st) {
-    const UnprojArgs& a = m;
-    const unsigned grid = (unsigned)((long long)a.B * a.chunks);
-    if (m.mask) {
-        if (a.NV <= 8) hipLaunchKernelGGL((unproject_kernel<T, CH, true, true>), dim3(grid), dim3(256), 0, st, m);
-        else hipLaunchKernelGGL((unproject_kernel<T, CH, false, true>), dim3(grid), dim3(256), 0, st, m);
-        LT_CHECK_LAUNCH("lt_unproject_masked_fwd");
-        return LT_OK;
-    }
-    if (a.NV <= 8) hipLaunchKernelGGL((unproject_kernel<T, CH, true>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((unproject_kernel<T, CH, false>), dim3(grid), dim3(256), 0, st, a);
-    LT_CHECK_LAUNCH("lt_unproject_fwd");
+    if (m.mask) launch_generic<T, CH, true>(m, st);
+    else launch_generic<T, CH, false>(m, st);
+    LT_CHECK_LAUNCH(m.mask ? "lt_unproject_masked_fwd" : "lt_unproject_fwd");
     return LT_OK;
 }
 
-}  // namespace
-
-extern "C" int lt_coord_volumes(const float* pos, const float* center, const float* rot, float step, int32_t B, int32_t V,
-                                int32_t cmu_transfer, float* coords, void* stream) {
-    LT_REQUIRE(pos && center && rot && coords && B >= 1 && V >= 2, LT_ERR_INVALID, "lt_coord_volumes: bad argument");
-    const long long total = (long long)B * V * V * V;
-    const long long blocks = cdiv(total, 256);
-    hipLaunchKernelGGL(coord_volumes_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream, pos,
-                       center, rot, step, B, V, cmu_transfer, coords);
-    LT_CHECK_LAUNCH("lt_coord_volumes");
+int launch_coord_volumes(const char* what, const float* pos, const float* center, const float* rot, float step, int B, int V, int cmu, float* coords,
+                         hipStream_t st) {
+    const long long blocks = cdiv((long long)B * V * V * V, 256);
+    hipLaunchKernelGGL(coord_volumes_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, pos, center, rot, step, B, V, cmu, coords);
+    LT_CHECK_LAUNCH(what);
     return LT_OK;
 }
 
-namespace {
 // fills the launch geometry and picks the kernel; a.coords (read) or the a.g_* grid description must be set by the caller.  a.mask set: the masked
 // instantiation of the SAME kernel the unmasked call takes (a masked plan never leaves the quad kernel for the generic one).
 int unproject_dispatch(UnprojMaskedArgs& a, int dtype, bool grid, hipStream_t st) {
@@ -559,40 +478,19 @@ int unproject_dispatch(UnprojMaskedArgs& a, int dtype, bool grid, hipStream_t st
     a.chunks = (int)cdiv(nvox, 256);
     a.xcd_pin = (a.B % 8 == 0) ? 1 : 0;
     LT_REQUIRE((long long)a.B * a.chunks < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_fwd: grid too large");
-    const unsigned nblk = (unsigned)((long long)a.B * a.chunks);
     // quad kernel: bf16, 32 channels, 4 or 8 views, view softmax, bricked volume (BASELINE configurations 2 and 4)
     const bool no_q4 = env_on("LT_UNPROJ_NO_Q4");       // A/B, read per call
     const bool quad = dtype == LT_BF16 && a.C == 32 && (a.NV == 4 || a.NV == 8) && a.bricked && a.agg == LT_AGG_SOFTMAX && !no_q4 &&
                       (long long)a.NV * a.h * a.w * a.C < (1ll << 30);
-    if (quad && a.mask) {
-        if (a.NV == 4) {
-            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<1, true, true>), dim3(nblk), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((unproject_qn_kernel<1, false, true>), dim3(nblk), dim3(256), 0, st, a);
-        } else {
-            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<2, true, true>), dim3(nblk), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((unproject_qn_kernel<2, false, true>), dim3(nblk), dim3(256), 0, st, a);
-        }
-        LT_CHECK_LAUNCH("lt_unproject_masked_fwd(quad)");
-        return LT_OK;
-    }
     if (quad) {
-        const UnprojArgs& u = a;
-        if (a.NV == 4) {
-            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<1, true>), dim3(nblk), dim3(256), 0, st, u);
-            else hipLaunchKernelGGL((unproject_qn_kernel<1, false>), dim3(nblk), dim3(256), 0, st, u);
-        } else {
-            if (grid) hipLaunchKernelGGL((unproject_qn_kernel<2, true>), dim3(nblk), dim3(256), 0, st, u);
-            else hipLaunchKernelGGL((unproject_qn_kernel<2, false>), dim3(nblk), dim3(256), 0, st, u);
-        }
-        LT_CHECK_LAUNCH("lt_unproject_fwd(quad)");
+        if (a.mask) launch_quad<true>(a, grid, st);
+        else launch_quad<false>(a, grid, st);
+        LT_CHECK_LAUNCH(a.mask ? "lt_unproject_masked_fwd(quad)" : "lt_unproject_fwd(quad)");
         return LT_OK;
     }
     if (grid) {      // no fused kernel for this configuration: materialise the grid (it is a returned tensor anyway), then gather
-        const long long total = (long long)a.B * nvox;
-        const long long blocks = cdiv(total, 256);
-        hipLaunchKernelGGL(coord_volumes_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, a.g_pos, a.g_center, a.g_rot,
-                           a.g_step, a.B, a.v0, a.g_cmu, a.coords_out);
-        LT_CHECK_LAUNCH("lt_unproject_grid_fwd(coords)");
+        const int rc = launch_coord_volumes("lt_unproject_grid_fwd(coords)", a.g_pos, a.g_center, a.g_rot, a.g_step, a.B, a.v0, a.g_cmu, a.coords_out, st);
+        if (rc != LT_OK) return rc;
         a.coords = a.coords_out;
     }
     if (dtype == LT_F32) {
@@ -602,70 +500,65 @@ int unproject_dispatch(UnprojMaskedArgs& a, int dtype, bool grid, hipStream_t st
     if (a.C % 8 == 0) return launch_unproject<bf16_t, 8>(a, st);
     return launch_unproject<bf16_t, 1>(a, st);
 }
+
+// The cuboid of the grid entries (the voxel centres are computed from it and written to coords_out); the coordinate entries read `coords` and have none.
+struct UnprojCuboid {
+    const float *pos, *center, *rot;
+    float step;
+    int cmu;
+    float* coords_out;
+};
+
+// The one body behind the four forward entries: `who` is the entry that was called, `cub` is set by the grid entries (v0 = v1 = v2 = V there) and
+// `masked` by the masked ones.
+int unproject_forward(const char* who, int dtype, const void* feats, const float* proj, const float* coords, const UnprojCuboid* cub, const float* conf,
+                      bool masked, const uint8_t* view_mask, void* out, int B, int NV, int C, int h, int w, int v0, int v1, int v2, int agg, void* stream) {
+    LT_REQUIRE(feats && proj && out && (cub ? cub->pos && cub->center && cub->rot && cub->coords_out : coords != nullptr), LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(!masked || view_mask, LT_ERR_INVALID, "%s: null view_mask", who);
+    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    LT_REQUIRE(agg >= LT_AGG_SUM && agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "%s: unknown aggregation %d", who, agg);
+    LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "%s: LT_AGG_CONF* needs confidences", who);
+    LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && (cub ? v0 >= 2 : v0 >= 1 && v1 >= 1 && v2 >= 1), LT_ERR_INVALID, "%s: bad shape", who);
+    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
+    UnprojMaskedArgs a = {};
+    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out; a.mask = masked ? view_mask : nullptr;
+    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = v0; a.v1 = v1; a.v2 = v2; a.agg = agg;
+    if (cub) { a.g_pos = cub->pos; a.g_center = cub->center; a.g_rot = cub->rot; a.g_step = cub->step; a.g_cmu = cub->cmu; a.coords_out = cub->coords_out; }
+    return unproject_dispatch(a, dtype, cub != nullptr, (hipStream_t)stream);
+}
+
 }  // namespace
+
+extern "C" int lt_coord_volumes(const float* pos, const float* center, const float* rot, float step, int32_t B, int32_t V,
+                                int32_t cmu_transfer, float* coords, void* stream) {
+    LT_REQUIRE(pos && center && rot && coords && B >= 1 && V >= 2, LT_ERR_INVALID, "lt_coord_volumes: bad argument");
+    return launch_coord_volumes("lt_coord_volumes", pos, center, rot, step, B, V, cmu_transfer, coords, (hipStream_t)stream);
+}
 
 extern "C" int lt_unproject_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf,
                                 void* out, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1,
                                 int32_t v2, int32_t agg, void* stream) {
-    LT_REQUIRE(feats && proj && coords && out, LT_ERR_INVALID, "lt_unproject_fwd: null argument");
-    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "lt_unproject_fwd: bad dtype %d", dtype);
-    LT_REQUIRE(agg >= LT_AGG_SUM && agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "lt_unproject_fwd: unknown aggregation %d", agg);
-    LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "lt_unproject_fwd: LT_AGG_CONF* needs confidences");
-    LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_INVALID, "lt_unproject_fwd: bad shape");
-    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_fwd: feature maps too large");
-    UnprojMaskedArgs a = {};
-    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out;
-    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = v0; a.v1 = v1; a.v2 = v2; a.agg = agg;
-    return unproject_dispatch(a, dtype, false, (hipStream_t)stream);
+    return unproject_forward("lt_unproject_fwd", dtype, feats, proj, coords, nullptr, conf, false, nullptr, out, B, NV, C, h, w, v0, v1, v2, agg, stream);
 }
 
 extern "C" int lt_unproject_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
                                        void* out, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2, int32_t agg,
                                        void* stream) {
-    LT_REQUIRE(feats && proj && coords && out, LT_ERR_INVALID, "lt_unproject_masked_fwd: null argument");
-    LT_REQUIRE(view_mask, LT_ERR_INVALID, "lt_unproject_masked_fwd: null view_mask");
-    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "lt_unproject_masked_fwd: bad dtype %d", dtype);
-    LT_REQUIRE(agg >= LT_AGG_SUM && agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "lt_unproject_masked_fwd: unknown aggregation %d", agg);
-    LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "lt_unproject_masked_fwd: LT_AGG_CONF* needs confidences");
-    LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_INVALID, "lt_unproject_masked_fwd: bad shape");
-    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_masked_fwd: feature maps too large");
-    UnprojMaskedArgs a = {};
-    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out; a.mask = view_mask;
-    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = v0; a.v1 = v1; a.v2 = v2; a.agg = agg;
-    return unproject_dispatch(a, dtype, false, (hipStream_t)stream);
+    return unproject_forward("lt_unproject_masked_fwd", dtype, feats, proj, coords, nullptr, conf, true, view_mask, out, B, NV, C, h, w, v0, v1, v2, agg, stream);
 }
 
 extern "C" int lt_unproject_grid_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                                      float step, int32_t cmu_transfer, float* coords_out, const float* conf, void* out, int32_t B, int32_t NV,
                                      int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream) {
-    LT_REQUIRE(feats && proj && pos && center && rot && coords_out && out, LT_ERR_INVALID, "lt_unproject_grid_fwd: null argument");
-    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "lt_unproject_grid_fwd: bad dtype %d", dtype);
-    LT_REQUIRE(agg >= LT_AGG_SUM && agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "lt_unproject_grid_fwd: unknown aggregation %d", agg);
-    LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "lt_unproject_grid_fwd: LT_AGG_CONF* needs confidences");
-    LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && V >= 2, LT_ERR_INVALID, "lt_unproject_grid_fwd: bad shape");
-    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_grid_fwd: feature maps too large");
-    UnprojMaskedArgs a = {};
-    a.feats = feats; a.proj = proj; a.coords = nullptr; a.conf = conf; a.out = out;
-    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = V; a.v1 = V; a.v2 = V; a.agg = agg;
-    a.g_pos = pos; a.g_center = center; a.g_rot = rot; a.g_step = step; a.g_cmu = cmu_transfer; a.coords_out = coords_out;
-    return unproject_dispatch(a, dtype, true, (hipStream_t)stream);
+    const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
+    return unproject_forward("lt_unproject_grid_fwd", dtype, feats, proj, nullptr, &cub, conf, false, nullptr, out, B, NV, C, h, w, V, V, V, agg, stream);
 }
 
 extern "C" int lt_unproject_grid_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                                             float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask, void* out,
                                             int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream) {
-    LT_REQUIRE(feats && proj && pos && center && rot && coords_out && out, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: null argument");
-    LT_REQUIRE(view_mask, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: null view_mask");
-    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: bad dtype %d", dtype);
-    LT_REQUIRE(agg >= LT_AGG_SUM && agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: unknown aggregation %d", agg);
-    LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: LT_AGG_CONF* needs confidences");
-    LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && V >= 2, LT_ERR_INVALID, "lt_unproject_grid_masked_fwd: bad shape");
-    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_grid_masked_fwd: feature maps too large");
-    UnprojMaskedArgs a = {};
-    a.feats = feats; a.proj = proj; a.coords = nullptr; a.conf = conf; a.out = out; a.mask = view_mask;
-    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = V; a.v1 = V; a.v2 = V; a.agg = agg;
-    a.g_pos = pos; a.g_center = center; a.g_rot = rot; a.g_step = step; a.g_cmu = cmu_transfer; a.coords_out = coords_out;
-    return unproject_dispatch(a, dtype, true, (hipStream_t)stream);
+    const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
+    return unproject_forward("lt_unproject_grid_masked_fwd", dtype, feats, proj, nullptr, &cub, conf, true, view_mask, out, B, NV, C, h, w, V, V, V, agg, stream);
 }
 
 namespace {

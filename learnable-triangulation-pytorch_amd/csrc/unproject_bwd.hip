@@ -29,7 +29,7 @@
 // hold no per-view register array (the host entry dispatches on NV > UB_MAXV; nothing changes for NV <= 8).
 #include <stdlib.h>
 
-#include "lt_common.h"
+#include "unproj_geom.h"
 
 using namespace lt;
 
@@ -53,56 +53,17 @@ struct UnprojBwdArgs {
     long long nvox;
 };
 
-struct Tap {                 // one view's projection of one voxel: four tap pixels (x, y; clamped into the map) and weights; weight 0 = padding / masked
-    int x[4], y[4];
-    float k[4];
-    int x0, y0;              // unclamped origin of the 2x2 patch (>= -1; 0 for an inactive voxel, whose weights are all 0)
-};
-
-__device__ __forceinline__ Tap project_taps(const float* __restrict__ P, float X0, float X1, float X2, int h, int w) {
-    // the arithmetic of sample_view<float> in unproject.hip (IEEE divisions: this is the fp32 path)
-    const float px = __fadd_rn(fmaf(X2, P[2], fmaf(X1, P[1], __fmul_rn(X0, P[0]))), P[3]);
-    const float py = __fadd_rn(fmaf(X2, P[6], fmaf(X1, P[5], __fmul_rn(X0, P[4]))), P[7]);
-    float pz = __fadd_rn(fmaf(X2, P[10], fmaf(X1, P[9], __fmul_rn(X0, P[8]))), P[11]);
-    const bool invalid = pz <= 0.0f;
-    if (pz == 0.0f) pz = 1.0f;
-    const float u = __fdiv_rn(px, pz), v = __fdiv_rn(py, pz);
-    const float gx = __fmul_rn(2.0f, __fsub_rn(__fdiv_rn(u, (float)h), 0.5f));
-    const float gy = __fmul_rn(2.0f, __fsub_rn(__fdiv_rn(v, (float)w), 0.5f));
-    const float ix = __fmul_rn(__fadd_rn(gx, 1.0f), 0.5f * (float)(w - 1));
-    const float iy = __fmul_rn(__fadd_rn(gy, 1.0f), 0.5f * (float)(h - 1));
-    const float xw = floorf(ix), yn = floorf(iy);
-    const float we = __fsub_rn(ix, xw), ww = __fsub_rn(1.0f, we);
-    const float ws = __fsub_rn(iy, yn), wn = __fsub_rn(1.0f, ws);
-    const bool xw_ok = xw >= 0.f && xw <= (float)(w - 1), xe_ok = xw >= -1.f && xw <= (float)(w - 2);
-    const bool yn_ok = yn >= 0.f && yn <= (float)(h - 1), ys_ok = yn >= -1.f && yn <= (float)(h - 2);
-    const bool act = !invalid && (xw_ok || xe_ok) && (yn_ok || ys_ok);
-    const int x0 = act ? (int)xw : 0, y0 = act ? (int)yn : 0;
-    const int xwc = min(max(x0, 0), w - 1), xec = min(max(x0 + 1, 0), w - 1);
-    const int ync = min(max(y0, 0), h - 1), ysc = min(max(y0 + 1, 0), h - 1);
-    Tap t;
-    t.x0 = x0; t.y0 = y0;
-    t.x[0] = xwc; t.x[1] = xec; t.x[2] = xwc; t.x[3] = xec;
-    t.y[0] = ync; t.y[1] = ync; t.y[2] = ysc; t.y[3] = ysc;
-    t.k[0] = (act && yn_ok && xw_ok) ? __fmul_rn(wn, ww) : 0.f;
-    t.k[1] = (act && yn_ok && xe_ok) ? __fmul_rn(wn, we) : 0.f;
-    t.k[2] = (act && ys_ok && xw_ok) ? __fmul_rn(ws, ww) : 0.f;
-    t.k[3] = (act && ys_ok && xe_ok) ? __fmul_rn(ws, we) : 0.f;
-    return t;
-}
-
-template <typename T> __device__ __forceinline__ void ld4(const T* p, float (&f)[4]);
-template <> __device__ __forceinline__ void ld4<float>(const float* p, float (&f)[4]) {
-    const float4 v = *(const float4*)p;
-    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-}
-template <> __device__ __forceinline__ void ld4<bf16_t>(const bf16_t* p, float (&f)[4]) {
-    const uint2 v = *(const uint2*)p;
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-}
-
 constexpr int UB_MAXV = 8;   // views kept in registers
+
+// one view's sample of one voxel / channel vector: all four clamped corners, blended with the zeroed weights (the second load discipline of unproj_geom.h)
+template <typename T>
+__device__ __forceinline__ void sample_one_view(const T* fm, const Tap& t, int w, int C, float (&x)[4]) {
+    float t0[4], t1[4], t2[4], t3[4];
+    ChVec<T, 4>::ld(fm + (long long)(t.y[0] * w + t.x[0]) * C, t0); ChVec<T, 4>::ld(fm + (long long)(t.y[1] * w + t.x[1]) * C, t1);
+    ChVec<T, 4>::ld(fm + (long long)(t.y[2] * w + t.x[2]) * C, t2); ChVec<T, 4>::ld(fm + (long long)(t.y[3] * w + t.x[3]) * C, t3);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = t0[e] * t.k[0] + t1[e] * t.k[1] + t2[e] * t.k[2] + t3[e] * t.k[3];
+}
 
 // sampled values x[v][4] of one voxel / channel vector in every view (the forward's bilinear sampling with its padding / depth rules)
 template <typename T, int MV>
@@ -112,13 +73,8 @@ __device__ __forceinline__ void sample_views(const UnprojBwdArgs& a, const T* fe
 #pragma unroll
     for (int v = 0; v < MV; ++v) {
         if (v < a.NV) {
-            tp[v] = project_taps(P + v * 12, X0, X1, X2, a.h, a.w);
-            const T* fm = feats + v * hw * a.C + c0;
-            float t0[4], t1[4], t2[4], t3[4];
-            ld4<T>(fm + (long long)(tp[v].y[0] * a.w + tp[v].x[0]) * a.C, t0); ld4<T>(fm + (long long)(tp[v].y[1] * a.w + tp[v].x[1]) * a.C, t1);
-            ld4<T>(fm + (long long)(tp[v].y[2] * a.w + tp[v].x[2]) * a.C, t2); ld4<T>(fm + (long long)(tp[v].y[3] * a.w + tp[v].x[3]) * a.C, t3);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[v][e] = t0[e] * tp[v].k[0] + t1[e] * tp[v].k[1] + t2[e] * tp[v].k[2] + t3[e] * tp[v].k[3];
+            tp[v] = project_taps<false>(P + v * 12, X0, X1, X2, a.h, a.w);
+            sample_one_view<T>(feats + v * hw * a.C + c0, tp[v], a.w, a.C, x[v]);
         }
     }
 }
@@ -183,7 +139,7 @@ __global__ __launch_bounds__(256) void unproject_bwd_kernel(const UnprojBwdArgs 
         const int c0 = (int)(q - vox * tpv) * 4;
         const float X0 = coords[vox * 3], X1 = coords[vox * 3 + 1], X2 = coords[vox * 3 + 2];
         float g[4];
-        ld4<float>(gout + vox * a.C + c0, g);
+        ChVec<float, 4>::ld(gout + vox * a.C + c0, g);
         Tap tp[UB_MAXV];
         float x[UB_MAXV][4], dx[UB_MAXV][4];
         sample_views<T, UB_MAXV>(a, feats, P, X0, X1, X2, c0, tp, x);
@@ -247,7 +203,7 @@ __global__ __launch_bounds__(256) void unproj_taps_kernel(const UnprojBwdArgs a)
     for (int v = 0; v < a.NV; ++v) {
         int x0 = 1 << 30, x1 = -1, y0 = 1 << 30, y1 = -1;
         if (vox >= 0) {
-            const Tap t = project_taps(P + v * 12, X0, X1, X2, a.h, a.w);
+            const Tap t = project_taps<false>(P + v * 12, X0, X1, X2, a.h, a.w);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (t.k[k] != 0.f) { x0 = min(x0, t.x[k]); x1 = max(x1, t.x[k]); y0 = min(y0, t.y[k]); y1 = max(y1, t.y[k]); }
@@ -284,7 +240,7 @@ __global__ __launch_bounds__(256) void unproj_dx_kernel(const UnprojBwdArgs a) {
         const int c0 = (int)(q - vox * tpv) * 4;
         const float X0 = coords[vox * 3], X1 = coords[vox * 3 + 1], X2 = coords[vox * 3 + 2];
         float g[4];
-        ld4<float>(gout + vox * a.C + c0, g);
+        ChVec<float, 4>::ld(gout + vox * a.C + c0, g);
         float x[MV][4], dx[MV][4];
         {
             Tap tp[MV];
@@ -349,28 +305,6 @@ __global__ void unproj_gconf_finalize_kernel(const UnprojBwdArgs a, int nblk1) {
 // per workgroup into LDS.  The arithmetic is that of sample_views / view_gradients, expression for expression.
 constexpr int UB_MANYV = 32;     // view limit of the many-view kernels: their LDS copies and the finalizer's workgroup shape are sized by it
 
-// one view's sample of one voxel / channel vector: the bilinear sum of sample_views
-template <typename T>
-__device__ __forceinline__ void sample_one_view(const T* fm, const Tap& t, int w, int C, float (&x)[4]) {
-    float t0[4], t1[4], t2[4], t3[4];
-    ld4<T>(fm + (long long)(t.y[0] * w + t.x[0]) * C, t0); ld4<T>(fm + (long long)(t.y[1] * w + t.x[1]) * C, t1);
-    ld4<T>(fm + (long long)(t.y[2] * w + t.x[2]) * C, t2); ld4<T>(fm + (long long)(t.y[3] * w + t.x[3]) * C, t3);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = t0[e] * t.k[0] + t1[e] * t.k[1] + t2[e] * t.k[2] + t3[e] * t.k[3];
-}
-
-// K0's tap record (txy, tw) back as the Tap that project_taps returned for it
-__device__ __forceinline__ Tap tap_of_record(int xy, const float4 k, int h, int w) {
-    Tap t;
-    t.x0 = (xy & 0xffff) - 1; t.y0 = (xy >> 16) - 1;
-    const int xwc = min(max(t.x0, 0), w - 1), xec = min(max(t.x0 + 1, 0), w - 1);
-    const int ync = min(max(t.y0, 0), h - 1), ysc = min(max(t.y0 + 1, 0), h - 1);
-    t.x[0] = xwc; t.x[1] = xec; t.x[2] = xwc; t.x[3] = xec;
-    t.y[0] = ync; t.y[1] = ync; t.y[2] = ysc; t.y[3] = ysc;
-    t.k[0] = k.x; t.k[1] = k.y; t.k[2] = k.z; t.k[3] = k.w;
-    return t;
-}
-
 // softmax / max over any number of views: view_gradients' arithmetic with the samples recomputed per pass.  sample(v, x) gives view v's
 // sampled vector, emit(v, dx, sampled) takes d out / d x_v times the upstream gradient in view order (sampled: sample(v) was the last
 // call of sample).  Pass 1: the max as an fmaxf chain / the first maximal view; pass 2: s and tt in view order; pass 3: dx_v.
@@ -431,7 +365,7 @@ __global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdAr
         const long long vox = q / tpv;
         const int c0 = (int)(q - vox * tpv) * 4;
         float g[4];
-        ld4<float>(gout + vox * a.C + c0, g);
+        ChVec<float, 4>::ld(gout + vox * a.C + c0, g);
         const int* txy = a.txy + (long long)b * a.NV * a.nvox + vox;
         const float4* tw = a.tw + (long long)b * a.NV * a.nvox + vox;
         auto sample = [&](int v, float (&x)[4]) {
@@ -487,7 +421,7 @@ __global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdAr
         const long long vox = q / tpv;
         const int c0 = (int)(q - vox * tpv) * 4;
         float g[4];
-        ld4<float>(gout + vox * a.C + c0, g);
+        ChVec<float, 4>::ld(gout + vox * a.C + c0, g);
         const int* txy = a.txy + ((long long)b * a.NV + vg) * a.nvox + vox;
         const float4* tw = a.tw + ((long long)b * a.NV + vg) * a.nvox + vox;
 #pragma unroll
@@ -576,7 +510,7 @@ __global__ __launch_bounds__(256) void unproject_bwd_many_kernel(const UnprojBwd
         const int c0 = (int)(q - vox * tpv) * 4;
         const float X0 = coords[vox * 3], X1 = coords[vox * 3 + 1], X2 = coords[vox * 3 + 2];
         float g[4];
-        ld4<float>(gout + vox * a.C + c0, g);
+        ChVec<float, 4>::ld(gout + vox * a.C + c0, g);
         Tap cur;
         auto scatter = [&](int v, const float (&dx)[4]) {
             float* gm = gfeats + v * hw * a.C + c0;
@@ -592,20 +526,20 @@ __global__ __launch_bounds__(256) void unproject_bwd_many_kernel(const UnprojBwd
         };
         if (a.agg == LT_AGG_SOFTMAX || a.agg == LT_AGG_MAX) {
             auto sample = [&](int v, float (&x)[4]) {
-                cur = project_taps(Ps + v * 12, X0, X1, X2, a.h, a.w);
+                cur = project_taps<false>(Ps + v * 12, X0, X1, X2, a.h, a.w);
                 sample_one_view<T>(feats + v * hw * a.C + c0, cur, a.w, a.C, x);
             };
             auto emit = [&](int v, const float (&dx)[4], bool sampled) {
                 if (!sampled) {
                     if (dx[0] == 0.f && dx[1] == 0.f && dx[2] == 0.f && dx[3] == 0.f) return;      // max: a view that wins no channel
-                    cur = project_taps(Ps + v * 12, X0, X1, X2, a.h, a.w);
+                    cur = project_taps<false>(Ps + v * 12, X0, X1, X2, a.h, a.w);
                 }
                 scatter(v, dx);
             };
             cross_view_gradients(a.agg, a.NV, g, sample, emit);
         } else {
             for (int v = 0; v < a.NV; ++v) {
-                cur = project_taps(Ps + v * 12, X0, X1, X2, a.h, a.w);
+                cur = project_taps<false>(Ps + v * 12, X0, X1, X2, a.h, a.w);
                 float dx[4] = {g[0], g[1], g[2], g[3]};
                 if (a.agg == LT_AGG_CONF) {
                     const float* cf = a.conf + ((long long)b * a.NV + v) * a.C + c0;
