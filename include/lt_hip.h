@@ -423,6 +423,18 @@ size_t lt_unproject_bwd_workspace(int32_t B, int32_t NV, int32_t C, int32_t v0, 
 int lt_unproject_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const float* grad_out,
                      float* grad_feats, float* grad_conf, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1,
                      int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes, void* stream);
+/* lt_unproject_bwd over the VALID views of every sample, the backward of lt_unproject_masked_fwd: view_mask is DEVICE (B, NV) uint8, non-zero =
+ * valid (NULL is LT_ERR_INVALID).  Sample b gets what autograd derives for the unprojection of its views {v : view_mask[b][v]} alone:
+ * grad_feats[b, v] and grad_conf[b, v, :] of a masked view are +0.0 everywhere (the buffers are still written completely, no pre-zeroing); a
+ * masked view's feature map, projection matrix and confidence are never read (NaN there cannot leak); max: the first maximal VALID view;
+ * conf_norm: the normaliser, and the derivative through it, over the valid views.  A sample without a valid view gets zeros.  The valid
+ * views are walked in index order: for NV <= 8 the arithmetic is the unmasked kernel's on the compacted views, operation for operation, and
+ * with an all-ones mask every NV gives lt_unproject_bwd's bits.  Same workspace (lt_unproject_bwd_workspace), argument checks, 1 <= NV <= 32
+ * and chunked walk of the batch as lt_unproject_bwd.  Gather path only: C > 64 or not a power of two, and LT_UNPROJ_BWD_ATOMICS=1, are
+ * LT_ERR_UNSUPPORTED (there is no masked scatter). */
+int lt_unproject_masked_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                            const float* grad_out, float* grad_feats, float* grad_conf, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w,
+                            int32_t v0, int32_t v1, int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes, void* stream);
 int lt_softargmax3d_bwd(const float* probs, const float* coords, const float* kp, const float* grad_kp, const int32_t* gp_idx,
                         const float* gp_val, float multiplier, int32_t softmax, int32_t channels_last, float* grad_logits, int32_t B,
                         int32_t J, int64_t nvox, void* stream);

@@ -27,7 +27,11 @@
 // reference and for configurations the gather does not take (C > 64 or not a power of two).
 // More than 8 views (up to UB_MANYV = 32): K0 and K2 as they are; K1, the confidence finalizer and the scatter have many-view forms below that
 // hold no per-view register array (the host entry dispatches on NV > UB_MAXV; nothing changes for NV <= 8).
+// lt_unproject_masked_bwd (training with per-sample view masks): MASKED instantiations of K0, of every K1 form and of both finalizers -- a masked view gets
+// empty bounding boxes from K0 and is skipped by K1, so the unchanged K2 stores zeros for it; the valid views are walked in index order.  Gather path only.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "unproj_geom.h"
 
@@ -53,7 +57,28 @@ struct UnprojBwdArgs {
     long long nvox;
 };
 
+// lt_unproject_masked_bwd's K0, K1 and finalizers get the mask behind the same arguments; the unmasked kernels (and K2, which needs no mask: a
+// masked view has only empty bounding boxes) keep UnprojBwdArgs as their whole argument block
+struct UnprojBwdMaskedArgs : UnprojBwdArgs {
+    const uint8_t* mask;     // (B, NV), non-zero = the view is valid
+};
+template <bool MASKED> using UnprojBwdArgsOf = std::conditional_t<MASKED, UnprojBwdMaskedArgs, UnprojBwdArgs>;
+
 constexpr int UB_MAXV = 8;   // views kept in registers
+
+// Sample b's mask row as bits (NV <= 32).  b comes from the block index in K0 and K1: the row is read with scalar loads into one scalar
+// register, and every test of a view below is a scalar branch.
+__device__ __forceinline__ unsigned mask_bits(const uint8_t* __restrict__ mask, int b, int NV) {
+    const uint8_t* mk = mask + (long long)b * NV;
+    unsigned bits = 0;
+    for (int v = 0; v < NV; ++v) bits |= (mk[v] ? 1u : 0u) << v;
+    return bits;
+}
+// does view v take part?  Without a mask: constant true, so the unmasked instantiations compile to what they did before the mask existed
+template <bool MASKED> __device__ __forceinline__ bool view_on(unsigned mbits, int v) {
+    if constexpr (MASKED) return ((mbits >> v) & 1u) != 0;
+    else return true;
+}
 
 // one view's sample of one voxel / channel vector: all four clamped corners, blended with the zeroed weights (the second load discipline of unproj_geom.h)
 template <typename T>
@@ -66,58 +91,74 @@ __device__ __forceinline__ void sample_one_view(const T* fm, const Tap& t, int w
 }
 
 // sampled values x[v][4] of one voxel / channel vector in every view (the forward's bilinear sampling with its padding / depth rules)
-template <typename T, int MV>
+// MASKED: a masked view is neither projected nor sampled (its matrix and its map are never read); its tp[v] and x[v] stay unset
+template <typename T, int MV, bool MASKED = false>
 __device__ __forceinline__ void sample_views(const UnprojBwdArgs& a, const T* feats, const float* P, float X0, float X1, float X2, int c0,
-                                             Tap (&tp)[MV], float (&x)[MV][4]) {
+                                             Tap (&tp)[MV], float (&x)[MV][4], unsigned mbits = ~0u) {
     const long long hw = (long long)a.h * a.w;
 #pragma unroll
     for (int v = 0; v < MV; ++v) {
-        if (v < a.NV) {
+        if (v < a.NV && view_on<MASKED>(mbits, v)) {
             tp[v] = project_taps<false>(P + v * 12, X0, X1, X2, a.h, a.w);
             sample_one_view<T>(feats + v * hw * a.C + c0, tp[v], a.w, a.C, x[v]);
         }
     }
 }
 
-// d out / d x_v times the upstream gradient, per channel of the vector; gc[v][e] = g * x_v (the confidence gradient's summand)
-template <int MV>
+// d out / d x_v times the upstream gradient, per channel of the vector; gc[v][e] = g * x_v (the confidence gradient's summand).
+// MASKED: the valid views alone, in index order -- the first valid view starts the max as view 0 does without a mask, so on the valid views
+// this is the unmasked arithmetic on the compacted views, operation for operation; dx[v] of a masked view stays unset (nothing reads it)
+template <int MV, bool MASKED = false>
 __device__ __forceinline__ void view_gradients(const UnprojBwdArgs& a, int b, int c0, const float (&g)[4], const float (&x)[MV][4],
-                                               float (&dx)[MV][4]) {
+                                               float (&dx)[MV][4], unsigned mbits = ~0u) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         if (a.agg == LT_AGG_SOFTMAX) {
             float m = x[0][e];
+            if constexpr (MASKED) {
+                bool have = false;
 #pragma unroll
-            for (int v = 1; v < MV; ++v) if (v < a.NV) m = fmaxf(m, x[v][e]);
+                for (int v = 0; v < MV; ++v) if (v < a.NV && view_on<MASKED>(mbits, v)) { m = have ? fmaxf(m, x[v][e]) : x[v][e]; have = true; }
+            } else {
+#pragma unroll
+                for (int v = 1; v < MV; ++v) if (v < a.NV) m = fmaxf(m, x[v][e]);
+            }
             float s = 0.f, tt = 0.f, ex[MV];
 #pragma unroll
-            for (int v = 0; v < MV; ++v) if (v < a.NV) { ex[v] = expf(x[v][e] - m); s += ex[v]; tt += x[v][e] * ex[v]; }
+            for (int v = 0; v < MV; ++v) if (v < a.NV && view_on<MASKED>(mbits, v)) { ex[v] = expf(x[v][e] - m); s += ex[v]; tt += x[v][e] * ex[v]; }
             const float out = __fdiv_rn(tt, s);
 #pragma unroll
-            for (int v = 0; v < MV; ++v) if (v < a.NV) dx[v][e] = g[e] * __fdiv_rn(ex[v], s) * (1.0f + x[v][e] - out);
-        } else if (a.agg == LT_AGG_MAX) {               // torch.max(dim): gradient to the FIRST maximal view
+            for (int v = 0; v < MV; ++v) if (v < a.NV && view_on<MASKED>(mbits, v)) dx[v][e] = g[e] * __fdiv_rn(ex[v], s) * (1.0f + x[v][e] - out);
+        } else if (a.agg == LT_AGG_MAX) {               // torch.max(dim): gradient to the FIRST maximal (valid) view
             int am = 0;
             float best = x[0][e];
+            if constexpr (MASKED) {
+                bool have = false;
 #pragma unroll
-            for (int v = 1; v < MV; ++v) if (v < a.NV && x[v][e] > best) { best = x[v][e]; am = v; }
+                for (int v = 0; v < MV; ++v)
+                    if (v < a.NV && view_on<MASKED>(mbits, v) && (!have || x[v][e] > best)) { best = x[v][e]; am = v; have = true; }
+            } else {
 #pragma unroll
-            for (int v = 0; v < MV; ++v) if (v < a.NV) dx[v][e] = v == am ? g[e] : 0.f;
+                for (int v = 1; v < MV; ++v) if (v < a.NV && x[v][e] > best) { best = x[v][e]; am = v; }
+            }
+#pragma unroll
+            for (int v = 0; v < MV; ++v) if (v < a.NV && view_on<MASKED>(mbits, v)) dx[v][e] = v == am ? g[e] : 0.f;
         } else if (a.agg == LT_AGG_CONF || a.agg == LT_AGG_CONF_NORM) {
             float cs = 1.f;
-            if (a.agg == LT_AGG_CONF_NORM) {            // the forward normalises the confidences over the views (triangulation.py:268-269)
+            if (a.agg == LT_AGG_CONF_NORM) {            // the forward normalises the confidences over the (valid) views (triangulation.py:268-269)
                 cs = 0.f;
 #pragma unroll
-                for (int v = 0; v < MV; ++v) if (v < a.NV) cs += a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
+                for (int v = 0; v < MV; ++v) if (v < a.NV && view_on<MASKED>(mbits, v)) cs += a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
             }
 #pragma unroll
             for (int v = 0; v < MV; ++v)
-                if (v < a.NV) {
+                if (v < a.NV && view_on<MASKED>(mbits, v)) {
                     const float cv = a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
                     dx[v][e] = g[e] * (a.agg == LT_AGG_CONF_NORM ? __fdiv_rn(cv, cs) : cv);
                 }
         } else {
 #pragma unroll
-            for (int v = 0; v < MV; ++v) if (v < a.NV) dx[v][e] = g[e];
+            for (int v = 0; v < MV; ++v) if (v < a.NV && view_on<MASKED>(mbits, v)) dx[v][e] = g[e];
         }
     }
 }
@@ -189,8 +230,11 @@ __device__ __forceinline__ int wave_max(int v) {
     return v;
 }
 
-// K0: grid (ceil(nbricks / 4), B), 4 waves, one brick per wave
-__global__ __launch_bounds__(256) void unproj_taps_kernel(const UnprojBwdArgs a) {
+// K0: grid (ceil(nbricks / 4), B), 4 waves, one brick per wave.  MASKED: a masked view gets the empty bounding box for every brick and nothing
+// else -- it is not projected, its matrix is not read, its tap records stay unwritten: K2 then finds no brick for any tile of that view and
+// stores zeros without reading its tap records or its dxs, and K1 never looks at a masked view.
+template <bool MASKED = false>
+__global__ __launch_bounds__(256) void unproj_taps_kernel(const UnprojBwdArgsOf<MASKED> a) {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int nbricks = a.nb0 * a.nb1 * a.nb2;
     const int brick = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -200,8 +244,16 @@ __global__ __launch_bounds__(256) void unproj_taps_kernel(const UnprojBwdArgs a)
     const long long vox = brick_voxel(a, brick, lane);
     float X0 = 0.f, X1 = 0.f, X2 = 0.f;
     if (vox >= 0) { X0 = coords[vox * 3]; X1 = coords[vox * 3 + 1]; X2 = coords[vox * 3 + 2]; }
+    unsigned mbits = ~0u;
+    if constexpr (MASKED) mbits = mask_bits(a.mask, b, a.NV);
     for (int v = 0; v < a.NV; ++v) {
         int x0 = 1 << 30, x1 = -1, y0 = 1 << 30, y1 = -1;
+        if constexpr (MASKED) {
+            if (!view_on<MASKED>(mbits, v)) {
+                if (lane == 0) *(int4*)(a.bbox + (((long long)b * a.NV + v) * nbricks + brick) * 4) = make_int4(x0, x1, y0, y1);
+                continue;
+            }
+        }
         if (vox >= 0) {
             const Tap t = project_taps<false>(P + v * 12, X0, X1, X2, a.h, a.w);
 #pragma unroll
@@ -218,12 +270,17 @@ __global__ __launch_bounds__(256) void unproj_taps_kernel(const UnprojBwdArgs a)
 
 // K1: grid (nblk1, B): one lane per (voxel, 4-channel vector), grid-stride (stride a multiple of C/4: a lane keeps its channel vector).
 // MV = view capacity of the register arrays (4 or 8): at 4 views the kernel fits 128 VGPRs and two waves share a SIMD
-template <typename T, int MV>
-__global__ __launch_bounds__(256) void unproj_dx_kernel(const UnprojBwdArgs a) {
+// MASKED: masked views are skipped in the sampling, in every cross-view reduction and in the stores (K2 never reads their dxs); their
+// confidence partials are written as the zeros their accumulators still hold.  A sample without a valid view walks no voxel.
+// gfx950 resource usage, fp32 / bf16 maps: see DESIGN.md ("Masked unprojection backward")
+template <typename T, int MV, bool MASKED = false>
+__global__ __launch_bounds__(256) void unproj_dx_kernel(const UnprojBwdArgsOf<MASKED> a) {
     __shared__ float red[256][4];
     const int tpv = a.C >> 2;
-    const long long items = a.nvox * tpv;
     const int b = blockIdx.y;
+    unsigned mbits = ~0u;
+    if constexpr (MASKED) mbits = mask_bits(a.mask, b, a.NV);
+    const long long items = (MASKED && mbits == 0) ? 0 : a.nvox * tpv;
     const T* feats = (const T*)a.feats + (long long)b * a.NV * a.h * a.w * a.C;
     const float* P = a.proj + (long long)b * a.NV * 12;
     const float* coords = a.coords + (long long)b * a.nvox * 3;
@@ -244,12 +301,12 @@ __global__ __launch_bounds__(256) void unproj_dx_kernel(const UnprojBwdArgs a) {
         float x[MV][4], dx[MV][4];
         {
             Tap tp[MV];
-            sample_views<T, MV>(a, feats, P, X0, X1, X2, c0, tp, x);
+            sample_views<T, MV, MASKED>(a, feats, P, X0, X1, X2, c0, tp, x, mbits);
         }
-        view_gradients<MV>(a, b, c0, g, x, dx);
+        view_gradients<MV, MASKED>(a, b, c0, g, x, dx, mbits);
 #pragma unroll
         for (int v = 0; v < MV; ++v)
-            if (v < a.NV) {
+            if (v < a.NV && view_on<MASKED>(mbits, v)) {
                 *(float4*)(dxs + ((long long)v * a.nvox + vox) * a.C + c0) = make_float4(dx[v][0], dx[v][1], dx[v][2], dx[v][3]);
                 if (want_gc)
 #pragma unroll
@@ -277,21 +334,26 @@ __global__ __launch_bounds__(256) void unproj_dx_kernel(const UnprojBwdArgs a) {
 }
 
 // one thread per (b, c): the partials of every workgroup in index order; conf_norm: chain rule through c_v / sum_u c_u
-__global__ void unproj_gconf_finalize_kernel(const UnprojBwdArgs a, int nblk1) {
+// MASKED: the normaliser and the dot product run over the valid views (a masked view's confidence is never read); a masked view gets +0.0
+template <bool MASKED = false>
+__global__ void unproj_gconf_finalize_kernel(const UnprojBwdArgsOf<MASKED> a, int nblk1) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.B * a.C) return;
     const int b = i / a.C, c = i - b * a.C;
+    unsigned mbits = ~0u;
+    if constexpr (MASKED) mbits = mask_bits(a.mask, b, a.NV);
     double s[UB_MAXV];
     for (int v = 0; v < a.NV; ++v) {
         double t = 0.0;
-        for (int k = 0; k < nblk1; ++k) t += a.gcpart[(((long long)b * nblk1 + k) * a.NV + v) * a.C + c];
+        if (view_on<MASKED>(mbits, v))
+            for (int k = 0; k < nblk1; ++k) t += a.gcpart[(((long long)b * nblk1 + k) * a.NV + v) * a.C + c];
         s[v] = t;
     }
     if (a.agg == LT_AGG_CONF_NORM) {      // s[v] is the gradient of the NORMALISED confidence n_v = c_v / S: d/dc_v = (s_v - sum_u s_u n_u) / S
         double S = 0.0, dot = 0.0;
-        for (int v = 0; v < a.NV; ++v) S += (double)a.conf[((long long)b * a.NV + v) * a.C + c];
-        for (int v = 0; v < a.NV; ++v) dot += s[v] * (double)a.conf[((long long)b * a.NV + v) * a.C + c] / S;
-        for (int v = 0; v < a.NV; ++v) s[v] = (s[v] - dot) / S;
+        for (int v = 0; v < a.NV; ++v) if (view_on<MASKED>(mbits, v)) S += (double)a.conf[((long long)b * a.NV + v) * a.C + c];
+        for (int v = 0; v < a.NV; ++v) if (view_on<MASKED>(mbits, v)) dot += s[v] * (double)a.conf[((long long)b * a.NV + v) * a.C + c] / S;
+        for (int v = 0; v < a.NV; ++v) s[v] = view_on<MASKED>(mbits, v) ? (s[v] - dot) / S : 0.0;
     }
     for (int v = 0; v < a.NV; ++v) a.gconf[((long long)b * a.NV + v) * a.C + c] = (float)s[v];
 }
@@ -308,40 +370,48 @@ constexpr int UB_MANYV = 32;     // view limit of the many-view kernels: their L
 // softmax / max over any number of views: view_gradients' arithmetic with the samples recomputed per pass.  sample(v, x) gives view v's
 // sampled vector, emit(v, dx, sampled) takes d out / d x_v times the upstream gradient in view order (sampled: sample(v) was the last
 // call of sample).  Pass 1: the max as an fmaxf chain / the first maximal view; pass 2: s and tt in view order; pass 3: dx_v.
-template <class Sample, class Emit>
-__device__ __forceinline__ void cross_view_gradients(int agg, int NV, const float (&g)[4], Sample sample, Emit emit) {
+// MASKED: the valid views (bits of mbits, at least one set) alone, in index order: the first valid view takes view 0's part, masked views
+// are neither sampled nor emitted.
+template <bool MASKED = false, class Sample, class Emit>
+__device__ __forceinline__ void cross_view_gradients(int agg, int NV, const float (&g)[4], Sample sample, Emit emit, unsigned mbits = ~0u) {
     float x[4], dx[4];
+    const int vf = MASKED ? __ffs((int)mbits) - 1 : 0;  // the view that starts the max
     if (agg == LT_AGG_SOFTMAX) {
         float m[4], s[4] = {0.f, 0.f, 0.f, 0.f}, tt[4] = {0.f, 0.f, 0.f, 0.f}, out[4];
-        sample(0, m);
-        for (int v = 1; v < NV; ++v) {
+        sample(vf, m);
+        for (int v = vf + 1; v < NV; ++v) {
+            if (!view_on<MASKED>(mbits, v)) continue;
             sample(v, x);
 #pragma unroll
             for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], x[e]);
         }
-        for (int v = 0; v < NV; ++v) {
+        for (int v = vf; v < NV; ++v) {
+            if (!view_on<MASKED>(mbits, v)) continue;
             sample(v, x);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float ex = expf(x[e] - m[e]); s[e] += ex; tt[e] += x[e] * ex; }
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) out[e] = __fdiv_rn(tt[e], s[e]);
-        for (int v = 0; v < NV; ++v) {
+        for (int v = vf; v < NV; ++v) {
+            if (!view_on<MASKED>(mbits, v)) continue;
             sample(v, x);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float ex = expf(x[e] - m[e]); dx[e] = g[e] * __fdiv_rn(ex, s[e]) * (1.0f + x[e] - out[e]); }
             emit(v, dx, true);
         }
-    } else {                                            // LT_AGG_MAX: torch.max(dim), gradient to the FIRST maximal view
+    } else {                                            // LT_AGG_MAX: torch.max(dim), gradient to the FIRST maximal (valid) view
         float best[4];
-        int am[4] = {0, 0, 0, 0};
-        sample(0, best);
-        for (int v = 1; v < NV; ++v) {
+        int am[4] = {vf, vf, vf, vf};
+        sample(vf, best);
+        for (int v = vf + 1; v < NV; ++v) {
+            if (!view_on<MASKED>(mbits, v)) continue;
             sample(v, x);
 #pragma unroll
             for (int e = 0; e < 4; ++e) if (x[e] > best[e]) { best[e] = x[e]; am[e] = v; }
         }
-        for (int v = 0; v < NV; ++v) {
+        for (int v = vf; v < NV; ++v) {
+            if (!view_on<MASKED>(mbits, v)) continue;
 #pragma unroll
             for (int e = 0; e < 4; ++e) dx[e] = v == am[e] ? g[e] : 0.f;
             emit(v, dx, false);
@@ -352,11 +422,17 @@ __device__ __forceinline__ void cross_view_gradients(int agg, int NV, const floa
 // K1 for NV > UB_MAXV, softmax / max: grid (nblk1, B), one lane per (voxel, 4-channel vector) as in unproj_dx_kernel; per view and pass one
 // tap record (20 bytes, the same for the C / 4 lanes of a voxel) and four 16-byte taps.
 // gfx950 resource usage: fp32 maps 64 VGPRs and 8 waves per SIMD, bf16 maps 68 VGPRs and 7 waves; no LDS, no scratch
-template <typename T>
-__global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdArgs a) {
+// MASKED: every pass walks the valid views only (a masked view has no tap records: K0 wrote none); a sample without a valid view does nothing
+template <typename T, bool MASKED = false>
+__global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdArgsOf<MASKED> a) {
     const int tpv = a.C >> 2;
     const long long items = a.nvox * tpv;
     const int b = blockIdx.y;
+    unsigned mbits = ~0u;
+    if constexpr (MASKED) {
+        mbits = mask_bits(a.mask, b, a.NV);
+        if (mbits == 0) return;
+    }
     const long long hw = (long long)a.h * a.w;
     const T* feats = (const T*)a.feats + (long long)b * a.NV * hw * a.C;
     const float* gout = a.gout + (long long)b * a.nvox * a.C;
@@ -375,7 +451,7 @@ __global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdAr
         auto emit = [&](int v, const float (&dx)[4], bool) {
             *(float4*)(dxs + ((long long)v * a.nvox + vox) * a.C + c0) = make_float4(dx[0], dx[1], dx[2], dx[3]);
         };
-        cross_view_gradients(a.agg, a.NV, g, sample, emit);
+        cross_view_gradients<MASKED>(a.agg, a.NV, g, sample, emit, mbits);
     }
 }
 
@@ -384,14 +460,21 @@ __global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdAr
 // the 8-view kernel gives for it).  d out / d x_v per channel (c_v, or c_v / sum over ALL views for conf_norm) is computed once per
 // workgroup into LDS; the maps are sampled only where a confidence gradient is asked for.
 // gfx950 resource usage: fp32 maps 79 VGPRs and 6 waves per SIMD, bf16 maps 81 VGPRs and 5 waves; 6 KB LDS, no scratch
-template <typename T>
-__global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdArgs a) {
+// MASKED: conf_norm's sum runs over the valid views; a masked view of the group is neither stored nor sampled (K0 wrote no tap records for
+// it, K2 never reads its dxs) and its confidence partials are the zeros of its accumulators; a group without a valid view walks no voxel.
+template <typename T, bool MASKED = false>
+__global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdArgsOf<MASKED> a) {
     __shared__ float red[256][4];
     __shared__ float coef[UB_MAXV][64];
     const int tpv = a.C >> 2;
-    const long long items = a.nvox * tpv;
     const int b = blockIdx.y;
     const int vg = blockIdx.z * UB_MAXV, nv = min(UB_MAXV, a.NV - vg);
+    unsigned mbits = ~0u, gbits = ~0u;                    // the sample's mask, and the group's share of it (bit v = view vg + v)
+    if constexpr (MASKED) {
+        mbits = mask_bits(a.mask, b, a.NV);
+        gbits = mbits >> vg;
+    }
+    const long long items = (MASKED && (gbits & 0xffu) == 0) ? 0 : a.nvox * tpv;
     const long long hw = (long long)a.h * a.w;
     const T* feats = (const T*)a.feats + ((long long)b * a.NV + vg) * hw * a.C;
     const float* gout = a.gout + (long long)b * a.nvox * a.C;
@@ -402,10 +485,11 @@ __global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdAr
         for (int i = threadIdx.x; i < nv * a.C; i += 256) {
             const int v = i / a.C, c = i - v * a.C;
             const float* cf = a.conf + (long long)b * a.NV * a.C + c;
+            if (!view_on<MASKED>(gbits, v)) continue;
             float cv = cf[(vg + v) * a.C];
             if (a.agg == LT_AGG_CONF_NORM) {
                 float cs = 0.f;
-                for (int u = 0; u < a.NV; ++u) cs += cf[u * a.C];
+                for (int u = 0; u < a.NV; ++u) if (view_on<MASKED>(mbits, u)) cs += cf[u * a.C];
                 cv = __fdiv_rn(cv, cs);
             }
             coef[v][c] = cv;
@@ -426,7 +510,7 @@ __global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdAr
         const float4* tw = a.tw + ((long long)b * a.NV + vg) * a.nvox + vox;
 #pragma unroll
         for (int v = 0; v < UB_MAXV; ++v)
-            if (v < nv) {
+            if (v < nv && view_on<MASKED>(gbits, v)) {
                 float4 d = make_float4(g[0], g[1], g[2], g[3]);
                 if (is_conf) {
                     const float4 k = *(const float4*)&coef[v][c0];
@@ -466,15 +550,20 @@ __global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdAr
 // finalizer does (each thread for itself: the same S and dot in every thread of a channel).
 // gfx950 resource usage: 54 VGPRs, 2 KB LDS, no scratch; 8 waves per SIMD
 constexpr int UB_FIN_C = 8;
-__global__ __launch_bounds__(UB_MANYV * UB_FIN_C) void unproj_gconf_finalize_many_kernel(const UnprojBwdArgs a, int nblk1) {
+// MASKED: S and dot over the valid views; the thread of a masked view writes +0.0
+template <bool MASKED = false>
+__global__ __launch_bounds__(UB_MANYV * UB_FIN_C) void unproj_gconf_finalize_many_kernel(const UnprojBwdArgsOf<MASKED> a, int nblk1) {
     __shared__ double sv[UB_MANYV][UB_FIN_C];
     const int cc = a.C < UB_FIN_C ? a.C : UB_FIN_C;                       // channels per workgroup (C = 4: half of the threads idle)
     const int chunks = a.C / cc;
     const int b = blockIdx.x / chunks, ci = threadIdx.x % UB_FIN_C, v = threadIdx.x / UB_FIN_C;
     const int c = (blockIdx.x - b * chunks) * cc + ci;
     const bool mine = ci < cc && v < a.NV;
+    unsigned mbits = ~0u;
+    if constexpr (MASKED) mbits = mask_bits(a.mask, b, a.NV);
+    const bool on = view_on<MASKED>(mbits, v);
     double t = 0.0;
-    if (mine)
+    if (mine && on)
         for (int k = 0; k < nblk1; ++k) t += a.gcpart[(((long long)b * nblk1 + k) * a.NV + v) * a.C + c];
     sv[v][ci] = t;
     __syncthreads();
@@ -482,9 +571,9 @@ __global__ __launch_bounds__(UB_MANYV * UB_FIN_C) void unproj_gconf_finalize_man
     if (a.agg == LT_AGG_CONF_NORM) {
         const float* cf = a.conf + (long long)b * a.NV * a.C + c;
         double S = 0.0, dot = 0.0;
-        for (int u = 0; u < a.NV; ++u) S += (double)cf[u * a.C];
-        for (int u = 0; u < a.NV; ++u) dot += sv[u][ci] * (double)cf[u * a.C] / S;
-        t = (t - dot) / S;
+        for (int u = 0; u < a.NV; ++u) if (view_on<MASKED>(mbits, u)) S += (double)cf[u * a.C];
+        for (int u = 0; u < a.NV; ++u) if (view_on<MASKED>(mbits, u)) dot += sv[u][ci] * (double)cf[u * a.C] / S;
+        t = on ? (t - dot) / S : 0.0;
     }
     a.gconf[((long long)b * a.NV + v) * a.C + c] = (float)t;
 }
@@ -773,6 +862,127 @@ bool gather_takes(int C) { return C >= 4 && C <= 64 && (C & (C - 1)) == 0 && !en
 
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
+// K0, K1 and the confidence finalizers of one chunk of the batch.  An unmasked kernel receives a plain UnprojBwdArgs by value (the base of m)
+// and a masked one all of m: the unmasked kernels keep their argument block, and with it their code.
+template <bool MASKED>
+int launch_taps_dx(const char* who, const UnprojBwdMaskedArgs& m, int dtype, int nbricks, int nblk1, hipStream_t st) {
+    const UnprojBwdArgsOf<MASKED>& c = m;
+    const int nb = c.B, NV = c.NV, C = c.C, agg = c.agg;
+    hipLaunchKernelGGL(unproj_taps_kernel<MASKED>, dim3((unsigned)cdiv(nbricks, 4), (unsigned)nb), dim3(256), 0, st, c);
+    LT_CHECK_LAUNCH(who);
+    const dim3 g1((unsigned)nblk1, (unsigned)nb);
+    if (NV > UB_MAXV) {                                       // views in passes (softmax, max) or in groups of UB_MAXV (grid z)
+        const dim3 gz((unsigned)nblk1, (unsigned)nb, (unsigned)cdiv(NV, UB_MAXV));
+        if (agg == LT_AGG_SOFTMAX || agg == LT_AGG_MAX) {
+            if (dtype == LT_F32) hipLaunchKernelGGL((unproj_dx_passes_kernel<float, MASKED>), g1, dim3(256), 0, st, c);
+            else hipLaunchKernelGGL((unproj_dx_passes_kernel<bf16_t, MASKED>), g1, dim3(256), 0, st, c);
+        } else if (dtype == LT_F32) hipLaunchKernelGGL((unproj_dx_groups_kernel<float, MASKED>), gz, dim3(256), 0, st, c);
+        else hipLaunchKernelGGL((unproj_dx_groups_kernel<bf16_t, MASKED>), gz, dim3(256), 0, st, c);
+    } else if (dtype == LT_F32) {
+        if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<float, 4, MASKED>), g1, dim3(256), 0, st, c);
+        else hipLaunchKernelGGL((unproj_dx_kernel<float, UB_MAXV, MASKED>), g1, dim3(256), 0, st, c);
+    } else {
+        if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, 4, MASKED>), g1, dim3(256), 0, st, c);
+        else hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, UB_MAXV, MASKED>), g1, dim3(256), 0, st, c);
+    }
+    LT_CHECK_LAUNCH(who);
+    if (c.gconf && NV > UB_MAXV) {
+        hipLaunchKernelGGL(unproj_gconf_finalize_many_kernel<MASKED>, dim3((unsigned)(nb * (C / (C < UB_FIN_C ? C : UB_FIN_C)))), dim3(UB_MANYV * UB_FIN_C), 0, st, c, nblk1);
+        LT_CHECK_LAUNCH(who);
+    } else if (c.gconf) {
+        hipLaunchKernelGGL(unproj_gconf_finalize_kernel<MASKED>, dim3((unsigned)cdiv((long long)nb * C, 64)), dim3(64), 0, st, c, nblk1);
+        LT_CHECK_LAUNCH(who);
+    }
+    return LT_OK;
+}
+
+// The one body behind lt_unproject_bwd and lt_unproject_masked_bwd: `who` is the entry that was called, `masked` says which
+int unproject_backward(const char* who, bool masked, int dtype, const void* feats, const float* proj, const float* coords, const float* conf,
+                       const uint8_t* view_mask, const float* grad_out, float* grad_feats, float* grad_conf, int B, int NV, int C, int h, int w, int v0,
+                       int v1, int v2, int agg, void* workspace, size_t workspace_bytes, void* stream) {
+    LT_REQUIRE(feats && proj && coords && grad_out && grad_feats, LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(!masked || view_mask, LT_ERR_INVALID, "%s: null view_mask", who);
+    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    LT_REQUIRE(agg == LT_AGG_SUM || agg == LT_AGG_MAX || agg == LT_AGG_SOFTMAX || agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM, LT_ERR_UNSUPPORTED,
+               "%s: unknown aggregation %d", who, agg);
+    const bool is_conf = agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM;
+    LT_REQUIRE(!is_conf || conf, LT_ERR_INVALID, "%s: the conf aggregations need confidences", who);
+    LT_REQUIRE(B >= 1 && NV >= 1 && NV <= UB_MANYV && C >= 4 && C % 4 == 0 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_UNSUPPORTED,
+               "%s: needs 1 <= NV <= %d and C %% 4 == 0 (got NV=%d C=%d)", who, UB_MANYV, NV, C);
+    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
+    if (masked) {                                              // there is no masked scatter
+        LT_REQUIRE(!env_on("LT_UNPROJ_BWD_ATOMICS"), LT_ERR_UNSUPPORTED,
+                   "%s: LT_UNPROJ_BWD_ATOMICS selects the scatter path, which has no masked form (only the gather takes a view mask)", who);
+        LT_REQUIRE(gather_takes(C), LT_ERR_UNSUPPORTED,
+                   "%s: only the gather path takes a view mask, and it needs C a power of two <= 64 (got C=%d; the scatter has no masked form)", who, C);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    UnprojBwdMaskedArgs a;
+    a.mask = masked ? view_mask : nullptr;
+    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.gout = grad_out; a.gfeats = grad_feats; a.gconf = is_conf ? grad_conf : nullptr;
+    a.dxs = nullptr; a.bbox = nullptr; a.gcpart = nullptr; a.txy = nullptr; a.tw = nullptr;
+    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.agg = agg;
+    a.v0 = v0; a.v1 = v1; a.v2 = v2; a.nb0 = (int)cdiv(v0, 4); a.nb1 = (int)cdiv(v1, 4); a.nb2 = (int)cdiv(v2, 4);
+    a.nvox = (long long)v0 * v1 * v2;
+    const size_t fbytes = (size_t)NV * h * w * C * 4;
+    if (!gather_takes(C)) {
+        // round-2 scatter: global float atomics into zeroed buffers (not bitwise repeatable); unmasked only (refused above otherwise)
+        const UnprojBwdArgs& u = a;
+        LT_REQUIRE(agg != LT_AGG_CONF_NORM, LT_ERR_UNSUPPORTED, "%s: conf_norm needs the gather path (C a power of two <= 64)", who);
+        LT_REQUIRE(hipMemsetAsync(grad_feats, 0, fbytes * B, st) == hipSuccess, LT_ERR_LAUNCH, "%s: hipMemsetAsync failed", who);
+        if (a.gconf) LT_REQUIRE(hipMemsetAsync(a.gconf, 0, (size_t)B * NV * C * 4, st) == hipSuccess, LT_ERR_LAUNCH, "%s: hipMemsetAsync failed", who);
+        const long long blocks = cdiv(a.nvox * (C / 4), 256);
+        dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)B);
+        if (NV > UB_MAXV) {
+            if (dtype == LT_F32) hipLaunchKernelGGL(unproject_bwd_many_kernel<float>, grid, dim3(256), 0, st, u);
+            else hipLaunchKernelGGL(unproject_bwd_many_kernel<bf16_t>, grid, dim3(256), 0, st, u);
+        } else if (dtype == LT_F32) hipLaunchKernelGGL(unproject_bwd_kernel<float>, grid, dim3(256), 0, st, u);
+        else hipLaunchKernelGGL(unproject_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, u);
+        LT_CHECK_LAUNCH("lt_unproject_bwd(scatter)");
+        return LT_OK;
+    }
+    const int nbricks = a.nb0 * a.nb1 * a.nb2;
+    const int nblk1 = blocks_k1(a.nvox, C);
+    const size_t s_dx = align256((size_t)NV * a.nvox * C * 4), s_bb = align256((size_t)NV * nbricks * 16), s_gc = align256((size_t)nblk1 * NV * C * 8);
+    const size_t s_xy = align256((size_t)NV * a.nvox * 4), s_tw = align256((size_t)NV * a.nvox * 16);
+    const size_t per_sample = s_dx + s_bb + s_gc + s_xy + s_tw;
+    LT_REQUIRE(workspace && workspace_bytes >= per_sample && ((size_t)workspace % 16) == 0, LT_ERR_INVALID,
+               "%s: workspace of at least %zu bytes (one sample; lt_unproject_bwd_workspace for the whole batch), 16-byte aligned", who, per_sample);
+    const int chunk = (int)(workspace_bytes / per_sample < (size_t)B ? workspace_bytes / per_sample : (size_t)B);
+    const int tiles = (int)(cdiv(w, G_TW) * cdiv(h, G_TH));
+    const size_t in_elt = dtype == LT_F32 ? 4 : 2;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = B - b0 < chunk ? B - b0 : chunk;
+        UnprojBwdMaskedArgs c = a;
+        c.B = nb;
+        c.feats = (const char*)feats + (size_t)b0 * NV * h * w * C * in_elt;
+        c.proj = proj + (size_t)b0 * NV * 12;
+        c.coords = coords + (size_t)b0 * a.nvox * 3;
+        c.conf = conf ? conf + (size_t)b0 * NV * C : nullptr;
+        c.mask = a.mask ? a.mask + (size_t)b0 * NV : nullptr;
+        c.gout = grad_out + (size_t)b0 * a.nvox * C;
+        c.gfeats = grad_feats + (size_t)b0 * NV * h * w * C;
+        c.gconf = a.gconf ? a.gconf + (size_t)b0 * NV * C : nullptr;
+        char* wsp = (char*)workspace;
+        c.dxs = (float*)wsp; wsp += s_dx * nb;
+        c.bbox = (int*)wsp; wsp += s_bb * nb;
+        c.gcpart = (double*)wsp; wsp += s_gc * nb;
+        c.tw = (float4*)wsp; wsp += s_tw * nb;
+        c.txy = (int*)wsp;
+        int rc = masked ? launch_taps_dx<true>(who, c, dtype, nbricks, nblk1, st) : launch_taps_dx<false>(who, c, dtype, nbricks, nblk1, st);
+        if (rc != LT_OK) return rc;
+        switch (C / 4) {                                          // K2 as it is: a masked view has no brick to walk and stores zeros
+            case 1: rc = launch_gather<1>(c, tiles, NV, nb, st); break;
+            case 2: rc = launch_gather<2>(c, tiles, NV, nb, st); break;
+            case 4: rc = launch_gather<4>(c, tiles, NV, nb, st); break;
+            case 8: rc = launch_gather<8>(c, tiles, NV, nb, st); break;
+            default: rc = launch_gather<16>(c, tiles, NV, nb, st); break;
+        }
+        if (rc != LT_OK) return rc;
+    }
+    return LT_OK;
+}
+
 }  // namespace
 
 // bytes for ALL B samples at once; lt_unproject_bwd walks the batch in chunks when it is handed less (at least one sample's worth)
@@ -788,99 +998,13 @@ extern "C" size_t lt_unproject_bwd_workspace(int32_t B, int32_t NV, int32_t C, i
 extern "C" int lt_unproject_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const float* grad_out,
                                 float* grad_feats, float* grad_conf, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1,
                                 int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes, void* stream) {
-    LT_REQUIRE(feats && proj && coords && grad_out && grad_feats, LT_ERR_INVALID, "lt_unproject_bwd: null argument");
-    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "lt_unproject_bwd: bad dtype %d", dtype);
-    LT_REQUIRE(agg == LT_AGG_SUM || agg == LT_AGG_MAX || agg == LT_AGG_SOFTMAX || agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM, LT_ERR_UNSUPPORTED,
-               "lt_unproject_bwd: unknown aggregation %d", agg);
-    const bool is_conf = agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM;
-    LT_REQUIRE(!is_conf || conf, LT_ERR_INVALID, "lt_unproject_bwd: the conf aggregations need confidences");
-    LT_REQUIRE(B >= 1 && NV >= 1 && NV <= UB_MANYV && C >= 4 && C % 4 == 0 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_UNSUPPORTED,
-               "lt_unproject_bwd: needs 1 <= NV <= %d and C %% 4 == 0 (got NV=%d C=%d)", UB_MANYV, NV, C);
-    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_bwd: feature maps too large");
-    hipStream_t st = (hipStream_t)stream;
-    UnprojBwdArgs a;
-    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.gout = grad_out; a.gfeats = grad_feats; a.gconf = is_conf ? grad_conf : nullptr;
-    a.dxs = nullptr; a.bbox = nullptr; a.gcpart = nullptr; a.txy = nullptr; a.tw = nullptr;
-    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.agg = agg;
-    a.v0 = v0; a.v1 = v1; a.v2 = v2; a.nb0 = (int)cdiv(v0, 4); a.nb1 = (int)cdiv(v1, 4); a.nb2 = (int)cdiv(v2, 4);
-    a.nvox = (long long)v0 * v1 * v2;
-    const size_t fbytes = (size_t)NV * h * w * C * 4;
-    if (!gather_takes(C)) {
-        // round-2 scatter: global float atomics into zeroed buffers (not bitwise repeatable)
-        LT_REQUIRE(agg != LT_AGG_CONF_NORM, LT_ERR_UNSUPPORTED, "lt_unproject_bwd: conf_norm needs the gather path (C a power of two <= 64)");
-        LT_REQUIRE(hipMemsetAsync(grad_feats, 0, fbytes * B, st) == hipSuccess, LT_ERR_LAUNCH, "lt_unproject_bwd: hipMemsetAsync failed");
-        if (a.gconf) LT_REQUIRE(hipMemsetAsync(a.gconf, 0, (size_t)B * NV * C * 4, st) == hipSuccess, LT_ERR_LAUNCH, "lt_unproject_bwd: hipMemsetAsync failed");
-        const long long blocks = cdiv(a.nvox * (C / 4), 256);
-        dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)B);
-        if (NV > UB_MAXV) {
-            if (dtype == LT_F32) hipLaunchKernelGGL(unproject_bwd_many_kernel<float>, grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL(unproject_bwd_many_kernel<bf16_t>, grid, dim3(256), 0, st, a);
-        } else if (dtype == LT_F32) hipLaunchKernelGGL(unproject_bwd_kernel<float>, grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(unproject_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, a);
-        LT_CHECK_LAUNCH("lt_unproject_bwd(scatter)");
-        return LT_OK;
-    }
-    const int nbricks = a.nb0 * a.nb1 * a.nb2;
-    const int nblk1 = blocks_k1(a.nvox, C);
-    const size_t s_dx = align256((size_t)NV * a.nvox * C * 4), s_bb = align256((size_t)NV * nbricks * 16), s_gc = align256((size_t)nblk1 * NV * C * 8);
-    const size_t s_xy = align256((size_t)NV * a.nvox * 4), s_tw = align256((size_t)NV * a.nvox * 16);
-    const size_t per_sample = s_dx + s_bb + s_gc + s_xy + s_tw;
-    LT_REQUIRE(workspace && workspace_bytes >= per_sample && ((size_t)workspace % 16) == 0, LT_ERR_INVALID,
-               "lt_unproject_bwd: workspace of at least %zu bytes (one sample; lt_unproject_bwd_workspace for the whole batch), 16-byte aligned", per_sample);
-    const int chunk = (int)(workspace_bytes / per_sample < (size_t)B ? workspace_bytes / per_sample : (size_t)B);
-    const int tiles = (int)(cdiv(w, G_TW) * cdiv(h, G_TH));
-    const size_t in_elt = dtype == LT_F32 ? 4 : 2;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = B - b0 < chunk ? B - b0 : chunk;
-        UnprojBwdArgs c = a;
-        c.B = nb;
-        c.feats = (const char*)feats + (size_t)b0 * NV * h * w * C * in_elt;
-        c.proj = proj + (size_t)b0 * NV * 12;
-        c.coords = coords + (size_t)b0 * a.nvox * 3;
-        c.conf = conf ? conf + (size_t)b0 * NV * C : nullptr;
-        c.gout = grad_out + (size_t)b0 * a.nvox * C;
-        c.gfeats = grad_feats + (size_t)b0 * NV * h * w * C;
-        c.gconf = a.gconf ? a.gconf + (size_t)b0 * NV * C : nullptr;
-        char* wsp = (char*)workspace;
-        c.dxs = (float*)wsp; wsp += s_dx * nb;
-        c.bbox = (int*)wsp; wsp += s_bb * nb;
-        c.gcpart = (double*)wsp; wsp += s_gc * nb;
-        c.tw = (float4*)wsp; wsp += s_tw * nb;
-        c.txy = (int*)wsp;
-        hipLaunchKernelGGL(unproj_taps_kernel, dim3((unsigned)cdiv(nbricks, 4), (unsigned)nb), dim3(256), 0, st, c);
-        LT_CHECK_LAUNCH("lt_unproject_bwd(taps)");
-        const dim3 g1((unsigned)nblk1, (unsigned)nb);
-        if (NV > UB_MAXV) {                                       // views in passes (softmax, max) or in groups of UB_MAXV (grid z)
-            const dim3 gz((unsigned)nblk1, (unsigned)nb, (unsigned)cdiv(NV, UB_MAXV));
-            if (agg == LT_AGG_SOFTMAX || agg == LT_AGG_MAX) {
-                if (dtype == LT_F32) hipLaunchKernelGGL(unproj_dx_passes_kernel<float>, g1, dim3(256), 0, st, c);
-                else hipLaunchKernelGGL(unproj_dx_passes_kernel<bf16_t>, g1, dim3(256), 0, st, c);
-            } else if (dtype == LT_F32) hipLaunchKernelGGL(unproj_dx_groups_kernel<float>, gz, dim3(256), 0, st, c);
-            else hipLaunchKernelGGL(unproj_dx_groups_kernel<bf16_t>, gz, dim3(256), 0, st, c);
-        } else if (dtype == LT_F32) {
-            if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<float, 4>), g1, dim3(256), 0, st, c);
-            else hipLaunchKernelGGL((unproj_dx_kernel<float, UB_MAXV>), g1, dim3(256), 0, st, c);
-        } else {
-            if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, 4>), g1, dim3(256), 0, st, c);
-            else hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, UB_MAXV>), g1, dim3(256), 0, st, c);
-        }
-        LT_CHECK_LAUNCH("lt_unproject_bwd(dx)");
-        if (c.gconf && NV > UB_MAXV) {
-            hipLaunchKernelGGL(unproj_gconf_finalize_many_kernel, dim3((unsigned)(nb * (C / (C < UB_FIN_C ? C : UB_FIN_C)))), dim3(UB_MANYV * UB_FIN_C), 0, st, c, nblk1);
-            LT_CHECK_LAUNCH("lt_unproject_bwd(gconf)");
-        } else if (c.gconf) {
-            hipLaunchKernelGGL(unproj_gconf_finalize_kernel, dim3((unsigned)cdiv((long long)nb * C, 64)), dim3(64), 0, st, c, nblk1);
-            LT_CHECK_LAUNCH("lt_unproject_bwd(gconf)");
-        }
-        int rc;
-        switch (C / 4) {
-            case 1: rc = launch_gather<1>(c, tiles, NV, nb, st); break;
-            case 2: rc = launch_gather<2>(c, tiles, NV, nb, st); break;
-            case 4: rc = launch_gather<4>(c, tiles, NV, nb, st); break;
-            case 8: rc = launch_gather<8>(c, tiles, NV, nb, st); break;
-            default: rc = launch_gather<16>(c, tiles, NV, nb, st); break;
-        }
-        if (rc != LT_OK) return rc;
-    }
-    return LT_OK;
+    return unproject_backward("lt_unproject_bwd", false, dtype, feats, proj, coords, conf, nullptr, grad_out, grad_feats, grad_conf, B, NV, C, h, w, v0, v1, v2,
+                              agg, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lt_unproject_masked_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                                       const float* grad_out, float* grad_feats, float* grad_conf, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w,
+                                       int32_t v0, int32_t v1, int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes, void* stream) {
+    return unproject_backward("lt_unproject_masked_bwd", true, dtype, feats, proj, coords, conf, view_mask, grad_out, grad_feats, grad_conf, B, NV, C, h, w, v0,
+                              v1, v2, agg, workspace, workspace_bytes, stream);
 }

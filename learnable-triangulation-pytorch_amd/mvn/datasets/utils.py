@@ -11,9 +11,15 @@ import torch
 from lt_staging import PinnedRing
 
 
-def make_collate_fn(randomize_n_views=True, min_n_views=10, max_n_views=31):
+def make_collate_fn(randomize_n_views=True, min_n_views=10, max_n_views=31, mask_views=False):
     """Reference datasets/utils.py:6-39: drops ``None`` items, optionally sub-samples the views (np.random, like the
-    reference), and stacks per-view lists into the batch dict."""
+    reference), and stacks per-view lists into the batch dict.
+
+    mask_views (with randomize_n_views): every batch has the SAME view count, ``min(total_n_views, max_n_views)`` views (a random choice of
+    that many, in ascending index order), and the drawn view count becomes ``batch["view_mask"]`` instead of the batch's shape: ``n_views`` is
+    drawn once per batch as the reference draws it, and every sample gets its own random subset of ``n_views`` valid views ((B, NV) uint8,
+    1 = valid).  One training plan then serves every draw (``masked_training`` on the model).  False: the function and its sequence of
+    np.random calls are the reference's."""
 
     def collate_fn(items):
         items = [x for x in items if x is not None]
@@ -24,7 +30,15 @@ def make_collate_fn(randomize_n_views=True, min_n_views=10, max_n_views=31):
         key = "images" if "images" in items[0] else "frames"        # "frames" + "bboxes": deferred pixel work (prepare_batch_frames)
         total_n_views = min(len(item[key]) for item in items)
         indexes = np.arange(total_n_views)
-        if randomize_n_views:
+        if randomize_n_views and mask_views:
+            kept = min(total_n_views, max_n_views)
+            n_views = np.random.randint(min_n_views, kept + 1)
+            indexes = np.sort(np.random.choice(np.arange(total_n_views), size=kept, replace=False))
+            view_mask = np.zeros((len(items), kept), dtype=np.uint8)
+            for row in view_mask:          # every sample its own subset of n_views valid views
+                row[np.random.choice(kept, size=n_views, replace=False)] = 1
+            batch["view_mask"] = view_mask
+        elif randomize_n_views:
             n_views = np.random.randint(min_n_views, min(total_n_views, max_n_views) + 1)
             indexes = np.random.choice(np.arange(total_n_views), size=n_views, replace=False)
         if key == "images":

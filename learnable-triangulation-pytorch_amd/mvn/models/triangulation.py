@@ -75,10 +75,15 @@ class _VolTrainPlan:
     forward / backward run the layers while recording them; later steps re-launch the recorded closures over the same buffers.  What
     changes from step to step enters through fixed buffers: the images (layout change into ``x_in``), the geometry block (one pinned
     H2D copy, as in inference), the parameters (gathered live into the GEMM layouts), the loss gradient (``lt_softargmax3d_bwd`` into
-    ``gl``)."""
+    ``gl``).
 
-    def __init__(self, model, B, NV, Hh, W, device):
+    masked (``masked_training`` steps with ``batch["view_mask"]``): the tape records lt_unproject_grid_masked_fwd / lt_unproject_masked_bwd in the
+    unmasked pair's place; the (B, NV) uint8 mask rides at the end of the geometry block as in the inference plan, so another mask is just
+    another step of the same tape."""
+
+    def __init__(self, model, B, NV, Hh, W, device, masked=False):
         self.model, self.B, self.NV, self.Hh, self.W, self.device = model, B, NV, Hh, W, device
+        self.masked = bool(masked)
         self.tape = None
         self.step_id = 0
 
@@ -135,8 +140,10 @@ class _VolTrainPlan:
             pf = model.process_features[0]
             self.feats = feats = tape.conv(feats256, pf.weight, pf.bias, None)
             h, w = feats.shape[2], feats.shape[3]
-            n_geo = B * NV * 12 + B * 15
-            self.G = {"hw": (h, w), "offs": (B * NV * 12, B * NV * 12 + 3 * B, B * NV * 12 + 6 * B), "geo_ring": PinnedRing(n_geo, torch.float32, GEO_RING)}
+            o_mask = B * NV * 12 + B * 15          # masked plans: B*NV mask bytes behind the floats (whole words), as in the inference plan
+            n_geo = o_mask + ((B * NV + 3) // 4 if self.masked else 0)
+            self.G = {"hw": (h, w), "offs": (B * NV * 12, B * NV * 12 + 3 * B, B * NV * 12 + 6 * B), "geo_ring": PinnedRing(n_geo, torch.float32, GEO_RING),
+                      "masked": self.masked, "o_mask": o_mask}
             self.geo = torch.zeros(n_geo, dtype=torch.float32, device=device)
             self.n_front = len(tape.fwd_ops)
         else:
@@ -159,9 +166,15 @@ class _VolTrainPlan:
             cmu = int(bool(model.transfer_cmu_to_human36m))
             volc = self.volc
             conf_p = None if volc is None else volc.t.data_ptr()          # (B, NV, 32) raw confidences; 'conf_norm' is normalised inside the kernels
-            tape.do(lambda s_: H.check(lib.lt_unproject_grid_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                                 coords.data_ptr(), conf_p, vol.t.data_ptr(), B, NV, 32, h, w, V, agg, s_), "lt_unproject_grid_fwd"),
-                    "unproject")
+            mask_p = gp + 4 * G["o_mask"]          # masked plans: the step's (B, NV) mask, behind the geometry in the same block
+            if self.masked:
+                tape.do(lambda s_: H.check(lib.lt_unproject_grid_masked_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
+                                                                            coords.data_ptr(), conf_p, mask_p, vol.t.data_ptr(), B, NV, 32, h, w, V, agg, s_),
+                                           "lt_unproject_grid_masked_fwd"), "unproject")
+            else:
+                tape.do(lambda s_: H.check(lib.lt_unproject_grid_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
+                                                                     coords.data_ptr(), conf_p, vol.t.data_ptr(), B, NV, 32, h, w, V, agg, s_), "lt_unproject_grid_fwd"),
+                        "unproject")
             tape._derive(vol, (feats, volc))
             need_f, need_c = tape.carries(feats), tape.carries(volc)
 
@@ -185,9 +198,14 @@ class _VolTrainPlan:
                 # entry point walks the batch in chunks
                 nws = int(max(16, min(per_sample * B, max(per_sample, op.UNPROJECT_BWD_WORKSPACE_CAP))))
                 tape._ws_need(nws)
-                tape.do(lambda s_: H.check(lib.lt_unproject_bwd(ac, feats.t.data_ptr(), gp, coords.data_ptr(), conf_p, dvol32.data_ptr(), gfe32.data_ptr(),
-                                                                H.ptr(gconf), B, NV, 32, h, w, V, V, V, agg, tape._ws.data_ptr(), nws, s_), "lt_unproject_bwd"),
-                        "unproject_bwd")
+                if self.masked:
+                    tape.do(lambda s_: H.check(lib.lt_unproject_masked_bwd(ac, feats.t.data_ptr(), gp, coords.data_ptr(), conf_p, mask_p, dvol32.data_ptr(),
+                                                                           gfe32.data_ptr(), H.ptr(gconf), B, NV, 32, h, w, V, V, V, agg, tape._ws.data_ptr(), nws, s_),
+                                               "lt_unproject_masked_bwd"), "unproject_bwd")
+                else:
+                    tape.do(lambda s_: H.check(lib.lt_unproject_bwd(ac, feats.t.data_ptr(), gp, coords.data_ptr(), conf_p, dvol32.data_ptr(), gfe32.data_ptr(),
+                                                                    H.ptr(gconf), B, NV, 32, h, w, V, V, V, agg, tape._ws.data_ptr(), nws, s_), "lt_unproject_bwd"),
+                            "unproject_bwd")
                 gfe = gfe32
                 if tape.act16:
                     gfe = torch.empty(feats.t.shape, dtype=torch.bfloat16, device=device)
@@ -215,6 +233,9 @@ class _VolTrainPlan:
         if self.volc is not None:          # the returned vol_confidences (reference :266-269, :355): (B, NV, 32), normalised over the views for conf_norm
             conf_out = self.volc.t.reshape(B, NV, 32).clone()
             if model.volume_aggregation_method == "conf_norm":
+                if self.masked:          # the inference rule: normalised over the valid views, a masked view's entries 0 (an all-ones mask: the same bits)
+                    on = torch.from_numpy(batch["view_mask"]).to(device, non_blocking=True).bool()[:, :, None]
+                    conf_out = torch.where(on, conf_out, torch.zeros((), dtype=conf_out.dtype, device=device))
                 conf_out = conf_out / conf_out.sum(dim=1, keepdim=True)
         self.conf_out = conf_out
         feats_out = torch.empty(B, NV, 32, h, w, dtype=torch.float32, device=device)          # the returned features, contiguous like the reference's
@@ -436,6 +457,9 @@ class VolumetricTriangulationNet(_PlannedNet):
         # returned joint) in last_keypoint_stats; the 7-tuple keeps its bits.  Ignored in train(), where last_keypoint_stats is None.
         self.keypoint_stats = False
         self.last_keypoint_stats = None
+        # True: a train() forward takes batch["view_mask"] -- the masked training step (lt_unproject_grid_masked_fwd / lt_unproject_masked_bwd: every
+        # sample's volume and its gradient over its valid views alone; the backbone still runs on every image).  False: a mask in train() is refused.
+        self.masked_training = False
         if self.volume_aggregation_method not in H.AGG:
             raise ValueError("Unknown volume_aggregation_method: {}".format(self.volume_aggregation_method))
         # same config mutation as the reference (:228-231)
@@ -600,7 +624,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         B, NV = images.shape[:2]
         vm = _batch_view_mask(batch, B, NV, 1, "VolumetricTriangulationNet")          # optional (B, NV) validity mask: refused before any launch
         if vm is not None:
-            if _bn_in_train_mode(self):
+            if _bn_in_train_mode(self) and not self.masked_training:
                 raise NotImplementedError("VolumetricTriangulationNet: batch['view_mask'] is inference only (there is no masked backward); call eval() first")
             batch = dict(batch, view_mask=vm)
         H.require_gpu(images, "images")
@@ -658,10 +682,8 @@ class VolumetricTriangulationNet(_PlannedNet):
             raise RuntimeError("training updates the parameters where they live: move the model to %s first (model.to(device), as "
                                "train.py:424 does); %d tensors are elsewhere, e.g. %s" % (images.device, len(off), off[0]))
         B, NV = images.shape[:2]
-        key = (B, NV, images.shape[3], images.shape[4], images.device, self.volume_size, float(self.cuboid_side), float(self.volume_multiplier),
-               bool(self.volume_softmax), self.volume_aggregation_method, bool(self.transfer_cmu_to_human36m), self.num_joints,
-               tuple(p.requires_grad for p in params), id(getattr(self, "grad_reducer", None)), getattr(self, "train_precision", "fp32"),
-               tuple(c.training for c in self.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm)))
+        masked = batch.get("view_mask") is not None          # (forward() let it through: masked_training)
+        key = self._train_plan_key(B, NV, images.shape[3], images.shape[4], images.device, params, masked)
         if getattr(self, "train_precision", "fp32") not in ("fp32", "bf16", "act16", "fp8v2v"):
             raise ValueError("train_precision must be 'fp32' (the reference's precision), 'bf16' (bf16 MFMA convolutions, fp32 storage), 'act16' (bf16 MFMA "
                              "convolutions AND bf16 activations / activation gradients) or 'fp8v2v' (act16 with V2V's 3x3x3 convolutions on the fp8 MFMA)")
@@ -679,7 +701,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         if plan is None:
             while len(plans) >= 2:
                 plans.popitem(last=False)          # frees its activations and gradient buffers
-            plan = plans[key] = _VolTrainPlan(self, B, NV, images.shape[3], images.shape[4], images.device)
+            plan = plans[key] = _VolTrainPlan(self, B, NV, images.shape[3], images.shape[4], images.device, masked=masked)
         plans.move_to_end(key)
         kp, probs, feats, coords, base_points = _VolTrainFn.apply(plan, images, batch, *params)
         # every BatchNorm's num_batches_tracked += 1 (what nn.BatchNorm does in train()): ONE liblt_hip launch over a table of the counters'
@@ -693,6 +715,15 @@ class VolumetricTriangulationNet(_PlannedNet):
         position, sides = self.__dict__.pop("_train_extra")
         cuboids = [volumetric.Cuboid3D(position[i], sides) for i in range(images.shape[0])]
         return kp, feats, probs, plan.conf_out, cuboids, coords, base_points
+
+    def _train_plan_key(self, B, NV, Hh, W, device, params, masked=False):
+        """Everything a training plan bakes in.  ``masked``: its tape records the masked unprojection pair (steps with ``batch["view_mask"]`` under
+        ``masked_training``); steps without a mask keep their plan: an unmasked key is the tuple it always was."""
+        key = (B, NV, Hh, W, device, self.volume_size, float(self.cuboid_side), float(self.volume_multiplier),
+               bool(self.volume_softmax), self.volume_aggregation_method, bool(self.transfer_cmu_to_human36m), self.num_joints,
+               tuple(p.requires_grad for p in params), id(getattr(self, "grad_reducer", None)), getattr(self, "train_precision", "fp32"),
+               tuple(c.training for c in self.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm)))
+        return key + ("view_mask",) if masked else key
 
     def _chunk_plan(self, images, batch, lo, hi):
         """Samples lo .. hi of the call and the plan of that shape: (images, batch, B, P)."""
@@ -815,6 +846,9 @@ class AlgebraicTriangulationNet(_PlannedNet):
         # keeps its bits.  Ignored in train(), where last_keypoint_stats is None.
         self.keypoint_stats = False
         self.last_keypoint_stats = None
+        # True: a train() forward takes batch["view_mask"] -- confidences normalised over each sample's valid views, the DLT of the valid views alone, zero
+        # gradient into a masked view's keypoints and confidences (the backbone still runs on every image).  False: a mask in train() is refused.
+        self.masked_training = False
 
     def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False):
         """masked: the plan of forwards with ``batch["view_mask"]`` -- the same launches, plus the mask's device block and its pinned staging ring (the
@@ -858,12 +892,12 @@ class AlgebraicTriangulationNet(_PlannedNet):
         B, NV = images.shape[:2]
         Hh, W = images.shape[3:]
         vm = _batch_view_mask(batch, B, NV, 2, "AlgebraicTriangulationNet")          # optional (B, NV) validity mask: refused before any launch
-        if vm is not None and _bn_in_train_mode(self):
+        if vm is not None and _bn_in_train_mode(self) and not self.masked_training:
             raise NotImplementedError("AlgebraicTriangulationNet: batch['view_mask'] is inference only (there is no masked backward); call eval() first")
         H.require_gpu(images, "images")
         self.last_keypoint_stats = None
         if _bn_in_train_mode(self):
-            return self._forward_train(images, proj_matricies)          # keypoint_stats is ignored there
+            return self._forward_train(images, proj_matricies, vm)          # keypoint_stats is ignored there
         _sync_buffers_before_eval(self)
         masked, stats = vm is not None, bool(self.keypoint_stats)
         with torch.cuda.device(device):
@@ -876,8 +910,12 @@ class AlgebraicTriangulationNet(_PlannedNet):
         key = (B, NV, Hh, W, self.compute_dtype, device, float(self.heatmap_multiplier), bool(self.heatmap_softmax), self.tile_override, masked)
         return key + ("keypoint_stats",) if stats else key
 
-    def _forward_train(self, images, proj_matricies):
-        """Training mode (round 3; the reference's loop for model_type "alg", train.py:189-236): the backbone -- heatmap head and, with
+    def _forward_train(self, images, proj_matricies, view_mask=None):
+        """view_mask (``masked_training``): the checked host (B, NV) mask -- the tape is the unmasked step's (the backbone runs on every image); the tail
+        normalises the confidences over each sample's valid views (+ 1e-5 for a valid view, exactly 0 for a masked one, as lt_alg_tail_masked_fwd
+        defines) and triangulates the valid views alone; a masked view's 2D keypoints and confidences get zero gradient.
+
+        Training mode (round 3; the reference's loop for model_type "alg", train.py:189-236): the backbone -- heatmap head and, with
         ``use_confidences``, the alg_confidences head included -- runs its recorded training step (lt_train.TrainTape: batch-statistics
         BatchNorm, liblt_hip backward); 2D soft-argmax, confidence normalisation and the DLT are autograd nodes over liblt_hip kernels
         (lt_softargmax2d_bwd, lt_triangulate_dlt_bwd: what autograd derives through torch.svd in the reference).  Same 4-tuple as inference."""
@@ -924,6 +962,14 @@ class AlgebraicTriangulationNet(_PlannedNet):
         N, J, h, w = hm.shape
         kp2d, heatmaps = op.integrate_tensor_2d(hm * self.heatmap_multiplier, self.heatmap_softmax)      # reference :158
         conf = conf_raw.reshape(B, NV, J) if conf_raw.numel() else torch.ones(B, NV, J, dtype=torch.float32, device=device)
+        if view_mask is not None:
+            on = torch.from_numpy(view_mask).to(device).bool()[:, :, None]
+            zero = torch.zeros((), dtype=torch.float32, device=device)
+            conf = torch.where(on, conf, zero)
+            conf = torch.where(on, conf / conf.sum(dim=1, keepdim=True) + 1e-5, zero)
+            kp2d = kp2d.reshape(B, NV, J, 2) * torch.tensor([W / w, Hh / h], dtype=torch.float32, device=device)
+            kp3d = multiview.triangulate_batch_of_points(proj_matricies.to(device), kp2d, confidences_batch=conf, view_mask=view_mask, masked_backward=True)
+            return kp3d, kp2d, heatmaps.reshape(B, NV, J, h, w), conf
         conf = conf / conf.sum(dim=1, keepdim=True) + 1e-5                                                 # reference :173-174
         scale = torch.tensor([W / w, Hh / h], dtype=torch.float32, device=device)
         kp2d = kp2d.reshape(B, NV, J, 2) * scale                                                          # reference :181-184

@@ -119,22 +119,24 @@ class _TriangulateFn(torch.autograd.Function):
         return None, gpts, gconf
 
 
-def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_batch=None, view_mask=None):
+def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_batch=None, view_mask=None, masked_backward=False):
     """Confidence-weighted DLT for every (sample, joint) in one launch (reference :171-183 loops B x J
     torch.svd calls).  proj (B,NV,3,4), points (B,NV,J,2), confidences (B,NV,J) -> (B,J,3) fp32.  Differentiable with respect to the
     points and the confidences when they require grad.
 
     view_mask: optional (B,NV) bool / uint8 tensor or array, non-zero = the view is there.  Sample b then gets the DLT of its valid views
     alone, bit for bit: a masked view's rows are given weight 0 with its point and matrix zeroed, and the kernel's QR skips a row of zeros, so
-    NaN in a masked view cannot leak.  A sample needs two valid views (ValueError).  Inference only: NotImplementedError with inputs that
-    require grad."""
+    NaN in a masked view cannot leak.  A sample needs two valid views (ValueError).  Inference only by default: NotImplementedError with
+    inputs that require grad.  masked_backward=True opts into the differentiable masked DLT: the same construction in front of
+    lt_triangulate_dlt / lt_triangulate_dlt_bwd, whose gradient for a row of zeros is zero and which torch.where routes back as zero -- a masked
+    view's points and confidences get exactly zero gradient, the valid ones what the DLT of the valid views alone gives."""
     H.require_gpu(points_batch, "points_batch")
     P = proj_matricies_batch.to(points_batch.device, torch.float32).contiguous()
     pts = points_batch.float().contiguous()
     conf = None if confidences_batch is None else confidences_batch.float().contiguous()
     if view_mask is not None:
         from mvn.utils import op
-        if torch.is_grad_enabled() and (pts.requires_grad or (conf is not None and conf.requires_grad)):
+        if not masked_backward and torch.is_grad_enabled() and (pts.requires_grad or (conf is not None and conf.requires_grad)):
             raise NotImplementedError("triangulate_batch_of_points: view_mask is inference only (no masked backward); call it under torch.no_grad()")
         B, NV, J = pts.shape[:3]
         m = torch.from_numpy(op.view_mask_host(view_mask, B, NV, min_valid=2)).to(pts.device).bool()

@@ -94,14 +94,15 @@ def _unproject_launch(feats_cl, P, cv, conf, method, mask=None):
 class _UnprojectFn(torch.autograd.Function):
     """lt_unproject_fwd / lt_unproject_bwd as one autograd node: what autograd builds in the reference from grid_sample, the
     in-place depth mask and the view aggregation (op.py:113-162).  Gradients reach the heatmaps and (conf modes) the confidences;
-    projections and coordinates get none, exactly as in the reference (they do not require grad there)."""
+    projections and coordinates get none, exactly as in the reference (they do not require grad there).  mask: a (B,NV) uint8 device tensor makes
+    it the node over lt_unproject_masked_fwd / lt_unproject_masked_bwd (every sample over its valid views alone; masked views get zero gradients)."""
 
     @staticmethod
-    def forward(ctx, heatmaps, P, cv, conf, method):
+    def forward(ctx, heatmaps, P, cv, conf, method, mask=None):
         feats = _as_channels_last(heatmaps, 2)
-        out = _unproject_launch(feats, P, cv, conf, method)
+        out = _unproject_launch(feats, P, cv, conf, method, mask)
         ctx.save_for_backward(feats, P, cv, conf if conf is not None else torch.empty(0, device=feats.device))
-        ctx.method, ctx.has_conf = method, conf is not None
+        ctx.method, ctx.has_conf, ctx.mask = method, conf is not None, mask
         return out.permute(0, 4, 1, 2, 3)
 
     @staticmethod
@@ -117,20 +118,31 @@ class _UnprojectFn(torch.autograd.Function):
         # deterministic gather: workspace for as many samples as fit 2 GiB at a time (the entry walks the batch in chunks)
         per_sample = lib.lt_unproject_bwd_workspace(1, NV, Cc, v0, v1, v2)
         ws = torch.empty(max(16, min(per_sample * B, max(per_sample, UNPROJECT_BWD_WORKSPACE_CAP))), dtype=torch.uint8, device=feats.device)
-        H.check(lib.lt_unproject_bwd(H.dtype_code(feats.dtype), feats.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), g.data_ptr(),
-                                     gfeats.data_ptr(), H.ptr(gconf), B, NV, Cc, h, w, v0, v1, v2,
-                                     H.AGG["conf"] if conf is not None else H.AGG[ctx.method], ws.data_ptr(), ws.numel(), H.cur_stream()), "lt_unproject_bwd")
-        return gfeats.permute(0, 1, 4, 2, 3).to(feats.dtype), None, None, gconf, None
+        agg = H.AGG["conf"] if conf is not None else H.AGG[ctx.method]
+        if ctx.mask is not None:
+            H.check(lib.lt_unproject_masked_bwd(H.dtype_code(feats.dtype), feats.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), ctx.mask.data_ptr(),
+                                                g.data_ptr(), gfeats.data_ptr(), H.ptr(gconf), B, NV, Cc, h, w, v0, v1, v2, agg, ws.data_ptr(), ws.numel(),
+                                                H.cur_stream()), "lt_unproject_masked_bwd")
+        else:
+            H.check(lib.lt_unproject_bwd(H.dtype_code(feats.dtype), feats.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), g.data_ptr(),
+                                         gfeats.data_ptr(), H.ptr(gconf), B, NV, Cc, h, w, v0, v1, v2, agg, ws.data_ptr(), ws.numel(), H.cur_stream()),
+                    "lt_unproject_bwd")
+        return gfeats.permute(0, 1, 4, 2, 3).to(feats.dtype), None, None, gconf, None, None
 
 
-def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="sum", vol_confidences=None, view_mask=None):
+def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="sum", vol_confidences=None, view_mask=None,
+                       masked_backward=False):
     """heatmaps (B,NV,C,h,w), proj_matricies (B,NV,3,4), coord_volumes (B,V0,V1,V2,3),
     vol_confidences (B,NV,C) for 'conf*' -> volumes (B,C,V0,V1,V2).  Reference: op.py:99-166.  Differentiable with respect to the
     heatmaps and the confidences (lt_unproject_bwd) whenever one of them requires grad.
 
     view_mask: optional (B,NV) bool / uint8 tensor or array, non-zero = the view is there.  Sample b then gets what this function gives for its
-    valid views alone (lt_unproject_masked_fwd: masked views are never read; a sample without a valid view gets zeros).  Inference only:
-    with inputs that require grad it raises NotImplementedError.  None takes exactly the unmasked path."""
+    valid views alone (lt_unproject_masked_fwd: masked views are never read; a sample without a valid view gets zeros).  Inference only by
+    default: with inputs that require grad it raises NotImplementedError.  None takes exactly the unmasked path.
+
+    masked_backward=True opts into the differentiable masked op (lt_unproject_masked_bwd): what autograd derives for this function called on each
+    sample's valid views alone -- a masked view's heatmaps and confidences get exactly zero gradient, conf_norm's normaliser is differentiated
+    over the valid views.  Gather path only (C a power of two <= 64); ignored without a view_mask."""
     if volume_aggregation_method not in _METHODS:
         raise ValueError("Unknown volume_aggregation_method: {}".format(volume_aggregation_method))
     H.require_gpu(heatmaps, "heatmaps")
@@ -141,9 +153,12 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
     if volume_aggregation_method.startswith("conf"):
         conf = vol_confidences.to(heatmaps.device, torch.float32).contiguous()
     if view_mask is not None:
-        if torch.is_grad_enabled() and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad)):
+        needs_grad = torch.is_grad_enabled() and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad))
+        if needs_grad and not masked_backward:
             raise NotImplementedError("unproject_heatmaps: view_mask is inference only (no masked backward); call it under torch.no_grad()")
         mask = _view_mask_device(view_mask, heatmaps.shape[0], heatmaps.shape[1], heatmaps.device)
+        if needs_grad:
+            return _UnprojectFn.apply(heatmaps, P, cv, conf, volume_aggregation_method, mask)
         return _unproject_launch(_as_channels_last(heatmaps, 2), P, cv, conf, volume_aggregation_method, mask).permute(0, 4, 1, 2, 3)
     if torch.is_grad_enabled() and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad)):
         return _UnprojectFn.apply(heatmaps, P, cv, conf, volume_aggregation_method)
