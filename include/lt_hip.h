@@ -200,6 +200,9 @@ typedef struct lt_wshape {
 /* lt_conv_skip_fwd: the second 3x3x3 32 -> 32 convolution of a Res3DBlock with its 1x1x1 16 -> 32 skip convolution computed in the launch, on shapes
  * the column-walk halo kernel takes in every sample chunk (LT_NO_CONV_SKIP, LT_HALO_NO_COL, LT_HALO_NO_PERSIST, LT_CONV_NO_HALO: off) */
 int lt_sel_conv_skip(int32_t dtype, const int32_t x[5], const lt_wshape* w, const int32_t skip_x[5], const lt_wshape* skip_w);
+/* which kernel lt_conv_fwd gives a bf16 7x7x7 / stride 1 / pad 3 convolution 32 -> (9..16) of x: 1 = the column walk (>= 256 whole columns of >= 2
+ * tiles of 4 x 8 x 8 voxels, their count a multiple of 8), 0 = one tile per workgroup (LT_HALO_NO_COL7: always 0) */
+int lt_sel_halo7_col(int32_t dtype, const int32_t x[5]);
 /* lt_conv_cat2_fwd: a Bottleneck's 1x1 expand of t2 and its 1x1 stride-s downsample of x as one launch, from 200 tiles of 288 x 256 on
  * (LT_NO_CONV_CAT2, LT_CONV_NO_V7, LT_CONV_NO_V3: off; LT_CAT2_ANY_SIZE: any size) */
 int lt_sel_conv_cat2(int32_t dtype, const int32_t t2[5], const lt_wshape* w_expand, const int32_t x[5], const lt_wshape* w_down, int32_t stride_down);

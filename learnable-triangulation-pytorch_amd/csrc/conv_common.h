@@ -77,6 +77,15 @@ inline bool halo_col_fits(long long N, int D, int H, int W) {
     return nblk >= 1024 && nblk % 8 == 0 && D / 4 >= 2 && cols % 8 == 0 && cols >= 256;
 }
 
+// The geometry conv3d_halo7_col_kernel (the column walk of the 7^3 32 -> 16 layer) covers: tiles of 4 x 8 x 8 voxels, columns of >= 2 tiles, and whole
+// columns for every workgroup of the persistent grid (>= 256 columns -- the CU count halo_col_fits assumes -- in a multiple of 8 for the XCD dealing).
+// conv3d_halo_try checks it at launch time; anything else stays on the one-tile kernel.
+inline bool halo7_col_fits(long long N, int D, int H, int W) {
+    if (D % 4 || H % 8 || W % 8) return false;
+    const long long cols = N * (H / 8) * (W / 8);
+    return D / 4 >= 2 && cols % 8 == 0 && cols >= 256 && cols < (1ll << 31);
+}
+
 // The "plain pointwise" layer: its one phase has one tap at offset 0, unit strides, no padding, an output grid equal to the input grid, and dense K
 // (k_pad == Cin) -- GEMM row m is input pixel m, so the kernels' pointwise modes need no tap table.  (A caller with several phases asks per phase.)
 inline bool plain_pointwise(const ConvArgs& a) {

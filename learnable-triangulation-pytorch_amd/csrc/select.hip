@@ -37,6 +37,11 @@ extern "C" int lt_sel_conv_skip(int32_t dtype, const int32_t x[5], const lt_wsha
     return halo_col_fits(nc, D, H, W) && halo_col_fits(N - (N - 1) / nc * nc, D, H, W);
 }
 
+extern "C" int lt_sel_halo7_col(int32_t dtype, const int32_t x[5]) {
+    if (dtype != LT_BF16 || x[4] != 32 || env_on("LT_HALO_NO_COL7")) return 0;
+    return halo7_col_fits(x[0], x[1], x[2], x[3]);
+}
+
 extern "C" int lt_sel_conv_cat2(int32_t dtype, const int32_t t2[5], const lt_wshape* we, const int32_t x[5], const lt_wshape* wd, int32_t s) {
     if (dtype != LT_BF16 || env_on("LT_NO_CONV_CAT2") || env_on("LT_CONV_NO_V7") || env_on("LT_CONV_NO_V3")) return 0;
     const int N = t2[0], Ho = t2[2], Wo = t2[3], P = t2[4];

@@ -28,7 +28,7 @@ GROUPS = [
     (r"^deconv4x4 2048->256", "head: 4x4 / 2 transposed 2048 -> 256", "`conv_igemm7` (four parity phases)", "pose_resnet.py:208-233"),
     (r"^conv(1x1|3x3) \d+(\+\d+)?->\d+ @\d+x1x", "other backbone convolutions (layer2-4 block 0, layer4, process_features)", "`conv_igemm2 / 3 / 6 / 7` by tile count", "pose_resnet.py:75-95; triangulation.py:238-240"),
     (r"^unproject", "unprojection + view softmax + coordinate grid", "`unproject_qn_kernel<1, GRID>`", "op.py:99-166; triangulation.py:298-339"),
-    (r"^conv7x7x7", "V2V front 7^3 32 -> 16", "`conv3d_halo7b_kernel`", "v2v.py:146"),
+    (r"^conv7x7x7", "V2V front 7^3 32 -> 16", "`conv3d_halo7_col_kernel` (>= 256 columns of >= 2 tiles) / `conv3d_halo7b_kernel`", "v2v.py:146"),
     (r"^conv3x3x3 32->32 .*skip", "V2V 16 -> 32 block: second 3^3 with the skip convolution inside", "`conv3d_halo_col_kernel<.., SKIP>`", "v2v.py:20-42"),
     (r"^conv3x3x3 32->32", "V2V 3^3 32 -> 32 at 64^3 (8)", "`conv3d_halo_col_kernel` (>= 256 columns) / `conv3d_halo_persist_kernel`", "v2v.py:20-42"),
     (r"^conv3x3x3 (16->32|64->64|32->64) ", "V2V 3^3 16 -> 32, 32 -> 64, 64 -> 64 (64^3 / 32^3)", "`conv3d_halo_wreg_kernel`", "v2v.py:20-42"),

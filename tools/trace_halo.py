@@ -1,5 +1,9 @@
 #!/usr/bin/env python
-"""Shader-clock accounting of the persistent 3^3 halo kernel's per-tile phases (GPU, profiling build liblt_hip_trace.so)."""
+"""Shader-clock accounting of the halo kernels' per-tile phases (GPU, profiling build liblt_hip_trace.so).
+
+    trace_halo.py [B] [--no-residual]        the 3^3 32 -> 32 layer at 64^3: column walk, or the persistent kernel under LT_HALO_NO_COL=1
+    trace_halo.py [B] --k7 [--residual]      V2V's front layer, 7^3 32 -> 16 at 64^3 (affine + ReLU as in the model): column walk, or the
+                                             one-tile kernel under LT_HALO_NO_COL7=1 (64 workgroups sampled across the launch, one tile each)"""
 import ctypes as C
 import os
 import sys
@@ -20,20 +24,28 @@ import torch
 import lt_engine as E
 import lt_hip as H
 
+NAMES3 = ["total", "wait+barrier", "halo issue / tile setup", "res issue", "tap loop (+ deferred epilogue)", "barrier", "epilogue / bookkeeping"]
+NAMES7 = ["total", "wait: halo / plane group landed", "tile setup (+ residual request)", "-", "tap nest (49 chunks)", "drain / seam barrier",
+          "epilogue / bookkeeping"]
+
 
 def main():
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-    with_res = "--no-residual" not in sys.argv
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    k7 = "--k7" in sys.argv
+    B = int(args[0]) if args else 16
+    with_res = "--residual" in sys.argv if k7 else "--no-residual" not in sys.argv
     lib = H.lib()
     lib.lt_trace_read_halo.restype = C.c_int
     lib.lt_trace_read_halo.argtypes = [C.c_void_p, C.c_int]
     dev, dt = "cuda:0", torch.bfloat16
     st = torch.cuda.current_stream().cuda_stream
+    ks, cout = (7, 16) if k7 else (3, 32)
     x = torch.randn(B, 64, 64, 64, 32, device=dev).to(dt)
-    w = torch.randn(32, 32, 3, 3, 3) * 0.05
-    res = E.Act(torch.randn(B, 64, 64, 64, 32, device=dev).to(dt))
+    w = torch.randn(cout, 32, ks, ks, ks) * 0.05
+    res = E.Act(torch.randn(B, 64, 64, 64, cout, device=dev).to(dt)) if with_res else None
+    bn = (torch.ones(cout), torch.zeros(cout), torch.zeros(cout), torch.ones(cout)) if k7 else None
     b = E.PlanBuilder(dev, dt)
-    b.conv(E.Act(x), w, None, None, stride=1, pad=1, relu=True, residual=res if with_res else None)
+    b.conv(E.Act(x), w, torch.zeros(cout) if k7 else None, bn, stride=1, pad=ks // 2, relu=True, residual=res)
     plan = b.finish()
     for _ in range(3):
         plan.run_eager(st)
@@ -47,11 +59,18 @@ def main():
     r = buf.reshape(-1, 8)
     r = r[r[:, 7] > 0]
     nt = r[:, 7].mean()
-    names = ["total", "wait+barrier", "halo issue / tile setup", "res issue", "tap loop (+ deferred epilogue)", "barrier", "epilogue / bookkeeping"]
-    kern = "persistent" if os.environ.get("LT_HALO_NO_COL") else "column-walk"
-    print(kern + (" [" + " ".join(EXTRA) + "]" if EXTRA else "") + " 3^3 32->32 @64^3 B=%d: %.0f us, %d workgroups sampled, %.1f tiles each" % (B, us, len(r), nt))
+    if k7:
+        kern, layer, names = "one-tile" if os.environ.get("LT_HALO_NO_COL7") else "column-walk", "7^3 32->16", NAMES7
+    else:
+        kern, layer, names = "persistent" if os.environ.get("LT_HALO_NO_COL") else "column-walk", "3^3 32->32", NAMES3
+    print(kern + (" [" + " ".join(EXTRA) + "]" if EXTRA else "") + " %s @64^3 B=%d%s: %.0f us, %d workgroups sampled, %.1f tiles each"
+          % (layer, B, " +residual" if with_res else "", us, len(r), nt))
     for k, nm in enumerate(names):
-        print("  %-32s %9.0f cycles/tile" % (nm, r[:, k].mean() / nt))
+        if nm != "-":
+            print("  %-32s %9.0f cycles/tile" % (nm, r[:, k].mean() / nt))
+    if k7:
+        tiles_per_cu = B * 16 * 8 * 8 / 256.0
+        print("  launch time / tiles per CU       %9.2f us/tile  (256 CUs, %.0f tiles each: includes what the stamps cannot see)" % (us / tiles_per_cu, tiles_per_cu))
 
 
 if __name__ == "__main__":
