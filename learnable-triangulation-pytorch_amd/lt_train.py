@@ -2,16 +2,16 @@
 ``record()`` methods -- the same code that records the inference plan -- run against a ``TrainTape`` that EXECUTES every layer
 as it is recorded, in training mode (convolution without a folded BatchNorm -> batch statistics -> normalise + ReLU + residual),
 keeps every launch as a closure over fixed buffers, and records the backward the same way on the first ``run_backward()``; later steps
-REPLAY the two launch lists (DESIGN.md "Training step").  The backward of a layer:
+REPLAY the two launch lists (DESIGN.md "Training step").  The backward of a layer (TrainTape._conv_bwd calls the four methods in this order):
 
-    activation / BatchNorm backward   lt_bn_act_bwd / lt_act_bwd   (csrc/train.hip)
-    bias gradient                     lt_channel_sum
-    weight gradient                   lt_conv_wgrad               (exact-fp32 MFMA, no atomics) on a SIDE stream, behind an event
+    activation / BatchNorm backward   lt_bn_act_bwd / lt_act_bwd   (csrc/train.hip)                                       TrainTape._act_grad
+    bias gradient                     lt_channel_sum                                                                       TrainTape._bias_grad
+    weight gradient                   lt_conv_wgrad               (exact-fp32 MFMA, no atomics) on a SIDE stream, behind an event   TrainTape._weight_grad
     input gradient                    lt_conv_fwd over dY with the weights transposed + flipped (stride 1), as a parity-phase transposed
                                       convolution (stride-2 layers: k=3/p=1 or k=1/p=0 with output_padding 1) or as the strided convolution a
                                       transposed layer is the adjoint of; an already existing gradient of the input rides in as the
-                                      epilogue's residual, so sums over consumers cost no extra pass
-    max pool                          lt_maxpool_bwd
+                                      epilogue's residual, so sums over consumers cost no extra pass                        TrainTape._input_grad
+    max pool                          lt_maxpool_bwd                                                                       TrainTape.maxpool
 
 The weights are live (lt_gather_f32 from the Parameters into each layer's GEMM layout, index maps built at record time), the
 parameter gradients land in one flat arena (contiguous buckets for lt_dist.GradReducer).  fp32 throughout by default (the reference
@@ -25,6 +25,8 @@ gradient only into an input that carries one) -- none at all in front of the fir
 """
 import ctypes as C
 import os
+from dataclasses import dataclass
+from typing import Tuple
 
 import numpy as np
 import torch
@@ -34,6 +36,94 @@ import lt_hip as H
 from lt_staging import PinnedRing
 
 BN_EPS = 1e-5
+
+
+# ---- host logic of a convolution layer's backward: pure functions of shapes (no device, no library) --------------------------------
+@dataclass(frozen=True)
+class WgradGeom:
+    """The weight-gradient GEMM of one layer, dW[r][tap * gath_ch + g] = sum over the pixels of the ROWS operand of rows[pix][r] * gath[pix * stride + tap - pad][g],
+    as lt_conv_wgrad / lt_conv_wgrad_bf16 / lt_conv_wgrad_bf16_nhwc take it.  A convolution has dY in the rows role and its input in the gathered role; a
+    ConvTranspose has them swapped (wgrad_geometry)."""
+    n_img: int
+    gath_dims: Tuple[int, int, int]          # D, H, W of the gathered ("X-role") operand
+    gath_ch: int                             # its channels ...
+    gath_ld: int                             # ... and the stride between its pixels
+    rows_dims: Tuple[int, int, int]          # D, H, W of the rows ("dY-role") operand
+    rows_ch: int
+    rows_ld: int
+    st3: Tuple[int, int, int]
+    pd3: Tuple[int, int, int]
+    ks3: Tuple[int, int, int]
+    ntaps: int
+    cop: int                                 # rows of dW (rows_ch padded as lt_conv_cout_pad does)
+    kp: int                                  # columns of dW = ntaps * gath_ch
+    wrows: int                               # GEMM rows = pixels of the rows operand over all images
+
+    @property
+    def pa_px(self):                         # pixels per image of the rows operand
+        return self.rows_dims[0] * self.rows_dims[1] * self.rows_dims[2]
+
+    @property
+    def pb_px(self):                         # ... of the gathered operand
+        return self.gath_dims[0] * self.gath_dims[1] * self.gath_dims[2]
+
+    def args(self, nhwc=False):
+        """The positional arguments the three weight-gradient entry points share, from ``N`` to ``ntaps`` (include/lt_hip.h); ``nhwc``: with the ``ldx`` that
+        lt_conv_wgrad_bf16_nhwc and its ``_ok`` twin take behind ``Cin``."""
+        return ((self.n_img, *self.gath_dims, self.gath_ch) + ((self.gath_ld,) if nhwc else ()) +
+                (*self.rows_dims, H.i3(self.st3), H.i3(self.pd3), self.rows_ch, self.rows_ld, self.cop, self.kp, self.ntaps))
+
+
+def wgrad_geometry(x_shape, z_shape, w_shape, stride, pad, transposed, dy_channels=None):
+    """WgradGeom of the layer with input ``x_shape`` and output ``z_shape`` (channels-last, [N, D, H, W, C]; the input buffer may be wider than the filter).
+    ``dy_channels``: dY is read through a copy widened with zero channels to that many (dy_pad_channels) -- rows of dW past Cout come out zero."""
+    nd = len(w_shape) - 2
+    st3 = ((1,) + (stride,) * 2) if nd == 2 else (stride,) * 3
+    pd3 = ((0,) + (pad,) * 2) if nd == 2 else (pad,) * 3
+    ks3 = ((1,) + tuple(w_shape[2:])) if nd == 2 else tuple(w_shape[2:])
+    ntaps = ks3[0] * ks3[1] * ks3[2]
+    N, D, Hh, W, cin_buf = x_shape
+    oN, oD, oH, oW, Cout = z_shape
+    if not transposed:
+        dyc = Cout if dy_channels is None else dy_channels
+        cop = E.cout_pad_of(Cout)
+        assert cop >= dyc
+        return WgradGeom(N, (D, Hh, W), cin_buf, cin_buf, (oD, oH, oW), dyc, dyc, st3, pd3, ks3, ntaps, cop, ntaps * cin_buf, oN * oD * oH * oW)
+    # ConvTranspose: out[2 q - p + a] += x[q][ci] W[ci][co][a]  ->  dW[ci][a][co] = sum_q x[q][ci] dY[2 q - p + a][co]: the same
+    # kernel with the layer's INPUT in the role of "dy" (rows = input pixels) and the output gradient in the role of "x"
+    assert dy_channels is None, "a widened dY has another leading dimension than the Cout the gathered role is told"
+    cin_t = w_shape[0]
+    return WgradGeom(oN, (oD, oH, oW), Cout, Cout, (D, Hh, W), cin_t, cin_buf, st3, pd3, ks3, ntaps, E.cout_pad_of(cin_t), ntaps * Cout, N * D * Hh * W)
+
+
+def wgrad_unpack_map(geom, w_shape, transposed):
+    """int32 map from dW [cop][tap * gath_ch + g] into the Parameter's own layout ([Cout, Cin, k..], ConvTranspose [Cin, Cout, k..]: the rows role first either
+    way), flat: parameter.reshape(-1) = dW.reshape(-1)[map].  Drops the padded rows and, for a convolution over a buffer wider than the filter (the stem's
+    3-channel images), the extra input channels."""
+    assert geom.gath_ch == w_shape[1] or not transposed
+    ar = torch.arange(geom.cop * geom.kp, dtype=torch.int32).reshape(geom.cop, geom.kp)
+    imap = ar[:w_shape[0]].reshape(w_shape[0], *geom.ks3, geom.gath_ch)[..., :w_shape[1]].permute(0, 4, 1, 2, 3)
+    return (imap[:, :, 0] if len(w_shape) == 4 else imap).contiguous().reshape(-1)
+
+
+def dy_pad_channels(Cout, act16):
+    """Channels dY is widened to (with zeros) before lt_conv_fwd reads it as an input: a power of two, at least one 16-byte vector per pixel (4 fp32 / 8 bf16
+    channels); ``Cout`` itself when it is one already (17 joints -> 32)."""
+    cmin = 8 if act16 else 4
+    return Cout if (Cout >= cmin and Cout & (Cout - 1) == 0) else max(cmin, 1 << (Cout - 1).bit_length())
+
+
+def input_grad_conv(w_shape, stride, pad, transposed):
+    """The input gradient of a layer as an lt_conv_fwd over dY: (view transform of the weight tensor or None, keyword arguments of the convolution)."""
+    nd = len(w_shape) - 2
+    if not transposed and stride == 1:
+        # correlation with the flipped, transposed filter [Cin, Cout, k..]
+        return (lambda t: t.transpose(0, 1).flip(*range(2, 2 + nd))), dict(stride=1, pad=w_shape[2] - 1 - pad)
+    if not transposed:
+        # the adjoint of a strided convolution is the transposed convolution with the SAME weight tensor read as [in = Cout, out = Cin]
+        return None, dict(stride=2, pad=pad, transposed=True, output_padding=1)
+    # the adjoint of ConvTranspose(weight [Cin, Cout, k..], stride 2) is Conv(stride 2) with that tensor read as [out = Cin, in = Cout]
+    return None, dict(stride=2, pad=pad)
 
 
 class TrainTape(E.Recorder):
@@ -515,11 +605,34 @@ class TrainTape(E.Recorder):
         # what this layer owes: the input's gradient only if the input carries one, the residual's likewise, a parameter's only if it is trainable
         need_dx = self.carries(x)
         w_rg, b_rg = weight.requires_grad, bias is not None and bias.requires_grad
+        dy, dy16 = self._act_grad(dz, z, y_raw, stats, bn, flags, residual, need_dx, w_rg or b_rg)
+        bias_sum, cs_need = self._bias_grad(bias, dy, rows, Cout, deferred=w_rg and self.overlap)
+        # lt_conv_fwd wants a power-of-two channel count on its input: dY widened with zero channels (17 joints -> 32) for the input gradient
+        # (and, in the 16-bit step, for the octet pack of the weight gradient)
+        cpad = dy_pad_channels(Cout, self.act16)
+        widen = cpad != Cout and ((self.act16 and w_rg) or need_dx)
+        dy_in = torch.empty(*dy.shape[:-1], cpad, dtype=self.adt, device=self.device) if widen else dy
+        if widen:
+            ac = self.acode
+            self.do(lambda st: H.check(lib.lt_convert_pad(ac, dy.data_ptr(), ac, dy_in.data_ptr(), rows, Cout, cpad, st), "lt_convert_pad"), "pad")
+        if w_rg:
+            self._weight_grad(x, z, weight, stride, pad, transposed, dy, dy_in, dy16, bias_sum, cs_need)
+        self._grads_ready()
+        if need_dx:          # (skipped where the input carries none: the network input, the output of a frozen part)
+            self._input_grad(x, weight, stride, pad, transposed, dy_in, dy16)
+
+    def _act_grad(self, dz, z, y_raw, stats, bn, flags, residual, need_dx, conv_rg):
+        """Activation / BatchNorm backward of the layer with output ``z``: records lt_bn_act_bwd (gamma / beta gradients, the residual's gradient on the way) or
+        lt_act_bwd, allocates or accumulates into the residual's gradient.  Returns (dy, dy16): the gradient of the convolution's output (None if nobody reads
+        it; ``conv_rg``: the weight or the bias does) and, in the mixed step, its bf16 copy for the input gradient (else None)."""
+        lib = H.lib()
+        Cout = z.shape[-1]
+        rows = z.t.numel() // Cout
         bn_rg = bn is not None and (bn[0].requires_grad or bn[1].requires_grad)
         # dy feeds the input gradient, the weight gradient and the bias gradient; lt_bn_act_bwd writes dres in its apply pass only, lt_act_bwd always writes dy
-        need_dy = need_dx or w_rg or b_rg or bn is None or self.carries(residual) or not bn_rg
+        need_dy = need_dx or conv_rg or bn is None or self.carries(residual) or not bn_rg
         dy = torch.empty(z.t.shape, dtype=self.adt, device=self.device) if need_dy else None
-        dres, acc_res = None, 0
+        dy16, dres, acc_res = None, None, 0
         rp = residual.t if residual is not None else None
         if self.carries(residual):
             dres = self.grad_of(residual)
@@ -535,7 +648,6 @@ class TrainTape(E.Recorder):
                 dgamma = self._grad_view(gamma) if gamma.requires_grad else torch.empty(Cout, dtype=torch.float32, device=self.device)
                 dbeta = self._grad_view(beta) if beta.requires_grad else torch.empty(Cout, dtype=torch.float32, device=self.device)
             self._ws_need(lib.lt_bn_act_bwd_workspace(rows, Cout))
-            dy16 = None
             if self.mixed and not self.act16 and need_dx and Cout >= 4 and Cout & (Cout - 1) == 0:      # the input gradient's bf16 operand on the way
                 dy16 = torch.empty(dy.shape, dtype=torch.bfloat16, device=self.device)
             self.do(lambda st: H.check(lib.lt_bn_act_bwd(dz.data_ptr(), y_raw.t.data_ptr(), H.ptr(rp), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(),
@@ -553,162 +665,124 @@ class TrainTape(E.Recorder):
                 self.do(lambda st: H.check(lib.lt_convert_pad(H.LT_F32, dy32.data_ptr(), H.LT_BF16, dy.data_ptr(), rows, Cout, Cout, st), "lt_convert_pad"), "cast")
             else:
                 self.do(lambda st: H.check(lib.lt_act_bwd(dz.data_ptr(), z.t.data_ptr(), H.ptr(rp), dy.data_ptr(), H.ptr(dres), acc_res, total, flags | self.aflag, st), "lt_act_bwd"))
-        bias_sum = None
-        if bias is not None and bias.requires_grad:
-            db = self._grad_view(bias)
-            cs_need = lib.lt_channel_sum_workspace(rows, Cout)
-            ac = self.acode
-            bias_sum = lambda st, ws: H.check(lib.lt_channel_sum_dt(ac, dy.data_ptr(), rows, Cout, db.data_ptr(), 0, ws, st), "lt_channel_sum")
-            if not (weight.requires_grad and self.overlap):          # (with a side stream: in front of the layer's weight gradient over there -- only Adam reads it)
-                self._ws_need(cs_need)
-                self.do(lambda st, fn=bias_sum: fn(st, self._ws.data_ptr()))          # (fn bound now: the name is cleared below and the closure is replayed later)
-                bias_sum = None
-        nd = weight.dim() - 2
-        st3 = ((1,) + (stride,) * 2) if nd == 2 else (stride,) * 3
-        pd3 = ((0,) + (pad,) * 2) if nd == 2 else (pad,) * 3
-        ks = tuple(weight.shape[2:])
-        ks3 = ((1,) + ks) if nd == 2 else ks
-        taps_all = torch.tensor([(a, b, c, 0) for a in range(ks3[0]) for b in range(ks3[1]) for c in range(ks3[2])], dtype=torch.int32, device=self.device)
-        ntaps = taps_all.shape[0]
-        N, D, Hh, W, cin_buf = x.shape
-        # lt_conv_fwd wants a power-of-two channel count on its input: dY widened with zero channels (17 joints -> 32) for the input gradient
-        # (and, in the 16-bit step, for the octet pack of the weight gradient)
-        dy_in, cpad = dy, Cout
-        if (Cout & (Cout - 1) or Cout < 4) and ((self.act16 and w_rg) or need_dx):
-            cpad = max(4, 1 << (Cout - 1).bit_length())
-            if self.act16:
-                cpad = max(8, cpad)
-            dyp = torch.empty(*dy.shape[:-1], cpad, dtype=self.adt, device=self.device)
-            ac_ = self.acode
-            self.do(lambda st: H.check(lib.lt_convert_pad(ac_, dy.data_ptr(), ac_, dyp.data_ptr(), rows, Cout, cpad, st), "lt_convert_pad"), "pad")
-            dy_in = dyp                     # (dy itself must keep its name: the closures above read it when they are replayed)
-        if weight.requires_grad:
-            # ---- weight gradient: dw[co][tap * Cin + ci] over the GEMM rows of the forward convolution, then into the Parameter's layout
-            if not transposed:
-                cop, kp = E.cout_pad_of(Cout), ntaps * cin_buf
-                a_ptr, b_ptr = dy, x.t
-                geo = (N, D, Hh, W, cin_buf, z.shape[1], z.shape[2], z.shape[3], Cout, Cout)
-                wrows = rows
-                ar = torch.arange(cop * kp, dtype=torch.int32).reshape(cop, kp)
-                imap = ar[:Cout].reshape(Cout, *ks3, cin_buf)[..., :weight.shape[1]].permute(0, 4, 1, 2, 3)
-            else:
-                # ConvTranspose: out[2 q - p + a] += x[q][ci] W[ci][co][a]  ->  dW[ci][a][co] = sum_q x[q][ci] dY[2 q - p + a][co]: the same
-                # kernel with the layer's INPUT in the role of "dy" (rows = input pixels) and the output gradient in the role of "x"
-                cin_t = weight.shape[0]
-                cop, kp = E.cout_pad_of(cin_t), ntaps * Cout
-                a_ptr, b_ptr = x.t, dy
-                oN, oD, oH, oW, _ = z.shape
-                geo = (oN, oD, oH, oW, Cout, D, Hh, W, cin_t, cin_buf)
-                wrows = N * D * Hh * W
-                ar = torch.arange(cop * kp, dtype=torch.int32).reshape(cop, kp)
-                imap = ar[:cin_t].reshape(cin_t, *ks3, Cout).permute(0, 4, 1, 2, 3)
-            imap = (imap[:, :, 0] if nd == 2 else imap).contiguous().reshape(-1).to(self.device)
-            dw = torch.empty(cop, kp, dtype=torch.float32, device=self.device)
-            use16, direct = self.wgrad16, False
-            n_img = geo[0]
-            pa_px, pb_px = geo[5] * geo[6] * geo[7], geo[1] * geo[2] * geo[3]          # pixels per image of the dY-role / X-role tensor
-            if use16:
-                need = lib.lt_conv_wgrad_bf16_workspace((n_img + 7) // 8 * pa_px, cop, kp)
-                pk_need = (lib.lt_pack_n8_bf16_bytes(n_img, pa_px, geo[9]), lib.lt_pack_n8_bf16_bytes(n_img, pb_px, geo[4]))
-                # where the bf16 copy the convolutions read exists already (same layout), the pack reads that: 2 instead of 4 bytes per element
-                if self.act16:          # the activations / gradients are the bf16 operands (dY through its zero-padded copy when Cout % 8)
-                    if cin_buf % 8 or (transposed and Cout % 8):
-                        raise NotImplementedError("train_precision 'act16': a weight gradient over %d input channels" % cin_buf)
-                    if transposed and dy_in is not dy:
-                        # dY was widened to ``cpad`` channels (Cout a multiple of 8 but no power of two): the transposed layer's kernels are told geo[4] = Cout as
-                        # channel count AND leading dimension of the X-role operand, which the widened copy does not have -- silently wrong gradients.
-                        # No layer of V2V / pose_resnet has this shape; refuse it instead of guessing.
-                        raise NotImplementedError("train_precision 'act16': the weight gradient of a transposed convolution with %d output channels "
-                                                  "(not a power of two: dY is read through a zero-padded copy with another leading dimension)" % Cout)
-                    x16, d16 = x.t, dy_in
-                    if not transposed and dy_in is not dy:
-                        geo = geo[:8] + (cpad, cpad)          # Cout, ldy of the widened dY (cout_pad_of(Cout) == cpad rows of dw, the extra ones zero)
-                        assert cop >= cpad
-                    pk_need = (lib.lt_pack_n8_bf16_bytes(n_img, pa_px, geo[9]), lib.lt_pack_n8_bf16_bytes(n_img, pb_px, geo[4]))
-                else:
-                    x16e = self._bf16.get(id(x))
-                    x16 = x16e[1] if x16e is not None and x16e[1].shape == x.t.shape and cin_buf % 8 == 0 else None
-                    d16 = dy16 if (bn is not None and dy16 is not None and Cout % 8 == 0) else None
-                a16, b16 = (d16, x16) if not transposed else (x16, d16)
-                self.keep += [t for t in (a16, b16) if t is not None]
-                # both operands there as channels-last bf16 tensors (always in the 16-bit step) and a shape of the kernel that transposes in registers:
-                # no octet packs (LT_WGRAD16_PACKED=1: the packed kernels everywhere)
-                direct = bool(a16 is not None and b16 is not None and lib.lt_conv_wgrad_bf16_nhwc_ok(
-                    geo[0], geo[1], geo[2], geo[3], geo[4], geo[4], geo[5], geo[6], geo[7], H.i3(st3), H.i3(pd3), geo[8], geo[9], cop, kp, ntaps))
-            else:
-                need = lib.lt_conv_wgrad_workspace(wrows, cop, kp)
-            self.keep += [taps_all, a_ptr, b_ptr, imap, dw]
-            gview = self._grad_view(weight)
-            ng = gview.numel()
-            label = "wgrad %s %s rows %d cout_pad %d K %d" % ("x".join(map(str, weight.shape)), "T" if transposed else "", wrows, cop, kp)
-            # load balance of the two streams: with the convolutions on the bf16 MFMA the main stream's backward (input gradients + BatchNorm)
-            # is shorter than the side stream's fp32 weight gradients, so every k-th weight gradient stays on the main stream
-            self._n_wgrad += 1
-            on_main = self.wgrad_main_every > 0 and self._n_wgrad % self.wgrad_main_every == 0
-            ev = torch.cuda.Event() if (self.overlap and not on_main) else None
-            if bias_sum is not None:
-                need = max(need, cs_need)
-            if ev is None:          # on the main stream: the main stream's workspace (the side stream's may be in use by a concurrent weight gradient)
-                self._ws_need(need)
-            elif self._ws2.numel() < need:
-                self._ws2.record_stream(self.side)          # a side-stream kernel of the recording step may still be using it: not to be handed out before that
-                self._ws2 = torch.empty(int(need), dtype=torch.uint8, device=self.device)
-            if use16 and not direct:
-                pk = self._pk_main if ev is None else self._pk_side
-                for i in range(2):
-                    if pk[i].numel() < pk_need[i]:
-                        if ev is not None:
-                            pk[i].record_stream(self.side)
-                        pk[i] = torch.empty(int(pk_need[i]), dtype=torch.uint8, device=self.device)
+        return dy, dy16
 
-            def wgrad(st):
-                if ev is not None:          # dY (and this layer's BatchNorm / bias gradients) are complete on the main stream: the side stream may go
-                    ev.record(torch.cuda.current_stream(self.device))
-                    self.side.wait_event(ev)
-                    st = self.side.cuda_stream
-                ws = (self._ws if ev is None else self._ws2).data_ptr()
-                if bias_sum is not None:
-                    bias_sum(st, ws)
-                if use16 and direct:
-                    H.check(lib.lt_conv_wgrad_bf16_nhwc(a16.data_ptr(), b16.data_ptr(), taps_all.data_ptr(), dw.data_ptr(), geo[0], geo[1], geo[2], geo[3], geo[4], geo[4],
-                                                        geo[5], geo[6], geo[7], H.i3(st3), H.i3(pd3), geo[8], geo[9], cop, kp, ntaps, 0, ws, st), "lt_conv_wgrad_bf16_nhwc")
-                elif use16:
-                    pk = self._pk_main if ev is None else self._pk_side
-                    for src, src16, dst, px, ch in ((a_ptr, a16, pk[0], pa_px, geo[9]), (b_ptr, b16, pk[1], pb_px, geo[4])):
-                        if src16 is not None:
-                            H.check(lib.lt_pack_n8_from_bf16(src16.data_ptr(), dst.data_ptr(), n_img, px, ch, ch, st), "lt_pack_n8_from_bf16")
-                        else:
-                            H.check(lib.lt_pack_n8_bf16(src.data_ptr(), dst.data_ptr(), n_img, px, ch, ch, st), "lt_pack_n8_bf16")
-                    H.check(lib.lt_conv_wgrad_bf16(pk[0].data_ptr(), pk[1].data_ptr(), taps_all.data_ptr(), dw.data_ptr(), geo[0], geo[1], geo[2], geo[3], geo[4],
-                                                   geo[5], geo[6], geo[7], H.i3(st3), H.i3(pd3), geo[8], geo[9], cop, kp, ntaps, 0, ws, st), "lt_conv_wgrad_bf16")
-                else:
-                    H.check(lib.lt_conv_wgrad(a_ptr.data_ptr(), b_ptr.data_ptr(), taps_all.data_ptr(), dw.data_ptr(), geo[0], geo[1], geo[2], geo[3], geo[4], geo[5],
-                                              geo[6], geo[7], H.i3(st3), H.i3(pd3), geo[8], geo[9], cop, kp, ntaps, 0, ws, st), "lt_conv_wgrad")
-                H.check(lib.lt_gather_f32(dw.data_ptr(), imap.data_ptr(), gview.data_ptr(), ng, st), "lt_gather_f32")      # into the Parameter's layout
-            self.do(wgrad, label)
-        self._grads_ready()
-        # ---- input gradient (skipped where the input carries none: the network input, the output of a frozen part)
-        if not need_dx:
-            return
+    def _bias_grad(self, bias, dy, rows, Cout, deferred):
+        """Bias gradient = channel sums of dy.  Returns (fn(stream, workspace) or None, workspace bytes): ``deferred`` (a side stream and a weight gradient to
+        ride in front of -- only Adam reads the sum) hands the launch back for _weight_grad's closure, otherwise it is recorded here."""
+        if bias is None or not bias.requires_grad:
+            return None, 0
+        lib = H.lib()
+        db = self._grad_view(bias)
+        cs_need = lib.lt_channel_sum_workspace(rows, Cout)
+        ac = self.acode
+        bias_sum = lambda st, ws: H.check(lib.lt_channel_sum_dt(ac, dy.data_ptr(), rows, Cout, db.data_ptr(), 0, ws, st), "lt_channel_sum")
+        if deferred:
+            return bias_sum, cs_need
+        self._ws_need(cs_need)
+        self.do(lambda st: bias_sum(st, self._ws.data_ptr()))
+        return None, 0
+
+    def _weight_grad(self, x, z, weight, stride, pad, transposed, dy, dy_in, dy16, bias_sum, cs_need):
+        """Weight gradient dw[co][tap * Cin + ci] over the GEMM rows of the forward convolution, then into the Parameter's layout: one recorded closure, on the
+        side stream behind an event unless this one stays on the main stream.  ``dy_in`` is ``dy`` or its widened copy, ``dy16`` its bf16 copy if there is one,
+        ``bias_sum`` the bias gradient that rides in front (_bias_grad)."""
+        lib = H.lib()
+        Cout, cin_buf = z.shape[-1], x.shape[-1]
+        widened = dy_in is not dy
+        if self.act16:          # the activations / gradients are the bf16 operands (dY through its zero-padded copy when Cout % 8)
+            if cin_buf % 8 or (transposed and Cout % 8):
+                raise NotImplementedError("train_precision 'act16': a weight gradient over %d input channels" % cin_buf)
+            if transposed and widened:
+                # dY was widened (Cout a multiple of 8 but no power of two): the transposed layer's kernels are told Cout as channel count AND
+                # leading dimension of the X-role operand, which the widened copy does not have -- silently wrong gradients (ADVICE r4).
+                # No layer of V2V / pose_resnet has this shape; refuse it instead of guessing.
+                raise NotImplementedError("train_precision 'act16': the weight gradient of a transposed convolution with %d output channels "
+                                          "(not a power of two: dY is read through a zero-padded copy with another leading dimension)" % Cout)
+        # (the 16-bit step reads the widened dY: its channel count is Cout and ldy of the rows role, the extra rows of dw come out zero)
+        g = wgrad_geometry(x.shape, z.shape, weight.shape, stride, pad, transposed, dy_in.shape[-1] if (self.act16 and widened) else None)
+        a_ptr, b_ptr = (dy, x.t) if not transposed else (x.t, dy)
+        taps_all = torch.tensor([(a, b, c, 0) for a in range(g.ks3[0]) for b in range(g.ks3[1]) for c in range(g.ks3[2])], dtype=torch.int32, device=self.device)
+        imap = wgrad_unpack_map(g, weight.shape, transposed).to(self.device)
+        dw = torch.empty(g.cop, g.kp, dtype=torch.float32, device=self.device)
+        use16, direct, a16, b16, pk_need = self.wgrad16, False, None, None, (0, 0)
+        if use16:
+            need = lib.lt_conv_wgrad_bf16_workspace((g.n_img + 7) // 8 * g.pa_px, g.cop, g.kp)
+            pk_need = (lib.lt_pack_n8_bf16_bytes(g.n_img, g.pa_px, g.rows_ld), lib.lt_pack_n8_bf16_bytes(g.n_img, g.pb_px, g.gath_ch))
+            # where the bf16 copy the convolutions read exists already (same layout), the pack reads that: 2 instead of 4 bytes per element
+            if self.act16:
+                x16, d16 = x.t, dy_in
+            else:
+                x16e = self._bf16.get(id(x))
+                x16 = x16e[1] if x16e is not None and x16e[1].shape == x.t.shape and cin_buf % 8 == 0 else None
+                d16 = dy16 if Cout % 8 == 0 else None
+            a16, b16 = (d16, x16) if not transposed else (x16, d16)
+            self.keep += [t for t in (a16, b16) if t is not None]
+            # both operands there as channels-last bf16 tensors (always in the 16-bit step) and a shape of the kernel that transposes in registers:
+            # no octet packs (LT_WGRAD16_PACKED=1: the packed kernels everywhere)
+            direct = bool(a16 is not None and b16 is not None and lib.lt_conv_wgrad_bf16_nhwc_ok(*g.args(nhwc=True)))
+        else:
+            need = lib.lt_conv_wgrad_workspace(g.wrows, g.cop, g.kp)
+        self.keep += [taps_all, a_ptr, b_ptr, imap, dw]
+        gview = self._grad_view(weight)
+        # load balance of the two streams: with the convolutions on the bf16 MFMA the main stream's backward (input gradients + BatchNorm)
+        # is shorter than the side stream's fp32 weight gradients, so every k-th weight gradient stays on the main stream
+        self._n_wgrad += 1
+        on_main = self.wgrad_main_every > 0 and self._n_wgrad % self.wgrad_main_every == 0
+        ev = torch.cuda.Event() if (self.overlap and not on_main) else None
+        self._wgrad_buffers(max(need, cs_need), (0, 0) if direct else pk_need, ev is not None)
+        geo = g.args(nhwc=direct)
+
+        def wgrad(st):
+            if ev is not None:          # dY (and this layer's BatchNorm / bias gradients) are complete on the main stream: the side stream may go
+                ev.record(torch.cuda.current_stream(self.device))
+                self.side.wait_event(ev)
+                st = self.side.cuda_stream
+            ws = (self._ws if ev is None else self._ws2).data_ptr()
+            if bias_sum is not None:
+                bias_sum(st, ws)
+            if use16 and direct:
+                H.check(lib.lt_conv_wgrad_bf16_nhwc(a16.data_ptr(), b16.data_ptr(), taps_all.data_ptr(), dw.data_ptr(), *geo, 0, ws, st), "lt_conv_wgrad_bf16_nhwc")
+            elif use16:
+                pk = self._pk_main if ev is None else self._pk_side
+                for src, src16, dst, px, ch in ((a_ptr, a16, pk[0], g.pa_px, g.rows_ld), (b_ptr, b16, pk[1], g.pb_px, g.gath_ch)):
+                    if src16 is not None:
+                        H.check(lib.lt_pack_n8_from_bf16(src16.data_ptr(), dst.data_ptr(), g.n_img, px, ch, ch, st), "lt_pack_n8_from_bf16")
+                    else:
+                        H.check(lib.lt_pack_n8_bf16(src.data_ptr(), dst.data_ptr(), g.n_img, px, ch, ch, st), "lt_pack_n8_bf16")
+                H.check(lib.lt_conv_wgrad_bf16(pk[0].data_ptr(), pk[1].data_ptr(), taps_all.data_ptr(), dw.data_ptr(), *geo, 0, ws, st), "lt_conv_wgrad_bf16")
+            else:
+                H.check(lib.lt_conv_wgrad(a_ptr.data_ptr(), b_ptr.data_ptr(), taps_all.data_ptr(), dw.data_ptr(), *geo, 0, ws, st), "lt_conv_wgrad")
+            H.check(lib.lt_gather_f32(dw.data_ptr(), imap.data_ptr(), gview.data_ptr(), gview.numel(), st), "lt_gather_f32")      # into the Parameter's layout
+        self.do(wgrad, "wgrad %s %s rows %d cout_pad %d K %d" % ("x".join(map(str, weight.shape)), "T" if transposed else "", g.wrows, g.cop, g.kp))
+
+    def _wgrad_buffers(self, need, pk_need, side):
+        """Grows the workspace and the two octet-pack buffers of the stream a weight gradient runs on to ``need`` / ``pk_need`` bytes."""
+        if not side:          # on the main stream: the main stream's workspace (the side stream's may be in use by a concurrent weight gradient)
+            self._ws_need(need)
+        elif self._ws2.numel() < need:
+            self._ws2.record_stream(self.side)          # a side-stream kernel of the recording step may still be using it: not to be handed out before that
+            self._ws2 = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+        pk = self._pk_side if side else self._pk_main
+        for i in range(2):
+            if pk[i].numel() < pk_need[i]:
+                if side:
+                    pk[i].record_stream(self.side)
+                pk[i] = torch.empty(int(pk_need[i]), dtype=torch.uint8, device=self.device)
+
+    def _input_grad(self, x, weight, stride, pad, transposed, dy_in, dy16):
+        """Input gradient: lt_conv_fwd over dY in the formulation input_grad_conv picks; a gradient of the input that is already there rides in as the residual."""
         prev = self.grad_of(x)
         dya = E.Act(dy_in)
-        if bn is not None and not self.act16 and dy16 is not None:
+        if dy16 is not None:
             self._bf16[id(dya)] = (dya, dy16)
-        res = E.Act(prev) if prev is not None else None
-        if not transposed and stride == 1:
-            # correlation with the flipped, transposed filter [Cin, Cout, k..]
-            dx = self._live_conv(dya, weight, lambda t: t.transpose(0, 1).flip(*range(2, 2 + nd)), None, stride=1, pad=ks[0] - 1 - pad, residual=res)
-        elif not transposed:
-            assert stride == 2 and all(d % 2 == 0 for d in ((Hh, W) if nd == 2 else (D, Hh, W))), "stride-2 layers need even input sizes"
-            # the adjoint of a strided convolution is the transposed convolution with the SAME weight tensor read as [in = Cout, out = Cin]
-            dx = self._live_conv(dya, weight, None, None, stride=2, pad=pad, transposed=True, output_padding=1, residual=res)
-        else:
-            # the adjoint of ConvTranspose(weight [Cin, Cout, k..], stride 2) is Conv(stride 2) with that tensor read as [out = Cin, in = Cout]
-            dx = self._live_conv(dya, weight, None, None, stride=2, pad=pad, residual=res)
-        g = dx.t
-        if g.shape[-1] != cin_buf:
-            raise RuntimeError("input gradient has %d channels, the activation %d" % (g.shape[-1], cin_buf))
-        self._add_grad(x, g)
+        wt, kw = input_grad_conv(weight.shape, stride, pad, transposed)
+        if kw.get("transposed"):
+            assert stride == 2 and all(d % 2 == 0 for d in x.shape[1 - weight.dim():-1]), "stride-2 layers need even input sizes"
+        dx = self._live_conv(dya, weight, wt, None, residual=E.Act(prev) if prev is not None else None, **kw)
+        if dx.t.shape[-1] != x.shape[-1]:
+            raise RuntimeError("input gradient has %d channels, the activation %d" % (dx.t.shape[-1], x.shape[-1]))
+        self._add_grad(x, dx.t)
 
     # ---- driver ---------------------------------------------------------------------------------------------------------------------
     def seed(self, act, grad):

@@ -225,7 +225,7 @@ class _VolTrainPlan:
             tape.do(lambda s_: H.check(lib.lt_softargmax3d_fwd(logits.t.data_ptr(), coords.data_ptr(), mult, sm, 1, J, kp.data_ptr(), probs.data_ptr(), B, J, V ** 3,
                                                                ws.data_ptr(), s_), "lt_softargmax3d_fwd"))
             self.gl = torch.empty(B, V ** 3, J, dtype=torch.float32, device=device)         # d loss / d logits, channels-last like the logits (fp32 in every
-            tape.seed(logits, self.gl.view(logits.t.shape))                                  # precision: the logits layer stores fp32, TrainTape._conv_bwd rounds its dY once)
+            tape.seed(logits, self.gl.view(logits.t.shape))                                  # precision: the logits layer stores fp32, TrainTape._act_grad rounds its dY once)
         else:
             tape.replay(tape.fwd_ops, self.n_front)
         self.step_id += 1

@@ -8,6 +8,7 @@
     the lt_conv_fwd contract (tests/emul.py), against torch.autograd;
   * the weight-gradient block layout dW[co][tap * Cin + ci] (and the transposed role) and the map that unpacks it into the
     Parameter's own layout, against torch.autograd.
+The geometry, the unpack map, the widening of dY and the choice of the input-gradient formulation are the tape's own (the pure helpers of lt_train).
 What remains for the GPU suite (tests/test_gpu_train.py) is kernel == contract."""
 import numpy as np
 import pytest
@@ -15,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 import lt_engine as E
+import lt_train as T
 from emul import emulate_conv
 
 CASES = [  # nd, Cin, Cout, k, stride, pad, transposed, spatial
@@ -25,9 +27,11 @@ CASES = [  # nd, Cin, Cout, k, stride, pad, transposed, spatial
     (2, 16, 8, 4, 2, 1, True, (3, 4)),
     (3, 8, 8, 3, 1, 1, False, (4, 4, 6)),
     (3, 16, 8, 2, 2, 0, True, (2, 3, 2)),
-    (3, 8, 17, 1, 1, 0, False, (2, 2, 3)),
+    (3, 8, 17, 1, 1, 0, False, (2, 2, 3)),          # 17 joints: dY widened to 32 channels
+    (2, 3, 16, 3, 1, 1, False, (5, 6)),             # the stem: 3-channel images in an 8-channel buffer (cin_buf > Cin)
 ]
 IDS = ["nd%d_%dto%d_k%ds%dp%d%s" % (c[0], c[1], c[2], c[3], c[4], c[5], "_T" if c[6] else "") for c in CASES]
+CIN_BUF = 8          # channels of the narrowest activation buffer the weight-gradient tests hand over (zero channels appended past Cin)
 
 
 def _cl(x):  # N,C,(D),H,W -> N,D,H,W,C
@@ -77,10 +81,9 @@ def test_live_weight_maps_equal_host_packing(case, dtype):
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_input_gradient_formulations(case):
-    """dx of every layer kind through the lt_conv_fwd contract (emulate_conv) with the weights TrainTape would gather."""
+    """dx of every layer kind through the lt_conv_fwd contract (emulate_conv) with the weights TrainTape would gather, over dY widened with zero
+    channels as the tape widens it (17 joints -> 32: a buffer wider than the filter's input channels)."""
     nd, Cin, Cout, k, s, p, tr, sp = case
-    if Cout & (Cout - 1):
-        pytest.skip("the tape pads dY to a power-of-two channel count first (covered on the GPU)")
     g = torch.Generator().manual_seed(11 * Cin + Cout + k)
     N = 2
     x = torch.randn(N, Cin, *sp, generator=g, dtype=torch.float64).requires_grad_(True)
@@ -90,22 +93,36 @@ def test_input_gradient_formulations(case):
     dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
     (y * dy).sum().backward()
     wf = w.float()
-    dyc = _cl(dy.float())
-    if not tr and s == 1:
-        spec = _gathered_spec(wf, lambda t: t.transpose(0, 1).flip(*range(2, 2 + nd)), tuple(dyc.shape), stride=1, pad=k - 1 - p)
-    elif not tr:
-        spec = _gathered_spec(wf, None, tuple(dyc.shape), stride=2, pad=p, transposed=True, output_padding=1)
-    else:
-        spec = _gathered_spec(wf, None, tuple(dyc.shape), stride=2, pad=p)
+    dyc = F.pad(_cl(dy.float()), (0, T.dy_pad_channels(Cout, False) - Cout))
+    wt, kw = T.input_grad_conv(tuple(w.shape), s, p, tr)
+    spec = _gathered_spec(wf, wt, tuple(dyc.shape), **kw)
     dx = _from_cl(emulate_conv(spec, dyc), nd)
     assert dx.shape == x.grad.shape, (dx.shape, x.grad.shape)
     assert float((dx.double() - x.grad).abs().max()) <= 2e-5 * float(x.grad.abs().max())
 
 
+def _wgrad_operands(case, x, dy, w):
+    """The two operands of the layer's weight-gradient GEMM as the 16-bit tape hands them to TrainTape._weight_grad, and its geometry: the input in a buffer
+    of at least CIN_BUF channels, dY widened to dy_pad_channels (both with zero channels appended); ``rows_t`` is the "dy" role (GEMM rows), ``gath_t`` the
+    "x" role (gathered at row * stride + tap - pad) -- dY and the input for a convolution, swapped for a ConvTranspose."""
+    nd, Cin, Cout, k, s, p, tr, sp = case
+    xc, dyc = _cl(x), _cl(dy)                       # N, D, H, W, C
+    z_shape = tuple(dyc.shape)
+    xc = F.pad(xc, (0, max(Cin, CIN_BUF) - Cin))
+    cpad = T.dy_pad_channels(Cout, True)
+    dyc = F.pad(dyc, (0, cpad - Cout))
+    geom = T.wgrad_geometry(tuple(xc.shape), z_shape, tuple(w.shape), s, p, tr, cpad if cpad != Cout else None)
+    rows_t, gath_t = (dyc, xc) if not tr else (xc, dyc)
+    assert tuple(rows_t.shape) == (geom.n_img, *geom.rows_dims, geom.rows_ld) and tuple(gath_t.shape) == (geom.n_img, *geom.gath_dims, geom.gath_ld)
+    assert geom.gath_ld == geom.gath_ch and geom.wrows == geom.n_img * geom.pa_px and geom.kp == geom.ntaps * geom.gath_ch
+    return geom, rows_t[..., :geom.rows_ch], gath_t
+
+
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_weight_gradient_block_layout_and_unpack_map(case):
     """dW[co][tap * Cin + ci] = sum over output pixels of dY[pix][co] * X[pix * stride + tap - pad][ci] (ConvTranspose: the roles of the
-    layer's input and of dY swapped), then the unpack map of TrainTape._conv_bwd -> the Parameter's layout; vs torch.autograd."""
+    layer's input and of dY swapped) over the geometry of lt_train.wgrad_geometry, then lt_train.wgrad_unpack_map -> the Parameter's layout; vs
+    torch.autograd.  The rows of dW that belong to the zero channels of a widened dY are exactly zero."""
     nd, Cin, Cout, k, s, p, tr, sp = case
     g = torch.Generator().manual_seed(5 * Cin + Cout + 2 * k)
     N = 2
@@ -115,17 +132,9 @@ def test_weight_gradient_block_layout_and_unpack_map(case):
     y = conv(x, w, None, stride=s, padding=p)
     dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
     (y * dy).sum().backward()
-    ks3 = (1,) + (k,) * 2 if nd == 2 else (k,) * 3
-    st3 = (1, s, s) if nd == 2 else (s, s, s)
-    pd3 = (0, p, p) if nd == 2 else (p, p, p)
-    xc, dyc = _cl(x), _cl(dy)                       # N, D, H, W, C
-    if not tr:
-        rows_t, gath_t, cr, cg = dyc, xc, Cout, Cin       # "dy" role: rows; "x" role: gathered at row * stride + tap - pad
-    else:
-        rows_t, gath_t, cr, cg = xc, dyc, Cin, Cout
-    cop = E.cout_pad_of(cr)
-    kp = ks3[0] * ks3[1] * ks3[2] * cg
-    dw = torch.zeros(cop, kp, dtype=torch.float64)
+    geom, rows_t, gath_t = _wgrad_operands(case, x, dy, w)
+    ks3, st3, pd3, cr, cg = geom.ks3, geom.st3, geom.pd3, geom.rows_ch, geom.gath_ch
+    dw = torch.zeros(geom.cop, geom.kp, dtype=torch.float64)
     Nn, Dr, Hr, Wr, _ = rows_t.shape
     _, Dg, Hg, Wg, _ = gath_t.shape
     t = 0
@@ -146,14 +155,19 @@ def test_weight_gradient_block_layout_and_unpack_map(case):
                                 continue
                             dw[:cr, t * cg:(t + 1) * cg] += rows_t[:, od, oh, ow, :].t() @ gath_t[:, i_d, i_h, i_w, :]
                 t += 1
-    ar = torch.arange(cop * kp).reshape(cop, kp)
-    if not tr:
-        imap = ar[:Cout].reshape(Cout, *ks3, Cin)[..., :Cin].permute(0, 4, 1, 2, 3)
-    else:
-        imap = ar[:Cin].reshape(Cin, *ks3, Cout).permute(0, 4, 1, 2, 3)
-    imap = (imap[:, :, 0] if nd == 2 else imap).contiguous().reshape(-1)
-    gw = dw.reshape(-1)[imap].reshape(w.shape)
+    if not tr and geom.rows_ch > Cout:
+        assert geom.rows_ch == 32 and float(dw[Cout:].abs().max()) == 0.0
+    imap = T.wgrad_unpack_map(geom, tuple(w.shape), tr)
+    assert imap.dtype == torch.int32 and imap.device.type == "cpu"
+    gw = dw.reshape(-1)[imap.long()].reshape(w.shape)
     assert float((gw - w.grad).abs().max()) <= 1e-10 * float(w.grad.abs().max())
+
+
+def test_dy_pad_channels():
+    """The channel count dY is widened to: a power of two of at least one 16-byte vector per pixel, Cout itself where it is one."""
+    want = {3: (4, 8), 4: (4, 8), 17: (32, 32), 24: (32, 32), 32: (32, 32)}
+    for Cout, (off, on) in want.items():
+        assert T.dy_pad_channels(Cout, False) == off and T.dy_pad_channels(Cout, True) == on, Cout
 
 
 def test_adam_groups_follow_the_reference_config():
@@ -203,16 +217,12 @@ def test_weight_gradient_from_image_octets(case, N):
     y = conv(x, w, None, stride=s, padding=p)
     dy = rd(torch.randn(y.shape, generator=g))
     (y * dy).sum().backward()
-    ks3 = (1,) + (k,) * 2 if nd == 2 else (k,) * 3
-    st3 = (1, s, s) if nd == 2 else (s, s, s)
-    pd3 = (0, p, p) if nd == 2 else (p, p, p)
-    xc, dyc = _cl(x), _cl(dy)
-    rows_t, gath_t, cr, cg = (dyc, xc, Cout, Cin) if not tr else (xc, dyc, Cin, Cout)
+    geom, rows_t, gath_t = _wgrad_operands(case, x, dy, w)
+    ks3, st3, pd3, cr, cg = geom.ks3, geom.st3, geom.pd3, geom.rows_ch, geom.gath_ch
     ro, ga = _pack_n8(rows_t).double(), _pack_n8(gath_t).double()          # [G, D, H, W, C, 8]
     G = ro.shape[0]
     assert G == (N + 7) // 8 and float(ro[-1, ..., (N - 1) % 8 + 1:].abs().sum()) == 0.0          # images past N are zeros
-    kp = ks3[0] * ks3[1] * ks3[2] * cg
-    dw = torch.zeros(cr, kp, dtype=torch.float64)
+    dw = torch.zeros(geom.cop, geom.kp, dtype=torch.float64)
     _, Dr, Hr, Wr, _, _ = ro.shape
     _, Dg, Hg, Wg, _, _ = ga.shape
     t = 0
@@ -226,15 +236,9 @@ def test_weight_gradient_from_image_octets(case, N):
                         for ow in range(Wr):
                             i_w = ow * st3[2] - pd3[2] + c
                             if 0 <= i_d < Dg and 0 <= i_h < Hg and 0 <= i_w < Wg:          # one validity test per OCTET
-                                dw[:, t * cg:(t + 1) * cg] += torch.einsum("gce,gke->ck", ro[:, od, oh, ow], ga[:, i_d, i_h, i_w])
+                                dw[:cr, t * cg:(t + 1) * cg] += torch.einsum("gce,gke->ck", ro[:, od, oh, ow], ga[:, i_d, i_h, i_w])
                 t += 1
-    ar = torch.arange(cr * kp).reshape(cr, kp)
-    if not tr:
-        imap = ar.reshape(Cout, *ks3, Cin).permute(0, 4, 1, 2, 3)
-    else:
-        imap = ar.reshape(Cin, *ks3, Cout).permute(0, 4, 1, 2, 3)
-    imap = (imap[:, :, 0] if nd == 2 else imap).contiguous().reshape(-1)
-    gw = dw.reshape(-1)[imap].reshape(w.shape)
+    gw = dw.reshape(-1)[T.wgrad_unpack_map(geom, tuple(w.shape), tr).long()].reshape(w.shape)
     assert float((gw - w.grad).abs().max()) <= 1e-10 * float(w.grad.abs().max())
 
 
