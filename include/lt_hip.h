@@ -388,6 +388,26 @@ int lt_softargmax2d_bwd(const float* probs, const float* coords, const float* gr
                         int32_t NJ, int32_t h, int32_t w, void* stream);
 int lt_triangulate_dlt_bwd(const float* proj, const float* points, const float* conf, const float* grad_out, float* grad_points, float* grad_conf,
                            int32_t B, int32_t NV, int32_t J, void* stream);
+/* integrate_tensor_2d's backward with a gradient on BOTH outputs: grad_coords N*J,2 (may be NULL: a zero coordinate gradient, bit for bit) and
+ * grad_probs N*J,h,w on the returned heatmaps (may be NULL: the result is then bit-identical to lt_softargmax2d_bwd, which stays as it is).
+ *   softmax:  grad_heatmaps_i = [coordinate term of lt_softargmax2d_bwd] + mult * p_i * (gp_i - sum_k p_k gp_k)
+ *   ReLU:     grad_heatmaps_i = [coordinate term] + mult * [e_i > 0] * gp_i        (the returned heatmaps are relu(mult * h), un-normalised)
+ * Fixed-order sums, no atomics.  LT_ERR_INVALID: probs, coords or grad_heatmaps NULL, both gradients NULL, a size < 1, h * w >= 2^31. */
+int lt_softargmax2d_bwd_full(const float* probs, const float* coords, const float* grad_coords, const float* grad_probs, float mult, int32_t softmax,
+                             float* grad_heatmaps, int32_t NJ, int32_t h, int32_t w, void* stream);
+/* 2D heatmap targets and the heatmap loss of the backbone's own training (the reference's op.py:169-196 and the MSE against its renders); all fp32.
+ * lt_render_gaussians_2d: points n,2 as (x, y) in heatmap pixels, sigmas n,2 -> out n,h,w:
+ *     out[i, y, x] = exp(-((x - px)^2 / sx^2 + (y - py)^2 / sy^2) / 2) / norm,   norm = 2 pi sx sx if normalize else 1
+ *   (sigma_x TWICE in the normaliser, as gaussian_2d_pdf of the reference has it).
+ * lt_heatmap_mse_fwd: pred NJ,h,w contiguous, validity NJ or NULL (= all 1) ->
+ *     terms[i] = validity[i] * sum_xy (pred - G)^2          (G: the render above, never written to memory; the loss is sum(terms) / (h w max(1, sum validity)))
+ *     grad_pred (may be NULL) = 2 validity[i] (pred - G) / (h w max(1, sum validity)), written in the same pass; terms keep their bits either way.
+ *   A heatmap with validity == 0 gets terms = 0 and an all-zero gradient row, and its points / sigmas are NEVER read (a NaN keypoint of a missing
+ *   annotation does not leak).  sum validity is re-added in a fixed order by every workgroup: no host round trip, no atomics, equal bits every call.
+ * LT_ERR_INVALID: a NULL pointer other than validity / grad_pred, a size < 1, h * w >= 2^31.  LT_ERR_UNSUPPORTED: h + w > 8192. */
+int lt_render_gaussians_2d(const float* points, const float* sigmas, float* out, int32_t n, int32_t h, int32_t w, int32_t normalize, void* stream);
+int lt_heatmap_mse_fwd(const float* pred, const float* points, const float* sigmas, const float* validity, int32_t normalize, float* terms,
+                       float* grad_pred, int32_t NJ, int32_t h, int32_t w, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training-step pieces outside the convolutions: what torch.autograd derives in the

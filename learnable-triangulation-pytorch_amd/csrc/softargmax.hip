@@ -931,6 +931,43 @@ __global__ __launch_bounds__(256) void sa2_bwd_kernel(const float* __restrict__ 
     }
 }
 
+// The same backward with a gradient on BOTH outputs of integrate_tensor_2d (lt_softargmax2d_bwd_full): gp is the gradient on the returned heatmaps.
+//   softmax: the returned heatmaps are p:  d L / d h_i = [coordinate term] + mult p_i (gp_i - sum_k p_k gp_k)
+//   ReLU:    the returned heatmaps are e = relu(mult h), un-normalised (op.py:27):  d L / d h_i = [coordinate term] + mult [e_i > 0] gp_i
+// Same grid as sa2_bwd_kernel; every workgroup re-adds sum_k p_k gp_k, as it re-adds S in ReLU mode.  The coordinate term is sa2_bwd_kernel's expression
+// character for character (the build keeps a * b + c unfused), so gp == NULL gives that kernel's bits; gcoords == NULL is a zero coordinate gradient.
+__global__ __launch_bounds__(256) void sa2_bwd_full_kernel(const float* __restrict__ probs, const float* __restrict__ coords, const float* __restrict__ gcoords,
+                                                            const float* __restrict__ gprobs, float mult, int softmax, float* __restrict__ ghm, int h, int w) {
+    __shared__ float red[4];
+    const long long base = (long long)blockIdx.y * h * w;
+    const float X = coords[blockIdx.y * 2], Y = coords[blockIdx.y * 2 + 1];
+    const float gx = gcoords ? gcoords[blockIdx.y * 2] : 0.f, gy = gcoords ? gcoords[blockIdx.y * 2 + 1] : 0.f;
+    const int n = h * w;
+    float invS = 1.f;
+    if (!softmax) {
+        float s = 0.f;
+        for (int i = threadIdx.x; i < n; i += 256) s += probs[base + i];
+        invS = 1.f / block_reduce(s, red, false);
+    }
+    float D = 0.f;
+    if (gprobs && softmax) {
+        float d = 0.f;
+        for (int i = threadIdx.x; i < n; i += 256) d += probs[base + i] * gprobs[base + i];
+        D = block_reduce(d, red, false);
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const int yy = i / w, xx = i - yy * w;
+        const float pi = probs[base + i];
+        const float wgt = softmax ? pi : (pi > 0.f ? invS : 0.f);
+        float g = mult * wgt * (((float)xx - X) * gx + ((float)yy - Y) * gy);
+        if (gprobs) {
+            const float gp = gprobs[base + i];
+            g += softmax ? mult * pi * (gp - D) : (pi > 0.f ? mult * gp : 0.f);
+        }
+        ghm[base + i] = g;
+    }
+}
+
 // the DLT's backward by the formulas above dlt_grad_w / dlt_grad_row: fp64, one lane per (sample, joint)
 __global__ void dlt_bwd_kernel(const float* __restrict__ proj, const float* __restrict__ pts, const float* __restrict__ conf,
                                const float* __restrict__ gout, float* __restrict__ gpts, float* __restrict__ gconf, int B, int NV, int J) {
@@ -967,6 +1004,19 @@ extern "C" int lt_softargmax2d_bwd(const float* probs, const float* coords, cons
     const int bx = (int)((h * w + 255) / 256);
     hipLaunchKernelGGL(sa2_bwd_kernel, dim3(bx < 64 ? bx : 64, NJ), dim3(256), 0, (hipStream_t)stream, probs, coords, grad_coords, mult, softmax, grad_heatmaps, h, w);
     LT_CHECK_LAUNCH("lt_softargmax2d_bwd");
+    return LT_OK;
+}
+
+extern "C" int lt_softargmax2d_bwd_full(const float* probs, const float* coords, const float* grad_coords, const float* grad_probs, float mult, int32_t softmax,
+                                        float* grad_heatmaps, int32_t NJ, int32_t h, int32_t w, void* stream) {
+    LT_REQUIRE(probs && coords && grad_heatmaps, LT_ERR_INVALID, "lt_softargmax2d_bwd_full: null probs, coords or grad_heatmaps");
+    LT_REQUIRE(grad_coords || grad_probs, LT_ERR_INVALID, "lt_softargmax2d_bwd_full: grad_coords and grad_probs are both null (nothing to backpropagate)");
+    LT_REQUIRE(NJ >= 1 && h >= 1 && w >= 1, LT_ERR_INVALID, "lt_softargmax2d_bwd_full: bad shape (NJ %d, h %d, w %d)", NJ, h, w);
+    LT_REQUIRE((int64_t)h * w < 0x80000000LL, LT_ERR_INVALID, "lt_softargmax2d_bwd_full: h * w = %lld does not fit the int32 index of a heatmap", (long long)h * w);
+    const int bx = (int)(((int64_t)h * w + 255) / 256);
+    hipLaunchKernelGGL(sa2_bwd_full_kernel, dim3(bx < 64 ? bx : 64, NJ), dim3(256), 0, (hipStream_t)stream, probs, coords, grad_coords, grad_probs, mult, softmax,
+                       grad_heatmaps, h, w);
+    LT_CHECK_LAUNCH("lt_softargmax2d_bwd_full");
     return LT_OK;
 }
 

@@ -73,6 +73,73 @@ class _VolumetricCEFn(torch.autograd.Function):
         return None, op.sparse_prob_grad(ctx.volumes, idx, (gval * g).contiguous()), None, None
 
 
+class _HeatmapMSEFn(torch.autograd.Function):
+    """lt_heatmap_mse_fwd as one autograd node: loss terms and d loss / d heatmaps out of ONE pass over the prediction (the Gaussian targets are never
+    written to memory); backward scales the stored gradient by the upstream scalar on the device.  Keypoints, sigmas and validity get no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, points, sigmas, validity, normalize):
+        h, w = pred.shape[-2:]
+        pr = pred.float().contiguous()
+        NJ = pr.numel() // (h * w)
+        terms = torch.empty(NJ, dtype=torch.float32, device=pr.device)
+        need = ctx.needs_input_grad[0]
+        grad = torch.empty_like(pr) if need else None
+        with torch.cuda.device(pr.device):
+            H.check(H.lib().lt_heatmap_mse_fwd(pr.data_ptr(), points.data_ptr(), sigmas.data_ptr(), validity.data_ptr(), int(bool(normalize)), terms.data_ptr(),
+                                               H.ptr(grad), NJ, h, w, H.cur_stream()), "lt_heatmap_mse_fwd")
+        if need:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = pred.dtype
+        return terms.sum() / (h * w * torch.clamp(validity.sum(), min=1))
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.saved_tensors:
+            return None, None, None, None, None
+        (grad,) = ctx.saved_tensors
+        return (grad * g).to(ctx.in_dtype), None, None, None, None
+
+
+class HeatmapMSELoss(nn.Module):
+    """The 2D heatmap loss the reference's backbone was trained with: mean squared error between the predicted heatmaps and Gaussians rendered at the
+    ground-truth keypoints (op.render_points_as_2d_gaussians), over the annotated joints:
+
+        sum_ij validity_ij * sum_xy (pred_ij - G_ij)^2 / (h * w * max(1, sum validity))
+
+    forward(heatmaps_pred (..., J, h, w), keypoints_2d_gt (..., J, 2), keypoints_binary_validity (..., J, 1) or (..., J), sigmas=None (..., J, 2)).
+    keypoints_2d_gt are (x, y) IN HEATMAP PIXELS: from image pixels of an (H, W) input, x_hm = x * w / W and y_hm = y * h / H (the inverse of the
+    scaling AlgebraicTriangulationNet applies to its 2D keypoints, triangulation.py:181-184 of the reference).  ``sigma`` (heatmap pixels) is used for
+    both axes of every joint unless ``sigmas`` gives them per joint; ``normalize`` divides the targets by 2 pi sigma_x sigma_x as gaussian_2d_pdf does.
+    A joint with validity 0 contributes exactly nothing and its keypoint is never read -- it may be NaN (a missing annotation).  One liblt_hip launch
+    (lt_heatmap_mse_fwd); the gradient reaches ``heatmaps_pred`` only.  numpy fp64: mvn.utils.multiview.heatmap_mse_2d."""
+
+    def __init__(self, sigma=2.0, normalize=False):
+        super().__init__()
+        self.sigma, self.normalize = float(sigma), bool(normalize)
+
+    def forward(self, heatmaps_pred, keypoints_2d_gt, keypoints_binary_validity, sigmas=None):
+        H.require_gpu(heatmaps_pred, "heatmaps_pred")
+        dev = heatmaps_pred.device
+        if heatmaps_pred.dim() < 3:
+            raise ValueError("heatmaps_pred must be (..., J, h, w), got %s" % (tuple(heatmaps_pred.shape),))
+        lead = tuple(heatmaps_pred.shape[:-2])
+        NJ = int(torch.Size(lead).numel())
+        if tuple(keypoints_2d_gt.shape) != lead + (2,):
+            raise ValueError("keypoints_2d_gt must be %s, got %s" % (lead + (2,), tuple(keypoints_2d_gt.shape)))
+        if tuple(keypoints_binary_validity.shape) not in (lead, lead + (1,)):
+            raise ValueError("keypoints_binary_validity must be %s or %s, got %s" % (lead + (1,), lead, tuple(keypoints_binary_validity.shape)))
+        pts = keypoints_2d_gt.detach().to(dev, torch.float32).reshape(NJ, 2).contiguous()
+        val = keypoints_binary_validity.detach().to(dev, torch.float32).reshape(NJ).contiguous()
+        if sigmas is None:
+            sg = torch.full((NJ, 2), self.sigma, dtype=torch.float32, device=dev)
+        else:
+            if tuple(sigmas.shape) != lead + (2,):
+                raise ValueError("sigmas must be %s, got %s" % (lead + (2,), tuple(sigmas.shape)))
+            sg = sigmas.detach().to(dev, torch.float32).reshape(NJ, 2).contiguous()
+        return _HeatmapMSEFn.apply(heatmaps_pred, pts, sg, val, self.normalize)
+
+
 class VolumetricCELoss(nn.Module):
     """loss.py:52-80: mean over ALL (sample, joint) pairs of validity * -log(p[nearest voxel to the ground truth] + 1e-6)."""
 

@@ -6,6 +6,8 @@ The nn.Conv2d / nn.BatchNorm2d children are PARAMETER CONTAINERS ONLY: ``record(
 emits liblt_hip launches (implicit-GEMM convolutions on MFMA with BatchNorm, bias, residual and ReLU folded
 into the epilogue, channels-last activations); ``forward`` replays the recorded plan.
 """
+from collections import OrderedDict
+
 import torch
 import torch.nn as nn
 
@@ -135,6 +137,155 @@ class GlobalAveragePoolingHead(nn.Module):
         return o
 
 
+class BackboneTrainPlan:
+    """The training step of a PoseResNet backbone for one input shape (lt_train.TrainTape, recorded once / replayed): images -> heatmap logits
+    (N, J, h, w) and, with the ``alg_confidences`` head, its sigmoid output (N, J).  ``model`` owns the step -- its parameters, ``train_precision``
+    and ``grad_reducer`` are the tape's -- and ``backbone`` is the PoseResNet it runs: ``model.backbone`` for AlgebraicTriangulationNet (whose tail --
+    2D soft-argmax, confidence normalisation, DLT -- runs on the two small outputs as ordinary autograd nodes, mvn.utils.op / multiview), the module
+    itself for PoseResNet's own train() forward.  The two outputs are the seeded ones; the feature map and the ``vol_confidences`` head are computed on
+    the way and handed out without a gradient (``extras``): a layer whose output nobody seeds records no backward and leaves its parameters without one."""
+
+    def __init__(self, model, N, Hh, W, device, backbone=None):
+        self.model, self.N, self.Hh, self.W, self.device = model, N, Hh, W, device
+        self.backbone = model.backbone if backbone is None else backbone
+        self.tape = None
+        self.step_id = 0
+
+    def forward(self, x):
+        import lt_train
+        model, N, Hh, W, device = self.model, self.N, self.Hh, self.W, self.device
+        lib = H.lib()
+        st = torch.cuda.current_stream(device).cuda_stream
+        first = self.tape is None
+        if first:
+            prec = getattr(model, "train_precision", "fp32")
+            if prec not in ("fp32", "bf16", "act16"):
+                raise ValueError("%s.train_precision must be 'fp32', 'bf16' or 'act16' (there is no 3D convolution for 'fp8v2v')" % type(model).__name__)
+            mixed = prec != "fp32"
+            self.tape = tape = lt_train.TrainTape(device, params=list(model.parameters()), reducer=getattr(model, "grad_reducer", None), mixed=mixed, act16=prec == "act16")
+            self.x_in = tape.alloc((N, 1, Hh, W, E.min_cin_of(torch.bfloat16 if mixed else torch.float32)))
+            tape.no_grad(self.x_in)
+        tape = self.tape
+        E.stage_images(x, self.x_in, st)
+        if first:
+            hm, feats, algc, volc = self.backbone.record(tape, self.x_in, want_heatmaps=True)
+            self.hm, self.algc, self.feats, self.volc = hm, algc, feats, volc
+            self.g_hm = torch.empty_like(hm.t)
+            tape.seed(hm, self.g_hm)
+            self.g_conf = None
+            if algc is not None:
+                self.g_conf = torch.empty_like(algc.t)
+                tape.seed(algc, self.g_conf)
+        else:
+            tape.stream = st
+            tape._gather_all("fwd", tape.fwd_jobs)
+            tape.replay(tape.fwd_ops)
+        self.step_id += 1
+        _, _, h, w, J = self.hm.shape
+        hm_out = torch.empty(N, J, h, w, dtype=torch.float32, device=device)
+        H.check(lib.lt_nhwc_to_nchw_f32(H.LT_F32, self.hm.t.data_ptr(), hm_out.data_ptr(), N, J, h * w, J, st), "lt_nhwc_to_nchw_f32")
+        conf_out = self.algc.t.reshape(N, J).clone() if self.algc is not None else torch.empty(0, device=device)
+        return hm_out, conf_out
+
+    def extras(self):
+        """The outputs of the latest forward that carry no gradient: (features (N, C, h, w) fp32, contiguous like the reference's; vol_confidences
+        (N, 32) or None)."""
+        N, _, h, w, Cf = self.feats.shape
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        feats_out = torch.empty(N, Cf, h, w, dtype=torch.float32, device=self.device)
+        H.check(H.lib().lt_nhwc_to_nchw_f32(self.tape.acode, self.feats.t.data_ptr(), feats_out.data_ptr(), N, Cf, h * w, Cf, st), "lt_nhwc_to_nchw_f32")
+        return feats_out, None if self.volc is None else self.volc.t.reshape(N, -1).float().clone()
+
+    def backward(self, g_hm, g_conf):
+        N = self.N
+        _, _, h, w, J = self.hm.shape
+        lib = H.lib()
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        if g_hm is None:
+            H.check(lib.lt_zero(self.g_hm.data_ptr(), self.g_hm.numel() * 4, st), "lt_zero")
+        else:
+            g = g_hm.float().contiguous()
+            H.check(lib.lt_nchw_to_nhwc(H.LT_F32, g.data_ptr(), self.g_hm.data_ptr(), N, J, h * w, J, st), "lt_nchw_to_nhwc")
+        if self.g_conf is not None:
+            if g_conf is None:
+                H.check(lib.lt_zero(self.g_conf.data_ptr(), self.g_conf.numel() * 4, st), "lt_zero")
+            else:
+                self.g_conf.view(N, J).copy_(g_conf.float())
+        pg = self.tape.run_backward()
+        flat = self.tape.arena.clone()          # autograd gets its own copy: the arena is overwritten by the next step
+        off = self.tape.arena.data_ptr()
+        return {p: flat[(v.data_ptr() - off) // 4:(v.data_ptr() - off) // 4 + v.numel()].view(v.shape) for p, v in pg.items()}
+
+
+class BackboneTrainFn(torch.autograd.Function):
+    """The training-mode backbone as ONE autograd node (the counterpart of triangulation._VolTrainFn).  Inputs: (plan, images (N,3,H,W),
+    *parameters); outputs: heatmap logits (N,J,h,w), raw confidences (N,J) (empty without the head)."""
+
+    @staticmethod
+    def forward(ctx, plan, x, *params):
+        ctx.set_materialize_grads(False)
+        with torch.cuda.device(x.device):
+            hm, conf = plan.forward(x)
+        ctx.plan, ctx.step_id, ctx.params = plan, plan.step_id, params
+        if conf.numel() == 0:
+            ctx.mark_non_differentiable(conf)
+        return hm, conf
+
+    @staticmethod
+    def backward(ctx, g_hm, g_conf):
+        plan = ctx.plan
+        if ctx.step_id != plan.step_id:
+            raise RuntimeError("only the LATEST training forward of a shape can be backpropagated (its activations live in the plan's buffers, "
+                               "which a newer forward has overwritten)")
+        with torch.cuda.device(plan.device):
+            pg = plan.backward(g_hm, g_conf)
+        return (None, None) + tuple(pg.get(p) if p.requires_grad else None for p in ctx.params)
+
+
+def backbone_train_step(model, x, backbone=None):
+    """One recorded training forward of ``model``'s backbone on x (N,3,H,W) fp32 contiguous: (plan, heatmap logits (N,J,h,w), raw alg_confidences (N,J)
+    or an empty tensor), both outputs differentiable with respect to ``model``'s parameters.  Everything around the tape that both users share:
+
+    BatchNorm modules in train() use batch statistics (and update the running ones, ``num_batches_tracked`` included); modules left in eval() normalise
+    with their frozen RUNNING STATISTICS (lt_train.TrainTape.conv) -- that alone freezes no parameter.  Frozen PARAMETERS are requires_grad_(False): the
+    tape records no gradient for them and no backward in front of the first trainable layer (both are in the plan key).  ``model.grad_reducer`` gets
+    DistributedDataParallel's semantics; ``model.train_precision`` picks the tape's precision; at most two plans per model are kept (LRU)."""
+    bns = [c for c in model.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm) and c.training]
+    if any(c.momentum is None or abs(c.momentum - 0.1) > 1e-12 or not c.track_running_stats or not c.affine for c in bns):
+        raise NotImplementedError("BatchNorm with a momentum other than 0.1, without running statistics or without affine parameters")
+    params = tuple(model.parameters())
+    device = x.device
+    off = [n for n, t in list(model.named_parameters()) + list(model.named_buffers()) if t.device != device]
+    if off:
+        raise RuntimeError("training updates the parameters where they live: move the model to %s first (model.to(device), as "
+                           "train.py:424 does); %d tensors are elsewhere, e.g. %s" % (device, len(off), off[0]))
+    N, _, Hh, W = x.shape
+    red = getattr(model, "grad_reducer", None)
+    if red is not None:          # DistributedDataParallel's semantics, as in the volumetric model
+        if not red.attached:
+            red.attach(model)
+        else:
+            red.sync_buffers()
+        model.__dict__["_buffers_stale"] = True          # this step updates the running statistics per rank: the next eval forward re-syncs
+    key = (N, Hh, W, device, tuple(p.requires_grad for p in params), id(red), getattr(model, "train_precision", "fp32"),
+           tuple(c.training for c in model.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm)))
+    plans = model.__dict__.setdefault("_train_plans", OrderedDict())
+    plan = plans.get(key)
+    if plan is None:
+        while len(plans) >= 2:
+            plans.popitem(last=False)
+        plan = plans[key] = BackboneTrainPlan(model, N, Hh, W, device, backbone=backbone)
+    plans.move_to_end(key)
+    hm, conf_raw = BackboneTrainFn.apply(plan, x, *params)
+    nbt = [c.num_batches_tracked for c in bns]
+    tab_key = tuple(t.data_ptr() for t in nbt)
+    tab = model.__dict__.get("_nbt_table")
+    if tab is None or tab[0] != tab_key:
+        tab = model.__dict__["_nbt_table"] = (tab_key, torch.tensor(tab_key, dtype=torch.int64).to(device))
+    H.check(H.lib().lt_add_i64_multi(tab[1].data_ptr(), len(nbt), 1, torch.cuda.current_stream(device).cuda_stream), "lt_add_i64_multi")
+    return plan, hm, conf_raw
+
+
 class PoseResNet(E.PlanCache):
     def __init__(self, block_kind, layers, num_joints, num_input_channels=3, deconv_with_bias=False, num_deconv_layers=3,
                  num_deconv_filters=(256, 256, 256), num_deconv_kernels=(4, 4, 4), final_conv_kernel=1,
@@ -224,12 +375,22 @@ class PoseResNet(E.PlanCache):
 
     # ---- stand-alone forward (reference :293-318) --------------------------------------------
     def forward(self, x):
-        """x: (N,3,H,W) fp32 on the GPU -> (heatmaps (N,J,h,w), features (N,256,h,w), alg_confidences, vol_confidences)."""
+        """x: (N,3,H,W) fp32 on the GPU -> (heatmaps (N,J,h,w), features (N,256,h,w), alg_confidences, vol_confidences).
+
+        In train() the module runs its recorded training step (BackboneTrainPlan: batch-statistics BatchNorm, running statistics updated, liblt_hip
+        backward) and returns the same 4-tuple: ``heatmaps`` are the raw logits and differentiable -- train them with loss.HeatmapMSELoss -- and so are
+        the ``alg_confidences`` when the head exists.  ``features`` and ``vol_confidences`` are returned WITHOUT a grad_fn: nothing in the 2D training of
+        the reference puts a loss on them, and parameters that feed only them (the vol_confidences head) end the step with ``grad is None``, as autograd
+        leaves parameters no loss depends on.  Only the latest forward of a shape can be backpropagated.  ``train_precision`` ('fp32' / 'bf16' / 'act16'),
+        ``grad_reducer`` and requires_grad_(False) work as on AlgebraicTriangulationNet (backbone_train_step)."""
         H.require_gpu(x, "images")
         if self.training:
-            raise NotImplementedError("training runs through VolumetricTriangulationNet, whose step is recorded as a whole (lt_train.py); "
-                                      "the stand-alone forward of this module is inference only: call .eval()")
-        key = (tuple(x.shape), self.compute_dtype, x.device)
+            xs = x if x.dtype == torch.float32 and x.is_contiguous() else x.float().contiguous()
+            plan, hm, conf_raw = backbone_train_step(self, xs, backbone=self)
+            with torch.cuda.device(x.device):
+                feats, volc = plan.extras()
+            return hm, feats, (conf_raw if conf_raw.numel() else None), volc
+        key =(tuple(x.shape), self.compute_dtype, x.device)
         N, _, Hh, W = x.shape
 
         def build():

@@ -315,96 +315,8 @@ class _VolTrainFn(torch.autograd.Function):
         return (None, None, None) + grads
 
 
-class _AlgTrainPlan:
-    """The training step of AlgebraicTriangulationNet's backbone for one input shape (lt_train.TrainTape, recorded once / replayed): images ->
-    heatmap logits (N, J, h, w) and, with ``use_confidences``, the alg_confidences head's sigmoid output (N, J).  The tail of the model -- 2D
-    soft-argmax, confidence normalisation, DLT -- runs on these two small tensors as ordinary autograd nodes (mvn.utils.op / multiview)."""
-
-    def __init__(self, model, N, Hh, W, device):
-        self.model, self.N, self.Hh, self.W, self.device = model, N, Hh, W, device
-        self.tape = None
-        self.step_id = 0
-
-    def forward(self, x):
-        import lt_train
-        model, N, Hh, W, device = self.model, self.N, self.Hh, self.W, self.device
-        lib = H.lib()
-        st = torch.cuda.current_stream(device).cuda_stream
-        first = self.tape is None
-        if first:
-            prec = getattr(model, "train_precision", "fp32")
-            if prec not in ("fp32", "bf16", "act16"):
-                raise ValueError("AlgebraicTriangulationNet.train_precision must be 'fp32', 'bf16' or 'act16' (there is no 3D convolution for 'fp8v2v')")
-            mixed = prec != "fp32"
-            self.tape = tape = lt_train.TrainTape(device, params=list(model.parameters()), reducer=getattr(model, "grad_reducer", None), mixed=mixed, act16=prec == "act16")
-            self.x_in = tape.alloc((N, 1, Hh, W, E.min_cin_of(torch.bfloat16 if mixed else torch.float32)))
-            tape.no_grad(self.x_in)
-        tape = self.tape
-        E.stage_images(x, self.x_in, st)
-        if first:
-            hm, _, algc, _ = model.backbone.record(tape, self.x_in, want_heatmaps=True)
-            self.hm, self.algc = hm, algc
-            self.g_hm = torch.empty_like(hm.t)
-            tape.seed(hm, self.g_hm)
-            self.g_conf = None
-            if algc is not None:
-                self.g_conf = torch.empty_like(algc.t)
-                tape.seed(algc, self.g_conf)
-        else:
-            tape.stream = st
-            tape._gather_all("fwd", tape.fwd_jobs)
-            tape.replay(tape.fwd_ops)
-        self.step_id += 1
-        _, _, h, w, J = self.hm.shape
-        hm_out = torch.empty(N, J, h, w, dtype=torch.float32, device=device)
-        H.check(lib.lt_nhwc_to_nchw_f32(H.LT_F32, self.hm.t.data_ptr(), hm_out.data_ptr(), N, J, h * w, J, st), "lt_nhwc_to_nchw_f32")
-        conf_out = self.algc.t.reshape(N, J).clone() if self.algc is not None else torch.empty(0, device=device)
-        return hm_out, conf_out
-
-    def backward(self, g_hm, g_conf):
-        N = self.N
-        _, _, h, w, J = self.hm.shape
-        lib = H.lib()
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        if g_hm is None:
-            H.check(lib.lt_zero(self.g_hm.data_ptr(), self.g_hm.numel() * 4, st), "lt_zero")
-        else:
-            g = g_hm.float().contiguous()
-            H.check(lib.lt_nchw_to_nhwc(H.LT_F32, g.data_ptr(), self.g_hm.data_ptr(), N, J, h * w, J, st), "lt_nchw_to_nhwc")
-        if self.g_conf is not None:
-            if g_conf is None:
-                H.check(lib.lt_zero(self.g_conf.data_ptr(), self.g_conf.numel() * 4, st), "lt_zero")
-            else:
-                self.g_conf.view(N, J).copy_(g_conf.float())
-        pg = self.tape.run_backward()
-        flat = self.tape.arena.clone()          # autograd gets its own copy: the arena is overwritten by the next step
-        off = self.tape.arena.data_ptr()
-        return {p: flat[(v.data_ptr() - off) // 4:(v.data_ptr() - off) // 4 + v.numel()].view(v.shape) for p, v in pg.items()}
-
-
-class _AlgTrainFn(torch.autograd.Function):
-    """The training-mode backbone of AlgebraicTriangulationNet as ONE autograd node (the counterpart of _VolTrainFn).  Inputs: (plan, images
-    (N,3,H,W), *parameters); outputs: heatmap logits (N,J,h,w), raw confidences (N,J) (empty without the head)."""
-
-    @staticmethod
-    def forward(ctx, plan, x, *params):
-        ctx.set_materialize_grads(False)
-        with torch.cuda.device(x.device):
-            hm, conf = plan.forward(x)
-        ctx.plan, ctx.step_id, ctx.params = plan, plan.step_id, params
-        if conf.numel() == 0:
-            ctx.mark_non_differentiable(conf)
-        return hm, conf
-
-    @staticmethod
-    def backward(ctx, g_hm, g_conf):
-        plan = ctx.plan
-        if ctx.step_id != plan.step_id:
-            raise RuntimeError("only the LATEST training forward of a shape can be backpropagated (its activations live in the plan's buffers, "
-                               "which a newer forward has overwritten)")
-        with torch.cuda.device(plan.device):
-            pg = plan.backward(g_hm, g_conf)
-        return (None, None) + tuple(pg.get(p) if p.requires_grad else None for p in ctx.params)
+# the backbone's recorded training step (one plan class for this module's AlgebraicTriangulationNet and for PoseResNet's own train() forward)
+_AlgTrainPlan, _AlgTrainFn = pose_resnet.BackboneTrainPlan, pose_resnet.BackboneTrainFn
 
 
 class _PlannedNet(E.PlanCache):
@@ -918,47 +830,20 @@ class AlgebraicTriangulationNet(_PlannedNet):
         Training mode (round 3; the reference's loop for model_type "alg", train.py:189-236): the backbone -- heatmap head and, with
         ``use_confidences``, the alg_confidences head included -- runs its recorded training step (lt_train.TrainTape: batch-statistics
         BatchNorm, liblt_hip backward); 2D soft-argmax, confidence normalisation and the DLT are autograd nodes over liblt_hip kernels
-        (lt_softargmax2d_bwd, lt_triangulate_dlt_bwd: what autograd derives through torch.svd in the reference).  Same 4-tuple as inference."""
+        (lt_softargmax2d_bwd, lt_triangulate_dlt_bwd: what autograd derives through torch.svd in the reference).  Same 4-tuple as inference; the returned
+        heatmaps (after softmax / ReLU) are differentiable too -- an auxiliary loss.HeatmapMSELoss on them trains through lt_softargmax2d_bwd_full, a
+        loss that leaves them alone backpropagates through lt_softargmax2d_bwd exactly as before."""
         # BatchNorm modules in train() use batch statistics (and update the running ones); modules left in eval() normalise with their frozen
         # RUNNING STATISTICS (round 3; lt_train.TrainTape.conv) -- that alone freezes no parameter.  Frozen PARAMETERS are requires_grad_(False): the tape
         # records no gradient for them and no backward in front of the first trainable layer (both are in the plan key below)
-        bns = [c for c in self.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm) and c.training]
-        if any(c.momentum is None or abs(c.momentum - 0.1) > 1e-12 or not c.track_running_stats or not c.affine for c in bns):
-            raise NotImplementedError("BatchNorm with a momentum other than 0.1, without running statistics or without affine parameters")
-        params = tuple(self.parameters())
-        off = [n for n, t in list(self.named_parameters()) + list(self.named_buffers()) if t.device != images.device]
-        if off:
-            raise RuntimeError("training updates the parameters where they live: move the model to %s first (model.to(device), as "
-                               "train.py:424 does); %d tensors are elsewhere, e.g. %s" % (images.device, len(off), off[0]))
+        # (the plan cache, the reducer, the num_batches_tracked bump: pose_resnet.backbone_train_step, shared with PoseResNet's own train() forward)
         device = images.device
         B, NV = images.shape[:2]
         Hh, W = images.shape[3:]
-        red = getattr(self, "grad_reducer", None)
-        if red is not None:          # DistributedDataParallel's semantics, as in the volumetric model
-            if not red.attached:
-                red.attach(self)
-            else:
-                red.sync_buffers()
-            self.__dict__["_buffers_stale"] = True          # this step updates the running statistics per rank: the next eval forward re-syncs
-        key = (B * NV, Hh, W, device, tuple(p.requires_grad for p in params), id(red), getattr(self, "train_precision", "fp32"),
-               tuple(c.training for c in self.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm)))
-        plans = self.__dict__.setdefault("_train_plans", OrderedDict())
-        plan = plans.get(key)
-        if plan is None:
-            while len(plans) >= 2:
-                plans.popitem(last=False)
-            plan = plans[key] = _AlgTrainPlan(self, B * NV, Hh, W, device)
-        plans.move_to_end(key)
         x = images.reshape(B * NV, 3, Hh, W)
         if x.dtype != torch.float32 or not x.is_contiguous():
             x = x.float().contiguous()
-        hm, conf_raw = _AlgTrainFn.apply(plan, x, *params)
-        nbt = [c.num_batches_tracked for c in bns]
-        tab_key = tuple(t.data_ptr() for t in nbt)
-        tab = self.__dict__.get("_nbt_table")
-        if tab is None or tab[0] != tab_key:
-            tab = self.__dict__["_nbt_table"] = (tab_key, torch.tensor(tab_key, dtype=torch.int64).to(device))
-        H.check(H.lib().lt_add_i64_multi(tab[1].data_ptr(), len(nbt), 1, torch.cuda.current_stream(device).cuda_stream), "lt_add_i64_multi")
+        _, hm, conf_raw = pose_resnet.backbone_train_step(self, x)
         N, J, h, w = hm.shape
         kp2d, heatmaps = op.integrate_tensor_2d(hm * self.heatmap_multiplier, self.heatmap_softmax)      # reference :158
         conf = conf_raw.reshape(B, NV, J) if conf_raw.numel() else torch.ones(B, NV, J, dtype=torch.float32, device=device)

@@ -224,6 +224,66 @@ def heatmap_stats_2d(heatmaps, mult=1.0, softmax=True, coords=None):
     return peak.reshape(lead), idx.reshape(lead), mass.reshape(lead), cov.reshape(lead + (2, 2))
 
 
+# ---- the numpy fp64 statement of the 2D heatmap targets, the heatmap loss and the soft-argmax backward with both gradients (CPU only) -----------------
+def render_gaussians_2d(points, sigmas, image_shape, normalize=True):
+    """The numpy fp64 statement of liblt_hip's ``lt_render_gaussians_2d`` (op.render_points_as_2d_gaussians; the reference's op.py:169-196).
+
+    points (n, 2) as (x, y) in heatmap pixels, sigmas (n, 2), image_shape (h, w) -> (n, h, w) fp64:
+      G[i, y, x] = exp(-((x - px)^2 / sx^2 + (y - py)^2 / sy^2) / 2) / norm,   norm = 2 pi sx sx if normalize else 1
+    sigma_x TWICE in the normaliser: what gaussian_2d_pdf of the reference computes (op.py:172), kept."""
+    pts, sg = np.asarray(points, dtype=np.float64).reshape(-1, 2), np.asarray(sigmas, dtype=np.float64).reshape(-1, 2)
+    h, w = image_shape
+    x, y = np.arange(w, dtype=np.float64)[None, None, :], np.arange(h, dtype=np.float64)[None, :, None]
+    px, py, sx, sy = (a[:, None, None] for a in (pts[:, 0], pts[:, 1], sg[:, 0], sg[:, 1]))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        g = np.exp(-((x - px) ** 2 / sx ** 2 + (y - py) ** 2 / sy ** 2) / 2)
+        return g / (2 * np.pi * sx * sx) if normalize else g
+
+
+def heatmap_mse_2d(pred, points, sigmas, validity=None, normalize=False):
+    """The numpy fp64 statement of liblt_hip's ``lt_heatmap_mse_fwd`` (loss.HeatmapMSELoss).
+
+    pred (NJ, h, w), points / sigmas (NJ, 2), validity (NJ,) or None (all 1).  With G = render_gaussians_2d(points, sigmas, (h, w), normalize):
+      terms[i] = validity[i] * sum_xy (pred[i] - G[i])^2,   loss = sum(terms) / (h w max(1, sum validity)),
+      grad[i]  = 2 validity[i] (pred[i] - G[i]) / (h w max(1, sum validity))          (d loss / d pred)
+    A heatmap with validity == 0 contributes exactly 0 to both and its points / sigmas are not looked at (they may be NaN) -- unlike the tensor
+    expression validity * (pred - G)^2, where 0 * NaN poisons the sum.  Returns (loss, terms (NJ,), grad (NJ, h, w)) in fp64."""
+    p = np.asarray(pred, dtype=np.float64)
+    NJ, h, w = p.shape
+    v = np.ones(NJ) if validity is None else np.asarray(validity, dtype=np.float64).reshape(NJ)
+    on = v != 0
+    diff = np.zeros_like(p)
+    if on.any():
+        diff[on] = p[on] - render_gaussians_2d(np.asarray(points).reshape(NJ, 2)[on], np.asarray(sigmas).reshape(NJ, 2)[on], (h, w), normalize)
+    den = h * w * max(1.0, float(v.sum()))
+    terms = v * (diff ** 2).sum(axis=(1, 2))
+    return float(terms.sum() / den), terms, 2.0 * v[:, None, None] * diff / den
+
+
+def softargmax2d_backward(probs, coords, grad_coords=None, grad_probs=None, mult=1.0, softmax=True):
+    """The numpy fp64 statement of liblt_hip's ``lt_softargmax2d_bwd_full``: d L / d heatmaps of op.integrate_tensor_2d given the gradients on its two
+    outputs.  probs (NJ, h, w) and coords (NJ, 2) are the forward's outputs; grad_coords (NJ, 2) or None (zero), grad_probs (NJ, h, w) or None (zero).
+      softmax:  dh_i = mult p_i ((c_i - coords) . g) + mult p_i (gp_i - sum_k p_k gp_k)
+      ReLU:     dh_i = mult [e_i > 0] ((c_i - coords) . g) / sum_k e_k + mult [e_i > 0] gp_i        (the returned heatmaps are e = relu(mult h), op.py:27)"""
+    p = np.asarray(probs, dtype=np.float64)
+    NJ, h, w = p.shape
+    c = np.asarray(coords, dtype=np.float64).reshape(NJ, 2)
+    g = np.zeros((NJ, 2)) if grad_coords is None else np.asarray(grad_coords, dtype=np.float64).reshape(NJ, 2)
+    x, y = np.arange(w, dtype=np.float64)[None, None, :], np.arange(h, dtype=np.float64)[None, :, None]
+    a = (x - c[:, 0, None, None]) * g[:, 0, None, None] + (y - c[:, 1, None, None]) * g[:, 1, None, None]
+    if softmax:
+        out = mult * p * a
+        if grad_probs is not None:
+            gp = np.asarray(grad_probs, dtype=np.float64)
+            out = out + mult * p * (gp - (p * gp).sum(axis=(1, 2), keepdims=True))
+        return out
+    on = p > 0
+    out = mult * np.where(on, a / p.sum(axis=(1, 2), keepdims=True), 0.0)
+    if grad_probs is not None:
+        out = out + mult * np.where(on, np.asarray(grad_probs, dtype=np.float64), 0.0)
+    return out
+
+
 def _dlt_rows(P, pts, conf):
     """A (2 n, 4) of one joint: rows c_v (x_{v,r} P_v[2, :] - P_v[r, :])."""
     A = np.empty((2 * len(P), 4))

@@ -343,11 +343,14 @@ def _softargmax2d_launch(heatmaps, softmax, with_stats=False):
 
 
 class _SoftArgmax2dFn(torch.autograd.Function):
-    """lt_softargmax2d_fwd / _bwd as one node (the algebraic model's training, train.py:189-236): the gradient of the coordinates reaches the
-    heatmaps; a gradient on the returned (softmaxed) heatmaps is refused -- no loss of the reference uses them."""
+    """lt_softargmax2d_fwd / _bwd as one node with TWO differentiable outputs (coordinates, heatmaps after softmax / ReLU).  A step whose loss touches
+    the coordinates alone (the algebraic model's training, train.py:189-236) takes lt_softargmax2d_bwd as it always did -- the same launch, the same
+    bits; a gradient on the returned heatmaps (an auxiliary 2D heatmap loss) goes through lt_softargmax2d_bwd_full, with or without one on the
+    coordinates."""
 
     @staticmethod
     def forward(ctx, heatmaps, softmax, stats_out=None):
+        ctx.set_materialize_grads(False)              # an unused output arrives as None in backward: that is how the old entry is chosen
         # stats_out (integrate_tensor_2d_with_stats): a list that receives the statistics of this forward; they are no outputs of the node (no gradient)
         if stats_out is None:
             coords, probs = _softargmax2d_launch(heatmaps, softmax)
@@ -356,23 +359,64 @@ class _SoftArgmax2dFn(torch.autograd.Function):
             stats_out.append(st)
         ctx.save_for_backward(coords, probs)
         ctx.softmax, ctx.in_dtype = bool(softmax), heatmaps.dtype
-        ctx.mark_non_differentiable(probs)
         return coords, probs
 
     @staticmethod
     def backward(ctx, g_coords, g_probs):
         coords, probs = ctx.saved_tensors
+        if g_coords is None and g_probs is None:
+            return None, None, None
         N, J, h, w = probs.shape
-        g = g_coords.float().contiguous()
+        g = None if g_coords is None else g_coords.float().contiguous()
         ghm = torch.empty_like(probs)
-        H.check(H.lib().lt_softargmax2d_bwd(probs.data_ptr(), coords.data_ptr(), g.data_ptr(), 1.0, int(ctx.softmax), ghm.data_ptr(), N * J, h, w,
-                                            H.cur_stream()), "lt_softargmax2d_bwd")
+        if g_probs is None:          # no gradient on the heatmaps: the entry and the launch of every step recorded before they were differentiable
+            H.check(H.lib().lt_softargmax2d_bwd(probs.data_ptr(), coords.data_ptr(), g.data_ptr(), 1.0, int(ctx.softmax), ghm.data_ptr(), N * J, h, w,
+                                                H.cur_stream()), "lt_softargmax2d_bwd")
+        else:
+            gp = g_probs.float().contiguous()
+            H.check(H.lib().lt_softargmax2d_bwd_full(probs.data_ptr(), coords.data_ptr(), H.ptr(g), gp.data_ptr(), 1.0, int(ctx.softmax), ghm.data_ptr(),
+                                                     N * J, h, w, H.cur_stream()), "lt_softargmax2d_bwd_full")
         return ghm.to(ctx.in_dtype), None, None
 
 
+def gaussian_2d_pdf(coords, means, sigmas, normalize=True):
+    """coords, means, sigmas (n, 2) as (x, y) -> (n,) values of the axis-aligned Gaussian.  Reference: op.py:169-175, a plain tensor expression on
+    whatever device the inputs live on (the parity shim; the rendering kernel is behind render_points_as_2d_gaussians).  The normaliser is
+    2 pi sigma_x sigma_x -- sigma_x twice, as in the reference."""
+    normalization = 1.0
+    if normalize:
+        normalization = 2 * np.pi * sigmas[:, 0] * sigmas[:, 0]
+    exp = torch.exp(-((coords[:, 0] - means[:, 0]) ** 2 / sigmas[:, 0] ** 2 + (coords[:, 1] - means[:, 1]) ** 2 / sigmas[:, 1] ** 2) / 2)
+    return exp / normalization
+
+
+def render_points_as_2d_gaussians(points, sigmas, image_shape, normalize=True):
+    """points (n, 2) as (x, y) in pixels of the rendered map, sigmas (n, 2), image_shape (h, w) -> (n, h, w) fp32 Gaussians.  Reference: op.py:178-196.
+    GPU tensors: one lt_render_gaussians_2d launch (the reference materialises an (n, h, w, 2) grid and two repeats); CPU tensors (dataset-side code):
+    the broadcast tensor expression.  No gradient flows to points or sigmas through the GPU path.  numpy fp64: mvn.utils.multiview.render_gaussians_2d."""
+    h, w = int(image_shape[0]), int(image_shape[1])
+    n = points.shape[0]
+    if not points.is_cuda:
+        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+        grid = torch.stack([xx, yy], dim=-1).reshape(1, h * w, 2).expand(n, h * w, 2).reshape(-1, 2)
+        rep = lambda t: t.float()[:, None, :].expand(n, h * w, 2).reshape(-1, 2)
+        return gaussian_2d_pdf(grid, rep(points), rep(sigmas), normalize=normalize).reshape(n, h, w)
+    pts = points.detach().float().contiguous()
+    sg = sigmas.detach().to(points.device, torch.float32).contiguous()
+    if pts.shape != (n, 2) or sg.shape != (n, 2):
+        raise ValueError("render_points_as_2d_gaussians: points and sigmas must be (n, 2), got %s and %s" % (tuple(points.shape), tuple(sigmas.shape)))
+    out = torch.empty(n, h, w, dtype=torch.float32, device=points.device)
+    if n:
+        with torch.cuda.device(points.device):
+            H.check(H.lib().lt_render_gaussians_2d(pts.data_ptr(), sg.data_ptr(), out.data_ptr(), n, h, w, int(bool(normalize)), H.cur_stream()),
+                    "lt_render_gaussians_2d")
+    return out
+
+
 def integrate_tensor_2d(heatmaps, softmax=True):
-    """heatmaps (N,J,h,w) -> (coordinates (N,J,2) as (x,y), heatmaps after softmax / ReLU).  Reference: op.py:11-47.  Differentiable with
-    respect to the heatmaps (through the coordinates) when they require grad."""
+    """heatmaps (N,J,h,w) -> (coordinates (N,J,2) as (x,y), heatmaps after softmax / ReLU).  Reference: op.py:11-47.  When the input requires grad both
+    outputs are differentiable with respect to it: a loss on the coordinates alone takes lt_softargmax2d_bwd (as before the heatmaps were differentiable:
+    same launch, same bits), a gradient on the returned heatmaps lt_softargmax2d_bwd_full."""
     H.require_gpu(heatmaps, "heatmaps")
     if torch.is_grad_enabled() and heatmaps.requires_grad:
         return _SoftArgmax2dFn.apply(heatmaps, softmax)
@@ -381,8 +425,8 @@ def integrate_tensor_2d(heatmaps, softmax=True):
 def integrate_tensor_2d_with_stats(heatmaps, softmax=True):
     """integrate_tensor_2d plus the per-heatmap statistics, out of the same pass that writes the normalised heatmaps (lt_softargmax2d_stats_fwd).  Returns
     (coordinates, heatmaps, (peak (N,J), peak_index (N,J) int32, mass (N,J), covariance (N,J,2,2) in heatmap px^2 about the returned coordinates)): the first
-    two are bit for bit what integrate_tensor_2d returns and differentiable in the same way; the statistics carry no gradient.  The definitions in numpy
-    fp64: mvn.utils.multiview.heatmap_stats_2d."""
+    two are bit for bit what integrate_tensor_2d returns and differentiable in the same way (coordinates and heatmaps both); the statistics carry no
+    gradient.  The definitions in numpy fp64: mvn.utils.multiview.heatmap_stats_2d."""
     H.require_gpu(heatmaps, "heatmaps")
     if torch.is_grad_enabled() and heatmaps.requires_grad:
         out = []
