@@ -302,6 +302,26 @@ int lt_unproject_masked_fwd(int32_t dtype, const void* feats, const float* proj,
 int lt_unproject_grid_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                                  float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask, void* out,
                                  int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream);
+/* Several cuboids per frame: lt_unproject_masked_fwd / lt_unproject_grid_masked_fwd with the views taken through an index.  Cuboid p of the P
+ * reads the maps, projections, confidences and mask of frame frame_of[p] of the F:
+ *   by frame  (F): feats F,NV,h,w,C   proj F,NV,3,4   conf F,NV,C   view_mask F,NV uint8 or NULL = every view valid
+ *   by cuboid (P): coords / coords_out P,v0,v1,v2,3   out P,v0,v1,v2,C   pos, center P,3   rot P,9
+ *   frame_of: DEVICE (P) int32 in [0, F), any order; a frame may have no cuboid.
+ * The result is bit-identical to the masked (view_mask) or unmasked (NULL) entry on feats, proj, conf and view_mask gathered by frame_of, without
+ * the P / F copies of the maps: the kernel choice is the unindexed call's own rule (the fused bf16 kernel for C = 32, 4 or 8 views, view softmax,
+ * bricked volume; a grid call without one runs lt_coord_volumes over the P cuboids first), each kernel as the indexed instantiation of its masked
+ * form.  A workgroup reads its cuboid's frame once, as a scalar, and clamps it into [0, F-1]: an index outside that range cannot make the kernel
+ * read outside feats -- it reads a wrong frame instead; callers check their indices (both plan hosts refuse a bad one before any launch).
+ * With P % 8 == 0 cuboid p is pinned to XCD p % 8 like a sample of the unindexed entries; LT_UNPROJ_PIN=frame (A/B, read per call) pins cuboid p
+ * to XCD frame_of[p] % 8 instead, so that the cuboids of one frame share an L2 (LT_UNPROJ_PIN=cuboid: the default; same bits either way).
+ * frame_of NULL, F < 1 or P < 1: LT_ERR_INVALID; P * chunks >= 2^31 workgroups: LT_ERR_UNSUPPORTED. */
+int lt_unproject_indexed_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                             const int32_t* frame_of, void* out, int32_t F, int32_t P, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0,
+                             int32_t v1, int32_t v2, int32_t agg, void* stream);
+int lt_unproject_grid_indexed_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
+                                  float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask,
+                                  const int32_t* frame_of, void* out, int32_t F, int32_t P, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V,
+                                  int32_t agg, void* stream);
 /* The seam of the cascade (lt_plan_forward_cascade, CascadeTriangulationNet): the pelvis and cuboid algebra of VolumetricTriangulationNet.forward
  * (triangulation.py:284-296) on joints that are already on the device, bit-identical to what the host route writes into a plan's geometry block.
  *   keypoints_3d: DEVICE (B, J, 3) fp32.  kind LT_KIND_MPII: base = joint 6; LT_KIND_COCO: base = (joint 11 + joint 12) / 2, added and halved in fp32.
@@ -959,6 +979,23 @@ int lt_plan_create_cascade(const lt_cascade_plan_config* cfg, const lt_named_ten
 int lt_plan_forward_cascade(lt_plan* plan, const float* images, const double* K_host, const double* R_host, const double* t_host, const double* rot_host,
                             float* keypoints_3d, float* alg_keypoints_3d, float* base_points, float* volumes, float* features, float* coord_volumes,
                             float* vol_confidences, void* stream);
+/* Several cuboids per frame (VolumetricTriangulationNet.forward with batch["cuboid_frame"]): the backbone runs once on the cfg->B frames, and
+ * the gather (lt_unproject_grid_indexed_fwd), V2V and the soft-argmax run on P cuboids, cuboid p over the views of frame cuboid_frame[p].
+ * lt_plan_create_vol_multi: lt_plan_create_vol with cfg->B = the frames F and P >= 1 cuboids.  lt_vol_plan_config and lt_plan_info_t keep their
+ *   layout; lt_plan_info reports the frames.  P < 1 (and every config error of lt_plan_create_vol) is LT_ERR_INVALID before any device call.
+ * lt_plan_forward_vol_multi: images DEVICE (F, NV, 3, H, W) fp32 and the cameras HOST fp64 (F, NV, ...) as for lt_plan_forward_vol, per FRAME;
+ *   cuboid_frame_host HOST (P) int32 in [0, F), any order (a frame may have no cuboid; a value outside is LT_ERR_INVALID before any device call, the
+ *   message names the entry); base_points_host HOST (P, 3) fp64 and rot_host HOST (P, 9) fp64 or NULL, per CUBOID.  Outputs, DEVICE fp32:
+ *   keypoints_3d (P, J, 3) [required]; volumes (P, J, V, V, V); features (F, NV, 32, h, w); coord_volumes (P, V, V, V, 3); vol_confidences
+ *   (F, NV, 32) raw; each NULL as for lt_plan_forward_vol.  The assignment travels with the geometry block's copy, outside the captured graph: a
+ *   new assignment on a captured plan is just another forward.
+ * lt_plan_forward_vol on a multi plan, and lt_plan_forward_vol_multi on any other plan, are LT_ERR_INVALID.  lt_plan_set_view_mask (mask (F, NV):
+ * it applies to every cuboid of its frame) and lt_plan_set_keypoint_stats (P rows) work as on a volumetric plan.  Results are bit-identical to the
+ * Python host's. */
+int lt_plan_create_vol_multi(const lt_vol_plan_config* cfg, int32_t P, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out);
+int lt_plan_forward_vol_multi(lt_plan* plan, const float* images, const double* K_host, const double* R_host, const double* t_host,
+                              const int32_t* cuboid_frame_host, const double* base_points_host, const double* rot_host, float* keypoints_3d,
+                              float* volumes, float* features, float* coord_volumes, float* vol_confidences, void* stream);
 /* Per-sample view masks: mask_host is HOST (B, NV) uint8, non-zero = the view is there, NULL = all valid.  Sample b of every later forward gets what
  * the plan gives for that sample on its valid views alone: the gather skips masked views (lt_unproject_grid_masked_fwd), the algebraic tail normalises
  * the confidences over the valid views and forms the DLT from their rows (lt_alg_tail_masked_fwd: masked confidences are 0); a cascade plan applies the

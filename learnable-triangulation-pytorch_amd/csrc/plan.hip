@@ -290,6 +290,10 @@ struct lt_plan {
     const float* cur_proj = nullptr; void* out_kp2d = nullptr; float* out_hm = nullptr; float* out_conf = nullptr;          // algebraic / RANSAC plans
     // geometry block (fp32): proj B*NV*12 | pos B*3 | center B*3 | rot B*9 -- one H2D copy per forward from a ring of pinned blocks
     float* geo_dev = nullptr; StagingRing geo; size_t n_geo = 0, o_pos = 0, o_cen = 0, o_rot = 0;
+    // several cuboids per frame (lt_plan_create_vol_multi): P > 0 cuboids over the cfg.B frames -- the backbone is recorded at B * NV images, the gather, V2V and
+    // the tail at P; the block is proj B*NV*12 | pos P*3 | center P*3 | rot P*9 | frame_of P int32 (o_fof, in floats).  P == 0: one cuboid per sample.
+    int P = 0; size_t o_fof = 0;
+    int cuboids() const { return P ? P : cfg.B; }
     // results
     Act feats, vol, logits, volc;
     float* coords = nullptr; float* kp = nullptr; float* probs = nullptr; void* sa_ws = nullptr;
@@ -963,10 +967,11 @@ struct lt_plan {
 
     // VolumetricTriangulationNet._build_plan
     int build() {
-        const int B = cfg.B, NV = cfg.NV, V = cfg.volume_size, J = cfg.num_joints;
+        const int F = cfg.B, NV = cfg.NV, V = cfg.volume_size, J = cfg.num_joints;
+        const int B = cuboids();          // the gather, V2V and the tail: per cuboid; the backbone and the features: per frame
         Act f256, no_hm;
         const bool conf_head = cfg.aggregation == LT_AGG_CONF || cfg.aggregation == LT_AGG_CONF_NORM;
-        PL_TRY(record_backbone(B * NV, cfg.H, cfg.W, cfg.num_layers, cfg.style_caffe != 0, conf_head ? "backbone.vol_confidences" : nullptr, false, f256, volc, no_hm));
+        PL_TRY(record_backbone(F * NV, cfg.H, cfg.W, cfg.num_layers, cfg.style_caffe != 0, conf_head ? "backbone.vol_confidences" : nullptr, false, f256, volc, no_hm));
         WT pw; const float* pb;
         PL_TRY(get("process_features.0.weight", pw, 4)); PL_TRY(get_vec("process_features.0.bias", (int)pw.s[0], &pb));
         LT_REQUIRE(pw.s[0] == 32, LT_ERR_UNSUPPORTED, "lt_plan_create_vol: process_features has %d output channels (32)", (int)pw.s[0]);
@@ -975,7 +980,8 @@ struct lt_plan {
         feats.pooled = false;
         hm_h = feats.h; hm_w = feats.w;
         // geometry block + its pinned staging ring
-        n_geo = (size_t)B * NV * 12 + (size_t)B * 15; o_pos = (size_t)B * NV * 12; o_cen = o_pos + 3 * B; o_rot = o_pos + 6 * B;
+        o_pos = (size_t)F * NV * 12; o_cen = o_pos + 3 * B; o_rot = o_pos + 6 * B; o_fof = o_pos + 15 * (size_t)B;
+        n_geo = o_fof + (P ? (size_t)P : 0);
         void* g; PL_TRY(dev_alloc(n_geo * 4, &g)); geo_dev = (float*)g;
         PL_TRY(geo.alloc(n_geo * 4));
         void* c; PL_TRY(dev_alloc((size_t)B * V * V * V * 3 * 4, &c)); coords = (float*)c;
@@ -983,11 +989,14 @@ struct lt_plan {
         const float step = (float)(cfg.cuboid_side / (double)(V - 1));          // float(np.float32(side / (V - 1))): the fp64 quotient rounded once
         {
             const int dt = dtype, agg = cfg.aggregation, cmu = cfg.transfer_cmu_to_human36m ? 1 : 0, h = hm_h, w = hm_w;
-            const size_t op = o_pos, oc = o_cen, orr = o_rot; lt_plan* self = this;
+            const size_t op = o_pos, oc = o_cen, orr = o_rot, of = o_fof; lt_plan* self = this; const bool multi = P > 0;
             const void* fp = feats.p; float* cp = coords; void* vp = vol.p; const float* confp = volc.null() ? nullptr : (const float*)volc.p;
             // the block's address is read when the op runs: a masked plan (lt_plan_set_view_mask, before the first forward) has moved it to a block with the mask behind
             ops.push_back([=](hipStream_t s) {
                 const float* gp = self->geo_dev;
+                if (multi)
+                    return lt_unproject_grid_indexed_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, self->masked ? self->mask_dev : nullptr,
+                                                         (const int32_t*)(gp + of), vp, F, B, NV, 32, h, w, V, agg, s);
                 if (self->masked)
                     return lt_unproject_grid_masked_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, self->mask_dev, vp, B, NV, 32, h, w, V, agg, s);
                 return lt_unproject_grid_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, vp, B, NV, 32, h, w, V, agg, s);
@@ -1001,7 +1010,7 @@ struct lt_plan {
         PL_TRY(dev_alloc(wsb ? wsb : 16, &sa_ws));
         {   // tail op 1: the RETURNED features (B, NV, 32, h, w) fp32, skipped when the caller did not ask for them
             const int dt = dtype, h = hm_h, w = hm_w; const void* fp = feats.p; lt_plan* self = this;
-            ops.push_back([=](hipStream_t s) { return self->out_feats ? lt_nhwc_to_nchw_f32(dt, fp, self->out_feats, B * NV, 32, h * w, 32, s) : LT_OK; });
+            ops.push_back([=](hipStream_t s) { return self->out_feats ? lt_nhwc_to_nchw_f32(dt, fp, self->out_feats, F * NV, 32, h * w, 32, s) : LT_OK; });
         }
         {   // tail op 2: soft-argmax straight into the caller's tensors
             const float mult = (float)cfg.volume_multiplier; const int sm = cfg.volume_softmax ? 1 : 0, cl = logits.planar ? 0 : 1;
@@ -1095,9 +1104,10 @@ struct lt_plan {
     // cuboid position = base - side / 2; rotation about the vertical axis (identity in eval mode); one pinned block, one H2D copy.  base_points_host NULL
     // (cascade plans): the pos / center ranges are left for lt_cuboid_from_keypoints, which the caller enqueues behind the copy.  proj_img (cascade plans,
     // its block of this forward): K [R | t] at IMAGE resolution rounded to fp32, the algebraic stage's proj_matricies_batch.
+    // cuboid_frame (multi plans, checked by the caller): the P frame indices behind the rotations; base_points_host and rot_host are per cuboid there.
     int stage_geometry(const double* K_host, const double* R_host, const double* t_host, const double* base_points_host, const double* rot_host, hipStream_t st,
-                       float* pi = nullptr) {
-        const int B = cfg.B, NV = cfg.NV;
+                       float* pi = nullptr, const int32_t* cuboid_frame = nullptr) {
+        const int B = cfg.B, NV = cfg.NV, NC = cuboids();
         void* blk; PL_TRY(geo.acquire(&blk));
         float* gh = (float*)blk;
         const double sx = (double)hm_w / (double)cfg.W, sy = (double)hm_h / (double)cfg.H;
@@ -1121,13 +1131,14 @@ struct lt_plan {
                 }
         }
         const double half = (double)cfg.cuboid_side / 2.0;
-        for (int b = 0; b < B; ++b) {
+        for (int b = 0; b < NC; ++b) {
             for (int k = 0; k < 3 && base_points_host; ++k) {
                 gh[o_pos + 3 * b + k] = (float)(base_points_host[3 * b + k] - half);
                 gh[o_cen + 3 * b + k] = (float)base_points_host[3 * b + k];
             }
             for (int k = 0; k < 9; ++k) gh[o_rot + 9 * b + k] = rot_host ? (float)rot_host[9 * b + k] : ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f);
         }
+        if (cuboid_frame) memcpy(gh + o_fof, cuboid_frame, (size_t)NC * 4);
         if (masked) memcpy((uint8_t*)(gh + o_mask), mask_cur.data(), (size_t)B * NV);          // rides in the same block: one copy
         PL_HIP(hipMemcpyAsync(geo_dev, gh, n_geo * 4, hipMemcpyHostToDevice, st));
         return geo.commit(st);
@@ -1239,9 +1250,9 @@ int check_alg_config(const lt_alg_plan_config& c, const char* who) {
 }
 
 // a checked configuration + a state dict -> a recorded plan
-int make_vol_plan(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, const char* who, lt_plan** plan_out) {
+int make_vol_plan(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, const char* who, lt_plan** plan_out, int P = 0) {
     lt_plan* p = new lt_plan();
-    p->who = who;
+    p->who = who; p->P = P;
     p->cfg = *cfg;
     p->dtype = cfg->dtype; p->es = cfg->dtype == LT_F32 ? 4 : 2;
     if (!load_state_dict(p, weights, nweights)) { delete p; return LT_ERR_INVALID; }
@@ -1278,8 +1289,31 @@ int make_alg_plan(const lt_alg_plan_config& c, const lt_named_tensor* weights, i
     return LT_OK;
 }
 const char* plan_kind_name(const lt_plan* p) {
-    return p->model == 0 ? "a volumetric plan of lt_plan_create_vol" : p->model == MODEL_CASCADE ? "a cascade plan of lt_plan_create_cascade"
+    return p->model == 0 ? (p->P ? "a multi-cuboid plan of lt_plan_create_vol_multi" : "a volumetric plan of lt_plan_create_vol") : p->model == MODEL_CASCADE ? "a cascade plan of lt_plan_create_cascade"
            : p->model == LT_MODEL_RANSAC ? "an LT_MODEL_RANSAC plan of lt_plan_create_alg" : "an LT_MODEL_ALG plan of lt_plan_create_alg";
+}
+}  // namespace
+
+namespace {
+// the checked forward of a volumetric plan; cuboid_frame: the multi plans' assignment (base_points_host and rot_host per cuboid there), else null
+int forward_vol_any(lt_plan* p, const char* who, const float* images, const double* K_host, const double* R_host, const double* t_host, const int32_t* cuboid_frame,
+                    const double* base_points_host, const double* rot_host, float* keypoints_3d, float* volumes, float* features, float* coord_volumes,
+                    float* vol_confidences, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    bool detour;
+    PL_TRY(p->enter(st, detour));
+    const int B = p->cfg.B, NV = p->cfg.NV, V = p->cfg.volume_size;
+    p->ran = true;
+    PL_TRY(p->stage_geometry(K_host, R_host, t_host, base_points_host, rot_host, st, nullptr, cuboid_frame));
+    p->cur_images = images; p->out_kp = keypoints_3d; p->out_probs = volumes; p->out_feats = features;
+    PL_TRY(p->run(st));
+    if (coord_volumes) PL_HIP(hipMemcpyAsync(coord_volumes, p->coords, (size_t)p->cuboids() * V * V * V * 3 * 4, hipMemcpyDeviceToDevice, st));
+    if (vol_confidences) {
+        LT_REQUIRE(!p->volc.null(), LT_ERR_INVALID, "%s: vol_confidences asked of a plan without the confidence head (aggregation %d)", who, p->cfg.aggregation);
+        PL_HIP(hipMemcpyAsync(vol_confidences, p->volc.p, (size_t)B * NV * 32 * 4, hipMemcpyDeviceToDevice, st));          // RAW sigmoid outputs; 'conf_norm' divides by their sum over views
+    }
+    PL_TRY(p->leave(st, detour));
+    return LT_OK;
 }
 }  // namespace
 
@@ -1296,22 +1330,35 @@ extern "C" int lt_plan_forward_vol(lt_plan* p, const float* images, const double
     LT_REQUIRE(p, LT_ERR_INVALID, "lt_plan_forward_vol: null argument");
     LT_REQUIRE(p->model == 0, LT_ERR_INVALID, "lt_plan_forward_vol: the plan is %s; run it with %s", plan_kind_name(p),
                p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_alg");
+    LT_REQUIRE(!p->P, LT_ERR_INVALID, "lt_plan_forward_vol: the plan is %s; run it with lt_plan_forward_vol_multi", plan_kind_name(p));
     LT_REQUIRE(images && K_host && R_host && t_host && base_points_host && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_vol: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    bool detour;
-    PL_TRY(p->enter(st, detour));
-    const int B = p->cfg.B, NV = p->cfg.NV, V = p->cfg.volume_size;
-    p->ran = true;
-    PL_TRY(p->stage_geometry(K_host, R_host, t_host, base_points_host, rot_host, st));
-    p->cur_images = images; p->out_kp = keypoints_3d; p->out_probs = volumes; p->out_feats = features;
-    PL_TRY(p->run(st));
-    if (coord_volumes) PL_HIP(hipMemcpyAsync(coord_volumes, p->coords, (size_t)B * V * V * V * 3 * 4, hipMemcpyDeviceToDevice, st));
-    if (vol_confidences) {
-        LT_REQUIRE(!p->volc.null(), LT_ERR_INVALID, "lt_plan_forward_vol: vol_confidences asked of a plan without the confidence head (aggregation %d)", p->cfg.aggregation);
-        PL_HIP(hipMemcpyAsync(vol_confidences, p->volc.p, (size_t)B * NV * 32 * 4, hipMemcpyDeviceToDevice, st));          // RAW sigmoid outputs; 'conf_norm' divides by their sum over views
-    }
-    PL_TRY(p->leave(st, detour));
-    return LT_OK;
+    return forward_vol_any(p, "lt_plan_forward_vol", images, K_host, R_host, t_host, nullptr, base_points_host, rot_host, keypoints_3d, volumes, features,
+                           coord_volumes, vol_confidences, stream);
+}
+
+extern "C" int lt_plan_create_vol_multi(const lt_vol_plan_config* cfg, int32_t P, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
+    const char* who = "lt_plan_create_vol_multi";
+    LT_REQUIRE(cfg && weights && plan_out && nweights > 0, LT_ERR_INVALID, "%s: null argument", who);
+    PL_TRY(check_vol_config(cfg, who));
+    LT_REQUIRE(P >= 1, LT_ERR_INVALID, "%s: P %d cuboids (at least 1)", who, P);
+    *plan_out = nullptr;
+    return make_vol_plan(cfg, weights, nweights, who, plan_out, P);
+}
+
+extern "C" int lt_plan_forward_vol_multi(lt_plan* p, const float* images, const double* K_host, const double* R_host, const double* t_host,
+                                         const int32_t* cuboid_frame_host, const double* base_points_host, const double* rot_host, float* keypoints_3d,
+                                         float* volumes, float* features, float* coord_volumes, float* vol_confidences, void* stream) {
+    const char* who = "lt_plan_forward_vol_multi";
+    LT_REQUIRE(p, LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(p->model == 0 && p->P, LT_ERR_INVALID, "%s: the plan is %s; run it with %s", who, plan_kind_name(p),
+               p->model == 0 ? "lt_plan_forward_vol" : p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_alg");
+    LT_REQUIRE(images && K_host && R_host && t_host && cuboid_frame_host && base_points_host && keypoints_3d, LT_ERR_INVALID,
+               "%s: null argument (images, K, R, t, cuboid_frame, base_points and keypoints_3d are required)", who);
+    for (int i = 0; i < p->P; ++i)
+        LT_REQUIRE(cuboid_frame_host[i] >= 0 && cuboid_frame_host[i] < p->cfg.B, LT_ERR_INVALID, "%s: cuboid_frame[%d] = %d, the plan has frames 0 .. %d", who, i,
+                   cuboid_frame_host[i], p->cfg.B - 1);
+    return forward_vol_any(p, who, images, K_host, R_host, t_host, cuboid_frame_host, base_points_host, rot_host, keypoints_3d, volumes, features, coord_volumes,
+                           vol_confidences, stream);
 }
 
 extern "C" int lt_plan_create_alg(const lt_alg_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
@@ -1462,7 +1509,7 @@ extern "C" int lt_plan_set_keypoint_stats(lt_plan* p, float* stats_dev, int32_t*
     lt_plan* v = p->model == MODEL_CASCADE ? p->sub_vol : p;
     if (stats_dev && !v->ks_ws) {
         const int V = v->cfg.volume_size;
-        PL_TRY(v->dev_alloc(lt_softargmax3d_stats_workspace(v->cfg.B, v->cfg.num_joints, (int64_t)V * V * V), &v->ks_ws));
+        PL_TRY(v->dev_alloc(lt_softargmax3d_stats_workspace(v->cuboids(), v->cfg.num_joints, (int64_t)V * V * V), &v->ks_ws));
     }
     v->ks_stats = stats_dev; v->ks_index = peak_index_dev;
     return LT_OK;

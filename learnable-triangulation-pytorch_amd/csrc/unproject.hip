@@ -76,7 +76,14 @@ struct UnprojArgs {
 struct UnprojMaskedArgs : UnprojArgs {
     const uint8_t* mask;  // (B, NV), non-zero = the view is valid
 };
-template <bool MASKED> using UnprojArgsOf = std::conditional_t<MASKED, UnprojMaskedArgs, UnprojArgs>;
+// the indexed entries' kernels (several cuboids per frame): B counts the CUBOIDS; coords, coords_out, out and g_* are indexed by the cuboid p,
+// feats, proj, conf and mask by its frame frame_of[p] < F.  Built on the masked form: a null mask there means every view is valid.
+struct UnprojIndexedArgs : UnprojMaskedArgs {
+    const int32_t* frame_of;  // (B) the frame of every cuboid
+    int F;                    // frames
+};
+template <bool MASKED, bool INDEXED = false>
+using UnprojArgsOf = std::conditional_t<INDEXED, UnprojIndexedArgs, std::conditional_t<MASKED, UnprojMaskedArgs, UnprojArgs>>;
 
 // Brick (bi, bj, bk) of chunk c of a sample.  Raster order (k fastest) makes every 4-voxel i-slab of bricks sweep the WHOLE projected cube in every view:
 // at 8 views the per-slab working set (2.7 MB of feature rows) plus the output stream does not fit the 4 MB L2 of the XCD the sample is pinned to, and the
@@ -114,6 +121,34 @@ __device__ __forceinline__ void sample_chunk_of(const UnprojArgs& a, int& b, int
     }
 }
 
+// The frame of cuboid p: uniform over the workgroup, so it is read into a scalar register; clamped into [0, F-1] (one scalar max, one scalar min), so
+// that no index value can send a load outside the frames' tensors -- the hosts refuse such an index before any launch, this is the second line of defence.
+__device__ __forceinline__ int frame_of_cuboid(const UnprojIndexedArgs& a, int p) {
+    const int f = __builtin_amdgcn_readfirstlane(a.frame_of[p]);
+    return min(max(f, 0), a.F - 1);
+}
+
+// workgroup -> (cuboid, chunk, frame) of the indexed kernels.  xcd_pin 0 / 1: sample_chunk_of's mapping over the cuboids.  xcd_pin 2 (by frame): all cuboids
+// of a frame read the same maps, so cuboid p runs on XCD frame_of[p] % 8 -- the workgroups of XCD x walk the cuboids whose frame is x modulo 8, in increasing
+// p; the assignment lives on the device (it changes from forward to forward of a captured graph), so the grid is sized for the worst case (every cuboid on
+// one XCD) and a workgroup whose slot is past its XCD's last cuboid returns false and leaves.  Which workgroup computes a voxel does not touch its arithmetic.
+__device__ __forceinline__ bool cuboid_chunk_of(const UnprojIndexedArgs& a, int& p, int& chunk, int& f) {
+    if (a.xcd_pin != 2) {
+        sample_chunk_of(a, p, chunk);
+        f = frame_of_cuboid(a, p);
+        return true;
+    }
+    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    int slot = j / a.chunks;
+    chunk = j % a.chunks;
+    for (int q = 0; q < a.B; ++q) {
+        f = frame_of_cuboid(a, q);
+        if ((f & 7) != xcd) continue;
+        if (slot-- == 0) { p = q; return true; }
+    }
+    return false;
+}
+
 // Bilinear sample of CH channels for one voxel in one view (project_taps' geometry): only the corners inside the map are loaded, and
 // blended with the raw weights -- the first of the two load disciplines of unproj_geom.h.
 template <typename T, int CH>
@@ -136,24 +171,33 @@ __device__ __forceinline__ void sample_view(const T* __restrict__ fmap, const fl
 }
 
 // does view v take part?  Without a mask: constant true, so the unmasked instantiations compile to what they did before the mask existed
-template <bool MASKED, bool BITS>
+// (NULLABLE, the indexed kernels: a null mask means every view is valid; as bits that is all ones)
+template <bool MASKED, bool BITS, bool NULLABLE = false>
 __device__ __forceinline__ bool view_on(unsigned mbits, const uint8_t* __restrict__ mk, int v) {
     if constexpr (!MASKED) return true;
     else if constexpr (BITS) return ((mbits >> v) & 1u) != 0;
+    else if constexpr (NULLABLE) return !mk || mk[v] != 0;
     else return mk[v] != 0;
 }
 
 // MASKED: the views {v : mask[b][v]} of sample b alone, visited in increasing v -- exactly the unmasked arithmetic on the compacted views (a
 // masked view is never sampled; no valid view at all: zeros).  The mask of a sample is uniform over its workgroups: SMALL_NV keeps it as bits.
-template <typename T, int CH, bool SMALL_NV, bool MASKED = false>
-__global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKED> a) {
+// INDEXED (on the masked form): sample b is cuboid b, which reads the maps, projections, confidences and mask of its frame f = frame_of[b].
+template <typename T, int CH, bool SMALL_NV, bool MASKED = false, bool INDEXED = false>
+__global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKED, INDEXED> a) {
+    static_assert(MASKED || !INDEXED, "the indexed kernels are built on the masked form");
     constexpr bool FAST = sizeof(T) == 2;
     const int tpv = a.C / CH;  // lanes per voxel
-    int b, chunk;
-    sample_chunk_of(a, b, chunk);
+    int b, chunk, f;           // f: the sample whose views are read
+    if constexpr (INDEXED) {
+        if (!cuboid_chunk_of(a, b, chunk, f)) return;
+    } else {
+        sample_chunk_of(a, b, chunk);
+        f = b;
+    }
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
-    const T* feats = (const T*)a.feats + (long long)b * a.NV * a.h * a.w * a.C;
-    const float* P = a.proj + (long long)b * a.NV * 12;
+    const T* feats = (const T*)a.feats + (long long)f * a.NV * a.h * a.w * a.C;
+    const float* P = a.proj + (long long)f * a.NV * 12;
     const float* coords = a.coords + (long long)b * nvox * 3;
     T* out = (T*)a.out + (long long)b * nvox * a.C;
     int bi = 0, bj = 0, bk = 0;
@@ -161,8 +205,9 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
     const uint8_t* mk = nullptr;
     unsigned mbits = ~0u;
     if constexpr (MASKED) {
-        mk = a.mask + (long long)b * a.NV;
-        if (SMALL_NV) {
+        mk = a.mask + (long long)f * a.NV;
+        if constexpr (INDEXED) if (!a.mask) mk = nullptr;
+        if (SMALL_NV && (!INDEXED || mk)) {
             mbits = 0;
             for (int v = 0; v < a.NV; ++v) mbits |= (mk[v] ? 1u : 0u) << v;
         }
@@ -181,7 +226,7 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
             float vals[8][CH];
 #pragma unroll
             for (int v = 0; v < 8; ++v)
-                if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, vals[v]);
+                if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, vals[v]);
 #pragma unroll
             for (int e = 0; e < CH; ++e) {
                 float r;
@@ -191,7 +236,7 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
                         bool have = false;
                         m = 0.f;
 #pragma unroll
-                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) { m = have ? fmaxf(m, vals[v][e]) : vals[v][e]; have = true; }
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) { m = have ? fmaxf(m, vals[v][e]) : vals[v][e]; have = true; }
                     } else {
                         m = vals[0][e];
 #pragma unroll
@@ -200,14 +245,14 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
                     // sum_v x_v softmax_v(x) = (sum_v x_v e_v) / (sum_v e_v): one division per channel
                     float s = 0.f, tt = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) { const float ex = exp_<FAST>(vals[v][e] - m); s += ex; tt += vals[v][e] * ex; }
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) { const float ex = exp_<FAST>(vals[v][e] - m); s += ex; tt += vals[v][e] * ex; }
                     r = div_<FAST>(tt, s);
                 } else if (a.agg == LT_AGG_MAX) {
                     if constexpr (MASKED) {
                         bool have = false;
                         r = 0.f;
 #pragma unroll
-                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) { r = have ? fmaxf(r, vals[v][e]) : vals[v][e]; have = true; }
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) { r = have ? fmaxf(r, vals[v][e]) : vals[v][e]; have = true; }
                     } else {
                         r = vals[0][e];
 #pragma unroll
@@ -218,15 +263,15 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
                     if (a.agg == LT_AGG_CONF_NORM) {
                         cs = 0.f;
 #pragma unroll
-                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) cs += a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) cs += a.conf[((long long)f * a.NV + v) * a.C + c0 + e];
                     }
                     r = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) r += vals[v][e] * __fdiv_rn(a.conf[((long long)b * a.NV + v) * a.C + c0 + e], cs);
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) r += vals[v][e] * __fdiv_rn(a.conf[((long long)f * a.NV + v) * a.C + c0 + e], cs);
                 } else {
                     r = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV>(mbits, mk, v)) r += vals[v][e];
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) r += vals[v][e];
                 }
                 if constexpr (MASKED) if (mbits == 0) r = 0.f;   // no valid view
                 res[e] = r;
@@ -238,28 +283,28 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
                 m[e] = -INFINITY; s[e] = 0.f; acc[e] = 0.f; cs[e] = 1.f;
                 if (a.agg == LT_AGG_CONF_NORM) {
                     cs[e] = 0.f;
-                    for (int v = 0; v < a.NV; ++v) if (view_on<MASKED, SMALL_NV>(mbits, mk, v)) cs[e] += a.conf[((long long)b * a.NV + v) * a.C + c0 + e];
+                    for (int v = 0; v < a.NV; ++v) if (view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) cs[e] += a.conf[((long long)f * a.NV + v) * a.C + c0 + e];
                 }
             }
             bool any = !MASKED;
             if constexpr (MASKED)
-                for (int v = 0; v < a.NV; ++v) any = any || view_on<MASKED, SMALL_NV>(mbits, mk, v);
+                for (int v = 0; v < a.NV; ++v) any = any || view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v);
             if (a.agg == LT_AGG_SOFTMAX || a.agg == LT_AGG_MAX)
                 for (int v = 0; v < a.NV; ++v) {
-                    if (!view_on<MASKED, SMALL_NV>(mbits, mk, v)) continue;
+                    if (!view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) continue;
                     sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, val);
 #pragma unroll
                     for (int e = 0; e < CH; ++e) m[e] = fmaxf(m[e], val[e]);
                 }
             if (a.agg != LT_AGG_MAX)
                 for (int v = 0; v < a.NV; ++v) {
-                    if (!view_on<MASKED, SMALL_NV>(mbits, mk, v)) continue;
+                    if (!view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) continue;
                     sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, val);
 #pragma unroll
                     for (int e = 0; e < CH; ++e) {
                         if (a.agg == LT_AGG_SOFTMAX) { const float ex = exp_<FAST>(val[e] - m[e]); s[e] += ex; acc[e] += val[e] * ex; }
                         else if (a.agg == LT_AGG_CONF || a.agg == LT_AGG_CONF_NORM)
-                            acc[e] += val[e] * __fdiv_rn(a.conf[((long long)b * a.NV + v) * a.C + c0 + e], cs[e]);
+                            acc[e] += val[e] * __fdiv_rn(a.conf[((long long)f * a.NV + v) * a.C + c0 + e], cs[e]);
                         else acc[e] += val[e];
                     }
                 }
@@ -305,14 +350,21 @@ __device__ __forceinline__ f32x2_t pk_fma(f32x2_t a, f32x2_t b, f32x2_t c) { ret
 // the unmasked kernel on the valid views, so an all-ones mask gives its bits (the max starts from -inf where the unmasked kernel starts from view 0:
 // the same value unless EVERY valid view's sample is NaN, and then both write NaN).  (The lanes still project into their masked views: which
 // lane owns a view varies over the quad, and the 30 instructions are not worth a divergent branch.)
-template <int NVL, bool GRID, bool MASKED = false>
-__global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MASKED> a) {
+// INDEXED (on the masked form): as in unproject_kernel -- the maps, projections and mask of frame f = frame_of[b], everything of the cuboid by b.
+template <int NVL, bool GRID, bool MASKED = false, bool INDEXED = false>
+__global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MASKED, INDEXED> a) {
+    static_assert(MASKED || !INDEXED, "the indexed kernels are built on the masked form");
     typedef bf16_t T;
     constexpr int C = 32, NV = 4 * NVL;
-    int b, chunk;
-    sample_chunk_of(a, b, chunk);
+    int b, chunk, f;
+    if constexpr (INDEXED) {
+        if (!cuboid_chunk_of(a, b, chunk, f)) return;
+    } else {
+        sample_chunk_of(a, b, chunk);
+        f = b;
+    }
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
-    const T* feats = (const T*)a.feats + (long long)b * NV * a.h * a.w * C;
+    const T* feats = (const T*)a.feats + (long long)f * NV * a.h * a.w * C;
     const float* coords = GRID ? nullptr : a.coords + (long long)b * nvox * 3;
     float* coords_out = (GRID && a.coords_out) ? a.coords_out + (long long)b * nvox * 3 : nullptr;
     T* out = (T*)a.out + (long long)b * nvox * C;
@@ -324,7 +376,7 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
 #pragma unroll
     for (int s = 0; s < NVL; ++s)
 #pragma unroll
-        for (int i = 0; i < 12; ++i) P[s][i] = a.proj[((long long)b * NV + qv + 4 * s) * 12 + i];
+        for (int i = 0; i < 12; ++i) P[s][i] = a.proj[((long long)f * NV + qv + 4 * s) * 12 + i];
     float gp[3], gc[3], gR[9];
     if (GRID) {
 #pragma unroll
@@ -335,9 +387,11 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
     const float inv_h = __builtin_amdgcn_rcpf((float)h), inv_w = __builtin_amdgcn_rcpf((float)w);
     unsigned mbits = (1u << NV) - 1u;
     if constexpr (MASKED) {
-        mbits = 0;
+        if (!INDEXED || a.mask) {
+            mbits = 0;
 #pragma unroll
-        for (int v = 0; v < NV; ++v) mbits |= (a.mask[(long long)b * NV + v] ? 1u : 0u) << v;
+            for (int v = 0; v < NV; ++v) mbits |= (a.mask[(long long)f * NV + v] ? 1u : 0u) << v;
+        }
         mbits = __builtin_amdgcn_readfirstlane(mbits);
     }
 
@@ -437,27 +491,35 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
     }
 }
 
+// LT_UNPROJ_PIN unset: the indexed kernels pin by cuboid (false) or by frame (true) -- the faster of the two in tools/multi_cuboid_bench.py.  Measured at
+// BASELINE config 2's gather shape, bf16, 8 frames x 4 cuboids (profiles/multi_cuboid_bench.json): by cuboid 0.590 ms per launch, level with the unindexed
+// gather on 32 gathered samples (0.564 ms); by frame 1.541 ms (2.241 ms with 11, 7, 5, 3, 2, 2, 1, 1 cuboids per frame): its grid is sized for the worst case
+// and the XCD with the most cuboids sets the time, which costs more than the shared L2 saves (2.4 MB of maps per frame).
+constexpr bool PIN_DEFAULT_FRAME = false;
+
 // One workgroup of 256 threads per (sample, chunk).  An unmasked kernel receives a plain UnprojArgs by value (the base of m) and a masked one all of
 // m: that is what keeps the unmasked kernels' argument block, and with it their code, what it was before the mask existed.
-template <bool MASKED>
-void launch_chunks(void (*kern)(UnprojArgsOf<MASKED>), const UnprojMaskedArgs& m, hipStream_t st) {
-    const UnprojArgsOf<MASKED>& a = m;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)m.B * m.chunks)), dim3(256), 0, st, a);
+// An indexed kernel receives all of m (by frame, xcd_pin 2: eight times the workgroups, see cuboid_chunk_of).
+template <bool MASKED, bool INDEXED>
+void launch_chunks(void (*kern)(UnprojArgsOf<MASKED, INDEXED>), const UnprojIndexedArgs& m, hipStream_t st) {
+    const UnprojArgsOf<MASKED, INDEXED>& a = m;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)m.B * m.chunks * (INDEXED && m.xcd_pin == 2 ? 8 : 1))), dim3(256), 0, st, a);
 }
-template <bool MASKED>
-void launch_quad(const UnprojMaskedArgs& m, bool grid, hipStream_t st) {
-    launch_chunks<MASKED>(m.NV == 4 ? (grid ? unproject_qn_kernel<1, true, MASKED> : unproject_qn_kernel<1, false, MASKED>)
-                                    : (grid ? unproject_qn_kernel<2, true, MASKED> : unproject_qn_kernel<2, false, MASKED>), m, st);
+template <bool MASKED, bool INDEXED>
+void launch_quad(const UnprojIndexedArgs& m, bool grid, hipStream_t st) {
+    launch_chunks<MASKED, INDEXED>(m.NV == 4 ? (grid ? unproject_qn_kernel<1, true, MASKED, INDEXED> : unproject_qn_kernel<1, false, MASKED, INDEXED>)
+                                             : (grid ? unproject_qn_kernel<2, true, MASKED, INDEXED> : unproject_qn_kernel<2, false, MASKED, INDEXED>), m, st);
 }
-template <typename T, int CH, bool MASKED>
-void launch_generic(const UnprojMaskedArgs& m, hipStream_t st) {
-    launch_chunks<MASKED>(m.NV <= 8 ? unproject_kernel<T, CH, true, MASKED> : unproject_kernel<T, CH, false, MASKED>, m, st);
+template <typename T, int CH, bool MASKED, bool INDEXED>
+void launch_generic(const UnprojIndexedArgs& m, hipStream_t st) {
+    launch_chunks<MASKED, INDEXED>(m.NV <= 8 ? unproject_kernel<T, CH, true, MASKED, INDEXED> : unproject_kernel<T, CH, false, MASKED, INDEXED>, m, st);
 }
 template <typename T, int CH>
-int launch_unproject(const UnprojMaskedArgs& m, hipStream_t st) {
-    if (m.mask) launch_generic<T, CH, true>(m, st);
-    else launch_generic<T, CH, false>(m, st);
-    LT_CHECK_LAUNCH(m.mask ? "lt_unproject_masked_fwd" : "lt_unproject_fwd");
+int launch_unproject(const UnprojIndexedArgs& m, hipStream_t st) {
+    if (m.frame_of) launch_generic<T, CH, true, true>(m, st);
+    else if (m.mask) launch_generic<T, CH, true, false>(m, st);
+    else launch_generic<T, CH, false, false>(m, st);
+    LT_CHECK_LAUNCH(m.frame_of ? "lt_unproject_indexed_fwd" : m.mask ? "lt_unproject_masked_fwd" : "lt_unproject_fwd");
     return LT_OK;
 }
 
@@ -470,22 +532,30 @@ int launch_coord_volumes(const char* what, const float* pos, const float* center
 }
 
 // fills the launch geometry and picks the kernel; a.coords (read) or the a.g_* grid description must be set by the caller.  a.mask set: the masked
-// instantiation of the SAME kernel the unmasked call takes (a masked plan never leaves the quad kernel for the generic one).
-int unproject_dispatch(UnprojMaskedArgs& a, int dtype, bool grid, hipStream_t st) {
+// instantiation of the SAME kernel the unmasked call takes (a masked plan never leaves the quad kernel for the generic one).  a.frame_of set: the
+// indexed instantiation of that kernel, a.B cuboids over a.F frames.
+int unproject_dispatch(UnprojIndexedArgs& a, int dtype, bool grid, hipStream_t st) {
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
     a.bricked = (a.v0 % 4 == 0 && a.v1 % 4 == 0 && a.v2 % 16 == 0) ? 1 : 0;
     a.blocked = (a.bricked && a.v0 % 32 == 0 && a.v1 % 32 == 0 && a.v2 % 32 == 0 && !env_on("LT_UNPROJ_RASTER")) ? 1 : 0;          // LT_UNPROJ_RASTER=1: the old order (A/B)
     a.chunks = (int)cdiv(nvox, 256);
     a.xcd_pin = (a.B % 8 == 0) ? 1 : 0;
     LT_REQUIRE((long long)a.B * a.chunks < (1ll << 31), LT_ERR_UNSUPPORTED, "lt_unproject_fwd: grid too large");
+    if (a.frame_of) {
+        // LT_UNPROJ_PIN=frame | cuboid (A/B, read per call): which XCD a cuboid's workgroups run on -- see cuboid_chunk_of; unset: PIN_DEFAULT_FRAME
+        const char* pin = getenv("LT_UNPROJ_PIN");
+        const bool by_frame = pin && pin[0] ? pin[0] == 'f' : PIN_DEFAULT_FRAME;
+        if (by_frame && a.F > 1 && 8ll * a.B * a.chunks < (1ll << 31)) a.xcd_pin = 2;
+    }
     // quad kernel: bf16, 32 channels, 4 or 8 views, view softmax, bricked volume (BASELINE configurations 2 and 4)
     const bool no_q4 = env_on("LT_UNPROJ_NO_Q4");       // A/B, read per call
     const bool quad = dtype == LT_BF16 && a.C == 32 && (a.NV == 4 || a.NV == 8) && a.bricked && a.agg == LT_AGG_SOFTMAX && !no_q4 &&
                       (long long)a.NV * a.h * a.w * a.C < (1ll << 30);
     if (quad) {
-        if (a.mask) launch_quad<true>(a, grid, st);
-        else launch_quad<false>(a, grid, st);
-        LT_CHECK_LAUNCH(a.mask ? "lt_unproject_masked_fwd(quad)" : "lt_unproject_fwd(quad)");
+        if (a.frame_of) launch_quad<true, true>(a, grid, st);
+        else if (a.mask) launch_quad<true, false>(a, grid, st);
+        else launch_quad<false, false>(a, grid, st);
+        LT_CHECK_LAUNCH(a.frame_of ? "lt_unproject_indexed_fwd(quad)" : a.mask ? "lt_unproject_masked_fwd(quad)" : "lt_unproject_fwd(quad)");
         return LT_OK;
     }
     if (grid) {      // no fused kernel for this configuration: materialise the grid (it is a returned tensor anyway), then gather
@@ -509,10 +579,20 @@ struct UnprojCuboid {
     float* coords_out;
 };
 
-// The one body behind the four forward entries: `who` is the entry that was called, `cub` is set by the grid entries (v0 = v1 = v2 = V there) and
-// `masked` by the masked ones.
+// The frames of the indexed entries: cuboid p of the B reads frame frame_of[p] of the F.
+struct UnprojFrames {
+    const int32_t* frame_of;
+    int F;
+};
+
+// The one body behind the six forward entries: `who` is the entry that was called, `cub` is set by the grid entries (v0 = v1 = v2 = V there),
+// `masked` by the masked ones and `frames` by the indexed ones (B = their P cuboids; their view_mask may be null).
 int unproject_forward(const char* who, int dtype, const void* feats, const float* proj, const float* coords, const UnprojCuboid* cub, const float* conf,
-                      bool masked, const uint8_t* view_mask, void* out, int B, int NV, int C, int h, int w, int v0, int v1, int v2, int agg, void* stream) {
+                      bool masked, const uint8_t* view_mask, void* out, int B, int NV, int C, int h, int w, int v0, int v1, int v2, int agg, void* stream,
+                      const UnprojFrames* frames = nullptr) {
+    LT_REQUIRE(!frames || frames->frame_of, LT_ERR_INVALID, "%s: null frame_of", who);
+    LT_REQUIRE(!frames || frames->F >= 1, LT_ERR_INVALID, "%s: F %d frames", who, frames->F);
+    LT_REQUIRE(!frames || B >= 1, LT_ERR_INVALID, "%s: P %d cuboids", who, B);
     LT_REQUIRE(feats && proj && out && (cub ? cub->pos && cub->center && cub->rot && cub->coords_out : coords != nullptr), LT_ERR_INVALID, "%s: null argument", who);
     LT_REQUIRE(!masked || view_mask, LT_ERR_INVALID, "%s: null view_mask", who);
     LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "%s: bad dtype %d", who, dtype);
@@ -520,8 +600,9 @@ int unproject_forward(const char* who, int dtype, const void* feats, const float
     LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "%s: LT_AGG_CONF* needs confidences", who);
     LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && (cub ? v0 >= 2 : v0 >= 1 && v1 >= 1 && v2 >= 1), LT_ERR_INVALID, "%s: bad shape", who);
     LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
-    UnprojMaskedArgs a = {};
-    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out; a.mask = masked ? view_mask : nullptr;
+    UnprojIndexedArgs a = {};
+    if (frames) { a.frame_of = frames->frame_of; a.F = frames->F; }
+    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out; a.mask = (masked || frames) ? view_mask : nullptr;
     a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = v0; a.v1 = v1; a.v2 = v2; a.agg = agg;
     if (cub) { a.g_pos = cub->pos; a.g_center = cub->center; a.g_rot = cub->rot; a.g_step = cub->step; a.g_cmu = cub->cmu; a.coords_out = cub->coords_out; }
     return unproject_dispatch(a, dtype, cub != nullptr, (hipStream_t)stream);
@@ -559,6 +640,24 @@ extern "C" int lt_unproject_grid_masked_fwd(int32_t dtype, const void* feats, co
                                             int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream) {
     const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
     return unproject_forward("lt_unproject_grid_masked_fwd", dtype, feats, proj, nullptr, &cub, conf, true, view_mask, out, B, NV, C, h, w, V, V, V, agg, stream);
+}
+
+extern "C" int lt_unproject_indexed_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                                        const int32_t* frame_of, void* out, int32_t F, int32_t P, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0,
+                                        int32_t v1, int32_t v2, int32_t agg, void* stream) {
+    const UnprojFrames frames = {frame_of, F};
+    return unproject_forward("lt_unproject_indexed_fwd", dtype, feats, proj, coords, nullptr, conf, false, view_mask, out, P, NV, C, h, w, v0, v1, v2, agg, stream,
+                             &frames);
+}
+
+extern "C" int lt_unproject_grid_indexed_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
+                                             float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask,
+                                             const int32_t* frame_of, void* out, int32_t F, int32_t P, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V,
+                                             int32_t agg, void* stream) {
+    const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
+    const UnprojFrames frames = {frame_of, F};
+    return unproject_forward("lt_unproject_grid_indexed_fwd", dtype, feats, proj, nullptr, &cub, conf, false, view_mask, out, P, NV, C, h, w, V, V, V, agg, stream,
+                             &frames);
 }
 
 namespace {

@@ -125,6 +125,8 @@ class PlanInfo(C.Structure):
 SIGNATURES = {
     "lt_plan_create_vol": (C.c_int, [C.POINTER(VolPlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
     "lt_plan_forward_vol": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "lt_plan_create_vol_multi": (C.c_int, [C.POINTER(VolPlanConfig), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
+    "lt_plan_forward_vol_multi": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_create_alg": (C.c_int, [C.POINTER(AlgPlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
     "lt_plan_forward_alg": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_create_cascade": (C.c_int, [C.POINTER(CascadePlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
@@ -172,6 +174,8 @@ SIGNATURES = {
     "lt_unproject_grid_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_unproject_masked_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_unproject_grid_masked_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "lt_unproject_indexed_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "lt_unproject_grid_indexed_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_cuboid_from_keypoints": (C.c_int, [vp, i32, i32, i32, C.c_double, vp, vp, vp]),
     "lt_softargmax3d_workspace": (C.c_size_t, [i32, i32, i64]),
     "lt_softargmax3d_fwd": (C.c_int, [vp, vp, f32, i32, i32, i32, vp, vp, i32, i32, i64, vp, vp]),

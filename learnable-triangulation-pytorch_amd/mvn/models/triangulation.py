@@ -70,6 +70,15 @@ def _batch_view_mask(batch, B, NV, min_valid, who):
     return op.view_mask_host(vm, B, NV, min_valid=min_valid, what="%s: batch['view_mask']" % who)
 
 
+def _batch_cuboid_frame(batch, F, who):
+    """``batch["cuboid_frame"]`` -- the frame of every cuboid of a multi-cuboid forward -- as a checked host (P,) int32 array, or None when the batch has
+    none.  ValueError for an empty list, an index outside [0, F) or a non-integer entry -- raised before anything is launched."""
+    cf = batch.get("cuboid_frame") if isinstance(batch, dict) else None
+    if cf is None:
+        return None
+    return op.frame_index_host(cf, F, what="%s: batch['cuboid_frame']" % who)
+
+
 class _VolTrainPlan:
     """The training step of VolumetricTriangulationNet for one input shape, recorded once and replayed (lt_train.TrainTape): the first
     forward / backward run the layers while recording them; later steps re-launch the recorded closures over the same buffers.  What
@@ -387,13 +396,19 @@ class VolumetricTriangulationNet(_PlannedNet):
                                   "bfloat16": torch.bfloat16}[str(m.compute_dtype)]
 
     # ---------------------------------------------------------------------------------------
-    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False):
-        """masked: the plan of forwards with ``batch["view_mask"]`` -- the same launch list with lt_unproject_grid_masked_fwd in the gather's place; the
+    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False, cuboids=None):
+        """cuboids: the plan of forwards with ``batch["cuboid_frame"]`` -- P = ``cuboids`` cuboids over the B frames: the backbone and process_features
+        are recorded at B * NV images, the gather (lt_unproject_grid_indexed_fwd), V2V, the soft-argmax and their buffers at P; the P int32 frame indices
+        ride in the geometry block behind the rotations (in front of the mask), outside the captured graph like the rest of it: a new assignment of
+        cuboids to frames on a captured plan is just another forward.  None: one cuboid per sample, the plan it always was.
+        masked: the plan of forwards with ``batch["view_mask"]`` -- the same launch list with lt_unproject_grid_masked_fwd in the gather's place; the
         (B, NV) uint8 mask rides at the end of the geometry block (same pinned ring, same copy), outside the captured graph's baked pointers like the
         rest of the block, so a new mask on a captured plan is just another forward.
         stats: the plan of forwards with ``keypoint_stats`` -- the same launch list with lt_softargmax3d_stats_fwd in the tail op's place (same op kind)."""
         V, J = self.volume_size, self.num_joints
-        b, x_in = self._open_plan(B * NV, Hh, W, device, dry_run)
+        F, multi = B, cuboids is not None          # F frames carry the images, the features and the confidences ...
+        b, x_in = self._open_plan(F * NV, Hh, W, device, dry_run)
+        B = int(cuboids) if multi else F           # ... everything from the gather on is per cuboid
         lib = b.lib
         # the 1x1 heatmap head is dead in the volumetric path: only its SHAPE is used (reference :264)
         # bf16 plans: the fused stem reads the caller's fp32 images (pointer handed over per forward through this cell)
@@ -406,27 +421,33 @@ class VolumetricTriangulationNet(_PlannedNet):
         b.release(feats256)
         feats.pooled = False
         h, w = feats.shape[2], feats.shape[3]
-        # geometry block (fp32, one H2D copy per forward): proj B*NV*12 | pos B*3 | center B*3 | rot B*9
-        o_mask = B * NV * 12 + B * 15          # masked plans: B*NV mask bytes behind the floats (whole words)
-        n_geo = o_mask + ((B * NV + 3) // 4 if masked else 0)
+        # geometry block (fp32, one H2D copy per forward): proj F*NV*12 | pos B*3 | center B*3 | rot B*9 | [frame_of B int32] | [mask F*NV bytes]
+        o_fof = F * NV * 12 + B * 15           # multi-cuboid plans: the frame of every cuboid
+        o_mask = o_fof + (B if multi else 0)   # masked plans: F*NV mask bytes behind the words (whole words)
+        n_geo = o_mask + ((F * NV + 3) // 4 if masked else 0)
         geo = torch.zeros(n_geo, dtype=torch.float32, device=device)
         # pinned staging ring: forward N+1 fills the next slot while forward N's copy may still be queued (forward never blocks on the GPU otherwise)
         geo_ring = PinnedRing(n_geo, torch.float32, 1 if dry_run else GEO_RING, pin=not dry_run)
-        o_pos, o_cen, o_rot = B * NV * 12, B * NV * 12 + 3 * B, B * NV * 12 + 6 * B
+        o_pos, o_cen, o_rot = F * NV * 12, F * NV * 12 + 3 * B, F * NV * 12 + 6 * B
         coords = torch.empty(B, V, V, V, 3, dtype=torch.float32, device=device)
         step = float(np.float32(self.cuboid_side / (V - 1)))
         gp = geo.data_ptr()
         cmu = int(bool(self.transfer_cmu_to_human36m))
         conf = None
         if volc is not None:
-            conf = volc.t.reshape(B, NV, 32)   # 'conf_norm' is normalised inside the kernel (LT_AGG_CONF_NORM)
+            conf = volc.t.reshape(F, NV, 32)   # 'conf_norm' is normalised inside the kernel (LT_AGG_CONF_NORM)
         vol = b.alloc((B, V, V, V, 32))
         esz = E.esize(self.compute_dtype)
         agg = H.AGG[self.volume_aggregation_method]
         # ONE launch: the voxel centres are computed in registers from (position, centre, rotation, step) and written to the returned
         # coordinate tensor on the way (reference :298-339 + op.py:99-166); configurations without a fused kernel run
         # lt_coord_volumes + the generic gather inside the same call
-        if masked:
+        entry = "lt_unproject_grid_indexed_fwd" if multi else "lt_unproject_grid_masked_fwd" if masked else "lt_unproject_grid_fwd"
+        if multi:
+            unproject = lambda st: H.check(lib.lt_unproject_grid_indexed_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
+                                                                             coords.data_ptr(), H.ptr(conf), gp + 4 * o_mask if masked else None, gp + 4 * o_fof,
+                                                                             vol.t.data_ptr(), F, B, NV, 32, h, w, V, agg, st), entry)
+        elif masked:
             unproject = lambda st: H.check(lib.lt_unproject_grid_masked_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
                                                                             coords.data_ptr(), H.ptr(conf), gp + 4 * o_mask, vol.t.data_ptr(), B, NV, 32, h, w, V,
                                                                             agg, st), "lt_unproject_grid_masked_fwd")
@@ -435,9 +456,9 @@ class VolumetricTriangulationNet(_PlannedNet):
                                                                      coords.data_ptr(), H.ptr(conf), vol.t.data_ptr(), B, NV, 32, h, w, V, agg, st),
                                            "lt_unproject_grid_fwd")
         b.custom(unproject,
-                 "unproject", nbytes=(B * NV * h * w * 32 + B * V ** 3 * 32) * esz + B * V ** 3 * 12,   # feats once + volume once + the returned coords
+                 "unproject", nbytes=(F * NV * h * w * 32 + B * V ** 3 * 32) * esz + B * V ** 3 * 12,   # feats once + volume once + the returned coords
                  info={"feats": feats, "geo": geo, "coords": coords, "conf": conf, "vol": vol, "agg": self.volume_aggregation_method, "NV": NV,
-                       "offs": (o_pos, o_cen, o_rot), "step": step, "cmu": cmu, "masked": masked})
+                       "offs": (o_pos, o_cen, o_rot), "step": step, "cmu": cmu, "masked": masked, "entry": entry, "frames": F, "cuboids": B})
         logits = self.volume_net.record(b, vol)
         kp = torch.empty(B, J, 3, dtype=torch.float32, device=device)
         probs = torch.empty(B, J, V, V, V, dtype=torch.float32, device=device)
@@ -449,8 +470,8 @@ class VolumetricTriangulationNet(_PlannedNet):
         # launch from the plan's channels-last map straight into the tensor forward() hands out (it was a permuted view + an ATen cast copy);
         # skipped when the caller asked for views of the plan's buffers (copy_outputs = False)
         b.custom(lambda st, outs=None: None if not outs or len(outs) < 3 or outs[2] is None else H.check(lib.lt_nhwc_to_nchw_f32(
-                     b.code, feats.t.data_ptr(), outs[2].data_ptr(), B * NV, 32, h * w, 32, st), "lt_nhwc_to_nchw_f32"),
-                 "features_out", nbytes=B * NV * h * w * 32 * (esz + 4), info={"feats": feats}, tail=True)
+                     b.code, feats.t.data_ptr(), outs[2].data_ptr(), F * NV, 32, h * w, 32, st), "lt_nhwc_to_nchw_f32"),
+                 "features_out", nbytes=F * NV * h * w * 32 * (esz + 4), info={"feats": feats}, tail=True)
         # tail op (outside the captured graph): forward() points it at the tensors it returns, so the 17 x 64^3 probabilities
         # are written once, where the caller gets them, instead of being cloned out of a plan buffer (0.45 ms of copies per step)
         kstats = kindex = None
@@ -477,7 +498,8 @@ class VolumetricTriangulationNet(_PlannedNet):
             x_in.t.untyped_storage().resize_(0)   # the fused stem reads the caller's images: x_in is only a shape (150 MB at B = 32)
         return {"plan": plan, "x_in": x_in, "image_cell": image_cell, "feats": feats, "geo": geo, "geo_host": geo_ring.blocks[0], "geo_ring": geo_ring,
                 "coords": coords, "kp": kp, "probs": probs, "conf": conf, "logits": logits, "vol": vol, "hw": (h, w), "offs": (o_pos, o_cen, o_rot),
-                "captured": False, "masked": masked, "o_mask": o_mask, "kstats": kstats, "kindex": kindex}
+                "captured": False, "masked": masked, "o_mask": o_mask, "kstats": kstats, "kindex": kindex, "frames": F, "cuboids": B if multi else None,
+                "o_fof": o_fof}
 
     def _host_cameras(self, batch, B, image_shape, P):
         """The camera half of the host geometry (reference :272-279, :318-328): fills the projections and rotations of the next slot of the plan's
@@ -487,14 +509,17 @@ class VolumetricTriangulationNet(_PlannedNet):
         K, R, t = multiview.stack_cameras(batch["cameras"])
         proj = multiview.resized_projections(K, R, t, image_shape, (h, w))
         axis = [0, 1, 0] if self.kind == "coco" else [0, 0, 1]
-        rot = np.empty((B, 9))
-        for i in range(B):
+        nc = P.get("cuboids") or B          # one rotation per cuboid (multi-cuboid plans: B counts the frames)
+        rot = np.empty((nc, 9))
+        for i in range(nc):
             theta = np.random.uniform(0.0, 2 * np.pi) if self.training else 0.0
             rot[i] = volumetric.get_rotation_matrix(axis, theta).reshape(-1)
         o_pos, o_cen, o_rot = P["offs"]
         gh = P["geo_host"] = P["geo_ring"].acquire()
         gh[:o_pos] = torch.from_numpy(proj.astype(np.float32).reshape(-1))
-        gh[o_rot:o_rot + 9 * B] = torch.from_numpy(rot.astype(np.float32).reshape(-1))
+        gh[o_rot:o_rot + 9 * nc] = torch.from_numpy(rot.astype(np.float32).reshape(-1))
+        if P.get("cuboids"):
+            gh.view(torch.int32)[P["o_fof"]:P["o_fof"] + nc] = torch.from_numpy(batch["cuboid_frame"])
         if P.get("masked"):
             gh.view(torch.uint8)[4 * P["o_mask"]:4 * P["o_mask"] + B * len(batch["cameras"])] = torch.from_numpy(batch["view_mask"].reshape(-1))
         return gh
@@ -503,8 +528,9 @@ class VolumetricTriangulationNet(_PlannedNet):
         """numpy fp64 camera / cuboid algebra of the reference (:272-296, :318-328), vectorised; fills the plan's pinned
         geometry block (fp32: projections, cuboid origins, centres, rotations).  Returns (position, base, sides)."""
         kp3d = batch["keypoints_3d"] if self.use_gt_pelvis else batch["pred_keypoints_3d"]
-        base = np.empty((B, 3), dtype=np.float64)
-        for i in range(B):
+        nc = P.get("cuboids") or B          # multi-cuboid plans: one base point per cuboid
+        base = np.empty((nc, 3), dtype=np.float64)
+        for i in range(nc):
             k3 = np.asarray(kp3d[i])
             base[i] = (k3[11, :3] + k3[12, :3]) / 2 if self.kind == "coco" else k3[6, :3]
         sides = np.array([self.cuboid_side] * 3)
@@ -530,10 +556,27 @@ class VolumetricTriangulationNet(_PlannedNet):
         (overwritten at :277); ``batch`` as built by datasets/utils.py:14-37 (``cameras``, and
         ``pred_keypoints_3d`` or ``keypoints_3d``).  Returns the reference's 7-tuple (:355).
 
+        ``batch["cuboid_frame"]`` (eval only): several cuboids per frame.  P >= 1 integers in [0, B), any order -- the frame of every cuboid; the joints in
+        the batch then have P entries, one base point per cuboid.  The backbone runs on the B frames once; keypoints_3d, volumes, cuboids, coord_volumes and
+        base_points come back with P entries, features and vol_confidences with B.  One plan per (B, P); another assignment is another forward of it.
+
         Asynchronous like the reference's CUDA forward: nothing here waits for the GPU (results are ordered on the current
         stream).  One plan per batch shape whatever its size: BASELINE config 4 at 32 samples (2^31 elements per 32-channel volume) is ONE plan and one
         captured graph -- the convolution entry points walk such tensors in sample chunks (``max_samples_per_launch``)."""
         B, NV = images.shape[:2]
+        cf = _batch_cuboid_frame(batch, B, "VolumetricTriangulationNet")          # optional: several cuboids per frame, refused before any launch
+        if cf is not None:
+            if _bn_in_train_mode(self):
+                raise NotImplementedError("VolumetricTriangulationNet: batch['cuboid_frame'] is inference only (there is no indexed unprojection backward); "
+                                          "call eval() first")
+            key = "keypoints_3d" if self.use_gt_pelvis else "pred_keypoints_3d"
+            if len(batch[key]) != len(cf):
+                raise ValueError("VolumetricTriangulationNet: batch['cuboid_frame'] names %d cuboids, batch[%r] has %d entries (one base point per cuboid)" %
+                                 (len(cf), key, len(batch[key])))
+            if max(B, len(cf)) > self.max_samples_per_launch(NV, images.shape[3], images.shape[4]):
+                raise ValueError("VolumetricTriangulationNet: a multi-cuboid forward is one plan, and %d frames with %d cuboids would need sub-batches at this "
+                                 "shape (max_samples_per_launch); split the call" % (B, len(cf)))
+            batch = dict(batch, cuboid_frame=cf)
         vm = _batch_view_mask(batch, B, NV, 1, "VolumetricTriangulationNet")          # optional (B, NV) validity mask: refused before any launch
         if vm is not None:
             if _bn_in_train_mode(self) and not self.masked_training:
@@ -546,7 +589,7 @@ class VolumetricTriangulationNet(_PlannedNet):
             return self._forward_train(images, batch)          # keypoint_stats is ignored there: the training tape is not touched
         _sync_buffers_before_eval(self)
         cap = self.max_samples_per_launch(NV, images.shape[3], images.shape[4])
-        if B <= cap:
+        if B <= cap or cf is not None:
             with torch.cuda.device(images.device):
                 out = self._forward_chunk(images, batch, 0, B)
             self.last_keypoint_stats = self._take_keypoint_stats()
@@ -653,16 +696,21 @@ class VolumetricTriangulationNet(_PlannedNet):
         B = hi - lo
         masked = batch.get("view_mask") is not None
         stats = bool(self.keypoint_stats)
+        cf = batch.get("cuboid_frame")          # multi-cuboid forwards are never chunked (forward()): B frames, len(cf) cuboids
+        nc = None if cf is None else len(cf)
         # the key: everything a plan bakes in besides the weights (those: the fingerprint inside _plan_for)
-        P = self._plan_for(self._plan_key(B, NV, Hh, W, device, masked, stats), lambda: self._build_plan(B, NV, Hh, W, device, masked=masked, stats=stats))
+        P = self._plan_for(self._plan_key(B, NV, Hh, W, device, masked, stats, nc),
+                           lambda: self._build_plan(B, NV, Hh, W, device, masked=masked, stats=stats, cuboids=nc))
         return images, batch, B, P
 
-    def _plan_key(self, B, NV, Hh, W, device, masked=False, stats=False):
+    def _plan_key(self, B, NV, Hh, W, device, masked=False, stats=False, cuboids=None):
         """Everything a plan bakes in besides the weights; ``masked``: the plan records the masked gather (forwards without a mask keep their plan);
-        ``stats``: its tail is lt_softargmax3d_stats_fwd (``keypoint_stats``; forwards without the flag keep their plan)."""
-        return (B, NV, Hh, W, self.compute_dtype, device, self.use_graph, self.volume_size, float(self.cuboid_side),
-                float(self.volume_multiplier), bool(self.volume_softmax), self.volume_aggregation_method,
-                bool(self.transfer_cmu_to_human36m), self.tile_override, self.num_joints, masked, stats)
+        ``stats``: its tail is lt_softargmax3d_stats_fwd (``keypoint_stats``; forwards without the flag keep their plan); ``cuboids``: the P of a
+        multi-cuboid plan over B frames (forwards without ``batch["cuboid_frame"]`` keep their plan: their key is the tuple it always was)."""
+        key = (B, NV, Hh, W, self.compute_dtype, device, self.use_graph, self.volume_size, float(self.cuboid_side),
+               float(self.volume_multiplier), bool(self.volume_softmax), self.volume_aggregation_method,
+               bool(self.transfer_cmu_to_human36m), self.tile_override, self.num_joints, masked, stats)
+        return key if cuboids is None else key + ("cuboids", int(cuboids))
 
     @staticmethod
     def _plan_images(images, B, NV):
@@ -709,7 +757,7 @@ class VolumetricTriangulationNet(_PlannedNet):
             self.__dict__.setdefault("_chunk_stats", []).extend([kstats, kindex])
         conf = P["conf"]
         o_pos, o_cen, o_rot = P["offs"]
-        base_points = P["geo"][o_cen:o_rot].reshape(B, 3).clone()    # fp32(base), from the block that was just copied in
+        base_points = P["geo"][o_cen:o_rot].reshape(-1, 3).clone()    # fp32(base), from the block that was just copied in
         if self.copy_outputs:
             coords = coords.clone()
             conf = None if conf is None else conf.clone()
@@ -739,7 +787,7 @@ class VolumetricTriangulationNet(_PlannedNet):
             kp, feats, probs, conf, coords, base_points = self._replay(P, x, B, NV, side, cur, batch.get("view_mask"))
         x.record_stream(side)
         cur.wait_stream(side)
-        cuboids = [volumetric.Cuboid3D(position[i], sides) for i in range(B)]
+        cuboids = [volumetric.Cuboid3D(position[i], sides) for i in range(len(position))]
         return kp, feats, probs, conf, cuboids, coords, base_points
 
 
@@ -1035,6 +1083,10 @@ class CascadeTriangulationNet(nn.Module):
         is read from the device block; ``cuboids`` is a sequence that builds its ``Cuboid3D`` items on first access, and that access
         synchronises with the GPU (the forward itself never does, beyond what the two models' forwards do at their first call of a shape)."""
         B, NV = images.shape[:2]
+        if isinstance(batch, dict) and batch.get("cuboid_frame") is not None:
+            raise NotImplementedError("CascadeTriangulationNet: batch['cuboid_frame'] is not supported -- the algebraic stage gives ONE pelvis per frame, which "
+                                      "cannot centre several cuboids (that needs an association of people across the views); run VolumetricTriangulationNet "
+                                      "with one base point per cuboid")
         vm = _batch_view_mask(batch, B, NV, 2, "CascadeTriangulationNet")          # the one mask for both stages, refused before any launch
         if vm is not None:
             batch = dict(batch, view_mask=vm)

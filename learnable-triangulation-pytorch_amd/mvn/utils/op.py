@@ -62,6 +62,21 @@ def view_mask_host(view_mask, B, NV, min_valid=0, what="view_mask"):
     return m
 
 
+def frame_index_host(frame_index, F, what="frame_index"):
+    """The frame of every cuboid (a sequence, an array or a tensor of P >= 1 integers in [0, F), any order) as a C-contiguous host int32 array.
+    ValueError for an empty or non-flat list or an index outside [0, F) (the message names the first such entry), TypeError for a non-integer dtype."""
+    a = frame_index.detach().cpu().numpy() if torch.is_tensor(frame_index) else np.asarray(frame_index)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError("%s must be a flat list of at least one frame index, got shape %s" % (what, tuple(a.shape)))
+    if a.dtype.kind not in "iu":
+        raise TypeError("%s must hold integers, got dtype %s" % (what, a.dtype))
+    bad = (a < 0) | (a >= F)
+    if bad.any():
+        p = int(np.argmax(bad))
+        raise ValueError("%s[%d] = %d is outside the %d frame%s [0, %d)" % (what, p, int(a[p]), F, "" if F == 1 else "s", F))
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
 def _view_mask_device(view_mask, B, NV, device):
     """The mask as a (B, NV) uint8 device tensor for the masked entry points (a device tensor of the right form is used as it is)."""
     if torch.is_tensor(view_mask) and view_mask.is_cuda:
@@ -75,12 +90,18 @@ def _view_mask_device(view_mask, B, NV, device):
     return torch.from_numpy(view_mask_host(view_mask, B, NV)).to(device)
 
 
-def _unproject_launch(feats_cl, P, cv, conf, method, mask=None):
+def _unproject_launch(feats_cl, P, cv, conf, method, mask=None, frame_of=None):
     """feats_cl (B,NV,h,w,C) contiguous channels-last -> (B,v0,v1,v2,C) channels-last, same dtype.  mask: (B,NV) uint8 device tensor
-    (lt_unproject_masked_fwd) or None."""
+    (lt_unproject_masked_fwd) or None.  frame_of: (P,) int32 device tensor (lt_unproject_indexed_fwd: cv holds P cuboids, each over the views of its
+    frame of the B; the mask, if any, is per frame) or None."""
     B, NV, h, w, Cc = feats_cl.shape
     v0, v1, v2 = cv.shape[1:4]
-    out = torch.empty(B, v0, v1, v2, Cc, dtype=feats_cl.dtype, device=feats_cl.device)
+    out = torch.empty(cv.shape[0], v0, v1, v2, Cc, dtype=feats_cl.dtype, device=feats_cl.device)
+    if frame_of is not None:
+        H.check(H.lib().lt_unproject_indexed_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), H.ptr(mask),
+                                                 frame_of.data_ptr(), out.data_ptr(), B, cv.shape[0], NV, Cc, h, w, v0, v1, v2,
+                                                 H.AGG["conf"] if conf is not None else H.AGG[method], H.cur_stream()), "lt_unproject_indexed_fwd")
+        return out
     if mask is not None:
         H.check(H.lib().lt_unproject_masked_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), mask.data_ptr(),
                                                 out.data_ptr(), B, NV, Cc, h, w, v0, v1, v2, H.AGG["conf"] if conf is not None else H.AGG[method],
@@ -131,7 +152,7 @@ class _UnprojectFn(torch.autograd.Function):
 
 
 def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="sum", vol_confidences=None, view_mask=None,
-                       masked_backward=False):
+                       masked_backward=False, frame_index=None):
     """heatmaps (B,NV,C,h,w), proj_matricies (B,NV,3,4), coord_volumes (B,V0,V1,V2,3),
     vol_confidences (B,NV,C) for 'conf*' -> volumes (B,C,V0,V1,V2).  Reference: op.py:99-166.  Differentiable with respect to the
     heatmaps and the confidences (lt_unproject_bwd) whenever one of them requires grad.
@@ -142,9 +163,17 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
 
     masked_backward=True opts into the differentiable masked op (lt_unproject_masked_bwd): what autograd derives for this function called on each
     sample's valid views alone -- a masked view's heatmaps and confidences get exactly zero gradient, conf_norm's normaliser is differentiated
-    over the valid views.  Gather path only (C a power of two <= 64); ignored without a view_mask."""
+    over the valid views.  Gather path only (C a power of two <= 64); ignored without a view_mask.
+
+    frame_index: several cuboids per frame (lt_unproject_indexed_fwd).  heatmaps (F,NV,C,h,w), proj_matricies (F,NV,3,4), vol_confidences (F,NV,C) and
+    view_mask (F,NV) are per FRAME, coord_volumes (P,V0,V1,V2,3) per cuboid; frame_index holds the P frames of the cuboids (a sequence, an array or a
+    tensor of integers in [0, F), any order; checked on the host when it lives there -- a device tensor is used as it is, and the kernel clamps what
+    it reads) -> volumes (P,C,V0,V1,V2), bit-identical to this function on the inputs gathered by frame_index, without the copies.  Inference only:
+    NotImplementedError when an input requires grad.  None takes exactly the path without it."""
     if volume_aggregation_method not in _METHODS:
         raise ValueError("Unknown volume_aggregation_method: {}".format(volume_aggregation_method))
+    if frame_index is not None and torch.is_grad_enabled() and (heatmaps.requires_grad or (torch.is_tensor(vol_confidences) and vol_confidences.requires_grad)):
+        raise NotImplementedError("unproject_heatmaps: frame_index is inference only (no indexed backward); call it under torch.no_grad()")
     H.require_gpu(heatmaps, "heatmaps")
     H.dtype_code(heatmaps.dtype)
     P = proj_matricies.to(heatmaps.device, torch.float32).contiguous()
@@ -152,6 +181,18 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
     conf = None
     if volume_aggregation_method.startswith("conf"):
         conf = vol_confidences.to(heatmaps.device, torch.float32).contiguous()
+    if frame_index is not None:
+        F, NV = heatmaps.shape[:2]
+        if torch.is_tensor(frame_index) and frame_index.is_cuda:
+            if frame_index.dim() != 1 or frame_index.numel() == 0 or frame_index.dtype.is_floating_point or frame_index.dtype == torch.bool:
+                raise ValueError("frame_index must be a flat list of at least one integer frame index, got %s %s" % (frame_index.dtype, tuple(frame_index.shape)))
+            fof = frame_index.to(heatmaps.device, torch.int32).contiguous()
+        else:
+            fof = torch.from_numpy(frame_index_host(frame_index, F)).to(heatmaps.device)
+        if cv.shape[0] != fof.numel():
+            raise ValueError("frame_index has %d entries, coord_volumes holds %d cuboids" % (fof.numel(), cv.shape[0]))
+        mask = None if view_mask is None else _view_mask_device(view_mask, F, NV, heatmaps.device)
+        return _unproject_launch(_as_channels_last(heatmaps, 2), P, cv, conf, volume_aggregation_method, mask, fof).permute(0, 4, 1, 2, 3)
     if view_mask is not None:
         needs_grad = torch.is_grad_enabled() and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad))
         if needs_grad and not masked_backward:
