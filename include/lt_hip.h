@@ -203,6 +203,12 @@ int lt_sel_conv_skip(int32_t dtype, const int32_t x[5], const lt_wshape* w, cons
 /* which kernel lt_conv_fwd gives a bf16 7x7x7 / stride 1 / pad 3 convolution 32 -> (9..16) of x: 1 = the column walk (>= 256 whole columns of >= 2
  * tiles of 4 x 8 x 8 voxels, their count a multiple of 8), 0 = one tile per workgroup (LT_HALO_NO_COL7: always 0) */
 int lt_sel_halo7_col(int32_t dtype, const int32_t x[5]);
+/* the bf16 MFMA of conv2d_halo_kernel's instantiation (tile_rows, nphase) = (8, 1), (4, 1) (the 3x3) or (8, 4) (the transposed 4x4): 16 = 16x16x32,
+ * 32 = 32x32x16; 0 = no such instantiation (LT_H2D_MF32: 32 everywhere) */
+int lt_sel_halo2d_mfma(int32_t tile_rows, int32_t nphase);
+/* ... and of the 3x3x3 32 -> 32 column walk's instantiation kind: 0 = bf16 store, 1 = computed skip residual (lt_conv_skip_fwd), 2 = fp32 store
+ * (always 32); 0 = no such kind (LT_HALO_COL_MF32: 32 everywhere) */
+int lt_sel_halo_col_mfma(int32_t kind);
 /* lt_conv_cat2_fwd: a Bottleneck's 1x1 expand of t2 and its 1x1 stride-s downsample of x as one launch, from 200 tiles of 288 x 256 on
  * (LT_NO_CONV_CAT2, LT_CONV_NO_V7, LT_CONV_NO_V3: off; LT_CAT2_ANY_SIZE: any size) */
 int lt_sel_conv_cat2(int32_t dtype, const int32_t t2[5], const lt_wshape* w_expand, const int32_t x[5], const lt_wshape* w_down, int32_t stride_down);

@@ -21,7 +21,8 @@
 // Dispatch (conv3d_halo_try at the end; the first row that matches launches, and an A/B switch in brackets sends its row's layers on to the rows below):
 //   bf16 3^3 32->32, >= 1024 tiles, count % 8 == 0    [LT_HALO_NO_PERSIST]
 //     every workgroup gets whole columns of >= 2 tiles  conv3d_halo_col_kernel       column walk, ring of 4-plane halo groups, epilogue under the next
-//                                                       [LT_HALO_NO_COL]             tile's MFMAs (also: fp32 store, computed skip residual)
+//                                                       [LT_HALO_NO_COL]             tile's MFMAs (also: fp32 store, computed skip residual); 16x16x32 MFMAs
+//                                                                                    except for the fp32 store (LT_HALO_COL_MF32=1: 32x32x16, same kernel)
 //     else                                              conv3d_halo_persist_kernel   persistent, weights resident, double-buffered halo
 //   bf16 3^3 64->64, 16->32, 32->64, 128->128          conv3d_halo_wreg_kernel      halo-only LDS, weights as fragments from global memory
 //     with fragment-order weights  [LT_HALO_NO_WREG]
@@ -971,7 +972,9 @@ __global__ __launch_bounds__(512) void conv3d_halo_persist_kernel(const HaloArgs
 // 64^3 level): one more MFMA per fragment on the 16 input channels of the lane's own voxel (a 16-byte load instead of the 32-byte residual), its
 // BatchNorm scale folded into the bf16 weights and its shift into `shift` by the caller.  The skip convolution's launch, its 32-channel output and that
 // tensor's read here all disappear (lt_conv_skip_fwd).
-template <typename T, bool F32OUT, bool SKIP>
+// MFS: the consumers' bf16 MFMA, 32 = 32x32x16 or 16 = 16x16x32 -- the same tile per wave, LDS image, reads and cycles per tap; the chip holds a higher clock
+// on the 16x16x32 form (DESIGN.md "MFMA shape").  The loaders and the LDS layout (C::MF = 32 names the layout) are the same for both.
+template <typename T, bool F32OUT, bool SKIP, int MFS>
 __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, const int total_cols) {
     constexpr int KS = 3, CIN = 32, CP = 32;
     typedef HaloCfg<T, KS, CIN, CP, 9, 2> C;
@@ -1101,6 +1104,198 @@ __global__ __launch_bounds__(512) void conv3d_halo_col_kernel(const HaloArgs a, 
         return;
     }
 
+    if constexpr (MFS == 16) {
+        // ================================= consumer waves, v_mfma_f32_16x16x32_bf16 =================================
+        // The same 64 voxels x 32 channels per wave, the same LDS image and the same reads per tap (four voxel fragments + two weight fragments, one
+        // ds_read_b128 each), eight accumulators of four registers.  A unit is a whole tap (K = 32).  Lane (n = l & 15, q = l >> 4):
+        //   voxel fragment f = rows 2 f, 2 f + 1 of the wave's plane: voxel (2 f + (n >> 3), (n & 1) | (n >> 2 & 1) << 1 | (n >> 1 & 1) << 2), k-vector q --
+        //     with this column order the four 16-lane groups of the read are conflict-free under the plane's swizzle for every tap (tools/halo_bank_search.py);
+        //   weight fragment s = rows chan = 16 (n >> 3) + 8 (n >> 2 & 1) + 4 s + (n & 3) of the tap's slab, k-vector q (conflict-free as stored);
+        //   result register reg of (f, s) = channel 8 q + 4 s + reg of the lane's voxel: eight consecutive channels per fragment -- one 16-byte residual load
+        //     and one 16-byte store per piece, four pieces per tile under the next tile's taps.
+        static_assert(!F32OUT, "the fp32-store instantiation keeps the 32x32x16 form");
+        constexpr int NF = 4;
+        const int n16 = lane & 15, q = lane >> 4;
+        const int vr = n16 >> 3, vc = (n16 & 1) | (((n16 >> 2) & 1) << 1) | (((n16 >> 1) & 1) << 2);
+        int abase[KS];                                    // in-plane byte offset of (voxel of fragment 0, k-vector q), per kw; the swizzle does not depend on the row
+#pragma unroll
+        for (int kw = 0; kw < KS; ++kw) abase[kw] = (vr * C::PW + vc) * CINB + ((q ^ C::fswz(0, vr, vc + kw)) << 4);
+        unsigned bbase[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int chan = 16 * (n16 >> 3) + 8 * ((n16 >> 2) & 1) + 4 * s + (n16 & 3);
+            bbase[s] = lds0 + chan * CINB + ((q ^ ((-(chan / VPR)) & (NVV - 1))) << 4);
+        }
+        constexpr int RPU = NF + 2, PDU = 2, RING = PDU + 1, NU = C::NTAPS;
+        static_assert(PDU * RPU <= 15, "lookahead exceeds the lgkmcnt counter");
+        float esc[8], esf[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c = 8 * q + e;
+            const float bi = a.bias ? a.bias[c] : 0.f, sc = a.scale ? a.scale[c] : 1.f, sf = a.shift ? a.shift[c] : 0.f;
+            esc[e] = sc;
+            esf[e] = bi * sc + sf;
+        }
+        const EpiFloors fl = epi_floors(a.flags);
+        const bool has_res = a.res != nullptr;
+        const unsigned no_res = has_res ? 0u : 0x80008000u;  // zeros -> -0.0 pairs: v + -0.0 == v
+        const size_t ldc = (size_t)a.ldc;
+        const size_t voff0 = (((size_t)wave * a.H + vr) * a.W + vc) * ldc + 8 * q;
+        const size_t vstep = (size_t)2 * a.W * ldc;          // fragment f -> two rows on
+        const size_t dstep = (size_t)TD * a.H * a.W * ldc;   // next tile of the column
+        const size_t rstep = has_res ? vstep : 0;            // without a residual every piece reads the zero page
+        constexpr int SKC = 16;                              // channels per voxel of the skip tensor
+        const size_t svoff0 = (((size_t)wave * a.H + vr) * a.W + vc) * SKC + 8 * (q & 1);
+        const size_t svstep = (size_t)2 * a.W * SKC, sdstep = (size_t)TD * a.H * a.W * SKC;
+        // SKIP: a K = 16 product as ONE 16x16x32 MFMA per fragment with the upper half of K zeroed in the WEIGHT operand (lanes q >= 2 hold zeros; the voxel
+        // operand of those lanes repeats the lane's own 16 channels, so nothing foreign is multiplied).  Chosen over v_mfma_f32_16x16x16_bf16: that form takes
+        // 8-byte operands, i.e. 8-byte scattered loads of the skip tensor; here the loads stay 16 bytes, at 8 more cycles per fragment (32 per tile of ~3.5k)
+        V16 wsk[2];
+        if constexpr (SKIP) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int r = (n16 & 7) | (s << 3) | ((n16 >> 3) << 4);
+                wsk[s].u = *(const uint4*)((const T*)a.skip_w + (size_t)(32 * (q & 1) + r) * 8);
+                if (q >= 2) wsk[s].u = make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+
+        int n, h0, w0;
+        col_of(blockIdx.x, n, h0, w0);
+        size_t tbase = (((size_t)n * a.D * a.H + h0) * a.W + w0) * ldc + voff0;
+        size_t sbase = (((size_t)n * a.D * a.H + h0) * a.W + w0) * SKC + svoff0;
+        size_t pbase = 0;                                    // output offset of the tile whose epilogue is pending
+        f32x4 sacc[2];                                       // SKIP: W_skip . x_skip of the fragment whose piece is being issued
+        f32x4 acc[NF][2], pacc[NF][2];
+        uint4 rq[NF], rqn[NF];                               // residual (SKIP: skip input) of the pending tile / of the tile being computed
+        unsigned ha[KS];
+        unsigned hd1 = 0, hd2 = 0;                           // plane base of kd = 1 minus kd = 0, kd = 2 minus kd = 1
+        V16 fa[RING][NF], fb[RING][2];
+
+        auto load_unit = [&](auto uc) {
+            constexpr int tap = decltype(uc)::value, slot = tap % RING;
+            constexpr int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
+            if constexpr (tap > 0 && tap % 9 == 0) {         // first tap of the next kd: move the fragment bases one plane on
+                const unsigned dlt = kd == 1 ? hd1 : hd2;
+#pragma unroll
+                for (int kk = 0; kk < KS; ++kk) ha[kk] += dlt;
+            }
+            static_for<0, NF>([&](auto fc) {
+                constexpr int f = decltype(fc)::value;
+                lds_read16<((kh + 2 * f) * C::PW + kw) * CINB>(fa[slot][f], ha[kw]);
+            });
+            lds_read16<tap * C::SLAB>(fb[slot][0], bbase[0]);
+            lds_read16<tap * C::SLAB>(fb[slot][1], bbase[1]);
+        };
+        auto skip_mma = [&](auto pc) {                       // SKIP: fragment p of the pending tile (its skip channels are in rq[p])
+            constexpr int p = decltype(pc)::value;
+            if constexpr (SKIP) {
+                V16 xs;
+                xs.u = rq[p];
+                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < 2; ++s) sacc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wsk[s].h, xs.h, z, 0, 0, 0);
+            }
+        };
+        auto epi_piece = [&](auto pc) {                      // piece p of the pending tile: fragment p, the lane's eight channels
+            constexpr int p = decltype(pc)::value;
+            const unsigned rr[4] = {rq[p].x | no_res, rq[p].y | no_res, rq[p].z | no_res, rq[p].w | no_res};
+            unsigned o[4];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                const int e = 2 * d, s = d >> 1, r = e & 3;
+                float v0 = fmaf(pacc[p][s][r], esc[e], esf[e]);
+                float v1 = fmaf(pacc[p][s][r + 1], esc[e + 1], esf[e + 1]);
+                v0 = epi_apply(v0, fl, SKIP ? sacc[s][r] : __uint_as_float(rr[d] << 16));
+                v1 = epi_apply(v1, fl, SKIP ? sacc[s][r + 1] : __uint_as_float(rr[d] & 0xffff0000u));
+                o[d] = pack_bf16x2(v0, v1);
+            }
+            *(uint4*)((T*)a.y + pbase + p * vstep) = make_uint4(o[0], o[1], o[2], o[3]);
+        };
+        auto tap_loop = [&](auto epi_c) {
+            constexpr bool EPI = decltype(epi_c)::value;
+            static_for<0, PDU>([&](auto uc) { load_unit(uc); });
+            static_for<0, NU>([&](auto uc) {
+                constexpr int u = decltype(uc)::value;
+                constexpr int slot = u % RING;
+                constexpr int ahead = (u + PDU < NU) ? PDU : NU - 1 - u;
+                if constexpr (u + PDU < NU) load_unit(std::integral_constant<int, u + PDU>{});
+                lgkm_wait<ahead * RPU>();
+#pragma unroll
+                for (int f = 0; f < NF; ++f) frag_ready(fa[slot][f]);
+                frag_ready(fb[slot][0]);
+                frag_ready(fb[slot][1]);
+#pragma unroll
+                for (int f = 0; f < NF; ++f)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s)               // D[co][voxel]: weights first; eight independent accumulators in rotation
+                        acc[f][s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[slot][s].h, fa[slot][f].h, acc[f][s], 0, 0, 0);
+                // the pending tile's pieces under taps 1, 4, 7, 10 (the units 2, 8, 14, 20 of the 32x32x16 form), each skip product one tap ahead of its piece
+                if constexpr (EPI && SKIP && u % 3 == 0 && u < 12) skip_mma(std::integral_constant<int, u / 3>{});
+                if constexpr (EPI && u % 3 == 1 && u < 12) epi_piece(std::integral_constant<int, u / 3>{});
+                if constexpr (u == 0) {
+                    // residual of THIS tile, requested a whole tap loop before the pieces under the next tile consume it; explicitly GLOBAL loads (flat loads
+                    // would count in lgkmcnt, which the fragment pipeline counts by hand)
+                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                    typedef const __attribute__((address_space(1))) u32x4* gq_t;
+                    const unsigned long long rb = SKIP ? (unsigned long long)(size_t)((const T*)a.skip_x + sbase)
+                                                       : has_res ? (unsigned long long)(size_t)((const T*)a.res + tbase) : zp_bits;
+                    const size_t st = SKIP ? svstep : rstep;
+                    static_for<0, NF>([&](auto pc) {
+                        constexpr int p = decltype(pc)::value;
+                        const u32x4 rv = *(gq_t)(rb + (p * st) * sizeof(T));
+                        rqn[p] = make_uint4(rv[0], rv[1], rv[2], rv[3]);
+                    });
+                }
+            });
+        };
+
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of the weight slabs (and the constants)
+        {   // the pointers the tile loop uses, in SGPRs here (see the 32x32x16 form below)
+            const void* yp_ = a.y;
+            const void* sx_ = SKIP ? a.skip_x : a.res;
+            asm volatile("" ::"s"(yp_), "s"(sx_));
+        }
+        int sidx = 0, k = 0, icol = 0;
+        const int ntile = ncol * tpc;
+        for (int ti = 0; ti < ntile; ++ti) {
+            // A: plane groups sidx, sidx + 1 have landed; every consumer is done with the tap loop of the previous tile
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            {
+                const unsigned p0 = lds_halo + ((sidx + (wave >> 2)) & 3) * GROUP_B + (wave & 3) * PLANE_B;
+                const unsigned p1 = lds_halo + ((sidx + ((wave + 1) >> 2)) & 3) * GROUP_B + ((wave + 1) & 3) * PLANE_B;
+                const unsigned p2 = lds_halo + ((sidx + ((wave + 2) >> 2)) & 3) * GROUP_B + ((wave + 2) & 3) * PLANE_B;
+                hd1 = p1 - p0; hd2 = p2 - p1;
+#pragma unroll
+                for (int kw = 0; kw < KS; ++kw) ha[kw] = p0 + abase[kw];
+            }
+#pragma unroll
+            for (int f = 0; f < NF; ++f)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[f][0][e] = acc[f][1][e] = 0.f;
+            if (ti == 0) tap_loop(std::false_type{});
+            else tap_loop(std::true_type{});
+#pragma unroll
+            for (int f = 0; f < NF; ++f) { pacc[f][0] = acc[f][0]; pacc[f][1] = acc[f][1]; rq[f] = rqn[f]; }
+            pbase = tbase;
+            ++sidx;
+            tbase += dstep;
+            sbase += sdstep;
+            if (++k == tpc) {                                // next column
+                k = 0; ++sidx;
+                if (++icol < ncol) {
+                    col_of(blockIdx.x + icol * gridDim.x, n, h0, w0);
+                    tbase = (((size_t)n * a.D * a.H + h0) * a.W + w0) * ldc + voff0;
+                    sbase = (((size_t)n * a.D * a.H + h0) * a.W + w0) * SKC + svoff0;
+                }
+            }
+        }
+        static_for<0, NF>([&](auto pc) {                     // the last tile's epilogue has nothing to hide under
+            skip_mma(pc);
+            epi_piece(pc);
+        });
+        return;
+    }
     // ================================= consumer waves =================================
     // wave = output plane td of the tile; fragment i covers rows th = 4 i + v / 8, tw = v % 8 of that plane
     const int lvb = lane >> 5;
@@ -2160,6 +2355,15 @@ int launch_halo_wreg(const HaloArgs& a, hipStream_t s) {
     return LT_OK;
 }
 
+template <typename T, bool F32OUT, bool SKIP, int MFS>
+int launch_halo_col_as(const HaloArgs& a, hipStream_t s, int grid, int lds, int total_cols) {
+    auto kern = conv3d_halo_col_kernel<T, F32OUT, SKIP, MFS>;
+    LT_OPT_IN_LDS(kern, 160 * 1024);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, a, total_cols);
+    LT_CHECK_LAUNCH("lt_conv_fwd(halo, column walk)");
+    return LT_OK;
+}
+
 template <typename T>
 int launch_halo_col(const HaloArgs& a, hipStream_t s) {
     typedef HaloCfg<T, 3, 32, 32, 9, 2> C;
@@ -2168,21 +2372,12 @@ int launch_halo_col(const HaloArgs& a, hipStream_t s) {
     const int n_cu = lt::device_cu_count8();
     const int total_cols = a.N * a.tiles_h * a.tiles_w;  // % 8 == 0 (checked by the caller)
     const int grid = total_cols < n_cu ? total_cols : n_cu;
-    if (a.skip_x) {
-        auto kern = conv3d_halo_col_kernel<T, false, true>;
-        LT_OPT_IN_LDS(kern, 160 * 1024);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS, s, a, total_cols);
-    } else if (a.flags & LT_EPI_STORE_F32) {
-        auto kern = conv3d_halo_col_kernel<T, true, false>;
-        LT_OPT_IN_LDS(kern, 160 * 1024);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS, s, a, total_cols);
-    } else {
-        auto kern = conv3d_halo_col_kernel<T, false, false>;
-        LT_OPT_IN_LDS(kern, 160 * 1024);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS, s, a, total_cols);
-    }
-    LT_CHECK_LAUNCH("lt_conv_fwd(halo, column walk)");
-    return LT_OK;
+    // the MFMA shape per instantiation: halo_col_mfma (conv_common.h; LT_HALO_COL_MF32 is read here, per launch call)
+    const int kind = a.skip_x ? 1 : (a.flags & LT_EPI_STORE_F32) ? 2 : 0;
+    const bool mf16 = halo_col_mfma(kind) == 16;
+    if (kind == 1) return mf16 ? launch_halo_col_as<T, false, true, 16>(a, s, grid, LDS, total_cols) : launch_halo_col_as<T, false, true, 32>(a, s, grid, LDS, total_cols);
+    if (kind == 2) return launch_halo_col_as<T, true, false, 32>(a, s, grid, LDS, total_cols);
+    return mf16 ? launch_halo_col_as<T, false, false, 16>(a, s, grid, LDS, total_cols) : launch_halo_col_as<T, false, false, 32>(a, s, grid, LDS, total_cols);
 }
 
 template <typename T, int KS, int CIN, int CP, int TPC, int NBUF, int PD, bool LDR, int NPH = 1>

@@ -110,6 +110,22 @@ inline bool halo2d_fits(const ConvArgs& c, int cout_pad, int nphase) {
     return true;
 }
 
+// The bf16 MFMA of conv2d_halo_kernel per instantiation (tile rows, phases): 16 = v_mfma_f32_16x16x32_bf16, 32 = 32x32x16.  The same MACs, cycles and
+// operand bytes; the chip holds a higher clock on the 16x16x32 form (DESIGN.md "MFMA shape").  LT_H2D_MF32=1 (A/B, read per launch call): 32x32x16.
+inline int halo2d_mfma(int tile_rows, int nphase) {
+    (void)tile_rows; (void)nphase;
+    return env_on("LT_H2D_MF32") ? 32 : 16;
+}
+
+// ... and of conv3d_halo_col_kernel per instantiation: kind 0 = bf16 store, 1 = computed skip residual, 2 = fp32 store (training: always 32x32x16).
+// LT_HALO_COL_MF32=1 (A/B, read per launch call): 32x32x16.
+inline int halo_col_mfma(int kind) {
+#ifdef LT_TRACE
+    return 32;          // the shader-clock accounting lives in the 32x32x16 form
+#endif
+    return kind == 2 || env_on("LT_HALO_COL_MF32") ? 32 : 16;
+}
+
 union V16 {
     uint4 u;
     f32x4 f;

@@ -42,6 +42,13 @@ extern "C" int lt_sel_halo7_col(int32_t dtype, const int32_t x[5]) {
     return halo7_col_fits(x[0], x[1], x[2], x[3]);
 }
 
+extern "C" int lt_sel_halo2d_mfma(int32_t tile_rows, int32_t nphase) {
+    if ((tile_rows != 8 && tile_rows != 4) || (nphase != 1 && nphase != 4) || (tile_rows == 4 && nphase == 4)) return 0;
+    return halo2d_mfma(tile_rows, nphase);
+}
+
+extern "C" int lt_sel_halo_col_mfma(int32_t kind) { return kind < 0 || kind > 2 ? 0 : halo_col_mfma(kind); }
+
 extern "C" int lt_sel_conv_cat2(int32_t dtype, const int32_t t2[5], const lt_wshape* we, const int32_t x[5], const lt_wshape* wd, int32_t s) {
     if (dtype != LT_BF16 || env_on("LT_NO_CONV_CAT2") || env_on("LT_CONV_NO_V7") || env_on("LT_CONV_NO_V3")) return 0;
     const int N = t2[0], Ho = t2[2], Wo = t2[3], P = t2[4];

@@ -146,6 +146,8 @@ SIGNATURES = {
     "lt_conv_chunk_samples": (i32, [i32, i64]),
     "lt_sel_conv_skip": (C.c_int, [i32, i32 * 5, C.POINTER(WShape), i32 * 5, C.POINTER(WShape)]),
     "lt_sel_halo7_col": (C.c_int, [i32, i32 * 5]),
+    "lt_sel_halo2d_mfma": (C.c_int, [i32, i32]),
+    "lt_sel_halo_col_mfma": (C.c_int, [i32]),
     "lt_sel_conv_cat2": (C.c_int, [i32, i32 * 5, C.POINTER(WShape), i32 * 5, C.POINTER(WShape), i32]),
     "lt_sel_splitk_slices": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(WShape), i32]),
     "lt_sel_bottleneck": (C.c_int, [i32, i32 * 5, WShape * 3, i32 * 3]),
