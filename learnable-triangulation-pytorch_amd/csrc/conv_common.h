@@ -211,7 +211,8 @@ int conv7_try(const ConvArgs& a, int cout_pad, int max_taps, bool pw, hipStream_
 int conv_pw_try(int dtype, const ConvArgs& a, int cout_pad, int nphase, hipStream_t s);
 // conv2d_halo.hip (3x3 256 -> 256 on 24-wide maps, input halo in LDS, weights in layout 2): 1 / 0 / < 0 as above
 int conv2d_halo_try(int dtype, const ConvArgs& a, int cout_pad, int nphase, hipStream_t s);
-// conv3d_halo.hip: 1 = launched, 0 = not applicable (fall back), < 0 = error
+// conv3d_halo.hip (the dispatcher; one unit per kernel family behind it: conv3d_halo_col / _wreg / _tile.hip, conv3d_halo7.hip, declared in
+// conv3d_halo.h): 1 = launched, 0 = not applicable (fall back), < 0 = error
 int conv3d_halo_try(int dtype, const ConvArgs& a, int cout_pad, int nphase, bool forced, hipStream_t s);
 
 }  // namespace lt

@@ -430,7 +430,7 @@ static int conv_fwd_impl(const lt_conv_desc* d, const void* x, const float* bias
     }
     if (d->dtype == LT_F32) return dispatch<float>(a, d->cout_pad, d->nphase, max_taps, d->tile, s);
     if (d->dtype == LT_FP8) {
-        // the 3^3 layers of the 64^3 / 32^3 levels: input halo in LDS (conv3d_halo.hip); bf16 stores only
+        // the 3^3 layers of the 64^3 / 32^3 levels: input halo in LDS (conv3d_halo.hip; the fp8 rows are in conv3d_halo_tile.hip); bf16 stores only
         if ((d->tile == LT_TILE_AUTO || d->tile == LT_TILE_HALO) && !(d->flags & LT_EPI_STORE_F32)) {
             const int rc = conv3d_halo_try(LT_FP8, a, d->cout_pad, d->nphase, d->tile == LT_TILE_HALO, s);
             if (rc == 1) return LT_OK;
