@@ -522,6 +522,13 @@ int lt_bn_stats_fwd(int32_t dtype, const void* x, int64_t rows, int32_t C, float
  *   slabs whose partial sums are added in a fixed order: workspace of lt_conv_wgrad_workspace(rows = N*Do*Ho*Wo, cout_pad, k_pad) bytes,
  *   may be 0).  For a transposed convolution swap the roles (dy := the layer's INPUT at its own resolution, x := the output gradient,
  *   stride 2): dw[ci][tap * Cout + co].
+ *   accumulate (here and in lt_conv_wgrad_bf16 / lt_conv_wgrad_bf16_nhwc): 0 -> every element of dw [cout_pad][k_pad] is WRITTEN (rows past Cout and
+ *   columns past ntaps * Cin with zeros; dw may hold anything before the call); 1 -> the sum is ADDED to what dw holds, one fp32 addition per
+ *   element behind the ordered slab sum (dw + (s0 + s1 + ...); a shape with a single slab adds the accumulator to dw in the kernel's own epilogue).
+ *   Leading dimensions: dy is read as [rows][ldy >= Cout] and only its channels [0, Cout) are read -- channels [Cout, ldy) may hold anything, NaN
+ *   included, and never reach dw; the LDS-brick and pointwise kernels need ldy % 4 == 0 and other values of ldy take the generic kernel.  x of
+ *   lt_conv_wgrad and both packed operands of lt_conv_wgrad_bf16 are dense in their channels (the pack takes the source's ld and drops the padding);
+ *   lt_conv_wgrad_bf16_nhwc reads x16 as [..][ldx >= Cin] with the same promise for channels [Cin, ldx).
  * lt_adam_step  : torch.optim.Adam's single-tensor update (bias-corrected, eps outside the sqrt).  beta1 / beta2 are doubles: 1 - beta and
  *   1 - beta^step are formed in fp64 and then rounded to fp32, as torch does from its Python floats (1 - 0.999f is 1.3e-5 off 0.001).
  * -------------------------------------------------------------------------------------------*/
@@ -550,7 +557,8 @@ int lt_conv_wgrad(const float* dy, const float* x, const int32_t* taps, float* d
 /* The same weight gradient on the bf16 MFMA (mixed-precision training, BASELINE config 5): the reduction index is the pixel and the 16-bit MFMA
  * wants 8 consecutive K values per lane, so the operands are IMAGE-OCTET packed -- the one axis no tap ever shifts:
  *   lt_pack_n8_bf16: src [N][P][ld >= C] fp32 (P pixels per image) -> dst [ceil(N / 8)][P][C] elements of 8 bf16 (16 bytes) = the values of images
- *   8g .. 8g+7 at that pixel and channel, zero for images past N; dst is 16-byte aligned, lt_pack_n8_bf16_bytes(N, P, C) bytes.
+ *   8g .. 8g+7 at that pixel and channel, zero for images past N; dst is 16-byte aligned, lt_pack_n8_bf16_bytes(N, P, C) bytes.  Only channels
+ *   [0, C) of a pixel are read (the padding [C, ld) may hold anything); C, ld multiples of 4 and src 16-byte aligned: the vector kernel.
  *   lt_conv_wgrad_bf16: arguments as lt_conv_wgrad with dy16 = pack of dy [N][Do*Ho*Wo][ldy] and x16 = pack of x [N][D*H*W][Cin]; fp32
  *   accumulation, fixed summation order (slabs + ordered reduce: bitwise repeatable); workspace of lt_conv_wgrad_bf16_workspace(
  *   ceil(N / 8) * Do*Ho*Wo, cout_pad, k_pad) bytes.  Result = lt_conv_wgrad of the bf16-rounded operands up to fp32 summation order. */
@@ -574,6 +582,36 @@ int lt_conv_wgrad_bf16_nhwc_ok(int32_t N, int32_t D, int32_t H, int32_t W, int32
 int lt_conv_wgrad_bf16_nhwc(const void* dy16, const void* x16, const int32_t* taps, float* dw, int32_t N, int32_t D, int32_t H, int32_t W, int32_t Cin, int32_t ldx,
                             int32_t Do, int32_t Ho, int32_t Wo, const int32_t stride[3], const int32_t pad[3], int32_t Cout, int32_t ldy, int32_t cout_pad,
                             int32_t k_pad, int32_t ntaps, int32_t accumulate, void* workspace, void* stream);
+/* What the three entry points above would launch for a shape (host only: no GPU needed, nothing is launched).  The entry points take their kernel,
+ * slab count and grid from the very functions these queries call, so the answer cannot drift from the launch.  Arguments as the entry point's, N ..
+ * ntaps; a workspace is taken as given (without one lt_conv_wgrad falls back to its generic kernel for the pointwise, 2D-brick and 7^3 shapes).
+ *   family         LT_WGRAD_GENERIC (operands straight from L2), _BRICK3D (3^3 LDS bricks), _BRICK2D (3x3 LDS bricks), _POINTWISE (LDS GEMM), _K7 (7^3)
+ *   variant        generic: the wave tile, fp32 / packed bf16 0 = 128 x 64, 1 = 64 x 128, 2 = 32 x 256 (co x k), nhwc 0 = 128 x 64, 1 = 64 x 128;
+ *                  brick kernels: input channels per workgroup (fp32 3D 32, 2D 128; bf16 16 or 32; nhwc 32); pointwise and 7^3: 0
+ *   slabs          S: partial sums the ordered reduce adds (1 for a generic kernel: no workspace, no reduce)
+ *   units          what the slabs cut: generic = GEMM rows (pixels; octet rows = ceil(N / 8) * Do*Ho*Wo for the bf16 entry points), brick / 7^3 =
+ *                  bricks over (image or octet group, d, h, w), pointwise = chunks of 32 rows
+ *   units_per_slab slab s covers units [s * units_per_slab, min(units, (s + 1) * units_per_slab)); a generic kernel's trailing slabs may be empty
+ *   grid           the main kernel's grid (x, y, z); xcd_remap: 1 when a generic kernel deals its workgroups to the XCDs in contiguous ranges
+ * Returns LT_OK, or the error the entry point would return for the shape (lt_conv_wgrad_bf16_plan with nhwc != 0: LT_ERR_UNSUPPORTED where
+ * lt_conv_wgrad_bf16_nhwc_ok says 0).  A change to any slab planner re-checks tests/test_wgrad_plan_cpu.py: it names the case that reaches each branch. */
+#define LT_WGRAD_GENERIC 0
+#define LT_WGRAD_BRICK3D 1
+#define LT_WGRAD_BRICK2D 2
+#define LT_WGRAD_POINTWISE 3
+#define LT_WGRAD_K7 4
+typedef struct lt_wgrad_plan {
+    int32_t family, variant, slabs, units_per_slab;
+    int64_t units;
+    int32_t grid[3];
+    int32_t xcd_remap;
+} lt_wgrad_plan;
+int lt_conv_wgrad_plan(int32_t N, int32_t D, int32_t H, int32_t W, int32_t Cin, int32_t Do, int32_t Ho, int32_t Wo, const int32_t stride[3], const int32_t pad[3],
+                       int32_t Cout, int32_t ldy, int32_t cout_pad, int32_t k_pad, int32_t ntaps, lt_wgrad_plan* out);
+/* nhwc = 0: lt_conv_wgrad_bf16 (ldx is ignored); nhwc = 1: lt_conv_wgrad_bf16_nhwc */
+int lt_conv_wgrad_bf16_plan(int32_t nhwc, int32_t N, int32_t D, int32_t H, int32_t W, int32_t Cin, int32_t ldx, int32_t Do, int32_t Ho, int32_t Wo,
+                            const int32_t stride[3], const int32_t pad[3], int32_t Cout, int32_t ldy, int32_t cout_pad, int32_t k_pad, int32_t ntaps,
+                            lt_wgrad_plan* out);
 /* dst[i] = idx[i] >= 0 ? src[idx[i]] : 0 -- the layout changes between a Parameter's own layout and the GEMM layouts of its layer
  * (forward weights, input-gradient weights, weight-gradient blocks), with index maps built once when a training plan is recorded */
 int lt_gather_f32(const float* src, const int32_t* idx, float* dst, int64_t n, void* stream);

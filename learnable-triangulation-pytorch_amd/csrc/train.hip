@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
     // workgroups are dealt round-robin to the 8 XCDs: give every XCD a CONTIGUOUS range of (slab, tile group) pairs, slab-major, so that
     // the tiles of one slab (same dY / X rows) and neighbouring slabs (shared halo rows / planes) meet in the same L2
     const int total = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int lin2 = (total & 7) ? lin : (lin & 7) * (total >> 3) + (lin >> 3);
+    const int lin2 = xcd_remap_on(total) ? (lin & 7) * (total >> 3) + (lin >> 3) : lin;
     const int slab = lin2 / (int)gridDim.x, tgroup = lin2 - slab * (int)gridDim.x;
     const int t = tgroup * 4 + wave;
     if (t >= a.n_tiles) return;
@@ -1147,8 +1147,6 @@ extern "C" int lt_maxpool_bwd_dt(int32_t dtype, const void* x, const void* dy, v
     return LT_OK;
 }
 
-struct BrickPlan { int nbricks, bricks_per_slab, S; };
-
 // 3x3x3, stride 1, pad 1, channel counts multiples of 32 that are their own padding, the volume a whole number of bricks
 static bool brick_ok(int N, int D, int H, int W, int Cin, int Do, int Ho, int Wo, const int32_t* stride, const int32_t* pad, int Cout, int cout_pad, int k_pad, int ntaps) {
     if (ntaps != 27 || D != Do || H != Ho || W != Wo || stride[0] != 1 || stride[1] != 1 || stride[2] != 1 || pad[0] != 1 || pad[1] != 1 || pad[2] != 1) return false;
@@ -1156,19 +1154,81 @@ static bool brick_ok(int N, int D, int H, int W, int Cin, int Do, int Ho, int Wo
     return D % BRK_D == 0 && H % BRK_H == 0 && W % BRK_W == 0 && N >= 1;
 }
 
-static BrickPlan brick_plan(int N, int D, int H, int W, int Cin, int Cout, int cout_pad, int k_pad) {
-    BrickPlan p;
-    p.nbricks = N * (D / BRK_D) * (H / BRK_H) * (W / BRK_W);
-    const long long blocks = (long long)(Cout / 32) * (Cin / 32);
-    long long S = cdiv(1024, blocks);
-    const long long cap = (48ll << 20) / ((long long)cout_pad * k_pad * 4);
-    if (S > cap) S = cap;
-    if (S > p.nbricks) S = p.nbricks;
-    if (S < 1) S = 1;
-    S = balance_slabs(blocks, S);
-    p.bricks_per_slab = (int)cdiv(p.nbricks, S);
-    p.S = (int)cdiv(p.nbricks, p.bricks_per_slab);
-    return p;
+// What lt_conv_wgrad launches for a shape: the kernel family, its slabs and its grid.  The entry point launches from this record and lt_conv_wgrad_plan
+// reports it -- the one place where these rules stand.  `workspace`: the caller gave one (the pointwise, 2D-brick and 7^3 kernels need it and
+// leave the shape to the generic kernel without)
+struct WgradRoute {
+    int family, variant;
+    WgradPlan g;             // generic kernel
+    SlabPlan s;              // LDS kernels: bricks / chunks
+    dim3 grid;
+};
+
+static WgradRoute wgrad_route(int N, int D, int H, int W, int Cin, int Do, int Ho, int Wo, const int32_t* stride, const int32_t* pad, int Cout, int ldy, int cout_pad,
+                              int k_pad, int ntaps, bool workspace) {
+    WgradRoute r;
+    r.variant = 0; r.g = WgradPlan{0, 0, 0, 0, 0}; r.s = SlabPlan{0, 0, 0};
+    const long long M = (long long)N * Do * Ho * Wo;
+    const long long cap_slabs = (48ll << 20) / ((long long)cout_pad * k_pad * 4);
+    if (ldy % 4 == 0 && brick_ok(N, D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, cout_pad, k_pad, ntaps)) {          // (float4 rows of dY)
+        const long long blocks = (long long)(Cout / 32) * (Cin / 32);
+        r.family = LT_WGRAD_BRICK3D; r.variant = 32;
+        r.s = slab_plan((long long)N * (D / BRK_D) * (H / BRK_H) * (W / BRK_W), cdiv(1024, blocks), cap_slabs, blocks);
+        r.grid = dim3(Cout / 32, Cin / 32, (unsigned)r.s.S);
+        return r;
+    }
+    const bool unit = stride[0] == 1 && stride[1] == 1 && stride[2] == 1 && D == Do && H == Ho && W == Wo;
+    if (unit && ntaps == 1 && pad[0] == 0 && pad[1] == 0 && pad[2] == 0 && Cout % 4 == 0 && Cin % 4 == 0 && ldy % 4 == 0 && k_pad == Cin && Cout >= 64 && Cin >= 64 &&
+        workspace) {
+        // the bottleneck 1x1 layers: LDS-tiled GEMM
+        const long long tiles = cdiv(cout_pad, 128) * cdiv(k_pad, 128);
+        r.family = LT_WGRAD_POINTWISE;
+        r.s = slab_plan(cdiv(M, PW_R), cdiv(768, tiles), cap_slabs, tiles);
+        r.grid = dim3((unsigned)cdiv(cout_pad, 128), (unsigned)cdiv(k_pad, 128), (unsigned)r.s.S);
+        return r;
+    }
+    if (unit && ntaps == 9 && D == 1 && pad[0] == 0 && pad[1] == 1 && pad[2] == 1 && H % B2_H == 0 && W % B2_W == 0 && Cout % 32 == 0 && Cin % 32 == 0 && ldy % 4 == 0 &&
+        cout_pad >= Cout && k_pad == 9 * Cin && workspace) {
+        // the backbone's 3x3 layers (taps in (kh, kw) order): LDS bricks
+        const long long blocks = (long long)(Cout / 32) * cdiv(Cin, 128);
+        r.family = LT_WGRAD_BRICK2D; r.variant = 128;
+        r.s = slab_plan((long long)N * (H / B2_H) * (W / B2_W), cdiv(768, blocks), cap_slabs, blocks);
+        r.grid = dim3(Cout / 32, (unsigned)cdiv(Cin, 128), (unsigned)r.s.S);
+        return r;
+    }
+    if (unit && ntaps == 343 && pad[0] == 3 && pad[1] == 3 && pad[2] == 3 && Cin == 32 && Cout == 16 && cout_pad == 16 && k_pad == 343 * 32 && ldy >= 16 && ldy % 4 == 0 &&
+        D % BRK_D == 0 && H % BRK_H == 0 && W % BRK_W == 0 && workspace) {
+        r.family = LT_WGRAD_K7;
+        r.s = slab_plan((long long)N * (D / BRK_D) * (H / BRK_H) * (W / BRK_W), 73, cap_slabs, 0);          // 7 kd planes x 73 slabs = 511 workgroups, two per CU
+        r.grid = dim3(7, 1, (unsigned)r.s.S);
+        return r;
+    }
+    r.family = LT_WGRAD_GENERIC;
+    r.g = wgrad_plan(M, cout_pad, k_pad);
+    r.variant = r.g.variant;
+    r.grid = dim3((unsigned)cdiv(r.g.n_co_t * r.g.n_k_t, 4), (unsigned)r.g.S);
+    return r;
+}
+
+// the argument checks of lt_conv_wgrad (its plan query refuses what the entry point refuses)
+static int wgrad_check(int N, int D, int H, int W, int Cin, int Do, int Ho, int Wo, int Cout, int ldy, int cout_pad, int k_pad, int ntaps) {
+    LT_REQUIRE(ilog2_exact(Cin) >= 0, LT_ERR_UNSUPPORTED, "lt_conv_wgrad: Cin=%d must be a power of two", Cin);
+    LT_REQUIRE(Cout >= 1 && ldy >= Cout && cout_pad >= Cout && k_pad >= ntaps * Cin && ntaps >= 1, LT_ERR_INVALID, "lt_conv_wgrad: bad sizes");
+    const long long M = (long long)N * Do * Ho * Wo;
+    LT_REQUIRE(M >= 1 && M < (1ll << 31) && (long long)N * D * H * W * Cin < (1ll << 31) && M * ldy < (1ll << 40), LT_ERR_UNSUPPORTED,
+               "lt_conv_wgrad: too many rows / elements for 32-bit offsets");
+    return LT_OK;
+}
+
+extern "C" int lt_conv_wgrad_plan(int32_t N, int32_t D, int32_t H, int32_t W, int32_t Cin, int32_t Do, int32_t Ho, int32_t Wo, const int32_t stride[3],
+                                  const int32_t pad[3], int32_t Cout, int32_t ldy, int32_t cout_pad, int32_t k_pad, int32_t ntaps, lt_wgrad_plan* out) {
+    LT_REQUIRE(stride && pad && out, LT_ERR_INVALID, "lt_conv_wgrad_plan: null argument");
+    const int rc = wgrad_check(N, D, H, W, Cin, Do, Ho, Wo, Cout, ldy, cout_pad, k_pad, ntaps);
+    if (rc != LT_OK) return rc;
+    const WgradRoute r = wgrad_route(N, D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, ldy, cout_pad, k_pad, ntaps, true);
+    if (r.family == LT_WGRAD_GENERIC) fill_wgrad_plan(out, r.family, r.variant, r.g.S, (long long)N * Do * Ho * Wo, r.g.rows_per_slab, r.grid);
+    else fill_wgrad_plan(out, r.family, r.variant, r.s.S, r.s.units, r.s.per_slab, r.grid);
+    return LT_OK;
 }
 
 extern "C" size_t lt_conv_wgrad_workspace(int64_t rows, int32_t cout_pad, int32_t k_pad) {
@@ -1189,93 +1249,58 @@ extern "C" int lt_conv_wgrad(const float* dy, const float* x, const int32_t* tap
                              int32_t Do, int32_t Ho, int32_t Wo, const int32_t stride[3], const int32_t pad[3], int32_t Cout, int32_t ldy,
                              int32_t cout_pad, int32_t k_pad, int32_t ntaps, int32_t accumulate, void* workspace, void* stream) {
     LT_REQUIRE(dy && x && taps && dw && stride && pad, LT_ERR_INVALID, "lt_conv_wgrad: null argument");
+    const int rc = wgrad_check(N, D, H, W, Cin, Do, Ho, Wo, Cout, ldy, cout_pad, k_pad, ntaps);
+    if (rc != LT_OK) return rc;
     const int l2 = ilog2_exact(Cin);
-    LT_REQUIRE(l2 >= 0, LT_ERR_UNSUPPORTED, "lt_conv_wgrad: Cin=%d must be a power of two", Cin);
-    LT_REQUIRE(Cout >= 1 && ldy >= Cout && cout_pad >= Cout && k_pad >= ntaps * Cin && ntaps >= 1, LT_ERR_INVALID, "lt_conv_wgrad: bad sizes");
-    const long long M = (long long)N * Do * Ho * Wo;
-    LT_REQUIRE(M >= 1 && M < (1ll << 31) && (long long)N * D * H * W * Cin < (1ll << 31) && M * ldy < (1ll << 40), LT_ERR_UNSUPPORTED,
-               "lt_conv_wgrad: too many rows / elements for 32-bit offsets");
+    const long long M = (long long)N * Do * Ho * Wo, n = (long long)cout_pad * k_pad;
     hipStream_t st = (hipStream_t)stream;
-    if (ldy % 4 == 0 && brick_ok(N, D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, cout_pad, k_pad, ntaps)) {          // (float4 rows of dY)
-        const BrickPlan bp = brick_plan(N, D, H, W, Cin, Cout, cout_pad, k_pad);
+    const WgradRoute r = wgrad_route(N, D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, ldy, cout_pad, k_pad, ntaps, workspace != nullptr);
+    if (r.family == LT_WGRAD_BRICK3D) {
         LT_REQUIRE(workspace, LT_ERR_INVALID, "lt_conv_wgrad: this shape needs a workspace of lt_conv_wgrad_workspace() bytes");
         BrickArgs b;
         b.dy = dy; b.x = x; b.taps = (const int4*)taps; b.out = (float*)workspace;
         b.N = N; b.D = D; b.H = H; b.W = W; b.Cin = Cin; b.ldy = ldy; b.cout_pad = cout_pad; b.k_pad = k_pad;
-        b.nbd = D / BRK_D; b.nbh = H / BRK_H; b.nbw = W / BRK_W; b.nbricks = bp.nbricks; b.bricks_per_slab = bp.bricks_per_slab;
-        hipLaunchKernelGGL(conv3d_wgrad_brick_kernel, dim3(Cout / 32, Cin / 32, bp.S), dim3(256), 0, st, b);
+        b.nbd = D / BRK_D; b.nbh = H / BRK_H; b.nbw = W / BRK_W; b.nbricks = r.s.units; b.bricks_per_slab = r.s.per_slab;
+        hipLaunchKernelGGL(conv3d_wgrad_brick_kernel, r.grid, dim3(256), 0, st, b);
         LT_CHECK_LAUNCH("lt_conv_wgrad(brick)");
-        const long long n = (long long)cout_pad * k_pad;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, bp.S,
-                           accumulate);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, r.s.S, accumulate);
         LT_CHECK_LAUNCH("lt_conv_wgrad(reduce)");
         return LT_OK;
     }
-    const bool unit = stride[0] == 1 && stride[1] == 1 && stride[2] == 1 && D == Do && H == Ho && W == Wo;
-    const long long cap_slabs = (48ll << 20) / ((long long)cout_pad * k_pad * 4);
-    if (unit && ntaps == 1 && pad[0] == 0 && pad[1] == 0 && pad[2] == 0 && Cout % 4 == 0 && Cin % 4 == 0 && ldy % 4 == 0 && k_pad == Cin && Cout >= 64 && Cin >= 64 &&
-        workspace) {
-        // the bottleneck 1x1 layers: LDS-tiled GEMM
+    if (r.family == LT_WGRAD_POINTWISE) {
         PwArgs b;
         b.dy = dy; b.x = x; b.out = (float*)workspace; b.M = (int)M; b.Cout = Cout; b.Cin = Cin; b.ldy = ldy; b.cout_pad = cout_pad; b.k_pad = k_pad;
-        b.chunks = (int)cdiv(M, PW_R);
-        const long long tiles = cdiv(cout_pad, 128) * cdiv(k_pad, 128);
-        long long S = cdiv(768, tiles);
-        S = S > cap_slabs ? cap_slabs : S;
-        S = S > b.chunks ? b.chunks : S;
-        S = S < 1 ? 1 : S;
-        S = balance_slabs(tiles, S);
-        b.chunks_per_slab = (int)cdiv(b.chunks, S);
-        S = cdiv(b.chunks, b.chunks_per_slab);
-        hipLaunchKernelGGL(wgrad_pw_kernel, dim3((unsigned)cdiv(cout_pad, 128), (unsigned)cdiv(k_pad, 128), (unsigned)S), dim3(256), 0, st, b);
+        b.chunks = r.s.units; b.chunks_per_slab = r.s.per_slab;
+        hipLaunchKernelGGL(wgrad_pw_kernel, r.grid, dim3(256), 0, st, b);
         LT_CHECK_LAUNCH("lt_conv_wgrad(pointwise)");
-        const long long n = (long long)cout_pad * k_pad;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, (int)S, accumulate);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, r.s.S, accumulate);
         LT_CHECK_LAUNCH("lt_conv_wgrad(reduce)");
         return LT_OK;
     }
-    if (unit && ntaps == 9 && D == 1 && pad[0] == 0 && pad[1] == 1 && pad[2] == 1 && H % B2_H == 0 && W % B2_W == 0 && Cout % 32 == 0 && Cin % 32 == 0 && ldy % 4 == 0 &&
-        cout_pad >= Cout && k_pad == 9 * Cin && workspace) {
-        // the backbone's 3x3 layers (taps in (kh, kw) order): LDS bricks
+    if (r.family == LT_WGRAD_BRICK2D) {
         Brick2Args b;
         b.dy = dy; b.x = x; b.out = (float*)workspace; b.N = N; b.H = H; b.W = W; b.Cin = Cin; b.Cout = Cout; b.ldy = ldy; b.cout_pad = cout_pad; b.k_pad = k_pad;
-        b.nbh = H / B2_H; b.nbw = W / B2_W; b.nbricks = N * b.nbh * b.nbw;
-        const long long blocks = (long long)(Cout / 32) * cdiv(Cin, 128);
-        long long S = cdiv(768, blocks);
-        S = S > cap_slabs ? cap_slabs : S;
-        S = S > b.nbricks ? b.nbricks : S;
-        S = S < 1 ? 1 : S;
-        S = balance_slabs(blocks, S);
-        b.bricks_per_slab = (int)cdiv(b.nbricks, S);
-        S = cdiv(b.nbricks, b.bricks_per_slab);
+        b.nbh = H / B2_H; b.nbw = W / B2_W; b.nbricks = r.s.units; b.bricks_per_slab = r.s.per_slab;
         if (cout_pad > Cout)          // rows past Cout are not written by the kernel
-            LT_REQUIRE(hipMemsetAsync(workspace, 0, (size_t)S * cout_pad * k_pad * sizeof(float), st) == hipSuccess, LT_ERR_LAUNCH, "lt_conv_wgrad: memset failed");
-        hipLaunchKernelGGL(conv2d_wgrad_brick_kernel, dim3(Cout / 32, (unsigned)cdiv(Cin, 128), (unsigned)S), dim3(256), 0, st, b);
+            LT_REQUIRE(hipMemsetAsync(workspace, 0, (size_t)r.s.S * cout_pad * k_pad * sizeof(float), st) == hipSuccess, LT_ERR_LAUNCH, "lt_conv_wgrad: memset failed");
+        hipLaunchKernelGGL(conv2d_wgrad_brick_kernel, r.grid, dim3(256), 0, st, b);
         LT_CHECK_LAUNCH("lt_conv_wgrad(brick2d)");
-        const long long n = (long long)cout_pad * k_pad;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, (int)S, accumulate);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, r.s.S, accumulate);
         LT_CHECK_LAUNCH("lt_conv_wgrad(reduce)");
         return LT_OK;
     }
-    if (unit && ntaps == 343 && pad[0] == 3 && pad[1] == 3 && pad[2] == 3 && Cin == 32 && Cout == 16 && cout_pad == 16 && k_pad == 343 * 32 && ldy >= 16 && ldy % 4 == 0 &&
-        D % BRK_D == 0 && H % BRK_H == 0 && W % BRK_W == 0 && workspace) {
+    if (r.family == LT_WGRAD_K7) {
         BrickArgs b;
         b.dy = dy; b.x = x; b.taps = (const int4*)taps; b.out = (float*)workspace;
         b.N = N; b.D = D; b.H = H; b.W = W; b.Cin = Cin; b.ldy = ldy; b.cout_pad = cout_pad; b.k_pad = k_pad;
-        b.nbd = D / BRK_D; b.nbh = H / BRK_H; b.nbw = W / BRK_W; b.nbricks = N * b.nbd * b.nbh * b.nbw;
-        long long S = 73;                              // 7 kd planes x 73 slabs = 511 workgroups, two per CU
-        S = S > cap_slabs ? cap_slabs : S;
-        S = S > b.nbricks ? b.nbricks : S;
-        b.bricks_per_slab = (int)cdiv(b.nbricks, S);
-        S = cdiv(b.nbricks, b.bricks_per_slab);
-        hipLaunchKernelGGL(conv3d_wgrad_k7_kernel, dim3(7, 1, (unsigned)S), dim3(256), 0, st, b);
+        b.nbd = D / BRK_D; b.nbh = H / BRK_H; b.nbw = W / BRK_W; b.nbricks = r.s.units; b.bricks_per_slab = r.s.per_slab;
+        hipLaunchKernelGGL(conv3d_wgrad_k7_kernel, r.grid, dim3(256), 0, st, b);
         LT_CHECK_LAUNCH("lt_conv_wgrad(7^3)");
-        const long long n = (long long)cout_pad * k_pad;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, (int)S, accumulate);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, r.s.S, accumulate);
         LT_CHECK_LAUNCH("lt_conv_wgrad(reduce)");
         return LT_OK;
     }
-    const WgradPlan p = wgrad_plan(M, cout_pad, k_pad);
+    const WgradPlan& p = r.g;
     LT_REQUIRE(p.S == 1 || workspace, LT_ERR_INVALID, "lt_conv_wgrad: this shape needs a workspace of lt_conv_wgrad_workspace() bytes");
     WgradArgs a;
     a.dy = dy; a.x = x; a.taps = (const int4*)taps; a.out = p.S > 1 ? (float*)workspace : dw;
@@ -1284,13 +1309,11 @@ extern "C" int lt_conv_wgrad(const float* dy, const float* x, const int32_t* tap
     a.Cout = Cout; a.ldy = ldy; a.k_pad = k_pad; a.ntaps = ntaps; a.M = (int)M; a.accumulate = accumulate; a.cout_pad = cout_pad;
     a.n_k_t = p.n_k_t; a.n_tiles = p.n_co_t * p.n_k_t; a.rows_per_slab = p.rows_per_slab;
 
-    const dim3 grid((unsigned)cdiv(a.n_tiles, 4), (unsigned)p.S);
-    if (p.variant == 0) hipLaunchKernelGGL((conv_wgrad_kernel<4, 2>), grid, dim3(256), 0, st, a);
-    else if (p.variant == 1) hipLaunchKernelGGL((conv_wgrad_kernel<2, 4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<1, 8>), grid, dim3(256), 0, st, a);
+    if (p.variant == 0) hipLaunchKernelGGL((conv_wgrad_kernel<4, 2>), r.grid, dim3(256), 0, st, a);
+    else if (p.variant == 1) hipLaunchKernelGGL((conv_wgrad_kernel<2, 4>), r.grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_wgrad_kernel<1, 8>), r.grid, dim3(256), 0, st, a);
     LT_CHECK_LAUNCH("lt_conv_wgrad");
     if (p.S > 1) {
-        const long long n = (long long)cout_pad * k_pad;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, p.S,
                            accumulate);
         LT_CHECK_LAUNCH("lt_conv_wgrad(reduce)");

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad16_kernel(const W16Args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // every XCD gets a contiguous range of (slab, tile group) pairs, slab-major: the tiles of one slab (same dY / X rows) meet in one L2
     const int total = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int lin2 = (total & 7) ? lin : (lin & 7) * (total >> 3) + (lin >> 3);
+    const int lin2 = xcd_remap_on(total) ? (lin & 7) * (total >> 3) + (lin >> 3) : lin;
     const int slab = lin2 / (int)gridDim.x, tgroup = lin2 - slab * (int)gridDim.x;
     const int t = tgroup * 4 + wave;
     if (t >= a.n_tiles) return;
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256) void conv_wgrad16u_kernel(const W16UArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem16[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int total = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;          // XCD-contiguous (slab, tile) ranges, slab-major
-    const int lin2 = (total & 7) ? lin : (lin & 7) * (total >> 3) + (lin >> 3);
+    const int lin2 = xcd_remap_on(total) ? (lin & 7) * (total >> 3) + (lin >> 3) : lin;
     const int slab = lin2 / (int)gridDim.x, t = lin2 - slab * (int)gridDim.x;
     const int co0 = (t / a.n_k_t) * (16 * ACH), k0 = (t % a.n_k_t) * (16 * BCH);
     const int i = lane & 15, q = lane >> 4;
@@ -833,6 +833,58 @@ void reduce16(const void* workspace, float* dw, long long n, int S, int accumula
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(reduce_grid(n)), dim3(256), 0, st, (const float*)workspace, dw, n, S, accumulate);
 }
 
+// What lt_conv_wgrad_bf16 (nhwc = false) / lt_conv_wgrad_bf16_nhwc (true, on a shape lt_conv_wgrad_bf16_nhwc_ok accepts) launches: the kernel family, its
+// slabs and its grid.  The entry points launch from this record and lt_conv_wgrad_bf16_plan reports it -- the one place where these rules stand.
+// `workspace`: the caller gave one (the packed 7^3 kernel leaves the shape to the generic kernel without)
+struct Route16 {
+    int family, variant;     // brick: variant = ci per workgroup
+    Plan16 g;                // generic kernels
+    SlabPlan s;              // LDS kernels: bricks
+    dim3 grid;
+};
+
+Route16 route16(bool nhwc, int N, int D, int H, int W, int Cin, int Do, int Ho, int Wo, const int32_t* stride, const int32_t* pad, int Cout, int ldy, int cout_pad, int k_pad,
+                int ntaps, bool workspace) {
+    Route16 r;
+    r.variant = 0; r.g = Plan16{0, 0, 0, 0, 0}; r.s = SlabPlan{0, 0, 0};
+    const int G = (int)cdiv(N, 8);
+    const long long M = (long long)G * Do * Ho * Wo, n = (long long)cout_pad * k_pad;
+    const long long cap = (long long)(lt_conv_wgrad_bf16_workspace(M, cout_pad, k_pad) / ((size_t)n * 4));
+    const bool unit = stride[0] == 1 && stride[1] == 1 && stride[2] == 1 && D == Do && H == Ho && W == Wo;
+    if (brick16_ok(D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, cout_pad, k_pad, ntaps)) {
+        const int cib = nhwc || Cin >= 32 ? 32 : Cin;
+        const long long blocks = (long long)(Cout / 32) * (Cin / cib);
+        r.family = LT_WGRAD_BRICK3D; r.variant = cib;
+        r.s = slab_plan((long long)G * (D / B16_D) * (H / B16_H) * (W / B16_W), cdiv(256, blocks), cap, 0);          // one workgroup per CU (96 KB of LDS each): exactly one round
+        r.grid = dim3(Cout / 32, Cin / cib, (unsigned)r.s.S);
+        return r;
+    }
+    if (!nhwc && unit && ntaps == 343 && pad[0] == 3 && pad[1] == 3 && pad[2] == 3 && Cin == 32 && Cout == 16 && cout_pad == 16 && k_pad == 343 * 32 && ldy >= 16 &&
+        H % K16_H == 0 && W % K16_W == 0 && workspace) {
+        r.family = LT_WGRAD_K7;
+        r.s = slab_plan((long long)G * D * (H / K16_H) * (W / K16_W), 73, cap, 0);          // 7 kd planes x 73 slabs = 511 workgroups, two per CU
+        r.grid = dim3(7, 1, (unsigned)r.s.S);
+        return r;
+    }
+    r.family = LT_WGRAD_GENERIC;
+    r.g = nhwc ? plan16u(M, cout_pad, k_pad) : plan16(M, cout_pad, k_pad);
+    r.variant = r.g.variant;
+    const int n_tiles = r.g.n_co_t * r.g.n_k_t;          // packed: a tile per wave; nhwc: a tile per workgroup
+    r.grid = dim3((unsigned)(nhwc ? n_tiles : cdiv(n_tiles, 4)), (unsigned)r.g.S);
+    return r;
+}
+
+// the argument checks of lt_conv_wgrad_bf16 (its plan query refuses what the entry point refuses)
+int check16(int N, int D, int H, int W, int Cin, int Do, int Ho, int Wo, int Cout, int ldy, int cout_pad, int k_pad, int ntaps) {
+    LT_REQUIRE(ilog2_exact(Cin) >= 0, LT_ERR_UNSUPPORTED, "lt_conv_wgrad_bf16: Cin=%d must be a power of two", Cin);
+    LT_REQUIRE(Cout >= 1 && ldy >= Cout && cout_pad >= Cout && k_pad >= ntaps * Cin && ntaps >= 1 && N >= 1, LT_ERR_INVALID, "lt_conv_wgrad_bf16: bad sizes");
+    const int G = (int)cdiv(N, 8);
+    const long long M = (long long)G * Do * Ho * Wo;
+    LT_REQUIRE(M >= 1 && M < (1ll << 31) && (long long)G * D * H * W * Cin < (1ll << 31) && M * ldy < (1ll << 40), LT_ERR_UNSUPPORTED,
+               "lt_conv_wgrad_bf16: too many rows / elements for 32-bit offsets");
+    return LT_OK;
+}
+
 }  // namespace
 
 extern "C" size_t lt_pack_n8_bf16_bytes(int32_t N, int64_t P, int32_t C) {
@@ -882,60 +934,41 @@ extern "C" int lt_conv_wgrad_bf16(const void* dy16, const void* x16, const int32
                                   int32_t Do, int32_t Ho, int32_t Wo, const int32_t stride[3], const int32_t pad[3], int32_t Cout, int32_t ldy,
                                   int32_t cout_pad, int32_t k_pad, int32_t ntaps, int32_t accumulate, void* workspace, void* stream) {
     LT_REQUIRE(dy16 && x16 && taps && dw && stride && pad, LT_ERR_INVALID, "lt_conv_wgrad_bf16: null argument");
+    const int rc = check16(N, D, H, W, Cin, Do, Ho, Wo, Cout, ldy, cout_pad, k_pad, ntaps);
+    if (rc != LT_OK) return rc;
     const int l2 = ilog2_exact(Cin);
-    LT_REQUIRE(l2 >= 0, LT_ERR_UNSUPPORTED, "lt_conv_wgrad_bf16: Cin=%d must be a power of two", Cin);
-    LT_REQUIRE(Cout >= 1 && ldy >= Cout && cout_pad >= Cout && k_pad >= ntaps * Cin && ntaps >= 1 && N >= 1, LT_ERR_INVALID, "lt_conv_wgrad_bf16: bad sizes");
     const int G = (int)cdiv(N, 8);
     const long long M = (long long)G * Do * Ho * Wo;
-    LT_REQUIRE(M >= 1 && M < (1ll << 31) && (long long)G * D * H * W * Cin < (1ll << 31) && M * ldy < (1ll << 40), LT_ERR_UNSUPPORTED,
-               "lt_conv_wgrad_bf16: too many rows / elements for 32-bit offsets");
     hipStream_t st = (hipStream_t)stream;
     const long long n = (long long)cout_pad * k_pad;
-    const size_t ws_bytes = lt_conv_wgrad_bf16_workspace(M, cout_pad, k_pad);
-    const bool unit = stride[0] == 1 && stride[1] == 1 && stride[2] == 1 && D == Do && H == Ho && W == Wo;
-    if (brick16_ok(D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, cout_pad, k_pad, ntaps)) {
+    const Route16 r = route16(false, N, D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, ldy, cout_pad, k_pad, ntaps, workspace != nullptr);
+    if (r.family == LT_WGRAD_BRICK3D) {
         LT_REQUIRE(workspace, LT_ERR_INVALID, "lt_conv_wgrad_bf16: this shape needs a workspace of lt_conv_wgrad_bf16_workspace() bytes");
         Brick16Args b;
         b.dy = (const uint4*)dy16; b.x = (const uint4*)x16; b.taps = (const int4*)taps; b.out = (float*)workspace;
         b.D = D; b.H = H; b.W = W; b.Cin = Cin; b.ldy = ldy; b.cout_pad = cout_pad; b.k_pad = k_pad;
-        b.cib = Cin < 32 ? Cin : 32; b.nblk = (int)cdiv(27 * b.cib, 32);
-        b.nbd = D / B16_D; b.nbh = H / B16_H; b.nbw = W / B16_W; b.nbricks = G * b.nbd * b.nbh * b.nbw;
-        const long long blocks = (long long)(Cout / 32) * (Cin / b.cib);
-        long long S = cdiv(256, blocks);                  // one workgroup per CU (96 KB of LDS each): exactly one round
-        const long long cap = (long long)(ws_bytes / ((size_t)n * 4));
-        S = S > cap ? cap : S;
-        S = S > b.nbricks ? b.nbricks : S;
-        S = S < 1 ? 1 : S;
-        b.bricks_per_slab = (int)cdiv(b.nbricks, S);
-        S = cdiv(b.nbricks, b.bricks_per_slab);
+        b.cib = r.variant; b.nblk = (int)cdiv(27 * b.cib, 32);
+        b.nbd = D / B16_D; b.nbh = H / B16_H; b.nbw = W / B16_W; b.nbricks = r.s.units; b.bricks_per_slab = r.s.per_slab;
         const size_t lds = (size_t)(B16_HVOX * b.cib + B16_VOX * 32) * 16;
-        if (b.cib == 32) hipLaunchKernelGGL(conv3d_wgrad16_brick_kernel<32>, dim3(Cout / 32, Cin / 32, (unsigned)S), dim3(256), lds, st, b);
-        else hipLaunchKernelGGL(conv3d_wgrad16_brick_kernel<16>, dim3(Cout / 32, 1, (unsigned)S), dim3(256), lds, st, b);
+        if (b.cib == 32) hipLaunchKernelGGL(conv3d_wgrad16_brick_kernel<32>, r.grid, dim3(256), lds, st, b);
+        else hipLaunchKernelGGL(conv3d_wgrad16_brick_kernel<16>, r.grid, dim3(256), lds, st, b);
         LT_CHECK_LAUNCH("lt_conv_wgrad_bf16(brick)");
-        reduce16(workspace, dw, n, (int)S, accumulate, st);
+        reduce16(workspace, dw, n, r.s.S, accumulate, st);
         LT_CHECK_LAUNCH("lt_conv_wgrad_bf16(reduce)");
         return LT_OK;
     }
-    if (unit && ntaps == 343 && pad[0] == 3 && pad[1] == 3 && pad[2] == 3 && Cin == 32 && Cout == 16 && cout_pad == 16 && k_pad == 343 * 32 && ldy >= 16 &&
-        H % K16_H == 0 && W % K16_W == 0 && workspace) {
+    if (r.family == LT_WGRAD_K7) {
         Brick16Args b;
         b.dy = (const uint4*)dy16; b.x = (const uint4*)x16; b.taps = (const int4*)taps; b.out = (float*)workspace;
         b.D = D; b.H = H; b.W = W; b.Cin = Cin; b.ldy = ldy; b.cout_pad = cout_pad; b.k_pad = k_pad; b.cib = 32; b.nblk = 0;
-        b.nbd = D; b.nbh = H / K16_H; b.nbw = W / K16_W; b.nbricks = G * b.nbd * b.nbh * b.nbw;
-        long long S = 73;                                  // 7 kd planes x 73 slabs = 511 workgroups, two per CU
-        const long long cap = (long long)(ws_bytes / ((size_t)n * 4));
-        S = S > cap ? cap : S;
-        S = S > b.nbricks ? b.nbricks : S;
-        S = S < 1 ? 1 : S;
-        b.bricks_per_slab = (int)cdiv(b.nbricks, S);
-        S = cdiv(b.nbricks, b.bricks_per_slab);
-        hipLaunchKernelGGL(conv3d_wgrad16_k7_kernel, dim3(7, 1, (unsigned)S), dim3(256), 0, st, b);
+        b.nbd = D; b.nbh = H / K16_H; b.nbw = W / K16_W; b.nbricks = r.s.units; b.bricks_per_slab = r.s.per_slab;
+        hipLaunchKernelGGL(conv3d_wgrad16_k7_kernel, r.grid, dim3(256), 0, st, b);
         LT_CHECK_LAUNCH("lt_conv_wgrad_bf16(7^3)");
-        reduce16(workspace, dw, n, (int)S, accumulate, st);
+        reduce16(workspace, dw, n, r.s.S, accumulate, st);
         LT_CHECK_LAUNCH("lt_conv_wgrad_bf16(reduce)");
         return LT_OK;
     }
-    const Plan16 p = plan16(M, cout_pad, k_pad);
+    const Plan16& p = r.g;
     LT_REQUIRE(p.S == 1 || workspace, LT_ERR_INVALID, "lt_conv_wgrad_bf16: this shape needs a workspace of lt_conv_wgrad_bf16_workspace() bytes");
     W16Args a;
     a.dy = (const uint4*)dy16; a.x = (const uint4*)x16; a.taps = (const int4*)taps; a.out = p.S > 1 ? (float*)workspace : dw;
@@ -943,10 +976,9 @@ extern "C" int lt_conv_wgrad_bf16(const void* dy16, const void* x16, const int32
     a.sd = stride[0]; a.sh = stride[1]; a.sw = stride[2]; a.pd = pad[0]; a.ph = pad[1]; a.pw = pad[2];
     a.Cout = Cout; a.ldy = ldy; a.k_pad = k_pad; a.ntaps = ntaps; a.M = (int)M; a.accumulate = accumulate; a.cout_pad = cout_pad;
     a.n_k_t = p.n_k_t; a.n_tiles = p.n_co_t * p.n_k_t; a.rows_per_slab = p.rows_per_slab;
-    const dim3 grid((unsigned)cdiv(a.n_tiles, 4), (unsigned)p.S);
-    if (p.variant == 0) hipLaunchKernelGGL((conv_wgrad16_kernel<4, 2, 3>), grid, dim3(256), 0, st, a);
-    else if (p.variant == 1) hipLaunchKernelGGL((conv_wgrad16_kernel<2, 4, 3>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_wgrad16_kernel<1, 8, 2>), grid, dim3(256), 0, st, a);
+    if (p.variant == 0) hipLaunchKernelGGL((conv_wgrad16_kernel<4, 2, 3>), r.grid, dim3(256), 0, st, a);
+    else if (p.variant == 1) hipLaunchKernelGGL((conv_wgrad16_kernel<2, 4, 3>), r.grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_wgrad16_kernel<1, 8, 2>), r.grid, dim3(256), 0, st, a);
     LT_CHECK_LAUNCH("lt_conv_wgrad_bf16");
     if (p.S > 1) {
         reduce16(workspace, dw, n, p.S, accumulate, st);
@@ -986,29 +1018,21 @@ extern "C" int lt_conv_wgrad_bf16_nhwc(const void* dy16, const void* x16, const 
     hipStream_t st = (hipStream_t)stream;
     const int G = (int)cdiv(N, 8);
     const long long M = (long long)G * Do * Ho * Wo, n = (long long)cout_pad * k_pad;
-    if (brick16_ok(D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, cout_pad, k_pad, ntaps)) {
+    const Route16 r = route16(true, N, D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, ldy, cout_pad, k_pad, ntaps, workspace != nullptr);
+    if (r.family == LT_WGRAD_BRICK3D) {
         LT_REQUIRE(workspace, LT_ERR_INVALID, "lt_conv_wgrad_bf16_nhwc: this shape needs a workspace of lt_conv_wgrad_bf16_workspace() bytes");
-        const size_t ws_bytes = lt_conv_wgrad_bf16_workspace(M, cout_pad, k_pad);
         Brick16UArgs b;
         b.dy = (const unsigned short*)dy16; b.x = (const unsigned short*)x16; b.taps = (const int4*)taps; b.out = (float*)workspace;
         b.N = N; b.D = D; b.H = H; b.W = W; b.Cin = Cin; b.ldy = ldy; b.cout_pad = cout_pad; b.k_pad = k_pad;
-        b.nbd = D / B16_D; b.nbh = H / B16_H; b.nbw = W / B16_W; b.nbricks = G * b.nbd * b.nbh * b.nbw;
-        const long long blocks = (long long)(Cout / 32) * (Cin / 32);
-        long long S = cdiv(256, blocks);                  // one workgroup per CU (96 KB of LDS each): exactly one round
-        const long long cap = (long long)(ws_bytes / ((size_t)n * 4));
-        S = S > cap ? cap : S;
-        S = S > b.nbricks ? b.nbricks : S;
-        S = S < 1 ? 1 : S;
-        b.bricks_per_slab = (int)cdiv(b.nbricks, S);
-        S = cdiv(b.nbricks, b.bricks_per_slab);
+        b.nbd = D / B16_D; b.nbh = H / B16_H; b.nbw = W / B16_W; b.nbricks = r.s.units; b.bricks_per_slab = r.s.per_slab;
         const size_t lds = (size_t)(B16_HVOX * 32 + B16_VOX * 32) * 16;
-        hipLaunchKernelGGL(conv3d_wgrad16_brick_u_kernel, dim3(Cout / 32, Cin / 32, (unsigned)S), dim3(256), lds, st, b);
+        hipLaunchKernelGGL(conv3d_wgrad16_brick_u_kernel, r.grid, dim3(256), lds, st, b);
         LT_CHECK_LAUNCH("lt_conv_wgrad_bf16_nhwc(brick)");
-        reduce16(workspace, dw, n, (int)S, accumulate, st);
+        reduce16(workspace, dw, n, r.s.S, accumulate, st);
         LT_CHECK_LAUNCH("lt_conv_wgrad_bf16_nhwc(reduce)");
         return LT_OK;
     }
-    const Plan16 p = plan16u(M, cout_pad, k_pad);
+    const Plan16& p = r.g;
     LT_REQUIRE(p.S == 1 || workspace, LT_ERR_INVALID, "lt_conv_wgrad_bf16_nhwc: this shape needs a workspace of lt_conv_wgrad_bf16_workspace() bytes");
     W16UArgs a;
     a.dy = (const unsigned short*)dy16; a.x = (const unsigned short*)x16; a.taps = (const int4*)taps; a.out = p.S > 1 ? (float*)workspace : dw;
@@ -1017,23 +1041,39 @@ extern "C" int lt_conv_wgrad_bf16_nhwc(const void* dy16, const void* x16, const 
     a.Cout = Cout; a.ldy = ldy; a.k_pad = k_pad; a.ntaps = ntaps; a.M = (int)M; a.accumulate = accumulate; a.cout_pad = cout_pad;
     a.n_k_t = p.n_k_t; a.n_tiles = p.n_co_t * p.n_k_t; a.rows_per_slab = p.rows_per_slab;
     a.img_a = (unsigned)((long long)Do * Ho * Wo * ldy); a.img_b = (unsigned)((long long)D * H * W * ldx);
-    const dim3 grid((unsigned)a.n_tiles, (unsigned)p.S);
     const size_t lds = (size_t)3 * 128 * 64 * sizeof(float);          // the three other waves' 128 accumulator registers
     // Register sets in flight: three are 3 % faster on one stream (17.5 vs 18.1 ms of weight gradients per step) and slower in the step: the kernel runs
     // BESIDE the main stream's BatchNorm passes, one wave per SIMD -- at 448 allocated registers a 96-register wave of the BatchNorm-backward reduction
     // does not fit next to it (it ran 10.1 instead of 4.2 ms per step), at 400 it does: 140.1 -> 144.2 samples/s, same session.  LT_WGRAD16U_NS=3: the deep one.
     static const int ns = [] { const char* e = getenv("LT_WGRAD16U_NS"); return e ? atoi(e) : 2; }();
     if (ns == 2) {
-        if (p.variant == 0) hipLaunchKernelGGL((conv_wgrad16u_kernel<8, 4, 2>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((conv_wgrad16u_kernel<4, 8, 2>), grid, dim3(256), lds, st, a);
+        if (p.variant == 0) hipLaunchKernelGGL((conv_wgrad16u_kernel<8, 4, 2>), r.grid, dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((conv_wgrad16u_kernel<4, 8, 2>), r.grid, dim3(256), lds, st, a);
     } else {
-        if (p.variant == 0) hipLaunchKernelGGL((conv_wgrad16u_kernel<8, 4, 3>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((conv_wgrad16u_kernel<4, 8, 3>), grid, dim3(256), lds, st, a);
+        if (p.variant == 0) hipLaunchKernelGGL((conv_wgrad16u_kernel<8, 4, 3>), r.grid, dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((conv_wgrad16u_kernel<4, 8, 3>), r.grid, dim3(256), lds, st, a);
     }
     LT_CHECK_LAUNCH("lt_conv_wgrad_bf16_nhwc");
     if (p.S > 1) {
         reduce16(workspace, dw, n, p.S, accumulate, st);
         LT_CHECK_LAUNCH("lt_conv_wgrad_bf16_nhwc(reduce)");
     }
+    return LT_OK;
+}
+
+extern "C" int lt_conv_wgrad_bf16_plan(int32_t nhwc, int32_t N, int32_t D, int32_t H, int32_t W, int32_t Cin, int32_t ldx, int32_t Do, int32_t Ho, int32_t Wo,
+                                       const int32_t stride[3], const int32_t pad[3], int32_t Cout, int32_t ldy, int32_t cout_pad, int32_t k_pad, int32_t ntaps,
+                                       lt_wgrad_plan* out) {
+    LT_REQUIRE(stride && pad && out, LT_ERR_INVALID, "lt_conv_wgrad_bf16_plan: null argument");
+    if (nhwc) {
+        LT_REQUIRE(lt_conv_wgrad_bf16_nhwc_ok(N, D, H, W, Cin, ldx, Do, Ho, Wo, stride, pad, Cout, ldy, cout_pad, k_pad, ntaps), LT_ERR_UNSUPPORTED,
+                   "lt_conv_wgrad_bf16_plan: shape not covered by lt_conv_wgrad_bf16_nhwc (ask lt_conv_wgrad_bf16_nhwc_ok)");
+    } else {
+        const int rc = check16(N, D, H, W, Cin, Do, Ho, Wo, Cout, ldy, cout_pad, k_pad, ntaps);
+        if (rc != LT_OK) return rc;
+    }
+    const Route16 r = route16(nhwc != 0, N, D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, ldy, cout_pad, k_pad, ntaps, true);
+    if (r.family == LT_WGRAD_GENERIC) fill_wgrad_plan(out, r.family, r.variant, r.g.S, (long long)cdiv(N, 8) * Do * Ho * Wo, r.g.rows_per_slab, r.grid);
+    else fill_wgrad_plan(out, r.family, r.variant, r.s.S, r.s.units, r.s.per_slab, r.grid);
     return LT_OK;
 }

@@ -53,5 +53,32 @@ inline long long balance_slabs(long long blocks, long long S) {
     return S;
 }
 
+// Slabs of whole units (bricks, 32-row chunks) of an LDS kernel: at most `want`, at most `cap` (what the workspace holds) and one per unit; with
+// `blocks` > 0 (workgroups per slab) balanced to whole rounds of workgroups; then as few slabs as hold ceil(units / S) units each
+struct SlabPlan { int units, per_slab, S; };
+
+inline SlabPlan slab_plan(long long units, long long want, long long cap, long long blocks) {
+    long long S = want > cap ? cap : want;
+    S = S > units ? units : S;
+    S = S < 1 ? 1 : S;
+    if (blocks > 0) S = balance_slabs(blocks, S);
+    SlabPlan p;
+    p.units = (int)units;
+    p.per_slab = (int)lt::cdiv(units, S);
+    p.S = (int)lt::cdiv(units, p.per_slab);
+    return p;
+}
+
+// the generic kernels deal their (slab, tile group) pairs to the 8 XCDs in contiguous ranges when the grid is a multiple of 8 (the kernels and
+// the plan query read this one rule)
+__host__ __device__ inline bool xcd_remap_on(int total_workgroups) { return (total_workgroups & 7) == 0; }
+
+// fills the public answer of the plan queries (lt_conv_wgrad_plan, lt_conv_wgrad_bf16_plan) from what an entry point is about to launch
+inline void fill_wgrad_plan(lt_wgrad_plan* o, int family, int variant, int S, long long units, int per_slab, dim3 grid) {
+    o->family = family; o->variant = variant; o->slabs = S; o->units = units; o->units_per_slab = per_slab;
+    o->grid[0] = (int32_t)grid.x; o->grid[1] = (int32_t)grid.y; o->grid[2] = (int32_t)grid.z;
+    o->xcd_remap = family == LT_WGRAD_GENERIC && xcd_remap_on((int)(grid.x * grid.y * grid.z)) ? 1 : 0;
+}
+
 
 }  // namespace

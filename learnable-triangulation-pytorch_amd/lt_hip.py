@@ -66,6 +66,26 @@ def dims(shape):
     return (i32 * 5)(*shape)
 
 
+WGRAD_GENERIC, WGRAD_BRICK3D, WGRAD_BRICK2D, WGRAD_POINTWISE, WGRAD_K7 = range(5)          # lt_wgrad_plan.family
+WGRAD_F32, WGRAD_BF16, WGRAD_BF16_NHWC = "fp32", "bf16", "nhwc"                            # the three entry points, as wgrad_plan() names them
+
+
+class WgradPlan(C.Structure):
+    _fields_ = [("family", i32), ("variant", i32), ("slabs", i32), ("units_per_slab", i32), ("units", i64), ("grid", i32 * 3), ("xcd_remap", i32)]
+
+
+def wgrad_plan(entry, N, D, H, W, Cin, Do, Ho, Wo, stride, pad, Cout, ldy, cout_pad, k_pad, ntaps, ldx=None):
+    """What lt_conv_wgrad (``entry`` = WGRAD_F32), lt_conv_wgrad_bf16 (WGRAD_BF16) or lt_conv_wgrad_bf16_nhwc (WGRAD_BF16_NHWC, with ``ldx``) would launch:
+    the lt_wgrad_plan of lt_conv_wgrad_plan / lt_conv_wgrad_bf16_plan (host only), or None where the entry point refuses the shape."""
+    out = WgradPlan()
+    if entry == WGRAD_F32:
+        rc = lib().lt_conv_wgrad_plan(N, D, H, W, Cin, Do, Ho, Wo, i3(stride), i3(pad), Cout, ldy, cout_pad, k_pad, ntaps, C.byref(out))
+    else:
+        rc = lib().lt_conv_wgrad_bf16_plan(int(entry == WGRAD_BF16_NHWC), N, D, H, W, Cin, Cin if ldx is None else ldx, Do, Ho, Wo, i3(stride), i3(pad), Cout, ldy,
+                                           cout_pad, k_pad, ntaps, C.byref(out))
+    return out if rc == 0 else None
+
+
 PWCHAIN_MAX = 3
 
 
@@ -234,6 +254,8 @@ SIGNATURES = {
     "lt_conv_wgrad_bf16_nhwc_ok": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32, i32, i32, i32, i32]),
     "lt_conv_wgrad_bf16_nhwc": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32, i32, i32, i32, i32, i32, vp, vp]),
     "lt_conv_wgrad": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "lt_conv_wgrad_plan": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32, i32, i32, i32, i32, C.POINTER(WgradPlan)]),
+    "lt_conv_wgrad_bf16_plan": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32 * 3, i32 * 3, i32, i32, i32, i32, i32, C.POINTER(WgradPlan)]),
     "lt_adam_step": (C.c_int, [vp, vp, vp, vp, i64, f32, f64, f64, f32, f32, i32, vp]),
     "lt_unproject_bwd_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
     "lt_unproject_bwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]),
