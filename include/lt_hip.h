@@ -484,6 +484,28 @@ int lt_unproject_bwd(int32_t dtype, const void* feats, const float* proj, const 
 int lt_unproject_masked_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
                             const float* grad_out, float* grad_feats, float* grad_conf, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w,
                             int32_t v0, int32_t v1, int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes, void* stream);
+/* Several cuboids per frame, the backward of lt_unproject_indexed_fwd: what autograd derives for the unprojection of feats[frame_of], proj[frame_of],
+ * conf[frame_of] (and view_mask[frame_of]) without the P / F copies.
+ *   by frame  (F): feats F,NV,h,w,C   proj F,NV,3,4   conf F,NV,C   view_mask F,NV uint8 or NULL = every view valid   grad_feats F,NV,h,w,C fp32
+ *                  grad_conf F,NV,C fp32 or NULL
+ *   by cuboid (P): coords P,v0,v1,v2,3   grad_out P,v0,v1,v2,C fp32
+ *   frame_of: DEVICE (P) int32, any order, read inside the kernels only (a new assignment is just another call) and clamped into [0, F-1] as the
+ *   forward does.
+ * grad_feats[f] is the sum over the cuboids p with frame_of[p] == f of cuboid p's unindexed gradient, added per cell in (cuboid, brick, voxel) order
+ * inside the gather's LDS tile (K2 runs one workgroup per (tile, view, frame) and walks the frame's cuboids in ascending p); grad_conf[f] is the same
+ * sum, in fp64 over (cuboid, workgroup) with one rounding, and conf_norm's chain rule is applied once, on that sum.  A frame without a cuboid gets
+ * +0.0 everywhere; both outputs are written completely (no pre-zeroing).  Deterministic, no atomics; with frame_of = 0 .. F-1 the bits are those of
+ * lt_unproject_bwd (NULL mask) / lt_unproject_masked_bwd.  Layouts, dtypes, aggregations, 1 <= NV <= 32 and the error codes are those entries';
+ * gather path only (C a power of two <= 64; LT_UNPROJ_BWD_ATOMICS=1 is LT_ERR_UNSUPPORTED); frame_of NULL, F < 1 or P < 1: LT_ERR_INVALID.
+ * Workspace: lt_unproject_indexed_bwd_workspace (host only; 0 where the gather does not take C) = the fp64 confidence partials of ALL P cuboids
+ * (nblk1 * NV * C * 8 bytes each, rounded up to 256 in all) + P times one cuboid's dxs, tap records and bounding boxes (lt_unproject_bwd's blocks).
+ * With less -- at least the partials plus ONE cuboid's share -- the cuboids are walked in ascending chunks, a later chunk's tile starting from
+ * what the earlier ones stored: the same additions in the same order, so both gradients are bit-identical for every workspace size. */
+size_t lt_unproject_indexed_bwd_workspace(int32_t P, int32_t NV, int32_t C, int32_t v0, int32_t v1, int32_t v2);
+int lt_unproject_indexed_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                             const int32_t* frame_of, const float* grad_out, float* grad_feats, float* grad_conf, int32_t F, int32_t P, int32_t NV,
+                             int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes,
+                             void* stream);
 int lt_softargmax3d_bwd(const float* probs, const float* coords, const float* kp, const float* grad_kp, const int32_t* gp_idx,
                         const float* gp_val, float multiplier, int32_t softmax, int32_t channels_last, float* grad_logits, int32_t B,
                         int32_t J, int64_t nvox, void* stream);

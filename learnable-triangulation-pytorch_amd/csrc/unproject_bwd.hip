@@ -29,6 +29,10 @@
 // hold no per-view register array (the host entry dispatches on NV > UB_MAXV; nothing changes for NV <= 8).
 // lt_unproject_masked_bwd (training with per-sample view masks): MASKED instantiations of K0, of every K1 form and of both finalizers -- a masked view gets
 // empty bounding boxes from K0 and is skipped by K1, so the unchanged K2 stores zeros for it; the valid views are walked in index order.  Gather path only.
+// lt_unproject_indexed_bwd (training with several cuboids per frame): INDEXED instantiations, on the masked forms, of K0 and of every K1 form -- the grid
+// by cuboid, the frame-side reads through f = frame_of[p], a scalar per workgroup -- and of K2, one workgroup per (tile, view, FRAME) that keeps its tile
+// across the frame's cuboids (additions in (cuboid, brick, voxel) order); the confidence partials of all cuboids are finalized once, per frame.  Gather
+// path only; the cuboids may be walked in chunks (a later chunk's tile starts from the stored sums), with the same bits for every workspace size.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -62,9 +66,31 @@ struct UnprojBwdArgs {
 struct UnprojBwdMaskedArgs : UnprojBwdArgs {
     const uint8_t* mask;     // (B, NV), non-zero = the view is valid
 };
-template <bool MASKED> using UnprojBwdArgsOf = std::conditional_t<MASKED, UnprojBwdMaskedArgs, UnprojBwdArgs>;
+// lt_unproject_indexed_bwd (several cuboids per frame): B counts the CUBOIDS of one chunk; coords, gout and the whole workspace are indexed by the
+// chunk's cuboid b, feats, proj, conf and mask by its frame frame_of[p0 + b] < F, gfeats and gconf by the frame.  Built on the masked form: a null
+// mask there means every view is valid.
+struct UnprojBwdIndexedArgs : UnprojBwdMaskedArgs {
+    const int32_t* frame_of; // (P) the frame of every cuboid
+    int F, P;                // frames; cuboids of the whole call (the confidence finalizer walks all of them)
+    int p0;                  // first cuboid of this chunk (the chunk holds cuboids p0 .. p0 + B - 1)
+};
+template <bool MASKED, bool INDEXED = false>
+using UnprojBwdArgsOf = std::conditional_t<INDEXED, UnprojBwdIndexedArgs, std::conditional_t<MASKED, UnprojBwdMaskedArgs, UnprojBwdArgs>>;
 
 constexpr int UB_MAXV = 8;   // views kept in registers
+
+// the frame of cuboid p: uniform over the workgroup (p comes from the block index or from a scalar loop), read once as a scalar and clamped into
+// [0, F-1] as the forward does -- a bad index reads a wrong frame, never outside the frame-side buffers
+__device__ __forceinline__ int frame_of_cuboid(const UnprojBwdIndexedArgs& a, int p) {
+    const int f = __builtin_amdgcn_readfirstlane(a.frame_of[p]);
+    return min(max(f, 0), a.F - 1);
+}
+// the frame-side index of the workgroup's sample b: b itself, or the frame of the chunk's cuboid b
+template <bool MASKED, bool INDEXED>
+__device__ __forceinline__ int frame_side(const UnprojBwdArgsOf<MASKED, INDEXED>& a, int b) {
+    if constexpr (INDEXED) return frame_of_cuboid(a, a.p0 + b);
+    else return b;
+}
 
 // Sample b's mask row as bits (NV <= 32).  b comes from the block index in K0 and K1: the row is read with scalar loads into one scalar
 // register, and every test of a view below is a scalar branch.
@@ -73,6 +99,13 @@ __device__ __forceinline__ unsigned mask_bits(const uint8_t* __restrict__ mask, 
     unsigned bits = 0;
     for (int v = 0; v < NV; ++v) bits |= (mk[v] ? 1u : 0u) << v;
     return bits;
+}
+// the bits of frame-side row f as the kernels below take them: all ones without a mask (INDEXED: a null mask means every view is valid)
+template <bool MASKED, bool INDEXED>
+__device__ __forceinline__ unsigned mask_bits_of(const UnprojBwdArgsOf<MASKED, INDEXED>& a, int f) {
+    if constexpr (INDEXED) return a.mask ? mask_bits(a.mask, f, a.NV) : ~0u;
+    else if constexpr (MASKED) return mask_bits(a.mask, f, a.NV);
+    else return ~0u;
 }
 // does view v take part?  Without a mask: constant true, so the unmasked instantiations compile to what they did before the mask existed
 template <bool MASKED> __device__ __forceinline__ bool view_on(unsigned mbits, int v) {
@@ -233,19 +266,22 @@ __device__ __forceinline__ int wave_max(int v) {
 // K0: grid (ceil(nbricks / 4), B), 4 waves, one brick per wave.  MASKED: a masked view gets the empty bounding box for every brick and nothing
 // else -- it is not projected, its matrix is not read, its tap records stay unwritten: K2 then finds no brick for any tile of that view and
 // stores zeros without reading its tap records or its dxs, and K1 never looks at a masked view.
-template <bool MASKED = false>
-__global__ __launch_bounds__(256) void unproj_taps_kernel(const UnprojBwdArgsOf<MASKED> a) {
+// INDEXED (on the masked form, here and in every K1 form): sample b is the chunk's cuboid b -- its coordinates, upstream gradient and workspace rows by
+// b, the projections, maps, confidences and mask of its frame f = frame_of[p0 + b].
+template <bool MASKED = false, bool INDEXED = false>
+__global__ __launch_bounds__(256) void unproj_taps_kernel(const UnprojBwdArgsOf<MASKED, INDEXED> a) {
+    static_assert(MASKED || !INDEXED, "the indexed kernels are built on the masked form");
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int nbricks = a.nb0 * a.nb1 * a.nb2;
     const int brick = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (brick >= nbricks) return;
-    const float* P = a.proj + (long long)b * a.NV * 12;
+    const int f = frame_side<MASKED, INDEXED>(a, b);
+    const float* P = a.proj + (long long)f * a.NV * 12;
     const float* coords = a.coords + (long long)b * a.nvox * 3;
     const long long vox = brick_voxel(a, brick, lane);
     float X0 = 0.f, X1 = 0.f, X2 = 0.f;
     if (vox >= 0) { X0 = coords[vox * 3]; X1 = coords[vox * 3 + 1]; X2 = coords[vox * 3 + 2]; }
-    unsigned mbits = ~0u;
-    if constexpr (MASKED) mbits = mask_bits(a.mask, b, a.NV);
+    const unsigned mbits = mask_bits_of<MASKED, INDEXED>(a, f);
     for (int v = 0; v < a.NV; ++v) {
         int x0 = 1 << 30, x1 = -1, y0 = 1 << 30, y1 = -1;
         if constexpr (MASKED) {
@@ -273,16 +309,17 @@ __global__ __launch_bounds__(256) void unproj_taps_kernel(const UnprojBwdArgsOf<
 // MASKED: masked views are skipped in the sampling, in every cross-view reduction and in the stores (K2 never reads their dxs); their
 // confidence partials are written as the zeros their accumulators still hold.  A sample without a valid view walks no voxel.
 // gfx950 resource usage, fp32 / bf16 maps: see DESIGN.md ("Masked unprojection backward")
-template <typename T, int MV, bool MASKED = false>
-__global__ __launch_bounds__(256) void unproj_dx_kernel(const UnprojBwdArgsOf<MASKED> a) {
+template <typename T, int MV, bool MASKED = false, bool INDEXED = false>
+__global__ __launch_bounds__(256) void unproj_dx_kernel(const UnprojBwdArgsOf<MASKED, INDEXED> a) {
+    static_assert(MASKED || !INDEXED, "the indexed kernels are built on the masked form");
     __shared__ float red[256][4];
     const int tpv = a.C >> 2;
     const int b = blockIdx.y;
-    unsigned mbits = ~0u;
-    if constexpr (MASKED) mbits = mask_bits(a.mask, b, a.NV);
+    const int f = frame_side<MASKED, INDEXED>(a, b);
+    const unsigned mbits = mask_bits_of<MASKED, INDEXED>(a, f);
     const long long items = (MASKED && mbits == 0) ? 0 : a.nvox * tpv;
-    const T* feats = (const T*)a.feats + (long long)b * a.NV * a.h * a.w * a.C;
-    const float* P = a.proj + (long long)b * a.NV * 12;
+    const T* feats = (const T*)a.feats + (long long)f * a.NV * a.h * a.w * a.C;
+    const float* P = a.proj + (long long)f * a.NV * 12;
     const float* coords = a.coords + (long long)b * a.nvox * 3;
     const float* gout = a.gout + (long long)b * a.nvox * a.C;
     float* dxs = a.dxs + (long long)b * a.NV * a.nvox * a.C;
@@ -303,7 +340,7 @@ __global__ __launch_bounds__(256) void unproj_dx_kernel(const UnprojBwdArgsOf<MA
             Tap tp[MV];
             sample_views<T, MV, MASKED>(a, feats, P, X0, X1, X2, c0, tp, x, mbits);
         }
-        view_gradients<MV, MASKED>(a, b, c0, g, x, dx, mbits);
+        view_gradients<MV, MASKED>(a, f, c0, g, x, dx, mbits);
 #pragma unroll
         for (int v = 0; v < MV; ++v)
             if (v < a.NV && view_on<MASKED>(mbits, v)) {
@@ -423,18 +460,19 @@ __device__ __forceinline__ void cross_view_gradients(int agg, int NV, const floa
 // tap record (20 bytes, the same for the C / 4 lanes of a voxel) and four 16-byte taps.
 // gfx950 resource usage: fp32 maps 64 VGPRs and 8 waves per SIMD, bf16 maps 68 VGPRs and 7 waves; no LDS, no scratch
 // MASKED: every pass walks the valid views only (a masked view has no tap records: K0 wrote none); a sample without a valid view does nothing
-template <typename T, bool MASKED = false>
-__global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdArgsOf<MASKED> a) {
+template <typename T, bool MASKED = false, bool INDEXED = false>
+__global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdArgsOf<MASKED, INDEXED> a) {
+    static_assert(MASKED || !INDEXED, "the indexed kernels are built on the masked form");
     const int tpv = a.C >> 2;
     const long long items = a.nvox * tpv;
     const int b = blockIdx.y;
-    unsigned mbits = ~0u;
+    const int f = frame_side<MASKED, INDEXED>(a, b);
+    const unsigned mbits = mask_bits_of<MASKED, INDEXED>(a, f);
     if constexpr (MASKED) {
-        mbits = mask_bits(a.mask, b, a.NV);
         if (mbits == 0) return;
     }
     const long long hw = (long long)a.h * a.w;
-    const T* feats = (const T*)a.feats + (long long)b * a.NV * hw * a.C;
+    const T* feats = (const T*)a.feats + (long long)f * a.NV * hw * a.C;
     const float* gout = a.gout + (long long)b * a.nvox * a.C;
     float* dxs = a.dxs + (long long)b * a.NV * a.nvox * a.C;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < items; q += (long long)gridDim.x * 256) {
@@ -462,21 +500,25 @@ __global__ __launch_bounds__(256) void unproj_dx_passes_kernel(const UnprojBwdAr
 // gfx950 resource usage: fp32 maps 79 VGPRs and 6 waves per SIMD, bf16 maps 81 VGPRs and 5 waves; 6 KB LDS, no scratch
 // MASKED: conf_norm's sum runs over the valid views; a masked view of the group is neither stored nor sampled (K0 wrote no tap records for
 // it, K2 never reads its dxs) and its confidence partials are the zeros of its accumulators; a group without a valid view walks no voxel.
-template <typename T, bool MASKED = false>
-__global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdArgsOf<MASKED> a) {
+template <typename T, bool MASKED = false, bool INDEXED = false>
+__global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdArgsOf<MASKED, INDEXED> a) {
+    static_assert(MASKED || !INDEXED, "the indexed kernels are built on the masked form");
     __shared__ float red[256][4];
     __shared__ float coef[UB_MAXV][64];
     const int tpv = a.C >> 2;
     const int b = blockIdx.y;
+    int f = b;                                            // (written out, like the mask word below: through the helpers the unindexed forms' instructions moved)
+    if constexpr (INDEXED) f = frame_of_cuboid(a, a.p0 + b);
     const int vg = blockIdx.z * UB_MAXV, nv = min(UB_MAXV, a.NV - vg);
     unsigned mbits = ~0u, gbits = ~0u;                    // the sample's mask, and the group's share of it (bit v = view vg + v)
     if constexpr (MASKED) {
-        mbits = mask_bits(a.mask, b, a.NV);
+        if constexpr (INDEXED) mbits = a.mask ? mask_bits(a.mask, f, a.NV) : ~0u;          // (a null mask: every view valid)
+        else mbits = mask_bits(a.mask, b, a.NV);
         gbits = mbits >> vg;
     }
     const long long items = (MASKED && (gbits & 0xffu) == 0) ? 0 : a.nvox * tpv;
     const long long hw = (long long)a.h * a.w;
-    const T* feats = (const T*)a.feats + ((long long)b * a.NV + vg) * hw * a.C;
+    const T* feats = (const T*)a.feats + ((long long)f * a.NV + vg) * hw * a.C;
     const float* gout = a.gout + (long long)b * a.nvox * a.C;
     float* dxs = a.dxs + ((long long)b * a.NV + vg) * a.nvox * a.C;
     const bool is_conf = a.agg == LT_AGG_CONF || a.agg == LT_AGG_CONF_NORM;
@@ -484,7 +526,7 @@ __global__ __launch_bounds__(256) void unproj_dx_groups_kernel(const UnprojBwdAr
     if (is_conf) {
         for (int i = threadIdx.x; i < nv * a.C; i += 256) {
             const int v = i / a.C, c = i - v * a.C;
-            const float* cf = a.conf + (long long)b * a.NV * a.C + c;
+            const float* cf = a.conf + (long long)f * a.NV * a.C + c;
             if (!view_on<MASKED>(gbits, v)) continue;
             float cv = cf[(vg + v) * a.C];
             if (a.agg == LT_AGG_CONF_NORM) {
@@ -576,6 +618,39 @@ __global__ __launch_bounds__(UB_MANYV * UB_FIN_C) void unproj_gconf_finalize_man
         t = on ? (t - dot) / S : 0.0;
     }
     a.gconf[((long long)b * a.NV + v) * a.C + c] = (float)t;
+}
+
+// lt_unproject_indexed_bwd's finalizer, for every NV: unproj_gconf_finalize_many_kernel's shape with one workgroup per (FRAME, 8 channels).  a.gcpart
+// holds the partials of all a.P cuboids, (P, nblk1, NV, C), whatever the chunking of K0 - K2 was; thread (v, c) adds those of its frame's cuboids in
+// (cuboid, workgroup) order -- frame_of is scanned in ascending p, a scalar per step -- and rounds once, so with one cuboid per frame these are the
+// unindexed finalizers' bits.  conf_norm's chain rule is applied once, on that sum; a frame without a cuboid gets +0.0.
+// gfx950 resource usage: DESIGN.md ("Indexed unprojection backward")
+__global__ __launch_bounds__(UB_MANYV * UB_FIN_C) void unproj_gconf_finalize_indexed_kernel(const UnprojBwdIndexedArgs a, int nblk1) {
+    __shared__ double sv[UB_MANYV][UB_FIN_C];
+    const int cc = a.C < UB_FIN_C ? a.C : UB_FIN_C;
+    const int chunks = a.C / cc;
+    const int f = blockIdx.x / chunks, ci = threadIdx.x % UB_FIN_C, v = threadIdx.x / UB_FIN_C;
+    const int c = (blockIdx.x - f * chunks) * cc + ci;
+    const bool mine = ci < cc && v < a.NV;
+    const unsigned mbits = mask_bits_of<true, true>(a, f);
+    const bool on = view_on<true>(mbits, v);
+    double t = 0.0;
+    for (int p = 0; p < a.P; ++p) {
+        if (frame_of_cuboid(a, p) != f) continue;
+        if (mine && on)
+            for (int k = 0; k < nblk1; ++k) t += a.gcpart[(((long long)p * nblk1 + k) * a.NV + v) * a.C + c];
+    }
+    sv[v][ci] = t;
+    __syncthreads();
+    if (!mine) return;
+    if (a.agg == LT_AGG_CONF_NORM) {
+        const float* cf = a.conf + (long long)f * a.NV * a.C + c;
+        double S = 0.0, dot = 0.0;
+        for (int u = 0; u < a.NV; ++u) if (view_on<true>(mbits, u)) S += (double)cf[u * a.C];
+        for (int u = 0; u < a.NV; ++u) if (view_on<true>(mbits, u)) dot += sv[u][ci] * (double)cf[u * a.C] / S;
+        t = on ? (t - dot) / S : 0.0;
+    }
+    a.gconf[((long long)f * a.NV + v) * a.C + c] = (float)t;
 }
 
 // round-2 scatter for NV > UB_MAXV (same semantics as unproject_bwd_kernel: zeroed outputs, float atomics): one view at a time, softmax /
@@ -670,8 +745,13 @@ struct GatherCfg {
     static constexpr size_t LDS = (size_t)(TILE + 256 + 4 * WAVE_INTS + G_LIST + 4) * 4;
 };
 
-template <int CW>
-__global__ __launch_bounds__(256) void unproj_gather_kernel(const UnprojBwdArgs a) {
+// INDEXED (lt_unproject_indexed_bwd): grid (tiles, NV, F), a.B the cuboids of the chunk.  The workgroup of (tile, v, f) keeps its LDS tile across
+// cuboids: it scans frame_of over the chunk in ascending p (a scalar per step, uniform over the workgroup) and runs the brick walk below over the
+// tap records, bounding boxes and dxs of every cuboid of frame f, so a cell's additions are in (cuboid, brick, voxel) order; the tile is stored once
+// at the end.  The first chunk (p0 == 0) starts from the zero fill, a later one from what the chunks before it stored in gfeats -- the same additions
+// in the same order as one chunk over all cuboids, hence the same bits.  A frame without a cuboid stores zeros.  No LDS beyond the unindexed form's.
+template <int CW, bool INDEXED = false>
+__global__ __launch_bounds__(256) void unproj_gather_kernel(const std::conditional_t<INDEXED, UnprojBwdIndexedArgs, UnprojBwdArgs> a) {
     typedef GatherCfg<CW> G;
     constexpr int C = G::C, HALVES = G::HALVES, REC = G::REC;
     extern __shared__ float smem[];
@@ -684,14 +764,28 @@ __global__ __launch_bounds__(256) void unproj_gather_kernel(const UnprojBwdArgs 
     int* myR = wbase + wv * G::WAVE_INTS;                      // [HALVES][68] hit records
     const int tiles_x = (a.w + G_TW - 1) / G_TW;
     const int tx0 = (blockIdx.x % tiles_x) * G_TW, ty0 = (blockIdx.x / tiles_x) * G_TH;
-    const int v = blockIdx.y, b = blockIdx.z;
+    const int v = blockIdx.y, b = blockIdx.z;                  // b: the sample whose tile this is (INDEXED: the frame)
     const int nbricks = a.nb0 * a.nb1 * a.nb2;
-    const long long vbase = ((long long)b * a.NV + v) * a.nvox;
+    const long long vbase = ((long long)b * a.NV + v) * a.nvox; // the workspace rows that are walked: sample b's (INDEXED: set per cuboid of the frame, below)
     const int* txy = a.txy + vbase;
     const float4* tw = a.tw + vbase;
     const float* dxs = a.dxs + vbase * C + wv * CW;
     const int* bbox = a.bbox + ((long long)b * a.NV + v) * nbricks * 4;
     for (int i = threadIdx.x; i < G::TILE; i += 256) tile[i] = 0.f;
+    if constexpr (INDEXED) {
+        if (a.p0 > 0) {                                        // a later chunk goes on from the sums of the chunks before it (the store loop, backwards)
+            __syncthreads();
+            const float* gsrc = a.gfeats + ((long long)b * a.NV + v) * a.h * a.w * C;
+            for (int i = threadIdx.x; i < G_TH * G_TW * (C / 4); i += 256) {
+                const int cv = i % (C / 4), px = (i / (C / 4)) % G_TW, py = i / ((C / 4) * G_TW);
+                if (tx0 + px < a.w && ty0 + py < a.h) {
+                    const int hh = px / G::HPX;
+                    *(float4*)(tile + hh * G::HALF_SZ + py * G::RSH + (px - hh * G::HPX) * G::PS + cv * 4) =
+                        *(const float4*)(gsrc + ((long long)(ty0 + py) * a.w + tx0 + px) * C + cv * 4);
+                }
+            }
+        }
+    }
     // this lane's role in the hit loop: half-wave `half`, pixel-parity class t_of (see the records), channel c_of (lanes past 4 * CW of a
     // half idle: they work on a dummy cell)
     const int half = HALVES == 2 ? lane >> 5 : 0, hl_lane = HALVES == 2 ? lane & 31 : lane;
@@ -720,6 +814,17 @@ __global__ __launch_bounds__(256) void unproj_gather_kernel(const UnprojBwdArgs 
         }
         return r;
     };
+    int q = -1;                                                // INDEXED: the chunk's cuboid that is walked; those of frame b, in ascending order
+    do {
+    if constexpr (INDEXED) {
+        do ++q; while (q < a.B && frame_of_cuboid(a, a.p0 + q) != b);
+        if (q >= a.B) break;
+        const long long vb = ((long long)q * a.NV + v) * a.nvox;
+        txy = a.txy + vb;
+        tw = a.tw + vb;
+        dxs = a.dxs + vb * C + wv * CW;
+        bbox = a.bbox + ((long long)q * a.NV + v) * nbricks * 4;
+    }
     int g_next = 0;
     while (g_next < nbricks) {
         // ---- wave 0 lists the next (up to G_LIST) bricks whose tap bounding box meets the tile, in brick order
@@ -832,6 +937,8 @@ __global__ __launch_bounds__(256) void unproj_gather_kernel(const UnprojBwdArgs 
         }
         __syncthreads();                                       // the list is free to be rewritten; after the last round: the tile is complete
     }
+    } while (INDEXED);
+    if constexpr (INDEXED) __syncthreads();                    // a frame without a cuboid in this chunk walked nothing: its fill is ordered here
     // the tile's pixels inside the map, every channel: plain stores, each cell of gfeats written exactly once
     float* gm = a.gfeats + ((long long)b * a.NV + v) * a.h * a.w * C;
     constexpr int c4 = C / 4;
@@ -852,6 +959,14 @@ int launch_gather(const UnprojBwdArgs& c, int tiles, int NV, int nb, hipStream_t
     LT_CHECK_LAUNCH("lt_unproject_bwd(gather)");
     return LT_OK;
 }
+// the indexed instantiation: one workgroup per (tile, view, FRAME), over the c.B cuboids of the chunk
+template <int CW>
+int launch_gather_indexed(const UnprojBwdIndexedArgs& c, int tiles, hipStream_t st) {
+    LT_OPT_IN_LDS((unproj_gather_kernel<CW, true>), 160 * 1024);
+    hipLaunchKernelGGL((unproj_gather_kernel<CW, true>), dim3((unsigned)tiles, (unsigned)c.NV, (unsigned)c.F), dim3(256), GatherCfg<CW>::LDS, st, c);
+    LT_CHECK_LAUNCH("lt_unproject_indexed_bwd(gather)");
+    return LT_OK;
+}
 
 int blocks_k1(long long nvox, int C) {
     const long long blocks = cdiv(nvox * (C / 4), 256);
@@ -863,35 +978,38 @@ bool gather_takes(int C) { return C >= 4 && C <= 64 && (C & (C - 1)) == 0 && !en
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // K0, K1 and the confidence finalizers of one chunk of the batch.  An unmasked kernel receives a plain UnprojBwdArgs by value (the base of m)
-// and a masked one all of m: the unmasked kernels keep their argument block, and with it their code.
-template <bool MASKED>
-int launch_taps_dx(const char* who, const UnprojBwdMaskedArgs& m, int dtype, int nbricks, int nblk1, hipStream_t st) {
-    const UnprojBwdArgsOf<MASKED>& c = m;
+// and a masked one its masked base: the unmasked kernels keep their argument block, and with it their code.  INDEXED: all of m, c.B cuboids of one
+// chunk, and no finalizer -- the indexed entry runs its own once, after the last chunk.
+template <bool MASKED, bool INDEXED = false>
+int launch_taps_dx(const char* who, const UnprojBwdIndexedArgs& m, int dtype, int nbricks, int nblk1, hipStream_t st) {
+    const UnprojBwdArgsOf<MASKED, INDEXED>& c = m;
     const int nb = c.B, NV = c.NV, C = c.C, agg = c.agg;
-    hipLaunchKernelGGL(unproj_taps_kernel<MASKED>, dim3((unsigned)cdiv(nbricks, 4), (unsigned)nb), dim3(256), 0, st, c);
+    hipLaunchKernelGGL((unproj_taps_kernel<MASKED, INDEXED>), dim3((unsigned)cdiv(nbricks, 4), (unsigned)nb), dim3(256), 0, st, c);
     LT_CHECK_LAUNCH(who);
     const dim3 g1((unsigned)nblk1, (unsigned)nb);
     if (NV > UB_MAXV) {                                       // views in passes (softmax, max) or in groups of UB_MAXV (grid z)
         const dim3 gz((unsigned)nblk1, (unsigned)nb, (unsigned)cdiv(NV, UB_MAXV));
         if (agg == LT_AGG_SOFTMAX || agg == LT_AGG_MAX) {
-            if (dtype == LT_F32) hipLaunchKernelGGL((unproj_dx_passes_kernel<float, MASKED>), g1, dim3(256), 0, st, c);
-            else hipLaunchKernelGGL((unproj_dx_passes_kernel<bf16_t, MASKED>), g1, dim3(256), 0, st, c);
-        } else if (dtype == LT_F32) hipLaunchKernelGGL((unproj_dx_groups_kernel<float, MASKED>), gz, dim3(256), 0, st, c);
-        else hipLaunchKernelGGL((unproj_dx_groups_kernel<bf16_t, MASKED>), gz, dim3(256), 0, st, c);
+            if (dtype == LT_F32) hipLaunchKernelGGL((unproj_dx_passes_kernel<float, MASKED, INDEXED>), g1, dim3(256), 0, st, c);
+            else hipLaunchKernelGGL((unproj_dx_passes_kernel<bf16_t, MASKED, INDEXED>), g1, dim3(256), 0, st, c);
+        } else if (dtype == LT_F32) hipLaunchKernelGGL((unproj_dx_groups_kernel<float, MASKED, INDEXED>), gz, dim3(256), 0, st, c);
+        else hipLaunchKernelGGL((unproj_dx_groups_kernel<bf16_t, MASKED, INDEXED>), gz, dim3(256), 0, st, c);
     } else if (dtype == LT_F32) {
-        if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<float, 4, MASKED>), g1, dim3(256), 0, st, c);
-        else hipLaunchKernelGGL((unproj_dx_kernel<float, UB_MAXV, MASKED>), g1, dim3(256), 0, st, c);
+        if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<float, 4, MASKED, INDEXED>), g1, dim3(256), 0, st, c);
+        else hipLaunchKernelGGL((unproj_dx_kernel<float, UB_MAXV, MASKED, INDEXED>), g1, dim3(256), 0, st, c);
     } else {
-        if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, 4, MASKED>), g1, dim3(256), 0, st, c);
-        else hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, UB_MAXV, MASKED>), g1, dim3(256), 0, st, c);
+        if (NV <= 4) hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, 4, MASKED, INDEXED>), g1, dim3(256), 0, st, c);
+        else hipLaunchKernelGGL((unproj_dx_kernel<bf16_t, UB_MAXV, MASKED, INDEXED>), g1, dim3(256), 0, st, c);
     }
     LT_CHECK_LAUNCH(who);
-    if (c.gconf && NV > UB_MAXV) {
-        hipLaunchKernelGGL(unproj_gconf_finalize_many_kernel<MASKED>, dim3((unsigned)(nb * (C / (C < UB_FIN_C ? C : UB_FIN_C)))), dim3(UB_MANYV * UB_FIN_C), 0, st, c, nblk1);
-        LT_CHECK_LAUNCH(who);
-    } else if (c.gconf) {
-        hipLaunchKernelGGL(unproj_gconf_finalize_kernel<MASKED>, dim3((unsigned)cdiv((long long)nb * C, 64)), dim3(64), 0, st, c, nblk1);
-        LT_CHECK_LAUNCH(who);
+    if constexpr (!INDEXED) {
+        if (c.gconf && NV > UB_MAXV) {
+            hipLaunchKernelGGL(unproj_gconf_finalize_many_kernel<MASKED>, dim3((unsigned)(nb * (C / (C < UB_FIN_C ? C : UB_FIN_C)))), dim3(UB_MANYV * UB_FIN_C), 0, st, c, nblk1);
+            LT_CHECK_LAUNCH(who);
+        } else if (c.gconf) {
+            hipLaunchKernelGGL(unproj_gconf_finalize_kernel<MASKED>, dim3((unsigned)cdiv((long long)nb * C, 64)), dim3(64), 0, st, c, nblk1);
+            LT_CHECK_LAUNCH(who);
+        }
     }
     return LT_OK;
 }
@@ -917,7 +1035,8 @@ int unproject_backward(const char* who, bool masked, int dtype, const void* feat
                    "%s: only the gather path takes a view mask, and it needs C a power of two <= 64 (got C=%d; the scatter has no masked form)", who, C);
     }
     hipStream_t st = (hipStream_t)stream;
-    UnprojBwdMaskedArgs a;
+    UnprojBwdIndexedArgs a;
+    a.frame_of = nullptr; a.F = B; a.P = B; a.p0 = 0;
     a.mask = masked ? view_mask : nullptr;
     a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.gout = grad_out; a.gfeats = grad_feats; a.gconf = is_conf ? grad_conf : nullptr;
     a.dxs = nullptr; a.bbox = nullptr; a.gcpart = nullptr; a.txy = nullptr; a.tw = nullptr;
@@ -953,7 +1072,7 @@ int unproject_backward(const char* who, bool masked, int dtype, const void* feat
     const size_t in_elt = dtype == LT_F32 ? 4 : 2;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
-        UnprojBwdMaskedArgs c = a;
+        UnprojBwdIndexedArgs c = a;
         c.B = nb;
         c.feats = (const char*)feats + (size_t)b0 * NV * h * w * C * in_elt;
         c.proj = proj + (size_t)b0 * NV * 12;
@@ -983,7 +1102,103 @@ int unproject_backward(const char* who, bool masked, int dtype, const void* feat
     return LT_OK;
 }
 
+// lt_unproject_indexed_bwd's workspace: [fp64 confidence partials of ALL P cuboids (the finalizer runs once, over every chunk's partials)]
+// [dxs | bbox | tw | txy of one chunk of cuboids]
+struct IndexedWs {
+    size_t s_dx, s_bb, gc, s_xy, s_tw;                            // gc: one cuboid's partials, nblk1 * NV * C * 8 bytes (dense over the cuboids)
+    size_t per_cuboid() const { return s_dx + s_bb + s_xy + s_tw; }
+    size_t gc_all(int P) const { return align256(gc * (size_t)P); }
+};
+IndexedWs indexed_ws(int NV, int C, int v0, int v1, int v2) {
+    const long long nvox = (long long)v0 * v1 * v2;
+    const long long nbricks = cdiv(v0, 4) * cdiv(v1, 4) * cdiv(v2, 4);
+    IndexedWs s;
+    s.s_dx = align256((size_t)NV * nvox * C * 4); s.s_bb = align256((size_t)NV * nbricks * 16); s.gc = (size_t)blocks_k1(nvox, C) * NV * C * 8;
+    s.s_xy = align256((size_t)NV * nvox * 4); s.s_tw = align256((size_t)NV * nvox * 16);
+    return s;
+}
+
 }  // namespace
+
+extern "C" size_t lt_unproject_indexed_bwd_workspace(int32_t P, int32_t NV, int32_t C, int32_t v0, int32_t v1, int32_t v2) {
+    if (P < 1 || NV < 1 || C < 4 || v0 < 1 || v1 < 1 || v2 < 1 || !gather_takes(C)) return 0;
+    const IndexedWs s = indexed_ws(NV, C, v0, v1, v2);
+    return s.gc_all(P) + s.per_cuboid() * (size_t)P;
+}
+
+extern "C" int lt_unproject_indexed_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                                        const int32_t* frame_of, const float* grad_out, float* grad_feats, float* grad_conf, int32_t F, int32_t P, int32_t NV,
+                                        int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2, int32_t agg, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    const char* who = "lt_unproject_indexed_bwd";
+    LT_REQUIRE(feats && proj && coords && grad_out && grad_feats, LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(frame_of, LT_ERR_INVALID, "%s: null frame_of", who);
+    LT_REQUIRE(F >= 1 && P >= 1, LT_ERR_INVALID, "%s: needs F >= 1 frames and P >= 1 cuboids (got F=%d P=%d)", who, F, P);
+    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+    LT_REQUIRE(agg == LT_AGG_SUM || agg == LT_AGG_MAX || agg == LT_AGG_SOFTMAX || agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM, LT_ERR_UNSUPPORTED,
+               "%s: unknown aggregation %d", who, agg);
+    const bool is_conf = agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM;
+    LT_REQUIRE(!is_conf || conf, LT_ERR_INVALID, "%s: the conf aggregations need confidences", who);
+    LT_REQUIRE(NV >= 1 && NV <= UB_MANYV && C >= 4 && C % 4 == 0 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_UNSUPPORTED,
+               "%s: needs 1 <= NV <= %d and C %% 4 == 0 (got NV=%d C=%d)", who, UB_MANYV, NV, C);
+    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
+    LT_REQUIRE(F <= 65535, LT_ERR_UNSUPPORTED, "%s: at most 65535 frames (the gather's grid), got %d", who, F);
+    LT_REQUIRE(!env_on("LT_UNPROJ_BWD_ATOMICS"), LT_ERR_UNSUPPORTED,
+               "%s: LT_UNPROJ_BWD_ATOMICS selects the scatter path, which has no indexed form (only the gather takes a frame index)", who);
+    LT_REQUIRE(gather_takes(C), LT_ERR_UNSUPPORTED,
+               "%s: only the gather path takes a frame index, and it needs C a power of two <= 64 (got C=%d; the scatter has no indexed form)", who, C);
+    hipStream_t st = (hipStream_t)stream;
+    UnprojBwdIndexedArgs a;
+    a.frame_of = frame_of; a.F = F; a.P = P; a.p0 = 0;
+    a.mask = view_mask;
+    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.gout = grad_out; a.gfeats = grad_feats; a.gconf = is_conf ? grad_conf : nullptr;
+    a.dxs = nullptr; a.bbox = nullptr; a.gcpart = nullptr; a.txy = nullptr; a.tw = nullptr;
+    a.B = P; a.NV = NV; a.C = C; a.h = h; a.w = w; a.agg = agg;
+    a.v0 = v0; a.v1 = v1; a.v2 = v2; a.nb0 = (int)cdiv(v0, 4); a.nb1 = (int)cdiv(v1, 4); a.nb2 = (int)cdiv(v2, 4);
+    a.nvox = (long long)v0 * v1 * v2;
+    const int nbricks = a.nb0 * a.nb1 * a.nb2;
+    const int nblk1 = blocks_k1(a.nvox, C);
+    const IndexedWs s = indexed_ws(NV, C, v0, v1, v2);
+    const size_t fixed = s.gc_all(P), per_cuboid = s.per_cuboid();
+    LT_REQUIRE(workspace && workspace_bytes >= fixed + per_cuboid && ((size_t)workspace % 16) == 0, LT_ERR_INVALID,
+               "%s: workspace of at least %zu bytes (the confidence partials of all %d cuboids and one cuboid's share of the rest; "
+               "lt_unproject_indexed_bwd_workspace for all cuboids at once), 16-byte aligned", who, fixed + per_cuboid, P);
+    const size_t fit = (workspace_bytes - fixed) / per_cuboid;
+    const size_t cap = P < 65535 ? (size_t)P : 65535;             // K0 and K1 take the chunk's cuboids as grid y
+    const int chunk = (int)(fit < cap ? fit : cap);
+    const int tiles = (int)(cdiv(w, G_TW) * cdiv(h, G_TH));
+    double* gcall = (double*)workspace;                           // (P, nblk1, NV, C), dense
+    for (int p0 = 0; p0 < P; p0 += chunk) {
+        const int nb = P - p0 < chunk ? P - p0 : chunk;
+        UnprojBwdIndexedArgs c = a;
+        c.B = nb; c.p0 = p0;
+        c.coords = coords + (size_t)p0 * a.nvox * 3;
+        c.gout = grad_out + (size_t)p0 * a.nvox * C;
+        c.gcpart = gcall + (size_t)p0 * nblk1 * NV * C;
+        char* wsp = (char*)workspace + fixed;
+        c.dxs = (float*)wsp; wsp += s.s_dx * nb;
+        c.bbox = (int*)wsp; wsp += s.s_bb * nb;
+        c.tw = (float4*)wsp; wsp += s.s_tw * nb;
+        c.txy = (int*)wsp;
+        int rc = launch_taps_dx<true, true>(who, c, dtype, nbricks, nblk1, st);
+        if (rc != LT_OK) return rc;
+        switch (C / 4) {
+            case 1: rc = launch_gather_indexed<1>(c, tiles, st); break;
+            case 2: rc = launch_gather_indexed<2>(c, tiles, st); break;
+            case 4: rc = launch_gather_indexed<4>(c, tiles, st); break;
+            case 8: rc = launch_gather_indexed<8>(c, tiles, st); break;
+            default: rc = launch_gather_indexed<16>(c, tiles, st); break;
+        }
+        if (rc != LT_OK) return rc;
+    }
+    if (a.gconf) {
+        UnprojBwdIndexedArgs c = a;
+        c.gcpart = gcall;
+        hipLaunchKernelGGL(unproj_gconf_finalize_indexed_kernel, dim3((unsigned)(F * (C / (C < UB_FIN_C ? C : UB_FIN_C)))), dim3(UB_MANYV * UB_FIN_C), 0, st, c, nblk1);
+        LT_CHECK_LAUNCH(who);
+    }
+    return LT_OK;
+}
 
 // bytes for ALL B samples at once; lt_unproject_bwd walks the batch in chunks when it is handed less (at least one sample's worth)
 extern "C" size_t lt_unproject_bwd_workspace(int32_t B, int32_t NV, int32_t C, int32_t v0, int32_t v1, int32_t v2) {

@@ -260,6 +260,8 @@ SIGNATURES = {
     "lt_unproject_bwd_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
     "lt_unproject_bwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]),
     "lt_unproject_masked_bwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]),
+    "lt_unproject_indexed_bwd_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
+    "lt_unproject_indexed_bwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]),
     "lt_global_avgpool_bwd": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     "lt_global_avgpool_bwd_dt": (C.c_int, [i32, vp, vp, i32, i32, i32, i32, vp]),
     "lt_softargmax3d_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp, i32, i32, i64, vp]),

@@ -88,11 +88,18 @@ class _VolTrainPlan:
 
     masked (``masked_training`` steps with ``batch["view_mask"]``): the tape records lt_unproject_grid_masked_fwd / lt_unproject_masked_bwd in the
     unmasked pair's place; the (B, NV) uint8 mask rides at the end of the geometry block as in the inference plan, so another mask is just
-    another step of the same tape."""
+    another step of the same tape.
 
-    def __init__(self, model, B, NV, Hh, W, device, masked=False):
+    cuboids (``multi_cuboid_training`` steps with ``batch["cuboid_frame"]``): P = ``cuboids`` cuboids over the B frames.  The backbone and process_features
+    (the frozen backbone's inference plan included) are recorded at B * NV images; the volume, V2V, the soft-argmax and their buffers at P; the tape
+    records lt_unproject_grid_indexed_fwd / lt_unproject_indexed_bwd (with the mask, if ``masked``) in the pair's place.  The P int32 frame indices
+    ride in the geometry block behind the rotations, at the inference plan's offset, and are read inside the kernels only: another assignment of the
+    cuboids to the frames is just another step of the same tape."""
+
+    def __init__(self, model, B, NV, Hh, W, device, masked=False, cuboids=None):
         self.model, self.B, self.NV, self.Hh, self.W, self.device = model, B, NV, Hh, W, device
         self.masked = bool(masked)
+        self.cuboids = None if cuboids is None else int(cuboids)
         self.tape = None
         self.step_id = 0
 
@@ -100,6 +107,8 @@ class _VolTrainPlan:
         import lt_train
         model, B, NV, Hh, W, device = self.model, self.B, self.NV, self.Hh, self.W, self.device
         V, J = model.volume_size, model.num_joints
+        multi = self.cuboids is not None
+        nc = self.cuboids if multi else B          # B frames carry the images, the features and the confidences; everything from the gather on is per cuboid
         lib = H.lib()
         st = torch.cuda.current_stream(device).cuda_stream
         x = images.reshape(B * NV, 3, Hh, W)
@@ -149,10 +158,12 @@ class _VolTrainPlan:
             pf = model.process_features[0]
             self.feats = feats = tape.conv(feats256, pf.weight, pf.bias, None)
             h, w = feats.shape[2], feats.shape[3]
-            o_mask = B * NV * 12 + B * 15          # masked plans: B*NV mask bytes behind the floats (whole words), as in the inference plan
+            # proj B*NV*12 | pos nc*3 | center nc*3 | rot nc*9 | [frame_of nc int32] | [mask B*NV bytes], the inference plan's block (_build_plan)
+            o_fof = B * NV * 12 + nc * 15          # multi-cuboid plans: the frame of every cuboid
+            o_mask = o_fof + (nc if multi else 0)          # masked plans: B*NV mask bytes behind the words (whole words)
             n_geo = o_mask + ((B * NV + 3) // 4 if self.masked else 0)
-            self.G = {"hw": (h, w), "offs": (B * NV * 12, B * NV * 12 + 3 * B, B * NV * 12 + 6 * B), "geo_ring": PinnedRing(n_geo, torch.float32, GEO_RING),
-                      "masked": self.masked, "o_mask": o_mask}
+            self.G = {"hw": (h, w), "offs": (B * NV * 12, B * NV * 12 + 3 * nc, B * NV * 12 + 6 * nc), "geo_ring": PinnedRing(n_geo, torch.float32, GEO_RING),
+                      "masked": self.masked, "o_mask": o_mask, "o_fof": o_fof, "cuboids": nc if multi else None}
             self.geo = torch.zeros(n_geo, dtype=torch.float32, device=device)
             self.n_front = len(tape.fwd_ops)
         else:
@@ -168,15 +179,20 @@ class _VolTrainPlan:
         G["geo_ring"].commit(torch.cuda.current_stream(device))
         if first:
             feats, gp = self.feats, self.geo.data_ptr()
-            self.coords = coords = torch.empty(B, V, V, V, 3, dtype=torch.float32, device=device)
-            vol = tape.alloc((B, V, V, V, 32))
+            self.coords = coords = torch.empty(nc, V, V, V, 3, dtype=torch.float32, device=device)
+            vol = tape.alloc((nc, V, V, V, 32))
             step = float(np.float32(model.cuboid_side / (V - 1)))
             agg = H.AGG[model.volume_aggregation_method]
             cmu = int(bool(model.transfer_cmu_to_human36m))
             volc = self.volc
             conf_p = None if volc is None else volc.t.data_ptr()          # (B, NV, 32) raw confidences; 'conf_norm' is normalised inside the kernels
             mask_p = gp + 4 * G["o_mask"]          # masked plans: the step's (B, NV) mask, behind the geometry in the same block
-            if self.masked:
+            fof_p = gp + 4 * G.get("o_fof", 0)          # multi-cuboid plans: the step's (nc,) int32 frame indices, in the same block
+            if multi:
+                tape.do(lambda s_: H.check(lib.lt_unproject_grid_indexed_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
+                                                                             coords.data_ptr(), conf_p, mask_p if self.masked else None, fof_p, vol.t.data_ptr(),
+                                                                             B, nc, NV, 32, h, w, V, agg, s_), "lt_unproject_grid_indexed_fwd"), "unproject")
+            elif self.masked:
                 tape.do(lambda s_: H.check(lib.lt_unproject_grid_masked_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
                                                                             coords.data_ptr(), conf_p, mask_p, vol.t.data_ptr(), B, NV, 32, h, w, V, agg, s_),
                                            "lt_unproject_grid_masked_fwd"), "unproject")
@@ -204,10 +220,17 @@ class _VolTrainPlan:
                 per_sample = lib.lt_unproject_bwd_workspace(1, NV, 32, V, V, V)
                 # the gather's workspace comes out of the tape's shared main-stream scratch (it is only live during this one op; a private buffer per
                 # cached plan was up to 4 GiB each), capped like op.unproject_heatmaps' autograd path: below the whole batch's worth the
-                # entry point walks the batch in chunks
-                nws = int(max(16, min(per_sample * B, max(per_sample, op.UNPROJECT_BWD_WORKSPACE_CAP))))
+                # entry point walks the batch in chunks (multi-cuboid: the confidence partials of all cuboids and as many cuboids' shares as fit the cap)
+                if multi:
+                    nws = int(max(16, op.indexed_bwd_workspace(nc, NV, 32, V, V, V, cap=op.UNPROJECT_BWD_WORKSPACE_CAP)))
+                else:
+                    nws = int(max(16, min(per_sample * B, max(per_sample, op.UNPROJECT_BWD_WORKSPACE_CAP))))
                 tape._ws_need(nws)
-                if self.masked:
+                if multi:
+                    tape.do(lambda s_: H.check(lib.lt_unproject_indexed_bwd(ac, feats.t.data_ptr(), gp, coords.data_ptr(), conf_p, mask_p if self.masked else None,
+                                                                            fof_p, dvol32.data_ptr(), gfe32.data_ptr(), H.ptr(gconf), B, nc, NV, 32, h, w, V, V, V,
+                                                                            agg, tape._ws.data_ptr(), nws, s_), "lt_unproject_indexed_bwd"), "unproject_bwd")
+                elif self.masked:
                     tape.do(lambda s_: H.check(lib.lt_unproject_masked_bwd(ac, feats.t.data_ptr(), gp, coords.data_ptr(), conf_p, mask_p, dvol32.data_ptr(),
                                                                            gfe32.data_ptr(), H.ptr(gconf), B, NV, 32, h, w, V, V, V, agg, tape._ws.data_ptr(), nws, s_),
                                                "lt_unproject_masked_bwd"), "unproject_bwd")
@@ -226,14 +249,14 @@ class _VolTrainPlan:
                     tape.seed(volc, gconf)            # the head's backward (recorded earlier, so replayed later) starts from here
             tape.add_backward(unproject_bwd)
             self.logits = logits = model.volume_net.record(tape, vol)          # channels-last (B,V,V,V,J) fp32
-            self.kp = kp = torch.empty(B, J, 3, dtype=torch.float32, device=device)
-            self.probs = probs = torch.empty(B, J, V, V, V, dtype=torch.float32, device=device)
-            ws = torch.empty(max(1, lib.lt_softargmax3d_workspace(B, J, V ** 3)), dtype=torch.uint8, device=device)
+            self.kp = kp = torch.empty(nc, J, 3, dtype=torch.float32, device=device)
+            self.probs = probs = torch.empty(nc, J, V, V, V, dtype=torch.float32, device=device)
+            ws = torch.empty(max(1, lib.lt_softargmax3d_workspace(nc, J, V ** 3)), dtype=torch.uint8, device=device)
             self.mult, self.sm = float(model.volume_multiplier), int(bool(model.volume_softmax))
             mult, sm = self.mult, self.sm
-            tape.do(lambda s_: H.check(lib.lt_softargmax3d_fwd(logits.t.data_ptr(), coords.data_ptr(), mult, sm, 1, J, kp.data_ptr(), probs.data_ptr(), B, J, V ** 3,
+            tape.do(lambda s_: H.check(lib.lt_softargmax3d_fwd(logits.t.data_ptr(), coords.data_ptr(), mult, sm, 1, J, kp.data_ptr(), probs.data_ptr(), nc, J, V ** 3,
                                                                ws.data_ptr(), s_), "lt_softargmax3d_fwd"))
-            self.gl = torch.empty(B, V ** 3, J, dtype=torch.float32, device=device)         # d loss / d logits, channels-last like the logits (fp32 in every
+            self.gl = torch.empty(nc, V ** 3, J, dtype=torch.float32, device=device)         # d loss / d logits, channels-last like the logits (fp32 in every
             tape.seed(logits, self.gl.view(logits.t.shape))                                  # precision: the logits layer stores fp32, TrainTape._act_grad rounds its dY once)
         else:
             tape.replay(tape.fwd_ops, self.n_front)
@@ -249,7 +272,7 @@ class _VolTrainPlan:
         self.conf_out = conf_out
         feats_out = torch.empty(B, NV, 32, h, w, dtype=torch.float32, device=device)          # the returned features, contiguous like the reference's
         H.check(lib.lt_nhwc_to_nchw_f32(ac, self.feats.t.data_ptr(), feats_out.data_ptr(), B * NV, 32, h * w, 32, st), "lt_nhwc_to_nchw_f32")
-        base_points = self.geo[o_cen:o_rot].reshape(B, 3).clone()
+        base_points = self.geo[o_cen:o_rot].reshape(nc, 3).clone()
         return self.kp.clone(), self.probs.clone(), feats_out, self.coords.clone(), base_points, position, sides
 
     def _frozen_backbone(self, x, st):
@@ -381,6 +404,9 @@ class VolumetricTriangulationNet(_PlannedNet):
         # True: a train() forward takes batch["view_mask"] -- the masked training step (lt_unproject_grid_masked_fwd / lt_unproject_masked_bwd: every
         # sample's volume and its gradient over its valid views alone; the backbone still runs on every image).  False: a mask in train() is refused.
         self.masked_training = False
+        # True: a train() forward takes batch["cuboid_frame"] -- the multi-cuboid training step (lt_unproject_grid_indexed_fwd / lt_unproject_indexed_bwd:
+        # the backbone runs, forward and backward, on the F frames once; every frame's features get the sum of its cuboids' gradients).  False: refused.
+        self.multi_cuboid_training = False
         if self.volume_aggregation_method not in H.AGG:
             raise ValueError("Unknown volume_aggregation_method: {}".format(self.volume_aggregation_method))
         # same config mutation as the reference (:228-231)
@@ -556,7 +582,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         (overwritten at :277); ``batch`` as built by datasets/utils.py:14-37 (``cameras``, and
         ``pred_keypoints_3d`` or ``keypoints_3d``).  Returns the reference's 7-tuple (:355).
 
-        ``batch["cuboid_frame"]`` (eval only): several cuboids per frame.  P >= 1 integers in [0, B), any order -- the frame of every cuboid; the joints in
+        ``batch["cuboid_frame"]`` (eval(); train() with ``multi_cuboid_training``): several cuboids per frame.  P >= 1 integers in [0, B), any order -- the frame of every cuboid; the joints in
         the batch then have P entries, one base point per cuboid.  The backbone runs on the B frames once; keypoints_3d, volumes, cuboids, coord_volumes and
         base_points come back with P entries, features and vol_confidences with B.  One plan per (B, P); another assignment is another forward of it.
 
@@ -566,7 +592,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         B, NV = images.shape[:2]
         cf = _batch_cuboid_frame(batch, B, "VolumetricTriangulationNet")          # optional: several cuboids per frame, refused before any launch
         if cf is not None:
-            if _bn_in_train_mode(self):
+            if _bn_in_train_mode(self) and not self.multi_cuboid_training:
                 raise NotImplementedError("VolumetricTriangulationNet: batch['cuboid_frame'] is inference only (there is no indexed unprojection backward); "
                                           "call eval() first")
             key = "keypoints_3d" if self.use_gt_pelvis else "pred_keypoints_3d"
@@ -638,7 +664,9 @@ class VolumetricTriangulationNet(_PlannedNet):
                                "train.py:424 does); %d tensors are elsewhere, e.g. %s" % (images.device, len(off), off[0]))
         B, NV = images.shape[:2]
         masked = batch.get("view_mask") is not None          # (forward() let it through: masked_training)
-        key = self._train_plan_key(B, NV, images.shape[3], images.shape[4], images.device, params, masked)
+        cf = batch.get("cuboid_frame")                       # (forward() let it through: multi_cuboid_training; checked, one base point per cuboid)
+        nc = None if cf is None else len(cf)
+        key = self._train_plan_key(B, NV, images.shape[3], images.shape[4], images.device, params, masked, nc)
         if getattr(self, "train_precision", "fp32") not in ("fp32", "bf16", "act16", "fp8v2v"):
             raise ValueError("train_precision must be 'fp32' (the reference's precision), 'bf16' (bf16 MFMA convolutions, fp32 storage), 'act16' (bf16 MFMA "
                              "convolutions AND bf16 activations / activation gradients) or 'fp8v2v' (act16 with V2V's 3x3x3 convolutions on the fp8 MFMA)")
@@ -656,7 +684,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         if plan is None:
             while len(plans) >= 2:
                 plans.popitem(last=False)          # frees its activations and gradient buffers
-            plan = plans[key] = _VolTrainPlan(self, B, NV, images.shape[3], images.shape[4], images.device, masked=masked)
+            plan = plans[key] = _VolTrainPlan(self, B, NV, images.shape[3], images.shape[4], images.device, masked=masked, cuboids=nc)
         plans.move_to_end(key)
         kp, probs, feats, coords, base_points = _VolTrainFn.apply(plan, images, batch, *params)
         # every BatchNorm's num_batches_tracked += 1 (what nn.BatchNorm does in train()): ONE liblt_hip launch over a table of the counters'
@@ -668,17 +696,19 @@ class VolumetricTriangulationNet(_PlannedNet):
             tab = self.__dict__["_nbt_table"] = (tab_key, torch.tensor(tab_key, dtype=torch.int64).to(images.device))
         H.check(H.lib().lt_add_i64_multi(tab[1].data_ptr(), len(nbt), 1, torch.cuda.current_stream(images.device).cuda_stream), "lt_add_i64_multi")
         position, sides = self.__dict__.pop("_train_extra")
-        cuboids = [volumetric.Cuboid3D(position[i], sides) for i in range(images.shape[0])]
+        cuboids = [volumetric.Cuboid3D(position[i], sides) for i in range(len(position))]          # (one per cuboid: the frames, or batch["cuboid_frame"]'s P)
         return kp, feats, probs, plan.conf_out, cuboids, coords, base_points
 
-    def _train_plan_key(self, B, NV, Hh, W, device, params, masked=False):
+    def _train_plan_key(self, B, NV, Hh, W, device, params, masked=False, cuboids=None):
         """Everything a training plan bakes in.  ``masked``: its tape records the masked unprojection pair (steps with ``batch["view_mask"]`` under
-        ``masked_training``); steps without a mask keep their plan: an unmasked key is the tuple it always was."""
+        ``masked_training``); steps without a mask keep their plan: an unmasked key is the tuple it always was.  ``cuboids``: the P of a multi-cuboid step
+        over B frames (``batch["cuboid_frame"]`` under ``multi_cuboid_training``); a step without it keeps its key and its tape."""
         key = (B, NV, Hh, W, device, self.volume_size, float(self.cuboid_side), float(self.volume_multiplier),
                bool(self.volume_softmax), self.volume_aggregation_method, bool(self.transfer_cmu_to_human36m), self.num_joints,
                tuple(p.requires_grad for p in params), id(getattr(self, "grad_reducer", None)), getattr(self, "train_precision", "fp32"),
                tuple(c.training for c in self.modules() if isinstance(c, nn.modules.batchnorm._BatchNorm)))
-        return key + ("view_mask",) if masked else key
+        key = key + ("view_mask",) if masked else key
+        return key if cuboids is None else key + ("cuboids", int(cuboids))
 
     def _chunk_plan(self, images, batch, lo, hi):
         """Samples lo .. hi of the call and the plan of that shape: (images, batch, B, P)."""

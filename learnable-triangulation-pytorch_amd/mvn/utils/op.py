@@ -151,8 +151,57 @@ class _UnprojectFn(torch.autograd.Function):
         return gfeats.permute(0, 1, 4, 2, 3).to(feats.dtype), None, None, gconf, None, None
 
 
+class _UnprojectIndexedFn(torch.autograd.Function):
+    """lt_unproject_indexed_fwd / lt_unproject_indexed_bwd as one autograd node (several cuboids per frame): what autograd derives for unproject_heatmaps on
+    heatmaps[frame_index], proj[frame_index], conf[frame_index] -- every frame's heatmaps and confidences get the sum of its cuboids' gradients, a frame
+    without a cuboid zeros -- without the gathered copies.  fof: the (P,) int32 device tensor of frames; mask: a (F,NV) uint8 device tensor or None."""
+
+    @staticmethod
+    def forward(ctx, heatmaps, P, cv, conf, method, mask, fof):
+        feats = _as_channels_last(heatmaps, 2)
+        out = _unproject_launch(feats, P, cv, conf, method, mask, fof)
+        ctx.save_for_backward(feats, P, cv, conf if conf is not None else torch.empty(0, device=feats.device), fof)
+        ctx.method, ctx.has_conf, ctx.mask = method, conf is not None, mask
+        return out.permute(0, 4, 1, 2, 3)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        feats, P, cv, conf, fof = ctx.saved_tensors
+        conf = conf if ctx.has_conf else None
+        F, NV, h, w, Cc = feats.shape
+        nc = cv.shape[0]
+        g = grad_out.permute(0, 2, 3, 4, 1).float().contiguous()               # (P, v0, v1, v2, C) channels-last fp32
+        gfeats = torch.empty(F, NV, h, w, Cc, dtype=torch.float32, device=feats.device)      # written completely by the gather, empty frames included
+        gconf = torch.empty_like(conf) if conf is not None else None
+        v0, v1, v2 = cv.shape[1:4]
+        lib = H.lib()
+        # the confidence partials of all cuboids plus as many cuboids' shares as fit the cap (the entry walks the cuboids in chunks, same bits)
+        ws = torch.empty(max(16, indexed_bwd_workspace(nc, NV, Cc, v0, v1, v2, cap=UNPROJECT_BWD_WORKSPACE_CAP)), dtype=torch.uint8, device=feats.device)
+        agg = H.AGG["conf"] if conf is not None else H.AGG[ctx.method]
+        H.check(lib.lt_unproject_indexed_bwd(H.dtype_code(feats.dtype), feats.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), H.ptr(ctx.mask), fof.data_ptr(),
+                                             g.data_ptr(), gfeats.data_ptr(), H.ptr(gconf), F, nc, NV, Cc, h, w, v0, v1, v2, agg, ws.data_ptr(), ws.numel(),
+                                             H.cur_stream()), "lt_unproject_indexed_bwd")
+        return gfeats.permute(0, 1, 4, 2, 3).to(feats.dtype), None, None, gconf, None, None, None
+
+
+def indexed_bwd_workspace(P, NV, C, v0, v1, v2, chunk=None, cap=None):
+    """Bytes of lt_unproject_indexed_bwd's workspace for P cuboids walked ``chunk`` cuboids at a time (None: all at once, lt_unproject_indexed_bwd_workspace
+    itself; 1: the least the entry takes): the fp64 confidence partials of ALL P cuboids -- min(2048, ceil(nvox C / 1024)) NV C 8 bytes each, rounded up to
+    256 in all (include/lt_hip.h) -- plus ``chunk`` cuboids' shares of the rest.  cap: the largest chunk whose workspace stays within ``cap`` bytes
+    instead (at least one cuboid).  0 where the gather does not take C."""
+    whole = H.lib().lt_unproject_indexed_bwd_workspace(P, NV, C, v0, v1, v2)
+    if whole == 0:
+        return 0
+    nvox = v0 * v1 * v2
+    partials = (min(2048, -(-nvox * (C // 4) // 256)) * NV * C * 8 * P + 255) // 256 * 256
+    share = (whole - partials) // P
+    if cap is not None:
+        chunk = max(1, min(P, (cap - partials) // share))
+    return whole if chunk is None else partials + share * min(P, int(chunk))
+
+
 def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="sum", vol_confidences=None, view_mask=None,
-                       masked_backward=False, frame_index=None):
+                       masked_backward=False, frame_index=None, indexed_backward=False):
     """heatmaps (B,NV,C,h,w), proj_matricies (B,NV,3,4), coord_volumes (B,V0,V1,V2,3),
     vol_confidences (B,NV,C) for 'conf*' -> volumes (B,C,V0,V1,V2).  Reference: op.py:99-166.  Differentiable with respect to the
     heatmaps and the confidences (lt_unproject_bwd) whenever one of them requires grad.
@@ -168,12 +217,20 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
     frame_index: several cuboids per frame (lt_unproject_indexed_fwd).  heatmaps (F,NV,C,h,w), proj_matricies (F,NV,3,4), vol_confidences (F,NV,C) and
     view_mask (F,NV) are per FRAME, coord_volumes (P,V0,V1,V2,3) per cuboid; frame_index holds the P frames of the cuboids (a sequence, an array or a
     tensor of integers in [0, F), any order; checked on the host when it lives there -- a device tensor is used as it is, and the kernel clamps what
-    it reads) -> volumes (P,C,V0,V1,V2), bit-identical to this function on the inputs gathered by frame_index, without the copies.  Inference only:
-    NotImplementedError when an input requires grad.  None takes exactly the path without it."""
+    it reads) -> volumes (P,C,V0,V1,V2), bit-identical to this function on the inputs gathered by frame_index, without the copies.  Inference only
+    by default: NotImplementedError when an input requires grad.  None takes exactly the path without it.
+
+    indexed_backward=True opts into the differentiable indexed op (lt_unproject_indexed_bwd): what autograd derives for this function on the inputs
+    gathered by frame_index -- a frame's heatmaps and confidences get the sum of its cuboids' gradients, a frame without a cuboid zeros.  Gather path
+    only (C a power of two <= 64); ignored without a frame_index.  A view_mask then needs masked_backward=True as well."""
     if volume_aggregation_method not in _METHODS:
         raise ValueError("Unknown volume_aggregation_method: {}".format(volume_aggregation_method))
-    if frame_index is not None and torch.is_grad_enabled() and (heatmaps.requires_grad or (torch.is_tensor(vol_confidences) and vol_confidences.requires_grad)):
+    indexed_grad = frame_index is not None and torch.is_grad_enabled() and (heatmaps.requires_grad or
+                                                                              (torch.is_tensor(vol_confidences) and vol_confidences.requires_grad))
+    if indexed_grad and not indexed_backward:
         raise NotImplementedError("unproject_heatmaps: frame_index is inference only (no indexed backward); call it under torch.no_grad()")
+    if indexed_grad and view_mask is not None and not masked_backward:
+        raise NotImplementedError("unproject_heatmaps: view_mask is inference only (no masked backward); call it under torch.no_grad()")
     H.require_gpu(heatmaps, "heatmaps")
     H.dtype_code(heatmaps.dtype)
     P = proj_matricies.to(heatmaps.device, torch.float32).contiguous()
@@ -192,6 +249,8 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
         if cv.shape[0] != fof.numel():
             raise ValueError("frame_index has %d entries, coord_volumes holds %d cuboids" % (fof.numel(), cv.shape[0]))
         mask = None if view_mask is None else _view_mask_device(view_mask, F, NV, heatmaps.device)
+        if indexed_grad and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad)):
+            return _UnprojectIndexedFn.apply(heatmaps, P, cv, conf, volume_aggregation_method, mask, fof)
         return _unproject_launch(_as_channels_last(heatmaps, 2), P, cv, conf, volume_aggregation_method, mask, fof).permute(0, 4, 1, 2, 3)
     if view_mask is not None:
         needs_grad = torch.is_grad_enabled() and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad))
