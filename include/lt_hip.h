@@ -743,8 +743,10 @@ int lt_heatmap_argmax_nchw_f32(const float* heatmaps, int32_t ld, float* heatmap
 /* RANSACTriangulationNet.triangulate_ransac (reference :75-128) for every (sample, joint), fp64 inside.  proj B,NV,3,4 fp32;
  * points B,NV,J,2 int64; pairs B,J,n_iters,2 int32 = the 2-view hypotheses to try, in order (the reference's random draws), or
  * NULL = every pair (a, b), a < b, in lexicographic order (exhaustive: always at least as large an inlier set as any draw; n_iters
- * is then ignored).  A hypothesis' inlier set = the pair + every view with reprojection error 1/2 |p - pi(X)| < eps, kept when
- * strictly larger than the best so far; the final DLT on the inliers is refined with direct_opt by minimising scipy's
+ * is then ignored).  A draw with an index outside [0, NV) or with two equal indices is skipped (nothing outside the problem is read);
+ * the two indices of a valid draw may come in either order.  A hypothesis' inlier set = the pair + every view with reprojection error
+ * 1/2 |p - pi(X)| < eps, kept when strictly larger than the best so far (among sets of equal size the first found stays); no valid draw
+ * at all: the inlier set is all NV views.  The final DLT on the inliers is refined with direct_opt by minimising scipy's
  * least_squares(loss='huber') objective.  out_kp3d B,J,3 fp32; out_inliers B,J,NV uint8 (1 = inlier) or NULL.  2 <= NV <= 32. */
 int lt_triangulate_ransac(const float* proj, const int64_t* points, const int32_t* pairs, int32_t n_iters, double eps, int32_t direct_opt,
                           float* out_kp3d, uint8_t* out_inliers, int32_t B, int32_t NV, int32_t J, void* stream);

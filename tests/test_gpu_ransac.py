@@ -10,20 +10,11 @@ import torch
 import lt_hip as H
 from gpu_util import check, record, rel_err
 from oracle import spec, synth
+from ransac_ref import huber_cost
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 CASES = [(nv, d) for nv in (2, 3, 4, 8) for d in (0, 1)]
-
-
-def huber_cost(P, pts, X, inl):
-    """scipy's least_squares(loss='huber', f_scale=1) cost 0.5 sum_v rho(r_v^2), r_v = 1/2 |p_v - pi_v(X)| over the inlier views."""
-    c = 0.0
-    for v in np.nonzero(inl)[0]:
-        q = P[v].astype(np.float64) @ np.append(X, 1.0)
-        z = 0.25 * float(np.sum((pts[v] - q[:2] / q[2]) ** 2))
-        c += z if z <= 1 else 2 * np.sqrt(z) - 1
-    return 0.5 * c
 
 
 def _argmax_case(N, J, h, w, ld, seed):

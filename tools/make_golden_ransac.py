@@ -1,7 +1,8 @@
-"""Generates tests/golden/ransac_ops.npz and tests/golden/ransac_net.npz by running the REFERENCE's RANSACTriangulationNet (CPU, numpy +
-scipy) where the reference tree is available (the same loader as oracle/make_golden.py).  Writes only these two files:
+"""Generates tests/golden/ransac_ops.npz, tests/golden/ransac_net.npz and tests/golden/ransac_branches.npz by running the REFERENCE's
+RANSACTriangulationNet (CPU, numpy + scipy) where the reference tree is available (the same loader as oracle/make_golden.py).  Writes
+only these files, or with --only ops|net|branches only that one (the others stay byte-identical):
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_ransac.py
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_ransac.py [--only branches]
 
 Every problem is solved by the reference twice:
   * "replay": random.seed fixed, random.sample wrapped so that the draws the reference makes are logged (the GPU kernel replays them);
@@ -9,7 +10,8 @@ Every problem is solved by the reference twice:
               the mode lt_triangulate_ransac runs by default.
 For each run the fixture keeps the inlier mask, the point before and after the Huber refinement, scipy's final cost and a
 ``well_posed`` flag (scipy restarted from the DLT point moved by 1 mm, and scipy with tolerances of 1e-14, land within 1e-5 relative
-of the same point).
+of the same point).  ransac_branches.npz: NV = 16 and 32 (inlier sets far wider than the 8 views of ransac_ops.npz: the refinement's
+per-view starts and 32-bit masks), the exhaustive run only, for tests/test_gpu_ransac_kernels.py.
 """
 import itertools
 import json
@@ -21,8 +23,9 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from oracle import ref_loader, spec, synth  # noqa: E402
+from ransac_ref import synth_problems  # noqa: E402  (the generator the tests share)
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 EPS = 15
@@ -93,12 +96,12 @@ def eps_margin(errs):
     return float(np.abs(e - EPS).min()) if e.size else np.inf
 
 
-def solve_problem(ref, P, pts, pairs=None):
+def solve_problem(ref, P, pts, pairs=None, modes=("replay", "exh")):
     """Both runs of one problem (P (NV,3,4) fp32, pts (NV,2) int64).  pairs: replay these draws instead of random ones."""
     NV = len(pts)
     out = {}
     margins = []
-    for mode in ("replay", "exh"):
+    for mode in modes:
         if mode == "replay":
             sched, n = (pairs, len(pairs)) if pairs is not None else (None, 10)
         else:
@@ -119,32 +122,6 @@ def solve_problem(ref, P, pts, pairs=None):
         mask[inl] = 1
         out[mode] = {"post": post, "pre": pre, "inl": mask, "draws": np.array(draws, np.int32), "cost": cost, "well": well}
     return out, min(margins)
-
-
-def synth_problems(rs, B, NV, J, image=384):
-    """Cameras on a ring of ~5 m around a 2 m volume, realistic K for 384^2 crops, joints projected and quantised to the 4-pixel grid
-    of argmax x 4, 0-2 outlier views per problem."""
-    P = np.zeros((B, NV, 3, 4), np.float32)
-    pts = np.zeros((B, NV, J, 2), np.int64)
-    for b in range(B):
-        for v in range(NV):
-            phi = 2 * np.pi * v / NV + rs.uniform(-0.2, 0.2)
-            C = np.array([5000 * np.cos(phi), 5000 * np.sin(phi), rs.uniform(800, 1800)])
-            fwd = -C / np.linalg.norm(C)
-            right = np.cross(fwd, [0, 0, 1.0]); right /= np.linalg.norm(right)
-            R = np.stack([right, np.cross(fwd, right), fwd])
-            f = rs.uniform(600, 900)
-            K = np.array([[f, 0, image / 2 + rs.uniform(-8, 8)], [0, f * rs.uniform(0.99, 1.01), image / 2 + rs.uniform(-8, 8)], [0, 0, 1]])
-            P[b, v] = (K @ np.concatenate([R, (-R @ C)[:, None]], 1)).astype(np.float32)
-        X = rs.uniform(-1000, 1000, (J, 3))
-        for v in range(NV):
-            q = np.concatenate([X, np.ones((J, 1))], 1) @ P[b, v].astype(np.float64).T
-            pts[b, v] = (np.round(q[:, :2] / q[:, 2:] / 4) * 4).astype(np.int64)
-        for j in range(J):
-            nout = rs.randint(0, min(2, NV - 2) + 1)
-            for v in rs.choice(NV, nout, replace=False):
-                pts[b, v, j] = rs.randint(0, image // 4, 2) * 4
-    return P, pts
 
 
 def gen_ops(mvn):
@@ -192,6 +169,34 @@ def gen_ops(mvn):
         out["rep_X"] = X3
         out["rep_err"] = np.stack([ref._rep(X3, pts[0, :, j], P[0]) for j in range(J)])      # (J, J 3D points, NV)
     np.savez_compressed(os.path.join(GOLD, "ransac_ops.npz"), **out)
+
+
+def gen_branches(mvn):
+    """B = 1, J = 12 at NV = 16 and 32 from RandomState(NV), direct optimisation, the exhaustive schedule only: solve_problem's record of
+    the reference's triangulate_ransac + scipy under the tags nv16_d1 and nv32_d1."""
+    ref = RefRansac(mvn)
+    B, J = 1, 12
+    out = {}
+    with ref:
+        for NV in (16, 32):
+            random.seed(NV)
+            P, pts = synth_problems(np.random.RandomState(NV), B, NV, J)
+            res = {k: [] for k in ("post", "pre", "inl", "cost", "well")}
+            margin = np.inf
+            for j in range(J):
+                r, mg = solve_problem(ref, P[0], pts[0, :, j], modes=("exh",))
+                margin = min(margin, mg)
+                for k in res:
+                    res[k].append(r["exh"][k])
+            assert margin >= 1e-6, (NV, margin)
+            tag = "nv%d_d1" % NV
+            out[tag + "_P"] = P
+            out[tag + "_pts"] = pts
+            for k, v in res.items():
+                a = np.array(v)
+                out["%s_exh_%s" % (tag, k)] = a.reshape((B, J) + a.shape[1:])
+            print("ransac_branches %s: %d problems, %d well posed, min |err - eps| %.2e" % (tag, B * J, int(out[tag + "_exh_well"].sum()), margin))
+    np.savez_compressed(os.path.join(GOLD, "ransac_branches.npz"), **out)
 
 
 def solve_problem_nodirect(ref, P, pts):
@@ -259,11 +264,16 @@ def gen_net(mvn):
 
 
 def main():
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--only", choices=("ops", "net", "branches"), help="write this fixture alone")
+    only = ap.parse_args().only
     torch.manual_seed(0)
     torch.set_num_threads(8)
     mvn = ref_loader.load()
-    gen_ops(mvn)
-    gen_net(mvn)
+    for name, gen in (("ops", gen_ops), ("net", gen_net), ("branches", gen_branches)):
+        if only in (None, name):
+            gen(mvn)
 
 
 if __name__ == "__main__":
