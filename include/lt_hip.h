@@ -328,6 +328,27 @@ int lt_unproject_grid_indexed_fwd(int32_t dtype, const void* feats, const float*
                                   float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask,
                                   const int32_t* frame_of, void* out, int32_t F, int32_t P, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V,
                                   int32_t agg, void* stream);
+/* Ragged view batches: samples with different numbers of views, without padding.  The T = sum(n_b) views of the B samples lie sample-major
+ * (sample 0's views first):
+ *   by view   (T): feats T,h,w,C   proj T,3,4   conf T,C or NULL
+ *   by sample (B): coords / coords_out B,v0,v1,v2,3   out B,v0,v1,v2,C   pos, center B,3   rot B,9
+ *   view_base: DEVICE (B + 1) int32, the exclusive prefix sum of the counts: sample b reads rows view_base[b] + v, v < n_b = view_base[b+1] - view_base[b].
+ *   NVcap: the most views a sample may have, 1..32; it selects the kernel as NV does for the other entries (4 or 8 with bf16, C = 32, view softmax and
+ *          a bricked volume: the fused kernel; NVcap <= 8: the register-resident generic kernel; else the recomputing one).
+ * The kernels are the ragged instantiations of the masked forms: sample b's validity bits are the prefix (1 << n_b) - 1, so the result is bit-identical
+ * to lt_unproject_masked_fwd / lt_unproject_grid_masked_fwd on the inputs padded to (B, NVcap) with a prefix mask -- and with every n_b = NVcap to the
+ * unmasked entries on the same tensors seen as (B, NVcap, ...).  A view slot past n_b issues no feature load, and the fused kernel, which projects into
+ * every slot, loads the projection of the sample's last view in such a slot's place: no address outside the T rows is formed for a load.  A workgroup
+ * reads its sample's two offsets once, as scalars, and clamps n_b into [0, min(NVcap, T)] and the first row into [0, T - n_b]: a bad table cannot make
+ * the kernel read outside feats, proj or conf -- it reads wrong views instead; callers check their counts.  n_b = 0 writes zeros.
+ * NULL feats, proj, out, view_base (coords, or pos / center / rot / coords_out), B < 1, T < 1, NVcap outside [1, 32], a bad dtype or aggregation code:
+ * LT_ERR_INVALID before any device work. */
+int lt_unproject_ragged_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const int32_t* view_base,
+                            void* out, int32_t B, int32_t T, int32_t NVcap, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2,
+                            int32_t agg, void* stream);
+int lt_unproject_grid_ragged_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
+                                 float step, int32_t cmu_transfer, float* coords_out, const float* conf, const int32_t* view_base, void* out,
+                                 int32_t B, int32_t T, int32_t NVcap, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream);
 /* The seam of the cascade (lt_plan_forward_cascade, CascadeTriangulationNet): the pelvis and cuboid algebra of VolumetricTriangulationNet.forward
  * (triangulation.py:284-296) on joints that are already on the device, bit-identical to what the host route writes into a plan's geometry block.
  *   keypoints_3d: DEVICE (B, J, 3) fp32.  kind LT_KIND_MPII: base = joint 6; LT_KIND_COCO: base = (joint 11 + joint 12) / 2, added and halved in fp32.
@@ -709,6 +730,15 @@ int lt_alg_tail_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld
 int lt_alg_tail_masked_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
                            const uint8_t* view_mask, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t NV,
                            int32_t J, void* stream);
+/* lt_alg_tail_fwd over ragged view batches (the layout of lt_unproject_ragged_fwd): keypoints_hm and keypoints_2d T,J,2, conf_raw T,ld_conf,
+ * confidences T,J, proj T,3,4, keypoints_3d B,J,3; view_base DEVICE (B + 1) int32.  Sample b is lt_alg_tail_fwd on its rows view_base[b] ..
+ * view_base[b+1] alone: confidences normalised over the sample's views + 1e-5, its k-th view into partial k % 4, the DLT over exactly those rows in
+ * order -- bit-identical to lt_alg_tail_masked_fwd on the inputs padded to (B, NVcap) with a prefix mask.  The count is clamped into
+ * [0, min(NVcap, T)] and the first row into [0, T - count] on the device; a sample with fewer than two views gets NaN joints (the hosts refuse
+ * such counts before launching).  NULL keypoints_hm, proj, keypoints_3d or view_base, B < 1, T < 1, J < 1, NVcap outside [1, 32]: LT_ERR_INVALID. */
+int lt_alg_tail_ragged_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                           const int32_t* view_base, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t T,
+                           int32_t NVcap, int32_t J, void* stream);
 /* The algebraic tail with the statistics of its joints (mvn.utils.multiview.triangulation_stats states them in numpy fp64).  view_mask NULL:
  * keypoints_2d, confidences and keypoints_3d are bit for bit lt_alg_tail_fwd's; view_mask DEVICE (B, NV): lt_alg_tail_masked_fwd's (same loops, same
  * dlt_add_view / SVD sequence).  stats2d: the B*NV*J,5 records of lt_softargmax2d_stats_fwd for keypoints_hm.  Additional outputs:
@@ -1064,6 +1094,27 @@ int lt_plan_create_vol_multi(const lt_vol_plan_config* cfg, int32_t P, const lt_
 int lt_plan_forward_vol_multi(lt_plan* plan, const float* images, const double* K_host, const double* R_host, const double* t_host,
                               const int32_t* cuboid_frame_host, const double* base_points_host, const double* rot_host, float* keypoints_3d,
                               float* volumes, float* features, float* coord_volumes, float* vol_confidences, void* stream);
+/* Ragged view batches at plan level: B samples with different numbers of views, T = sum(n_b) images in all, sample 0's views first (the layout of
+ * lt_unproject_ragged_fwd).  cfg->B = the samples, cfg->NV = NVcap, the most views a sample may have (1 .. 32; 4 and 8 reach the fused gather under its
+ * usual conditions); the config structs and lt_plan_info_t keep their layout.  The backbone is recorded at T images; the gather is
+ * lt_unproject_grid_ragged_fwd, the algebraic tail lt_alg_tail_ragged_fwd.  The B + 1 offsets are formed from view_counts_host (HOST int32[B]) at every
+ * forward and travel outside the captured graph: other counts with the same (B, T, NVcap) are another forward of the plan.
+ * lt_plan_create_vol_ragged / lt_plan_forward_vol_ragged: as lt_plan_create_vol / lt_plan_forward_vol with images DEVICE (T, 3, H, W), K, R, t HOST fp64 per
+ *   image (T), base_points_host and rot_host per sample (B); outputs as lt_plan_forward_vol with features (T, 32, h, w) and vol_confidences (T, 32) (raw).
+ *   Counts 1 .. NVcap.  lt_plan_set_keypoint_stats works (B rows).
+ * lt_plan_create_alg_ragged / lt_plan_forward_alg_ragged: model LT_MODEL_ALG only; images (T, 3, H, W), proj DEVICE (T, 3, 4); keypoints_3d (B, J, 3),
+ *   keypoints_2d (T, J, 2) fp32, heatmaps (T, J, h, w), confidences (T, J).  Counts 2 .. NVcap.
+ * LT_ERR_INVALID before any device call: NVcap outside 1 .. 32, T outside [B (algebraic: 2 B), B NVcap], counts outside their range or not summing to T
+ * (the message names the sample), the plain forwards (lt_plan_forward_vol, _vol_multi, _alg) on a ragged plan and the ragged forwards on any other plan,
+ * lt_plan_set_view_mask on a ragged plan (drop the view from the batch instead).  LT_ERR_UNSUPPORTED: lt_plan_set_alg_keypoint_stats on a ragged plan.
+ * Results are bit-identical to the Python host's (batch["view_counts"]). */
+int lt_plan_create_vol_ragged(const lt_vol_plan_config* cfg, int32_t T, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out);
+int lt_plan_forward_vol_ragged(lt_plan* plan, const float* images, const double* K_host, const double* R_host, const double* t_host,
+                               const int32_t* view_counts_host, const double* base_points_host, const double* rot_host, float* keypoints_3d,
+                               float* volumes, float* features, float* coord_volumes, float* vol_confidences, void* stream);
+int lt_plan_create_alg_ragged(const lt_alg_plan_config* cfg, int32_t T, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out);
+int lt_plan_forward_alg_ragged(lt_plan* plan, const float* images, const float* proj, const int32_t* view_counts_host, float* keypoints_3d,
+                               void* keypoints_2d, float* heatmaps, float* confidences, void* stream);
 /* Per-sample view masks: mask_host is HOST (B, NV) uint8, non-zero = the view is there, NULL = all valid.  Sample b of every later forward gets what
  * the plan gives for that sample on its valid views alone: the gather skips masked views (lt_unproject_grid_masked_fwd), the algebraic tail normalises
  * the confidences over the valid views and forms the DLT from their rows (lt_alg_tail_masked_fwd: masked confidences are 0); a cascade plan applies the

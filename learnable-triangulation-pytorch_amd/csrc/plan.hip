@@ -293,6 +293,13 @@ struct lt_plan {
     // several cuboids per frame (lt_plan_create_vol_multi): P > 0 cuboids over the cfg.B frames -- the backbone is recorded at B * NV images, the gather, V2V and
     // the tail at P; the block is proj B*NV*12 | pos P*3 | center P*3 | rot P*9 | frame_of P int32 (o_fof, in floats).  P == 0: one cuboid per sample.
     int P = 0; size_t o_fof = 0;
+    // ragged view batches (lt_plan_create_vol_ragged / lt_plan_create_alg_ragged): T > 0 images over the cfg.B samples, cfg.NV = NVcap -- the backbone is recorded
+    // at T images, the gather (lt_unproject_grid_ragged_fwd) or the algebraic tail (lt_alg_tail_ragged_fwd) finds a sample's views through the B + 1 int32
+    // offsets.  Volumetric plans carry them in the geometry block behind the rotations (o_vb, in floats), algebraic plans in a block of their own (vb_dev)
+    // behind its pinned ring.  T == 0: NV views per sample.
+    int T = 0; size_t o_vb = 0;
+    int32_t* vb_dev = nullptr; StagingRing avb;
+    int images() const { return T ? T : cfg.B * cfg.NV; }
     int cuboids() const { return P ? P : cfg.B; }
     // results
     Act feats, vol, logits, volc;
@@ -971,7 +978,8 @@ struct lt_plan {
         const int B = cuboids();          // the gather, V2V and the tail: per cuboid; the backbone and the features: per frame
         Act f256, no_hm;
         const bool conf_head = cfg.aggregation == LT_AGG_CONF || cfg.aggregation == LT_AGG_CONF_NORM;
-        PL_TRY(record_backbone(F * NV, cfg.H, cfg.W, cfg.num_layers, cfg.style_caffe != 0, conf_head ? "backbone.vol_confidences" : nullptr, false, f256, volc, no_hm));
+        const int NI = images();
+        PL_TRY(record_backbone(NI, cfg.H, cfg.W, cfg.num_layers, cfg.style_caffe != 0, conf_head ? "backbone.vol_confidences" : nullptr, false, f256, volc, no_hm));
         WT pw; const float* pb;
         PL_TRY(get("process_features.0.weight", pw, 4)); PL_TRY(get_vec("process_features.0.bias", (int)pw.s[0], &pb));
         LT_REQUIRE(pw.s[0] == 32, LT_ERR_UNSUPPORTED, "lt_plan_create_vol: process_features has %d output channels (32)", (int)pw.s[0]);
@@ -980,8 +988,9 @@ struct lt_plan {
         feats.pooled = false;
         hm_h = feats.h; hm_w = feats.w;
         // geometry block + its pinned staging ring
-        o_pos = (size_t)F * NV * 12; o_cen = o_pos + 3 * B; o_rot = o_pos + 6 * B; o_fof = o_pos + 15 * (size_t)B;
-        n_geo = o_fof + (P ? (size_t)P : 0);
+        o_pos = (size_t)NI * 12; o_cen = o_pos + 3 * B; o_rot = o_pos + 6 * B; o_fof = o_pos + 15 * (size_t)B;
+        o_vb = o_fof;          // ragged plans (never multi): the B + 1 offsets behind the rotations
+        n_geo = o_fof + (P ? (size_t)P : 0) + (T ? (size_t)B + 1 : 0);
         void* g; PL_TRY(dev_alloc(n_geo * 4, &g)); geo_dev = (float*)g;
         PL_TRY(geo.alloc(n_geo * 4));
         void* c; PL_TRY(dev_alloc((size_t)B * V * V * V * 3 * 4, &c)); coords = (float*)c;
@@ -989,11 +998,14 @@ struct lt_plan {
         const float step = (float)(cfg.cuboid_side / (double)(V - 1));          // float(np.float32(side / (V - 1))): the fp64 quotient rounded once
         {
             const int dt = dtype, agg = cfg.aggregation, cmu = cfg.transfer_cmu_to_human36m ? 1 : 0, h = hm_h, w = hm_w;
-            const size_t op = o_pos, oc = o_cen, orr = o_rot, of = o_fof; lt_plan* self = this; const bool multi = P > 0;
+            const size_t op = o_pos, oc = o_cen, orr = o_rot, of = o_fof; lt_plan* self = this; const bool multi = P > 0; const int rT = T;
             const void* fp = feats.p; float* cp = coords; void* vp = vol.p; const float* confp = volc.null() ? nullptr : (const float*)volc.p;
             // the block's address is read when the op runs: a masked plan (lt_plan_set_view_mask, before the first forward) has moved it to a block with the mask behind
             ops.push_back([=](hipStream_t s) {
                 const float* gp = self->geo_dev;
+                if (rT)
+                    return lt_unproject_grid_ragged_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, (const int32_t*)(gp + of), vp, B, rT, NV, 32, h, w,
+                                                        V, agg, s);
                 if (multi)
                     return lt_unproject_grid_indexed_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, self->masked ? self->mask_dev : nullptr,
                                                          (const int32_t*)(gp + of), vp, F, B, NV, 32, h, w, V, agg, s);
@@ -1010,7 +1022,7 @@ struct lt_plan {
         PL_TRY(dev_alloc(wsb ? wsb : 16, &sa_ws));
         {   // tail op 1: the RETURNED features (B, NV, 32, h, w) fp32, skipped when the caller did not ask for them
             const int dt = dtype, h = hm_h, w = hm_w; const void* fp = feats.p; lt_plan* self = this;
-            ops.push_back([=](hipStream_t s) { return self->out_feats ? lt_nhwc_to_nchw_f32(dt, fp, self->out_feats, F * NV, 32, h * w, 32, s) : LT_OK; });
+            ops.push_back([=](hipStream_t s) { return self->out_feats ? lt_nhwc_to_nchw_f32(dt, fp, self->out_feats, NI, 32, h * w, 32, s) : LT_OK; });
         }
         {   // tail op 2: soft-argmax straight into the caller's tensors
             const float mult = (float)cfg.volume_multiplier; const int sm = cfg.volume_softmax ? 1 : 0, cl = logits.planar ? 0 : 1;
@@ -1032,7 +1044,7 @@ struct lt_plan {
     // every call because it reads the caller's proj and writes the caller's outputs: ALG lt_softargmax2d_fwd + lt_alg_tail_fwd, RANSAC lt_triangulate_ransac.
     int build_alg() {
         const lt_alg_plan_config& c = acfg;
-        const int B = c.B, NV = c.NV, N = B * NV, J = c.num_joints, Hh = c.H, W = c.W;
+        const int B = c.B, NV = c.NV, N = images(), J = c.num_joints, Hh = c.H, W = c.W;
         const bool ransac = c.model == LT_MODEL_RANSAC;
         Act f256, hm;
         PL_TRY(record_backbone(N, Hh, W, c.num_layers, c.style_caffe != 0, !ransac && c.use_confidences ? "backbone.alg_confidences" : nullptr, true, f256, algc, hm));
@@ -1067,7 +1079,14 @@ struct lt_plan {
         {   // tail op 2: confidences normalised over the views, keypoints to image pixels, the DLT (triangulation.py:166-193)
             const float sx = (float)((double)W / (double)w), sy = (float)((double)Hh / (double)h);          // torch.tensor([W / w, H / h], float32)
             const float* kh = kp_hm; const float* cp = algc.null() ? nullptr : (const float*)algc.p; const int ldc = algc.null() ? J : algc.c;
+            const int rT = T;
+            if (rT) {          // the offsets' device block and its pinned ring (stage_view_base)
+                PL_TRY(avb.alloc(((size_t)B + 1) * 4));
+                PL_TRY(dev_alloc(((size_t)B + 1) * 4, &q)); vb_dev = (int32_t*)q;
+            }
             ops.push_back([=](hipStream_t s) {
+                if (rT)
+                    return lt_alg_tail_ragged_fwd(kh, cp, ldc, self->cur_proj, sx, sy, self->vb_dev, (float*)self->out_kp2d, self->out_conf, self->out_kp, B, rT, NV, J, s);
                 if (self->aks_stats2d)
                     return lt_alg_tail_stats_fwd(kh, cp, ldc, self->cur_proj, sx, sy, self->masked ? self->mask_dev : nullptr, self->aks_stats2d, (float*)self->out_kp2d,
                                                  self->out_conf, self->out_kp, self->aks_cov2d, self->aks_reproj, self->aks_cov3d, B, NV, J, s);
@@ -1106,12 +1125,12 @@ struct lt_plan {
     // its block of this forward): K [R | t] at IMAGE resolution rounded to fp32, the algebraic stage's proj_matricies_batch.
     // cuboid_frame (multi plans, checked by the caller): the P frame indices behind the rotations; base_points_host and rot_host are per cuboid there.
     int stage_geometry(const double* K_host, const double* R_host, const double* t_host, const double* base_points_host, const double* rot_host, hipStream_t st,
-                       float* pi = nullptr, const int32_t* cuboid_frame = nullptr) {
-        const int B = cfg.B, NV = cfg.NV, NC = cuboids();
+                       float* pi = nullptr, const int32_t* cuboid_frame = nullptr, const int32_t* view_counts = nullptr) {
+        const int B = cfg.B, NV = cfg.NV, NC = cuboids(), NI = images();
         void* blk; PL_TRY(geo.acquire(&blk));
         float* gh = (float*)blk;
         const double sx = (double)hm_w / (double)cfg.W, sy = (double)hm_h / (double)cfg.H;
-        for (int i = 0; i < B * NV; ++i) {
+        for (int i = 0; i < NI; ++i) {
             double K[9];
             for (int k = 0; k < 9; ++k) K[k] = K_host[(size_t)i * 9 + k];
             const double* R = R_host + (size_t)i * 9; const double* t = t_host + (size_t)i * 3;
@@ -1139,6 +1158,11 @@ struct lt_plan {
             for (int k = 0; k < 9; ++k) gh[o_rot + 9 * b + k] = rot_host ? (float)rot_host[9 * b + k] : ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f);
         }
         if (cuboid_frame) memcpy(gh + o_fof, cuboid_frame, (size_t)NC * 4);
+        if (view_counts) {          // ragged plans (counts checked by the caller): the exclusive prefix sum, B + 1 int32
+            int32_t* vb = (int32_t*)(gh + o_vb);
+            vb[0] = 0;
+            for (int b = 0; b < B; ++b) vb[b + 1] = vb[b] + view_counts[b];
+        }
         if (masked) memcpy((uint8_t*)(gh + o_mask), mask_cur.data(), (size_t)B * NV);          // rides in the same block: one copy
         PL_HIP(hipMemcpyAsync(geo_dev, gh, n_geo * 4, hipMemcpyHostToDevice, st));
         return geo.commit(st);
@@ -1176,6 +1200,15 @@ struct lt_plan {
         PL_TRY(amask.alloc(n));
         void* q; PL_TRY(dev_alloc(n, &q)); amask_dev = (uint8_t*)q; mask_dev = amask_dev;
         return LT_OK;
+    }
+    // ragged algebraic plans, per forward: the offsets of the counts (checked by the caller) to the device through their ring
+    int stage_view_base(const int32_t* view_counts, hipStream_t st) {
+        void* blk; PL_TRY(avb.acquire(&blk));
+        int32_t* vb = (int32_t*)blk;
+        vb[0] = 0;
+        for (int b = 0; b < cfg.B; ++b) vb[b + 1] = vb[b] + view_counts[b];
+        PL_HIP(hipMemcpyAsync(vb_dev, vb, ((size_t)cfg.B + 1) * 4, hipMemcpyHostToDevice, st));
+        return avb.commit(st);
     }
     // algebraic plans, per forward: a changed mask to the device through the ring
     int stage_alg_mask(hipStream_t st) {
@@ -1250,9 +1283,9 @@ int check_alg_config(const lt_alg_plan_config& c, const char* who) {
 }
 
 // a checked configuration + a state dict -> a recorded plan
-int make_vol_plan(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, const char* who, lt_plan** plan_out, int P = 0) {
+int make_vol_plan(const lt_vol_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, const char* who, lt_plan** plan_out, int P = 0, int T = 0) {
     lt_plan* p = new lt_plan();
-    p->who = who; p->P = P;
+    p->who = who; p->P = P; p->T = T;
     p->cfg = *cfg;
     p->dtype = cfg->dtype; p->es = cfg->dtype == LT_F32 ? 4 : 2;
     if (!load_state_dict(p, weights, nweights)) { delete p; return LT_ERR_INVALID; }
@@ -1272,10 +1305,10 @@ int check_alg_heads(const lt_alg_plan_config& c, const lt_named_tensor* weights,
     for (const std::string& k : heads) LT_REQUIRE(probe.has(k), LT_ERR_INVALID, "%s: state dict has no '%s'", who, k.c_str());
     return LT_OK;
 }
-int make_alg_plan(const lt_alg_plan_config& c, const lt_named_tensor* weights, int32_t nweights, const char* who, lt_plan** plan_out) {
+int make_alg_plan(const lt_alg_plan_config& c, const lt_named_tensor* weights, int32_t nweights, const char* who, lt_plan** plan_out, int T = 0) {
     PL_TRY(check_alg_heads(c, weights, nweights, who));
     lt_plan* p = new lt_plan();
-    p->who = who;
+    p->who = who; p->T = T;
     p->model = c.model; p->acfg = c;
     memset(&p->cfg, 0, sizeof(p->cfg));
     p->cfg.dtype = c.dtype; p->cfg.num_layers = c.num_layers; p->cfg.style_caffe = c.style_caffe; p->cfg.num_joints = c.num_joints;
@@ -1289,6 +1322,7 @@ int make_alg_plan(const lt_alg_plan_config& c, const lt_named_tensor* weights, i
     return LT_OK;
 }
 const char* plan_kind_name(const lt_plan* p) {
+    if (p->T) return p->model == 0 ? "a ragged volumetric plan of lt_plan_create_vol_ragged" : "a ragged algebraic plan of lt_plan_create_alg_ragged";
     return p->model == 0 ? (p->P ? "a multi-cuboid plan of lt_plan_create_vol_multi" : "a volumetric plan of lt_plan_create_vol") : p->model == MODEL_CASCADE ? "a cascade plan of lt_plan_create_cascade"
            : p->model == LT_MODEL_RANSAC ? "an LT_MODEL_RANSAC plan of lt_plan_create_alg" : "an LT_MODEL_ALG plan of lt_plan_create_alg";
 }
@@ -1298,19 +1332,19 @@ namespace {
 // the checked forward of a volumetric plan; cuboid_frame: the multi plans' assignment (base_points_host and rot_host per cuboid there), else null
 int forward_vol_any(lt_plan* p, const char* who, const float* images, const double* K_host, const double* R_host, const double* t_host, const int32_t* cuboid_frame,
                     const double* base_points_host, const double* rot_host, float* keypoints_3d, float* volumes, float* features, float* coord_volumes,
-                    float* vol_confidences, void* stream) {
+                    float* vol_confidences, void* stream, const int32_t* view_counts = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     bool detour;
     PL_TRY(p->enter(st, detour));
-    const int B = p->cfg.B, NV = p->cfg.NV, V = p->cfg.volume_size;
+    const int V = p->cfg.volume_size;
     p->ran = true;
-    PL_TRY(p->stage_geometry(K_host, R_host, t_host, base_points_host, rot_host, st, nullptr, cuboid_frame));
+    PL_TRY(p->stage_geometry(K_host, R_host, t_host, base_points_host, rot_host, st, nullptr, cuboid_frame, view_counts));
     p->cur_images = images; p->out_kp = keypoints_3d; p->out_probs = volumes; p->out_feats = features;
     PL_TRY(p->run(st));
     if (coord_volumes) PL_HIP(hipMemcpyAsync(coord_volumes, p->coords, (size_t)p->cuboids() * V * V * V * 3 * 4, hipMemcpyDeviceToDevice, st));
     if (vol_confidences) {
         LT_REQUIRE(!p->volc.null(), LT_ERR_INVALID, "%s: vol_confidences asked of a plan without the confidence head (aggregation %d)", who, p->cfg.aggregation);
-        PL_HIP(hipMemcpyAsync(vol_confidences, p->volc.p, (size_t)B * NV * 32 * 4, hipMemcpyDeviceToDevice, st));          // RAW sigmoid outputs; 'conf_norm' divides by their sum over views
+        PL_HIP(hipMemcpyAsync(vol_confidences, p->volc.p, (size_t)p->images() * 32 * 4, hipMemcpyDeviceToDevice, st));          // RAW sigmoid outputs; 'conf_norm' divides by their sum over views
     }
     PL_TRY(p->leave(st, detour));
     return LT_OK;
@@ -1331,6 +1365,7 @@ extern "C" int lt_plan_forward_vol(lt_plan* p, const float* images, const double
     LT_REQUIRE(p->model == 0, LT_ERR_INVALID, "lt_plan_forward_vol: the plan is %s; run it with %s", plan_kind_name(p),
                p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_alg");
     LT_REQUIRE(!p->P, LT_ERR_INVALID, "lt_plan_forward_vol: the plan is %s; run it with lt_plan_forward_vol_multi", plan_kind_name(p));
+    LT_REQUIRE(!p->T, LT_ERR_INVALID, "lt_plan_forward_vol: the plan is %s; run it with lt_plan_forward_vol_ragged", plan_kind_name(p));
     LT_REQUIRE(images && K_host && R_host && t_host && base_points_host && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_vol: null argument");
     return forward_vol_any(p, "lt_plan_forward_vol", images, K_host, R_host, t_host, nullptr, base_points_host, rot_host, keypoints_3d, volumes, features,
                            coord_volumes, vol_confidences, stream);
@@ -1351,7 +1386,7 @@ extern "C" int lt_plan_forward_vol_multi(lt_plan* p, const float* images, const 
     const char* who = "lt_plan_forward_vol_multi";
     LT_REQUIRE(p, LT_ERR_INVALID, "%s: null argument", who);
     LT_REQUIRE(p->model == 0 && p->P, LT_ERR_INVALID, "%s: the plan is %s; run it with %s", who, plan_kind_name(p),
-               p->model == 0 ? "lt_plan_forward_vol" : p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_alg");
+               p->model == 0 ? (p->T ? "lt_plan_forward_vol_ragged" : "lt_plan_forward_vol") : p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_alg");
     LT_REQUIRE(images && K_host && R_host && t_host && cuboid_frame_host && base_points_host && keypoints_3d, LT_ERR_INVALID,
                "%s: null argument (images, K, R, t, cuboid_frame, base_points and keypoints_3d are required)", who);
     for (int i = 0; i < p->P; ++i)
@@ -1359,6 +1394,81 @@ extern "C" int lt_plan_forward_vol_multi(lt_plan* p, const float* images, const 
                    cuboid_frame_host[i], p->cfg.B - 1);
     return forward_vol_any(p, who, images, K_host, R_host, t_host, cuboid_frame_host, base_points_host, rot_host, keypoints_3d, volumes, features, coord_volumes,
                            vol_confidences, stream);
+}
+
+namespace {
+// the counts of a ragged forward against the plan: each in [min_views, NVcap], summing to T; the message names the first bad sample
+int check_view_counts(const lt_plan* p, const char* who, const int32_t* view_counts, int min_views) {
+    long long sum = 0;
+    for (int b = 0; b < p->cfg.B; ++b) {
+        LT_REQUIRE(view_counts[b] >= min_views && view_counts[b] <= p->cfg.NV, LT_ERR_INVALID, "%s: sample %d has %d view%s, the plan takes %d to %d (NVcap)", who, b,
+                   view_counts[b], view_counts[b] == 1 ? "" : "s", min_views, p->cfg.NV);
+        sum += view_counts[b];
+    }
+    LT_REQUIRE(sum == p->T, LT_ERR_INVALID, "%s: view_counts sums to %lld views over %d samples, the plan holds %d images", who, sum, p->cfg.B, p->T);
+    return LT_OK;
+}
+// T images over B samples of at most NVcap (and at least min_views) views each
+int check_ragged_shape(const char* who, int B, int NVcap, int T, int min_views) {
+    LT_REQUIRE(NVcap >= 1 && NVcap <= 32, LT_ERR_INVALID, "%s: NV %d (NVcap of a ragged plan: 1 .. 32)", who, NVcap);
+    LT_REQUIRE(T >= 1 && (long long)T >= (long long)min_views * B && (long long)T <= (long long)B * NVcap, LT_ERR_INVALID,
+               "%s: T %d images over B %d samples of %d to %d views", who, T, B, min_views, NVcap);
+    return LT_OK;
+}
+}  // namespace
+
+extern "C" int lt_plan_create_vol_ragged(const lt_vol_plan_config* cfg, int32_t T, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
+    const char* who = "lt_plan_create_vol_ragged";
+    LT_REQUIRE(cfg && weights && plan_out && nweights > 0, LT_ERR_INVALID, "%s: null argument", who);
+    PL_TRY(check_vol_config(cfg, who));
+    PL_TRY(check_ragged_shape(who, cfg->B, cfg->NV, T, 1));
+    *plan_out = nullptr;
+    return make_vol_plan(cfg, weights, nweights, who, plan_out, 0, T);
+}
+
+extern "C" int lt_plan_forward_vol_ragged(lt_plan* p, const float* images, const double* K_host, const double* R_host, const double* t_host,
+                                          const int32_t* view_counts_host, const double* base_points_host, const double* rot_host, float* keypoints_3d,
+                                          float* volumes, float* features, float* coord_volumes, float* vol_confidences, void* stream) {
+    const char* who = "lt_plan_forward_vol_ragged";
+    LT_REQUIRE(p, LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(p->model == 0 && p->T, LT_ERR_INVALID, "%s: the plan is %s; run it with %s", who, plan_kind_name(p),
+               p->model == 0 ? (p->P ? "lt_plan_forward_vol_multi" : "lt_plan_forward_vol") : p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_alg");
+    LT_REQUIRE(images && K_host && R_host && t_host && view_counts_host && base_points_host && keypoints_3d, LT_ERR_INVALID,
+               "%s: null argument (images, K, R, t, view_counts, base_points and keypoints_3d are required)", who);
+    PL_TRY(check_view_counts(p, who, view_counts_host, 1));
+    return forward_vol_any(p, who, images, K_host, R_host, t_host, nullptr, base_points_host, rot_host, keypoints_3d, volumes, features, coord_volumes,
+                           vol_confidences, stream, view_counts_host);
+}
+
+extern "C" int lt_plan_create_alg_ragged(const lt_alg_plan_config* cfg, int32_t T, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
+    const char* who = "lt_plan_create_alg_ragged";
+    LT_REQUIRE(cfg && weights && plan_out && nweights > 0, LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(cfg->model == LT_MODEL_ALG, LT_ERR_INVALID, "%s: model %d (LT_MODEL_ALG only: RANSAC has no ragged plan)", who, cfg->model);
+    PL_TRY(check_alg_config(*cfg, who));
+    PL_TRY(check_ragged_shape(who, cfg->B, cfg->NV, T, 2));
+    *plan_out = nullptr;
+    return make_alg_plan(*cfg, weights, nweights, who, plan_out, T);
+}
+
+extern "C" int lt_plan_forward_alg_ragged(lt_plan* p, const float* images, const float* proj, const int32_t* view_counts_host, float* keypoints_3d,
+                                          void* keypoints_2d, float* heatmaps, float* confidences, void* stream) {
+    const char* who = "lt_plan_forward_alg_ragged";
+    LT_REQUIRE(p, LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(p->model == LT_MODEL_ALG && p->T, LT_ERR_INVALID, "%s: the plan is %s; run it with %s", who, plan_kind_name(p),
+               p->model == 0 ? (p->T ? "lt_plan_forward_vol_ragged" : p->P ? "lt_plan_forward_vol_multi" : "lt_plan_forward_vol")
+                             : p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_alg");
+    LT_REQUIRE(images && proj && view_counts_host && keypoints_3d, LT_ERR_INVALID, "%s: null argument (images, proj, view_counts and keypoints_3d are required)", who);
+    PL_TRY(check_view_counts(p, who, view_counts_host, 2));
+    hipStream_t st = (hipStream_t)stream;
+    bool detour;
+    PL_TRY(p->enter(st, detour));
+    p->ran = true;
+    PL_TRY(p->stage_view_base(view_counts_host, st));
+    p->cur_images = images; p->cur_proj = proj; p->out_kp = keypoints_3d;
+    p->out_kp2d = keypoints_2d; p->out_hm = heatmaps; p->out_conf = confidences;
+    PL_TRY(p->run(st));
+    PL_TRY(p->leave(st, detour));
+    return LT_OK;
 }
 
 extern "C" int lt_plan_create_alg(const lt_alg_plan_config* cfg, const lt_named_tensor* weights, int32_t nweights, lt_plan** plan_out) {
@@ -1373,6 +1483,7 @@ extern "C" int lt_plan_forward_alg(lt_plan* p, const float* images, const float*
     LT_REQUIRE(p, LT_ERR_INVALID, "lt_plan_forward_alg: null argument");
     LT_REQUIRE(p->model == LT_MODEL_ALG || p->model == LT_MODEL_RANSAC, LT_ERR_INVALID, "lt_plan_forward_alg: the plan is %s; run it with %s", plan_kind_name(p),
                p->model == MODEL_CASCADE ? "lt_plan_forward_cascade" : "lt_plan_forward_vol");
+    LT_REQUIRE(!p->T, LT_ERR_INVALID, "lt_plan_forward_alg: the plan is %s; run it with lt_plan_forward_alg_ragged", plan_kind_name(p));
     LT_REQUIRE(images && proj && keypoints_3d, LT_ERR_INVALID, "lt_plan_forward_alg: null argument (images, proj and keypoints_3d are required)");
     hipStream_t st = (hipStream_t)stream;
     bool detour;
@@ -1469,6 +1580,7 @@ extern "C" int lt_plan_forward_cascade(lt_plan* p, const float* images, const do
 extern "C" int lt_plan_set_view_mask(lt_plan* p, const uint8_t* mask_host) {
     const char* who = "lt_plan_set_view_mask";
     LT_REQUIRE(p, LT_ERR_INVALID, "%s: null plan", who);
+    LT_REQUIRE(!p->T, LT_ERR_INVALID, "%s: the plan is %s; a ragged plan takes no view mask (drop the view from the batch instead)", who, plan_kind_name(p));
     LT_REQUIRE(p->model != LT_MODEL_RANSAC, LT_ERR_UNSUPPORTED, "%s: the plan is %s; RANSAC takes no view mask (its inlier search drops views per joint)", who,
                plan_kind_name(p));
     const int B = p->cfg.B, NV = p->cfg.NV;
@@ -1521,6 +1633,8 @@ extern "C" int lt_plan_set_alg_keypoint_stats(lt_plan* p, float* stats2d_dev, in
     LT_REQUIRE(p, LT_ERR_INVALID, "%s: null plan", who);
     LT_REQUIRE(p->model == LT_MODEL_ALG || p->model == MODEL_CASCADE, LT_ERR_UNSUPPORTED, "%s: the plan is %s; the statistics are those of the algebraic joints", who,
                plan_kind_name(p));
+    LT_REQUIRE(!p->T, LT_ERR_UNSUPPORTED, "%s: the plan is %s; there is no ragged statistics tail (pad the batch and use lt_plan_set_view_mask on a plan of "
+               "lt_plan_create_alg)", who, plan_kind_name(p));
     const int n = (stats2d_dev != nullptr) + (peak_index_dev != nullptr) + (cov2d_img_dev != nullptr) + (reproj_err_dev != nullptr) + (cov3d_dev != nullptr);
     LT_REQUIRE(n == 0 || n == 5, LT_ERR_INVALID,
                "%s: stats2d_dev, peak_index_dev, cov2d_img_dev, reproj_err_dev and cov3d_dev come together (all NULL: the plain tail); %d of 5 given", who, n);

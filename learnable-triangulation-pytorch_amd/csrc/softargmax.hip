@@ -804,26 +804,37 @@ struct AlgTailStats {
 // STATS (alg_tail_stats_kernel, lt_alg_tail_stats_fwd): the same loops, which also write every view's 2D covariance in image pixels (S Sigma_hm S in
 // fp64, rounded once), then dlt_stats_finish in dlt_solve's place.  Sigma_v in the propagation is that ROUNDED value read back, like the joint in the
 // reprojection error: both statistics can be reproduced from the outputs alone.
-template <bool MASKED, bool STATS>
+// RAGGED (alg_tail_ragged_kernel, lt_alg_tail_ragged_fwd): the unmasked tail over the rows view_base[b] .. view_base[b + 1] of sample b -- kp_hm, conf_raw,
+// proj, kp2d and conf_out are (T, ...) over all views, sample-major; NV is NVcap.  The count is clamped into [0, min(NVcap, T)] and the first row into
+// [0, T - count] (the hosts refuse such tables before launching; the second line of defence); fewer than two views: NaN joints.
+template <bool MASKED, bool STATS, bool RAGGED = false>
 __device__ __forceinline__ void alg_tail_body(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
                                               float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
-                                              float* __restrict__ kp3d, int B, int NV, int J, const AlgTailStats& so) {
+                                              float* __restrict__ kp3d, int B, int NV, int J, const AlgTailStats& so, const int32_t* __restrict__ view_base = nullptr,
+                                              int T = 0) {
+    static_assert(!RAGGED || (!MASKED && !STATS), "the ragged tail is the plain tail over a sample's rows");
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= B * J) return;
     const int b = g / J, j = g - b * J;
     const uint8_t* mk = MASKED ? mask + (long long)b * NV : nullptr;
+    long long r0 = (long long)b * NV;   // the row of the sample's first view
+    if constexpr (RAGGED) {
+        const int lo = view_base[b], nb = min(max(view_base[b + 1] - lo, 0), min(NV, T));
+        r0 = min(max(lo, 0), T - nb);
+        NV = nb;
+    }
     float part[4] = {0.f, 0.f, 0.f, 0.f};
     int nvalid = 0;
     for (int v = 0; v < NV; ++v) {
         if (MASKED && !mk[v]) continue;
-        const float c = conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f;
+        const float c = conf_raw ? conf_raw[(r0 + v) * ld_conf + j] : 1.f;
         part[nvalid & 3] = __fadd_rn(part[nvalid & 3], c);
         ++nvalid;
     }
     const float sum = __fadd_rn(__fadd_rn(__fadd_rn(part[0], part[1]), part[2]), part[3]);
     double R[4][4] = {};  // R of A = QR, grown one (valid) view at a time
     for (int v = 0; v < NV; ++v) {
-        const long long i = ((long long)b * NV + v) * J + j;
+        const long long i = (r0 + v) * J + j;
         const float x = __fmul_rn(kp_hm[i * 2], sx), y = __fmul_rn(kp_hm[i * 2 + 1], sy);
         if (kp2d) { kp2d[i * 2] = x; kp2d[i * 2 + 1] = y; }
         if (STATS) {
@@ -836,29 +847,29 @@ __device__ __forceinline__ void alg_tail_body(const float* __restrict__ kp_hm, c
             if (conf_out) conf_out[i] = 0.f;
             continue;
         }
-        const float c = __fadd_rn(__fdiv_rn(conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f, sum), 1e-5f);
+        const float c = __fadd_rn(__fdiv_rn(conf_raw ? conf_raw[(r0 + v) * ld_conf + j] : 1.f, sum), 1e-5f);
         if (conf_out) conf_out[i] = c;
-        dlt_add_view(R, proj + ((long long)b * NV + v) * 12, (double)x, (double)y, (double)c);
+        dlt_add_view(R, proj + (r0 + v) * 12, (double)x, (double)y, (double)c);
     }
     float* o = kp3d + (long long)g * 3;
     if (STATS) {
-        const long long i0 = (long long)b * NV * J + j;
+        const long long i0 = r0 * J + j;
         // a view's values again, by the expressions of the loop above (each one IEEE rounding, so the same bits)
         auto view = [&](const int v, double& x, double& y, double& c, double (&s)[3]) -> bool {
             if (MASKED && !mk[v]) return false;
             const long long i = i0 + (long long)v * J;
             x = (double)__fmul_rn(kp_hm[i * 2], sx); y = (double)__fmul_rn(kp_hm[i * 2 + 1], sy);
-            c = (double)__fadd_rn(__fdiv_rn(conf_raw ? conf_raw[((long long)b * NV + v) * ld_conf + j] : 1.f, sum), 1e-5f);
+            c = (double)__fadd_rn(__fdiv_rn(conf_raw ? conf_raw[(r0 + v) * ld_conf + j] : 1.f, sum), 1e-5f);
             const float* s2 = so.stats2d + i * 5;
             s[0] = (double)(float)((double)sx * (double)sx * (double)s2[2]);
             s[1] = (double)(float)((double)sx * (double)sy * (double)s2[3]);
             s[2] = (double)(float)((double)sy * (double)sy * (double)s2[4]);
             return true;
         };
-        dlt_stats_finish(R, !(MASKED && nvalid < 2), proj + (long long)b * NV * 12, NV, J, view, o, so.reproj + i0, so.cov3d + (long long)g * 6);
+        dlt_stats_finish(R, !(MASKED && nvalid < 2), proj + r0 * 12, NV, J, view, o, so.reproj + i0, so.cov3d + (long long)g * 6);
         return;
     }
-    if (MASKED && nvalid < 2) { o[0] = o[1] = o[2] = __int_as_float(0x7fc00000); return; }
+    if ((MASKED || RAGGED) && nvalid < 2) { o[0] = o[1] = o[2] = __int_as_float(0x7fc00000); return; }
     dlt_solve(R, o);
 }
 
@@ -868,6 +879,12 @@ __global__ void alg_tail_kernel(const float* __restrict__ kp_hm, const float* __
                                 float sx, float sy, const uint8_t* __restrict__ mask, float* __restrict__ kp2d, float* __restrict__ conf_out,
                                 float* __restrict__ kp3d, int B, int NV, int J) {
     alg_tail_body<MASKED, false>(kp_hm, conf_raw, ld_conf, proj, sx, sy, mask, kp2d, conf_out, kp3d, B, NV, J, AlgTailStats());
+}
+
+__global__ void alg_tail_ragged_kernel(const float* __restrict__ kp_hm, const float* __restrict__ conf_raw, int ld_conf, const float* __restrict__ proj,
+                                       float sx, float sy, const int32_t* __restrict__ view_base, float* __restrict__ kp2d, float* __restrict__ conf_out,
+                                       float* __restrict__ kp3d, int B, int T, int NVcap, int J) {
+    alg_tail_body<false, false, true>(kp_hm, conf_raw, ld_conf, proj, sx, sy, nullptr, kp2d, conf_out, kp3d, B, NVcap, J, AlgTailStats(), view_base, T);
 }
 
 template <bool MASKED>
@@ -1190,4 +1207,20 @@ extern "C" int lt_alg_tail_masked_fwd(const float* keypoints_hm, const float* co
                                       int32_t J, void* stream) {
     return alg_tail_launch<true, false>("lt_alg_tail_masked_fwd", keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y, view_mask, keypoints_2d, confidences,
                                  keypoints_3d, B, NV, J, stream);
+}
+
+extern "C" int lt_alg_tail_ragged_fwd(const float* keypoints_hm, const float* conf_raw, int32_t ld_conf, const float* proj, float scale_x, float scale_y,
+                                      const int32_t* view_base, float* keypoints_2d, float* confidences, float* keypoints_3d, int32_t B, int32_t T,
+                                      int32_t NVcap, int32_t J, void* stream) {
+    const char* name = "lt_alg_tail_ragged_fwd";
+    LT_REQUIRE(keypoints_hm && proj && keypoints_3d, LT_ERR_INVALID, "%s: null argument", name);
+    LT_REQUIRE(view_base, LT_ERR_INVALID, "%s: null view_base", name);
+    LT_REQUIRE(B >= 1 && T >= 1 && J >= 1, LT_ERR_INVALID, "%s: bad shape (B %d, T %d, J %d)", name, B, T, J);
+    LT_REQUIRE(NVcap >= 1 && NVcap <= 32, LT_ERR_INVALID, "%s: NVcap %d (1..32)", name, NVcap);
+    LT_REQUIRE((long long)B * J < (1ll << 31), LT_ERR_INVALID, "%s: B %d x J %d", name, B, J);
+    LT_REQUIRE(!conf_raw || ld_conf >= J, LT_ERR_INVALID, "%s: ld_conf %d < J %d", name, ld_conf, J);
+    hipLaunchKernelGGL(alg_tail_ragged_kernel, dim3((B * J + 63) / 64), dim3(64), 0, (hipStream_t)stream, keypoints_hm, conf_raw, ld_conf, proj, scale_x, scale_y,
+                       view_base, keypoints_2d, confidences, keypoints_3d, B, T, NVcap, J);
+    LT_CHECK_LAUNCH(name);
+    return LT_OK;
 }

@@ -82,8 +82,15 @@ struct UnprojIndexedArgs : UnprojMaskedArgs {
     const int32_t* frame_of;  // (B) the frame of every cuboid
     int F;                    // frames
 };
-template <bool MASKED, bool INDEXED = false>
-using UnprojArgsOf = std::conditional_t<INDEXED, UnprojIndexedArgs, std::conditional_t<MASKED, UnprojMaskedArgs, UnprojArgs>>;
+// the ragged entries' kernels (samples with different view counts): feats, proj and conf are (T, ...) over all views, sample-major; sample b's NV is
+// view_base[b + 1] - view_base[b] <= the NV of the arguments (NVcap) and its rows start at view_base[b].  Built on the masked form: the valid views are
+// the prefix.  It is also the host's whole argument record (mask, frame_of and view_base are exclusive), which every kernel gets its base of.
+struct UnprojRaggedArgs : UnprojIndexedArgs {
+    const int32_t* view_base;  // (B + 1) exclusive prefix sum of the view counts
+    int T;                     // rows of feats, proj and conf
+};
+template <bool MASKED, bool INDEXED = false, bool RAGGED = false>
+using UnprojArgsOf = std::conditional_t<RAGGED, UnprojRaggedArgs, std::conditional_t<INDEXED, UnprojIndexedArgs, std::conditional_t<MASKED, UnprojMaskedArgs, UnprojArgs>>>;
 
 // Brick (bi, bj, bk) of chunk c of a sample.  Raster order (k fastest) makes every 4-voxel i-slab of bricks sweep the WHOLE projected cube in every view:
 // at 8 views the per-slab working set (2.7 MB of feature rows) plus the output stream does not fit the 4 MB L2 of the XCD the sample is pinned to, and the
@@ -149,6 +156,15 @@ __device__ __forceinline__ bool cuboid_chunk_of(const UnprojIndexedArgs& a, int&
     return false;
 }
 
+// The views of sample b of the ragged kernels: its first row and its count, uniform over the workgroup, so both are scalar.  The count is clamped into
+// [0, min(NVcap, T)] and the row into [0, T - count]: no table value can send a load outside the T rows -- the hosts refuse such a table before any launch,
+// this is the second line of defence, as frame_of_cuboid is.
+__device__ __forceinline__ void views_of_sample(const UnprojRaggedArgs& a, int b, int cap, int& row, int& nb) {
+    const int lo = __builtin_amdgcn_readfirstlane(a.view_base[b]), hi = __builtin_amdgcn_readfirstlane(a.view_base[b + 1]);
+    nb = min(max(hi - lo, 0), min(cap, a.T));
+    row = min(max(lo, 0), a.T - nb);
+}
+
 // Bilinear sample of CH channels for one voxel in one view (project_taps' geometry): only the corners inside the map are loaded, and
 // blended with the raw weights -- the first of the two load disciplines of unproj_geom.h.
 template <typename T, int CH>
@@ -183,10 +199,14 @@ __device__ __forceinline__ bool view_on(unsigned mbits, const uint8_t* __restric
 // MASKED: the views {v : mask[b][v]} of sample b alone, visited in increasing v -- exactly the unmasked arithmetic on the compacted views (a
 // masked view is never sampled; no valid view at all: zeros).  The mask of a sample is uniform over its workgroups: SMALL_NV keeps it as bits.
 // INDEXED (on the masked form): sample b is cuboid b, which reads the maps, projections, confidences and mask of its frame f = frame_of[b].
-template <typename T, int CH, bool SMALL_NV, bool MASKED = false, bool INDEXED = false>
-__global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKED, INDEXED> a) {
+// RAGGED (on the masked form): sample b's views are the rows view_base[b] + v, v < n_b, of feats, proj and conf; its mask is the prefix of n_b bits (kept
+// as bits whatever NV is: NVcap <= 32), n_b = 0: zeros.
+template <typename T, int CH, bool SMALL_NV, bool MASKED = false, bool INDEXED = false, bool RAGGED = false>
+__global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKED, INDEXED, RAGGED> a) {
     static_assert(MASKED || !INDEXED, "the indexed kernels are built on the masked form");
+    static_assert(!RAGGED || (MASKED && !INDEXED), "the ragged kernels are built on the masked form");
     constexpr bool FAST = sizeof(T) == 2;
+    constexpr bool BITS = SMALL_NV || RAGGED;
     const int tpv = a.C / CH;  // lanes per voxel
     int b, chunk, f;           // f: the sample whose views are read
     if constexpr (INDEXED) {
@@ -196,15 +216,24 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
         f = b;
     }
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
-    const T* feats = (const T*)a.feats + (long long)f * a.NV * a.h * a.w * a.C;
-    const float* P = a.proj + (long long)f * a.NV * 12;
+    long long vrow;            // the row of the sample's first view
+    unsigned mbits = ~0u;
+    if constexpr (RAGGED) {
+        int row, nb;
+        views_of_sample(a, b, a.NV, row, nb);
+        vrow = row;
+        mbits = nb >= 32 ? ~0u : (1u << nb) - 1u;
+    } else {
+        vrow = (long long)f * a.NV;
+    }
+    const T* feats = (const T*)a.feats + vrow * a.h * a.w * a.C;
+    const float* P = a.proj + vrow * 12;
     const float* coords = a.coords + (long long)b * nvox * 3;
     T* out = (T*)a.out + (long long)b * nvox * a.C;
     int bi = 0, bj = 0, bk = 0;
     if (a.bricked) brick_of(a, chunk, bi, bj, bk);
     const uint8_t* mk = nullptr;
-    unsigned mbits = ~0u;
-    if constexpr (MASKED) {
+    if constexpr (MASKED && !RAGGED) {
         mk = a.mask + (long long)f * a.NV;
         if constexpr (INDEXED) if (!a.mask) mk = nullptr;
         if (SMALL_NV && (!INDEXED || mk)) {
@@ -226,7 +255,7 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
             float vals[8][CH];
 #pragma unroll
             for (int v = 0; v < 8; ++v)
-                if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, vals[v]);
+                if (v < a.NV && view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, vals[v]);
 #pragma unroll
             for (int e = 0; e < CH; ++e) {
                 float r;
@@ -236,7 +265,7 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
                         bool have = false;
                         m = 0.f;
 #pragma unroll
-                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) { m = have ? fmaxf(m, vals[v][e]) : vals[v][e]; have = true; }
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) { m = have ? fmaxf(m, vals[v][e]) : vals[v][e]; have = true; }
                     } else {
                         m = vals[0][e];
 #pragma unroll
@@ -245,14 +274,14 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
                     // sum_v x_v softmax_v(x) = (sum_v x_v e_v) / (sum_v e_v): one division per channel
                     float s = 0.f, tt = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) { const float ex = exp_<FAST>(vals[v][e] - m); s += ex; tt += vals[v][e] * ex; }
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) { const float ex = exp_<FAST>(vals[v][e] - m); s += ex; tt += vals[v][e] * ex; }
                     r = div_<FAST>(tt, s);
                 } else if (a.agg == LT_AGG_MAX) {
                     if constexpr (MASKED) {
                         bool have = false;
                         r = 0.f;
 #pragma unroll
-                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) { r = have ? fmaxf(r, vals[v][e]) : vals[v][e]; have = true; }
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) { r = have ? fmaxf(r, vals[v][e]) : vals[v][e]; have = true; }
                     } else {
                         r = vals[0][e];
 #pragma unroll
@@ -263,15 +292,15 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
                     if (a.agg == LT_AGG_CONF_NORM) {
                         cs = 0.f;
 #pragma unroll
-                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) cs += a.conf[((long long)f * a.NV + v) * a.C + c0 + e];
+                        for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) cs += a.conf[(vrow + v) * a.C + c0 + e];
                     }
                     r = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) r += vals[v][e] * __fdiv_rn(a.conf[((long long)f * a.NV + v) * a.C + c0 + e], cs);
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) r += vals[v][e] * __fdiv_rn(a.conf[(vrow + v) * a.C + c0 + e], cs);
                 } else {
                     r = 0.f;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) r += vals[v][e];
+                    for (int v = 0; v < 8; ++v) if (v < a.NV && view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) r += vals[v][e];
                 }
                 if constexpr (MASKED) if (mbits == 0) r = 0.f;   // no valid view
                 res[e] = r;
@@ -283,28 +312,28 @@ __global__ __launch_bounds__(256) void unproject_kernel(const UnprojArgsOf<MASKE
                 m[e] = -INFINITY; s[e] = 0.f; acc[e] = 0.f; cs[e] = 1.f;
                 if (a.agg == LT_AGG_CONF_NORM) {
                     cs[e] = 0.f;
-                    for (int v = 0; v < a.NV; ++v) if (view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) cs[e] += a.conf[((long long)f * a.NV + v) * a.C + c0 + e];
+                    for (int v = 0; v < a.NV; ++v) if (view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) cs[e] += a.conf[(vrow + v) * a.C + c0 + e];
                 }
             }
             bool any = !MASKED;
             if constexpr (MASKED)
-                for (int v = 0; v < a.NV; ++v) any = any || view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v);
+                for (int v = 0; v < a.NV; ++v) any = any || view_on<MASKED, BITS, INDEXED>(mbits, mk, v);
             if (a.agg == LT_AGG_SOFTMAX || a.agg == LT_AGG_MAX)
                 for (int v = 0; v < a.NV; ++v) {
-                    if (!view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) continue;
+                    if (!view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) continue;
                     sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, val);
 #pragma unroll
                     for (int e = 0; e < CH; ++e) m[e] = fmaxf(m[e], val[e]);
                 }
             if (a.agg != LT_AGG_MAX)
                 for (int v = 0; v < a.NV; ++v) {
-                    if (!view_on<MASKED, SMALL_NV, INDEXED>(mbits, mk, v)) continue;
+                    if (!view_on<MASKED, BITS, INDEXED>(mbits, mk, v)) continue;
                     sample_view<T, CH>(feats + (long long)v * a.h * a.w * a.C, P + v * 12, X0, X1, X2, a.h, a.w, a.C, c0, val);
 #pragma unroll
                     for (int e = 0; e < CH; ++e) {
                         if (a.agg == LT_AGG_SOFTMAX) { const float ex = exp_<FAST>(val[e] - m[e]); s[e] += ex; acc[e] += val[e] * ex; }
                         else if (a.agg == LT_AGG_CONF || a.agg == LT_AGG_CONF_NORM)
-                            acc[e] += val[e] * __fdiv_rn(a.conf[((long long)f * a.NV + v) * a.C + c0 + e], cs[e]);
+                            acc[e] += val[e] * __fdiv_rn(a.conf[(vrow + v) * a.C + c0 + e], cs[e]);
                         else acc[e] += val[e];
                     }
                 }
@@ -351,9 +380,13 @@ __device__ __forceinline__ f32x2_t pk_fma(f32x2_t a, f32x2_t b, f32x2_t c) { ret
 // the same value unless EVERY valid view's sample is NaN, and then both write NaN).  (The lanes still project into their masked views: which
 // lane owns a view varies over the quad, and the 30 instructions are not worth a divergent branch.)
 // INDEXED (on the masked form): as in unproject_kernel -- the maps, projections and mask of frame f = frame_of[b], everything of the cuboid by b.
-template <int NVL, bool GRID, bool MASKED = false, bool INDEXED = false>
-__global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MASKED, INDEXED> a) {
+// RAGGED (on the masked form): as in unproject_kernel -- rows view_base[b] + v, the prefix mask of n_b bits.  The rows behind a sample's last view are
+// the next sample's, and behind row T - 1 nobody's: a lane whose view slot is not one of the sample's loads the projection of the sample's LAST view
+// in its place (row clamped below T), so no address outside the T rows is formed for a load; what it projects is never sampled (the slot is masked).
+template <int NVL, bool GRID, bool MASKED = false, bool INDEXED = false, bool RAGGED = false>
+__global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MASKED, INDEXED, RAGGED> a) {
     static_assert(MASKED || !INDEXED, "the indexed kernels are built on the masked form");
+    static_assert(!RAGGED || (MASKED && !INDEXED), "the ragged kernels are built on the masked form");
     typedef bf16_t T;
     constexpr int C = 32, NV = 4 * NVL;
     int b, chunk, f;
@@ -364,7 +397,16 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
         f = b;
     }
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
-    const T* feats = (const T*)a.feats + (long long)f * NV * a.h * a.w * C;
+    long long vrow;            // the row of the sample's first view
+    int nb = NV;
+    if constexpr (RAGGED) {
+        int row;
+        views_of_sample(a, b, NV, row, nb);
+        vrow = row;
+    } else {
+        vrow = (long long)f * NV;
+    }
+    const T* feats = (const T*)a.feats + vrow * a.h * a.w * C;
     const float* coords = GRID ? nullptr : a.coords + (long long)b * nvox * 3;
     float* coords_out = (GRID && a.coords_out) ? a.coords_out + (long long)b * nvox * 3 : nullptr;
     T* out = (T*)a.out + (long long)b * nvox * C;
@@ -374,9 +416,12 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
     const int h = a.h, w = a.w;
     float P[NVL][12];
 #pragma unroll
-    for (int s = 0; s < NVL; ++s)
+    for (int s = 0; s < NVL; ++s) {
+        long long prow = vrow + qv + 4 * s;
+        if constexpr (RAGGED) prow = min(vrow + min(qv + 4 * s, max(nb - 1, 0)), (long long)a.T - 1);
 #pragma unroll
-        for (int i = 0; i < 12; ++i) P[s][i] = a.proj[((long long)f * NV + qv + 4 * s) * 12 + i];
+        for (int i = 0; i < 12; ++i) P[s][i] = a.proj[prow * 12 + i];
+    }
     float gp[3], gc[3], gR[9];
     if (GRID) {
 #pragma unroll
@@ -386,7 +431,9 @@ __global__ __launch_bounds__(256) void unproject_qn_kernel(const UnprojArgsOf<MA
     }
     const float inv_h = __builtin_amdgcn_rcpf((float)h), inv_w = __builtin_amdgcn_rcpf((float)w);
     unsigned mbits = (1u << NV) - 1u;
-    if constexpr (MASKED) {
+    if constexpr (RAGGED) {
+        mbits = (1u << nb) - 1u;
+    } else if constexpr (MASKED) {
         if (!INDEXED || a.mask) {
             mbits = 0;
 #pragma unroll
@@ -500,26 +547,27 @@ constexpr bool PIN_DEFAULT_FRAME = false;
 // One workgroup of 256 threads per (sample, chunk).  An unmasked kernel receives a plain UnprojArgs by value (the base of m) and a masked one all of
 // m: that is what keeps the unmasked kernels' argument block, and with it their code, what it was before the mask existed.
 // An indexed kernel receives all of m (by frame, xcd_pin 2: eight times the workgroups, see cuboid_chunk_of).
-template <bool MASKED, bool INDEXED>
-void launch_chunks(void (*kern)(UnprojArgsOf<MASKED, INDEXED>), const UnprojIndexedArgs& m, hipStream_t st) {
-    const UnprojArgsOf<MASKED, INDEXED>& a = m;
+template <bool MASKED, bool INDEXED, bool RAGGED = false>
+void launch_chunks(void (*kern)(UnprojArgsOf<MASKED, INDEXED, RAGGED>), const UnprojRaggedArgs& m, hipStream_t st) {
+    const UnprojArgsOf<MASKED, INDEXED, RAGGED>& a = m;
     hipLaunchKernelGGL(kern, dim3((unsigned)((long long)m.B * m.chunks * (INDEXED && m.xcd_pin == 2 ? 8 : 1))), dim3(256), 0, st, a);
 }
-template <bool MASKED, bool INDEXED>
-void launch_quad(const UnprojIndexedArgs& m, bool grid, hipStream_t st) {
-    launch_chunks<MASKED, INDEXED>(m.NV == 4 ? (grid ? unproject_qn_kernel<1, true, MASKED, INDEXED> : unproject_qn_kernel<1, false, MASKED, INDEXED>)
-                                             : (grid ? unproject_qn_kernel<2, true, MASKED, INDEXED> : unproject_qn_kernel<2, false, MASKED, INDEXED>), m, st);
+template <bool MASKED, bool INDEXED, bool RAGGED = false>
+void launch_quad(const UnprojRaggedArgs& m, bool grid, hipStream_t st) {
+    launch_chunks<MASKED, INDEXED, RAGGED>(m.NV == 4 ? (grid ? unproject_qn_kernel<1, true, MASKED, INDEXED, RAGGED> : unproject_qn_kernel<1, false, MASKED, INDEXED, RAGGED>)
+                                                     : (grid ? unproject_qn_kernel<2, true, MASKED, INDEXED, RAGGED> : unproject_qn_kernel<2, false, MASKED, INDEXED, RAGGED>), m, st);
 }
-template <typename T, int CH, bool MASKED, bool INDEXED>
-void launch_generic(const UnprojIndexedArgs& m, hipStream_t st) {
-    launch_chunks<MASKED, INDEXED>(m.NV <= 8 ? unproject_kernel<T, CH, true, MASKED, INDEXED> : unproject_kernel<T, CH, false, MASKED, INDEXED>, m, st);
+template <typename T, int CH, bool MASKED, bool INDEXED, bool RAGGED = false>
+void launch_generic(const UnprojRaggedArgs& m, hipStream_t st) {
+    launch_chunks<MASKED, INDEXED, RAGGED>(m.NV <= 8 ? unproject_kernel<T, CH, true, MASKED, INDEXED, RAGGED> : unproject_kernel<T, CH, false, MASKED, INDEXED, RAGGED>, m, st);
 }
 template <typename T, int CH>
-int launch_unproject(const UnprojIndexedArgs& m, hipStream_t st) {
-    if (m.frame_of) launch_generic<T, CH, true, true>(m, st);
+int launch_unproject(const UnprojRaggedArgs& m, hipStream_t st) {
+    if (m.view_base) launch_generic<T, CH, true, false, true>(m, st);
+    else if (m.frame_of) launch_generic<T, CH, true, true>(m, st);
     else if (m.mask) launch_generic<T, CH, true, false>(m, st);
     else launch_generic<T, CH, false, false>(m, st);
-    LT_CHECK_LAUNCH(m.frame_of ? "lt_unproject_indexed_fwd" : m.mask ? "lt_unproject_masked_fwd" : "lt_unproject_fwd");
+    LT_CHECK_LAUNCH(m.view_base ? "lt_unproject_ragged_fwd" : m.frame_of ? "lt_unproject_indexed_fwd" : m.mask ? "lt_unproject_masked_fwd" : "lt_unproject_fwd");
     return LT_OK;
 }
 
@@ -533,8 +581,8 @@ int launch_coord_volumes(const char* what, const float* pos, const float* center
 
 // fills the launch geometry and picks the kernel; a.coords (read) or the a.g_* grid description must be set by the caller.  a.mask set: the masked
 // instantiation of the SAME kernel the unmasked call takes (a masked plan never leaves the quad kernel for the generic one).  a.frame_of set: the
-// indexed instantiation of that kernel, a.B cuboids over a.F frames.
-int unproject_dispatch(UnprojIndexedArgs& a, int dtype, bool grid, hipStream_t st) {
+// indexed instantiation of that kernel, a.B cuboids over a.F frames.  a.view_base set: the ragged instantiation, a.NV = NVcap.
+int unproject_dispatch(UnprojRaggedArgs& a, int dtype, bool grid, hipStream_t st) {
     const long long nvox = (long long)a.v0 * a.v1 * a.v2;
     a.bricked = (a.v0 % 4 == 0 && a.v1 % 4 == 0 && a.v2 % 16 == 0) ? 1 : 0;
     a.blocked = (a.bricked && a.v0 % 32 == 0 && a.v1 % 32 == 0 && a.v2 % 32 == 0 && !env_on("LT_UNPROJ_RASTER")) ? 1 : 0;          // LT_UNPROJ_RASTER=1: the old order (A/B)
@@ -552,10 +600,11 @@ int unproject_dispatch(UnprojIndexedArgs& a, int dtype, bool grid, hipStream_t s
     const bool quad = dtype == LT_BF16 && a.C == 32 && (a.NV == 4 || a.NV == 8) && a.bricked && a.agg == LT_AGG_SOFTMAX && !no_q4 &&
                       (long long)a.NV * a.h * a.w * a.C < (1ll << 30);
     if (quad) {
-        if (a.frame_of) launch_quad<true, true>(a, grid, st);
+        if (a.view_base) launch_quad<true, false, true>(a, grid, st);
+        else if (a.frame_of) launch_quad<true, true>(a, grid, st);
         else if (a.mask) launch_quad<true, false>(a, grid, st);
         else launch_quad<false, false>(a, grid, st);
-        LT_CHECK_LAUNCH(a.frame_of ? "lt_unproject_indexed_fwd(quad)" : a.mask ? "lt_unproject_masked_fwd(quad)" : "lt_unproject_fwd(quad)");
+        LT_CHECK_LAUNCH(a.view_base ? "lt_unproject_ragged_fwd(quad)" : a.frame_of ? "lt_unproject_indexed_fwd(quad)" : a.mask ? "lt_unproject_masked_fwd(quad)" : "lt_unproject_fwd(quad)");
         return LT_OK;
     }
     if (grid) {      // no fused kernel for this configuration: materialise the grid (it is a returned tensor anyway), then gather
@@ -585,11 +634,21 @@ struct UnprojFrames {
     int F;
 };
 
-// The one body behind the six forward entries: `who` is the entry that was called, `cub` is set by the grid entries (v0 = v1 = v2 = V there),
+// The views of the ragged entries: sample b reads rows view_base[b] .. view_base[b + 1] of the T; NV of the call is NVcap.
+struct UnprojRagged {
+    const int32_t* view_base;
+    int T;
+};
+
+// The one body behind the eight forward entries: `who` is the entry that was called, `cub` is set by the grid entries (v0 = v1 = v2 = V there),
 // `masked` by the masked ones and `frames` by the indexed ones (B = their P cuboids; their view_mask may be null).
 int unproject_forward(const char* who, int dtype, const void* feats, const float* proj, const float* coords, const UnprojCuboid* cub, const float* conf,
                       bool masked, const uint8_t* view_mask, void* out, int B, int NV, int C, int h, int w, int v0, int v1, int v2, int agg, void* stream,
-                      const UnprojFrames* frames = nullptr) {
+                      const UnprojFrames* frames = nullptr, const UnprojRagged* ragged = nullptr) {
+    LT_REQUIRE(!ragged || ragged->view_base, LT_ERR_INVALID, "%s: null view_base", who);
+    LT_REQUIRE(!ragged || B >= 1, LT_ERR_INVALID, "%s: B %d samples", who, B);
+    LT_REQUIRE(!ragged || ragged->T >= 1, LT_ERR_INVALID, "%s: T %d images", who, ragged->T);
+    LT_REQUIRE(!ragged || (NV >= 1 && NV <= 32), LT_ERR_INVALID, "%s: NVcap %d (1..32)", who, NV);
     LT_REQUIRE(!frames || frames->frame_of, LT_ERR_INVALID, "%s: null frame_of", who);
     LT_REQUIRE(!frames || frames->F >= 1, LT_ERR_INVALID, "%s: F %d frames", who, frames->F);
     LT_REQUIRE(!frames || B >= 1, LT_ERR_INVALID, "%s: P %d cuboids", who, B);
@@ -600,8 +659,9 @@ int unproject_forward(const char* who, int dtype, const void* feats, const float
     LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "%s: LT_AGG_CONF* needs confidences", who);
     LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && (cub ? v0 >= 2 : v0 >= 1 && v1 >= 1 && v2 >= 1), LT_ERR_INVALID, "%s: bad shape", who);
     LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
-    UnprojIndexedArgs a = {};
+    UnprojRaggedArgs a = {};
     if (frames) { a.frame_of = frames->frame_of; a.F = frames->F; }
+    if (ragged) { a.view_base = ragged->view_base; a.T = ragged->T; }
     a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out; a.mask = (masked || frames) ? view_mask : nullptr;
     a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = v0; a.v1 = v1; a.v2 = v2; a.agg = agg;
     if (cub) { a.g_pos = cub->pos; a.g_center = cub->center; a.g_rot = cub->rot; a.g_step = cub->step; a.g_cmu = cub->cmu; a.coords_out = cub->coords_out; }
@@ -658,6 +718,23 @@ extern "C" int lt_unproject_grid_indexed_fwd(int32_t dtype, const void* feats, c
     const UnprojFrames frames = {frame_of, F};
     return unproject_forward("lt_unproject_grid_indexed_fwd", dtype, feats, proj, nullptr, &cub, conf, false, view_mask, out, P, NV, C, h, w, V, V, V, agg, stream,
                              &frames);
+}
+
+extern "C" int lt_unproject_ragged_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const int32_t* view_base,
+                                       void* out, int32_t B, int32_t T, int32_t NVcap, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2,
+                                       int32_t agg, void* stream) {
+    const UnprojRagged ragged = {view_base, T};
+    return unproject_forward("lt_unproject_ragged_fwd", dtype, feats, proj, coords, nullptr, conf, false, nullptr, out, B, NVcap, C, h, w, v0, v1, v2, agg, stream,
+                             nullptr, &ragged);
+}
+
+extern "C" int lt_unproject_grid_ragged_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
+                                            float step, int32_t cmu_transfer, float* coords_out, const float* conf, const int32_t* view_base, void* out,
+                                            int32_t B, int32_t T, int32_t NVcap, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream) {
+    const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
+    const UnprojRagged ragged = {view_base, T};
+    return unproject_forward("lt_unproject_grid_ragged_fwd", dtype, feats, proj, nullptr, &cub, conf, false, nullptr, out, B, NVcap, C, h, w, V, V, V, agg, stream,
+                             nullptr, &ragged);
 }
 
 namespace {

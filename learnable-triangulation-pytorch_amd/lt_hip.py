@@ -147,6 +147,10 @@ SIGNATURES = {
     "lt_plan_forward_vol": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_create_vol_multi": (C.c_int, [C.POINTER(VolPlanConfig), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
     "lt_plan_forward_vol_multi": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "lt_plan_create_vol_ragged": (C.c_int, [C.POINTER(VolPlanConfig), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
+    "lt_plan_forward_vol_ragged": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "lt_plan_create_alg_ragged": (C.c_int, [C.POINTER(AlgPlanConfig), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
+    "lt_plan_forward_alg_ragged": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_create_alg": (C.c_int, [C.POINTER(AlgPlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
     "lt_plan_forward_alg": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "lt_plan_create_cascade": (C.c_int, [C.POINTER(CascadePlanConfig), C.POINTER(NamedTensor), i32, C.POINTER(NamedTensor), i32, C.POINTER(vp)]),
@@ -208,6 +212,9 @@ SIGNATURES = {
     "lt_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_alg_tail_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
     "lt_alg_tail_masked_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "lt_alg_tail_ragged_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "lt_unproject_ragged_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "lt_unproject_grid_ragged_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_alg_tail_stats_fwd": (C.c_int, [vp, vp, i32, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_triangulate_dlt_stats": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "lt_heatmap_argmax_nchw_f32": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

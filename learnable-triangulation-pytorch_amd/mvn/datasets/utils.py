@@ -160,6 +160,30 @@ def prepare_batch_frames(batch, device, image_shape, norm_image=True):
     return (out,) + _targets(batch, device)
 
 
+def ragged_batch(images, proj_matricies, batch):
+    """A padded (B, NV, ...) batch with batch["view_mask"] -> its ragged form (images_r, proj_r, batch_r): the valid views of every sample, sample 0's first.
+    images (B,NV,3,H,W) -> (T,3,H,W); proj_matricies (B,NV,3,4) or None -> (T,3,4) or None; batch["cameras"] (cameras[v][b], as the models take them)
+    -> a flat list of T cameras in the same order; batch_r["view_counts"] holds the B counts and has no "view_mask"; every other key is passed on.
+    Pure indexing: it works on CPU tensors and on device tensors alike, and copies nothing but the gathered rows.  Without a view_mask every view is
+    valid (the padded batch reshaped)."""
+    from mvn.utils import op
+    B, NV = images.shape[:2]
+    mask = batch.get("view_mask")
+    m = np.ones((B, NV), np.uint8) if mask is None else op.view_mask_host(mask, B, NV, min_valid=1)
+    rows = np.flatnonzero(m.reshape(-1))
+    idx = torch.from_numpy(rows.astype(np.int64)).to(images.device)
+    out = {k: v for k, v in batch.items() if k != "view_mask"}
+    out["view_counts"] = [int(n) for n in m.sum(axis=1)]
+    if batch.get("cameras") is not None:
+        cams = batch["cameras"]
+        out["cameras"] = [cams[int(r) % NV][int(r) // NV] for r in rows]
+    images_r = images.reshape((B * NV,) + tuple(images.shape[2:])).index_select(0, idx)
+    proj_r = None
+    if proj_matricies is not None:
+        proj_r = proj_matricies.reshape(B * NV, 3, 4).index_select(0, idx.to(proj_matricies.device))
+    return images_r, proj_r, out
+
+
 def _upload(desc, regions, off, device):
     """descriptors + the pixel regions they point at (desc[:, 0] = byte offset of each region after the descriptors) -> one pinned
     block of the staging ring and one asynchronous H2D copy.  Returns (device uint8 tensor, byte length of the descriptors)."""

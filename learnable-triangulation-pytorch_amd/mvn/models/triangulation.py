@@ -79,6 +79,14 @@ def _batch_cuboid_frame(batch, F, who):
     return op.frame_index_host(cf, F, what="%s: batch['cuboid_frame']" % who)
 
 
+def _refuse_view_counts(batch, who):
+    """``batch["view_counts"]`` (a ragged batch, mvn.datasets.utils.ragged_batch) on a model without a ragged plan is refused before anything is launched
+    (VolumetricTriangulationNet and AlgebraicTriangulationNet take it in eval())."""
+    if isinstance(batch, dict) and batch.get("view_counts") is not None:
+        raise NotImplementedError("%s: batch['view_counts'] (a ragged batch) is not taken by this model; pad the batch to (B, NV) and pass "
+                                  "batch['view_mask'] instead, or run VolumetricTriangulationNet / AlgebraicTriangulationNet on the ragged batch" % who)
+
+
 class _VolTrainPlan:
     """The training step of VolumetricTriangulationNet for one input shape, recorded once and replayed (lt_train.TrainTape): the first
     forward / backward run the layers while recording them; later steps re-launch the recorded closures over the same buffers.  What
@@ -422,8 +430,12 @@ class VolumetricTriangulationNet(_PlannedNet):
                                   "bfloat16": torch.bfloat16}[str(m.compute_dtype)]
 
     # ---------------------------------------------------------------------------------------
-    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False, cuboids=None):
-        """cuboids: the plan of forwards with ``batch["cuboid_frame"]`` -- P = ``cuboids`` cuboids over the B frames: the backbone and process_features
+    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False, cuboids=None, ragged=None):
+        """ragged: the plan of forwards with ``batch["view_counts"]`` -- B samples over ``ragged`` = T images in all, NV = NVcap: the backbone and
+        process_features are recorded at T images, the gather is lt_unproject_grid_ragged_fwd, everything behind it is the plain plan's; the B + 1 int32
+        offsets ride in the geometry block behind the rotations, outside the captured graph: other counts with the same (B, T, NVcap) are just another
+        forward.  None: NV views per sample, the plan it always was.
+        cuboids: the plan of forwards with ``batch["cuboid_frame"]`` -- P = ``cuboids`` cuboids over the B frames: the backbone and process_features
         are recorded at B * NV images, the gather (lt_unproject_grid_indexed_fwd), V2V, the soft-argmax and their buffers at P; the P int32 frame indices
         ride in the geometry block behind the rotations (in front of the mask), outside the captured graph like the rest of it: a new assignment of
         cuboids to frames on a captured plan is just another forward.  None: one cuboid per sample, the plan it always was.
@@ -433,7 +445,9 @@ class VolumetricTriangulationNet(_PlannedNet):
         stats: the plan of forwards with ``keypoint_stats`` -- the same launch list with lt_softargmax3d_stats_fwd in the tail op's place (same op kind)."""
         V, J = self.volume_size, self.num_joints
         F, multi = B, cuboids is not None          # F frames carry the images, the features and the confidences ...
-        b, x_in = self._open_plan(F * NV, Hh, W, device, dry_run)
+        assert ragged is None or not (multi or masked), "a ragged plan has neither a mask nor several cuboids per frame"
+        nimg = F * NV if ragged is None else int(ragged)          # images of the backbone pass
+        b, x_in = self._open_plan(nimg, Hh, W, device, dry_run)
         B = int(cuboids) if multi else F           # ... everything from the gather on is per cuboid
         lib = b.lib
         # the 1x1 heatmap head is dead in the volumetric path: only its SHAPE is used (reference :264)
@@ -447,21 +461,23 @@ class VolumetricTriangulationNet(_PlannedNet):
         b.release(feats256)
         feats.pooled = False
         h, w = feats.shape[2], feats.shape[3]
-        # geometry block (fp32, one H2D copy per forward): proj F*NV*12 | pos B*3 | center B*3 | rot B*9 | [frame_of B int32] | [mask F*NV bytes]
-        o_fof = F * NV * 12 + B * 15           # multi-cuboid plans: the frame of every cuboid
+        # geometry block (fp32, one H2D copy per forward): proj nimg*12 | pos B*3 | center B*3 | rot B*9 | [frame_of B int32] | [mask F*NV bytes]
+        # (ragged plans: | view_base (B + 1) int32 behind the rotations)
+        o_fof = nimg * 12 + B * 15             # multi-cuboid plans: the frame of every cuboid
         o_mask = o_fof + (B if multi else 0)   # masked plans: F*NV mask bytes behind the words (whole words)
-        n_geo = o_mask + ((F * NV + 3) // 4 if masked else 0)
+        o_vb = o_fof                           # ragged plans: the B + 1 offsets (the exclusive prefix sum of the counts; the last one is T)
+        n_geo = o_mask + ((F * NV + 3) // 4 if masked else 0) + (B + 1 if ragged is not None else 0)
         geo = torch.zeros(n_geo, dtype=torch.float32, device=device)
         # pinned staging ring: forward N+1 fills the next slot while forward N's copy may still be queued (forward never blocks on the GPU otherwise)
         geo_ring = PinnedRing(n_geo, torch.float32, 1 if dry_run else GEO_RING, pin=not dry_run)
-        o_pos, o_cen, o_rot = F * NV * 12, F * NV * 12 + 3 * B, F * NV * 12 + 6 * B
+        o_pos, o_cen, o_rot = nimg * 12, nimg * 12 + 3 * B, nimg * 12 + 6 * B
         coords = torch.empty(B, V, V, V, 3, dtype=torch.float32, device=device)
         step = float(np.float32(self.cuboid_side / (V - 1)))
         gp = geo.data_ptr()
         cmu = int(bool(self.transfer_cmu_to_human36m))
         conf = None
         if volc is not None:
-            conf = volc.t.reshape(F, NV, 32)   # 'conf_norm' is normalised inside the kernel (LT_AGG_CONF_NORM)
+            conf = volc.t.reshape(F, NV, 32) if ragged is None else volc.t.reshape(nimg, 32)   # 'conf_norm' is normalised inside the kernel (LT_AGG_CONF_NORM)
         vol = b.alloc((B, V, V, V, 32))
         esz = E.esize(self.compute_dtype)
         agg = H.AGG[self.volume_aggregation_method]
@@ -469,7 +485,12 @@ class VolumetricTriangulationNet(_PlannedNet):
         # coordinate tensor on the way (reference :298-339 + op.py:99-166); configurations without a fused kernel run
         # lt_coord_volumes + the generic gather inside the same call
         entry = "lt_unproject_grid_indexed_fwd" if multi else "lt_unproject_grid_masked_fwd" if masked else "lt_unproject_grid_fwd"
-        if multi:
+        if ragged is not None:
+            entry = "lt_unproject_grid_ragged_fwd"
+            unproject = lambda st: H.check(lib.lt_unproject_grid_ragged_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
+                                                                            coords.data_ptr(), H.ptr(conf), gp + 4 * o_vb, vol.t.data_ptr(), B, nimg, NV, 32, h, w, V,
+                                                                            agg, st), entry)
+        elif multi:
             unproject = lambda st: H.check(lib.lt_unproject_grid_indexed_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
                                                                              coords.data_ptr(), H.ptr(conf), gp + 4 * o_mask if masked else None, gp + 4 * o_fof,
                                                                              vol.t.data_ptr(), F, B, NV, 32, h, w, V, agg, st), entry)
@@ -482,7 +503,7 @@ class VolumetricTriangulationNet(_PlannedNet):
                                                                      coords.data_ptr(), H.ptr(conf), vol.t.data_ptr(), B, NV, 32, h, w, V, agg, st),
                                            "lt_unproject_grid_fwd")
         b.custom(unproject,
-                 "unproject", nbytes=(F * NV * h * w * 32 + B * V ** 3 * 32) * esz + B * V ** 3 * 12,   # feats once + volume once + the returned coords
+                 "unproject", nbytes=(nimg * h * w * 32 + B * V ** 3 * 32) * esz + B * V ** 3 * 12,   # feats once + volume once + the returned coords
                  info={"feats": feats, "geo": geo, "coords": coords, "conf": conf, "vol": vol, "agg": self.volume_aggregation_method, "NV": NV,
                        "offs": (o_pos, o_cen, o_rot), "step": step, "cmu": cmu, "masked": masked, "entry": entry, "frames": F, "cuboids": B})
         logits = self.volume_net.record(b, vol)
@@ -496,8 +517,8 @@ class VolumetricTriangulationNet(_PlannedNet):
         # launch from the plan's channels-last map straight into the tensor forward() hands out (it was a permuted view + an ATen cast copy);
         # skipped when the caller asked for views of the plan's buffers (copy_outputs = False)
         b.custom(lambda st, outs=None: None if not outs or len(outs) < 3 or outs[2] is None else H.check(lib.lt_nhwc_to_nchw_f32(
-                     b.code, feats.t.data_ptr(), outs[2].data_ptr(), F * NV, 32, h * w, 32, st), "lt_nhwc_to_nchw_f32"),
-                 "features_out", nbytes=F * NV * h * w * 32 * (esz + 4), info={"feats": feats}, tail=True)
+                     b.code, feats.t.data_ptr(), outs[2].data_ptr(), nimg, 32, h * w, 32, st), "lt_nhwc_to_nchw_f32"),
+                 "features_out", nbytes=nimg * h * w * 32 * (esz + 4), info={"feats": feats}, tail=True)
         # tail op (outside the captured graph): forward() points it at the tensors it returns, so the 17 x 64^3 probabilities
         # are written once, where the caller gets them, instead of being cloned out of a plan buffer (0.45 ms of copies per step)
         kstats = kindex = None
@@ -525,7 +546,7 @@ class VolumetricTriangulationNet(_PlannedNet):
         return {"plan": plan, "x_in": x_in, "image_cell": image_cell, "feats": feats, "geo": geo, "geo_host": geo_ring.blocks[0], "geo_ring": geo_ring,
                 "coords": coords, "kp": kp, "probs": probs, "conf": conf, "logits": logits, "vol": vol, "hw": (h, w), "offs": (o_pos, o_cen, o_rot),
                 "captured": False, "masked": masked, "o_mask": o_mask, "kstats": kstats, "kindex": kindex, "frames": F, "cuboids": B if multi else None,
-                "o_fof": o_fof}
+                "o_fof": o_fof, "ragged": None if ragged is None else nimg, "o_vb": o_vb}
 
     def _host_cameras(self, batch, B, image_shape, P):
         """The camera half of the host geometry (reference :272-279, :318-328): fills the projections and rotations of the next slot of the plan's
@@ -546,6 +567,8 @@ class VolumetricTriangulationNet(_PlannedNet):
         gh[o_rot:o_rot + 9 * nc] = torch.from_numpy(rot.astype(np.float32).reshape(-1))
         if P.get("cuboids"):
             gh.view(torch.int32)[P["o_fof"]:P["o_fof"] + nc] = torch.from_numpy(batch["cuboid_frame"])
+        if P.get("ragged"):
+            gh.view(torch.int32)[P["o_vb"]:P["o_vb"] + B + 1] = torch.from_numpy(batch["view_base"])
         if P.get("masked"):
             gh.view(torch.uint8)[4 * P["o_mask"]:4 * P["o_mask"] + B * len(batch["cameras"])] = torch.from_numpy(batch["view_mask"].reshape(-1))
         return gh
@@ -589,6 +612,8 @@ class VolumetricTriangulationNet(_PlannedNet):
         Asynchronous like the reference's CUDA forward: nothing here waits for the GPU (results are ordered on the current
         stream).  One plan per batch shape whatever its size: BASELINE config 4 at 32 samples (2^31 elements per 32-channel volume) is ONE plan and one
         captured graph -- the convolution entry points walk such tensors in sample chunks (``max_samples_per_launch``)."""
+        if isinstance(batch, dict) and batch.get("view_counts") is not None:
+            return self._forward_ragged(images, batch)
         B, NV = images.shape[:2]
         cf = _batch_cuboid_frame(batch, B, "VolumetricTriangulationNet")          # optional: several cuboids per frame, refused before any launch
         if cf is not None:
@@ -636,6 +661,62 @@ class VolumetricTriangulationNet(_PlannedNet):
         self.last_keypoint_stats = self._take_keypoint_stats()
         conf = None if parts[0][3] is None else cat(3)
         return cat(0), cat(1), cat(2), conf, [c for p in parts for c in p[4]], cat(5), cat(6)
+
+    def _forward_ragged(self, images, batch):
+        """``batch["view_counts"]`` (eval() only): a ragged batch, as mvn.datasets.utils.ragged_batch builds it.  images (T,3,H,W), the views of all samples
+        with sample 0's first; ``batch["cameras"]`` a flat list of the T cameras in that order; view_counts the B counts (1..32 each, summing to T); one
+        base point per sample.  The backbone runs on the T images and nothing else; sample b gets what the forward gives for that sample on its own views
+        alone.  Returns the 7-tuple with features (T,32,h,w) and vol_confidences (T,32) ('conf_norm': normalised over each sample's views), everything
+        else per sample.  One plan per (B, T, NVcap), NVcap the smallest of 4, 8, 32 that holds the largest count; other counts are another forward of it."""
+        who = "VolumetricTriangulationNet"
+        if batch.get("view_mask") is not None:
+            raise NotImplementedError("%s: batch['view_counts'] with batch['view_mask']; drop the missing views from the ragged batch instead of masking them" % who)
+        if batch.get("cuboid_frame") is not None:
+            raise NotImplementedError("%s: batch['view_counts'] with batch['cuboid_frame']; run the multi-cuboid forward on a padded batch with "
+                                      "batch['view_mask'] instead" % who)
+        if _bn_in_train_mode(self):
+            raise NotImplementedError("%s: batch['view_counts'] is inference only (a training tape is recorded per tensor shape); call eval() first, or pad "
+                                      "the batch and train with batch['view_mask'] and masked_training" % who)
+        if images.dim() != 4:
+            raise ValueError("%s: with batch['view_counts'] the images are (T, 3, H, W), got %s" % (who, tuple(images.shape)))
+        T, Hh, W = images.shape[0], images.shape[2], images.shape[3]
+        counts, base, nvcap = op.view_counts_host(batch["view_counts"], T, what="%s: batch['view_counts']" % who)
+        B = counts.size
+        key = "keypoints_3d" if self.use_gt_pelvis else "pred_keypoints_3d"
+        for k in ("cameras", key):
+            if batch.get(k) is None:
+                raise ValueError("%s: with batch['view_counts'] the batch needs %r (%s)" %
+                                 (who, k, "a flat list of the T cameras" if k == "cameras" else "one base point per sample"))
+        cams = batch["cameras"]
+        if len(cams) != T or any(isinstance(c, (list, tuple)) for c in cams):
+            raise ValueError("%s: with batch['view_counts'] batch['cameras'] is a flat list of the T = %d cameras, got %d entries%s" %
+                             (who, T, len(cams), " of lists" if len(cams) and isinstance(cams[0], (list, tuple)) else ""))
+        if len(batch[key]) != B:
+            raise ValueError("%s: batch['view_counts'] names %d samples, batch[%r] has %d entries (one base point per sample)" % (who, B, key, len(batch[key])))
+        if B > self.max_samples_per_launch(nvcap, Hh, W):
+            raise ValueError("%s: a ragged forward is one plan, and %d samples would need sub-batches at this shape (max_samples_per_launch); split the call" % (who, B))
+        H.require_gpu(images, "images")
+        self.last_keypoint_stats = None
+        self.__dict__.pop("_chunk_stats", None)
+        _sync_buffers_before_eval(self)
+        device = images.device
+        stats = bool(self.keypoint_stats)
+        with torch.cuda.device(device):
+            P = self._plan_for(self._plan_key(B, nvcap, Hh, W, device, False, stats, None, T),
+                               lambda: self._build_plan(B, nvcap, Hh, W, device, stats=stats, ragged=T))
+            # cameras[v][b] with one "sample" of T views: stack_cameras gives the T projections in the batch's order
+            position, _, sides = self._host_geometry(dict(batch, cameras=[[c] for c in cams], view_base=base), B, (Hh, W), P)
+            cur = torch.cuda.current_stream(device)
+            side = self._side_stream(device)
+            side.wait_stream(cur)
+            x = images if images.dtype == torch.float32 and images.is_contiguous() else images.float().contiguous()
+            with torch.cuda.stream(side):
+                self._copy_geometry(P, side)
+                kp, feats, probs, conf, coords, base_points = self._replay(P, x, B, nvcap, side, cur, view_counts=counts)
+            x.record_stream(side)
+            cur.wait_stream(side)
+        self.last_keypoint_stats = self._take_keypoint_stats()
+        return kp, feats, probs, conf, [volumetric.Cuboid3D(position[i], sides) for i in range(B)], coords, base_points
 
     def _take_keypoint_stats(self):
         """The op.KeypointStats of the forward whose chunks just ran (``_replay`` left each chunk's records behind), chunks concatenated; None for a
@@ -733,14 +814,16 @@ class VolumetricTriangulationNet(_PlannedNet):
                            lambda: self._build_plan(B, NV, Hh, W, device, masked=masked, stats=stats, cuboids=nc))
         return images, batch, B, P
 
-    def _plan_key(self, B, NV, Hh, W, device, masked=False, stats=False, cuboids=None):
-        """Everything a plan bakes in besides the weights; ``masked``: the plan records the masked gather (forwards without a mask keep their plan);
+    def _plan_key(self, B, NV, Hh, W, device, masked=False, stats=False, cuboids=None, ragged=None):
+        """``ragged``: the T of a ragged plan of B samples, NV = NVcap (forwards without ``batch["view_counts"]`` keep their key).
+        Everything a plan bakes in besides the weights; ``masked``: the plan records the masked gather (forwards without a mask keep their plan);
         ``stats``: its tail is lt_softargmax3d_stats_fwd (``keypoint_stats``; forwards without the flag keep their plan); ``cuboids``: the P of a
         multi-cuboid plan over B frames (forwards without ``batch["cuboid_frame"]`` keep their plan: their key is the tuple it always was)."""
         key = (B, NV, Hh, W, self.compute_dtype, device, self.use_graph, self.volume_size, float(self.cuboid_side),
                float(self.volume_multiplier), bool(self.volume_softmax), self.volume_aggregation_method,
                bool(self.transfer_cmu_to_human36m), self.tile_override, self.num_joints, masked, stats)
-        return key if cuboids is None else key + ("cuboids", int(cuboids))
+        key = key if cuboids is None else key + ("cuboids", int(cuboids))
+        return key if ragged is None else key + ("ragged", int(ragged))
 
     @staticmethod
     def _plan_images(images, B, NV):
@@ -755,8 +838,9 @@ class VolumetricTriangulationNet(_PlannedNet):
         P["geo"].copy_(P["geo_host"], non_blocking=True)
         P["geo_ring"].commit(side)
 
-    def _replay(self, P, x, B, NV, side, cur, view_mask=None):
-        """On the side stream, behind the geometry: the plan's launches.  Returns (kp, feats, probs, conf, coords, base_points).  view_mask (masked
+    def _replay(self, P, x, B, NV, side, cur, view_mask=None, view_counts=None):
+        """view_counts (ragged plans): the host counts of this forward -- features come back as (T,32,h,w), confidences as (T,32).
+        On the side stream, behind the geometry: the plan's launches.  Returns (kp, feats, probs, conf, coords, base_points).  view_mask (masked
         plans): the host mask of this forward, for the returned conf_norm confidences."""
         device = x.device
         h, w = P["hw"]
@@ -775,13 +859,13 @@ class VolumetricTriangulationNet(_PlannedNet):
         kstats, kindex = P.get("kstats"), P.get("kindex")          # plans with keypoint_stats: the records of lt_softargmax3d_stats_fwd
         if self.copy_outputs:       # fresh result tensors like the reference's: the tail ops write them directly
             kp, probs = torch.empty_like(kp), torch.empty_like(probs)
-            feats = torch.empty(B, NV, 32, h, w, dtype=torch.float32, device=device)
+            feats = torch.empty((P["ragged"], 32, h, w) if P.get("ragged") else (B, NV, 32, h, w), dtype=torch.float32, device=device)
             if kstats is not None:
                 kstats, kindex = torch.empty_like(kstats), torch.empty_like(kindex)
             plan.run(st, (kp, probs, feats, kstats, kindex))
         else:
             plan.run(st)
-            feats = P["feats"].t.reshape(B, NV, h, w, 32).permute(0, 1, 4, 2, 3)
+            feats = P["feats"].t.reshape(B, NV, h, w, 32).permute(0, 1, 4, 2, 3) if not P.get("ragged") else P["feats"].t.permute(0, 3, 1, 2)
         if kstats is not None:          # left for forward(), which hands them out as last_keypoint_stats (one pair per chunk of the call)
             kstats.record_stream(cur); kindex.record_stream(cur)
             self.__dict__.setdefault("_chunk_stats", []).extend([kstats, kindex])
@@ -791,7 +875,19 @@ class VolumetricTriangulationNet(_PlannedNet):
         if self.copy_outputs:
             coords = coords.clone()
             conf = None if conf is None else conf.clone()
-        if conf is not None and self.volume_aggregation_method == "conf_norm":
+        if conf is not None and self.volume_aggregation_method == "conf_norm" and view_counts is not None:
+            # normalised over each sample's views: the rows scattered into a zero-filled (B, largest count) batch and summed as the plain forward sums
+            # its (B, NV) -- with equal counts that IS the plain forward's tensor, so the same bits
+            # (the two index tensors are kept per plan and counts: a forward with the counts of the last one builds and uploads nothing)
+            top = int(view_counts.max())
+            ck = tuple(int(n) for n in view_counts)
+            if P.get("conf_index", (None,))[0] != ck:
+                P["conf_index"] = (ck, torch.from_numpy(np.repeat(np.arange(B), view_counts)).to(device),
+                                   torch.from_numpy(np.concatenate([i * top + np.arange(n) for i, n in enumerate(view_counts)])).to(device))
+            _, seg, slot = P["conf_index"]
+            sums = torch.zeros(B * top, conf.shape[-1], dtype=conf.dtype, device=device).index_copy_(0, slot, conf).reshape(B, top, -1).sum(dim=1, keepdim=True)
+            conf = conf / sums[:, 0].index_select(0, seg)
+        elif conf is not None and self.volume_aggregation_method == "conf_norm":
             if view_mask is not None:          # normalised over the valid views, a masked view's entries 0 (an all-ones mask: the same bits)
                 on = torch.from_numpy(view_mask).to(device, non_blocking=True).bool()[:, :, None]
                 conf = torch.where(on, conf, torch.zeros((), dtype=conf.dtype, device=device))
@@ -840,16 +936,20 @@ class AlgebraicTriangulationNet(_PlannedNet):
         # gradient into a masked view's keypoints and confidences (the backbone still runs on every image).  False: a mask in train() is refused.
         self.masked_training = False
 
-    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False):
-        """masked: the plan of forwards with ``batch["view_mask"]`` -- the same launches, plus the mask's device block and its pinned staging ring (the
+    def _build_plan(self, B, NV, Hh, W, device, dry_run=False, masked=False, stats=False, ragged=None):
+        """ragged: the plan of forwards with ``batch["view_counts"]`` -- B samples over ``ragged`` = T images in all, NV = NVcap: the launches of T images,
+        plus the device block of the B + 1 int32 view offsets and its pinned staging ring (the tail after the plan is then lt_alg_tail_ragged_fwd; other
+        counts with the same (B, T, NVcap) are another forward of the plan).
+        masked: the plan of forwards with ``batch["view_mask"]`` -- the same launches, plus the mask's device block and its pinned staging ring (the
         tail after the plan is then lt_alg_tail_masked_fwd).
         stats: the plan of forwards with ``keypoint_stats`` -- the same launch list with lt_softargmax2d_stats_fwd in the soft-argmax op's place (the tail
         after the plan is then lt_alg_tail_stats_fwd)."""
-        b, x_in = self._open_plan(B * NV, Hh, W, device, dry_run)
+        assert ragged is None or not (masked or stats), "a ragged plan has neither a mask nor the statistics"
+        N = B * NV if ragged is None else int(ragged)          # images of the backbone pass
+        b, x_in = self._open_plan(N, Hh, W, device, dry_run)
         lib = b.lib
         hm, feats, algc, _ = self.backbone.record(b, x_in, want_heatmaps=True)
         b.release(feats)
-        N = B * NV
         J, h, w = hm.shape[4], hm.shape[2], hm.shape[3]
         hm_nchw = torch.empty(N, J, h, w, dtype=torch.float32, device=device)
         b.custom(lambda st: H.check(lib.lt_nhwc_to_nchw_f32(H.LT_F32, hm.t.data_ptr(), hm_nchw.data_ptr(), N, J, h * w, J, st), "lt_nhwc_to_nchw_f32"))
@@ -869,7 +969,10 @@ class AlgebraicTriangulationNet(_PlannedNet):
         plan = b.finish()
         plan.keep += [hm_nchw, kp2d, probs] + ([kstats, kindex] if stats else [])
         P = {"plan": plan, "x_in": x_in, "kp2d": kp2d, "probs": probs, "algc": algc, "hw": (h, w), "J": J, "masked": masked, "hm_nchw": hm_nchw,
-             "kstats": kstats, "kindex": kindex}
+             "kstats": kstats, "kindex": kindex, "ragged": None if ragged is None else N}
+        if ragged is not None:
+            P.update({"view_base": torch.zeros(B + 1, dtype=torch.int32, device=device),
+                      "view_base_ring": PinnedRing(B + 1, torch.int32, 1 if dry_run else GEO_RING, pin=not dry_run)})
         if masked:
             P.update({"mask": torch.zeros(N, dtype=torch.uint8, device=device),
                       "mask_ring": PinnedRing(N, torch.uint8, 1 if dry_run else GEO_RING, pin=not dry_run)})
@@ -878,6 +981,8 @@ class AlgebraicTriangulationNet(_PlannedNet):
     def forward(self, images, proj_matricies, batch):
         """Returns (keypoints_3d (B,J,3), keypoints_2d (B,NV,J,2) in image pixels, heatmaps (B,NV,J,h,w) after
         softmax, alg_confidences (B,NV,J)) -- reference :149-200."""
+        if isinstance(batch, dict) and batch.get("view_counts") is not None:
+            return self._forward_ragged(images, proj_matricies, batch)
         device = images.device
         B, NV = images.shape[:2]
         Hh, W = images.shape[3:]
@@ -894,11 +999,60 @@ class AlgebraicTriangulationNet(_PlannedNet):
             P = self._plan_for(self._plan_key(B, NV, Hh, W, device, masked, stats), lambda: self._build_plan(B, NV, Hh, W, device, masked=masked, stats=stats))
             return self._run(P, images, proj_matricies, B, NV, Hh, W, device, vm)
 
-    def _plan_key(self, B, NV, Hh, W, device, masked=False, stats=False):
-        """``masked``: the plan carries the mask's block; ``stats``: its soft-argmax op is lt_softargmax2d_stats_fwd (``keypoint_stats``).  Forwards without
+    def _forward_ragged(self, images, proj_matricies, batch):
+        """``batch["view_counts"]`` (eval() only): a ragged batch, as mvn.datasets.utils.ragged_batch builds it.  images (T,3,H,W) and proj_matricies
+        (T,3,4), the views of all samples with sample 0's first; view_counts the B counts (2..32 each, summing to T).  The backbone runs on the T images and
+        nothing else; sample b gets what the forward gives for that sample on its own views alone (lt_alg_tail_ragged_fwd: confidences normalised over the
+        sample's views + 1e-5, the DLT over its rows).  Returns keypoints_3d (B,J,3), keypoints_2d (T,J,2), heatmaps (T,J,h,w), alg_confidences (T,J)."""
+        who = "AlgebraicTriangulationNet"
+        if batch.get("view_mask") is not None:
+            raise NotImplementedError("%s: batch['view_counts'] with batch['view_mask']; drop the missing views from the ragged batch instead of masking them" % who)
+        if _bn_in_train_mode(self):
+            raise NotImplementedError("%s: batch['view_counts'] is inference only (a training tape is recorded per tensor shape); call eval() first, or pad "
+                                      "the batch and train with batch['view_mask'] and masked_training" % who)
+        if self.keypoint_stats:
+            raise NotImplementedError("%s: keypoint_stats with batch['view_counts'] (there is no ragged statistics tail); pad the batch and pass "
+                                      "batch['view_mask'] instead, or set keypoint_stats = False" % who)
+        if images.dim() != 4:
+            raise ValueError("%s: with batch['view_counts'] the images are (T, 3, H, W), got %s" % (who, tuple(images.shape)))
+        T, Hh, W = images.shape[0], images.shape[2], images.shape[3]
+        counts, base, nvcap = op.view_counts_host(batch["view_counts"], T, min_views=2, what="%s: batch['view_counts']" % who)
+        B = counts.size
+        if tuple(proj_matricies.shape) != (T, 3, 4):
+            raise ValueError("%s: with batch['view_counts'] proj_matricies are (T, 3, 4) = (%d, 3, 4), got %s" % (who, T, tuple(proj_matricies.shape)))
+        device = images.device
+        H.require_gpu(images, "images")
+        self.last_keypoint_stats = None
+        _sync_buffers_before_eval(self)
+        with torch.cuda.device(device):
+            P = self._plan_for(self._plan_key(B, nvcap, Hh, W, device, ragged=T), lambda: self._build_plan(B, nvcap, Hh, W, device, ragged=T))
+            h, w = P["hw"]; J = P["J"]
+            cur = torch.cuda.current_stream(device)
+            st = cur.cuda_stream
+            host = P["view_base_ring"].acquire()          # the offsets to their device block through the plan's pinned ring
+            host.copy_(torch.from_numpy(base))
+            P["view_base"].copy_(host, non_blocking=True)
+            P["view_base_ring"].commit(cur)
+            E.stage_images(images.float().contiguous(), P["x_in"], st)
+            P["plan"].run_eager(st)
+            heatmaps = P["probs"].clone()
+            algc = P["algc"]
+            proj = proj_matricies.to(device, torch.float32).contiguous()
+            kp2d = torch.empty(T, J, 2, dtype=torch.float32, device=device)
+            conf = torch.empty(T, J, dtype=torch.float32, device=device)
+            kp3d = torch.empty(B, J, 3, dtype=torch.float32, device=device)
+            H.check(H.lib().lt_alg_tail_ragged_fwd(P["kp2d"].data_ptr(), None if algc is None else algc.t.data_ptr(), J if algc is None else algc.t.shape[-1],
+                                                   proj.data_ptr(), W / w, Hh / h, P["view_base"].data_ptr(), kp2d.data_ptr(), conf.data_ptr(), kp3d.data_ptr(),
+                                                   B, T, nvcap, J, st), "lt_alg_tail_ragged_fwd")
+        return kp3d, kp2d, heatmaps, conf
+
+    def _plan_key(self, B, NV, Hh, W, device, masked=False, stats=False, ragged=None):
+        """``ragged``: the T of a ragged plan of B samples, NV = NVcap (forwards without ``batch["view_counts"]`` keep their key).
+        ``masked``: the plan carries the mask's block; ``stats``: its soft-argmax op is lt_softargmax2d_stats_fwd (``keypoint_stats``).  Forwards without
         a mask or without the flag keep their plans: an unflagged key is the tuple it always was."""
         key = (B, NV, Hh, W, self.compute_dtype, device, float(self.heatmap_multiplier), bool(self.heatmap_softmax), self.tile_override, masked)
-        return key + ("keypoint_stats",) if stats else key
+        key = key + ("keypoint_stats",) if stats else key
+        return key if ragged is None else key + ("ragged", int(ragged))
 
     def _forward_train(self, images, proj_matricies, view_mask=None):
         """view_mask (``masked_training``): the checked host (B, NV) mask -- the tape is the unmasked step's (the backbone runs on every image); the tail
@@ -1016,6 +1170,7 @@ class RANSACTriangulationNet(_PlannedNet):
     def forward(self, images, proj_matricies, batch):
         """Returns (keypoints_3d (B,J,3) fp32, keypoints_2d (B,NV,J,2) int64 image pixels, raw heatmaps (B,NV,J,h,w), confidences
         (B,NV,J) zeros) -- reference :27-73."""
+        _refuse_view_counts(batch, "RANSACTriangulationNet")
         if isinstance(batch, dict) and batch.get("view_mask") is not None:
             raise NotImplementedError("RANSACTriangulationNet takes no batch['view_mask']: its inlier search already drops views per joint")
         H.require_gpu(images, "images")
@@ -1112,6 +1267,7 @@ class CascadeTriangulationNet(nn.Module):
         ``VolumetricTriangulationNet.forward`` and the 4-tuple of ``AlgebraicTriangulationNet.forward``, same shapes and dtypes.  ``base_points``
         is read from the device block; ``cuboids`` is a sequence that builds its ``Cuboid3D`` items on first access, and that access
         synchronises with the GPU (the forward itself never does, beyond what the two models' forwards do at their first call of a shape)."""
+        _refuse_view_counts(batch, "CascadeTriangulationNet")
         B, NV = images.shape[:2]
         if isinstance(batch, dict) and batch.get("cuboid_frame") is not None:
             raise NotImplementedError("CascadeTriangulationNet: batch['cuboid_frame'] is not supported -- the algebraic stage gives ONE pelvis per frame, which "

@@ -119,7 +119,7 @@ class _TriangulateFn(torch.autograd.Function):
         return None, gpts, gconf
 
 
-def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_batch=None, view_mask=None, masked_backward=False):
+def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_batch=None, view_mask=None, masked_backward=False, view_counts=None):
     """Confidence-weighted DLT for every (sample, joint) in one launch (reference :171-183 loops B x J
     torch.svd calls).  proj (B,NV,3,4), points (B,NV,J,2), confidences (B,NV,J) -> (B,J,3) fp32.  Differentiable with respect to the
     points and the confidences when they require grad.
@@ -129,7 +129,37 @@ def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_
     NaN in a masked view cannot leak.  A sample needs two valid views (ValueError).  Inference only by default: NotImplementedError with
     inputs that require grad.  masked_backward=True opts into the differentiable masked DLT: the same construction in front of
     lt_triangulate_dlt / lt_triangulate_dlt_bwd, whose gradient for a row of zeros is zero and which torch.where routes back as zero -- a masked
-    view's points and confidences get exactly zero gradient, the valid ones what the DLT of the valid views alone gives."""
+    view's points and confidences get exactly zero gradient, the valid ones what the DLT of the valid views alone gives.
+
+    view_counts: a ragged batch.  proj (T,3,4), points (T,J,2) and confidences (T,J) hold the views of all samples, sample 0's first; view_counts the B
+    counts (2..32 each, summing to T) -> (B,J,3): sample b is the DLT of its own rows alone, bit for bit.  This is the padded route, not a ragged
+    kernel (the ragged DLT exists only inside lt_alg_tail_ragged_fwd, behind its confidence normalisation): the rows are scattered into a zero-filled
+    (B, largest count) batch on the device and lt_triangulate_dlt runs on that, as the view_mask path above does -- the kernel's QR skips a row of zeros.  Inference only: NotImplementedError with inputs that require grad,
+    and together with view_mask (drop the view from the batch instead)."""
+    if view_counts is not None:
+        from mvn.utils import op
+        if view_mask is not None:
+            raise NotImplementedError("triangulate_batch_of_points: view_counts with view_mask; drop the missing views from the ragged batch instead of masking them")
+        if torch.is_grad_enabled() and (points_batch.requires_grad or (confidences_batch is not None and confidences_batch.requires_grad)):
+            raise NotImplementedError("triangulate_batch_of_points: view_counts is inference only (no ragged backward); call it under torch.no_grad(), or pad "
+                                      "the batch and use view_mask with masked_backward=True")
+        if points_batch.dim() != 3:
+            raise ValueError("triangulate_batch_of_points: with view_counts the points are (T, J, 2), got %s" % (tuple(points_batch.shape),))
+        T, J = points_batch.shape[:2]
+        counts, base, _ = op.view_counts_host(view_counts, T, min_views=2)
+        if tuple(proj_matricies_batch.shape) != (T, 3, 4):
+            raise ValueError("triangulate_batch_of_points: with view_counts proj_matricies are (T, 3, 4) = (%d, 3, 4), got %s" % (T, tuple(proj_matricies_batch.shape)))
+        H.require_gpu(points_batch, "points_batch")
+        dev = points_batch.device
+        B, top = counts.size, int(counts.max())
+        slot = torch.from_numpy(np.concatenate([b * top + np.arange(n) for b, n in enumerate(counts)]).astype(np.int64)).to(dev)
+        P = torch.zeros(B * top, 3, 4, dtype=torch.float32, device=dev).index_copy_(0, slot, proj_matricies_batch.to(dev, torch.float32))
+        pts = torch.zeros(B * top, J, 2, dtype=torch.float32, device=dev).index_copy_(0, slot, points_batch.float())
+        src = torch.ones(T, J, dtype=torch.float32, device=dev) if confidences_batch is None else confidences_batch.float()
+        conf = torch.zeros(B * top, J, dtype=torch.float32, device=dev).index_copy_(0, slot, src)
+        out = torch.empty(B, J, 3, dtype=torch.float32, device=dev)
+        H.check(H.lib().lt_triangulate_dlt(P.data_ptr(), pts.data_ptr(), conf.data_ptr(), out.data_ptr(), B, top, J, H.cur_stream()), "lt_triangulate_dlt")
+        return out
     H.require_gpu(points_batch, "points_batch")
     P = proj_matricies_batch.to(points_batch.device, torch.float32).contiguous()
     pts = points_batch.float().contiguous()

@@ -77,6 +77,42 @@ def frame_index_host(frame_index, F, what="frame_index"):
     return np.ascontiguousarray(a.astype(np.int32))
 
 
+def view_counts_host(view_counts, T=None, min_views=1, what="view_counts"):
+    """The views of every sample of a ragged batch (a sequence, an array or a tensor of B >= 1 integers) -> (counts, view_base, NVcap): the counts as a host
+    int32 array, their exclusive prefix sum (B + 1 int32, what the ragged kernels read) and the smallest of 4, 8, 32 that holds the largest count (the
+    kernel instantiation).  ValueError for an empty or non-flat list, a count below ``min_views`` or above 32 (the message names the first such sample)
+    or counts that do not sum to ``T``; TypeError for a non-integer dtype."""
+    a = view_counts.detach().cpu().numpy() if torch.is_tensor(view_counts) else np.asarray(view_counts)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError("%s must be a flat list of at least one view count, got shape %s" % (what, tuple(a.shape)))
+    if a.dtype.kind not in "iu":
+        raise TypeError("%s must hold integers, got dtype %s" % (what, a.dtype))
+    bad = (a < min_views) | (a > 32)
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError("%s: sample %d has %d view%s, %d to 32 allowed" % (what, b, int(a[b]), "" if a[b] == 1 else "s", min_views))
+    total = int(a.sum())
+    if T is not None and total != T:
+        raise ValueError("%s sums to %d views over %d samples, the batch holds %d" % (what, total, a.size, T))
+    counts = np.ascontiguousarray(a.astype(np.int32))
+    base = np.zeros(counts.size + 1, np.int32)
+    np.cumsum(counts, out=base[1:])
+    top = int(counts.max())
+    return counts, base, (4 if top <= 4 else 8 if top <= 8 else 32)
+
+
+def _unproject_ragged_launch(feats_cl, P, cv, conf, method, view_base, nvcap):
+    """feats_cl (T,h,w,C) contiguous channels-last over the views of all samples -> (B,v0,v1,v2,C) channels-last, same dtype (lt_unproject_ragged_fwd).
+    view_base: (B + 1,) int32 device tensor."""
+    T, h, w, Cc = feats_cl.shape
+    B, v0, v1, v2 = cv.shape[:4]
+    out = torch.empty(B, v0, v1, v2, Cc, dtype=feats_cl.dtype, device=feats_cl.device)
+    H.check(H.lib().lt_unproject_ragged_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), view_base.data_ptr(),
+                                            out.data_ptr(), B, T, nvcap, Cc, h, w, v0, v1, v2, H.AGG["conf"] if conf is not None else H.AGG[method],
+                                            H.cur_stream()), "lt_unproject_ragged_fwd")
+    return out
+
+
 def _view_mask_device(view_mask, B, NV, device):
     """The mask as a (B, NV) uint8 device tensor for the masked entry points (a device tensor of the right form is used as it is)."""
     if torch.is_tensor(view_mask) and view_mask.is_cuda:
@@ -201,7 +237,7 @@ def indexed_bwd_workspace(P, NV, C, v0, v1, v2, chunk=None, cap=None):
 
 
 def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="sum", vol_confidences=None, view_mask=None,
-                       masked_backward=False, frame_index=None, indexed_backward=False):
+                       masked_backward=False, frame_index=None, indexed_backward=False, view_counts=None):
     """heatmaps (B,NV,C,h,w), proj_matricies (B,NV,3,4), coord_volumes (B,V0,V1,V2,3),
     vol_confidences (B,NV,C) for 'conf*' -> volumes (B,C,V0,V1,V2).  Reference: op.py:99-166.  Differentiable with respect to the
     heatmaps and the confidences (lt_unproject_bwd) whenever one of them requires grad.
@@ -222,9 +258,36 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
 
     indexed_backward=True opts into the differentiable indexed op (lt_unproject_indexed_bwd): what autograd derives for this function on the inputs
     gathered by frame_index -- a frame's heatmaps and confidences get the sum of its cuboids' gradients, a frame without a cuboid zeros.  Gather path
-    only (C a power of two <= 64); ignored without a frame_index.  A view_mask then needs masked_backward=True as well."""
+    only (C a power of two <= 64); ignored without a frame_index.  A view_mask then needs masked_backward=True as well.
+
+    view_counts: a ragged batch (lt_unproject_ragged_fwd), samples with different numbers of views and no padding.  heatmaps (T,C,h,w), proj_matricies
+    (T,3,4) and vol_confidences (T,C) hold the views of all samples, sample 0's first; view_counts the B counts (1..32 each, summing to T; a sequence, an
+    array or a tensor); coord_volumes (B,V0,V1,V2,3) -> volumes (B,C,V0,V1,V2): sample b is this function on its own views alone.  Inference only:
+    NotImplementedError when an input requires grad, and together with view_mask (drop the view from the batch instead) or frame_index."""
     if volume_aggregation_method not in _METHODS:
         raise ValueError("Unknown volume_aggregation_method: {}".format(volume_aggregation_method))
+    if view_counts is not None:
+        if view_mask is not None:
+            raise NotImplementedError("unproject_heatmaps: view_counts with view_mask; drop the missing views from the ragged batch instead of masking them")
+        if frame_index is not None:
+            raise NotImplementedError("unproject_heatmaps: view_counts with frame_index; gather each cuboid's views into the ragged batch instead")
+        if torch.is_grad_enabled() and (heatmaps.requires_grad or (torch.is_tensor(vol_confidences) and vol_confidences.requires_grad)):
+            raise NotImplementedError("unproject_heatmaps: view_counts is inference only (no ragged backward); call it under torch.no_grad(), or pad the "
+                                      "batch and train with view_mask and masked_backward=True")
+        if heatmaps.dim() != 4:
+            raise ValueError("unproject_heatmaps: with view_counts the heatmaps are (T, C, h, w), got %s" % (tuple(heatmaps.shape),))
+        counts, base, nvcap = view_counts_host(view_counts, heatmaps.shape[0])
+        if coord_volumes.shape[0] != counts.size:
+            raise ValueError("view_counts has %d entries, coord_volumes holds %d samples" % (counts.size, coord_volumes.shape[0]))
+        if tuple(proj_matricies.shape) != (heatmaps.shape[0], 3, 4):
+            raise ValueError("unproject_heatmaps: with view_counts proj_matricies are (T, 3, 4) = (%d, 3, 4), got %s" % (heatmaps.shape[0], tuple(proj_matricies.shape)))
+        H.require_gpu(heatmaps, "heatmaps")
+        H.dtype_code(heatmaps.dtype)
+        P = proj_matricies.to(heatmaps.device, torch.float32).contiguous()
+        cv = coord_volumes.to(heatmaps.device, torch.float32).contiguous()
+        conf = vol_confidences.to(heatmaps.device, torch.float32).contiguous() if volume_aggregation_method.startswith("conf") else None
+        vb = torch.from_numpy(base).to(heatmaps.device)
+        return _unproject_ragged_launch(_as_channels_last(heatmaps, 1), P, cv, conf, volume_aggregation_method, vb, nvcap).permute(0, 4, 1, 2, 3)
     indexed_grad = frame_index is not None and torch.is_grad_enabled() and (heatmaps.requires_grad or
                                                                               (torch.is_tensor(vol_confidences) and vol_confidences.requires_grad))
     if indexed_grad and not indexed_backward:
