@@ -284,7 +284,45 @@ int lt_rotate_points(const float* x, const float* rot, float* y, int64_t n, void
  * of the grid entries) are FINITE.  A NaN or infinite pixel coordinate gives a NaN sample in the reference's CPU
  * grid_sample and a zero sample in both kernels here (their in-range tests are float comparisons, which a NaN
  * fails); nobody should rely on either.  Feature maps may hold anything; only a masked view's map is never read.
+ *
+ * ONE operation, described by lt_unproject_desc; the variant is WHICH POINTERS ARE SET:
+ *   coords set                              the coordinate form: the voxel centres are read (pos, center, rot, coords_out NULL)
+ *   pos, center, rot, coords_out set        the grid form: the model's cuboid grid, v0 = v1 = v2 = V (coords NULL); see lt_unproject_grid_fwd
+ *   view_mask set                           over the valid views of every sample (lt_unproject_masked_fwd); NULL: every view is valid
+ *   frame_of set, F frames                  B cuboids over F frames (lt_unproject_indexed_fwd); view_mask, if set, is per frame
+ *   view_base set, T images                 a ragged batch, NV = NVcap (lt_unproject_ragged_fwd)
+ * Kernel instantiation: view_base -> ragged; else frame_of -> indexed (nullable mask); else view_mask -> masked; else plain.
+ * view_base together with view_mask or frame_of, and any backward with view_base, have no kernel: LT_ERR_UNSUPPORTED.  Both of coords and
+ * the cuboid set, or neither: LT_ERR_INVALID.  All checks precede any device work.
+ *   lt_unproject_desc_fwd            out: B,v0,v1,v2,C channels-last `dtype` (grid form: coords_out is written too)
+ *   lt_unproject_desc_bwd_workspace  host only: bytes for `items` samples (cuboids, with frame_of) walked at once; items = B: the whole batch,
+ *                                    items = 1: the least lt_unproject_desc_bwd takes; 0 where the gather does not take C.  The two layouts:
+ *                                    lt_unproject_bwd (plain, masked) and lt_unproject_indexed_bwd (frame_of) below
+ *   lt_unproject_desc_bwd            grad_out, grad_feats, grad_conf, the workspace and its chunked walk as lt_unproject_bwd / lt_unproject_indexed_bwd
+ *                                    below; in the grid form it reads the coords_out its forward wrote, so one descriptor serves both directions
+ * The eleven lt_unproject_*_fwd / *_bwd entries and the two workspace queries below are shorthands: each fills a descriptor and calls these.
  * -------------------------------------------------------------------------------------------*/
+typedef struct lt_unproject_desc {
+    int32_t dtype;
+    const void* feats;           /* B,NV,h,w,C (frame_of: F,NV,h,w,C; view_base: T,h,w,C) */
+    const float* proj;
+    const float* coords;         /* coordinate form: read; NULL in the grid form */
+    const float *pos, *center, *rot;   /* grid form: all set, with coords_out */
+    float step;
+    int32_t cmu_transfer;
+    float* coords_out;
+    const float* conf;           /* LT_AGG_CONF*: the confidences; else NULL */
+    const uint8_t* view_mask;    /* NULL: every view valid */
+    const int32_t* frame_of;     /* set: B cuboids over F frames */
+    int32_t F;
+    const int32_t* view_base;    /* set: ragged, T images in all, NV = NVcap */
+    int32_t T;
+    int32_t B, NV, C, h, w, v0, v1, v2, agg;
+} lt_unproject_desc;
+int lt_unproject_desc_fwd(const lt_unproject_desc* desc, void* out, void* stream);
+size_t lt_unproject_desc_bwd_workspace(const lt_unproject_desc* desc, int32_t items);
+int lt_unproject_desc_bwd(const lt_unproject_desc* desc, const float* grad_out, float* grad_feats, float* grad_conf, void* workspace,
+                          size_t workspace_bytes, void* stream);
 int lt_unproject_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf,
                      void* out, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1,
                      int32_t v2, int32_t agg, void* stream);
@@ -462,7 +500,8 @@ int lt_heatmap_mse_fwd(const float* pred, const float* points, const float* sigm
  * (mvn/models/loss.py:52-80; the reference walks samples and joints in Python with a .cpu() per sample), and the
  * batch statistics of training-mode BatchNorm.  All gradients are fp32.
  *
- * lt_unproject_bwd: grad_out B,v0,v1,v2,C (channels-last, fp32; the coordinate volume's grid shape) -> grad_feats B,NV,h,w,C fp32 (written
+ * lt_unproject_bwd (like lt_unproject_masked_bwd and lt_unproject_indexed_bwd below, a shorthand of lt_unproject_desc_bwd; the two workspace queries
+ *   are shorthands of lt_unproject_desc_bwd_workspace): grad_out B,v0,v1,v2,C (channels-last, fp32; the coordinate volume's grid shape) -> grad_feats B,NV,h,w,C fp32 (written
  *   completely, no pre-zeroing), grad_conf B,NV,C or NULL.  Autograd semantics of op.py:113-162: nothing flows to the grid / projections;
  *   depth <= 0 samples pass no gradient but their zero takes part in the view softmax, d out/d x_v = w_v (1 + x_v - out); 'max': the first
  *   maximal view.  Tie rule of 'max': the whole gradient of a voxel and channel goes to the LOWEST view index among the views whose sample equals

@@ -997,21 +997,21 @@ struct lt_plan {
         PL_TRY(alloc(B, V, V, V, 32, es, vol));
         const float step = (float)(cfg.cuboid_side / (double)(V - 1));          // float(np.float32(side / (V - 1))): the fp64 quotient rounded once
         {
-            const int dt = dtype, agg = cfg.aggregation, cmu = cfg.transfer_cmu_to_human36m ? 1 : 0, h = hm_h, w = hm_w;
-            const size_t op = o_pos, oc = o_cen, orr = o_rot, of = o_fof; lt_plan* self = this; const bool multi = P > 0; const int rT = T;
-            const void* fp = feats.p; float* cp = coords; void* vp = vol.p; const float* confp = volc.null() ? nullptr : (const float*)volc.p;
+            // everything of the descriptor that is fixed when the plan is built; the grid form, the variant by the pointers set when the op runs
+            lt_unproject_desc d0 = {};
+            d0.dtype = dtype; d0.feats = feats.p; d0.step = step; d0.cmu_transfer = cfg.transfer_cmu_to_human36m ? 1 : 0; d0.coords_out = coords;
+            d0.conf = volc.null() ? nullptr : (const float*)volc.p;
+            d0.F = F; d0.T = T; d0.B = B; d0.NV = NV; d0.C = 32; d0.h = hm_h; d0.w = hm_w; d0.v0 = d0.v1 = d0.v2 = V; d0.agg = cfg.aggregation;
+            const size_t op = o_pos, oc = o_cen, orr = o_rot, of = o_fof; lt_plan* self = this; const bool multi = P > 0; void* vp = vol.p;
             // the block's address is read when the op runs: a masked plan (lt_plan_set_view_mask, before the first forward) has moved it to a block with the mask behind
             ops.push_back([=](hipStream_t s) {
                 const float* gp = self->geo_dev;
-                if (rT)
-                    return lt_unproject_grid_ragged_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, (const int32_t*)(gp + of), vp, B, rT, NV, 32, h, w,
-                                                        V, agg, s);
-                if (multi)
-                    return lt_unproject_grid_indexed_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, self->masked ? self->mask_dev : nullptr,
-                                                         (const int32_t*)(gp + of), vp, F, B, NV, 32, h, w, V, agg, s);
-                if (self->masked)
-                    return lt_unproject_grid_masked_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, self->mask_dev, vp, B, NV, 32, h, w, V, agg, s);
-                return lt_unproject_grid_fwd(dt, fp, gp, gp + op, gp + oc, gp + orr, step, cmu, cp, confp, vp, B, NV, 32, h, w, V, agg, s);
+                lt_unproject_desc d = d0;
+                d.proj = gp; d.pos = gp + op; d.center = gp + oc; d.rot = gp + orr;
+                d.view_mask = self->masked ? self->mask_dev : nullptr;
+                if (d.T) d.view_base = (const int32_t*)(gp + of);
+                else if (multi) d.frame_of = (const int32_t*)(gp + of);
+                return lt_unproject_desc_fwd(&d, vp, s);
             });
         }
         PL_TRY(record_v2v(vol, logits));

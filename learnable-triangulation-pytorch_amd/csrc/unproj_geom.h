@@ -144,4 +144,14 @@ __device__ __forceinline__ Tap tap_of_record(int xy, const float4 k, int h, int 
     return t;
 }
 
+// Host side: the descriptor of the shorthand entries (lt_unproject_fwd, lt_unproject_bwd and their kin) -- the coordinate form, plain; a shorthand
+// then sets the pointers of its variant
+inline lt_unproject_desc unproject_coord_desc(int dtype, const void* feats, const float* proj, const float* coords, const float* conf, int B, int NV, int C,
+                                              int h, int w, int v0, int v1, int v2, int agg) {
+    lt_unproject_desc d = {};
+    d.dtype = dtype; d.feats = feats; d.proj = proj; d.coords = coords; d.conf = conf;
+    d.B = B; d.NV = NV; d.C = C; d.h = h; d.w = w; d.v0 = v0; d.v1 = v1; d.v2 = v2; d.agg = agg;
+    return d;
+}
+
 }  // namespace lt

@@ -620,52 +620,57 @@ int unproject_dispatch(UnprojRaggedArgs& a, int dtype, bool grid, hipStream_t st
     return launch_unproject<bf16_t, 1>(a, st);
 }
 
-// The cuboid of the grid entries (the voxel centres are computed from it and written to coords_out); the coordinate entries read `coords` and have none.
-struct UnprojCuboid {
-    const float *pos, *center, *rot;
-    float step;
-    int cmu;
-    float* coords_out;
-};
-
-// The frames of the indexed entries: cuboid p of the B reads frame frame_of[p] of the F.
-struct UnprojFrames {
-    const int32_t* frame_of;
-    int F;
-};
-
-// The views of the ragged entries: sample b reads rows view_base[b] .. view_base[b + 1] of the T; NV of the call is NVcap.
-struct UnprojRagged {
-    const int32_t* view_base;
-    int T;
-};
-
-// The one body behind the eight forward entries: `who` is the entry that was called, `cub` is set by the grid entries (v0 = v1 = v2 = V there),
-// `masked` by the masked ones and `frames` by the indexed ones (B = their P cuboids; their view_mask may be null).
-int unproject_forward(const char* who, int dtype, const void* feats, const float* proj, const float* coords, const UnprojCuboid* cub, const float* conf,
-                      bool masked, const uint8_t* view_mask, void* out, int B, int NV, int C, int h, int w, int v0, int v1, int v2, int agg, void* stream,
-                      const UnprojFrames* frames = nullptr, const UnprojRagged* ragged = nullptr) {
-    LT_REQUIRE(!ragged || ragged->view_base, LT_ERR_INVALID, "%s: null view_base", who);
-    LT_REQUIRE(!ragged || B >= 1, LT_ERR_INVALID, "%s: B %d samples", who, B);
-    LT_REQUIRE(!ragged || ragged->T >= 1, LT_ERR_INVALID, "%s: T %d images", who, ragged->T);
-    LT_REQUIRE(!ragged || (NV >= 1 && NV <= 32), LT_ERR_INVALID, "%s: NVcap %d (1..32)", who, NV);
-    LT_REQUIRE(!frames || frames->frame_of, LT_ERR_INVALID, "%s: null frame_of", who);
-    LT_REQUIRE(!frames || frames->F >= 1, LT_ERR_INVALID, "%s: F %d frames", who, frames->F);
-    LT_REQUIRE(!frames || B >= 1, LT_ERR_INVALID, "%s: P %d cuboids", who, B);
-    LT_REQUIRE(feats && proj && out && (cub ? cub->pos && cub->center && cub->rot && cub->coords_out : coords != nullptr), LT_ERR_INVALID, "%s: null argument", who);
-    LT_REQUIRE(!masked || view_mask, LT_ERR_INVALID, "%s: null view_mask", who);
-    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "%s: bad dtype %d", who, dtype);
-    LT_REQUIRE(agg >= LT_AGG_SUM && agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "%s: unknown aggregation %d", who, agg);
-    LT_REQUIRE((agg != LT_AGG_CONF && agg != LT_AGG_CONF_NORM) || conf, LT_ERR_INVALID, "%s: LT_AGG_CONF* needs confidences", who);
-    LT_REQUIRE(B >= 1 && NV >= 1 && C >= 1 && h >= 2 && w >= 2 && (cub ? v0 >= 2 : v0 >= 1 && v1 >= 1 && v2 >= 1), LT_ERR_INVALID, "%s: bad shape", who);
-    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
+// The one body behind lt_unproject_desc_fwd and its eight shorthands: `who` is the entry that was called.  The variant is which pointers of d are set
+// (include/lt_hip.h); unproject_dispatch picks the instantiation from the same pointers.
+int unproject_forward(const char* who, const lt_unproject_desc& d, void* out, void* stream) {
+    const bool cuboid_any = d.pos || d.center || d.rot || d.coords_out, grid = !d.coords;
+    LT_REQUIRE(!d.view_base || !(d.view_mask || d.frame_of), LT_ERR_UNSUPPORTED, "%s: view_base with %s has no kernel (a ragged batch takes neither a view mask nor a frame index)",
+               who, d.view_mask ? "view_mask" : "frame_of");
+    LT_REQUIRE(!d.view_base || d.B >= 1, LT_ERR_INVALID, "%s: B %d samples", who, d.B);
+    LT_REQUIRE(!d.view_base || d.T >= 1, LT_ERR_INVALID, "%s: T %d images", who, d.T);
+    LT_REQUIRE(!d.view_base || (d.NV >= 1 && d.NV <= 32), LT_ERR_INVALID, "%s: NVcap %d (1..32)", who, d.NV);
+    LT_REQUIRE(!d.frame_of || d.F >= 1, LT_ERR_INVALID, "%s: F %d frames", who, d.F);
+    LT_REQUIRE(!d.frame_of || d.B >= 1, LT_ERR_INVALID, "%s: P %d cuboids", who, d.B);
+    LT_REQUIRE(!(d.coords && cuboid_any), LT_ERR_INVALID, "%s: both coords and the cuboid (pos, center, rot, coords_out) are set", who);
+    LT_REQUIRE(d.coords || cuboid_any, LT_ERR_INVALID, "%s: null argument (neither coords nor the cuboid pos, center, rot, coords_out is set)", who);
+    LT_REQUIRE(d.feats && d.proj && out && (!grid || (d.pos && d.center && d.rot && d.coords_out)), LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(d.dtype == LT_F32 || d.dtype == LT_BF16, LT_ERR_INVALID, "%s: bad dtype %d", who, d.dtype);
+    LT_REQUIRE(d.agg >= LT_AGG_SUM && d.agg <= LT_AGG_CONF_NORM, LT_ERR_INVALID, "%s: unknown aggregation %d", who, d.agg);
+    LT_REQUIRE((d.agg != LT_AGG_CONF && d.agg != LT_AGG_CONF_NORM) || d.conf, LT_ERR_INVALID, "%s: LT_AGG_CONF* needs confidences", who);
+    LT_REQUIRE(d.B >= 1 && d.NV >= 1 && d.C >= 1 && d.h >= 2 && d.w >= 2 && (grid ? d.v0 >= 2 && d.v1 == d.v0 && d.v2 == d.v0 : d.v0 >= 1 && d.v1 >= 1 && d.v2 >= 1),
+               LT_ERR_INVALID, "%s: bad shape", who);
+    LT_REQUIRE((long long)d.NV * d.h * d.w * d.C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
     UnprojRaggedArgs a = {};
-    if (frames) { a.frame_of = frames->frame_of; a.F = frames->F; }
-    if (ragged) { a.view_base = ragged->view_base; a.T = ragged->T; }
-    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.out = out; a.mask = (masked || frames) ? view_mask : nullptr;
-    a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.v0 = v0; a.v1 = v1; a.v2 = v2; a.agg = agg;
-    if (cub) { a.g_pos = cub->pos; a.g_center = cub->center; a.g_rot = cub->rot; a.g_step = cub->step; a.g_cmu = cub->cmu; a.coords_out = cub->coords_out; }
-    return unproject_dispatch(a, dtype, cub != nullptr, (hipStream_t)stream);
+    a.frame_of = d.frame_of; a.F = d.frame_of ? d.F : 0;
+    a.view_base = d.view_base; a.T = d.view_base ? d.T : 0;
+    a.feats = d.feats; a.proj = d.proj; a.coords = d.coords; a.conf = d.conf; a.out = out; a.mask = d.view_mask;
+    a.B = d.B; a.NV = d.NV; a.C = d.C; a.h = d.h; a.w = d.w; a.v0 = d.v0; a.v1 = d.v1; a.v2 = d.v2; a.agg = d.agg;
+    if (grid) { a.g_pos = d.pos; a.g_center = d.center; a.g_rot = d.rot; a.g_step = d.step; a.g_cmu = d.cmu_transfer; a.coords_out = d.coords_out; }
+    return unproject_dispatch(a, d.dtype, grid, (hipStream_t)stream);
+}
+
+// the grid shorthands' descriptor (V cubed), plain; unproject_coord_desc (unproj_geom.h) is the coordinate shorthands'
+lt_unproject_desc grid_desc(int dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot, float step, int cmu,
+                            float* coords_out, const float* conf, int B, int NV, int C, int h, int w, int V, int agg) {
+    lt_unproject_desc d = unproject_coord_desc(dtype, feats, proj, nullptr, conf, B, NV, C, h, w, V, V, V, agg);
+    d.pos = pos; d.center = center; d.rot = rot; d.step = step; d.cmu_transfer = cmu; d.coords_out = coords_out;
+    return d;
+}
+// what is an error for a shorthand but a variant for the descriptor: the null pointer of the shorthand's own variant
+int masked_forward(const char* who, lt_unproject_desc d, const uint8_t* view_mask, void* out, void* stream) {
+    LT_REQUIRE(view_mask, LT_ERR_INVALID, "%s: null view_mask", who);
+    d.view_mask = view_mask;
+    return unproject_forward(who, d, out, stream);
+}
+int indexed_forward(const char* who, lt_unproject_desc d, const uint8_t* view_mask, const int32_t* frame_of, int F, void* out, void* stream) {
+    LT_REQUIRE(frame_of, LT_ERR_INVALID, "%s: null frame_of", who);
+    d.view_mask = view_mask; d.frame_of = frame_of; d.F = F;
+    return unproject_forward(who, d, out, stream);
+}
+int ragged_forward(const char* who, lt_unproject_desc d, const int32_t* view_base, int T, void* out, void* stream) {
+    LT_REQUIRE(view_base, LT_ERR_INVALID, "%s: null view_base", who);
+    d.view_base = view_base; d.T = T;
+    return unproject_forward(who, d, out, stream);
 }
 
 }  // namespace
@@ -676,65 +681,63 @@ extern "C" int lt_coord_volumes(const float* pos, const float* center, const flo
     return launch_coord_volumes("lt_coord_volumes", pos, center, rot, step, B, V, cmu_transfer, coords, (hipStream_t)stream);
 }
 
+extern "C" int lt_unproject_desc_fwd(const lt_unproject_desc* desc, void* out, void* stream) {
+    LT_REQUIRE(desc, LT_ERR_INVALID, "lt_unproject_desc_fwd: null descriptor");
+    return unproject_forward("lt_unproject_desc_fwd", *desc, out, stream);
+}
+
 extern "C" int lt_unproject_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf,
                                 void* out, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1,
                                 int32_t v2, int32_t agg, void* stream) {
-    return unproject_forward("lt_unproject_fwd", dtype, feats, proj, coords, nullptr, conf, false, nullptr, out, B, NV, C, h, w, v0, v1, v2, agg, stream);
+    return unproject_forward("lt_unproject_fwd", unproject_coord_desc(dtype, feats, proj, coords, conf, B, NV, C, h, w, v0, v1, v2, agg), out, stream);
 }
 
 extern "C" int lt_unproject_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
                                        void* out, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2, int32_t agg,
                                        void* stream) {
-    return unproject_forward("lt_unproject_masked_fwd", dtype, feats, proj, coords, nullptr, conf, true, view_mask, out, B, NV, C, h, w, v0, v1, v2, agg, stream);
+    return masked_forward("lt_unproject_masked_fwd", unproject_coord_desc(dtype, feats, proj, coords, conf, B, NV, C, h, w, v0, v1, v2, agg), view_mask, out, stream);
 }
 
 extern "C" int lt_unproject_grid_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                                      float step, int32_t cmu_transfer, float* coords_out, const float* conf, void* out, int32_t B, int32_t NV,
                                      int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream) {
-    const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
-    return unproject_forward("lt_unproject_grid_fwd", dtype, feats, proj, nullptr, &cub, conf, false, nullptr, out, B, NV, C, h, w, V, V, V, agg, stream);
+    return unproject_forward("lt_unproject_grid_fwd", grid_desc(dtype, feats, proj, pos, center, rot, step, cmu_transfer, coords_out, conf, B, NV, C, h, w, V, agg),
+                             out, stream);
 }
 
 extern "C" int lt_unproject_grid_masked_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                                             float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask, void* out,
                                             int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream) {
-    const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
-    return unproject_forward("lt_unproject_grid_masked_fwd", dtype, feats, proj, nullptr, &cub, conf, true, view_mask, out, B, NV, C, h, w, V, V, V, agg, stream);
+    return masked_forward("lt_unproject_grid_masked_fwd", grid_desc(dtype, feats, proj, pos, center, rot, step, cmu_transfer, coords_out, conf, B, NV, C, h, w, V, agg),
+                          view_mask, out, stream);
 }
 
 extern "C" int lt_unproject_indexed_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
                                         const int32_t* frame_of, void* out, int32_t F, int32_t P, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0,
                                         int32_t v1, int32_t v2, int32_t agg, void* stream) {
-    const UnprojFrames frames = {frame_of, F};
-    return unproject_forward("lt_unproject_indexed_fwd", dtype, feats, proj, coords, nullptr, conf, false, view_mask, out, P, NV, C, h, w, v0, v1, v2, agg, stream,
-                             &frames);
+    return indexed_forward("lt_unproject_indexed_fwd", unproject_coord_desc(dtype, feats, proj, coords, conf, P, NV, C, h, w, v0, v1, v2, agg), view_mask, frame_of, F, out,
+                           stream);
 }
 
 extern "C" int lt_unproject_grid_indexed_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                                              float step, int32_t cmu_transfer, float* coords_out, const float* conf, const uint8_t* view_mask,
                                              const int32_t* frame_of, void* out, int32_t F, int32_t P, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t V,
                                              int32_t agg, void* stream) {
-    const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
-    const UnprojFrames frames = {frame_of, F};
-    return unproject_forward("lt_unproject_grid_indexed_fwd", dtype, feats, proj, nullptr, &cub, conf, false, view_mask, out, P, NV, C, h, w, V, V, V, agg, stream,
-                             &frames);
+    return indexed_forward("lt_unproject_grid_indexed_fwd", grid_desc(dtype, feats, proj, pos, center, rot, step, cmu_transfer, coords_out, conf, P, NV, C, h, w, V, agg),
+                           view_mask, frame_of, F, out, stream);
 }
 
 extern "C" int lt_unproject_ragged_fwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const int32_t* view_base,
                                        void* out, int32_t B, int32_t T, int32_t NVcap, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2,
                                        int32_t agg, void* stream) {
-    const UnprojRagged ragged = {view_base, T};
-    return unproject_forward("lt_unproject_ragged_fwd", dtype, feats, proj, coords, nullptr, conf, false, nullptr, out, B, NVcap, C, h, w, v0, v1, v2, agg, stream,
-                             nullptr, &ragged);
+    return ragged_forward("lt_unproject_ragged_fwd", unproject_coord_desc(dtype, feats, proj, coords, conf, B, NVcap, C, h, w, v0, v1, v2, agg), view_base, T, out, stream);
 }
 
 extern "C" int lt_unproject_grid_ragged_fwd(int32_t dtype, const void* feats, const float* proj, const float* pos, const float* center, const float* rot,
                                             float step, int32_t cmu_transfer, float* coords_out, const float* conf, const int32_t* view_base, void* out,
                                             int32_t B, int32_t T, int32_t NVcap, int32_t C, int32_t h, int32_t w, int32_t V, int32_t agg, void* stream) {
-    const UnprojCuboid cub = {pos, center, rot, step, cmu_transfer, coords_out};
-    const UnprojRagged ragged = {view_base, T};
-    return unproject_forward("lt_unproject_grid_ragged_fwd", dtype, feats, proj, nullptr, &cub, conf, false, nullptr, out, B, NVcap, C, h, w, V, V, V, agg, stream,
-                             nullptr, &ragged);
+    return ragged_forward("lt_unproject_grid_ragged_fwd", grid_desc(dtype, feats, proj, pos, center, rot, step, cmu_transfer, coords_out, conf, B, NVcap, C, h, w, V, agg),
+                          view_base, T, out, stream);
 }
 
 namespace {

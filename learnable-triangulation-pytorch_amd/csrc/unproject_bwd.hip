@@ -952,20 +952,25 @@ __global__ __launch_bounds__(256) void unproj_gather_kernel(const std::condition
     }
 }
 
-template <int CW>
-int launch_gather(const UnprojBwdArgs& c, int tiles, int NV, int nb, hipStream_t st) {
-    LT_OPT_IN_LDS(unproj_gather_kernel<CW>, 160 * 1024);
-    hipLaunchKernelGGL(unproj_gather_kernel<CW>, dim3((unsigned)tiles, (unsigned)NV, (unsigned)nb), dim3(256), GatherCfg<CW>::LDS, st, c);
-    LT_CHECK_LAUNCH("lt_unproject_bwd(gather)");
+// K2 of one chunk: one workgroup per (tile, view, sample of the chunk); INDEXED: per (tile, view, FRAME), over the m.B cuboids of the chunk.  The
+// unindexed kernel receives a plain UnprojBwdArgs by value (the base of m), as in launch_taps_dx.
+template <int CW, bool INDEXED>
+int launch_gather(const UnprojBwdIndexedArgs& m, int tiles, hipStream_t st) {
+    const std::conditional_t<INDEXED, UnprojBwdIndexedArgs, UnprojBwdArgs>& c = m;
+    LT_OPT_IN_LDS((unproj_gather_kernel<CW, INDEXED>), 160 * 1024);
+    hipLaunchKernelGGL((unproj_gather_kernel<CW, INDEXED>), dim3((unsigned)tiles, (unsigned)m.NV, (unsigned)(INDEXED ? m.F : m.B)), dim3(256), GatherCfg<CW>::LDS, st, c);
+    LT_CHECK_LAUNCH(INDEXED ? "lt_unproject_indexed_bwd(gather)" : "lt_unproject_bwd(gather)");
     return LT_OK;
 }
-// the indexed instantiation: one workgroup per (tile, view, FRAME), over the c.B cuboids of the chunk
-template <int CW>
-int launch_gather_indexed(const UnprojBwdIndexedArgs& c, int tiles, hipStream_t st) {
-    LT_OPT_IN_LDS((unproj_gather_kernel<CW, true>), 160 * 1024);
-    hipLaunchKernelGGL((unproj_gather_kernel<CW, true>), dim3((unsigned)tiles, (unsigned)c.NV, (unsigned)c.F), dim3(256), GatherCfg<CW>::LDS, st, c);
-    LT_CHECK_LAUNCH("lt_unproject_indexed_bwd(gather)");
-    return LT_OK;
+template <bool INDEXED>
+int launch_gather_c(const UnprojBwdIndexedArgs& m, int tiles, hipStream_t st) {
+    switch (m.C / 4) {                                            // K2 as it is: a masked view has no brick to walk and stores zeros
+        case 1: return launch_gather<1, INDEXED>(m, tiles, st);
+        case 2: return launch_gather<2, INDEXED>(m, tiles, st);
+        case 4: return launch_gather<4, INDEXED>(m, tiles, st);
+        case 8: return launch_gather<8, INDEXED>(m, tiles, st);
+        default: return launch_gather<16, INDEXED>(m, tiles, st);
+    }
 }
 
 int blocks_k1(long long nvox, int C) {
@@ -1014,41 +1019,77 @@ int launch_taps_dx(const char* who, const UnprojBwdIndexedArgs& m, int dtype, in
     return LT_OK;
 }
 
-// The one body behind lt_unproject_bwd and lt_unproject_masked_bwd: `who` is the entry that was called, `masked` says which
-int unproject_backward(const char* who, bool masked, int dtype, const void* feats, const float* proj, const float* coords, const float* conf,
-                       const uint8_t* view_mask, const float* grad_out, float* grad_feats, float* grad_conf, int B, int NV, int C, int h, int w, int v0,
-                       int v1, int v2, int agg, void* workspace, size_t workspace_bytes, void* stream) {
-    LT_REQUIRE(feats && proj && coords && grad_out && grad_feats, LT_ERR_INVALID, "%s: null argument", who);
-    LT_REQUIRE(!masked || view_mask, LT_ERR_INVALID, "%s: null view_mask", who);
+// The gather's workspace, both layouts (their byte counts: include/lt_hip.h); bytes = fixed + per_item * the items walked at once:
+//   plain, masked  [dxs | bbox | gcpart | tw | txy], each block one chunk of samples long: a sample's share includes its fp64 confidence partials,
+//                  which are finalized per chunk
+//   indexed        [gcpart of ALL P cuboids, dense (P, nblk1, NV, C), rounded up to 256 in all][dxs | bbox | tw | txy], each block one chunk of cuboids
+//                  long: the finalizer runs once, over every chunk's partials
+struct BwdWs {
+    size_t s_dx, s_bb, s_gc, s_xy, s_tw;                          // one item's blocks, each rounded up to 256
+    size_t fixed, per_item;
+    int nblk1;
+};
+BwdWs bwd_ws(bool indexed, int P, int NV, int C, int v0, int v1, int v2) {
+    const long long nvox = (long long)v0 * v1 * v2;
+    const long long nbricks = cdiv(v0, 4) * cdiv(v1, 4) * cdiv(v2, 4);
+    BwdWs s;
+    s.nblk1 = blocks_k1(nvox, C);
+    const size_t gc = (size_t)s.nblk1 * NV * C * 8;              // one item's partials
+    s.s_dx = align256((size_t)NV * nvox * C * 4); s.s_bb = align256((size_t)NV * nbricks * 16); s.s_gc = align256(gc);
+    s.s_xy = align256((size_t)NV * nvox * 4); s.s_tw = align256((size_t)NV * nvox * 16);
+    s.fixed = indexed ? align256(gc * (size_t)P) : 0;
+    s.per_item = s.s_dx + s.s_bb + s.s_xy + s.s_tw + (indexed ? 0 : s.s_gc);
+    return s;
+}
+// the three workspace queries: 0 where there is nothing to walk or the gather does not take C
+size_t bwd_ws_bytes(bool indexed, int P, int items, int NV, int C, int v0, int v1, int v2) {
+    if (P < 1 || items < 1 || NV < 1 || C < 4 || v0 < 1 || v1 < 1 || v2 < 1 || !gather_takes(C)) return 0;
+    const BwdWs s = bwd_ws(indexed, P, NV, C, v0, v1, v2);
+    return s.fixed + s.per_item * (size_t)(items < P ? items : P);
+}
+
+// The one body behind lt_unproject_desc_bwd and its three shorthands: `who` is the entry that was called.  d.frame_of set: the indexed walk (d.B cuboids
+// over d.F frames, on the nullable-mask instantiations); else d.view_mask set: the masked instantiations; else the plain ones, on their own argument block.
+int unproject_backward(const char* who, const lt_unproject_desc& d, const float* grad_out, float* grad_feats, float* grad_conf, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    const bool indexed = d.frame_of != nullptr, masked = !indexed && d.view_mask;
+    const char* const form = indexed ? "indexed" : "masked";      // the variants the scatter does not have, and what each takes
+    const char* const takes = indexed ? "frame index" : "view mask";
+    const float* coords = d.coords ? d.coords : d.coords_out;     // grid form: the voxel centres its forward wrote
+    const int dtype = d.dtype, B = d.B, NV = d.NV, C = d.C, h = d.h, w = d.w, agg = d.agg;
+    LT_REQUIRE(!d.view_base, LT_ERR_UNSUPPORTED, "%s: view_base has no backward (a ragged batch is inference only)", who);
+    LT_REQUIRE(!(d.coords && (d.pos || d.center || d.rot || d.coords_out)), LT_ERR_INVALID, "%s: both coords and the cuboid (pos, center, rot, coords_out) are set", who);
+    LT_REQUIRE(d.feats && d.proj && coords && grad_out && grad_feats, LT_ERR_INVALID, "%s: null argument", who);
+    LT_REQUIRE(!indexed || (d.F >= 1 && B >= 1), LT_ERR_INVALID, "%s: needs F >= 1 frames and P >= 1 cuboids (got F=%d P=%d)", who, d.F, B);
     LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "%s: bad dtype %d", who, dtype);
     LT_REQUIRE(agg == LT_AGG_SUM || agg == LT_AGG_MAX || agg == LT_AGG_SOFTMAX || agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM, LT_ERR_UNSUPPORTED,
                "%s: unknown aggregation %d", who, agg);
     const bool is_conf = agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM;
-    LT_REQUIRE(!is_conf || conf, LT_ERR_INVALID, "%s: the conf aggregations need confidences", who);
-    LT_REQUIRE(B >= 1 && NV >= 1 && NV <= UB_MANYV && C >= 4 && C % 4 == 0 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_UNSUPPORTED,
+    LT_REQUIRE(!is_conf || d.conf, LT_ERR_INVALID, "%s: the conf aggregations need confidences", who);
+    LT_REQUIRE(B >= 1 && NV >= 1 && NV <= UB_MANYV && C >= 4 && C % 4 == 0 && h >= 2 && w >= 2 && d.v0 >= 1 && d.v1 >= 1 && d.v2 >= 1, LT_ERR_UNSUPPORTED,
                "%s: needs 1 <= NV <= %d and C %% 4 == 0 (got NV=%d C=%d)", who, UB_MANYV, NV, C);
     LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
-    if (masked) {                                              // there is no masked scatter
+    LT_REQUIRE(!indexed || d.F <= 65535, LT_ERR_UNSUPPORTED, "%s: at most 65535 frames (the gather's grid), got %d", who, d.F);
+    if (indexed || masked) {                                      // there is no masked and no indexed scatter
         LT_REQUIRE(!env_on("LT_UNPROJ_BWD_ATOMICS"), LT_ERR_UNSUPPORTED,
-                   "%s: LT_UNPROJ_BWD_ATOMICS selects the scatter path, which has no masked form (only the gather takes a view mask)", who);
+                   "%s: LT_UNPROJ_BWD_ATOMICS selects the scatter path, which has no %s form (only the gather takes a %s)", who, form, takes);
         LT_REQUIRE(gather_takes(C), LT_ERR_UNSUPPORTED,
-                   "%s: only the gather path takes a view mask, and it needs C a power of two <= 64 (got C=%d; the scatter has no masked form)", who, C);
+                   "%s: only the gather path takes a %s, and it needs C a power of two <= 64 (got C=%d; the scatter has no %s form)", who, takes, C, form);
     }
     hipStream_t st = (hipStream_t)stream;
     UnprojBwdIndexedArgs a;
-    a.frame_of = nullptr; a.F = B; a.P = B; a.p0 = 0;
-    a.mask = masked ? view_mask : nullptr;
-    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.gout = grad_out; a.gfeats = grad_feats; a.gconf = is_conf ? grad_conf : nullptr;
+    a.frame_of = d.frame_of; a.F = indexed ? d.F : B; a.P = B; a.p0 = 0;
+    a.mask = d.view_mask;
+    a.feats = d.feats; a.proj = d.proj; a.coords = coords; a.conf = d.conf; a.gout = grad_out; a.gfeats = grad_feats; a.gconf = is_conf ? grad_conf : nullptr;
     a.dxs = nullptr; a.bbox = nullptr; a.gcpart = nullptr; a.txy = nullptr; a.tw = nullptr;
     a.B = B; a.NV = NV; a.C = C; a.h = h; a.w = w; a.agg = agg;
-    a.v0 = v0; a.v1 = v1; a.v2 = v2; a.nb0 = (int)cdiv(v0, 4); a.nb1 = (int)cdiv(v1, 4); a.nb2 = (int)cdiv(v2, 4);
-    a.nvox = (long long)v0 * v1 * v2;
-    const size_t fbytes = (size_t)NV * h * w * C * 4;
+    a.v0 = d.v0; a.v1 = d.v1; a.v2 = d.v2; a.nb0 = (int)cdiv(d.v0, 4); a.nb1 = (int)cdiv(d.v1, 4); a.nb2 = (int)cdiv(d.v2, 4);
+    a.nvox = (long long)d.v0 * d.v1 * d.v2;
     if (!gather_takes(C)) {
-        // round-2 scatter: global float atomics into zeroed buffers (not bitwise repeatable); unmasked only (refused above otherwise)
+        // round-2 scatter: global float atomics into zeroed buffers (not bitwise repeatable); the plain variant only (refused above otherwise)
         const UnprojBwdArgs& u = a;
         LT_REQUIRE(agg != LT_AGG_CONF_NORM, LT_ERR_UNSUPPORTED, "%s: conf_norm needs the gather path (C a power of two <= 64)", who);
-        LT_REQUIRE(hipMemsetAsync(grad_feats, 0, fbytes * B, st) == hipSuccess, LT_ERR_LAUNCH, "%s: hipMemsetAsync failed", who);
+        LT_REQUIRE(hipMemsetAsync(grad_feats, 0, (size_t)B * NV * h * w * C * 4, st) == hipSuccess, LT_ERR_LAUNCH, "%s: hipMemsetAsync failed", who);
         if (a.gconf) LT_REQUIRE(hipMemsetAsync(a.gconf, 0, (size_t)B * NV * C * 4, st) == hipSuccess, LT_ERR_LAUNCH, "%s: hipMemsetAsync failed", who);
         const long long blocks = cdiv(a.nvox * (C / 4), 256);
         dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)B);
@@ -1061,165 +1102,104 @@ int unproject_backward(const char* who, bool masked, int dtype, const void* feat
         return LT_OK;
     }
     const int nbricks = a.nb0 * a.nb1 * a.nb2;
-    const int nblk1 = blocks_k1(a.nvox, C);
-    const size_t s_dx = align256((size_t)NV * a.nvox * C * 4), s_bb = align256((size_t)NV * nbricks * 16), s_gc = align256((size_t)nblk1 * NV * C * 8);
-    const size_t s_xy = align256((size_t)NV * a.nvox * 4), s_tw = align256((size_t)NV * a.nvox * 16);
-    const size_t per_sample = s_dx + s_bb + s_gc + s_xy + s_tw;
-    LT_REQUIRE(workspace && workspace_bytes >= per_sample && ((size_t)workspace % 16) == 0, LT_ERR_INVALID,
-               "%s: workspace of at least %zu bytes (one sample; lt_unproject_bwd_workspace for the whole batch), 16-byte aligned", who, per_sample);
-    const int chunk = (int)(workspace_bytes / per_sample < (size_t)B ? workspace_bytes / per_sample : (size_t)B);
+    const BwdWs s = bwd_ws(indexed, B, NV, C, d.v0, d.v1, d.v2);
+    const bool ws_ok = workspace && workspace_bytes >= s.fixed + s.per_item && ((size_t)workspace % 16) == 0;
+    if (indexed)
+        LT_REQUIRE(ws_ok, LT_ERR_INVALID,
+                   "%s: workspace of at least %zu bytes (the confidence partials of all %d cuboids and one cuboid's share of the rest; "
+                   "lt_unproject_indexed_bwd_workspace for all cuboids at once), 16-byte aligned", who, s.fixed + s.per_item, B);
+    LT_REQUIRE(ws_ok, LT_ERR_INVALID, "%s: workspace of at least %zu bytes (one sample; lt_unproject_bwd_workspace for the whole batch), 16-byte aligned", who,
+               s.per_item);
+    const size_t fit = (workspace_bytes - s.fixed) / s.per_item;
+    const size_t cap = indexed && B > 65535 ? 65535 : (size_t)B;  // indexed: K0 and K1 take the chunk's cuboids as grid y
+    const int chunk = (int)(fit < cap ? fit : cap);
     const int tiles = (int)(cdiv(w, G_TW) * cdiv(h, G_TH));
     const size_t in_elt = dtype == LT_F32 ? 4 : 2;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
         UnprojBwdIndexedArgs c = a;
         c.B = nb;
-        c.feats = (const char*)feats + (size_t)b0 * NV * h * w * C * in_elt;
-        c.proj = proj + (size_t)b0 * NV * 12;
         c.coords = coords + (size_t)b0 * a.nvox * 3;
-        c.conf = conf ? conf + (size_t)b0 * NV * C : nullptr;
-        c.mask = a.mask ? a.mask + (size_t)b0 * NV : nullptr;
         c.gout = grad_out + (size_t)b0 * a.nvox * C;
-        c.gfeats = grad_feats + (size_t)b0 * NV * h * w * C;
-        c.gconf = a.gconf ? a.gconf + (size_t)b0 * NV * C : nullptr;
-        char* wsp = (char*)workspace;
-        c.dxs = (float*)wsp; wsp += s_dx * nb;
-        c.bbox = (int*)wsp; wsp += s_bb * nb;
-        c.gcpart = (double*)wsp; wsp += s_gc * nb;
-        c.tw = (float4*)wsp; wsp += s_tw * nb;
-        c.txy = (int*)wsp;
-        int rc = masked ? launch_taps_dx<true>(who, c, dtype, nbricks, nblk1, st) : launch_taps_dx<false>(who, c, dtype, nbricks, nblk1, st);
-        if (rc != LT_OK) return rc;
-        switch (C / 4) {                                          // K2 as it is: a masked view has no brick to walk and stores zeros
-            case 1: rc = launch_gather<1>(c, tiles, NV, nb, st); break;
-            case 2: rc = launch_gather<2>(c, tiles, NV, nb, st); break;
-            case 4: rc = launch_gather<4>(c, tiles, NV, nb, st); break;
-            case 8: rc = launch_gather<8>(c, tiles, NV, nb, st); break;
-            default: rc = launch_gather<16>(c, tiles, NV, nb, st); break;
-        }
-        if (rc != LT_OK) return rc;
-    }
-    return LT_OK;
-}
-
-// lt_unproject_indexed_bwd's workspace: [fp64 confidence partials of ALL P cuboids (the finalizer runs once, over every chunk's partials)]
-// [dxs | bbox | tw | txy of one chunk of cuboids]
-struct IndexedWs {
-    size_t s_dx, s_bb, gc, s_xy, s_tw;                            // gc: one cuboid's partials, nblk1 * NV * C * 8 bytes (dense over the cuboids)
-    size_t per_cuboid() const { return s_dx + s_bb + s_xy + s_tw; }
-    size_t gc_all(int P) const { return align256(gc * (size_t)P); }
-};
-IndexedWs indexed_ws(int NV, int C, int v0, int v1, int v2) {
-    const long long nvox = (long long)v0 * v1 * v2;
-    const long long nbricks = cdiv(v0, 4) * cdiv(v1, 4) * cdiv(v2, 4);
-    IndexedWs s;
-    s.s_dx = align256((size_t)NV * nvox * C * 4); s.s_bb = align256((size_t)NV * nbricks * 16); s.gc = (size_t)blocks_k1(nvox, C) * NV * C * 8;
-    s.s_xy = align256((size_t)NV * nvox * 4); s.s_tw = align256((size_t)NV * nvox * 16);
-    return s;
-}
-
-}  // namespace
-
-extern "C" size_t lt_unproject_indexed_bwd_workspace(int32_t P, int32_t NV, int32_t C, int32_t v0, int32_t v1, int32_t v2) {
-    if (P < 1 || NV < 1 || C < 4 || v0 < 1 || v1 < 1 || v2 < 1 || !gather_takes(C)) return 0;
-    const IndexedWs s = indexed_ws(NV, C, v0, v1, v2);
-    return s.gc_all(P) + s.per_cuboid() * (size_t)P;
-}
-
-extern "C" int lt_unproject_indexed_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
-                                        const int32_t* frame_of, const float* grad_out, float* grad_feats, float* grad_conf, int32_t F, int32_t P, int32_t NV,
-                                        int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2, int32_t agg, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-    const char* who = "lt_unproject_indexed_bwd";
-    LT_REQUIRE(feats && proj && coords && grad_out && grad_feats, LT_ERR_INVALID, "%s: null argument", who);
-    LT_REQUIRE(frame_of, LT_ERR_INVALID, "%s: null frame_of", who);
-    LT_REQUIRE(F >= 1 && P >= 1, LT_ERR_INVALID, "%s: needs F >= 1 frames and P >= 1 cuboids (got F=%d P=%d)", who, F, P);
-    LT_REQUIRE(dtype == LT_F32 || dtype == LT_BF16, LT_ERR_INVALID, "%s: bad dtype %d", who, dtype);
-    LT_REQUIRE(agg == LT_AGG_SUM || agg == LT_AGG_MAX || agg == LT_AGG_SOFTMAX || agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM, LT_ERR_UNSUPPORTED,
-               "%s: unknown aggregation %d", who, agg);
-    const bool is_conf = agg == LT_AGG_CONF || agg == LT_AGG_CONF_NORM;
-    LT_REQUIRE(!is_conf || conf, LT_ERR_INVALID, "%s: the conf aggregations need confidences", who);
-    LT_REQUIRE(NV >= 1 && NV <= UB_MANYV && C >= 4 && C % 4 == 0 && h >= 2 && w >= 2 && v0 >= 1 && v1 >= 1 && v2 >= 1, LT_ERR_UNSUPPORTED,
-               "%s: needs 1 <= NV <= %d and C %% 4 == 0 (got NV=%d C=%d)", who, UB_MANYV, NV, C);
-    LT_REQUIRE((long long)NV * h * w * C < (1ll << 31), LT_ERR_UNSUPPORTED, "%s: feature maps too large", who);
-    LT_REQUIRE(F <= 65535, LT_ERR_UNSUPPORTED, "%s: at most 65535 frames (the gather's grid), got %d", who, F);
-    LT_REQUIRE(!env_on("LT_UNPROJ_BWD_ATOMICS"), LT_ERR_UNSUPPORTED,
-               "%s: LT_UNPROJ_BWD_ATOMICS selects the scatter path, which has no indexed form (only the gather takes a frame index)", who);
-    LT_REQUIRE(gather_takes(C), LT_ERR_UNSUPPORTED,
-               "%s: only the gather path takes a frame index, and it needs C a power of two <= 64 (got C=%d; the scatter has no indexed form)", who, C);
-    hipStream_t st = (hipStream_t)stream;
-    UnprojBwdIndexedArgs a;
-    a.frame_of = frame_of; a.F = F; a.P = P; a.p0 = 0;
-    a.mask = view_mask;
-    a.feats = feats; a.proj = proj; a.coords = coords; a.conf = conf; a.gout = grad_out; a.gfeats = grad_feats; a.gconf = is_conf ? grad_conf : nullptr;
-    a.dxs = nullptr; a.bbox = nullptr; a.gcpart = nullptr; a.txy = nullptr; a.tw = nullptr;
-    a.B = P; a.NV = NV; a.C = C; a.h = h; a.w = w; a.agg = agg;
-    a.v0 = v0; a.v1 = v1; a.v2 = v2; a.nb0 = (int)cdiv(v0, 4); a.nb1 = (int)cdiv(v1, 4); a.nb2 = (int)cdiv(v2, 4);
-    a.nvox = (long long)v0 * v1 * v2;
-    const int nbricks = a.nb0 * a.nb1 * a.nb2;
-    const int nblk1 = blocks_k1(a.nvox, C);
-    const IndexedWs s = indexed_ws(NV, C, v0, v1, v2);
-    const size_t fixed = s.gc_all(P), per_cuboid = s.per_cuboid();
-    LT_REQUIRE(workspace && workspace_bytes >= fixed + per_cuboid && ((size_t)workspace % 16) == 0, LT_ERR_INVALID,
-               "%s: workspace of at least %zu bytes (the confidence partials of all %d cuboids and one cuboid's share of the rest; "
-               "lt_unproject_indexed_bwd_workspace for all cuboids at once), 16-byte aligned", who, fixed + per_cuboid, P);
-    const size_t fit = (workspace_bytes - fixed) / per_cuboid;
-    const size_t cap = P < 65535 ? (size_t)P : 65535;             // K0 and K1 take the chunk's cuboids as grid y
-    const int chunk = (int)(fit < cap ? fit : cap);
-    const int tiles = (int)(cdiv(w, G_TW) * cdiv(h, G_TH));
-    double* gcall = (double*)workspace;                           // (P, nblk1, NV, C), dense
-    for (int p0 = 0; p0 < P; p0 += chunk) {
-        const int nb = P - p0 < chunk ? P - p0 : chunk;
-        UnprojBwdIndexedArgs c = a;
-        c.B = nb; c.p0 = p0;
-        c.coords = coords + (size_t)p0 * a.nvox * 3;
-        c.gout = grad_out + (size_t)p0 * a.nvox * C;
-        c.gcpart = gcall + (size_t)p0 * nblk1 * NV * C;
-        char* wsp = (char*)workspace + fixed;
+        char* wsp = (char*)workspace + s.fixed;
         c.dxs = (float*)wsp; wsp += s.s_dx * nb;
         c.bbox = (int*)wsp; wsp += s.s_bb * nb;
+        if (indexed) {                                            // the frame side stays whole: the kernels reach it through frame_of[p0 + b]
+            c.p0 = b0;
+            c.gcpart = (double*)workspace + (size_t)b0 * s.nblk1 * NV * C;
+        } else {
+            c.feats = (const char*)d.feats + (size_t)b0 * NV * h * w * C * in_elt;
+            c.proj = d.proj + (size_t)b0 * NV * 12;
+            c.conf = d.conf ? d.conf + (size_t)b0 * NV * C : nullptr;
+            c.mask = a.mask ? a.mask + (size_t)b0 * NV : nullptr;
+            c.gfeats = grad_feats + (size_t)b0 * NV * h * w * C;
+            c.gconf = a.gconf ? a.gconf + (size_t)b0 * NV * C : nullptr;
+            c.gcpart = (double*)wsp; wsp += s.s_gc * nb;
+        }
         c.tw = (float4*)wsp; wsp += s.s_tw * nb;
         c.txy = (int*)wsp;
-        int rc = launch_taps_dx<true, true>(who, c, dtype, nbricks, nblk1, st);
+        int rc = indexed  ? launch_taps_dx<true, true>(who, c, dtype, nbricks, s.nblk1, st)
+                 : masked ? launch_taps_dx<true>(who, c, dtype, nbricks, s.nblk1, st)
+                          : launch_taps_dx<false>(who, c, dtype, nbricks, s.nblk1, st);
         if (rc != LT_OK) return rc;
-        switch (C / 4) {
-            case 1: rc = launch_gather_indexed<1>(c, tiles, st); break;
-            case 2: rc = launch_gather_indexed<2>(c, tiles, st); break;
-            case 4: rc = launch_gather_indexed<4>(c, tiles, st); break;
-            case 8: rc = launch_gather_indexed<8>(c, tiles, st); break;
-            default: rc = launch_gather_indexed<16>(c, tiles, st); break;
-        }
+        rc = indexed ? launch_gather_c<true>(c, tiles, st) : launch_gather_c<false>(c, tiles, st);
         if (rc != LT_OK) return rc;
     }
-    if (a.gconf) {
+    if (indexed && a.gconf) {
         UnprojBwdIndexedArgs c = a;
-        c.gcpart = gcall;
-        hipLaunchKernelGGL(unproj_gconf_finalize_indexed_kernel, dim3((unsigned)(F * (C / (C < UB_FIN_C ? C : UB_FIN_C)))), dim3(UB_MANYV * UB_FIN_C), 0, st, c, nblk1);
+        c.gcpart = (double*)workspace;
+        hipLaunchKernelGGL(unproj_gconf_finalize_indexed_kernel, dim3((unsigned)(d.F * (C / (C < UB_FIN_C ? C : UB_FIN_C)))), dim3(UB_MANYV * UB_FIN_C), 0, st, c, s.nblk1);
         LT_CHECK_LAUNCH(who);
     }
     return LT_OK;
 }
 
+}  // namespace
+
+extern "C" size_t lt_unproject_desc_bwd_workspace(const lt_unproject_desc* d, int32_t items) {
+    if (!d || d->view_base) return 0;
+    return bwd_ws_bytes(d->frame_of != nullptr, d->B, items, d->NV, d->C, d->v0, d->v1, d->v2);
+}
+
+extern "C" int lt_unproject_desc_bwd(const lt_unproject_desc* desc, const float* grad_out, float* grad_feats, float* grad_conf, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    LT_REQUIRE(desc, LT_ERR_INVALID, "lt_unproject_desc_bwd: null descriptor");
+    return unproject_backward("lt_unproject_desc_bwd", *desc, grad_out, grad_feats, grad_conf, workspace, workspace_bytes, stream);
+}
+
 // bytes for ALL B samples at once; lt_unproject_bwd walks the batch in chunks when it is handed less (at least one sample's worth)
 extern "C" size_t lt_unproject_bwd_workspace(int32_t B, int32_t NV, int32_t C, int32_t v0, int32_t v1, int32_t v2) {
-    if (B < 1 || NV < 1 || C < 4 || v0 < 1 || v1 < 1 || v2 < 1 || !gather_takes(C)) return 0;
-    const long long nvox = (long long)v0 * v1 * v2;
-    const long long nbricks = cdiv(v0, 4) * cdiv(v1, 4) * cdiv(v2, 4);
-    const size_t per_sample = align256((size_t)NV * nvox * C * 4) + align256((size_t)NV * nbricks * 16) + align256((size_t)blocks_k1(nvox, C) * NV * C * 8) +
-                              align256((size_t)NV * nvox * 4) + align256((size_t)NV * nvox * 16);
-    return per_sample * (size_t)B;
+    return bwd_ws_bytes(false, B, B, NV, C, v0, v1, v2);
+}
+
+extern "C" size_t lt_unproject_indexed_bwd_workspace(int32_t P, int32_t NV, int32_t C, int32_t v0, int32_t v1, int32_t v2) {
+    return bwd_ws_bytes(true, P, P, NV, C, v0, v1, v2);
 }
 
 extern "C" int lt_unproject_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const float* grad_out,
                                 float* grad_feats, float* grad_conf, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1,
                                 int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes, void* stream) {
-    return unproject_backward("lt_unproject_bwd", false, dtype, feats, proj, coords, conf, nullptr, grad_out, grad_feats, grad_conf, B, NV, C, h, w, v0, v1, v2,
-                              agg, workspace, workspace_bytes, stream);
+    return unproject_backward("lt_unproject_bwd", unproject_coord_desc(dtype, feats, proj, coords, conf, B, NV, C, h, w, v0, v1, v2, agg), grad_out, grad_feats, grad_conf,
+                              workspace, workspace_bytes, stream);
 }
 
 extern "C" int lt_unproject_masked_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
                                        const float* grad_out, float* grad_feats, float* grad_conf, int32_t B, int32_t NV, int32_t C, int32_t h, int32_t w,
                                        int32_t v0, int32_t v1, int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes, void* stream) {
-    return unproject_backward("lt_unproject_masked_bwd", true, dtype, feats, proj, coords, conf, view_mask, grad_out, grad_feats, grad_conf, B, NV, C, h, w, v0,
-                              v1, v2, agg, workspace, workspace_bytes, stream);
+    const char* who = "lt_unproject_masked_bwd";
+    LT_REQUIRE(view_mask, LT_ERR_INVALID, "%s: null view_mask", who);
+    lt_unproject_desc d = unproject_coord_desc(dtype, feats, proj, coords, conf, B, NV, C, h, w, v0, v1, v2, agg);
+    d.view_mask = view_mask;
+    return unproject_backward(who, d, grad_out, grad_feats, grad_conf, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lt_unproject_indexed_bwd(int32_t dtype, const void* feats, const float* proj, const float* coords, const float* conf, const uint8_t* view_mask,
+                                        const int32_t* frame_of, const float* grad_out, float* grad_feats, float* grad_conf, int32_t F, int32_t P, int32_t NV,
+                                        int32_t C, int32_t h, int32_t w, int32_t v0, int32_t v1, int32_t v2, int32_t agg, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+    const char* who = "lt_unproject_indexed_bwd";
+    LT_REQUIRE(frame_of, LT_ERR_INVALID, "%s: null frame_of", who);
+    lt_unproject_desc d = unproject_coord_desc(dtype, feats, proj, coords, conf, P, NV, C, h, w, v0, v1, v2, agg);
+    d.view_mask = view_mask; d.frame_of = frame_of; d.F = F;
+    return unproject_backward(who, d, grad_out, grad_feats, grad_conf, workspace, workspace_bytes, stream);
 }

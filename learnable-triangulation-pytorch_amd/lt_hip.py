@@ -115,6 +115,19 @@ class XrDesc(C.Structure):
     _fields_ = [("dtype", i32), ("C", i32), ("P", i32), ("M", C.c_int64), ("weight", vp * 2), ("scale", vp * 2), ("shift", vp * 2), ("consts", vp)]
 
 
+class UnprojectDesc(C.Structure):
+    """lt_unproject_desc: the variant of the unprojection is which pointers are set (include/lt_hip.h)."""
+    _fields_ = [("dtype", i32), ("feats", vp), ("proj", vp), ("coords", vp), ("pos", vp), ("center", vp), ("rot", vp), ("step", f32), ("cmu_transfer", i32),
+                ("coords_out", vp), ("conf", vp), ("view_mask", vp), ("frame_of", vp), ("F", i32), ("view_base", vp), ("T", i32),
+                ("B", i32), ("NV", i32), ("C", i32), ("h", i32), ("w", i32), ("v0", i32), ("v1", i32), ("v2", i32), ("agg", i32)]
+
+
+def unproject_entry(d, bwd=False):
+    """The legacy entry a descriptor stands for, e.g. "lt_unproject_grid_masked_fwd": what H.check and a plan's info["entry"] name."""
+    variant = "_ragged" if d.view_base else "_indexed" if d.frame_of else "_masked" if d.view_mask else ""
+    return "lt_unproject%s%s_%s" % ("" if bwd or d.coords else "_grid", variant, "bwd" if bwd else "fwd")
+
+
 class NamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", vp), ("ndim", i32), ("shape", C.c_int64 * 5)]
 
@@ -196,6 +209,9 @@ SIGNATURES = {
     "lt_nhwc_to_nchw_f32": (C.c_int, [i32, vp, vp, i32, i32, i32, i32, vp]),
     "lt_coord_volumes": (C.c_int, [vp, vp, vp, f32, i32, i32, i32, vp, vp]),
     "lt_rotate_points": (C.c_int, [vp, vp, vp, i64, vp]),
+    "lt_unproject_desc_fwd": (C.c_int, [C.POINTER(UnprojectDesc), vp, vp]),
+    "lt_unproject_desc_bwd_workspace": (C.c_size_t, [C.POINTER(UnprojectDesc), i32]),
+    "lt_unproject_desc_bwd": (C.c_int, [C.POINTER(UnprojectDesc), vp, vp, vp, vp, C.c_size_t, vp]),
     "lt_unproject_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_unproject_grid_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "lt_unproject_masked_fwd": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),

@@ -196,18 +196,13 @@ class _VolTrainPlan:
             conf_p = None if volc is None else volc.t.data_ptr()          # (B, NV, 32) raw confidences; 'conf_norm' is normalised inside the kernels
             mask_p = gp + 4 * G["o_mask"]          # masked plans: the step's (B, NV) mask, behind the geometry in the same block
             fof_p = gp + 4 * G.get("o_fof", 0)          # multi-cuboid plans: the step's (nc,) int32 frame indices, in the same block
-            if multi:
-                tape.do(lambda s_: H.check(lib.lt_unproject_grid_indexed_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                                             coords.data_ptr(), conf_p, mask_p if self.masked else None, fof_p, vol.t.data_ptr(),
-                                                                             B, nc, NV, 32, h, w, V, agg, s_), "lt_unproject_grid_indexed_fwd"), "unproject")
-            elif self.masked:
-                tape.do(lambda s_: H.check(lib.lt_unproject_grid_masked_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                                            coords.data_ptr(), conf_p, mask_p, vol.t.data_ptr(), B, NV, 32, h, w, V, agg, s_),
-                                           "lt_unproject_grid_masked_fwd"), "unproject")
-            else:
-                tape.do(lambda s_: H.check(lib.lt_unproject_grid_fwd(ac, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                                     coords.data_ptr(), conf_p, vol.t.data_ptr(), B, NV, 32, h, w, V, agg, s_), "lt_unproject_grid_fwd"),
-                        "unproject")
+            # one descriptor for the forward and the backward closure: the grid form (the backward reads the coords_out the forward wrote), the
+            # variant by the pointers that are set
+            desc = H.UnprojectDesc(dtype=ac, feats=feats.t.data_ptr(), proj=gp, pos=gp + 4 * o_pos, center=gp + 4 * o_cen, rot=gp + 4 * o_rot, step=step,
+                                   cmu_transfer=cmu, coords_out=coords.data_ptr(), conf=conf_p, view_mask=mask_p if self.masked else None,
+                                   frame_of=fof_p if multi else None, F=B, B=nc, NV=NV, C=32, h=h, w=w, v0=V, v1=V, v2=V, agg=agg)
+            fwd_entry, bwd_entry = H.unproject_entry(desc), H.unproject_entry(desc, bwd=True)
+            tape.do(lambda s_: H.check(lib.lt_unproject_desc_fwd(C.byref(desc), vol.t.data_ptr(), s_), fwd_entry), "unproject")
             tape._derive(vol, (feats, volc))
             need_f, need_c = tape.carries(feats), tape.carries(volc)
 
@@ -225,27 +220,13 @@ class _VolTrainPlan:
                     tape.do(lambda s_: H.check(lib.lt_convert_pad(H.LT_BF16, dvol16.data_ptr(), H.LT_F32, dvol32.data_ptr(), nvol // 32, 32, 32, s_), "lt_convert_pad"), "cast")
                 else:
                     dvol32 = dvol
-                per_sample = lib.lt_unproject_bwd_workspace(1, NV, 32, V, V, V)
                 # the gather's workspace comes out of the tape's shared main-stream scratch (it is only live during this one op; a private buffer per
                 # cached plan was up to 4 GiB each), capped like op.unproject_heatmaps' autograd path: below the whole batch's worth the
                 # entry point walks the batch in chunks (multi-cuboid: the confidence partials of all cuboids and as many cuboids' shares as fit the cap)
-                if multi:
-                    nws = int(max(16, op.indexed_bwd_workspace(nc, NV, 32, V, V, V, cap=op.UNPROJECT_BWD_WORKSPACE_CAP)))
-                else:
-                    nws = int(max(16, min(per_sample * B, max(per_sample, op.UNPROJECT_BWD_WORKSPACE_CAP))))
+                nws = int(max(16, op.unproject_bwd_workspace(desc, cap=op.UNPROJECT_BWD_WORKSPACE_CAP)))
                 tape._ws_need(nws)
-                if multi:
-                    tape.do(lambda s_: H.check(lib.lt_unproject_indexed_bwd(ac, feats.t.data_ptr(), gp, coords.data_ptr(), conf_p, mask_p if self.masked else None,
-                                                                            fof_p, dvol32.data_ptr(), gfe32.data_ptr(), H.ptr(gconf), B, nc, NV, 32, h, w, V, V, V,
-                                                                            agg, tape._ws.data_ptr(), nws, s_), "lt_unproject_indexed_bwd"), "unproject_bwd")
-                elif self.masked:
-                    tape.do(lambda s_: H.check(lib.lt_unproject_masked_bwd(ac, feats.t.data_ptr(), gp, coords.data_ptr(), conf_p, mask_p, dvol32.data_ptr(),
-                                                                           gfe32.data_ptr(), H.ptr(gconf), B, NV, 32, h, w, V, V, V, agg, tape._ws.data_ptr(), nws, s_),
-                                               "lt_unproject_masked_bwd"), "unproject_bwd")
-                else:
-                    tape.do(lambda s_: H.check(lib.lt_unproject_bwd(ac, feats.t.data_ptr(), gp, coords.data_ptr(), conf_p, dvol32.data_ptr(), gfe32.data_ptr(),
-                                                                    H.ptr(gconf), B, NV, 32, h, w, V, V, V, agg, tape._ws.data_ptr(), nws, s_), "lt_unproject_bwd"),
-                            "unproject_bwd")
+                tape.do(lambda s_: H.check(lib.lt_unproject_desc_bwd(C.byref(desc), dvol32.data_ptr(), gfe32.data_ptr(), H.ptr(gconf), tape._ws.data_ptr(), nws,
+                                                                     s_), bwd_entry), "unproject_bwd")
                 gfe = gfe32
                 if tape.act16:
                     gfe = torch.empty(feats.t.shape, dtype=torch.bfloat16, device=device)
@@ -484,25 +465,13 @@ class VolumetricTriangulationNet(_PlannedNet):
         # ONE launch: the voxel centres are computed in registers from (position, centre, rotation, step) and written to the returned
         # coordinate tensor on the way (reference :298-339 + op.py:99-166); configurations without a fused kernel run
         # lt_coord_volumes + the generic gather inside the same call
-        entry = "lt_unproject_grid_indexed_fwd" if multi else "lt_unproject_grid_masked_fwd" if masked else "lt_unproject_grid_fwd"
-        if ragged is not None:
-            entry = "lt_unproject_grid_ragged_fwd"
-            unproject = lambda st: H.check(lib.lt_unproject_grid_ragged_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                                            coords.data_ptr(), H.ptr(conf), gp + 4 * o_vb, vol.t.data_ptr(), B, nimg, NV, 32, h, w, V,
-                                                                            agg, st), entry)
-        elif multi:
-            unproject = lambda st: H.check(lib.lt_unproject_grid_indexed_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                                             coords.data_ptr(), H.ptr(conf), gp + 4 * o_mask if masked else None, gp + 4 * o_fof,
-                                                                             vol.t.data_ptr(), F, B, NV, 32, h, w, V, agg, st), entry)
-        elif masked:
-            unproject = lambda st: H.check(lib.lt_unproject_grid_masked_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                                            coords.data_ptr(), H.ptr(conf), gp + 4 * o_mask, vol.t.data_ptr(), B, NV, 32, h, w, V,
-                                                                            agg, st), "lt_unproject_grid_masked_fwd")
-        else:
-            unproject = lambda st: H.check(lib.lt_unproject_grid_fwd(b.code, feats.t.data_ptr(), gp, gp + 4 * o_pos, gp + 4 * o_cen, gp + 4 * o_rot, step, cmu,
-                                                                     coords.data_ptr(), H.ptr(conf), vol.t.data_ptr(), B, NV, 32, h, w, V, agg, st),
-                                           "lt_unproject_grid_fwd")
-        b.custom(unproject,
+        # the variant is which pointers of the descriptor are set (include/lt_hip.h); `entry` names it by its shorthand entry
+        desc = H.UnprojectDesc(dtype=b.code, feats=feats.t.data_ptr(), proj=gp, pos=gp + 4 * o_pos, center=gp + 4 * o_cen, rot=gp + 4 * o_rot, step=step,
+                               cmu_transfer=cmu, coords_out=coords.data_ptr(), conf=H.ptr(conf), view_mask=gp + 4 * o_mask if masked else None,
+                               frame_of=gp + 4 * o_fof if multi else None, F=F, view_base=gp + 4 * o_vb if ragged is not None else None, T=nimg,
+                               B=B, NV=NV, C=32, h=h, w=w, v0=V, v1=V, v2=V, agg=agg)
+        entry = H.unproject_entry(desc)
+        b.custom(lambda st: H.check(lib.lt_unproject_desc_fwd(C.byref(desc), vol.t.data_ptr(), st), entry),
                  "unproject", nbytes=(nimg * h * w * 32 + B * V ** 3 * 32) * esz + B * V ** 3 * 12,   # feats once + volume once + the returned coords
                  info={"feats": feats, "geo": geo, "coords": coords, "conf": conf, "vol": vol, "agg": self.volume_aggregation_method, "NV": NV,
                        "offs": (o_pos, o_cen, o_rot), "step": step, "cmu": cmu, "masked": masked, "entry": entry, "frames": F, "cuboids": B})

@@ -4,6 +4,8 @@
 Public tensors keep the reference's layouts (heatmaps B,NV,C,h,w; volumes B,C,V,V,V); internally the
 kernels are channels-last, so a channels-last-strided input (what our own networks produce) is consumed
 without a copy, and outputs are returned as permuted views of channels-last storage."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -101,18 +103,6 @@ def view_counts_host(view_counts, T=None, min_views=1, what="view_counts"):
     return counts, base, (4 if top <= 4 else 8 if top <= 8 else 32)
 
 
-def _unproject_ragged_launch(feats_cl, P, cv, conf, method, view_base, nvcap):
-    """feats_cl (T,h,w,C) contiguous channels-last over the views of all samples -> (B,v0,v1,v2,C) channels-last, same dtype (lt_unproject_ragged_fwd).
-    view_base: (B + 1,) int32 device tensor."""
-    T, h, w, Cc = feats_cl.shape
-    B, v0, v1, v2 = cv.shape[:4]
-    out = torch.empty(B, v0, v1, v2, Cc, dtype=feats_cl.dtype, device=feats_cl.device)
-    H.check(H.lib().lt_unproject_ragged_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), view_base.data_ptr(),
-                                            out.data_ptr(), B, T, nvcap, Cc, h, w, v0, v1, v2, H.AGG["conf"] if conf is not None else H.AGG[method],
-                                            H.cur_stream()), "lt_unproject_ragged_fwd")
-    return out
-
-
 def _view_mask_device(view_mask, B, NV, device):
     """The mask as a (B, NV) uint8 device tensor for the masked entry points (a device tensor of the right form is used as it is)."""
     if torch.is_tensor(view_mask) and view_mask.is_cuda:
@@ -126,114 +116,79 @@ def _view_mask_device(view_mask, B, NV, device):
     return torch.from_numpy(view_mask_host(view_mask, B, NV)).to(device)
 
 
-def _unproject_launch(feats_cl, P, cv, conf, method, mask=None, frame_of=None):
-    """feats_cl (B,NV,h,w,C) contiguous channels-last -> (B,v0,v1,v2,C) channels-last, same dtype.  mask: (B,NV) uint8 device tensor
-    (lt_unproject_masked_fwd) or None.  frame_of: (P,) int32 device tensor (lt_unproject_indexed_fwd: cv holds P cuboids, each over the views of its
-    frame of the B; the mask, if any, is per frame) or None."""
-    B, NV, h, w, Cc = feats_cl.shape
+def _unproject_desc(feats_cl, P, cv, conf, method, mask=None, frame_of=None, view_base=None, nvcap=None):
+    """The coordinate-form lt_unproject_desc of feats_cl (B,NV,h,w,C) contiguous channels-last over cv (B,v0,v1,v2,3); the variant is which of the rest is
+    given.  mask: (B,NV) uint8 device tensor.  frame_of: (P,) int32 device tensor -- cv holds P cuboids, each over the views of its frame of the B; the mask,
+    if any, is per frame.  view_base: (B + 1,) int32 device tensor -- feats_cl is (T,h,w,C) over the views of all samples, ``nvcap`` the most a sample has."""
+    h, w, Cc = feats_cl.shape[-3:]
     v0, v1, v2 = cv.shape[1:4]
-    out = torch.empty(cv.shape[0], v0, v1, v2, Cc, dtype=feats_cl.dtype, device=feats_cl.device)
-    if frame_of is not None:
-        H.check(H.lib().lt_unproject_indexed_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), H.ptr(mask),
-                                                 frame_of.data_ptr(), out.data_ptr(), B, cv.shape[0], NV, Cc, h, w, v0, v1, v2,
-                                                 H.AGG["conf"] if conf is not None else H.AGG[method], H.cur_stream()), "lt_unproject_indexed_fwd")
-        return out
-    if mask is not None:
-        H.check(H.lib().lt_unproject_masked_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), mask.data_ptr(),
-                                                out.data_ptr(), B, NV, Cc, h, w, v0, v1, v2, H.AGG["conf"] if conf is not None else H.AGG[method],
-                                                H.cur_stream()), "lt_unproject_masked_fwd")
-        return out
-    H.check(H.lib().lt_unproject_fwd(H.dtype_code(feats_cl.dtype), feats_cl.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), out.data_ptr(),
-                                     B, NV, Cc, h, w, v0, v1, v2, H.AGG["conf"] if conf is not None else H.AGG[method], H.cur_stream()), "lt_unproject_fwd")
+    return H.UnprojectDesc(dtype=H.dtype_code(feats_cl.dtype), feats=feats_cl.data_ptr(), proj=P.data_ptr(), coords=cv.data_ptr(), conf=H.ptr(conf),
+                           view_mask=H.ptr(mask), frame_of=H.ptr(frame_of), F=feats_cl.shape[0], view_base=H.ptr(view_base), T=feats_cl.shape[0],
+                           B=cv.shape[0], NV=feats_cl.shape[1] if view_base is None else nvcap, C=Cc, h=h, w=w, v0=v0, v1=v1, v2=v2,
+                           agg=H.AGG["conf"] if conf is not None else H.AGG[method])
+
+
+def _unproject_launch(feats_cl, P, cv, conf, method, mask=None, frame_of=None, view_base=None, nvcap=None):
+    """_unproject_desc's arguments -> (B,v0,v1,v2,C) channels-last, same dtype (lt_unproject_desc_fwd)."""
+    d = _unproject_desc(feats_cl, P, cv, conf, method, mask, frame_of, view_base, nvcap)
+    out = torch.empty(tuple(cv.shape[:4]) + (d.C,), dtype=feats_cl.dtype, device=feats_cl.device)
+    H.check(H.lib().lt_unproject_desc_fwd(ctypes.byref(d), out.data_ptr(), H.cur_stream()), H.unproject_entry(d))
     return out
 
 
+def unproject_bwd_workspace(desc, chunk=None, cap=None):
+    """Bytes of lt_unproject_desc_bwd's workspace for the desc.B samples (cuboids) walked ``chunk`` at a time (None: all at once; 1: the least the entry
+    takes), as lt_unproject_desc_bwd_workspace states them.  cap: the largest chunk whose workspace stays within ``cap`` bytes instead (at least one).
+    0 where the gather does not take C."""
+    query = lambda items: H.lib().lt_unproject_desc_bwd_workspace(ctypes.byref(desc), items)
+    n, one = desc.B, query(1)
+    if one == 0:
+        return 0
+    if cap is not None:
+        share = query(2) - one if n > 1 else one          # what every further item adds; the rest is there once
+        chunk = max(1, min(n, (cap - (one - share)) // share))
+    return query(n if chunk is None else min(n, int(chunk)))
+
+
+_ANY_FRAME = (H.i32 * 1)()          # indexed_bwd_workspace: a host-only query reads no pointer, it only asks whether frame_of is set
+
+
+def indexed_bwd_workspace(P, NV, C, v0, v1, v2, chunk=None, cap=None):
+    """Bytes of lt_unproject_indexed_bwd's workspace for P cuboids walked ``chunk`` cuboids at a time (None: all at once, lt_unproject_indexed_bwd_workspace
+    itself; 1: the least the entry takes): the fp64 confidence partials of ALL P cuboids plus ``chunk`` cuboids' shares of the rest (include/lt_hip.h).
+    cap: the largest chunk whose workspace stays within ``cap`` bytes instead (at least one cuboid).  0 where the gather does not take C."""
+    return unproject_bwd_workspace(H.UnprojectDesc(frame_of=ctypes.addressof(_ANY_FRAME), B=P, NV=NV, C=C, v0=v0, v1=v1, v2=v2), chunk, cap)
+
+
 class _UnprojectFn(torch.autograd.Function):
-    """lt_unproject_fwd / lt_unproject_bwd as one autograd node: what autograd builds in the reference from grid_sample, the
-    in-place depth mask and the view aggregation (op.py:113-162).  Gradients reach the heatmaps and (conf modes) the confidences;
-    projections and coordinates get none, exactly as in the reference (they do not require grad there).  mask: a (B,NV) uint8 device tensor makes
-    it the node over lt_unproject_masked_fwd / lt_unproject_masked_bwd (every sample over its valid views alone; masked views get zero gradients)."""
+    """lt_unproject_desc_fwd / lt_unproject_desc_bwd as one autograd node: what autograd builds in the reference from grid_sample, the in-place depth
+    mask and the view aggregation (op.py:113-162).  Gradients reach the heatmaps and (conf modes) the confidences; projections and coordinates get none,
+    exactly as in the reference (they do not require grad there).  mask: a (B,NV) uint8 device tensor makes it the node over every sample's valid views
+    alone (masked views get zero gradients).  fof: a (P,) int32 device tensor of frames makes it the node of several cuboids per frame -- what autograd
+    derives on heatmaps[fof], proj[fof], conf[fof] without the gathered copies: every frame's heatmaps and confidences get the sum of its cuboids'
+    gradients, a frame without a cuboid zeros; the mask is then (F,NV), per frame."""
 
     @staticmethod
-    def forward(ctx, heatmaps, P, cv, conf, method, mask=None):
+    def forward(ctx, heatmaps, P, cv, conf, method, mask=None, fof=None):
         feats = _as_channels_last(heatmaps, 2)
-        out = _unproject_launch(feats, P, cv, conf, method, mask)
+        out = _unproject_launch(feats, P, cv, conf, method, mask, fof)
         ctx.save_for_backward(feats, P, cv, conf if conf is not None else torch.empty(0, device=feats.device))
-        ctx.method, ctx.has_conf, ctx.mask = method, conf is not None, mask
+        ctx.method, ctx.has_conf, ctx.mask, ctx.fof = method, conf is not None, mask, fof
         return out.permute(0, 4, 1, 2, 3)
 
     @staticmethod
     def backward(ctx, grad_out):
         feats, P, cv, conf = ctx.saved_tensors
         conf = conf if ctx.has_conf else None
-        B, NV, h, w, Cc = feats.shape
         g = grad_out.permute(0, 2, 3, 4, 1).float().contiguous()               # (B, v0, v1, v2, C) channels-last fp32
-        gfeats = torch.empty(B, NV, h, w, Cc, dtype=torch.float32, device=feats.device)      # written completely by the gather
+        gfeats = torch.empty(feats.shape, dtype=torch.float32, device=feats.device)      # written completely by the gather, empty frames included
         gconf = torch.empty_like(conf) if conf is not None else None
-        v0, v1, v2 = cv.shape[1:4]
-        lib = H.lib()
-        # deterministic gather: workspace for as many samples as fit 2 GiB at a time (the entry walks the batch in chunks)
-        per_sample = lib.lt_unproject_bwd_workspace(1, NV, Cc, v0, v1, v2)
-        ws = torch.empty(max(16, min(per_sample * B, max(per_sample, UNPROJECT_BWD_WORKSPACE_CAP))), dtype=torch.uint8, device=feats.device)
-        agg = H.AGG["conf"] if conf is not None else H.AGG[ctx.method]
-        if ctx.mask is not None:
-            H.check(lib.lt_unproject_masked_bwd(H.dtype_code(feats.dtype), feats.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), ctx.mask.data_ptr(),
-                                                g.data_ptr(), gfeats.data_ptr(), H.ptr(gconf), B, NV, Cc, h, w, v0, v1, v2, agg, ws.data_ptr(), ws.numel(),
-                                                H.cur_stream()), "lt_unproject_masked_bwd")
-        else:
-            H.check(lib.lt_unproject_bwd(H.dtype_code(feats.dtype), feats.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), g.data_ptr(),
-                                         gfeats.data_ptr(), H.ptr(gconf), B, NV, Cc, h, w, v0, v1, v2, agg, ws.data_ptr(), ws.numel(), H.cur_stream()),
-                    "lt_unproject_bwd")
-        return gfeats.permute(0, 1, 4, 2, 3).to(feats.dtype), None, None, gconf, None, None
-
-
-class _UnprojectIndexedFn(torch.autograd.Function):
-    """lt_unproject_indexed_fwd / lt_unproject_indexed_bwd as one autograd node (several cuboids per frame): what autograd derives for unproject_heatmaps on
-    heatmaps[frame_index], proj[frame_index], conf[frame_index] -- every frame's heatmaps and confidences get the sum of its cuboids' gradients, a frame
-    without a cuboid zeros -- without the gathered copies.  fof: the (P,) int32 device tensor of frames; mask: a (F,NV) uint8 device tensor or None."""
-
-    @staticmethod
-    def forward(ctx, heatmaps, P, cv, conf, method, mask, fof):
-        feats = _as_channels_last(heatmaps, 2)
-        out = _unproject_launch(feats, P, cv, conf, method, mask, fof)
-        ctx.save_for_backward(feats, P, cv, conf if conf is not None else torch.empty(0, device=feats.device), fof)
-        ctx.method, ctx.has_conf, ctx.mask = method, conf is not None, mask
-        return out.permute(0, 4, 1, 2, 3)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        feats, P, cv, conf, fof = ctx.saved_tensors
-        conf = conf if ctx.has_conf else None
-        F, NV, h, w, Cc = feats.shape
-        nc = cv.shape[0]
-        g = grad_out.permute(0, 2, 3, 4, 1).float().contiguous()               # (P, v0, v1, v2, C) channels-last fp32
-        gfeats = torch.empty(F, NV, h, w, Cc, dtype=torch.float32, device=feats.device)      # written completely by the gather, empty frames included
-        gconf = torch.empty_like(conf) if conf is not None else None
-        v0, v1, v2 = cv.shape[1:4]
-        lib = H.lib()
-        # the confidence partials of all cuboids plus as many cuboids' shares as fit the cap (the entry walks the cuboids in chunks, same bits)
-        ws = torch.empty(max(16, indexed_bwd_workspace(nc, NV, Cc, v0, v1, v2, cap=UNPROJECT_BWD_WORKSPACE_CAP)), dtype=torch.uint8, device=feats.device)
-        agg = H.AGG["conf"] if conf is not None else H.AGG[ctx.method]
-        H.check(lib.lt_unproject_indexed_bwd(H.dtype_code(feats.dtype), feats.data_ptr(), P.data_ptr(), cv.data_ptr(), H.ptr(conf), H.ptr(ctx.mask), fof.data_ptr(),
-                                             g.data_ptr(), gfeats.data_ptr(), H.ptr(gconf), F, nc, NV, Cc, h, w, v0, v1, v2, agg, ws.data_ptr(), ws.numel(),
-                                             H.cur_stream()), "lt_unproject_indexed_bwd")
+        d = _unproject_desc(feats, P, cv, conf, ctx.method, ctx.mask, ctx.fof)
+        # deterministic gather: workspace for as many samples (cuboids) as fit 2 GiB at a time (the entry walks them in chunks, same bits)
+        ws = torch.empty(max(16, unproject_bwd_workspace(d, cap=UNPROJECT_BWD_WORKSPACE_CAP)), dtype=torch.uint8, device=feats.device)
+        H.check(H.lib().lt_unproject_desc_bwd(ctypes.byref(d), g.data_ptr(), gfeats.data_ptr(), H.ptr(gconf), ws.data_ptr(), ws.numel(), H.cur_stream()),
+                H.unproject_entry(d, bwd=True))
         return gfeats.permute(0, 1, 4, 2, 3).to(feats.dtype), None, None, gconf, None, None, None
-
-
-def indexed_bwd_workspace(P, NV, C, v0, v1, v2, chunk=None, cap=None):
-    """Bytes of lt_unproject_indexed_bwd's workspace for P cuboids walked ``chunk`` cuboids at a time (None: all at once, lt_unproject_indexed_bwd_workspace
-    itself; 1: the least the entry takes): the fp64 confidence partials of ALL P cuboids -- min(2048, ceil(nvox C / 1024)) NV C 8 bytes each, rounded up to
-    256 in all (include/lt_hip.h) -- plus ``chunk`` cuboids' shares of the rest.  cap: the largest chunk whose workspace stays within ``cap`` bytes
-    instead (at least one cuboid).  0 where the gather does not take C."""
-    whole = H.lib().lt_unproject_indexed_bwd_workspace(P, NV, C, v0, v1, v2)
-    if whole == 0:
-        return 0
-    nvox = v0 * v1 * v2
-    partials = (min(2048, -(-nvox * (C // 4) // 256)) * NV * C * 8 * P + 255) // 256 * 256
-    share = (whole - partials) // P
-    if cap is not None:
-        chunk = max(1, min(P, (cap - partials) // share))
-    return whole if chunk is None else partials + share * min(P, int(chunk))
 
 
 def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregation_method="sum", vol_confidences=None, view_mask=None,
@@ -287,7 +242,7 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
         cv = coord_volumes.to(heatmaps.device, torch.float32).contiguous()
         conf = vol_confidences.to(heatmaps.device, torch.float32).contiguous() if volume_aggregation_method.startswith("conf") else None
         vb = torch.from_numpy(base).to(heatmaps.device)
-        return _unproject_ragged_launch(_as_channels_last(heatmaps, 1), P, cv, conf, volume_aggregation_method, vb, nvcap).permute(0, 4, 1, 2, 3)
+        return _unproject_launch(_as_channels_last(heatmaps, 1), P, cv, conf, volume_aggregation_method, view_base=vb, nvcap=nvcap).permute(0, 4, 1, 2, 3)
     indexed_grad = frame_index is not None and torch.is_grad_enabled() and (heatmaps.requires_grad or
                                                                               (torch.is_tensor(vol_confidences) and vol_confidences.requires_grad))
     if indexed_grad and not indexed_backward:
@@ -313,7 +268,7 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
             raise ValueError("frame_index has %d entries, coord_volumes holds %d cuboids" % (fof.numel(), cv.shape[0]))
         mask = None if view_mask is None else _view_mask_device(view_mask, F, NV, heatmaps.device)
         if indexed_grad and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad)):
-            return _UnprojectIndexedFn.apply(heatmaps, P, cv, conf, volume_aggregation_method, mask, fof)
+            return _UnprojectFn.apply(heatmaps, P, cv, conf, volume_aggregation_method, mask, fof)
         return _unproject_launch(_as_channels_last(heatmaps, 2), P, cv, conf, volume_aggregation_method, mask, fof).permute(0, 4, 1, 2, 3)
     if view_mask is not None:
         needs_grad = torch.is_grad_enabled() and (heatmaps.requires_grad or (conf is not None and vol_confidences.requires_grad))
